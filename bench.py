@@ -26,7 +26,10 @@ the run.  Odd N > 1 has no collective layout: replicas.  `--parallel replicas | 
 torch.distributed.run on 127.0.0.1, the reference's launcher does the same: scripts/videocrafter/ddp_wrapper.py:9-13).
 Weights are random-init of the exact ModelScope architecture (no checkpoints offline).
 
-Prints ONE JSON line (rank 0) with the driver's fields plus
+Prints ONE JSON line (rank 0) with the driver's fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+A plain run only sets up, warms up, times the K steps and prints that line.  `--dump-outputs DIR` also writes what the last timed
+step returned (the uint8 frames, as float32) to DIR/frames.npy: same arguments, same inputs, so two builds compare output for output.
+`--full` adds the side measurements below (and, at N > 1, configs[2]'s 125-frame clip beside the frame-parallel headline):
   roofline     — dominant kernel = the MFMA implicit-GEMM family (conv3x3 / temporal conv /
                  linear): algorithmic FLOPs of its launches in one UNet step / their summed
                  durations, measured live with HIP events on the launch stream
@@ -63,6 +66,24 @@ def random_weights_(module, seed):
                 p.normal_(1.0, 0.1, generator=g)
             else:
                 p.normal_(0.0, 0.05, generator=g)
+
+
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs: an array larger than this in float32 is written as a seeded sample (values + indices <= this)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: the arrays the timed path returned in its last step, as DIR/<name>.npy in float32.  An array of more than
+    DUMP_MAX_BYTES in float32 (the 24-frame 256x256 video is 18 MiB) is written as a fixed, seeded sample of its flattened values
+    (DIR/<name>.npy) together with the flat indices of that sample (DIR/<name>_index.npy, float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)      # (sample_text2video returns numpy)
+        if a.size * 4 > DUMP_MAX_BYTES:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_BYTES // 12))
+            np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a.astype(np.float32))
 
 
 def _usable_cores():
@@ -332,6 +353,10 @@ def collective_layout_job(n: int, args, timeout_s: int):
             "--also-batched", "0", "--no-collective-job", "--also-frames", str(args.also_frames)]
     if args.frames:
         argv += ["--frames", str(args.frames)]
+    if args.full:
+        argv += ["--full"]
+    if args.dump_outputs:
+        argv += ["--dump-outputs", args.dump_outputs]      # this job computes the headline: its rank 0 writes the outputs
     err_path = os.path.join(tempfile.gettempdir(), f"t2v_bench_collective_{os.getpid()}.err")
     t0 = time.time()
     rc, out = self_launch(n, argv, timeout_s=timeout_s, capture=True, stderr_path=err_path)
@@ -421,7 +446,7 @@ def main_lvdm(args):
     for i in range(args.warmup):
         one(1 + i)
     torch.cuda.synchronize(dev)
-    cal_before = calibration_gemm(dev)
+    cal_before = calibration_gemm(dev) if args.full else None
     t0 = time.perf_counter()
     out = None
     for i in range(args.steps):
@@ -429,8 +454,24 @@ def main_lvdm(args):
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     assert out.shape == (1, frames, args.height, args.width, 3) and out.dtype.name == "uint8"
-    cal_after = calibration_gemm(dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frames": out})
     ms_per_step = elapsed / args.steps * 1e3
+    named = "BASELINE.json configs[4]" if (frames, args.height, args.width, args.ddim_steps) == (16, 256, 256, 50) else "custom geometry"
+    result = {
+        "metric": f"denoised frames/sec (UNet+VAE), VideoCrafter LVDM {frames}f@{args.width}x{args.height}",
+        "value": round(frames * args.steps / elapsed, 4), "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16",
+        "data": "synthetic",
+        "config": {"workload": f"VideoCrafter LVDM fp16 (random-init 0.96B UNetModel + VAE decoder), {frames} frames @ {args.width}x{args.height}, "
+                               f"{args.ddim_steps} lvdm DDIM steps, CFG 7.5, eta 0 ({named}); one step = one whole video through sample_text2video",
+                   "frames_per_video": frames, "videos_per_batch": 1, "layout": "single", "layout_requested": args.parallel,
+                   "parallelism": "1 GPU: cond+uncond batched as b=2", "rccl_communicators": []},
+    }
+    if not args.full:
+        emit(result)
+        return
+    cal_after = calibration_gemm(dev)
     px = (args.height // 8) * (args.width // 8) / 1024.0
     video_tflop = (2 * args.ddim_steps * LVDM_UNET_TFLOP_16F / 16 + VAE_TFLOP_PER_FRAME) * px * frames
     x = torch.randn(2, 4, frames, args.height // 8, args.width // 8, device=dev)
@@ -445,29 +486,19 @@ def main_lvdm(args):
     achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12
     step_ms_b2b = forward_ms_back_to_back(net, x, t, y, dev, context_kw=True)
     fused, plain_ms, plain_fl = fused_norm_split(prog, ms, gemm_ms, gemm_fl)
-    named = "BASELINE.json configs[4]" if (frames, args.height, args.width, args.ddim_steps) == (16, 256, 256, 50) else "custom geometry"
-    result = {
-        "metric": f"denoised frames/sec (UNet+VAE), VideoCrafter LVDM {frames}f@{args.width}x{args.height}",
-        "value": round(frames * args.steps / elapsed, 4), "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16",
-        "data": "synthetic",
-        "config": {"workload": f"VideoCrafter LVDM fp16 (random-init 0.96B UNetModel + VAE decoder), {frames} frames @ {args.width}x{args.height}, "
-                               f"{args.ddim_steps} lvdm DDIM steps, CFG 7.5, eta 0 ({named}); one step = one whole video through sample_text2video",
-                   "frames_per_video": frames, "videos_per_batch": 1, "layout": "single", "layout_requested": args.parallel,
-                   "parallelism": "1 GPU: cond+uncond batched as b=2", "rccl_communicators": []},
-        "roofline": {"bound": "mfma", "kernel": "gemm2_kernel / gemm_kernel family (conv (1,3,3) / linear)", "achieved": round(achieved, 1),
-                     "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": None,
-                     "launches_per_unet_step": n_gemm, "avg_launch_us": round(gemm_ms / n_gemm * 1e3, 2),
-                     "fused_norm_launches": len(fused),
-            "achieved_launches_without_a_fused_norm": round(plain_fl / (plain_ms * 1e-3) / 1e12, 1) if plain_ms > 0 else None,
-            "unet_step_ms_events": round(step_ms, 3),
-            "unet_step_ms": round(step_ms_b2b, 3),
-            "unet_step_frac_of_peak_back_to_back": round(prog.total_flops() / (step_ms_b2b * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                     "unet_step_frac_of_peak": round(prog.total_flops() / (step_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                     "calibration": {"gemm_8192_tflops_before": cal_before, "gemm_8192_tflops_after": cal_after, "smi_after": smi_snapshot()},
-                     "whole_video": {"tflop": round(video_tflop, 1), "tflops_per_gpu": round(video_tflop / (ms_per_step * 1e-3), 1),
-                                     "frac": round(video_tflop / (ms_per_step * 1e-3) / MFMA_PEAK_TFLOPS, 4)}},
-    }
+    result["roofline"] = {
+        "bound": "mfma", "kernel": "gemm2_kernel / gemm_kernel family (conv (1,3,3) / linear)", "achieved": round(achieved, 1),
+        "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": None,
+        "launches_per_unet_step": n_gemm, "avg_launch_us": round(gemm_ms / n_gemm * 1e3, 2),
+        "fused_norm_launches": len(fused),
+        "achieved_launches_without_a_fused_norm": round(plain_fl / (plain_ms * 1e-3) / 1e12, 1) if plain_ms > 0 else None,
+        "unet_step_ms_events": round(step_ms, 3),
+        "unet_step_ms": round(step_ms_b2b, 3),
+        "unet_step_frac_of_peak_back_to_back": round(prog.total_flops() / (step_ms_b2b * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+        "unet_step_frac_of_peak": round(prog.total_flops() / (step_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+        "calibration": {"gemm_8192_tflops_before": cal_before, "gemm_8192_tflops_after": cal_after, "smi_after": smi_snapshot()},
+        "whole_video": {"tflop": round(video_tflop, 1), "tflops_per_gpu": round(video_tflop / (ms_per_step * 1e-3), 1),
+                        "frac": round(video_tflop / (ms_per_step * 1e-3) / MFMA_PEAK_TFLOPS, 4)}}
     emit(result)
 
 
@@ -549,7 +580,7 @@ def main():
     ap.add_argument("--frames", type=int, default=0, help="frames per video; default 24 (configs[1], the clip BASELINE.json's metric names)")
     ap.add_argument("--also-frames", type=int, default=-1,
                     help="N > 1, frame-parallel layouts: also time a clip of this many frames in the same job and report it as `clip_125f` "
-                         "(default: 125 = configs[2]; with --frames: skipped; 0 = skip)")
+                         "(default: 125 = configs[2] with --full, else skipped; with --frames: skipped; 0 = skip)")
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=256)
     ap.add_argument("--ddim-steps", type=int, default=50)
@@ -572,12 +603,17 @@ def main():
     ap.add_argument("--model", default="modelscope", choices=["modelscope", "lvdm"],
                     help="modelscope (default; configs[1]-[3]) or lvdm = VideoCrafter, BASELINE.json configs[4]: 16 frames @256x256 through "
                          "sample_text2video (1 GPU; reported beside the headline, never the driver's default line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / per-kernel figures, GEMM calibration, the CPU baseline, "
+                         "the batched pass (--also-batched) and, at N > 1, the second clip (--also-frames); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the uint8 frames) to DIR/frames.npy as float32")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-check", action="store_true",
                     help="only check the launch path: ranks rendezvous over gloo, all-reduce their ranks, rank 0 prints one JSON line (no GPU)")
     args = ap.parse_args()
     if args.also_frames < 0:
-        args.also_frames = 0 if args.frames else 125
+        args.also_frames = 125 if args.full and not args.frames else 0
     if args.cpu_baseline_worker:
         cpu_baseline_worker(args.frames, args.ddim_steps)
         return
@@ -691,7 +727,7 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             el = float(tmax.item())
         assert out_ is not None and out_.dtype == torch.uint8
-        return el
+        return el, out_
 
     # ---- this job's own layout: first pass (lowering, weight packing, communicator set-up) + the frame-parallel self-check
     runner, err, self_check = None, "", None
@@ -717,13 +753,15 @@ def main():
         raise RuntimeError(f"layout {mode!r} failed on rank {rank}: {err or 'another rank failed'}")
     side_only = bool(coll is not None and coll.get("ok"))     # the headline already exists: this job's replicas pass is the side figure
     cal_before = None
-    if rank == 0 and not args.no_roofline and not side_only:
+    if rank == 0 and args.full and not args.no_roofline and not side_only:
         try:
             cal_before = calibration_gemm(dev)
         except Exception:                          # noqa: BLE001
             cal_before = None
     n_warm, n_steps = (1, min(args.steps, 2)) if side_only else (args.warmup, args.steps)
-    elapsed = timed(runner, n_warm, n_steps)
+    elapsed, out = timed(runner, n_warm, n_steps)
+    if rank == 0 and args.dump_outputs and not side_only:     # (side_only: the frame-parallel job that computed the headline wrote them)
+        dump_outputs(args.dump_outputs, {"frames": out})
 
     total_frames = runner.frames_per_video_all_ranks * n_steps
     value = total_frames / elapsed
@@ -786,7 +824,7 @@ def main():
             big(cond, uncond, 998)
             sync()
             k2 = min(args.steps, 5)                # the second clip is a side figure: at most 5 timed clips, whatever K the driver asks for
-            el = timed(big, 1, k2)
+            el, _ = timed(big, 1, k2)
             bgeom = (args.also_frames, args.height, args.width)
             result[key] = {
                 "frames_per_video": args.also_frames, "value": round(args.also_frames * k2 / el, 4), "unit": "frames/s",
@@ -802,7 +840,7 @@ def main():
             result[key] = {"frames_per_video": args.also_frames, "value": None, "note": "failed: " + (note or "on another rank")}
 
     cal0 = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # ---- live roofline of the dominant kernel (HIP events on the launch stream) -------------
         try:
             cal0 = {"gemm_8192_tflops_after": calibration_gemm(dev), "smi_after": smi_snapshot()}

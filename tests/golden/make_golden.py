@@ -1,6 +1,7 @@
 """Generate the committed golden fixtures FROM THE REAL REFERENCE (run in the build container).
 
     python tests/golden/make_golden.py            # tiny + full ModelScope config (~2 min CPU)
+    python tests/golden/make_golden.py --pins-only   # reference_pins.npz only (sub-module taps, tensor2vid, LVDM schedule)
 
 The reference (kabachuha/sd-webui-text2video @ /root/reference) ships no tests / golden
 vectors, so these fixtures are outputs of the reference's own classes
@@ -242,10 +243,72 @@ def infer_tiny():
     np.savez_compressed(os.path.join(OUT, "infer_tiny.npz"), **out)
 
 
+def tap_sample(n):
+    """Flat positions of a sub-module output that reference_pins.npz keeps: all of a small one, else a fixed strided sample of 1/20 of it
+    (at least 3072).  Stride 7919 is prime, so the positions are distinct.  tests/test_oracle_pin.py::_tap_sample is the same rule."""
+    k = n if n <= 3072 else max(3072, n // 20)
+    return (np.arange(k, dtype=np.int64) * 7919 + 13) % n
+
+
+def reference_pins():
+    """reference_pins.npz — what tests/test_oracle_pin.py compares the port and the product with, beyond the end-to-end goldens:
+    (a) the tiny UNet's output and its sub-module outputs (forward hooks on the input / output blocks and the middle block, 4-D ones
+        only; `tap_sample` of each, so that the file stays small),
+    (b) the reference's own `tensor2vid` (t2v_pipeline.py:447-460) on a seeded fp32 / fp16 video,
+    (c) the VideoCrafter DDIM schedule helpers (lvdm/models/modules/util.py:13-63): betas, and for (50 steps, eta 0) and
+        (10 steps, eta 1) the timesteps, alphas, previous alphas and sigmas, each in the dtype the helper returns,
+    (d) the state-dict keys and shapes of the VideoCrafter UNetModel (openaimodel3d.py) for the tiny and a one-block full-width config."""
+    import importlib
+    out = {}
+    cfg = configs.TINY_UNET
+    unet, _ = rb.build_reference_unet(cfg)
+    synth.load_synth(unet, seed=0)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(2, 4, 3, 16, 16, generator=g)
+    y = torch.randn(2, 7, cfg["context_dim"], generator=g)
+    t = torch.tensor([801, 401])
+    got, hooks = {}, []
+    for name, mod in unet.named_modules():
+        if name.count(".") == 2 and name.split(".")[0] in ("input_blocks", "output_blocks") or \
+                (name.startswith("middle_block.") and name.count(".") == 1):
+            hooks.append(mod.register_forward_hook(lambda m, i, o, n=name: got.__setitem__(n, o)))
+    with torch.no_grad():
+        out["blocks_out"] = unet(x, t, y).numpy()
+    for h in hooks:
+        h.remove()
+    for name, r in got.items():
+        if isinstance(r, torch.Tensor) and r.ndim == 4:
+            out["tap:" + name] = r.reshape(-1).numpy()[tap_sample(r.numel())]
+    pl = rb.bootstrap_pipeline()
+    vid = torch.randn(2, 3, 3, 16, 24, generator=torch.Generator().manual_seed(23)) * 0.8
+    out["t2v_u8_f32"] = np.stack(pl.tensor2vid(vid.clone()))
+    out["t2v_u8_f16"] = np.stack(pl.tensor2vid(vid.clone().half()))
+    vu = importlib.import_module("videocrafter.lvdm.models.modules.util")
+    betas = vu.make_beta_schedule("linear", 1000, linear_start=configs.LVDM_SCHEDULE["linear_start"],
+                                  linear_end=configs.LVDM_SCHEDULE["linear_end"])
+    out["lvdm_betas"] = np.asarray(betas)
+    ac = torch.tensor(np.cumprod(1.0 - betas, axis=0), dtype=torch.float32)          # ddpm3d.py:141-150 (to_torch = float32)
+    for steps, eta in ((50, 0.0), (10, 1.0)):
+        ts = vu.make_ddim_timesteps("uniform", steps, 1000, verbose=False)
+        sig, a, a_prev = vu.make_ddim_sampling_parameters(ac.cpu(), ts, eta, verbose=False)
+        for k, v in (("ts", ts), ("sigmas", sig), ("alphas", a), ("alphas_prev", a_prev)):
+            out[f"lvdm_{k}_{steps}_{eta}"] = v.numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    om = importlib.import_module("videocrafter.lvdm.models.modules.openaimodel3d")
+    for i, cfg in enumerate((configs.TINY_LVDM_UNET, dict(configs.LVDM_UNET, model_channels=320, num_res_blocks=1))):
+        with torch.device("meta"):          # keys and shapes only: skips the reference's (slow) default initialisation
+            sd = om.UNetModel(**cfg).state_dict()
+        out[f"lvdm_keys_{i}"] = np.array(list(sd.keys()))
+        out[f"lvdm_shapes_{i}"] = np.array([",".join(str(d) for d in v.shape) for v in sd.values()])
+    np.savez_compressed(os.path.join(OUT, "reference_pins.npz"), **out)
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     if "--infer-only" in sys.argv:
         infer_tiny()
+        sys.exit(0)
+    if "--pins-only" in sys.argv:
+        reference_pins()
         sys.exit(0)
     if "--lvdm-only" not in sys.argv:
         tiny()

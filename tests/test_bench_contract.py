@@ -47,7 +47,7 @@ def test_committed_bench_line_has_the_contract_fields():
 def test_bench_cli_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--parallel", "--videos"):
+    for flag in ("--gpus", "--steps", "--warmup", "--parallel", "--videos", "--full", "--dump-outputs"):
         assert flag in out.stdout
 
 
@@ -86,7 +86,8 @@ def test_layout_choice_is_comparable_across_n():
 
 def _args(**kw):
     import argparse
-    base = dict(steps=3, warmup=1, ddim_steps=50, height=256, width=256, frames=0, also_frames=125, collective_timeout=5)
+    base = dict(steps=3, warmup=1, ddim_steps=50, height=256, width=256, frames=0, also_frames=125, collective_timeout=5, full=False,
+                dump_outputs=None)
     base.update(kw)
     return argparse.Namespace(**base)
 
@@ -108,6 +109,10 @@ def test_frame_parallel_job_result_and_fallback_reason(monkeypatch, tmp_path):
     a = seen["argv"]
     assert a[a.index("--parallel") + 1] == "tshard" and a[a.index("--steps") + 1] == "3" and a[a.index("--warmup") + 1] == "1"
     assert a[a.index("--also-frames") + 1] == "125" and "--no-collective-job" in a and "--frames" not in a and seen["timeout"] == 77
+    assert "--full" not in a and "--dump-outputs" not in a
+    bench.collective_layout_job(8, _args(full=True, dump_outputs="outdir"), 77)      # the job that computes the headline gets both
+    a = seen["argv"]
+    assert "--full" in a and a[a.index("--dump-outputs") + 1] == "outdir"
     assert bench.collective_layout_job(2, _args(warmup=0), 5)["layout"] == "pairs"
     assert seen["argv"][seen["argv"].index("--warmup") + 1] == "1"          # the bounded job always warms up at least once
 
