@@ -26,7 +26,9 @@
 extern "C" {
 #endif
 
-#define T2V_ABI_VERSION 8   /* 8 (round 6): peer windows (t2v_comm_window_create / _open / t2v_comm_counters): exchanges as device-initiated stores into IPC-mapped mailboxes;
+#define T2V_ABI_VERSION 9   /* 9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
+                               for it in p[6] / p[7], layout below);
+                               8 (round 6): peer windows (t2v_comm_window_create / _open / t2v_comm_counters): exchanges as device-initiated stores into IPC-mapped mailboxes;
                                7 (round 6): ATTENTION p[6] / i[17] / i[18] (V^T scratch: spatial self-attention with LDS-DMA tiles); T2V_ERR_RESIDENCY — a launch that needs its whole grid co-resident was refused by the occupancy check (the caller
                                lowers again without norms fused into GEMM epilogues); a launch refused because a fault was raised mid-run reports T2V_ERR_ASYNC;
                                6 (round 5, second half): T2V_OP_STATS_HALO — the statistics parts of a T-sharded cross-frame GroupNorm and the RAW boundary
@@ -46,6 +48,11 @@ extern "C" {
 #define T2V_ERR_ASYNC (-6)     /* a kernel of an EARLIER run raised a fault (bounded grid barrier timed out): that run's results are invalid */
 #define T2V_ERR_RESIDENCY (-7) /* a fused-norm launch (T2V_EPI_GN, cross-tile LayerNorm, cooperative GroupNorm) does not fit co-resident on this device */
 
+/* RELPOS_ATTN i[17] = 3: longest clip, and the Ev^T table layout it reads (see RELPOS_ATTN below) */
+#define T2V_RELPOS_MAX_FRAMES 1024
+#define T2V_RELPOS_LONG_PADL 72
+#define T2V_RELPOS_LONG_COLS(R) ((2 * (R) + 158) / 8 * 8)
+
 /* ---- op kinds ------------------------------------------------------------------------- */
 enum t2v_op_kind {
   T2V_OP_GEMM = 1,        /* implicit-GEMM conv / linear on MFMA, fused epilogue            */
@@ -60,7 +67,7 @@ enum t2v_op_kind {
   T2V_OP_DDIM_STEP = 10,  /* DDIM_Gaussian update with half-channel CFG                     */
   T2V_OP_MEMSET = 11,     /* zero a byte range                                              */
   T2V_OP_LINCOMB = 12,    /* out = sum_i c_i * T_i (<= 6 latent-sized tensors): UniPC / DDIM updates */
-  T2V_OP_RELPOS_ATTN = 13, /* LVDM temporal attention with relative-position K / V terms (frames <= 32) */
+  T2V_OP_RELPOS_ATTN = 13, /* LVDM temporal attention with relative-position K / V terms (frames <= 32; <= T2V_RELPOS_MAX_FRAMES with i[17] = 3) */
   T2V_OP_EMBED_ROWS = 14,  /* token + positional embedding lookup (CLIP text towers) */
   T2V_OP_TO_UINT8 = 15,    /* tensor2vid: float video -> uint8 frames [F,H,(i W),3], truncating (t2v_pipeline.py:447-460) */
   T2V_OP_ALLGATHER = 16,   /* in-place all-gather of equal byte parts over the plan's communicator (RCCL, launch stream) */
@@ -200,7 +207,8 @@ enum t2v_gather {
  *      ABI 7, optional: p 6 = scratch fp16 [batch_outer * batch_inner * heads * 64, i[17]] with i[17] = nk rounded up to a multiple of 64
  *      (head_dim 64, not causal): V is transposed into it once per launch and the K / V^T tiles are staged by LDS-DMA (same bits as without
  *      the scratch; pays from ~512 keys); i[18] = waves per 64-key tile (0 = 8 | 4 | 8)
- * RELPOS_ATTN: i: as ATTENTION with nk == frames of the clip (<= 32), 14 head_dim (multiple of 8, <= 160),
+ * RELPOS_ATTN: i: as ATTENTION with nk == frames of the clip (<= 32 for i[17] = 0 | 1 | 2; <= T2V_RELPOS_MAX_FRAMES for i[17] = 3),
+ *      14 head_dim (multiple of 8, <= 160; 40 | 64 | 80 | 160 for i[17] = 3),
  *      15 max relative position R, 16 q_off: the nq queries are frames [q_off, q_off + nq) of the clip (nq == nk, q_off == 0
  *      unless the clip is T-sharded: then s - t below is s - (t + q_off)); 17 = 1: use the MFMA kernel where it applies (nq == nk,
  *      q_off == 0, nk - 1 <= R <= 31, head_dim 40 | 64 | 80 | 160; the relative tables are staged as fp16) — else the VALU kernel;
@@ -208,6 +216,10 @@ enum t2v_gather {
  *      dims), with the tables ALSO given packed for it: p[6] = fp16 [32][DK] rows jl = Ek[jl + R - (nk-1)] (DK = head_dim rounded up
  *      to 16; zero beyond the table / head_dim), p[7] = fp16 [DV][32] = Ev transposed, column jl = Ev[jl + R - (nk-1)] (DV = head_dim
  *      rounded up to 32) — where it does not apply the VALU kernel runs on p[4], p[5];
+ *      17 = 3 (ABI 9): the MFMA kernel for clips of ANY length 1 <= nk <= T2V_RELPOS_MAX_FRAMES, any R >= 0, T-sharded queries (any
+ *      nq <= nk, q_off), head_dim 40 | 64 | 80 | 160 — the only kernel for nk > 32; no fall-back: its tables are REQUIRED packed for it:
+ *      p[6] = fp16 [2R+1][DK] = Ek (zero columns beyond head_dim), p[7] = fp16 [DV][T2V_RELPOS_LONG_COLS(R)] = Ev transposed with
+ *      replicated edges: column c = Ev[clamp(c - T2V_RELPOS_LONG_PADL, 0, 2R)] (zero rows beyond head_dim);
  *      18 low-order output offset (as ATTENTION i[16]);  f: 0 scale;  p: 0 q, 1 k, 2 v, 3 out (fp16), 4 Ek fp32 [2R+1, head_dim],
  *      5 Ev fp32 [2R+1, head_dim]:  sim[t,s] = scale * q[t].(k[s] + Ek[clip(s-t)]),
  *      out[t] = sum_s softmax_s(sim)[t,s] * (v[s] + Ev[clip(s-t)])   (attention_temporal.py:107-144)

@@ -30,7 +30,9 @@ def knob(name: str, default):
 
 
 # ---- mirrors of include/t2v_hip.h (checked against the header by tests/test_abi.py) -------
-ABI_VERSION = 8
+ABI_VERSION = 9
+RELPOS_MAX_FRAMES = 1024            # T2V_RELPOS_MAX_FRAMES: longest clip of RELPOS_ATTN i[17] = 3
+RELPOS_LONG_PADL = 72               # T2V_RELPOS_LONG_PADL: replicated left-edge columns of its packed Ev^T table
 OP_GEMM, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_SOFTMAX = 1, 2, 3, 4, 5
 OP_NCTHW_TO_CL, OP_CL_TO_NCTHW, OP_TIME_EMBED, OP_COPY2D, OP_DDIM_STEP, OP_MEMSET = 6, 7, 8, 9, 10, 11
 OP_LINCOMB = 12

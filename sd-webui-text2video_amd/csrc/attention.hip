@@ -1252,6 +1252,278 @@ hipError_t launch_relpos16(const SeqAttnParams& p, const f16* ek16, const f16* e
   return hipGetLastError();
 }
 
+// ---- relative-position temporal attention on MFMA for clips of any length (i[17] = 3) --------------------------------------------
+// One wave per (pixel, head, 32-query block); it streams the clip in 32-key tiles with an online softmax.  Per tile, with t' = t + q_off
+// and the table row of (t, s) j = clamp(s - t', -R, R) + R:
+//  * S^T = K Q^T on MFMA (K fragments straight from global, Q fragments held for the whole block);
+//  * the tile's s - t' span 63 values, so its relative terms need a WINDOW of 63 table rows: slot w = (s - s0) - (t - t0) + 31 <-> row
+//    clamp(jb + w) with jb = s0 - t0' - 31 + R.  QE^T = Ek_win Q^T (two 32-row MFMA blocks, the row index clamped per lane, so the
+//    clipping is in the operand) goes to LDS as [slot][t] and is read back at the lane's own (t, s);
+//  * O^T += V^T P^T (V^T through LDS, P from the score registers) and O^T += Ev_win^T Pskew^T: the probabilities go to LDS as [t][key]
+//    and the B operand reads them skewed, zero outside the tile.  Ev^T comes from the host packed with T2V_RELPOS_LONG_PADL replicated edge
+//    columns on the left and enough on the right (packing.relpos_tables_long), so the window is a plain column range; its base is
+//    aligned down to 8 columns (8-byte fragment reads) and the shift dl absorbed by the skew: 4 or 5 K-steps of 16 slots;
+//  * a tile whose pairs all clip to ONE table row (|s - t'| >= R across the whole tile: most tiles of a long clip at R = 16) skips both
+//    window products: its scores add q_t . Ek[0] or q_t . Ek[2R] (one MFMA per block), and its probability mass goes to W[t, 0] /
+//    W[t, 2R], rescaled with O and added as W Ev at the end — the relative terms cost O(T (2R + 1) D), not O(T^2 D).
+// The tables are read from global memory (L2 / L1: 2R + 1 rows, shared by every wave), so the LDS holds only per-wave buffers and no
+// workgroup barrier exists: 13.3 / 13.3 / 15.5 / 20 KB per wave at head_dim 40 / 64 / 80 / 160.
+struct RelLongParams {
+  SeqAttnParams a;
+  const f16* ek16;            // [2R+1][DK]
+  const f16* evt16;           // [DV][nc]: column c = Ev[clamp(c - T2V_RELPOS_LONG_PADL, 0, 2R)]
+  int nc;                     // T2V_RELPOS_LONG_COLS(R)
+  int nqb;                    // 32-query blocks per (pixel, head)
+  long n_units;               // n_items * nqb
+};
+
+template <int D>
+__global__ __launch_bounds__(256) void relpos_long_kernel(const RelLongParams pp) {
+  const SeqAttnParams& p = pp.a;
+  constexpr int DK = (D + 15) / 16 * 16, NKK = DK / 16;
+  constexpr int DV = (D + 31) / 32 * 32, NDT = DV / 32;
+  constexpr int VT_PITCH = 32 * 2 + 8;           // bytes per V^T row: 32 keys
+  constexpr int QE_PITCH = 35;                   // floats per QE slot row (32 queries + 3: the skewed reads spread over the banks)
+  constexpr int P_PITCH = 40;                    // halves per probability row (the P rows overlay the QE rows, read before)
+  constexpr int WAVE_BYTES = DV * VT_PITCH + 64 * QE_PITCH * 4;
+  static_assert(WAVE_BYTES % 16 == 0 && (DV * VT_PITCH) % 16 == 0 && 32 * P_PITCH * 2 <= 64 * QE_PITCH * 4, "LDS carve-up");
+  extern __shared__ __attribute__((aligned(16))) unsigned char ssm[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long unit = (long)blockIdx.x * 4 + wave;
+  if (unit >= pp.n_units) return;                                // wave-uniform; no workgroup barrier in this kernel
+  unsigned char* vt = ssm + wave * WAVE_BYTES;                   // [DV][VT_PITCH]
+  float* qeb = reinterpret_cast<float*>(vt + DV * VT_PITCH);     // [64 slots][QE_PITCH]
+  f16* pb = reinterpret_cast<f16*>(qeb);                         // [32 queries][P_PITCH]
+  const long item = unit / pp.nqb;
+  const int t0 = (int)(unit - item * pp.nqb) * 32;
+  const int head = (int)(item % p.heads);
+  const long pos = item / p.heads;
+  const long bo = pos / p.b_inner, bi = pos % p.b_inner;
+  const f16* qb = p.q + bo * p.sq_out + bi * p.sq_in + head * D;
+  const f16* kb = p.k + bo * p.sk_out + bi * p.sk_in + head * D;
+  const f16* vb = p.v + bo * p.sk_out + bi * p.sk_in + head * D;
+  f16* ob = p.o + bo * p.so_out + bi * p.so_in + head * D;
+  const int T = p.T, R = p.R, Tq = p.Tq, nc = pp.nc;
+  const int t0a = t0 + p.q_off;                                  // absolute frame of the block's first query
+  const int frow = lane & 31, fhalf = lane >> 5;
+  const int tq = t0 + frow;                                      // this lane's query (local)
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f16x8 qf[NKK];
+#pragma unroll
+  for (int kk = 0; kk < NKK; ++kk) {
+    const int d0 = kk * 16 + fhalf * 8;
+    if (tq < Tq && d0 < D) qf[kk] = *reinterpret_cast<const f16x8*>(qb + (long)tq * p.sq_seq + d0);
+    else for (int e = 0; e < 8; ++e) qf[kk][e] = (f16)0.f;
+  }
+  // q_t . Ek[0] and q_t . Ek[2R]: A rows 0..15 = table row 0, rows 16..31 = table row 2R; accumulator r = 0 / 8 is row 4 fhalf / 16 + 4 fhalf
+  float qe_lo, qe_hi;
+  {
+    const f16* erow = pp.ek16 + (long)(frow < 16 ? 0 : 2 * R) * DK;
+    f32x16 qe = zero16;
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk)
+      qe = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(erow + kk * 16 + fhalf * 8), qf[kk], qe, 0, 0, 0);
+    qe_lo = qe[0];
+    qe_hi = qe[8];
+  }
+  f32x16 oacc[NDT];
+#pragma unroll
+  for (int d = 0; d < NDT; ++d) oacc[d] = zero16;
+  float m_run = -INFINITY, l_run = 0.f, w_lo = 0.f, w_hi = 0.f;
+  bool any_edge = false;
+  const float sl2 = p.scale * 1.44269504088896340736f;
+  for (int s0 = 0; s0 < T; s0 += 32) {
+    const int dmin = s0 - (t0a + 31), dmax = s0 + 31 - t0a;     // range of s - t' over the tile
+    const int edge = dmin >= R ? 1 : (dmax <= -R ? -1 : 0);      // wave-uniform: +-1 = every pair clips to row 2R / row 0
+    any_edge |= edge != 0;
+    // ---- V^T tile into LDS: unit = (key pair, 4 d)
+    for (int u = lane; u < 16 * (DV / 4); u += 64) {
+      const int kp = u / (DV / 4), dq = u - kp * (DV / 4);
+      const int key = s0 + 2 * kp;
+      const bool dok = dq * 4 < D;
+      f16x4 a, b;
+      if (dok && key < T) a = *reinterpret_cast<const f16x4*>(vb + (long)key * p.sk_seq + dq * 4);
+      else for (int e = 0; e < 4; ++e) a[e] = (f16)0.f;
+      if (dok && key + 1 < T) b = *reinterpret_cast<const f16x4*>(vb + (long)(key + 1) * p.sk_seq + dq * 4);
+      else for (int e = 0; e < 4; ++e) b[e] = (f16)0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        typedef f16 f16x2 __attribute__((ext_vector_type(2)));
+        f16x2 w = {a[e], b[e]};
+        *reinterpret_cast<f16x2*>(vt + (dq * 4 + e) * VT_PITCH + kp * 4) = w;
+      }
+    }
+    // ---- S^T = K Q^T
+    f32x16 sc = zero16;
+    {
+      const int key = s0 + frow;
+#pragma unroll
+      for (int kk = 0; kk < NKK; ++kk) {
+        const int d0 = kk * 16 + fhalf * 8;
+        f16x8 kf;
+        if (key < T && d0 < D) kf = *reinterpret_cast<const f16x8*>(kb + (long)key * p.sk_seq + d0);
+        else for (int e = 0; e < 8; ++e) kf[e] = (f16)0.f;
+        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], sc, 0, 0, 0);
+      }
+    }
+    const int jb = s0 - t0a - 31 + R;                            // table row of window slot 0
+    if (edge == 0) {
+      // ---- QE^T = Ek_win Q^T, slots 0..63 (62 used), written as [slot][t]
+#pragma unroll
+      for (int blk = 0; blk < 2; ++blk) {
+        int row = jb + blk * 32 + frow;
+        row = row < 0 ? 0 : (row > 2 * R ? 2 * R : row);
+        const f16* erow = pp.ek16 + (long)row * DK;
+        f32x16 qe = zero16;
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk)
+          qe = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(erow + kk * 16 + fhalf * 8), qf[kk], qe, 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) qeb[(blk * 32 + 8 * g + 4 * fhalf + e) * QE_PITCH + frow] = qe[4 * g + e];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // V^T / QE written by this wave, read back below by other lanes
+    // ---- scores of this lane's query t = frow: keys s0 + (r & 3) + 8 (r >> 2) + 4 fhalf
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kl = (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+      const float rel = edge > 0 ? qe_hi : (edge < 0 ? qe_lo : qeb[(kl - frow + 31) * QE_PITCH + frow]);
+      const float v = (s0 + kl < T) ? sc[r] + rel : -INFINITY;
+      sc[r] = v;
+      mx = fmaxf(mx, v);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));                          // finite: key s0 < T exists
+    // online softmax as attn_kernel: the running maximum only advances by more than 2^8; O, l and W carry the same stale factor
+    const float m_tile = mx * sl2;                               // scale > 0 (checked at launch)
+    const bool grow = m_tile - m_run > 8.0f;
+    if (__builtin_amdgcn_ballot_w64(grow) != 0) {
+      const float alpha = grow ? __builtin_amdgcn_exp2f(m_run - m_tile) : 1.0f;
+      l_run *= alpha;
+      w_lo *= alpha;
+      w_hi *= alpha;
+#pragma unroll
+      for (int d = 0; d < NDT; ++d)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
+      m_run = grow ? m_tile : m_run;
+    }
+    const float neg_m = -m_run;
+    float psum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], sl2, neg_m));
+      sc[r] = pv;
+      psum += pv;
+    }
+    psum += __shfl_xor(psum, 32);
+    l_run += psum;
+    if (edge > 0) w_hi += psum;
+    if (edge < 0) w_lo += psum;
+    // ---- O^T += V^T P^T
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2) {
+      f16x8 pf;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) pf[e] = (f16)sc[8 * t2 + e];
+      const int kofs = (t2 * 16 + 4 * fhalf) * 2;
+#pragma unroll
+      for (int d = 0; d < NDT; ++d) {
+        const unsigned char* vrow = vt + (d * 32 + frow) * VT_PITCH + kofs;
+        const f16x4 lo = *reinterpret_cast<const f16x4*>(vrow);
+        const f16x4 hi = *reinterpret_cast<const f16x4*>(vrow + 16);
+        const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[d], 0, 0, 0);
+      }
+    }
+    if (edge == 0) {
+      // ---- O^T += Ev_win^T Pskew^T: probabilities of query t at [t][key - s0] (over the QE rows, all read above)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f16x4 pw = {(f16)sc[4 * g], (f16)sc[4 * g + 1], (f16)sc[4 * g + 2], (f16)sc[4 * g + 3]};
+        *reinterpret_cast<f16x4*>(pb + frow * P_PITCH + 8 * g + 4 * fhalf) = pw;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      const int cb = jb + T2V_RELPOS_LONG_PADL;                       // Ev^T column of slot 0: >= 4 for a tile that is not clipped whole
+      const int dl = cb & 7, c0 = cb - dl;                       // aligned window base; slot w sits at aligned slot w + dl
+      const int nst = (dl + 62) / 16 + 1;                        // 4 or 5 steps of 16 aligned slots
+      for (int u = 0; u < nst; ++u) {
+        f16x8 pf;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int kl = 16 * u + 4 * fhalf + (e & 3) + 8 * (e >> 2) - dl + frow - 31;     // key - s0 of (t, aligned slot)
+          pf[e] = (kl >= 0 && kl < 32) ? pb[frow * P_PITCH + kl] : (f16)0.f;
+        }
+        const int cofs = c0 + 16 * u + 4 * fhalf;
+#pragma unroll
+        for (int d = 0; d < NDT; ++d) {
+          const f16* erow = pp.evt16 + (long)(d * 32 + frow) * nc + cofs;
+          const f16x4 lo = *reinterpret_cast<const f16x4*>(erow);
+          const f16x4 hi = *reinterpret_cast<const f16x4*>(erow + 8);
+          const f16x8 ef = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ef, pf, oacc[d], 0, 0, 0);
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // this tile's LDS reads before the next tile's writes
+  }
+  if (any_edge) {                                                // W[t, 0] Ev[0] + W[t, 2R] Ev[2R] of the tiles clipped whole
+#pragma unroll
+    for (int d = 0; d < NDT; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const f16* ecol = pp.evt16 + (long)(d * 32 + (r & 3) + 8 * (r >> 2) + 4 * fhalf) * nc + T2V_RELPOS_LONG_PADL;
+        oacc[d][r] += w_lo * (float)ecol[0] + w_hi * (float)ecol[2 * R];
+      }
+  }
+  if (tq < Tq) {
+    const float inv = 1.0f / l_run;
+    f16* orow = ob + (long)tq * p.so_seq;
+#pragma unroll
+    for (int d = 0; d < NDT; ++d)
+#pragma unroll
+      for (int qd = 0; qd < 4; ++qd) {
+        const int col = d * 32 + 8 * qd + 4 * fhalf;
+        if (col < D) {
+          f16x4 o, lo;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float val = oacc[d][4 * qd + r] * inv;
+            o[r] = (f16)val;
+            lo[r] = (f16)(val - (float)o[r]);
+          }
+          *reinterpret_cast<f16x4*>(orow + col) = o;
+          if (p.lo_off) *reinterpret_cast<f16x4*>(orow + p.lo_off + col) = lo;
+        }
+      }
+  }
+}
+
+template <int D>
+hipError_t launch_relpos_long(const SeqAttnParams& p, const f16* ek16, const f16* evt16, hipStream_t s) {
+  constexpr int DV = (D + 31) / 32 * 32;
+  constexpr int lds = 4 * (DV * (32 * 2 + 8) + 64 * 35 * 4);
+  static_assert(lds <= 160 * 1024, "LDS budget");
+  RelLongParams pp;
+  pp.a = p;
+  pp.ek16 = ek16;
+  pp.evt16 = evt16;
+  pp.nc = T2V_RELPOS_LONG_COLS(p.R);
+  pp.nqb = (p.Tq + 31) / 32;
+  pp.n_units = p.n_items * pp.nqb;
+  auto kern = relpos_long_kernel<D>;
+  static t2v_device_flags attr_set;       // per (instantiation, device)
+  {
+    const hipError_t e = t2v_set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, attr_set, s);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)((pp.n_units + 3) / 4)), dim3(256), lds, s, pp);
+  return hipGetLastError();
+}
+
 template <bool REL>
 hipError_t launch_seqattn(const t2v_op& op, hipStream_t s) {
   SeqAttnParams p;
@@ -1269,6 +1541,21 @@ hipError_t launch_seqattn(const t2v_op& op, hipStream_t s) {
   p.so_seq = op.i[11]; p.so_out = op.i[12]; p.so_in = op.i[13];
   p.scale = op.f[0];
   p.lo_off = REL ? op.i[18] : 0;
+  if (REL && op.i[17] == 3) {
+    // i[17] = 3: the MFMA kernel for clips of any length up to T2V_RELPOS_MAX_FRAMES, on the tables packed for it (p[6], p[7]); no fall-back
+    if (p.T <= 0 || p.T > T2V_RELPOS_MAX_FRAMES || p.Tq <= 0 || p.q_off < 0 || p.q_off + p.Tq > p.T || p.R < 0 || p.n_items <= 0 ||
+        !(p.scale > 0.f) || op.p[6] == 0 || op.p[7] == 0)
+      return hipErrorInvalidValue;
+    const f16* ek16 = reinterpret_cast<const f16*>(op.p[6]);
+    const f16* evt16 = reinterpret_cast<const f16*>(op.p[7]);
+    switch (p.D) {
+      case 40: return launch_relpos_long<40>(p, ek16, evt16, s);
+      case 64: return launch_relpos_long<64>(p, ek16, evt16, s);
+      case 80: return launch_relpos_long<80>(p, ek16, evt16, s);
+      case 160: return launch_relpos_long<160>(p, ek16, evt16, s);
+      default: return hipErrorInvalidValue;
+    }
+  }
   if (p.T <= 0 || p.T > 32 || p.Tq <= 0 || p.q_off < 0 || p.q_off + p.Tq > p.T || p.D <= 0 || p.D % 8 != 0 || p.D > 160 || p.n_items <= 0)
     return hipErrorInvalidValue;
   if (REL && (p.R < 0 || p.ek == nullptr || p.ev == nullptr)) return hipErrorInvalidValue;

@@ -179,16 +179,22 @@ int validate_op(const t2v_op& op, int idx) {
       return 0;
     }
     case T2V_OP_RELPOS_ATTN:
-      if (op.i[1] <= 0 || op.i[1] > 32 || op.i[0] <= 0 || op.i[16] < 0 || op.i[16] + op.i[0] > op.i[1])
-        return bad("relative-position attention needs nk <= 32 and queries [q_off, q_off + nq) inside the keys");
+      if (op.i[17] == 3) {
+        if (op.i[1] <= 0 || op.i[1] > T2V_RELPOS_MAX_FRAMES || op.i[0] <= 0 || op.i[16] < 0 || op.i[16] + op.i[0] > op.i[1])
+          return bad("relative-position attention i[17] = 3 needs nk <= T2V_RELPOS_MAX_FRAMES (1024) and queries [q_off, q_off + nq) inside the keys");
+        if (op.i[14] != 40 && op.i[14] != 64 && op.i[14] != 80 && op.i[14] != 160) return bad("relative-position attention i[17] = 3: head_dim 40, 64, 80 or 160");
+        if (!(op.f[0] > 0.f)) return bad("relative-position attention i[17] = 3: scale must be > 0");
+      } else if (op.i[1] <= 0 || op.i[1] > 32 || op.i[0] <= 0 || op.i[16] < 0 || op.i[16] + op.i[0] > op.i[1])
+        return bad("relative-position attention needs nk <= 32 (longer clips: i[17] = 3) and queries [q_off, q_off + nq) inside the keys");
       if (op.i[14] <= 0 || op.i[14] % 8 != 0 || op.i[14] > 160) return bad("relative-position attention head_dim: multiple of 8, <= 160");
       if (op.i[2] <= 0 || op.i[3] <= 0 || op.i[4] <= 0 || op.i[15] < 0 || op.i[18] < 0) return bad("empty relative-position attention");
       for (int k = 5; k <= 13; ++k)
         if (op.i[k] < 0) return bad("negative attention stride");
       for (int k = 0; k < 6; ++k)
         if (op.p[k] == 0) return bad("null relative-position attention pointer");
-      if (op.i[17] < 0 || op.i[17] > 2) return bad("relative-position attention kernel selector i[17]: 0 | 1 | 2");
+      if (op.i[17] < 0 || op.i[17] > 3) return bad("relative-position attention kernel selector i[17]: 0 | 1 | 2 | 3");
       if (op.i[17] == 2 && (op.p[6] == 0 || op.p[7] == 0)) return bad("relative-position attention i[17] = 2 needs the packed fp16 tables p[6], p[7]");
+      if (op.i[17] == 3 && (op.p[6] == 0 || op.p[7] == 0)) return bad("relative-position attention i[17] = 3 needs the packed fp16 tables p[6], p[7]");
       return 0;
     case T2V_OP_SOFTMAX:
       if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[2] < op.i[1] || op.i[3] < op.i[1] || op.p[0] == 0 || op.p[1] == 0) return bad("bad softmax shape / pointer");

@@ -12,6 +12,8 @@ import torch
 
 Recipe = Callable[[Dict[str, torch.Tensor]], torch.Tensor]
 
+RELPOS_LONG_PADL = 72          # T2V_RELPOS_LONG_PADL (include/t2v_hip.h): replicated left-edge columns of relpos_table_long's Ev^T
+
 
 def _f16(t: torch.Tensor, device) -> torch.Tensor:
     return t.detach().to(device=device, dtype=torch.float16).contiguous()
@@ -75,6 +77,30 @@ def relpos_table16(tab: torch.Tensor, frames: int, transposed: bool) -> torch.Te
     else:
         out = torch.zeros(32, (d + 15) // 16 * 16, dtype=torch.float16, device=tab.device)
         out[:n, :d] = tab[jbase:jbase + n].to(torch.float16)
+    return out.contiguous()
+
+
+def relpos_long_cols(R: int) -> int:
+    """Columns of the transposed V-side table of relpos_table_long (T2V_RELPOS_LONG_COLS in include/t2v_hip.h)."""
+    return (2 * R + 158) // 8 * 8
+
+
+def relpos_table_long(tab: torch.Tensor, transposed: bool) -> torch.Tensor:
+    """A relative-position table [2R+1, d] as the MFMA kernel for clips of any length reads it (csrc/attention.hip relpos_long_kernel,
+    RELPOS_ATTN i[17] = 3), fp16 and independent of the frame count.
+    transposed=False: [2R+1, DK] = the table, zero columns beyond d (DK = d rounded up to 16).
+    True: [DV, relpos_long_cols(R)] = the table transposed with replicated edges: column c holds row clamp(c - RELPOS_LONG_PADL, 0, 2R),
+    zero rows beyond d (DV = d rounded up to 32), so that any 80-column window the kernel reads is a plain column range."""
+    n_rows, d = tab.shape
+    R = (n_rows - 1) // 2
+    assert n_rows == 2 * R + 1
+    if not transposed:
+        out = torch.zeros(n_rows, (d + 15) // 16 * 16, dtype=torch.float16, device=tab.device)
+        out[:, :d] = tab.to(torch.float16)
+        return out.contiguous()
+    rows = (torch.arange(relpos_long_cols(R), device=tab.device) - RELPOS_LONG_PADL).clamp(0, 2 * R)
+    out = torch.zeros((d + 31) // 32 * 32, rows.numel(), dtype=torch.float16, device=tab.device)
+    out[:d] = tab[rows].t().to(torch.float16)
     return out.contiguous()
 
 

@@ -943,29 +943,47 @@ class Program:
                   b_outer: int, b_inner: int, q_strides, kv_strides, o_strides, scale: float, head_dim: int = 64,
                   rel_k: Optional[Ref] = None, rel_v: Optional[Ref] = None, max_rel: int = 0, causal: bool = False,
                   q_offset: int = 0, relpos_mfma: Optional[int] = None, lo_off: int = 0,
-                  rel_k16: Optional[Ref] = None, rel_vT16: Optional[Ref] = None, vt_scratch: Optional[Buf] = None, waves: int = 0) -> Op:
+                  rel_k16: Optional[Ref] = None, rel_vT16: Optional[Ref] = None, rel_k_long: Optional[Ref] = None,
+                  rel_vT_long: Optional[Ref] = None, vt_scratch: Optional[Buf] = None, waves: int = 0) -> Op:
         """softmax(q k^T scale) v over strided (sequence, outer, inner) batches.  With rel_k / rel_v (fp32
         [2*max_rel+1, head_dim] tables) the LVDM relative-position temporal attention op is emitted instead.
         lo_off (elements): also store the low-order fp16 image of every output value at o + lo_off (rows [hi | lo] for a K-doubled
-        output projection, precise_operands)."""
+        output projection, precise_operands).
+        rel_k_long / rel_vT_long: the same tables packed for the kernel of clips of any length (packing.relpos_table_long); required
+        for clips of more than 32 frames, which only that kernel runs."""
         assert head_dim in (40, 64, 80, 160) or rel_k is not None
         op = Op(L.OP_ATTENTION if rel_k is None else L.OP_RELPOS_ATTN, name)
         op.i[0:5] = [nq, nk, heads, b_outer, b_inner]
         op.i[14] = head_dim
         if rel_k is not None:
-            assert nk <= 32 and 0 <= q_offset and q_offset + nq <= nk and head_dim % 8 == 0
+            assert 0 <= q_offset and q_offset + nq <= nk and head_dim % 8 == 0
+            if nk > L.RELPOS_MAX_FRAMES:
+                raise ValueError(f"relative-position attention over {nk} frames: the kernel for long clips "
+                                 f"(csrc/attention.hip relpos_long_kernel) takes at most {L.RELPOS_MAX_FRAMES} frames")
             op.i[15], op.i[16] = max_rel, q_offset
             # i[17]: 0 the VALU kernel; 1 the round-3 MFMA kernel (measured slower, opt-in); 2 the persistent MFMA kernel for whole
-            # clips of <= 16 frames on tables packed for it (rel_k16 / rel_vT16: packing.relpos_tables16) — the default where it applies
+            # clips of <= 16 frames on tables packed for it (rel_k16 / rel_vT16: packing.relpos_tables16) — the default where it applies;
+            # 3 the MFMA kernel for clips of any length (rel_k_long / rel_vT_long: packing.relpos_table_long) — the only one beyond 32
+            # frames; at <= 32 frames an A/B switch only (T2V_RELPOS_MFMA=3 under T2V_EXPERIMENTAL=1, or relpos_mfma=3)
             sel = int(L.knob("T2V_RELPOS_MFMA", "2")) if relpos_mfma is None else int(relpos_mfma)
             fits16 = (rel_k16 is not None and rel_vT16 is not None and nq == nk and q_offset == 0 and nk <= 16 and max_rel >= nk - 1
                       and head_dim in (40, 64, 80, 160))
+            fits_long = rel_k_long is not None and rel_vT_long is not None and head_dim in (40, 64, 80, 160)
+            if nk > 32:
+                if not fits_long:
+                    raise ValueError(f"relative-position attention over {nk} frames needs the tables packed for the long-clip kernel "
+                                     f"(rel_k_long / rel_vT_long) and head_dim 40, 64, 80 or 160 (got {head_dim})")
+                sel = 3
+            elif sel == 3 and not fits_long:
+                sel = 0
             if sel == 2 and not fits16:
                 sel = 0
             op.i[17] = sel
             op.p[4], op.p[5] = rel_k, rel_v
             if sel == 2:
                 op.p[6], op.p[7] = rel_k16, rel_vT16
+            elif sel == 3:
+                op.p[6], op.p[7] = rel_k_long, rel_vT_long
             op.i[18] = lo_off
             assert not causal
         elif causal:

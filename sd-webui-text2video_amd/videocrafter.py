@@ -259,6 +259,14 @@ class _LvdmLowering(_Lowering):
         return Ref("weight", 0, self.packer.add(f"{key}:tab16{'T' if transposed else ''}.{frames}", "f16",
                                                 lambda sd, k=key, f=frames, t=transposed: pk.relpos_table16(sd[k].float(), f, t)))
 
+    def table_long(self, key, frames: int, transposed: bool) -> Optional[Ref]:
+        """The same table packed for the MFMA kernel of clips of any length (packing.relpos_table_long): needed beyond 32 frames, and
+        at <= 32 frames only when the T2V_RELPOS_MFMA=3 experiment selects that kernel."""
+        if frames <= 32 and str(L.knob("T2V_RELPOS_MFMA", "2")) != "3":
+            return None
+        return Ref("weight", 0, self.packer.add(f"{key}:tabL{'T' if transposed else ''}", "f16",
+                                                lambda sd, k=key, t=transposed: pk.relpos_table_long(sd[k].float(), t)))
+
     def w_conv133_hilo(self, key) -> Ref:
         return Ref("weight", 0, self.packer.add(key + ":c133hl", "f16", lambda sd, k=key: pk.pad_rows(pk.conv3x3(torch.cat([sd[k + ".weight"][:, :, 0]] * 2, dim=1)))))
 
@@ -372,6 +380,8 @@ class _LvdmLowering(_Lowering):
                         o_strides=(hw * lo, 0, lo), scale=scale, head_dim=d, lo_off=c if attn_lo else 0,
                         rel_k=self.table(f"{tb}.{attn}.relative_position_k.embeddings_table"),
                         rel_v=self.table(f"{tb}.{attn}.relative_position_v.embeddings_table"),
+                        rel_k_long=self.table_long(f"{tb}.{attn}.relative_position_k.embeddings_table", Ftot, False),
+                        rel_vT_long=self.table_long(f"{tb}.{attn}.relative_position_v.embeddings_table", Ftot, True),
                         max_rel=net.temporal_length, q_offset=sh.offset)
             P.free(q, kv_all)
             return out_proj(attn, a, src, next_norm)
@@ -398,6 +408,8 @@ class _LvdmLowering(_Lowering):
                             rel_v=self.table(f"{tb}.{attn}.relative_position_v.embeddings_table"),
                             rel_k16=self.table16(f"{tb}.{attn}.relative_position_k.embeddings_table", F, False),
                             rel_vT16=self.table16(f"{tb}.{attn}.relative_position_v.embeddings_table", F, True),
+                            rel_k_long=self.table_long(f"{tb}.{attn}.relative_position_k.embeddings_table", F, False),
+                            rel_vT_long=self.table_long(f"{tb}.{attn}.relative_position_v.embeddings_table", F, True),
                             max_rel=net.temporal_length)
             P.free(qkv)
             return out_proj(attn, a, src, next_norm)
