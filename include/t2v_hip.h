@@ -26,7 +26,9 @@
 extern "C" {
 #endif
 
-#define T2V_ABI_VERSION 9   /* 9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
+#define T2V_ABI_VERSION 10  /* 10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
+                               optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
+                               9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
                                for it in p[6] / p[7], layout below);
                                8 (round 6): peer windows (t2v_comm_window_create / _open / t2v_comm_counters): exchanges as device-initiated stores into IPC-mapped mailboxes;
                                7 (round 6): ATTENTION p[6] / i[17] / i[18] (V^T scratch: spatial self-attention with LDS-DMA tiles); T2V_ERR_RESIDENCY — a launch that needs its whole grid co-resident was refused by the occupancy check (the caller
@@ -75,7 +77,8 @@ enum t2v_op_kind {
   T2V_OP_RESHARD_ROWS = 18,  /* chunked row regrouping (pack / unpack of a frame <-> pixel resharding), optional fp32 residual */
   T2V_OP_ALLTOALL = 19,      /* frame <-> pixel resharding of a T-sharded clip over the plan's communicator */
   T2V_OP_STATS_HALO = 20,    /* GroupNorm statistics parts to every rank + raw boundary frames to the two neighbours: one grouped exchange */
-  T2V_OP_KIND_MAX = 21
+  T2V_OP_RESAMPLE = 21,      /* one separable pass of a table-driven uint8 image resize (Pillow's 8-bit resampler, bit-exact); optional float token output */
+  T2V_OP_KIND_MAX = 22
 };
 
 /* GEMM gather modes: how row m / reduction index k of the A operand are addressed          */
@@ -274,6 +277,18 @@ enum t2v_gather {
  *      chunks from q at p1 + q*cnt(me)*chunk.  The rank's own part is moved by RESHARD_ROWS ops.
  *      i: 0/1 chunk bytes (lo, hi), 2 nparts, 3 this rank's part, 4 frames per slice, 5 frames of the last slice, 6 direction;
  *      p: 0 send base, 1 receive base
+ * RESAMPLE (ABI 10): one pass of a separable resize of uint8 images src [N, H, W, 3] (interleaved RGB) along one axis, as Pillow's 8-bit
+ *      resampler runs it (Resample.c, PRECISION_BITS 22; `Image.resize(..., Image.LANCZOS)` = a horizontal pass into a uint8 intermediate,
+ *      then a vertical pass; a pass whose sizes are equal is left out by the host).  For output index o along the axis:
+ *        acc = 2^21 + sum_{j < count(o)} src[first(o) + j] * coef[o][j]   (int32),   value = clamp(acc >> 22, 0, 255)   (arithmetic shift)
+ *      axis 0: out [N, H, i[4], 3], o = output column;  axis 1: out [N, i[4], W, 3], o = output row.  first / count are clamped to the
+ *      source axis and count to the table row length before use: a malformed table cannot make the kernel read outside the image.
+ *      Output forms (i[7]): 0 = the uint8 value;  1 / 2 = lut[value] as fp32 / fp16 (the fp16 rounding of the fp32 entry) written as
+ *      channels-last tokens [N * rows * columns, i[8]] with channels 3 .. i[8]-1 zeroed — with lut[u] = 2 * (u / 255) - 1 evaluated on
+ *      the host in float32 (process_modelscope.py:129,137) the last pass writes the VAE encoder's entry buffer itself.
+ *      i: 0 N, 1 H, 2 W (of the source), 3 channels (= 3), 4 output size along the axis, 5 axis (0 horizontal | 1 vertical),
+ *      6 table row length (ksize), 7 output form, 8 ld of the token forms (>= 3);
+ *      p: 0 src uint8, 1 dst, 2 coef int32 [i[4]][i[6]], 3 bounds int32 [i[4]][2] = {first, count}, 4 lut fp32 [256] (forms 1 / 2)
  */
 typedef struct t2v_op {
   int32_t kind;

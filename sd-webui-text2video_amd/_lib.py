@@ -30,7 +30,7 @@ def knob(name: str, default):
 
 
 # ---- mirrors of include/t2v_hip.h (checked against the header by tests/test_abi.py) -------
-ABI_VERSION = 9
+ABI_VERSION = 10
 RELPOS_MAX_FRAMES = 1024            # T2V_RELPOS_MAX_FRAMES: longest clip of RELPOS_ATTN i[17] = 3
 RELPOS_LONG_PADL = 72               # T2V_RELPOS_LONG_PADL: replicated left-edge columns of its packed Ev^T table
 OP_GEMM, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_SOFTMAX = 1, 2, 3, 4, 5
@@ -40,6 +40,7 @@ OP_RELPOS_ATTN = 13
 OP_EMBED_ROWS = 14
 OP_TO_UINT8, OP_ALLGATHER, OP_HALO_EXCHANGE = 15, 16, 17
 OP_RESHARD_ROWS, OP_ALLTOALL, OP_STATS_HALO = 18, 19, 20
+OP_RESAMPLE = 21
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_TCONV3, GATHER_CONV3X3_C8 = 0, 1, 2, 3
 EPI_NONE, EPI_GEGLU, EPI_TATTN, EPI_STATS, EPI_GN, EPI_XATTN = 0, 1, 2, 3, 4, 5
 GN_PIECES = 36                  # T2V_GN_PIECES

@@ -8,6 +8,8 @@
 //                 (t2v_model.py:444), operand staging, SiLU(e) of emb_layers (:936)
 //   ddim_step     DDIM_Gaussian update incl. half-channel classifier-free guidance
 //                 (samplers/ddim/gaussian_sampler.py:125-136, 103-108, 199-211, 269-283)
+//   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
+//                 (process_modelscope.py:116-120, 174-178); the last pass can write the VAE encoder's tokens
 #include "t2v_kernels.h"
 
 namespace {
@@ -242,6 +244,162 @@ __global__ __launch_bounds__(256) void to_uint8_kernel(const TIN* in, unsigned c
   }
 }
 
+// Separable table-driven resampler for uint8 [N, H, W, 3] images (T2V_OP_RESAMPLE): ONE pass of Pillow's 8-bit resize
+// (Resample.c, PRECISION_BITS = 22) — the Lanczos resize of process_modelscope.py:116-120,174-178 is a horizontal pass into a
+// uint8 intermediate followed by a vertical one.  Per output index o with table row k[0..ksize) and bounds {first, count}:
+//   acc = 2^21 + sum_j src[first + j] * k[j]  (int32),  result = clamp(acc >> 22, 0, 255)  (arithmetic shift).
+// FORM 0 stores the byte; FORM 1 / 2 (the last pass in front of the VAE encoder) store lut[byte] as fp32 / fp16 channels-last
+// tokens of `ld` channels, the channels beyond 3 zeroed — the encoder's entry buffer, so no float image ever exists.
+// Bounds are clamped to the source axis before use: a malformed table gives wrong pixels, never a read outside the image.
+constexpr int RS_LDS_BYTES = 32768;
+
+__device__ __forceinline__ void rs_bounds(const int* bounds, int o, int in_size, int ksize, int& first, int& count) {
+  first = bounds[2 * o];
+  first = first < 0 ? 0 : (first > in_size ? in_size : first);
+  const int room = in_size - first;
+  count = bounds[2 * o + 1];
+  count = count < 0 ? 0 : (count > ksize ? ksize : count);
+  count = count > room ? room : count;
+}
+
+__device__ __forceinline__ int rs_clip8(int acc) {
+  const int v = acc >> 22;
+  return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+// one store unit: FORM 0 = 4 consecutive bytes of the output row (one dword store where the address allows; the tail of a row and
+// unaligned rows go byte by byte), FORM 1 / 2 = one pixel (3 bytes -> one token row of ld floats / halfs)
+template <int FORM>
+__device__ __forceinline__ void rs_store(void* dst_row, int e0, int row_bytes, const int (&v)[4], const float* lut, int ld) {
+  if constexpr (FORM == 0) {
+    unsigned char* d = reinterpret_cast<unsigned char*>(dst_row) + e0;
+    if (e0 + 4 <= row_bytes && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+      *reinterpret_cast<uint32_t*>(d) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+    } else {
+      for (int q = 0; q < 4 && e0 + q < row_bytes; ++q) d[q] = (unsigned char)v[q];
+    }
+  } else if constexpr (FORM == 1) {
+    float* d = reinterpret_cast<float*>(dst_row) + (size_t)(e0 / 3) * ld;
+    for (int c = 0; c < ld; ++c) d[c] = c < 3 ? lut[v[c]] : 0.f;
+  } else {
+    f16* d = reinterpret_cast<f16*>(dst_row) + (size_t)(e0 / 3) * ld;
+    if (ld == 8 && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {          // the encoder's 8-channel token row: one 16-byte store
+      f16x8 t = {(f16)lut[v[0]], (f16)lut[v[1]], (f16)lut[v[2]], (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+      *reinterpret_cast<f16x8*>(d) = t;
+    } else {
+      for (int c = 0; c < ld; ++c) d[c] = c < 3 ? (f16)lut[v[c]] : (f16)0.f;
+    }
+  }
+}
+
+// Horizontal pass: a workgroup owns 256 units of ONE source row — a unit is 4 consecutive output pixels (12 bytes, three dword
+// stores) for FORM 0 and one pixel (one token row) for FORM 1 / 2; a pixel's bounds and table row are read once for its three
+// channels.  The source span those outputs read is staged in LDS with 16-byte loads (LDS offset congruent to the global address
+// mod 16) when it fits, else the taps come from global memory.
+template <int FORM>
+__global__ __launch_bounds__(256) void resample_h_kernel(const unsigned char* src, void* dst, const int* coef, const int* bounds,
+                                                         const float* lut, int W, int Wout, int ksize, int ld, int tiles) {
+  constexpr int PX = FORM == 0 ? 4 : 1;                 // output pixels per unit
+  __shared__ __attribute__((aligned(16))) unsigned char smem[RS_LDS_BYTES];
+  __shared__ int s_lo, s_hi;
+  const long row = blockIdx.x / tiles;
+  const int tile = (int)(blockIdx.x - row * tiles);
+  const int row_bytes = Wout * 3;
+  const unsigned char* srow = src + row * (long)W * 3;
+  const int x_first = tile * 256 * PX;
+  int x_end = x_first + 256 * PX;
+  x_end = x_end > Wout ? Wout : x_end;
+  if (threadIdx.x == 0) { s_lo = W; s_hi = 0; }
+  __syncthreads();
+  for (int x = x_first + (int)threadIdx.x; x < x_end; x += 256) {
+    int first, count;
+    rs_bounds(bounds, x, W, ksize, first, count);
+    if (count > 0) { atomicMin(&s_lo, first); atomicMax(&s_hi, first + count); }
+  }
+  __syncthreads();
+  const int lo = s_lo, span = (s_hi - s_lo) * 3;        // bytes [lo * 3, lo * 3 + span) of the source row
+  const unsigned char* g = srow + (long)lo * 3;
+  const int pad = (int)(reinterpret_cast<uintptr_t>(g) & 15);
+  const bool staged = span > 0 && pad + span <= RS_LDS_BYTES;
+  if (staged) {
+    int head = (16 - pad) & 15;
+    head = head > span ? span : head;
+    const int nvec = (span - head) >> 4, tail0 = head + (nvec << 4);
+    for (int b = threadIdx.x; b < head; b += 256) smem[pad + b] = g[b];
+    for (int q = threadIdx.x; q < nvec; q += 256)
+      *reinterpret_cast<uint4*>(smem + pad + head + (q << 4)) = *reinterpret_cast<const uint4*>(g + head + (q << 4));
+    for (int b = tail0 + threadIdx.x; b < span; b += 256) smem[pad + b] = g[b];
+    __syncthreads();
+  }
+  const int x0 = x_first + (int)threadIdx.x * PX;
+  if (x0 >= Wout) return;
+  int v[PX * 3 + (FORM == 0 ? 0 : 1)] = {};
+#pragma unroll
+  for (int p = 0; p < PX; ++p) {
+    const int x = x0 + p;
+    if (x < Wout) {
+      int first, count;
+      rs_bounds(bounds, x, W, ksize, first, count);
+      const int* k = coef + (long)x * ksize;
+      const unsigned char* s = staged ? smem + pad + (first - lo) * 3 : srow + (long)first * 3;
+      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+      for (int j = 0; j < count; ++j, s += 3) {
+        const int kj = k[j];
+        a0 += (int)s[0] * kj; a1 += (int)s[1] * kj; a2 += (int)s[2] * kj;
+      }
+      v[p * 3] = rs_clip8(a0); v[p * 3 + 1] = rs_clip8(a1); v[p * 3 + 2] = rs_clip8(a2);
+    }
+  }
+  char* drow = reinterpret_cast<char*>(dst) + row * (long)Wout * (FORM == 0 ? 3 : (FORM == 1 ? 4 : 2) * ld);
+  if constexpr (FORM == 0) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const int u[4] = {v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]};
+      if (x0 * 3 + q * 4 < row_bytes) rs_store<0>(drow, x0 * 3 + q * 4, row_bytes, u, lut, ld);
+    }
+  } else {
+    rs_store<FORM>(drow, x0 * 3, row_bytes, v, lut, ld);
+  }
+}
+
+// Vertical pass: a workgroup owns 256 units of ONE output row; every tap is a coalesced read of the same bytes of a source row
+// (dword loads where the address allows), the table row and bounds are uniform over the workgroup.
+template <int FORM>
+__global__ __launch_bounds__(256) void resample_v_kernel(const unsigned char* src, void* dst, const int* coef, const int* bounds,
+                                                         const float* lut, int H, int W, int Hout, int ksize, int ld, int tiles) {
+  constexpr int UB = FORM == 0 ? 4 : 3;
+  const long orow = blockIdx.x / tiles;                 // image * Hout + y
+  const int tile = (int)(blockIdx.x - orow * tiles);
+  const long img = orow / Hout;
+  const int y = (int)(orow - img * Hout);
+  const int row_bytes = W * 3;
+  const int e0 = (tile * 256 + (int)threadIdx.x) * UB;
+  if (e0 >= row_bytes) return;
+  int first, count;
+  rs_bounds(bounds, y, H, ksize, first, count);
+  const int* k = coef + (long)y * ksize;
+  const unsigned char* s = src + (img * H + first) * (long)row_bytes + e0;
+  int acc[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+  const bool whole = e0 + UB <= row_bytes;
+  for (int j = 0; j < count; ++j, s += row_bytes) {
+    const int kj = k[j];
+    if (FORM == 0 && whole && (reinterpret_cast<uintptr_t>(s) & 3) == 0) {
+      const uint32_t u = *reinterpret_cast<const uint32_t*>(s);
+      acc[0] += (int)(u & 255u) * kj; acc[1] += (int)((u >> 8) & 255u) * kj;
+      acc[2] += (int)((u >> 16) & 255u) * kj; acc[3] += (int)(u >> 24) * kj;
+    } else {
+#pragma unroll
+      for (int q = 0; q < UB; ++q)
+        if (e0 + q < row_bytes) acc[q] += (int)s[q] * kj;
+    }
+  }
+  int v[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v[q] = rs_clip8(acc[q]);
+  char* drow = reinterpret_cast<char*>(dst) + orow * (long)W * (FORM == 0 ? 3 : (FORM == 1 ? 4 : 2) * ld);
+  rs_store<FORM>(drow, e0, row_bytes, v, lut, ld);
+}
+
 inline int grid_for(long n) {
   const long g = (n + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
@@ -294,6 +452,31 @@ hipError_t t2v_launch_to_uint8(const t2v_op& op, hipStream_t s) {
     const f16* in = reinterpret_cast<const f16*>(op.p[0]);
     if (half) hipLaunchKernelGGL((to_uint8_kernel<f16, true>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx, bgr);
     else hipLaunchKernelGGL((to_uint8_kernel<f16, false>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx, bgr);
+  }
+  return hipGetLastError();
+}
+
+hipError_t t2v_launch_resample(const t2v_op& op, hipStream_t s) {
+  // (shape, pointers and the grid size were checked by the executor's validation)
+  const int N = op.i[0], H = op.i[1], W = op.i[2], out = op.i[4], axis = op.i[5], ksize = op.i[6], form = op.i[7], ld = op.i[8];
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(op.p[0]);
+  void* dst = reinterpret_cast<void*>(op.p[1]);
+  const int* coef = reinterpret_cast<const int*>(op.p[2]);
+  const int* bounds = reinterpret_cast<const int*>(op.p[3]);
+  const float* lut = reinterpret_cast<const float*>(op.p[4]);
+  const int row_px = axis == 0 ? out : W;
+  const int units = form != 0 ? row_px : (axis == 0 ? (row_px + 3) / 4 : (row_px * 3 + 3) / 4);     // (as in the executor's validation)
+  const int tiles = (units + 255) / 256;
+  const long rows = (long)N * (axis == 0 ? H : out);
+  const dim3 g((unsigned)(rows * tiles));
+  if (axis == 0) {
+    if (form == 0) hipLaunchKernelGGL(resample_h_kernel<0>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, W, out, ksize, ld, tiles);
+    else if (form == 1) hipLaunchKernelGGL(resample_h_kernel<1>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, W, out, ksize, ld, tiles);
+    else hipLaunchKernelGGL(resample_h_kernel<2>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, W, out, ksize, ld, tiles);
+  } else {
+    if (form == 0) hipLaunchKernelGGL(resample_v_kernel<0>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
+    else if (form == 1) hipLaunchKernelGGL(resample_v_kernel<1>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
+    else hipLaunchKernelGGL(resample_v_kernel<2>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
   }
   return hipGetLastError();
 }

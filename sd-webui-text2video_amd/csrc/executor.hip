@@ -237,6 +237,22 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[1] > 4 || op.i[2] <= 0 || op.i[3] <= 0 || op.i[4] <= 0) return bad("empty uint8 conversion");
       if (op.p[0] == 0 || op.p[1] == 0) return bad("null uint8-conversion pointer");
       return 0;
+    case T2V_OP_RESAMPLE: {
+      const int out = op.i[4], axis = op.i[5], form = op.i[7], ld = op.i[8];
+      if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[2] <= 0 || out <= 0 || op.i[6] <= 0) return bad("resample: images, rows, columns, output size and table row length must be positive");
+      if (op.i[3] != 3) return bad("resample: interleaved RGB only (3 channels)");
+      if (axis != 0 && axis != 1) return bad("resample: axis must be 0 (horizontal) or 1 (vertical)");
+      if (form < 0 || form > 2) return bad("resample: unknown output form (0 uint8, 1 fp32 tokens, 2 fp16 tokens)");
+      if (form != 0 && (ld < 3 || op.p[4] == 0)) return bad("resample: the token forms need ld >= 3 and the 256-entry value table p[4]");
+      if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[3] == 0) return bad("null resample pointer (source, destination, coefficients, bounds)");
+      const long row_px = axis == 0 ? out : op.i[2];
+      if (row_px > (1 << 28)) return bad("resample: row too long");
+      // units of a row: a pixel (token forms), 4 pixels (horizontal, uint8) or 4 bytes (vertical, uint8) — 256 per workgroup
+      const long tiles = ((form != 0 ? row_px : (axis == 0 ? (row_px + 3) / 4 : (row_px * 3 + 3) / 4)) + 255) / 256;
+      // one workgroup of 256 threads per (row, tile): HIP refuses a launch of 2^32 threads or more
+      if ((long)op.i[0] * (axis == 0 ? op.i[1] : out) * tiles > 0xffffffL) return bad("resample: too many rows for one launch (rows x tiles of 256 units <= 2^24 - 1)");
+      return 0;
+    }
     case T2V_OP_ALLGATHER:
       if (op.i[2] < 1 || op.i[3] < 0 || op.i[3] >= op.i[2] || op.p[0] == 0) return bad("bad all-gather record");
       return 0;
@@ -352,6 +368,7 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
     case T2V_OP_RELPOS_ATTN: return t2v_launch_relpos_attention(op, s);
     case T2V_OP_EMBED_ROWS: return t2v_launch_embed_rows(op, s);
     case T2V_OP_TO_UINT8: return t2v_launch_to_uint8(op, s);
+    case T2V_OP_RESAMPLE: return t2v_launch_resample(op, s);
     case T2V_OP_RESHARD_ROWS: return t2v_launch_reshard_rows(op, s);
     case T2V_OP_MEMSET: {
       const size_t bytes = (size_t)(uint32_t)op.i[0] | ((size_t)(uint32_t)op.i[1] << 32);

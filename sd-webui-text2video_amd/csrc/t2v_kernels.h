@@ -240,6 +240,7 @@ hipError_t t2v_launch_softmax(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_ncthw_to_cl(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_cl_to_ncthw(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_to_uint8(const t2v_op& op, hipStream_t s);
+hipError_t t2v_launch_resample(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_reshard_rows(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_time_embed(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_copy2d(const t2v_op& op, hipStream_t s);

@@ -6,6 +6,7 @@ scripts/stable_lora/stable_utils/lora_processor.py:215-246, has mutated `.weight
 """
 from __future__ import annotations
 
+import math
 from typing import Callable, Dict, List, Tuple
 
 import torch
@@ -104,6 +105,73 @@ def relpos_table_long(tab: torch.Tensor, transposed: bool) -> torch.Tensor:
     return out.contiguous()
 
 
+RESAMPLE_PRECISION_BITS = 22   # Pillow's PRECISION_BITS (Resample.c): 8-bit resampling coefficients are 22-bit fixed point
+
+
+def _lanczos(x: float) -> float:
+    """Pillow's lanczos_filter: sinc(x) * sinc(x / 3) on -3 <= x < 3 (libm's sin through `math`, as the C code calls it)."""
+    def sinc(v):
+        if v == 0.0:
+            return 1.0
+        v = v * math.pi
+        return math.sin(v) / v
+    return sinc(x) * sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+def resample_ksize(in_size: int, out_size: int) -> int:
+    """Row length of resample_table(in_size, out_size): Pillow's ksize = ceil(support) * 2 + 1 with support = 3 * max(in / out, 1)."""
+    return int(math.ceil(3.0 * max(in_size / out_size, 1.0))) * 2 + 1
+
+
+def resample_identity_table(size: int):
+    """One-tap table that copies every index (coefficient 2^22: acc = 2^21 + u * 2^22, acc >> 22 = u): the pass that only converts
+    uint8 frames already at the target size into the encoder's tokens."""
+    import numpy as np
+    coef = np.full((size, 1), 1 << RESAMPLE_PRECISION_BITS, dtype=np.int32)
+    bounds = np.stack([np.arange(size, dtype=np.int32), np.ones(size, dtype=np.int32)], axis=1)
+    return coef, bounds
+
+
+def resample_table(in_size: int, out_size: int):
+    """Coefficient table of ONE pass of Pillow's 8-bit Lanczos resize (`Image.resize(..., Image.LANCZOS)`, Resample.c
+    precompute_coeffs + normalize_coeffs_8bpc) from `in_size` to `out_size` pixels, computed in float64 in the same operation order:
+    -> (coef int32 [out, ksize], bounds int32 [out, 2] = {first source index, taps}); taps beyond a row's count are zero.
+    T2V_OP_RESAMPLE evaluates it: acc = 2^21 + sum_j src[first + j] * coef[j], value = clamp(acc >> 22, 0, 255)."""
+    import numpy as np
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError(f"resample_table: sizes must be positive, got {in_size} -> {out_size}")
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 3.0 * filterscale
+    ksize = resample_ksize(in_size, out_size)
+    ss = 1.0 / filterscale
+    coef = np.zeros((out_size, ksize), dtype=np.int32)
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    one = float(1 << RESAMPLE_PRECISION_BITS)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [_lanczos((j + xmin - center + 0.5) * ss) for j in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        for j, v in enumerate(w):
+            coef[xx, j] = int(0.5 + v * one) if v >= 0 else int(-0.5 + v * one)
+        bounds[xx] = (xmin, xmax)
+    return coef, bounds
+
+
+def resample_lut() -> torch.Tensor:
+    """fp32 [256]: 2 * (u / 255) - 1 in float32, with the reference's own operations (process_modelscope.py:129,137: numpy `/ 255`
+    on a float32 array, then torch `2 * x - 1`) — the value table of T2V_OP_RESAMPLE's token forms, so that the bits do not depend on
+    the device's division."""
+    import numpy as np
+    return 2 * torch.from_numpy(np.arange(256).astype(np.float32) / 255) - 1
+
+
 def linear_dup(w: torch.Tensor) -> torch.Tensor:
     """[N, K] -> [N, 2K] = [W | W]: consumer of an operand laid out [hi (K) | lo (K)] per row."""
     w = linear(w)
@@ -164,7 +232,7 @@ class WeightPacker:
     out of ~2600 tensors, and the device addresses bound into the denoise programs stay valid."""
 
     def __init__(self):
-        self.recipes: List[Tuple[str, str, Recipe]] = []   # (name, 'f16'|'f32', fn)
+        self.recipes: List[Tuple[str, str, Recipe]] = []   # (name, 'f16'|'f32'|'i32', fn)
         self._names = set()
         self.deps: Dict[str, frozenset] = {}                # packed name -> state-dict keys its recipe read
 
@@ -195,6 +263,8 @@ class WeightPacker:
 
     @staticmethod
     def _cast(t: torch.Tensor, dtype: str, device) -> torch.Tensor:
+        if dtype == "i32":          # integer tables (T2V_OP_RESAMPLE coefficients / bounds)
+            return t.detach().to(device=device, dtype=torch.int32).contiguous()
         return _f16(t, device) if dtype == "f16" else _f32(t, device)
 
     def materialise(self, sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:

@@ -184,14 +184,63 @@ class TextToVideoSynthesis(object):
         L.async_status()               # the copy above synchronised: a fault raised by any kernel of this video surfaces HERE
         return [arr[i] for i in range(arr.shape[0])], x0
 
+    max_programs = 4          # resize programs kept (one per geometry; each owns a small device arena)
+
+    @staticmethod
+    def _as_u8_frames(frames, device) -> torch.Tensor:
+        """uint8 [F, H, W, 3] frames, numpy or tensor -> contiguous device tensor (a device tensor is taken as it is: no host copy)."""
+        t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(frames)))
+        if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[-1] != 3:
+            raise ValueError(f"expected uint8 frames [F, H, W, 3], got {t.dtype} {tuple(t.shape)}")
+        return t.to(device).contiguous()
+
     @torch.no_grad()
-    def compute_latents(self, vd_out, cpu_vae="GPU (half precision)", device=torch.device("cuda")):
+    def resize_frames(self, frames, height: int, width: int) -> torch.Tensor:
+        """uint8 RGB frames [F, H, W, 3] (numpy array or device tensor) -> device uint8 [F, height, width, 3]: the resize of
+        process_modelscope.py:116-120,174-178 (`Image.resize((width, height), Image.ANTIALIAS)` = Pillow's Lanczos filter) on the
+        GPU, bit-exact with Pillow (T2V_OP_RESAMPLE: a horizontal and a vertical integer pass).  Programs are cached per geometry."""
+        from . import packing as pk
+        from .program import Program, Ref
+        from .unet import _Compiled
+        x = self._as_u8_frames(frames, self.device)
+        n, h0, w0, _ = x.shape
+        if (h0, w0) == (height, width):
+            return x
+        cache = self.__dict__.setdefault("_resize_programs", {})
+        key = (n, h0, w0, height, width)
+        ent = cache.get(key)
+        if ent is None or next(iter(ent[1].values())).device != x.device:
+            prog, packer = Program(f"resize n{n} {h0}x{w0} -> {height}x{width}"), pk.WeightPacker()
+            prog.begin()
+            prog.resample("frames.resample", Ref("ext", L.EXT_X), Ref("ext", L.EXT_OUT), packer, n=n, src_hw=(h0, w0), dst_hw=(height, width))
+            prog.finish()
+            ent = (_Compiled(prog, packer), packer.materialise({}, x.device))
+            cache[key] = ent
+            while len(cache) > self.max_programs:
+                del cache[next(k for k in cache if k != key)]
+        comp, packed = ent
+        comp.ensure_bound(packed, x.device)
+        out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=x.device)
+        comp.bound.run({L.EXT_X: x.data_ptr(), L.EXT_OUT: out.data_ptr()}, torch.cuda.current_stream(x.device).cuda_stream)
+        return out
+
+    @torch.no_grad()
+    def compute_latents(self, vd_out, cpu_vae="GPU (half precision)", device=torch.device("cuda"), height=None, width=None):
         """vid2vid input side (t2v_pipeline.py:148-194): frames [b, 3, F, H, W] in [-1, 1] -> posterior mean x 0.18215,
         [b, 4, F, H/8, W/8] fp32 on the host.  All frames go through ONE batched encoder program (the reference
-        encodes them one at a time)."""
+        encodes them one at a time).
+        `vd_out` may also be uint8 RGB frames [F, H0, W0, 3] of ANY size (numpy array or device tensor; one clip): they are resized
+        to (height, width) — default: their own size — with Pillow's Lanczos filter, mapped to [-1, 1] and encoded by ONE program
+        (AutoencoderKL.encode_uint8); the frames make no float round trip through the host."""
         _note_cpu_vae(cpu_vae)                         # "CPU ..." modes: full-precision VAE, still on the GPU (see _note_cpu_vae)
         self.device = torch.device(device)
         self.autoencoder.to(self.device)
+        if (isinstance(vd_out, np.ndarray) and vd_out.dtype == np.uint8) or (isinstance(vd_out, torch.Tensor) and vd_out.dtype == torch.uint8):
+            x = self._as_u8_frames(vd_out, self.device)
+            F = x.shape[0]
+            h, w = (x.shape[1] if height is None else int(height)), (x.shape[2] if width is None else int(width))
+            mean = self.autoencoder.encode_uint8(x, h, w).mean.float() * SCALE_FACTOR
+            return mean.view(1, F, mean.shape[1], mean.shape[2], mean.shape[3]).permute(0, 2, 1, 3, 4).contiguous().cpu()
         bs, c, F, h, w = vd_out.shape
         x = vd_out.to(self.device).permute(0, 2, 1, 3, 4).reshape(bs * F, c, h, w).contiguous()
         if "half precision" in str(cpu_vae):
@@ -248,7 +297,8 @@ pipe: Optional[TextToVideoSynthesis] = None     # module-global model cache, as 
 
 def frames_to_video_tensor(frames) -> torch.Tensor:
     """[F, H, W, 3] uint8 RGB frames -> [1, 3, F, H, W] float32 in [-1, 1]: the array arithmetic of process_modelscope.py:117-131
-    (`/ 255`, `2 * x - 1`, one sample).  Reading / resizing the frames (ffmpeg, PIL) is host plumbing left to the caller."""
+    (`/ 255`, `2 * x - 1`, one sample).  Reading the frames (ffmpeg) is host plumbing left to the caller; frames of another size go
+    through `TextToVideoSynthesis.resize_frames` first."""
     arr = np.asarray(frames)
     if arr.ndim != 4 or arr.shape[-1] != 3:
         raise ValueError(f"expected frames [F, H, W, 3], got {arr.shape}")
@@ -270,12 +320,14 @@ def process_modelscope(args_dict: dict, extra_args=None):
     * no `stitch`: returns the BGR uint8 frames of the (last) video — what the reference writes as PNGs (:225-229);
       with (cond, uncond) tensors and batch_count > 1 the videos of seeds seed .. seed + batch_count - 1 are made in ONE
       batched pass, frames side by side.
-    * vid2vid (`do_vid2vid`, :80-142): `vid2vid_frames` = the input clip as [F, H, W, 3] uint8 RGB frames already at
-      (height, width) — what the reference has after vid2frames + PIL resize — or a [1, 3, F, H, W] float video in [-1, 1], or
+    * vid2vid (`do_vid2vid`, :80-142): `vid2vid_frames` = the input clip as [F, H, W, 3] uint8 RGB frames of ANY size — a numpy
+      array or a (device) tensor such as `infer_conditioned(..., to_host=False)` returns; frames not at (height, width) are
+      resized on the GPU exactly as the reference's PIL `Image.ANTIALIAS` resize does (:116-120; `pipe.resize_frames`) — or a
+      [1, 3, F, H, W] float video in [-1, 1], or
       ready latents [1, 4, F, h, w]; encoded by ONE batched VAE-encoder program (`compute_latents`), then
       `skip_steps = floor(steps * clamp(1 - strength, 0, 1))` and `infer(..., latents, strength, skip_steps, is_vid2vid=True)`.
-    * img2vid inpainting (`inpainting_frames` > 0 with an `inpainting_image` [H, W, 3] uint8 RGB, :170-217): the image is encoded
-      for every frame, `inpainting_weights` = the per-frame mask weights (a sequence of `frames` floats — the reference reads
+    * img2vid inpainting (`inpainting_frames` > 0 with an `inpainting_image` [H, W, 3] uint8 RGB of any size, :170-217): the image
+      is resized once like a vid2vid frame (:174-178) and encoded for every frame, `inpainting_weights` = the per-frame mask weights (a sequence of `frames` floats — the reference reads
       them from its deforum-style key string through T2VAnimKeys, host plumbing), latents = image * (1 - mask) + N(0,1) * mask
       with the noise from numpy's GLOBAL generator exactly like the reference (:205), `strength = 1`, and `mask` goes to the
       sampler (where, for DDIM_Gaussian, the reference's hook is inert: SURVEY App. C #5)."""
@@ -297,13 +349,40 @@ def process_modelscope(args_dict: dict, extra_args=None):
     inpainting = int(getattr(a, "inpainting_frames", 0) or 0) > 0 and getattr(a, "inpainting_image", None) is not None
     have_cond = getattr(a, "cond", None) is not None
 
+    def sized(frames):
+        """uint8 [F, H, W, 3] frames at (height, width): as given when they have that size, else resized by the pipeline on the
+        GPU with Pillow's Lanczos filter (process_modelscope.py:116-120,174-178) — a device tensor; a pipeline object that cannot
+        resize keeps the refusal.  (Two programs here: the resize with a uint8 result, then `compute_latents` on those frames, whose
+        front end is a one-tap copy pass into the encoder's tokens.  A caller that wants the single fused program calls
+        `pipe.compute_latents(frames, ..., height=, width=)` itself.)"""
+        if tuple(frames.shape[1:3]) == (height, width):
+            return frames
+        if not hasattr(pipe, "resize_frames"):
+            raise ValueError(f"input frames are {tuple(frames.shape[1:3])}, expected (height, width) = {(height, width)}: this pipeline "
+                             "object has no resize_frames, resize the frames before the call")
+        return pipe.resize_frames(frames, height, width)
+
     def to_latents(video):
         """frames / float video / latents -> [1, 4, F, h, w] on the host (compute_latents, t2v_pipeline.py:148-194)."""
         if isinstance(video, torch.Tensor) and video.ndim == 5 and video.shape[1] == 4:
             return video.float().cpu()
-        vd = video if (isinstance(video, torch.Tensor) and video.ndim == 5) else frames_to_video_tensor(video)
+        if isinstance(video, torch.Tensor) and video.ndim == 5:
+            vd = video
+        elif isinstance(video, torch.Tensor) and video.dtype == torch.uint8:
+            # a uint8 clip as a tensor (e.g. the device frames of infer_conditioned(..., to_host=False)): it stays where it is
+            if video.ndim != 4 or video.shape[-1] != 3:
+                raise ValueError(f"expected frames [F, H, W, 3], got {tuple(video.shape)}")
+            return pipe.compute_latents(sized(video), cpu_vae, device)
+        else:
+            arr = np.asarray(video)
+            if arr.ndim != 4 or arr.shape[-1] != 3:
+                raise ValueError(f"expected frames [F, H, W, 3], got {arr.shape}")
+            if arr.shape[1:3] != (height, width):
+                return pipe.compute_latents(sized(arr), cpu_vae, device)       # resized on the device: encoded from there
+            vd = frames_to_video_tensor(arr)
         if vd.shape[-2:] != (height, width):
-            raise ValueError(f"input frames are {tuple(vd.shape[-2:])}, expected (height, width) = {(height, width)}: resize on the host")
+            raise ValueError(f"the float video is {tuple(vd.shape[-2:])}, expected (height, width) = {(height, width)}: only uint8 frames "
+                             "are resized (pass the clip as [F, H, W, 3] uint8 frames)")
         return pipe.compute_latents(vd, cpu_vae, device)
 
     mask = None
@@ -321,13 +400,22 @@ def process_modelscope(args_dict: dict, extra_args=None):
         frames, _ = pipe.infer_conditioned(a.cond, a.uncond, steps=a.steps, seed=a.seed, videos=batch_count, **common)
         return frames
     urls, frames = [], None
+    inpaint_sized = None
     for batch in range(batch_count):
         seed = a.seed + batch if a.seed != -1 else -1
         if inpainting:
-            img = np.asarray(a.inpainting_image)
-            if img.shape != (height, width, 3):
-                raise ValueError(f"inpainting image is {img.shape}, expected {(height, width, 3)}: resize on the host")
-            image_latents = to_latents(np.repeat(img[np.newaxis], a.frames, axis=0)).numpy()
+            img = a.inpainting_image if isinstance(a.inpainting_image, torch.Tensor) else np.asarray(a.inpainting_image)
+            if img.ndim != 3 or img.shape[-1] != 3:
+                raise ValueError(f"inpainting image is {tuple(img.shape)}, expected [H, W, 3]")
+            if tuple(img.shape[:2]) != (height, width):
+                if inpaint_sized is None:
+                    inpaint_sized = sized(img[None])[0]                   # ONE image through the resize, then repeated per frame
+                img = inpaint_sized
+            if isinstance(img, torch.Tensor):
+                clip = img[None].expand(a.frames, *img.shape).contiguous()
+            else:
+                clip = np.repeat(img[np.newaxis], a.frames, axis=0)
+            image_latents = to_latents(clip).numpy()
             lh, lw = height // 8, width // 8
             latent_noise = np.random.normal(size=(1, 4, a.frames, lh, lw))            # the reference's unseeded draw (:205)
             weights = getattr(a, "inpainting_weights", None)

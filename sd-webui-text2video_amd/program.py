@@ -1054,6 +1054,52 @@ class Program:
         op.p[0:2] = [src, dst]
         return self._emit(op)
 
+    def resample(self, name: str, src: Ref, dst: Ref, packer, *, n: int, src_hw, dst_hw, form: str = "u8", ld: int = 3) -> List[Op]:
+        """Pillow's 8-bit Lanczos resize of uint8 frames src [n, H, W, 3] -> [n, H', W', 3] (process_modelscope.py:116-120,174-178) as
+        T2V_OP_RESAMPLE passes: horizontal into a uint8 intermediate, then vertical; a pass whose sizes are equal is left out.
+        form "u8": dst = the uint8 frames.  form "f32" / "f16": the LAST pass writes 2 * (u / 255) - 1 as channels-last tokens
+        [n * H' * W', ld] (channels >= 3 zeroed) — the VAE encoder's entry buffer; when no pass is needed a one-tap copy pass
+        (packing.resample_identity_table) does the conversion.  The tables are packed images of `packer` (int32; packing.resample_table)."""
+        from . import packing as pk
+        (H, W), (H2, W2) = src_hw, dst_hw
+        fcode = {"u8": 0, "f32": 1, "f16": 2}[form]
+        assert n > 0 and min(H, W, H2, W2) > 0 and (fcode == 0 or ld >= 3)
+        passes = ([(0, W, W2)] if W != W2 else []) + ([(1, H, H2)] if H != H2 else [])
+        identity = not passes and fcode != 0
+        if identity:
+            passes = [(1, H, H2)]
+        if not passes:
+            raise ValueError("resample: source and destination sizes are equal, nothing to emit")
+
+        def table(a, b, which):
+            build = (lambda: pk.resample_identity_table(a)) if identity else (lambda: pk.resample_table(a, b))
+            return Ref("weight", 0, packer.add(f"resample:{'copy' if identity else ''}{a}->{b}:{which}", "i32",
+                                               lambda sd, w=which: torch_from(build()[0 if w == "coef" else 1])))
+
+        def torch_from(arr):
+            import torch
+            return torch.from_numpy(arr)
+
+        lut = Ref("weight", 0, packer.add("resample:lut", "f32", lambda sd: pk.resample_lut())) if fcode else NULL
+        ops, cur, cur_hw, mid = [], src, (H, W), None
+        for idx, (axis, a, b) in enumerate(passes):
+            last = idx == len(passes) - 1
+            if last:
+                out = dst
+            else:
+                mid = self.alloc(n * H * b, 3, "u8")
+                out = mid.ref
+            op = Op(L.OP_RESAMPLE, f"{name}.{'h' if axis == 0 else 'v'}")
+            ksize = 1 if identity else pk.resample_ksize(a, b)
+            op.i[0:9] = [n, cur_hw[0], cur_hw[1], 3, b, axis, ksize, fcode if last else 0, ld if (last and fcode) else 3]
+            op.p[0:5] = [cur, out, table(a, b, "coef"), table(a, b, "bounds"), lut if last else NULL]
+            op.meta = dict(axis=axis, src=a, dst=b, form=form if last else "u8")
+            ops.append(self._emit(op))
+            cur, cur_hw = out, ((cur_hw[0], b) if axis == 0 else (b, cur_hw[1]))
+        if mid is not None:
+            self.free(mid)        # stream order: whatever reuses the block is launched after the last pass
+        return ops
+
     def time_embed(self, name: str, t: Ref, freqs: Ref, out: Buf) -> Op:
         op = Op(L.OP_TIME_EMBED, name)
         op.i[0:2] = [out.rows, out.cols]

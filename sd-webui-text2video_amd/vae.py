@@ -189,6 +189,33 @@ class AutoencoderKL(nn.Module):
         p0 = next(self.parameters())
         return DiagonalGaussianDistribution(moments.to(torch.float16 if p0.dtype == torch.float16 else torch.float32))
 
+    def encode_uint8(self, frames, height: int, width: int):
+        """frames uint8 [n, H0, W0, 3] (RGB, any size, device tensor) -> the posterior of the frames resized to (height, width) with
+        Pillow's Lanczos filter and mapped to [-1, 1] (process_modelscope.py:116-137), in ONE program: T2V_OP_RESAMPLE passes whose
+        last one writes the encoder's entry tokens, then the encoder of `encode`."""
+        if not frames.is_cuda:
+            raise L.T2VError("AutoencoderKL.encode_uint8 needs device tensors on an AMD GPU (no CPU fallback)")
+        if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3:
+            raise ValueError(f"expected uint8 frames [n, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
+        n, h0, w0, _ = frames.shape
+        nlev = len(self.ddconfig["ch_mult"]) - 1
+        assert height % (1 << nlev) == 0 and width % (1 << nlev) == 0
+        frames = frames.contiguous()
+        key = ("enc_u8", n, h0, w0, height, width)
+        comp = self._programs.get(key)
+        if comp is None:
+            low = _VaeLowering(self, n, height, width, "f16", "f32", self.debug_taps)
+            comp = _Compiled(low.build_encoder(u8_src=(h0, w0)), low.packer)
+            self._programs[key] = comp
+            while len(self._programs) > self.max_programs:          # each program owns a device arena
+                del self._programs[next(k for k in self._programs if k != key)]
+        self._refresh(comp, frames.device)
+        comp.ensure_bound(self._packed, frames.device)
+        moments = torch.empty((n, 2 * self.embed_dim, height >> nlev, width >> nlev), device=frames.device, dtype=torch.float32)
+        comp.bound.run({L.EXT_X: frames.data_ptr(), L.EXT_OUT: moments.data_ptr()}, torch.cuda.current_stream(frames.device).cuda_stream)
+        p0 = next(self.parameters())
+        return DiagonalGaussianDistribution(moments.to(torch.float16 if p0.dtype == torch.float16 else torch.float32))
+
     # ---- weights ------------------------------------------------------------------------------
     def _param_signature(self):
         return tuple((id(p), p._version, p.device.type, p.dtype) for p in self.parameters())
@@ -366,8 +393,11 @@ class _VaeLowering:
         P.free(out_attn)
         return out
 
-    def build_encoder(self) -> Program:
-        """Encoder.forward (autoencoder_modules.py:447-481) + quant_conv: image -> moments [n, 2*z, h/8, w/8]."""
+    def build_encoder(self, u8_src=None) -> Program:
+        """Encoder.forward (autoencoder_modules.py:447-481) + quant_conv: image -> moments [n, 2*z, h/8, w/8].
+        u8_src = (H0, W0): the input is uint8 frames [n, H0, W0, 3] of any size instead of a float image; the program then starts
+        with the Lanczos resize to (h, w) (Program.resample), whose last pass writes 2 * (u / 255) - 1 straight into the entry token
+        buffer in place of `x.to_tokens` — the same fp16 values that op stores for the float image of the same frames."""
         P, n, h, w = self.P, self.n, self.h, self.w
         dd = self.vae.ddconfig
         ch, ch_mult, nrb = dd["ch"], list(dd["ch_mult"]), dd["num_res_blocks"]
@@ -376,7 +406,11 @@ class _VaeLowering:
         assert dd["in_channels"] <= 8 and zc2 == 2 * self.vae.embed_dim == 8
         P.begin()
         xin = P.alloc(n * h * w, 8, "f16")
-        P.ncthw_to_cl("x.to_tokens", Ref("ext", L.EXT_X), self.z_dt, xin, B=n, C=dd["in_channels"], F=1, HW=h * w)
+        if u8_src is None:
+            P.ncthw_to_cl("x.to_tokens", Ref("ext", L.EXT_X), self.z_dt, xin, B=n, C=dd["in_channels"], F=1, HW=h * w)
+        else:
+            assert dd["in_channels"] == 3
+            P.resample("x.resample", Ref("ext", L.EXT_X), xin.ref, self.packer, n=n, src_hw=u8_src, dst_hw=(h, w), form="f16", ld=xin.ld)
         x = self.conv3("encoder.conv_in", xin, ch, h, w, cin=8)
         P.free(xin)
         P.tap("encoder.conv_in", x)
