@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define T2V_ABI_VERSION 10  /* 10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
+#define T2V_ABI_VERSION 11  /* 11: VideoCrafter depth adapter (additive: no existing record changes) — T2V_OP_DEPTH_TOKENS (depth frames -> PixelUnshuffle(8)
+                               tokens, optional per-frame min-max normalisation), T2V_OP_AVGPOOL2 (2x2 mean of channels-last fp32 tokens), GEMM i[18] = 2
+                               (ReLU), GEMM i[30] (residual row wrap for every gather mode, split-K allowed), T2V_EXT_ADAPTER (feature slots);
+                               10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
                                optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
                                9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
                                for it in p[6] / p[7], layout below);
@@ -78,7 +81,9 @@ enum t2v_op_kind {
   T2V_OP_ALLTOALL = 19,      /* frame <-> pixel resharding of a T-sharded clip over the plan's communicator */
   T2V_OP_STATS_HALO = 20,    /* GroupNorm statistics parts to every rank + raw boundary frames to the two neighbours: one grouped exchange */
   T2V_OP_RESAMPLE = 21,      /* one separable pass of a table-driven uint8 image resize (Pillow's 8-bit resampler, bit-exact); optional float token output */
-  T2V_OP_KIND_MAX = 22
+  T2V_OP_DEPTH_TOKENS = 22,  /* depth frames [n,1,H,W] -> PixelUnshuffle(8) channels-last fp16 tokens, optional per-frame min-max normalisation (T2I-Adapter entry) */
+  T2V_OP_AVGPOOL2 = 23,      /* 2x2 / stride 2 average pooling of channels-last fp32 tokens (mean in fp32), fp32 and / or fp16 out */
+  T2V_OP_KIND_MAX = 24
 };
 
 /* GEMM gather modes: how row m / reduction index k of the A operand are addressed          */
@@ -139,6 +144,8 @@ enum t2v_gather {
 #define T2V_EXT_XT_OUT 6 /* DDIM: x_{t-1} out                                                */
 #define T2V_EXT_NOISE 7  /* DDIM: eta-noise (may be null when sigma == 0)                    */
 #define T2V_EXT_EPS 8    /* DDIM: stacked UNet outputs [2,C,F,h,w] (cond, uncond)            */
+#define T2V_EXT_ADAPTER 9 /* first of T2V_EXT_SLOTS - 9 slots: adapter feature k at slot 9 + k, channels-last fp32 tokens [samples*F*h_k*w_k, C_k]
+                             (UNet: read as a residual at injection site k | adapter program: written by level k's last convolution)       */
 
 /* GroupNorm pass-1 granularity: rows of one statistics instance reduced per workgroup.  The
  * caller sizes the scratch as nparts*n_inst*ceil(rows/16)*groups*16 + n_inst*groups*8 bytes. */
@@ -162,12 +169,14 @@ enum t2v_gather {
  * GEMM:  out[M,N] = epi( gather(A)[M,K] * W[N,K]^T )       fp16 operands, fp32 accumulate
  *   i: 0 M, 1 N, 2 K, 3 lda, 4 ldw, 5 ldc, 6 ldr, 7 gather, 8 Hin|F, 9 Win|HW, 10 Cin,
  *      11 stride, 12 upsample, 13 Hout, 14 Wout, 15 rows_per_batch, 16 epilogue,
- *      17 out dtype, 18 act (0 none, 1 SiLU), 19 split_k, 20 bias_along_m, 21 ldrb,
+ *      17 out dtype, 18 act (0 none, 1 SiLU, 2 ReLU), 19 split_k, 20 bias_along_m, 21 ldrb,
  *      22 tile (0 = 128x128-class kernel; 1 256x256, 2 256x320, 3 128x256 (8 waves, 3-stage ring), 4 / 5 128x128 with a 4-deep
  *         ring on 4 / 8 waves, 6 / 7 = 1 / 2 with the two-group ping-pong schedule, 8 / 9 192x320 / 192x256 on 12 waves,
  *         10 = 192x192 on 12 waves, T2V_EPI_TATTN only; 11 = 128x320 on 8 waves, 12 = 64x64 on 4 waves with a 4-deep ring),
  *      23 tconv halo (input rows are [clip][F+2][HW]: one halo frame either side, T-sharding);
  *         for CONV3X3: 1 = zero padding (0,1,0,1) instead of (1,1,1,1) (LDM encoder Downsample, taps at +0..+2)
+ *      30 = R > 0 (ABI 11; every gather mode, split-K allowed, plain / statistics / GroupNorm epilogues): the residual has R rows and row
+ *         m >= R reads residual row m - R (M <= 2 R) — an adapter feature shared by the cond | uncond pair as the residual of a convolution;
  *      PLAIN gather only: 12 = R > 0 -> the residual has R rows and row m >= R reads residual row m - R; 13 = R > 0 -> likewise for the A
  *         operand (M <= 2R, no split-K): tensors shared by the cond | uncond pair of a guided step are computed once and wrapped;
  *      PLAIN gather only: 11 = 1 -> hi + lo fp16 output (fp16 out, plain epilogue, ldc >= 2N): out[m, N + n] = fp16(v - float(fp16(v)))
@@ -289,6 +298,16 @@ enum t2v_gather {
  *      i: 0 N, 1 H, 2 W (of the source), 3 channels (= 3), 4 output size along the axis, 5 axis (0 horizontal | 1 vertical),
  *      6 table row length (ksize), 7 output form, 8 ld of the token forms (>= 3);
  *      p: 0 src uint8, 1 dst, 2 coef int32 [i[4]][i[6]], 3 bounds int32 [i[4]][2] = {first, count}, 4 lut fp32 [256] (forms 1 / 2)
+ * DEPTH_TOKENS (ABI 11): out[(f*(H/8) + y/8)*(W/8) + x/8, (y%8)*8 + x%8] = fp16(v(f, y, x)) — nn.PixelUnshuffle(8) of n single-channel frames
+ *      [n, 1, H, W] as channels-last tokens, the A operand of the adapter's conv_in (lvdm/models/modules/adapter.py:93-99).  With i[4] = 1
+ *      v = 2 * (d - min_f) / (max_f - min_f + 1e-7) - 1 with the frame's own minimum / maximum (NaN if any pixel is NaN, as torch.amin / amax), evaluated in fp32 in that operation order
+ *      (ddpm3d.py:1463-1464; a constant frame gives exactly -1); with i[4] = 0 v = d.  One workgroup per frame; the reduction uses wavefront
+ *      shuffles and LDS.  Columns 64 .. i[5]-1 of the output rows are not written.
+ *      i: 0 n frames, 1 H, 2 W (multiples of 8), 3 in dtype, 4 normalise, 5 ld_out (>= 64, multiple of 8);  p: 0 in, 1 out fp16 (16-byte aligned)
+ * AVGPOOL2 (ABI 11): nn.AvgPool2d(2, 2) of n channels-last images: out[(f*Ho + y)*Wo + x, c] = 0.25 * (in[2y, 2x] + in[2y, 2x+1] + in[2y+1, 2x] +
+ *      in[2y+1, 2x+1])[c] in fp32, Ho = H / 2, Wo = W / 2 (a last odd row / column is dropped, as torch does)
+ *      i: 0 n images, 1 H, 2 W, 3 C (% 4 == 0), 4 ld_in, 5 ld of the fp32 output, 6 ld of the fp16 output;
+ *      p: 0 in fp32, 1 out fp32 (optional), 2 out fp16 (optional; the fp16 rounding of the fp32 mean) — at least one
  */
 typedef struct t2v_op {
   int32_t kind;

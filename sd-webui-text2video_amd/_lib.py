@@ -30,7 +30,7 @@ def knob(name: str, default):
 
 
 # ---- mirrors of include/t2v_hip.h (checked against the header by tests/test_abi.py) -------
-ABI_VERSION = 10
+ABI_VERSION = 11
 RELPOS_MAX_FRAMES = 1024            # T2V_RELPOS_MAX_FRAMES: longest clip of RELPOS_ATTN i[17] = 3
 RELPOS_LONG_PADL = 72               # T2V_RELPOS_LONG_PADL: replicated left-edge columns of its packed Ev^T table
 OP_GEMM, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_SOFTMAX = 1, 2, 3, 4, 5
@@ -41,12 +41,15 @@ OP_EMBED_ROWS = 14
 OP_TO_UINT8, OP_ALLGATHER, OP_HALO_EXCHANGE = 15, 16, 17
 OP_RESHARD_ROWS, OP_ALLTOALL, OP_STATS_HALO = 18, 19, 20
 OP_RESAMPLE = 21
+OP_DEPTH_TOKENS, OP_AVGPOOL2 = 22, 23
+ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2     # GEMM i[18]
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_TCONV3, GATHER_CONV3X3_C8 = 0, 1, 2, 3
 EPI_NONE, EPI_GEGLU, EPI_TATTN, EPI_STATS, EPI_GN, EPI_XATTN = 0, 1, 2, 3, 4, 5
 GN_PIECES = 36                  # T2V_GN_PIECES
 F16, F32 = 0, 1
 EXT_SLOTS = 16
 EXT_X, EXT_T, EXT_CTX, EXT_OUT, EXT_XT, EXT_XT_OUT, EXT_NOISE, EXT_EPS = 1, 2, 3, 4, 5, 6, 7, 8
+EXT_ADAPTER = 9                  # T2V_EXT_ADAPTER: adapter feature k at slot 9 + k (up to EXT_SLOTS - 9 features)
 OP_NI, OP_NF, OP_NP = 32, 8, 12
 GN_ROWS_PER_BLOCK = 64           # T2V_GN_ROWS_PER_BLOCK
 SYNC_INTS = 4096                 # T2V_SYNC_INTS

@@ -10,6 +10,9 @@
 //                 (samplers/ddim/gaussian_sampler.py:125-136, 103-108, 199-211, 269-283)
 //   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
 //                 (process_modelscope.py:116-120, 174-178); the last pass can write the VAE encoder's tokens
+//   depth_tokens  entry of the VideoCrafter depth adapter: per-frame min-max normalisation (ddpm3d.py:1463-1464) + PixelUnshuffle(8)
+//                 (adapter.py:93-99) of the depth frames, as the fp16 tokens conv_in reads
+//   avgpool2      the adapter's Downsample(use_conv=False): nn.AvgPool2d(2, 2) on channels-last fp32 tokens
 #include "t2v_kernels.h"
 
 namespace {
@@ -207,6 +210,80 @@ __global__ __launch_bounds__(256) void reshard_rows_kernel(const T* src, T* dst,
     } else {
       *reinterpret_cast<f16x8*>(dst + rd * ld_dst + c) = *reinterpret_cast<const f16x8*>(src + rs * ld_src + c);
     }
+  }
+}
+
+// Depth frames [n, 1, H, W] -> PixelUnshuffle(8) tokens [n * (H/8) * (W/8), 64] (channel = (y % 8) * 8 + x % 8), fp16.  One workgroup per
+// frame.  NORM: v = 2 * (d - min) / (max - min + 1e-7) - 1 with the frame's own extremes, every operation rounded to fp32 on its own (no
+// contraction: the reference evaluates the expression with separate torch ops) — a constant frame maps to exactly -1.  The extremes are
+// reduced with wavefront shuffles, then across the workgroup's four waves through LDS; no atomics.  A NaN pixel makes both extremes NaN,
+// as torch.amin / amax do (fminf / fmaxf alone would drop it).  A thread converts the 8 pixels of one row of a token and writes them as
+// ONE 16-byte store (they are 8 consecutive channels).
+template <typename TIN, bool NORM>
+__global__ __launch_bounds__(256) void depth_tokens_kernel(const TIN* in, f16* out, int H, int W, int ld) {
+  const int hw = H * W, w8 = W >> 3;
+  const TIN* src = in + (size_t)blockIdx.x * hw;
+  f16* dst = out + (size_t)blockIdx.x * (hw >> 6) * ld;
+  float mn = 0.f, den = 1.f;
+  if (NORM) {
+    float lo = (float)src[0], hi = lo;
+    int bad = 0;
+    for (int idx = threadIdx.x; idx < hw; idx += 256) {
+      const float d = (float)src[idx];
+      bad |= d != d;
+      lo = fminf(lo, d);
+      hi = fmaxf(hi, d);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lo = fminf(lo, __shfl_xor(lo, o));
+      hi = fmaxf(hi, __shfl_xor(hi, o));
+      bad |= __shfl_xor(bad, o);
+    }
+    __shared__ float s_lo[4], s_hi[4];
+    __shared__ int s_bad[4];
+    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; s_bad[threadIdx.x >> 6] = bad; }
+    __syncthreads();
+    lo = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
+    hi = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
+    if (s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) lo = hi = __builtin_nanf("");
+    mn = lo;
+    den = __fadd_rn(__fsub_rn(hi, lo), 1e-7f);
+  }
+  for (int u = threadIdx.x; u < (hw >> 3); u += 256) {        // unit = 8 consecutive pixels of one image row
+    const int y = u / w8, gx = u - y * w8;
+    const TIN* s8 = src + (size_t)y * W + gx * 8;
+    f16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float v = (float)s8[e];
+      if (NORM) v = __fsub_rn(__fdiv_rn(__fmul_rn(2.f, __fsub_rn(v, mn)), den), 1.f);
+      o[e] = (f16)v;
+    }
+    *reinterpret_cast<f16x8*>(dst + (size_t)((y >> 3) * w8 + gx) * ld + ((y & 7) << 3)) = o;      // ld % 8 == 0 (validated): 16-byte aligned
+  }
+}
+
+// nn.AvgPool2d(2, 2) of channels-last fp32 tokens: one thread per (output token, 4 channels); the mean is formed in fp32 and only then
+// rounded for the fp16 output (the operand of the convolution that follows)
+__global__ __launch_bounds__(256) void avgpool2_kernel(const float* in, float* out32, f16* out16, int n, int H, int W, int C, int ld_in,
+                                                       int ld32, int ld16) {
+  const int Ho = H >> 1, Wo = W >> 1, cv = C >> 2;
+  const long total = (long)n * Ho * Wo * cv;
+  for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) {
+    const long tok = u / cv;
+    const int c = (int)(u - tok * cv) * 4;
+    const int x = (int)(tok % Wo);
+    const long r = tok / Wo;
+    const int y = (int)(r % Ho);
+    const long f = r / Ho;
+    const float* s0 = in + ((f * H + 2 * y) * W + 2 * x) * ld_in + c;
+    const float* s1 = s0 + (size_t)W * ld_in;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(s0), b = *reinterpret_cast<const f32x4*>(s0 + ld_in);
+    const f32x4 d = *reinterpret_cast<const f32x4*>(s1), e = *reinterpret_cast<const f32x4*>(s1 + ld_in);
+    const f32x4 v = ((a + b) + (d + e)) * 0.25f;
+    if (out32) *reinterpret_cast<f32x4*>(out32 + tok * ld32 + c) = v;
+    if (out16) *reinterpret_cast<f16x4*>(out16 + tok * ld16 + c) = f16x4{(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
   }
 }
 
@@ -478,6 +555,31 @@ hipError_t t2v_launch_resample(const t2v_op& op, hipStream_t s) {
     else if (form == 1) hipLaunchKernelGGL(resample_v_kernel<1>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
     else hipLaunchKernelGGL(resample_v_kernel<2>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
   }
+  return hipGetLastError();
+}
+
+hipError_t t2v_launch_depth_tokens(const t2v_op& op, hipStream_t s) {
+  // (shape and pointers were checked by the executor's validation)
+  const int n = op.i[0], H = op.i[1], W = op.i[2], ld = op.i[5];
+  const bool f32 = op.i[3] == T2V_F32, norm = op.i[4] != 0;
+  f16* out = reinterpret_cast<f16*>(op.p[1]);
+  if (f32) {
+    const float* in = reinterpret_cast<const float*>(op.p[0]);
+    if (norm) hipLaunchKernelGGL((depth_tokens_kernel<float, true>), dim3(n), dim3(256), 0, s, in, out, H, W, ld);
+    else hipLaunchKernelGGL((depth_tokens_kernel<float, false>), dim3(n), dim3(256), 0, s, in, out, H, W, ld);
+  } else {
+    const f16* in = reinterpret_cast<const f16*>(op.p[0]);
+    if (norm) hipLaunchKernelGGL((depth_tokens_kernel<f16, true>), dim3(n), dim3(256), 0, s, in, out, H, W, ld);
+    else hipLaunchKernelGGL((depth_tokens_kernel<f16, false>), dim3(n), dim3(256), 0, s, in, out, H, W, ld);
+  }
+  return hipGetLastError();
+}
+
+hipError_t t2v_launch_avgpool2(const t2v_op& op, hipStream_t s) {
+  const int n = op.i[0], H = op.i[1], W = op.i[2], C = op.i[3];
+  const int g = grid_for((long)n * (H / 2) * (W / 2) * (C / 4));
+  hipLaunchKernelGGL(avgpool2_kernel, dim3(g), dim3(256), 0, s, reinterpret_cast<const float*>(op.p[0]), reinterpret_cast<float*>(op.p[1]),
+                     reinterpret_cast<f16*>(op.p[2]), n, H, W, C, op.i[4], op.i[5], op.i[6]);
   return hipGetLastError();
 }
 

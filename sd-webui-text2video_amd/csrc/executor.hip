@@ -66,6 +66,12 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.i[16] == T2V_EPI_STATS && (op.p[7] == 0 || op.i[19] > 1 || (g == T2V_GATHER_PLAIN && op.i[8] == 1)))
         return bad("column statistics (T2V_EPI_STATS): strips pointer p[7], no split-K, no fused LayerNorm");
       if (op.i[16] < 0 || op.i[16] > T2V_EPI_XATTN) return bad("unknown epilogue");
+      if (op.i[18] < 0 || op.i[18] > 2) return bad("unknown activation (0 none, 1 SiLU, 2 ReLU)");
+      if (op.i[30] != 0) {       // residual row wrap for every gather mode (ABI 11)
+        if (op.i[30] < 0 || M > 2 * op.i[30] || op.p[4] == 0) return bad("residual row wrap i[30]: positive, M <= 2 * wrap, and a residual");
+        if (op.i[16] == T2V_EPI_GEGLU || op.i[16] == T2V_EPI_TATTN || op.i[16] == T2V_EPI_XATTN || (g == T2V_GATHER_PLAIN && (op.i[12] != 0 || op.i[8] != 0)))
+          return bad("residual row wrap i[30]: plain / statistics / GroupNorm epilogues only, not beside i[12] or a fused LayerNorm");
+      }
       if (op.i[16] == T2V_EPI_XATTN) {
         const int tile = op.i[22];
         if (g != T2V_GATHER_PLAIN || N % 64 != 0 || K % 64 != 0 || op.i[17] != T2V_F16 || op.i[19] > 1 || op.i[18] != 0 || op.i[8] != 0 || op.i[11] == 1)
@@ -253,6 +259,21 @@ int validate_op(const t2v_op& op, int idx) {
       if ((long)op.i[0] * (axis == 0 ? op.i[1] : out) * tiles > 0xffffffL) return bad("resample: too many rows for one launch (rows x tiles of 256 units <= 2^24 - 1)");
       return 0;
     }
+    case T2V_OP_DEPTH_TOKENS:
+      if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[2] <= 0 || op.i[1] % 8 != 0 || op.i[2] % 8 != 0) return bad("depth tokens: frames > 0, H and W positive multiples of 8");
+      if ((long)op.i[1] * op.i[2] > (1L << 28)) return bad("depth tokens: frame too large");
+      if ((op.i[3] != T2V_F16 && op.i[3] != T2V_F32) || (op.i[4] != 0 && op.i[4] != 1) || op.i[5] < 64 || op.i[5] % 8 != 0)
+        return bad("depth tokens: input dtype, normalise flag (0 | 1), ld_out >= 64 and a multiple of 8");
+      if (op.p[0] == 0 || op.p[1] == 0) return bad("null depth-token pointer");
+      if (op.p[1] >= T2V_EXT_SLOTS && op.p[1] % 16 != 0) return bad("depth tokens: the output must be 16-byte aligned");
+      return 0;
+    case T2V_OP_AVGPOOL2:
+      if (op.i[0] <= 0 || op.i[1] < 2 || op.i[2] < 2 || op.i[3] <= 0 || op.i[3] % 4 != 0) return bad("average pooling: images > 0, H and W >= 2, C % 4 == 0");
+      if (op.i[4] < op.i[3] || op.i[4] % 4 != 0) return bad("average pooling: ld_in >= C and a multiple of 4");
+      if (op.p[0] == 0 || (op.p[1] == 0 && op.p[2] == 0)) return bad("average pooling: an input and at least one output");
+      if ((op.p[1] != 0 && (op.i[5] < op.i[3] || op.i[5] % 4 != 0)) || (op.p[2] != 0 && (op.i[6] < op.i[3] || op.i[6] % 4 != 0)))
+        return bad("average pooling: output leading dimensions >= C and multiples of 4");
+      return 0;
     case T2V_OP_ALLGATHER:
       if (op.i[2] < 1 || op.i[3] < 0 || op.i[3] >= op.i[2] || op.p[0] == 0) return bad("bad all-gather record");
       return 0;
@@ -318,6 +339,7 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
       p.halo = op.i[23];
       p.out_lo = (p.gather == T2V_GATHER_PLAIN && op.i[11] == 1) ? 1 : 0;
       if (p.gather == T2V_GATHER_PLAIN && op.i[16] != T2V_EPI_TATTN) { p.res_wrap = op.i[12]; p.a_wrap = op.i[13]; }
+      if (op.i[30] > 0) p.res_wrap = op.i[30];                    // (validated: not beside i[12])
       const int tile = op.i[22];
       if (p.epi == T2V_EPI_TATTN) {                              // fused QKV projection + temporal attention (tile 10)
         p.F = op.i[8]; p.HW = op.i[9]; p.tpix = op.i[10];
@@ -370,6 +392,8 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
     case T2V_OP_TO_UINT8: return t2v_launch_to_uint8(op, s);
     case T2V_OP_RESAMPLE: return t2v_launch_resample(op, s);
     case T2V_OP_RESHARD_ROWS: return t2v_launch_reshard_rows(op, s);
+    case T2V_OP_DEPTH_TOKENS: return t2v_launch_depth_tokens(op, s);
+    case T2V_OP_AVGPOOL2: return t2v_launch_avgpool2(op, s);
     case T2V_OP_MEMSET: {
       const size_t bytes = (size_t)(uint32_t)op.i[0] | ((size_t)(uint32_t)op.i[1] << 32);
       return hipMemsetAsync(reinterpret_cast<void*>(op.p[0]), 0, bytes, s);

@@ -57,9 +57,12 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, int m, int n
   }
   if (p.act == 1) {
     v0 = t2v_silu(v0); v1 = t2v_silu(v1); v2 = t2v_silu(v2); v3 = t2v_silu(v3);
+  } else if (p.act == 2) {      // ReLU (the depth adapter's ResnetBlock)
+    v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f);
   }
   if (p.res) {
-    const f32x4 r = *reinterpret_cast<const f32x4*>(p.res + (size_t)m * p.ldr + n);
+    const int mr = (p.res_wrap && m >= p.res_wrap) ? m - p.res_wrap : m;      // a residual shared by the cond | uncond pair: rows wrap once
+    const f32x4 r = *reinterpret_cast<const f32x4*>(p.res + (size_t)mr * p.ldr + n);
     v0 += r[0]; v1 += r[1]; v2 += r[2]; v3 += r[3];
   }
   if (p.out_f32) {

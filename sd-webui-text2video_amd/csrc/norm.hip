@@ -667,7 +667,7 @@ __global__ __launch_bounds__(GNC_THREADS) void splitk_gn_kernel(const GemmParams
         for (int z = 1; z < p.splitk; ++z) a += Load8<float>::ld(col + (size_t)z * zs);      // split order, as the reduction kernel
         a += cb;
         if (p.rowbias) a += Load8<float>::ld(p.rowbias + (m / p.rows_per_batch) * p.ldrb + c8);
-        if (p.res) a += Load8<float>::ld(p.res + m * p.ldr + c8);
+        if (p.res) a += Load8<float>::ld(p.res + ((p.res_wrap && m >= (size_t)p.res_wrap) ? m - (size_t)p.res_wrap : m) * p.ldr + c8);
         if (p.gn_store_out) {
           if (p.out_f32) {
             float* dst = reinterpret_cast<float*>(p.out) + m * p.ldc + c8;

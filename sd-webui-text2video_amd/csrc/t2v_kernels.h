@@ -55,7 +55,7 @@ struct GemmParams {
   // the 32-row strip of out[m, n], stats[m / 32][1][n] = sum of squares — fp32 [ceil(M / 32)][2][N].  The GroupNorm then needs no
   // statistics pass over the tensor (and no grid barrier): a small fold of the strips + one apply pass (norm.hip, phase 3).
   float* stats;
-  // Row wrap (PLAIN gather, M <= 2 * wrap, no split-K): operand row m >= a_wrap reads A row m - a_wrap; residual row m >= res_wrap reads
+  // Row wrap (M <= 2 * wrap; a_wrap: PLAIN gather, no split-K; res_wrap: any gather — t2v_op i[12] / i[30]): operand row m >= a_wrap reads A row m - a_wrap; residual row m >= res_wrap reads
   // residual row m - res_wrap.  The cond | uncond pair of a guided step shares every tensor up to the first text cross-attention
   // (same x_t, same t): those are computed ONCE (one sample's rows) and the first per-sample GEMMs read them through the wrap.
   int a_wrap, res_wrap;
@@ -241,6 +241,8 @@ hipError_t t2v_launch_ncthw_to_cl(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_cl_to_ncthw(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_to_uint8(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_resample(const t2v_op& op, hipStream_t s);
+hipError_t t2v_launch_depth_tokens(const t2v_op& op, hipStream_t s);
+hipError_t t2v_launch_avgpool2(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_reshard_rows(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_time_embed(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_copy2d(const t2v_op& op, hipStream_t s);
@@ -326,6 +328,7 @@ __device__ __forceinline__ void t2v_epilogue_rows(const GemmParams& p, const f32
           if (p.bias && p.bias_m) { const float bm = p.bias[m]; v[0] += bm; v[1] += bm; v[2] += bm; v[3] += bm; }
           if (p.rowbias) v += *reinterpret_cast<const f32x4*>(p.rowbias + (size_t)(m / p.rows_per_batch) * p.ldrb + n);
           if (p.act == 1) { v[0] = t2v_silu(v[0]); v[1] = t2v_silu(v[1]); v[2] = t2v_silu(v[2]); v[3] = t2v_silu(v[3]); }
+          else if (p.act == 2) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
           if (has_res) v += rcur[i];
           if (p.out_f32) {
             t2v_st_stream(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n, v);
@@ -408,7 +411,8 @@ __device__ __forceinline__ void t2v_epilogue_rows(const GemmParams& p, const f32
         if (p.bias && p.bias_m) { const float bm = p.bias[m]; v[0] += bm; v[1] += bm; v[2] += bm; v[3] += bm; }
         if (p.rowbias) v += *reinterpret_cast<const f32x4*>(p.rowbias + (size_t)(m / p.rows_per_batch) * p.ldrb + n);
         if (p.act == 1) { v[0] = t2v_silu(v[0]); v[1] = t2v_silu(v[1]); v[2] = t2v_silu(v[2]); v[3] = t2v_silu(v[3]); }
-        if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + (size_t)m * p.ldr + n);
+        else if (p.act == 2) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+        if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + (size_t)((p.res_wrap && m >= p.res_wrap) ? m - p.res_wrap : m) * p.ldr + n);
         if (p.out_f32) {
           t2v_st_stream(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n, v);
         } else {
@@ -736,6 +740,7 @@ __device__ __forceinline__ void t2v_epilogue_rows_gn(const GemmParams& p, f32x16
           if (p.bias && p.bias_m) { const float bm = p.bias[m]; v[0] += bm; v[1] += bm; v[2] += bm; v[3] += bm; }
           if (p.rowbias) v += *reinterpret_cast<const f32x4*>(p.rowbias + (size_t)(m / p.rows_per_batch) * p.ldrb + n);
           if (p.act == 1) { v[0] = t2v_silu(v[0]); v[1] = t2v_silu(v[1]); v[2] = t2v_silu(v[2]); v[3] = t2v_silu(v[3]); }
+          else if (p.act == 2) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
           if (has_res) v += r[i];
         } else {
           v = f32x4{0.f, 0.f, 0.f, 0.f};

@@ -499,7 +499,12 @@ class Program:
         op.p[3] = rowbias.ref if rowbias is not None else NULL
         op.p[4] = residual.ref if residual is not None else NULL
         op.p[5] = out.ref
-        if a_wrap or res_wrap:
+        if res_wrap and gather != L.GATHER_PLAIN:
+            # the residual wrap of the convolution gathers (i[30], ABI 11; i[12] is their upsample flag): an adapter feature shared by the
+            # cond | uncond pair as the residual of a Downsample convolution; the split-K reductions honour it too
+            assert not a_wrap and epi == L.EPI_NONE and a_lo is None and ln is None and M <= 2 * res_wrap and residual is not None
+            I[30] = res_wrap
+        elif a_wrap or res_wrap:
             assert gather == L.GATHER_PLAIN and epi == L.EPI_NONE and a_lo is None
             assert (not a_wrap or (M <= 2 * a_wrap and a.rows >= a_wrap)) and (not res_wrap or (M <= 2 * res_wrap and residual is not None))
             I[12], I[13] = res_wrap, a_wrap
@@ -1099,6 +1104,32 @@ class Program:
         if mid is not None:
             self.free(mid)        # stream order: whatever reuses the block is launched after the last pass
         return ops
+
+    def depth_tokens(self, name: str, src: Ref, src_dtype: str, out: Buf, *, n: int, H: int, W: int, normalise: bool) -> Op:
+        """T2V_OP_DEPTH_TOKENS: depth frames src [n, 1, H, W] -> nn.PixelUnshuffle(8) as channels-last fp16 tokens out [n * H/8 * W/8, 64]
+        (channel = dy * 8 + dx), the A operand of the adapter's conv_in.  normalise: each frame is first mapped to
+        2 * (d - min) / (max - min + 1e-7) - 1 with its own extremes (ddpm3d.py:1463-1464), inside the same launch."""
+        assert H % 8 == 0 and W % 8 == 0 and out.dtype == "f16" and out.cols == 64 and out.rows == n * (H // 8) * (W // 8)
+        op = Op(L.OP_DEPTH_TOKENS, name)
+        op.i[0:6] = [n, H, W, _DT[src_dtype], int(bool(normalise)), out.ld]
+        op.p[0:2] = [src, out.ref]
+        op.out = out
+        return self._emit(op)
+
+    def avgpool2(self, name: str, x: Buf, *, n: int, H: int, W: int, out32: Optional[Buf] = None, out16: Optional[Buf] = None) -> Op:
+        """T2V_OP_AVGPOOL2: nn.AvgPool2d(2, 2) of n channels-last fp32 images x [n * H * W, C] -> [n * (H // 2) * (W // 2), C]; the mean is
+        formed in fp32 and written as fp32 (`out32`: the residual stream) and / or fp16 (`out16`: the next convolution's operand)."""
+        rows = n * (H // 2) * (W // 2)
+        assert x.dtype == "f32" and x.rows == n * H * W and x.cols % 4 == 0 and (out32 is not None or out16 is not None)
+        op = Op(L.OP_AVGPOOL2, name)
+        op.i[0:5] = [n, H, W, x.cols, x.ld]
+        op.p[0] = x.ref
+        for k, (o, dt) in enumerate(((out32, "f32"), (out16, "f16"))):
+            if o is not None:
+                assert o.dtype == dt and o.rows == rows and o.cols == x.cols
+                op.i[5 + k], op.p[1 + k] = o.ld, o.ref
+        op.out, op.out2 = (out32, out16) if out32 is not None else (out16, None)
+        return self._emit(op)
 
     def time_embed(self, name: str, t: Ref, freqs: Ref, out: Buf) -> Op:
         op = Op(L.OP_TIME_EMBED, name)

@@ -433,9 +433,11 @@ class UNetSD(nn.Module):
 
     # ---- forward --------------------------------------------------------------------------
     def forward(self, x, t, y, fps=None, video_mask=None, focus_present_mask=None, prob_focus_present=0.0,
-                mask_last_frame_num=0):
+                mask_last_frame_num=0, *, adapter=None):
         """eps = model(x[b,4,F,h,w], t[b], y[b,L,ctx])  — reference t2v_model.py:386-459.
-        Output dtype follows the reference under autocast: fp16 for fp16 weights, else x.dtype."""
+        Output dtype follows the reference under autocast: fp16 for fp16 weights, else x.dtype.
+        adapter (videocrafter.UNetModel only): (samples, {ext slot: device pointer}) of the adapter features of this call — part of the
+        program key, handed to `_compile`, and added to the external pointers of the run."""
         # one-shot hint of the samplers ("every sample of this call has the same timestep"): consumed before anything can raise, so that
         # a failed call never leaves it set for a later call with genuinely different timesteps (ADVICE r05)
         hint_single, self.single_timestep = bool(self.single_timestep), False
@@ -468,13 +470,13 @@ class UNetSD(nn.Module):
         if not single and not tf.is_cuda:
             single = bool((tf == tf.reshape(-1)[0]).all())
         self._share_now = bool(getattr(self, "share_cfg_prefix", False)) and single
-        key = self._program_key(B, F, H, W, y.shape[1], x.dtype, y.dtype, out_dtype, shard, Bx)
+        key = self._program_key(B, F, H, W, y.shape[1], x.dtype, y.dtype, out_dtype, shard, Bx) + ((("adapter", adapter[0]),) if adapter else ())
         comp = self._programs.get(key)
         if comp is not None and comp.prog.gn_epilogue and L.exchange_disabled():
             comp = None        # an asynchronous fault was reported: lower again, without the norms fused into GEMM epilogues (_lib.exchange_disabled)
         if comp is None:
             comp = self._compile(B, F, H, W, y.shape[1], _dt(x.dtype), _dt(out_dtype), _dt(y.dtype), shard=shard,
-                                 x_batch=Bx if Bx != B else 0)
+                                 x_batch=Bx if Bx != B else 0, **({"adapter": adapter[0]} if adapter else {}))
             self._programs[key] = comp
             self._evict_programs(keep=key)
         if self._packed is None or self._packed_device != x.device or self.auto_refresh:
@@ -483,6 +485,8 @@ class UNetSD(nn.Module):
         comp.ensure_bound(self._packed, x.device, t_shard=self.t_shard if shard is not None else None)
         out = torch.empty((B, self.out_dim, F, H, W), device=x.device, dtype=out_dtype)
         ext = {L.EXT_X: x.data_ptr(), L.EXT_T: tf.data_ptr(), L.EXT_CTX: y.data_ptr(), L.EXT_OUT: out.data_ptr()}
+        if adapter:
+            ext.update(adapter[1])                                # T2V_EXT_ADAPTER + k
         # step-invariant prologue: skipped only when the caller passed the token of the previous run of THIS binding
         token, self.context_token = self.context_token, None
         reuse = token is not None and comp.ctx_token == token and comp.ctx_bound is comp.bound

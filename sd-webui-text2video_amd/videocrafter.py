@@ -226,15 +226,68 @@ class UNetModel(UNetSD):
 
     # ---- forward (openaimodel3d.py:632-670) ------------------------------------------------------
     def forward(self, x, timesteps=None, time_emb_replace=None, context=None, features_adapter=None, y=None, **kwargs):
-        if time_emb_replace is not None or features_adapter is not None or y is not None:
-            raise NotImplementedError("time_emb_replace / adapter features / class labels are not on the hot path")
-        return UNetSD.forward(self, x, timesteps, context)
+        """features_adapter (openaimodel3d.py:654-663): one [b, c, t, h, w] device tensor (fp16 / fp32) per input block k with
+        (k + 1) % 3 == 0, added to that block's result — the running activation and the skip connection alike.  b is the number of
+        samples of `x`; when the context holds more samples (the [cond | uncond] batch of a guided step on one x_t) every role
+        receives the same feature.  The list is converted to the program's layout once per distinct list (identity and `_version` of
+        its tensors, as the context K/V cache is keyed); afterwards a step costs only the adds."""
+        if time_emb_replace is not None or y is not None:
+            raise NotImplementedError("time_emb_replace / class labels are not on the hot path")
+        if features_adapter is None:
+            return UNetSD.forward(self, x, timesteps, context)
+        if self.t_shard is not None and self.t_shard.size > 1:
+            raise L.T2VError("T-sharded forward with adapter features: sharding the features along T is not built")
+        if context.shape[0] not in (x.shape[0], 2 * x.shape[0]):
+            raise ValueError("adapter features: the context holds one sample per sample of x, or the [cond | uncond] pair of each")
+        toks = self._adapter_tokens(list(features_adapter), x)
+        return UNetSD.forward(self, x, timesteps, context,
+                              adapter=(int(x.shape[0]), {L.EXT_ADAPTER + k: t.data_ptr() for k, t in enumerate(toks)}))
 
-    def _compile(self, B, F, H, W, Lctx, x_dt, out_dt, ctx_dt="f32", shard=None, x_batch=0):
+    def adapter_sites(self, H: int, W: int) -> List[tuple]:
+        """(channels, h, w) of the result of every input block that takes an adapter feature, for an H x W latent: block k with
+        (k + 1) % 3 == 0 (openaimodel3d.py:657) — the end of each level for the released two-ResBlock UNet."""
+        sites, h, w = [], H, W
+        for k, (_, parts) in enumerate(self._layout[0]):
+            for kind, _, _ in parts:
+                if kind == "down":
+                    h, w = (h + 1) // 2, (w + 1) // 2
+            if (k + 1) % 3 == 0:
+                sites.append((parts[-1][2], h, w))
+        return sites
+
+    def _adapter_tokens(self, feats: list, x) -> List[torch.Tensor]:
+        """The features as channels-last fp32 tokens [(b t h w), c] (what the injection reads), cached on the list's identity."""
+        Bx, _, F, H, W = x.shape
+        sites = self.adapter_sites(H, W)
+        if len(feats) != len(sites):
+            raise AssertionError("Mismatch features adapter")
+        if len(sites) > L.EXT_SLOTS - L.EXT_ADAPTER:
+            raise NotImplementedError(f"{len(sites)} adapter sites (at most {L.EXT_SLOTS - L.EXT_ADAPTER})")
+        for k, (f, (c, h, w)) in enumerate(zip(feats, sites)):          # checked on every call: the same list may meet another x
+            if not torch.is_tensor(f) or tuple(f.shape) != (Bx, c, F, h, w):
+                raise ValueError(f"adapter feature {k}: expected shape {(Bx, c, F, h, w)} for input block {3 * k + 2}, "
+                                 f"got {tuple(f.shape) if torch.is_tensor(f) else type(f).__name__}")
+            if f.device != x.device or f.dtype not in (torch.float16, torch.float32):
+                raise ValueError(f"adapter feature {k}: an fp16 / fp32 tensor on {x.device} is required (got {f.dtype} on {f.device})")
+        key = tuple((id(f), f._version, f.data_ptr(), tuple(f.shape), tuple(f.stride()), f.dtype, f.device) for f in feats)
+        cache = getattr(self, "_adapter_cache", None)
+        if cache is not None and cache[0] == key:
+            return cache[2]
+        toks = []
+        for k, (f, (c, h, w)) in enumerate(zip(feats, sites)):
+            # 'b c t h w -> (b t h w) c'; what Adapter.forward / get_adapter_features return is already stored that way: no copy
+            toks.append(f.permute(0, 2, 3, 4, 1).to(torch.float32).contiguous().reshape(Bx * F * h * w, c))
+        self._adapter_cache = (key, feats, toks)          # (`feats` kept alive: an id() is only unique among live objects)
+        self.adapter_conversions = getattr(self, "adapter_conversions", 0) + 1
+        return toks
+
+    def _compile(self, B, F, H, W, Lctx, x_dt, out_dt, ctx_dt="f32", shard=None, x_batch=0, adapter=None):
         """shard (program.TShardSpec): the clip's frames are split over a T group.  Every GroupNorm32 of this UNet spans
         all frames (all-gather of statistics partials) and the temporal attentions gather K/V along T; the (1,3,3)
-        convolutions, spatial / text attention and feed-forward are frame-local (no halo exchange: kernel_size_t = 1)."""
-        low = _LvdmLowering(self, B, F, H, W, Lctx, x_dt, out_dt, ctx_dt, keep_taps=self.debug_taps, shard=shard, x_batch=x_batch)
+        convolutions, spatial / text attention and feed-forward are frame-local (no halo exchange: kernel_size_t = 1).
+        adapter: samples of the adapter features (None / 0: a program without injection sites)."""
+        low = _LvdmLowering(self, B, F, H, W, Lctx, x_dt, out_dt, ctx_dt, keep_taps=self.debug_taps, shard=shard, x_batch=x_batch,
+                            adapter=adapter or 0)
         return _Compiled(low.build(), low.packer)
 
 
@@ -242,6 +295,13 @@ class UNetModel(UNetSD):
 # lowering
 # ------------------------------------------------------------------------------------------
 class _LvdmLowering(_Lowering):
+    def __init__(self, *args, adapter: int = 0, **kwargs):
+        """adapter: samples of the adapter features this program adds at its injection sites (0: none — the op list is then exactly
+        the one of a lowering that knows nothing of adapters)."""
+        super().__init__(*args, **kwargs)
+        self.adapter_fb = int(adapter)
+        assert not self.adapter_fb or self.shard is None, "adapter features are not sharded along T"
+
     def w_conv133(self, key, cin_pad=0) -> Ref:
         return Ref("weight", 0, self.packer.add(key + ":c133", "f16", lambda sd, k=key, c=cin_pad:
                                                 pk.pad_rows(pk.conv3x3(sd[k + ".weight"][:, :, 0], c))))
@@ -271,21 +331,31 @@ class _LvdmLowering(_Lowering):
         return Ref("weight", 0, self.packer.add(key + ":c133hl", "f16", lambda sd, k=key: pk.pad_rows(pk.conv3x3(torch.cat([sd[k + ".weight"][:, :, 0]] * 2, dim=1)))))
 
     def conv133(self, name, a: Buf, key, cout, h, w, *, stride=1, up=0, out_dtype="f32", rowbias=None, residual=None, cin=None,
-                dest: Optional[Buf] = None, dup_c8: bool = False, stats: Optional[Buf] = None, hilo: bool = False) -> Buf:
+                dest: Optional[Buf] = None, dup_c8: bool = False, stats: Optional[Buf] = None, hilo: bool = False, res_wrap: int = 0) -> Buf:
         cin = a.cols if cin is None else cin
         ho, wo = (h * 2, w * 2) if up else ((h + 1) // 2 if stride == 2 else h, (w + 1) // 2 if stride == 2 else w)
         n = (cout + 3) // 4 * 4
         out = self._dest(dest, self.Bc * self.F * ho * wo, n, out_dtype)
+        kw = dict(res_wrap=res_wrap) if res_wrap else {}
         gather = L.GATHER_CONV3X3_C8 if cin == 8 else L.GATHER_CONV3X3
         wref = self.w_conv133_hilo(key) if hilo else (self.w_conv133_dup(key) if dup_c8 else self.w_conv133(key, 8 if cin == 8 else 0))
         op = self.P.gemm(name, a, wref, n, 9 * cin, out, bias=self.vec(key + ".bias"),
                          gather=gather, conv=dict(Hin=h, Win=w, Cin=cin, stride=stride, up=up, Hout=ho, Wout=wo),
                          rowbias=rowbias, rows_per_batch=self.F * ho * wo if rowbias is not None else 0, residual=residual, stats=stats,
-                         k_alg=9 * cin // 2 if hilo else None)
+                         k_alg=9 * cin // 2 if hilo else None, **kw)
         self.last_stats = stats if (stats is not None and op.meta.get("stats")) else None
         return out
 
-    def res_block(self, prefix, x: Buf, cin, cout, h, w, dest: Optional[Buf] = None) -> Buf:
+    def plus_feature(self, name, res: Buf, feat: Buf) -> Buf:
+        """res + adapter feature as a new fp32 buffer (ONE launch: T2V_OP_RESHARD_ROWS with a zero source stride — the feature's rows repeat
+        for every role of a [cond | uncond] batch).  It becomes the residual of the block's last GEMM, so the block's result, written in
+        place into the concat buffer, already holds the feature for both of its consumers."""
+        assert res.dtype == "f32" and res.cols == feat.cols and res.rows % feat.rows == 0
+        out = self.P.alloc(res.rows, res.cols, "f32")
+        self.P.reshard_rows(name, feat, out, rows=res.rows, chunk=feat.rows, s_src=0, s_dst=feat.rows, residual=res)
+        return out
+
+    def res_block(self, prefix, x: Buf, cin, cout, h, w, dest: Optional[Buf] = None, inject: Optional[Buf] = None) -> Buf:
         """ResBlock._forward (openaimodel3d.py:244-271): GroupNorm32 statistics span all frames of a sample."""
         P = self.P
         a = self.gn(prefix + ".in_layers.0", x, prefix + ".in_layers.0", per_frame=False, eps=1e-5, silu=True)
@@ -311,13 +381,18 @@ class _LvdmLowering(_Lowering):
             P.free(x16)
         else:
             skip = x
+        if inject is not None:
+            with_feat = self.plus_feature(prefix + ".adapter", skip, inject)
+            if skip is not x:
+                P.free(skip)
+            skip = with_feat
         out = self.conv133(prefix + ".out_layers.3", b, prefix + ".out_layers.3", cout, h, w, residual=skip, dest=dest)
         P.free(b)
         if skip is not x:
             P.free(skip)
         return out
 
-    def st_transformer(self, prefix, x: Buf, c, h, w, dest: Optional[Buf] = None) -> Buf:
+    def st_transformer(self, prefix, x: Buf, c, h, w, dest: Optional[Buf] = None, inject: Optional[Buf] = None) -> Buf:
         """SpatialTemporalTransformer.forward + BasicTransformerBlockST._forward (attention_temporal.py:301-335,
         386-399): s-self, t-self (rel-pos), s-cross (text), t-self (rel-pos), GEGLU feed-forward."""
         P, net, B, F, hw = self.P, self.net, self.Bc, self.F, h * w
@@ -452,9 +527,15 @@ class _LvdmLowering(_Lowering):
             P.gemm(f"{tb}.ff.net.2", g, self.w_linear(f"{tb}.ff.net.2"), c, 4 * c, x4, bias=self.vec(f"{tb}.ff.net.2.bias"), residual=cur)
         P.free(g, cur)
         out = self._dest(dest, M, c, "f32")
+        res = x
+        if inject is not None:
+            assert x.rows == M, "an adapter site inside the shared cond | uncond prefix must end in a convolution"
+            res = self.plus_feature(prefix + ".adapter", x, inject)
         P.gemm(prefix + ".proj_out", x4, self.w_proj(prefix + ".proj_out", x4.cols // c), c, x4.cols, out, bias=self.vec(prefix + ".proj_out.bias"),
-               residual=x, k_alg=c, res_wrap=x.rows if x.rows != M else 0)
+               residual=res, k_alg=c, res_wrap=x.rows if x.rows != M else 0)
         P.free(x4)
+        if res is not x:
+            P.free(res)
         return out
 
     def build(self) -> Program:
@@ -514,31 +595,37 @@ class _LvdmLowering(_Lowering):
         P.ncthw_to_cl("x.to_tokens", Ref("ext", L.EXT_X), self.x_dt, xin, B=self.Bc, C=net.in_dim, F=F, HW=h * w,
                       src_batch=self.x_batch if self.x_batch != self.Bc else 0, lo_in_pad=self.stem_dup)
 
-        def run_parts(prefix, parts, x, h, w, dest=None):
+        def run_parts(prefix, parts, x, h, w, dest=None, inject=None):
+            """inject: the adapter feature added to this block's result (a residual operand of its last GEMM — the result lands in
+            the concat buffer with the feature in it: openaimodel3d.py:657-660 adds it before `hs.append`)."""
             for j, (kind, cin, cout) in enumerate(parts):
                 p = f"{prefix}.{j}"
                 d = dest if j == len(parts) - 1 else None
+                inj = inject if j == len(parts) - 1 else None
+                # a convolution has no residual of its own: the feature IS its residual (no extra launch), wrapped over the batch's roles
+                conv_res = dict(residual=inj, res_wrap=inj.rows if self.Bc > self.adapter_fb else 0) \
+                    if (inj is not None and kind in ("stem", "down")) else {}
                 spread = d if (self.sharing and d is not None and kind != "st") else None      # shared cond | uncond prefix: unet.py run_parts
                 if spread is not None:
                     d = None
                 if kind == "stem":
-                    y = self.conv133(p, x, p, cout, h, w, cin=8, dest=d, dup_c8=self.stem_dup)
+                    y = self.conv133(p, x, p, cout, h, w, cin=8, dest=d, dup_c8=self.stem_dup, **conv_res)
                 elif kind == "res":
-                    y = self.res_block(p, x, cin, cout, h, w, dest=d)
+                    y = self.res_block(p, x, cin, cout, h, w, dest=d, inject=inj)
                 elif kind == "st":
-                    y = self.st_transformer(p, x, cout, h, w, dest=d)
+                    y = self.st_transformer(p, x, cout, h, w, dest=d, inject=inj)
                 elif kind in ("down", "up"):
                     attr = "op" if kind == "down" else "conv"
                     if self.precise_rs and cin % 64 == 0:        # the cast as rows [hi | lo], the convolution against [W | W] (unet.py resample)
                         x16 = P.alloc(x.rows, 2 * cin, "f16")
                         P.copy2d(p + ".cast", x, x16.col_slice(0, cin), lo=x16.col_slice(cin, 2 * cin))
                         y = self.conv133(f"{p}.{attr}", x16, f"{p}.{attr}", cout, h, w, stride=2 if kind == "down" else 1,
-                                         up=1 if kind == "up" else 0, dest=d, hilo=True)
+                                         up=1 if kind == "up" else 0, dest=d, hilo=True, **conv_res)
                     else:
                         x16 = P.alloc(x.rows, cin, "f16")
                         P.copy2d(p + ".cast", x, x16)
                         y = self.conv133(f"{p}.{attr}", x16, f"{p}.{attr}", cout, h, w, stride=2 if kind == "down" else 1,
-                                         up=1 if kind == "up" else 0, dest=d)
+                                         up=1 if kind == "up" else 0, dest=d, **conv_res)
                     P.free(x16)
                     h, w = ((h + 1) // 2, (w + 1) // 2) if kind == "down" else (h * 2, w * 2)
                 else:
@@ -564,13 +651,18 @@ class _LvdmLowering(_Lowering):
         n_skip = len(inputs)
         cats: List[Buf] = []
         x = xin
+        n_feat = 0
         for k, (prefix, parts) in enumerate(inputs):
             sc = parts[-1][2]
             cin_total = outputs[n_skip - 1 - k][1][0][1]
             ho, wo = out_hw(parts, h, w)
             cat = P.alloc(self.B * self.F * ho * wo, cin_total, "f32")
             cats.append(cat)
-            x, h, w = run_parts(prefix, parts, x, h, w, dest=cat.borrow_cols(cin_total - sc, cin_total))
+            feat = None
+            if self.adapter_fb and (k + 1) % 3 == 0:          # openaimodel3d.py:657
+                feat = Buf(Ref("ext", L.EXT_ADAPTER + n_feat), self.adapter_fb * self.F * ho * wo, sc, sc, "f32")
+                n_feat += 1
+            x, h, w = run_parts(prefix, parts, x, h, w, dest=cat.borrow_cols(cin_total - sc, cin_total), inject=feat)
         cat = cats.pop()
         x, h, w = run_parts("middle_block", middle, x, h, w, dest=cat.borrow_cols(0, cat.cols - inputs[-1][1][-1][2]))
         for j, (prefix, parts) in enumerate(outputs):
@@ -586,6 +678,237 @@ class _LvdmLowering(_Lowering):
         P.free(a)
         P.cl_to_ncthw("eps.from_tokens", y, Ref("ext", L.EXT_OUT), self.out_dt, B=B, C=net.out_dim, F=F, HW=h * w)
         P.free(y, self.emb_out, self.kv_all)
+        P.finish()
+        return P
+
+
+# ------------------------------------------------------------------------------------------
+# depth adapter (lvdm/models/modules/adapter.py — the T2I-Adapter network of "VideoControl")
+# ------------------------------------------------------------------------------------------
+def _pad64(c: int) -> int:
+    return (c + 63) // 64 * 64
+
+
+def _adapter_block_params(in_c, out_c, down, ksize, sk, use_conv):
+    """ResnetBlock (adapter.py:39-71): same sub-module names, same registration order."""
+    ps = ksize // 2
+    m = nn.Module()
+    m.in_conv = nn.Conv2d(in_c, out_c, ksize, 1, ps) if (in_c != out_c or not sk) else None
+    m.block1 = nn.Conv2d(out_c, out_c, 3, 1, 1)
+    m.act = nn.ReLU()
+    m.block2 = nn.Conv2d(out_c, out_c, ksize, 1, ps)
+    m.skep = nn.Conv2d(in_c, out_c, ksize, 1, ps) if not sk else None
+    m.down = down
+    if down:
+        m.down_opt = _holder("op", nn.Conv2d(in_c, in_c, 3, stride=2, padding=1) if use_conv else nn.AvgPool2d(2, 2))
+    return m
+
+
+class Adapter(nn.Module):
+    """Drop-in for lvdm.models.modules.adapter.Adapter: same constructor, same state-dict keys (`load_state_dict(strict=True)` takes the
+    reference's), `forward(x[n, 1, H, W]) -> [features [n, c_i, H / 2^(3+i), W / 2^(3+i)]]` — computed by ONE program of HIP kernels
+    over all n frames (PixelUnshuffle(8) front end, convolutions as implicit GEMMs with ReLU / the skip as fused epilogues).  The
+    module tree only holds the parameters; there is no CPU fallback.  Each feature is stored as channels-last fp32 tokens — the layout
+    UNetModel's injection reads — and returned as an [n, c, h, w] view of it."""
+
+    def __init__(self, channels=[320, 640, 1280, 1280], nums_rb=3, cin=64, ksize=3, sk=False, use_conv=True, init_weights=True):
+        super().__init__()
+        channels = list(channels)
+        if cin != 64:
+            raise NotImplementedError(f"Adapter: cin = {cin}; the front end is PixelUnshuffle(8) of ONE depth channel (cin = 64)")
+        if ksize not in (1, 3):
+            raise NotImplementedError(f"Adapter: ksize = {ksize} (1 or 3)")
+        if not 1 <= len(channels) <= L.EXT_SLOTS - L.EXT_ADAPTER or nums_rb < 1:
+            raise NotImplementedError(f"Adapter: 1 .. {L.EXT_SLOTS - L.EXT_ADAPTER} levels of at least one block")
+        if not sk and any(a != b for a, b in zip(channels[:-1], channels[1:])):
+            raise NotImplementedError(
+                "Adapter(sk=False) with a change of channel count between levels: the reference fails too — its ResnetBlock applies "
+                "skep = Conv2d(in_c, out_c) to the output of in_conv, which already has out_c channels (adapter.py:50-52,66-69)")
+        self.channels, self.nums_rb, self.cin, self.ksize, self.sk, self.use_conv = channels, nums_rb, cin, ksize, bool(sk), bool(use_conv)
+        with (torch.device("meta") if not init_weights else torch.device("cpu")):
+            body = []
+            for i in range(len(channels)):
+                for j in range(nums_rb):
+                    down = i != 0 and j == 0
+                    body.append(_adapter_block_params(channels[i - 1] if down else channels[i], channels[i], down, ksize, sk, use_conv))
+            self.body = nn.ModuleList(body)
+            self.conv_in = nn.Conv2d(cin, channels[0], 3, 1, 1)
+        if not init_weights:
+            self.to_empty(device="cpu")
+        self._programs: dict = {}
+        self._packed, self._packed_sig, self._packed_device = None, None, None
+
+    def feature_shapes(self, H: int, W: int) -> List[tuple]:
+        """(channels, h, w) of every feature for H x W depth frames."""
+        out, h, w = [], H // 8, W // 8
+        for i, c in enumerate(self.channels):
+            if i:
+                h, w = ((h + 1) // 2, (w + 1) // 2) if self.use_conv else (h // 2, w // 2)
+            out.append((c, h, w))
+        return out
+
+    def _compile(self, n, H, W, x_dt="f32", normalise=False, front_only=False) -> _Compiled:
+        low = _AdapterLowering(self, n, H, W, x_dt, normalise, front_only)
+        return _Compiled(low.build(), low.packer)
+
+    def _signature(self):
+        return tuple((k, id(p), p._version, p.device.type, p.dtype) for k, p in self.named_parameters())
+
+    def _run(self, x, normalise: bool, front_only: bool = False):
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise L.T2VError("Adapter needs a device tensor on an AMD GPU (no CPU fallback)")
+        if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[2] < 8 or x.shape[3] < 8:
+            raise ValueError(f"Adapter: depth frames [n, 1, H, W] with H, W multiples of 8 are required, got {tuple(x.shape)}")
+        if x.dtype not in (torch.float16, torch.float32):
+            x = x.float()
+        x = x.contiguous()
+        n, _, H, W = x.shape
+        shapes = self.feature_shapes(H, W)
+        if not front_only and min(min(h, w) for _, h, w in shapes) < 1:
+            raise ValueError(f"Adapter: {H} x {W} frames are too small for {len(self.channels)} levels")
+        key = (n, H, W, x.dtype, bool(normalise), front_only)
+        comp = self._programs.get(key)
+        if comp is None:
+            while len(self._programs) >= 4:                    # (each program owns a device arena)
+                del self._programs[next(iter(self._programs))]
+            comp = self._programs[key] = self._compile(n, H, W, "f16" if x.dtype == torch.float16 else "f32", normalise, front_only)
+        sig = self._signature()
+        if self._packed is None or self._packed_sig != sig or self._packed_device != x.device:
+            self._packed, self._packed_sig, self._packed_device = {}, sig, x.device
+            for c in self._programs.values():
+                c.bound = None
+        missing = pk.WeightPacker()
+        for name, dtype, fn in comp.packer.recipes:
+            if name not in self._packed:
+                missing.add(name, dtype, fn)
+        if missing.recipes:
+            self._packed.update(missing.materialise(self.state_dict(), x.device))
+            comp.bound = None
+        comp.ensure_bound(self._packed, x.device)
+        ext = {L.EXT_X: x.data_ptr()}
+        if front_only:
+            outs = [torch.empty(n * (H // 8) * (W // 8), 64, device=x.device, dtype=torch.float16)]
+        else:
+            outs = [torch.empty(n * h * w, _pad64(c), device=x.device, dtype=torch.float32) for c, h, w in shapes]
+        ext.update({L.EXT_ADAPTER + k: o.data_ptr() for k, o in enumerate(outs)})
+        comp.bound.run(ext, torch.cuda.current_stream(x.device).cuda_stream)
+        self.last_program = comp.prog
+        return outs, shapes
+
+    @torch.no_grad()
+    def forward(self, x, normalise: bool = False):
+        """x [n, 1, H, W] (fp16 / fp32, on the device) -> list of [n, c_i, h_i, w_i] fp32 features.  normalise (not in the reference's
+        signature): map each frame to 2 (d - min) / (max - min + 1e-7) - 1 first, inside the front-end launch — raw depth in,
+        what `T2VAdapterDepth.get_batch_depth` + `get_adapter_features` compute in two calls."""
+        outs, shapes = self._run(x, normalise)
+        n = x.shape[0]
+        return [o.view(n, h, w, o.shape[1])[..., :c].permute(0, 3, 1, 2) for o, (c, h, w) in zip(outs, shapes)]
+
+    @torch.no_grad()
+    def normalise_depth(self, depth):
+        """depth [n, 1, H, W] -> the per-frame min-max normalised depth in [-1, 1] (ddpm3d.py:1463-1464) as fp32 [n, 1, H, W]: the
+        front-end op alone, its PixelUnshuffle(8) tokens folded back.  The values are the fp16 numbers the adapter's first convolution
+        reads, so `forward(normalise_depth(d))` and `forward(d, normalise=True)` give the same features bit for bit."""
+        (tok,), _ = self._run(depth, True, front_only=True)
+        n, _, H, W = depth.shape
+        return tok.view(n, H // 8, W // 8, 8, 8).permute(0, 1, 3, 2, 4).reshape(n, 1, H, W).float()
+
+
+class _AdapterLowering:
+    """Adapter.forward (adapter.py:93-105) for all n frames as one program: front end, conv_in, then every ResnetBlock = optional
+    Downsample, optional in_conv, block1 + ReLU (epilogue), block2 + skip (fused residual).  Activations are channels-last tokens
+    [n * h * w, C padded to 64] — fp32 for the residual stream, an fp16 cast of it as the next convolution's operand; padding channels
+    meet zero weight rows / columns and stay zero.  The last block2 of level k writes feature k straight to ext slot T2V_EXT_ADAPTER + k."""
+
+    def __init__(self, net: Adapter, n, H, W, x_dt, normalise, front_only=False):
+        self.net, self.n, self.H, self.W, self.x_dt, self.normalise, self.front_only = net, n, H, W, x_dt, normalise, front_only
+        self.P = Program(f"adapter n{n} {H}x{W}")
+        self.packer = pk.WeightPacker()
+
+    def vec(self, key, cout_p) -> Ref:
+        return Ref("weight", 0, self.packer.add(key + ":v", "f32", lambda sd, k=key, c=cout_p: nn.functional.pad(sd[k].float(), (0, c - sd[k].shape[0]))))
+
+    def weight(self, key, cout_p, cin_p, ksize) -> Ref:
+        def fn(sd, k=key):
+            w = sd[k + ".weight"].float()
+            w = nn.functional.pad(w, (0, 0, 0, 0, 0, cin_p - w.shape[1], 0, cout_p - w.shape[0]))
+            return pk.conv3x3(w) if ksize == 3 else pk.linear(w)
+        return Ref("weight", 0, self.packer.add(f"{key}:{'c3' if ksize == 3 else 'lin'}", "f16", fn))
+
+    def conv(self, key, a: Buf, cin, cout, ksize, h, w, out: Buf, *, stride=1, act=0, residual=None):
+        cip, cop = _pad64(cin), _pad64(cout)
+        assert a.cols == cip and out.cols == cop and a.dtype == "f16"
+        if ksize == 3:
+            ho, wo = ((h + 1) // 2, (w + 1) // 2) if stride == 2 else (h, w)
+            self.P.gemm(key, a, self.weight(key, cop, cip, 3), cop, 9 * cip, out, bias=self.vec(key + ".bias", cop), gather=L.GATHER_CONV3X3,
+                        conv=dict(Hin=h, Win=w, Cin=cip, stride=stride, up=0, Hout=ho, Wout=wo), residual=residual, act=act)
+        else:
+            assert stride == 1
+            self.P.gemm(key, a, self.weight(key, cop, cip, 1), cop, cip, out, bias=self.vec(key + ".bias", cop), residual=residual, act=act)
+
+    def cast(self, name, x32: Buf) -> Buf:
+        x16 = self.P.alloc(x32.rows, x32.cols, "f16")
+        self.P.copy2d(name, x32, x16)
+        return x16
+
+    def build(self) -> Program:
+        net, P, n = self.net, self.P, self.n
+        h, w = self.H // 8, self.W // 8
+        P.begin()
+        if self.front_only:
+            tok = Buf(Ref("ext", L.EXT_ADAPTER), n * h * w, 64, 64, "f16")
+            P.depth_tokens("unshuffle", Ref("ext", L.EXT_X), self.x_dt, tok, n=n, H=self.H, W=self.W, normalise=self.normalise)
+            P.finish()
+            return P
+        tok = P.alloc(n * h * w, 64, "f16")
+        P.depth_tokens("unshuffle", Ref("ext", L.EXT_X), self.x_dt, tok, n=n, H=self.H, W=self.W, normalise=self.normalise)
+        ch = net.channels
+        x32 = P.alloc(n * h * w, _pad64(ch[0]), "f32")
+        self.conv("conv_in", tok, net.cin, ch[0], 3, h, w, x32)
+        P.free(tok)
+        x16 = self.cast("conv_in.cast", x32)
+        last = len(ch) * net.nums_rb - 1
+        for i, c in enumerate(ch):
+            for j in range(net.nums_rb):
+                idx = i * net.nums_rb + j
+                key = f"body.{idx}"
+                down = i != 0 and j == 0
+                in_c = ch[i - 1] if down else c
+                if down:
+                    if net.use_conv:
+                        ho, wo = (h + 1) // 2, (w + 1) // 2
+                        d32 = P.alloc(n * ho * wo, _pad64(in_c), "f32")
+                        self.conv(key + ".down_opt.op", x16, in_c, in_c, 3, h, w, d32, stride=2)
+                        P.free(x16, x32)
+                        x32, x16 = d32, self.cast(key + ".down_opt.cast", d32)
+                    else:
+                        ho, wo = h // 2, w // 2
+                        d32, d16 = P.alloc(n * ho * wo, _pad64(in_c), "f32"), P.alloc(n * ho * wo, _pad64(in_c), "f16")
+                        P.avgpool2(key + ".down_opt", x32, n=n, H=h, W=w, out32=d32, out16=d16)
+                        P.free(x16, x32)
+                        x32, x16 = d32, d16
+                    h, w = ho, wo
+                M = n * h * w
+                if in_c != c or not net.sk:
+                    y32 = P.alloc(M, _pad64(c), "f32")
+                    self.conv(key + ".in_conv", x16, in_c, c, net.ksize, h, w, y32)
+                    P.free(x16, x32)
+                    x32, x16 = y32, self.cast(key + ".in_conv.cast", y32)
+                h16 = P.alloc(M, _pad64(c), "f16")
+                self.conv(key + ".block1", x16, c, c, 3, h, w, h16, act=L.ACT_RELU)
+                res = x32
+                if not net.sk:
+                    res = P.alloc(M, _pad64(c), "f32")
+                    self.conv(key + ".skep", x16, c, c, net.ksize, h, w, res)
+                P.free(x16)
+                out = Buf(Ref("ext", L.EXT_ADAPTER + i), M, _pad64(c), _pad64(c), "f32") if j == net.nums_rb - 1 else P.alloc(M, _pad64(c), "f32")
+                self.conv(key + ".block2", h16, c, c, net.ksize, h, w, out, residual=res)
+                P.free(h16, x32)
+                if res is not x32:
+                    P.free(res)
+                x32 = out
+                if idx != last:
+                    x16 = self.cast(key + ".cast", x32)
         P.finish()
         return P
 
@@ -708,6 +1031,58 @@ class LatentDiffusion(nn.Module):
         return self.decode_first_stage_2DAE(z, decode_bs=decode_bs, return_cpu=return_cpu, **kwargs)
 
 
+class T2VAdapterDepth(LatentDiffusion):
+    """ddpm3d.py:1436-1484 — LatentDiffusion + the depth adapter ("VideoControl").  The reference builds its parts from configs;
+    here `adapter_config` is an `Adapter` or a dict {"params": {Adapter keywords}, "cond_name": "depth"}, and `depth_stage_config`
+    an optional depth estimator: any callable frames [n, 3, H, W] -> depth [n, 1, H, W] on the device (the MiDaS network itself is
+    outside this package).  State-dict keys of the adapter: 'adapter.*', as in the released checkpoint."""
+
+    def __init__(self, depth_stage_config=None, adapter_config=None, *args, **kwargs):
+        init_weights = kwargs.get("init_weights", True)
+        super().__init__(*args, **kwargs)
+        if isinstance(adapter_config, Adapter):
+            self.adapter, self.condtype = adapter_config, "depth"
+        else:
+            cfg = dict(adapter_config or {})
+            self.adapter = Adapter(**dict(cfg.get("params", {})), init_weights=init_weights)
+            self.condtype = cfg.get("cond_name", "depth")
+        self.depth_stage_model = depth_stage_config
+
+    @torch.no_grad()
+    def get_batch_depth(self, batch_x=None, target_size=None, encode_bs=1, depth=None):
+        """videos batch_x [b, 3, t, h, w] -> min-max normalised depth [b, 1, t, H, W] in [-1, 1] (ddpm3d.py:1449-1469).
+        `depth_stage_model` is called on all (b t) frames at once and must return [b t, 1, H, W] at `target_size` already: the two
+        bicubic resizes the reference wraps around MiDaS (to 384 x 384 and back) are not part of this package.  Alternatively pass
+        the depth itself, `get_batch_depth(depth=d)` with d [b, 1, t, H, W]: only the normalisation runs (the front-end kernel)."""
+        if depth is None:
+            if self.depth_stage_model is None:
+                raise RuntimeError("no depth_stage_model attached: pass depth=[b, 1, t, H, W] instead")
+            b, _, t, _, _ = batch_x.shape
+            merged = batch_x.permute(0, 2, 1, 3, 4).reshape(b * t, batch_x.shape[1], batch_x.shape[3], batch_x.shape[4])
+            d = self.depth_stage_model(merged)
+        else:
+            if depth.dim() != 5 or depth.shape[1] != 1:
+                raise ValueError(f"depth must be [b, 1, t, H, W], got {tuple(depth.shape)}")
+            b, _, t, _, _ = depth.shape
+            d = depth.permute(0, 2, 1, 3, 4).reshape(b * t, 1, depth.shape[3], depth.shape[4])
+        if d.dim() != 4 or d.shape[0] != b * t or d.shape[1] != 1:
+            raise ValueError(f"the depth model must return [{b * t}, 1, H, W], got {tuple(d.shape)}")
+        if target_size is not None and tuple(d.shape[2:]) != tuple(target_size):
+            raise ValueError(f"depth maps of {tuple(d.shape[2:])} for target_size {tuple(target_size)}: the bicubic resizes around the depth "
+                             "model are not part of this package — depth must arrive at target_size")
+        out = self.adapter.normalise_depth(d)
+        return out.reshape(b, t, 1, d.shape[2], d.shape[3]).permute(0, 2, 1, 3, 4).contiguous()
+
+    @torch.no_grad()
+    def get_adapter_features(self, extra_cond, encode_bs=1):
+        """extra_cond [b, 1, t, h, w] -> list of [b, c_i, t, h_i, w_i] (ddpm3d.py:1471-1484).  The reference runs the adapter frame
+        by frame (`encode_bs`); here ONE program covers all b t frames — the results are per frame either way.  The returned tensors
+        are views of channels-last storage, the layout UNetModel's injection reads without a copy."""
+        b, c, t, h, w = extra_cond.shape
+        feats = self.adapter(extra_cond.permute(0, 2, 1, 3, 4).reshape(b * t, c, h, w))
+        return [f.reshape(b, t, *f.shape[1:]).permute(0, 2, 1, 3, 4) for f in feats]
+
+
 # ------------------------------------------------------------------------------------------
 # DDIM sampler (lvdm/samplers/ddim.py)
 # ------------------------------------------------------------------------------------------
@@ -743,12 +1118,17 @@ class DDIMSampler(object):
         if mask is not None or quantize_x0 or noise_dropout or score_corrector is not None or postprocess_fn is not None \
                 or cond_fn is not None or kwargs.get("uc_type") is not None:
             raise NotImplementedError("mask blending / quantisation / noise dropout / score correctors are not on the hot path")
+        # features_adapter: forwarded to every apply_model call (ddim.py:221-229 passes its **kwargs on for both evaluations of a
+        # guided step); temporal_length: accepted and ignored, as in the reference (ddim.py:80: the shape carries the length)
+        if kwargs.get("conditional_guidance_scale_temporal") is not None:
+            raise NotImplementedError("conditional_guidance_scale_temporal (temporal guidance) is not on the hot path")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=schedule_verbose)
         size = (batch_size, *shape)
         assert len(size) == 5
         return self.ddim_sampling(conditioning, size, callback=callback, img_callback=img_callback, temperature=temperature,
                                   x_T=x_T, log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, sample_noise=sample_noise, verbose=verbose)
+                                  unconditional_conditioning=unconditional_conditioning, sample_noise=sample_noise, verbose=verbose,
+                                  features_adapter=kwargs.get("features_adapter"))
 
     @staticmethod
     def _ctx(c):
@@ -760,7 +1140,8 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100, temperature=1.0,
-                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, sample_noise=None, verbose=True, **kw):
+                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, sample_noise=None, verbose=True,
+                      features_adapter=None, **kw):
         """ddim.py:135-206, p_sample_ddim :209-279 fused into one kernel launch per step (T2V_OP_DDIM_STEP mode 1)."""
         from . import samplers as S
         device = self.model.betas.device
@@ -777,6 +1158,7 @@ class DDIMSampler(object):
         prev_auto, unet.auto_refresh = unet.auto_refresh, False
         prev_eps = S._want_fp32_eps(unet)            # eps in fp32 inside the loop: the CFG combination amplifies fp16 output roundings
         nxt = torch.empty_like(img)
+        extra = {} if features_adapter is None else {"features_adapter": features_adapter}     # the same list object every step: converted once
         nb, C = img.shape[0], img.shape[1]          # nb videos per batch (sample_text2video's batch_size)
         f32 = torch.float32
         S.state.sampling_steps = total_steps
@@ -797,9 +1179,9 @@ class DDIMSampler(object):
                     xin = img if hasattr(unet, "share_cfg_prefix") else torch.cat([img, img])      # (a foreign model gets the reference's batch)
                     if hasattr(unet, "single_timestep"):
                         unet.single_timestep = True        # [ts | ts]: one timestep for the pair -> the prefix may be shared
-                    eps = self.model.apply_model(xin, torch.cat([ts, ts]), torch.cat([c, uc])).contiguous()
+                    eps = self.model.apply_model(xin, torch.cat([ts, ts]), torch.cat([c, uc]), **extra).contiguous()
                 else:
-                    eps = self.model.apply_model(img, ts, c).contiguous()
+                    eps = self.model.apply_model(img, ts, c, **extra).contiguous()
                 a_t, a_prev = self.ddim_alphas[index].to(f32), self.ddim_alphas_prev[index].to(f32)
                 sigma_t, s1m = self.ddim_sigmas[index].to(f32), self.ddim_sqrt_one_minus_alphas[index].to(f32)
                 coef = [float(s1m), float(a_t.sqrt()), float(a_prev.sqrt()), float((1.0 - a_prev - sigma_t ** 2).sqrt()),
@@ -878,3 +1260,35 @@ def sample_text2video(model, prompt, n_prompt, n_samples, batch_size, sample_typ
     out = np.concatenate(videos, axis=0)
     assert out.shape[0] >= n_samples
     return out
+
+
+@torch.no_grad()
+def adapter_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
+                             unconditional_guidance_scale=1.0, unconditional_guidance_scale_temporal=None, sampler=None, depth=None,
+                             **kwargs):
+    """videocrafter/sample_text2video_adapter.py:96-137: depth of `videos` [b, 3, t, h, w] -> adapter features -> DDIM with the
+    features at every step -> decoded clips.  -> (batch_variants [b, n_samples, c, t, H, W], extra_cond [b, 1, t, h, w]).
+    `model`: a T2VAdapterDepth.  sampler: a DDIMSampler to use (e.g. with a seeded `noise_gen`), as `sample_text2video` takes one;
+    default a fresh one.  depth [b, 1, t, h, w]: the depth clip itself instead of `videos` + the model's depth estimator."""
+    ddim_sampler = DDIMSampler(model) if sampler is None else sampler
+    batch_size = noise_shape[0]
+    if isinstance(prompts, str):
+        prompts = [prompts]
+    cond = model.get_learned_conditioning(prompts)
+    uc = model.get_learned_conditioning(batch_size * [""]) if unconditional_guidance_scale != 1.0 else None
+    if depth is not None:
+        extra_cond = model.get_batch_depth(depth=depth)
+    else:
+        b, c, t, h, w = videos.shape
+        extra_cond = model.get_batch_depth(videos, (h, w))
+    features_adapter = model.get_adapter_features(extra_cond)
+    batch_variants = []
+    for _ in range(n_samples):
+        samples, _ = ddim_sampler.sample(S=ddim_steps, conditioning=cond, batch_size=noise_shape[0], shape=noise_shape[1:], verbose=False,
+                                         unconditional_guidance_scale=unconditional_guidance_scale, unconditional_conditioning=uc,
+                                         eta=ddim_eta, temporal_length=noise_shape[2],
+                                         conditional_guidance_scale_temporal=unconditional_guidance_scale_temporal,
+                                         features_adapter=features_adapter, **kwargs)
+        batch_variants.append(model.decode_first_stage(samples, decode_bs=1, return_cpu=False))
+    batch_variants = torch.stack(batch_variants)
+    return batch_variants.permute(1, 0, 2, 3, 4, 5), extra_cond
