@@ -21,8 +21,18 @@
 // head_dim: ModelScope uses 64 everywhere; the LVDM UNet has 8 heads of C/8 = 40 / 80 / 160 channels
 // (openaimodel3d.py:459-466).  The reduction of Q K^T is zero-padded to a multiple of 16 and the rows of
 // O^T to a multiple of 32 inside LDS / registers only; nothing padded is read from or written to HBM.
-#include <cstdlib>
-
+//
+// Shared core.  The MFMA attention kernels of this file are built from one set of device helpers (below, in front of the kernels), so a
+// change to the softmax or to a fragment layout is made once, and the kernels that promise equal bits (attn_kernel / attn2_kernel) make
+// the same calls instead of carrying copies:
+//   load_row_frags       B / A fragments of one Q (or K) row, zero beyond head_dim and for a dead row     attn, attn2, relpos_mfma, relpos_long
+//   mask_keys            -inf behind a key bound (ragged last tile, causal diagonal)                      attn, attn2
+//   online_softmax_step  tile maximum, stale-maximum rescale of l and O, exp2, row sum                    attn, attn2, relpos_long (+ w_lo / w_hi)
+//   p_frag               the P operand of one 16-slot step, straight from the score registers            all five
+//   pv_step              O^T += A P^T with A rows read as lo | hi 8-byte halves (V^T, and the Ev^T images)   attn, relpos_mfma, relpos16, relpos_long
+//   stage_vt             the transposing (key pair, 4 d) V^T stage into LDS                               attn, relpos_mfma, relpos16, relpos_long
+//   store_o_hilo         O / l -> fp16 row, and its residual row at lo_off                                all five
+// attn2_kernel keeps its own V^T fragment read (one swizzled 16-byte load).  seqattn_kernel (VALU) and softmax_rows_kernel share none of it.
 #include "t2v_kernels.h"
 
 namespace {
@@ -38,10 +48,163 @@ struct AttnParams {
   int lo_off;   // != 0: also store fp16(o - float(fp16(o))) at o + lo_off (elements): rows [hi | lo] for a K-doubled to_out (precise_operands)
 };
 
+// ---- the shared flash-attention core -----------------------------------------------------------------------------------------------
+// Lane roles everywhere below: frow = lane & 31 is the MFMA row / column this lane feeds (a key or d as A operand, its query as B operand),
+// fhalf = lane >> 5 the half of the 16-slot reduction step.  Accumulator register r of a 32x32 block holds row (r & 3) + 8 (r >> 2) +
+// 4 fhalf of column frow: with keys on the row axis (S^T = K Q^T) these are 16 scores of the lane's own query.
+typedef f16 f16x2 __attribute__((ext_vector_type(2)));
+
+// Fragments of row `row` of a [row][d] matrix with `stride` elements per row (a query as B operand, a key as A operand):
+// d = kk * 16 + 8 * fhalf + 0..7, zero beyond D and for a row >= nrows.  nrows and stride are taken by reference so that, inlined, every
+// fragment tests and reads the caller's own kernel parameter, as the hand-written loops did: with them passed by value the compiler merges
+// the NKK loads under one branch, and attn2_kernel<4>, which lives at its 128-register cap, spills 8 more bytes per lane
+// (profiles/attention_shared_core.txt).
+template <int D, int NKK>
+__device__ __forceinline__ void load_row_frags(f16x8 (&fr)[NKK], const f16* base, int row, const int& nrows, const long& stride, int fhalf) {
+#pragma unroll
+  for (int kk = 0; kk < NKK; ++kk) {
+    const int d0 = kk * 16 + fhalf * 8;
+    if (row < nrows && d0 < D)
+      fr[kk] = *reinterpret_cast<const f16x8*>(base + (long)row * stride + d0);
+    else
+      for (int e = 0; e < 8; ++e) fr[kk][e] = (f16)0.f;
+  }
+}
+
+// Scores of keys >= key_end become -inf; s[T] is the 32-key block that starts at key0 + 32 T
+template <int NB>
+__device__ __forceinline__ void mask_keys(f32x16 (&s)[NB], int key0, int key_end, int fhalf) {
+#pragma unroll
+  for (int T = 0; T < NB; ++T)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = key0 + T * 32 + (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+      if (key >= key_end) s[T][r] = -INFINITY;
+    }
+}
+
+// One online-softmax step for this lane's query: s (raw scores of NB 32-key blocks, masked ones -inf) becomes the unnormalised
+// probabilities exp2(s * scale_log2 - m_run); returns their sum over the tile (both lane halves), already added to l_run.
+// The softmax is the VALU-bound part of the streaming kernels (32 scores per lane and tile against 16 MFMAs), so it is kept to
+// max / fma / exp2 / add per score: the scale is folded into the exponent's fma, exp2 is the bare v_exp_f32 (arguments <= 8, flushed
+// denormals are zeros of the sum anyway), and the running maximum is only advanced when it grows by more than 2^8 — O and l carry the same
+// stale factor, so the result is exact and the accumulator rescale (AGPR round trips) is rare.  `also` receives alpha inside the same
+// wave-uniform branch for whatever else the caller accumulates under the stale maximum (relpos_long_kernel: w_lo, w_hi).
+struct no_other_sums { __device__ __forceinline__ void operator()(float) const {} };
+template <int NB, int NDT, typename Also = no_other_sums>
+__device__ __forceinline__ float online_softmax_step(f32x16 (&s)[NB], float scale_log2, float& m_run, float& l_run, f32x16 (&oacc)[NDT],
+                                                     Also also = Also()) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int T = 0; T < NB; ++T)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[T][r]);
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const float m_tile = mx * scale_log2;                   // scale > 0 (checked at launch)
+  const bool grow = m_tile - m_run > 8.0f;                // first tile: m_run = -inf (its first key is visible to every query)
+  if (__builtin_amdgcn_ballot_w64(grow) != 0) {           // wave-uniform
+    const float alpha = grow ? __builtin_amdgcn_exp2f(m_run - m_tile) : 1.0f;   // exp2(-inf) = 0 on the first tile
+    l_run *= alpha;
+    also(alpha);
+#pragma unroll
+    for (int d = 0; d < NDT; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
+    m_run = grow ? m_tile : m_run;
+  }
+  float psum = 0.f;
+  const float neg_m = -m_run;
+#pragma unroll
+  for (int T = 0; T < NB; ++T)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[T][r], scale_log2, neg_m));
+      s[T][r] = pv;
+      psum += pv;
+    }
+  psum += __shfl_xor(psum, 32);
+  l_run += psum;
+  return psum;
+}
+
+// P operand of the 16-slot step t of a 32-key block: registers 8 t .. 8 t + 7 as they are (the key order inside a step is a free
+// permutation as long as the A operand uses the same one), so P never goes through LDS
+__device__ __forceinline__ f16x8 p_frag(const f32x16& s, int t) {
+  f16x8 pf;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) pf[e] = (f16)s[8 * t + e];
+  return pf;
+}
+
+// O^T += A pf for one 16-slot step: A = rows d * 32 + frow of an LDS image [row][slot] with `pitch` bytes per row (V^T, or a transposed
+// Ev table); the lane's 8 slots are the 4 at byte `ofs` and the 4 at ofs + 16 — the slot order of the score registers
+template <int NDT>
+__device__ __forceinline__ void pv_step(f32x16 (&oacc)[NDT], const unsigned char* img, int pitch, int ofs, const f16x8& pf, int frow) {
+#pragma unroll
+  for (int d = 0; d < NDT; ++d) {
+    const unsigned char* arow = img + (d * 32 + frow) * pitch + ofs;
+    const f16x4 lo = *reinterpret_cast<const f16x4*>(arow);
+    const f16x4 hi = *reinterpret_cast<const f16x4*>(arow + 16);
+    const f16x8 af = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, pf, oacc[d], 0, 0, 0);
+  }
+}
+
+// V rows key0 .. key0 + NKEYS - 1, transposed into the LDS image vt[d][key] (`pitch` bytes per row) by NT threads, this one being `tid`:
+// unit = (key pair, 4 d) -> 4 x 32-bit {V[2 kp][d], V[2 kp + 1][d]}.  Keys >= nk and the rows D .. DV - 1 are zeros.
+template <int D, int NKEYS, int NT>
+__device__ __forceinline__ void stage_vt(unsigned char* vt, int pitch, const f16* vb, long sk_seq, int key0, int nk, int tid) {
+  constexpr int DV = (D + 31) / 32 * 32;
+  for (int u = tid; u < (NKEYS / 2) * (DV / 4); u += NT) {
+    const int kp = u / (DV / 4), dq = u - kp * (DV / 4);
+    const int key = key0 + 2 * kp;
+    const bool dok = dq * 4 < D;
+    f16x4 a, b;
+    if (dok && key < nk) a = *reinterpret_cast<const f16x4*>(vb + (long)key * sk_seq + dq * 4);
+    else for (int e = 0; e < 4; ++e) a[e] = (f16)0.f;
+    if (dok && key + 1 < nk) b = *reinterpret_cast<const f16x4*>(vb + (long)(key + 1) * sk_seq + dq * 4);
+    else for (int e = 0; e < 4; ++e) b[e] = (f16)0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      f16x2 w = {a[e], b[e]};
+      *reinterpret_cast<f16x2*>(vt + (dq * 4 + e) * pitch + kp * 4) = w;
+    }
+  }
+}
+
+// This lane's 4-column groups of one output row: o = O * inv as fp16, and with lo_off != 0 the residual fp16(o - float(fp16(o))) beside it
+template <int D, int NDT>
+__device__ __forceinline__ void store_o_hilo(f16* orow, const f32x16 (&oacc)[NDT], float inv, int lo_off, int fhalf) {
+  f16* o4 = orow + 4 * fhalf;                       // this lane's first column; the rest are compile-time offsets from it
+#pragma unroll
+  for (int d = 0; d < NDT; ++d)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      const int col = d * 32 + 8 * qd;
+      if (col + 4 * fhalf < D) {
+        f16x4 o, lo;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float val = oacc[d][4 * qd + r] * inv;
+          o[r] = (f16)val;
+          lo[r] = (f16)(val - (float)o[r]);
+        }
+        *reinterpret_cast<f16x4*>(o4 + col) = o;
+        if (lo_off) *reinterpret_cast<f16x4*>(o4 + lo_off + col) = lo;
+      }
+    }
+}
+
 // KT = keys per LDS tile: 64, or 32 for sequences of <= 32 keys (temporal attention over the frames of one pixel:
 // half the LDS per workgroup, twice the workgroups per CU for a kernel that is bound by memory latency).
-constexpr int KT_MAIN = 64;
-template <int NW, int D, int KT = 64, bool PREFETCH = false>
+// Measured and not kept (profiles/r06_attention.txt; the 9216-token level at head_dim 64):
+//  * fetching the K / V tile of the next iteration into registers while the current one is processed: 66.5 vs 66.0 ms, 24 more VGPRs —
+//    the kernel is bound by the softmax VALU work, not by load latency;
+//  * timing-only ablations: the exp2 costs 3 %, the K / V staging 32 % — the staging is what attn2_kernel below removes;
+//  * attn2_kernel with the scores of tile t + 1 issued before the softmax of tile t (K tiles in a 3-deep ring): 529 / 866 TF/s against
+//    558 / 877 — the Q K^T MFMAs moved under the VALU work, but that did not hide the fp16 conversion of P, which stayed serial in
+//    front of P·V.
+template <int NW, int D, int KT = 64>
 __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
   constexpr int NT = NW * 64;
   constexpr int NKT = KT / 32;             // 32-key MFMA tiles per LDS tile
@@ -68,17 +231,9 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
   const f16* vb = p.v + bo * p.sk_out + bi * p.sk_in + head * D;
   f16* ob = p.o + bo * p.so_out + bi * p.so_in + head * D;
 
-  // Q fragments: query (lane&31), d = kk*16 + 8*fhalf + 0..7
   const int qrow = q0 + frow;
   f16x8 qf[NKK];
-#pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) {
-    const int d0 = kk * 16 + fhalf * 8;
-    if (qrow < p.nq && d0 < D)
-      qf[kk] = *reinterpret_cast<const f16x8*>(qb + (long)qrow * p.sq_seq + d0);
-    else
-      for (int e = 0; e < 8; ++e) qf[kk][e] = (f16)0.f;
-  }
+  load_row_frags<D>(qf, qb, qrow, p.nq, p.sq_seq, fhalf);
 
   f32x16 oacc[NDT];
 #pragma unroll
@@ -89,99 +244,21 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
   // last visible key of this lane's query; key 0 is visible to every query, so m_run is finite after the first tile
   const int key_end = p.causal ? min(p.nk, qrow + 1) : p.nk;
 
-  // PREFETCH (experiment, env T2V_ATTN_PREFETCH=1, 4-wave variants with head_dim <= 80): the K / V tile of the next
-  // iteration is fetched into registers while the current one is processed.  Measured equal-to-slower (66.5 vs 66.0 ms
-  // on the 9216-token level, 24 more VGPRs): the kernel is bound by the softmax VALU work, not by load latency.
-  constexpr bool PF = PREFETCH;
-  constexpr int KI = (KT * KCH + NT - 1) / NT;                 // 16-byte K chunks per thread
-  constexpr int VI = ((KT / 2) * (DV / 4) + NT - 1) / NT;      // (key pair, 4 d) V units per thread
-  f16x8 kreg[KI];
-  f16x4 vra[VI], vrb[VI];
-  auto gload = [&](int kt0) {
-#pragma unroll
-    for (int i = 0; i < KI; ++i) {
-      const int u = tid + i * NT;
-      const int row = u / KCH, c = u - row * KCH;
-      const int key = kt0 + row;
-      if (u < KT * KCH && key < p.nk && c * 8 < D)
-        kreg[i] = *reinterpret_cast<const f16x8*>(kb + (long)key * p.sk_seq + c * 8);
-      else
-        for (int e = 0; e < 8; ++e) kreg[i][e] = (f16)0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < VI; ++i) {
-      const int u = tid + i * NT;
-      const int kp = u / (DV / 4), dq = u - kp * (DV / 4);
-      const int key = kt0 + 2 * kp;
-      const bool dok = u < (KT / 2) * (DV / 4) && dq * 4 < D;
-      if (dok && key < p.nk) vra[i] = *reinterpret_cast<const f16x4*>(vb + (long)key * p.sk_seq + dq * 4);
-      else for (int e = 0; e < 4; ++e) vra[i][e] = (f16)0.f;
-      if (dok && key + 1 < p.nk) vrb[i] = *reinterpret_cast<const f16x4*>(vb + (long)(key + 1) * p.sk_seq + dq * 4);
-      else for (int e = 0; e < 4; ++e) vrb[i][e] = (f16)0.f;
-    }
-  };
-  auto lstore = [&]() {
-    // K tile: KT rows x KCH chunks of 16 B;  V tile, transposed: unit = (key pair, 4 d) -> 4 x 32-bit {V[2kp][d], V[2kp+1][d]}
-#pragma unroll
-    for (int i = 0; i < KI; ++i) {
-      const int u = tid + i * NT;
-      const int row = u / KCH, c = u - row * KCH;
-      if (u < KT * KCH) *reinterpret_cast<f16x8*>(k_lds + row * K_ROW + (c << 4)) = kreg[i];
-    }
-#pragma unroll
-    for (int i = 0; i < VI; ++i) {
-      const int u = tid + i * NT;
-      const int kp = u / (DV / 4), dq = u - kp * (DV / 4);
-      if (u < (KT / 2) * (DV / 4)) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          typedef f16 f16x2 __attribute__((ext_vector_type(2)));
-          f16x2 w = {vra[i][e], vrb[i][e]};
-          *reinterpret_cast<f16x2*>(vt_lds + (dq * 4 + e) * VT_ROW + kp * 4) = w;
-        }
-      }
-    }
-  };
-  if (PF) gload(0);
-
   for (int kt0 = 0; kt0 < p.nk; kt0 += KT) {
     __syncthreads();  // previous tile fully consumed
-#ifdef T2V_ATTN_NOSTAGE   // timing experiment only (wrong results): the K / V tile staged once
-    if (kt0 == 0)
-#endif
-    if constexpr (PF) {
-      lstore();
-    } else {
-      // straight global -> LDS (few registers: the single-wave variants live on occupancy)
-      for (int u = tid; u < KT * KCH; u += NT) {
-        const int row = u / KCH, c = u - row * KCH;
-        const int key = kt0 + row;
-        f16x8 val;
-        if (key < p.nk && c * 8 < D)
-          val = *reinterpret_cast<const f16x8*>(kb + (long)key * p.sk_seq + c * 8);
-        else
-          for (int e = 0; e < 8; ++e) val[e] = (f16)0.f;
-        *reinterpret_cast<f16x8*>(k_lds + row * K_ROW + (c << 4)) = val;
-      }
-      for (int u = tid; u < (KT / 2) * (DV / 4); u += NT) {
-        const int kp = u / (DV / 4), dq = u - kp * (DV / 4);
-        const int key = kt0 + 2 * kp;
-        const bool dok = dq * 4 < D;
-        f16x4 a, b;
-        if (dok && key < p.nk) a = *reinterpret_cast<const f16x4*>(vb + (long)key * p.sk_seq + dq * 4);
-        else for (int e = 0; e < 4; ++e) a[e] = (f16)0.f;
-        if (dok && key + 1 < p.nk) b = *reinterpret_cast<const f16x4*>(vb + (long)(key + 1) * p.sk_seq + dq * 4);
-        else for (int e = 0; e < 4; ++e) b[e] = (f16)0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          typedef f16 f16x2 __attribute__((ext_vector_type(2)));
-          f16x2 w = {a[e], b[e]};
-          *reinterpret_cast<f16x2*>(vt_lds + (dq * 4 + e) * VT_ROW + kp * 4) = w;
-        }
-      }
+    // straight global -> LDS (few registers: the single-wave variants live on occupancy).  K tile: KT rows x KCH chunks of 16 B
+    for (int u = tid; u < KT * KCH; u += NT) {
+      const int row = u / KCH, c = u - row * KCH;
+      const int key = kt0 + row;
+      f16x8 val;
+      if (key < p.nk && c * 8 < D)
+        val = *reinterpret_cast<const f16x8*>(kb + (long)key * p.sk_seq + c * 8);
+      else
+        for (int e = 0; e < 8; ++e) val[e] = (f16)0.f;
+      *reinterpret_cast<f16x8*>(k_lds + row * K_ROW + (c << 4)) = val;
     }
+    stage_vt<D, KT, NT>(vt_lds, VT_ROW, vb, p.sk_seq, kt0, p.nk, tid);
     __syncthreads();
-    if (PF && kt0 + KT < p.nk) gload(kt0 + KT);
 
     // ---- S^T = K Q^T : NKT 32-key tiles --------------------------------------------
     const bool t1_live = (kt0 + 32) < p.nk;   // wave-uniform
@@ -198,98 +275,21 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
         s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], kk == 0 ? zero16 : s[T], 0, 0, 0);
       }
     }
-    // ---- online softmax for this lane's query -------------------------------------
-    // The softmax is the VALU-bound part of this kernel (32 scores per lane and tile against 16 MFMAs), so it is kept
-    // to max / fma / exp2 / add per score: keys are masked only in tiles that need it (ragged end, causal diagonal),
-    // the scale is folded into the exponent's fma, exp2 is the bare v_exp_f32 (arguments <= 8, flushed denormals are
-    // zeros of the sum anyway), and the running maximum is only advanced when it grows by more than 2^8 — O and l
-    // carry the same stale factor, so the result is exact and the accumulator rescale (AGPR round trips) is rare.
-    if (kt0 + KT > p.nk || (p.causal && kt0 + KT - 1 > q0)) {     // wave-uniform
-#pragma unroll
-      for (int T = 0; T < NKT; ++T)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kt0 + T * 32 + (r & 3) + 8 * (r >> 2) + 4 * fhalf;
-          if (key >= key_end) s[T][r] = -INFINITY;
-        }
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int T = 0; T < NKT; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[T][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_tile = mx * p.scale_log2;                 // scale > 0 (checked at launch)
-    const bool grow = m_tile - m_run > 8.0f;                // first tile: m_run = -inf (key kt0 = 0 is always visible)
-    if (__builtin_amdgcn_ballot_w64(grow) != 0) {           // wave-uniform
-      const float alpha = grow ? __builtin_amdgcn_exp2f(m_run - m_tile) : 1.0f;   // exp2(-inf) = 0 on the first tile
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < NDT; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-      m_run = grow ? m_tile : m_run;
-    }
-    float psum = 0.f;
-    const float neg_m = -m_run;
-#pragma unroll
-    for (int T = 0; T < NKT; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-#ifdef T2V_ATTN_NOEXP     // timing experiment only (wrong results): the softmax without its transcendental
-        const float pv = __builtin_fmaf(s[T][r], p.scale_log2, neg_m);
-#else
-        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[T][r], p.scale_log2, neg_m));
-#endif
-        s[T][r] = pv;
-        psum += pv;
-      }
-    psum += __shfl_xor(psum, 32);
-    l_run += psum;
+    // ---- online softmax for this lane's query; keys are masked only in tiles that need it (ragged end, causal diagonal)
+    if (kt0 + KT > p.nk || (p.causal && kt0 + KT - 1 > q0)) mask_keys(s, kt0, key_end, fhalf);     // wave-uniform
+    online_softmax_step(s, p.scale_log2, m_run, l_run, oacc);
 
     // ---- O^T += V^T P^T -----------------------------------------------------------
 #pragma unroll
     for (int T = 0; T < NKT; ++T) {
       if (T == 1 && !t1_live) continue;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        f16x8 pf;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pf[e] = (f16)s[T][8 * t + e];
-        const int kofs = (T * 32 + t * 16 + 4 * fhalf) * 2;  // byte offset of key slot e=0
-#pragma unroll
-        for (int d = 0; d < NDT; ++d) {
-          const unsigned char* vrow = vt_lds + (d * 32 + frow) * VT_ROW + kofs;
-          const f16x4 lo = *reinterpret_cast<const f16x4*>(vrow);
-          const f16x4 hi = *reinterpret_cast<const f16x4*>(vrow + 16);
-          const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[d], 0, 0, 0);
-        }
-      }
+      for (int t = 0; t < 2; ++t)
+        pv_step(oacc, vt_lds, VT_ROW, (T * 32 + t * 16 + 4 * fhalf) * 2, p_frag(s[T], t), frow);   // byte offset of key slot e = 0
     }
   }
 
-  if (qrow < p.nq) {
-    const float inv = 1.0f / l_run;
-    f16* orow = ob + (long)qrow * p.so_seq;
-#pragma unroll
-    for (int d = 0; d < NDT; ++d)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int col = d * 32 + 8 * qd + 4 * fhalf;
-        if (col < D) {
-          f16x4 o, lo;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float val = oacc[d][4 * qd + r] * inv;
-            o[r] = (f16)val;
-            lo[r] = (f16)(val - (float)o[r]);
-          }
-          *reinterpret_cast<f16x4*>(orow + col) = o;
-          if (p.lo_off) *reinterpret_cast<f16x4*>(orow + p.lo_off + col) = lo;
-        }
-      }
-  }
+  if (qrow < p.nq) store_o_hilo<D>(ob + (long)qrow * p.so_seq, oacc, 1.0f / l_run, p.lo_off, fhalf);
 }
 
 // ---- spatial self-attention at head_dim 64 with the K / V^T tiles staged by LDS-DMA (round 6) ---------------------------------------
@@ -304,7 +304,8 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
 //    registers, no ds_write, double-buffered: the pieces of tile t + 1 are issued after the one barrier of tile t and land under its
 //    MFMAs / softmax;
 //  * NW = 8 waves (256 queries) share a tile.
-// Scores, online softmax, P fragments and the epilogue are attn_kernel's, unchanged (same values, same order: bit-identical results).
+// Scores, online softmax, P fragments and the epilogue are the shared core's, called exactly as attn_kernel calls it (same values, same
+// order: bit-identical results).
 __device__ __attribute__((aligned(256))) unsigned char attn_zero_page[256];
 
 __global__ __launch_bounds__(256) void vt_transpose_kernel(const AttnParams p, f16* vt, int n_pad) {
@@ -358,11 +359,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn2_kernel(const AttnParams p, c
 
   const int qrow = q0 + frow;
   f16x8 qf[NKK];
-#pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) {
-    if (qrow < p.nq) qf[kk] = *reinterpret_cast<const f16x8*>(qb + (long)qrow * p.sq_seq + kk * 16 + fhalf * 8);
-    else for (int e = 0; e < 8; ++e) qf[kk][e] = (f16)0.f;
-  }
+  load_row_frags<D>(qf, qb, qrow, p.nq, p.sq_seq, fhalf);
   f32x16 oacc[NDT];
 #pragma unroll
   for (int d = 0; d < NDT; ++d)
@@ -412,50 +409,14 @@ __global__ __launch_bounds__(NW * 64, 4) void attn2_kernel(const AttnParams p, c
         s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], kk == 0 ? zero16 : s[T], 0, 0, 0);
       }
     }
-    if (kt0 + KT > p.nk) {                                    // ragged last tile (wave-uniform)
-#pragma unroll
-      for (int T = 0; T < NKT; ++T)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kt0 + T * 32 + (r & 3) + 8 * (r >> 2) + 4 * fhalf >= p.nk) s[T][r] = -INFINITY;
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int T = 0; T < NKT; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[T][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_tile = mx * p.scale_log2;
-    const bool grow = m_tile - m_run > 8.0f;
-    if (__builtin_amdgcn_ballot_w64(grow) != 0) {
-      const float alpha = grow ? __builtin_amdgcn_exp2f(m_run - m_tile) : 1.0f;
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < NDT; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-      m_run = grow ? m_tile : m_run;
-    }
-    float psum = 0.f;
-    const float neg_m = -m_run;
-#pragma unroll
-    for (int T = 0; T < NKT; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[T][r], p.scale_log2, neg_m));
-        s[T][r] = pv;
-        psum += pv;
-      }
-    psum += __shfl_xor(psum, 32);
-    l_run += psum;
+    if (kt0 + KT > p.nk) mask_keys(s, kt0, p.nk, fhalf);      // ragged last tile (wave-uniform)
+    online_softmax_step(s, p.scale_log2, m_run, l_run, oacc);
 #pragma unroll
     for (int T = 0; T < NKT; ++T) {
       if (T == 1 && !t1_live) continue;
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        f16x8 pf;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pf[e] = (f16)s[T][8 * u + e];
+        const f16x8 pf = p_frag(s[T], u);
 #pragma unroll
         for (int d = 0; d < NDT; ++d) {
           const f16x8 vf = *reinterpret_cast<const f16x8*>(vl + (d * 32 + frow) * 128 + (((4 * T + 2 * u + fhalf) ^ sw) << 4));
@@ -464,188 +425,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn2_kernel(const AttnParams p, c
       }
     }
   }
-  if (qrow < p.nq) {
-    const float inv = 1.0f / l_run;
-    f16* orow = ob + (long)qrow * p.so_seq;
-#pragma unroll
-    for (int d = 0; d < NDT; ++d)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int col = d * 32 + 8 * qd + 4 * fhalf;
-        f16x4 o, lo;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float val = oacc[d][4 * qd + r] * inv;
-          o[r] = (f16)val;
-          lo[r] = (f16)(val - (float)o[r]);
-        }
-        *reinterpret_cast<f16x4*>(orow + col) = o;
-        if (p.lo_off) *reinterpret_cast<f16x4*>(orow + p.lo_off + col) = lo;
-      }
-  }
-}
-
-// The same kernel with the scores of tile t + 1 issued BEFORE the softmax of tile t (experiment, round 6): the 8 Q K^T MFMAs run in the matrix
-// pipe while this wave's own VALU works on the previous tile's scores.  K tiles in a 3-deep ring (K(t + 1) is read one tile early), V^T in 2.
-template <int NW, int MINW>
-__global__ __launch_bounds__(NW * 64, MINW) void attn2p_kernel(const AttnParams p, const f16* __restrict__ vt, int n_pad) {
-  constexpr int D = 64, KT = 64, NKK = 4, NDT = 2, NKT = 2;
-  constexpr int PIECES = 16, PPW = PIECES / NW;               // 1-KiB DMA pieces per tile (8 K + 8 V^T), per wave
-  static_assert(PIECES % NW == 0, "pieces must divide over the waves");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[5 * 8192];       // K ring [3][8 KiB] | V^T ring [2][8 KiB]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int head = blockIdx.y;
-  const int bo = blockIdx.z / p.b_inner, bi = blockIdx.z % p.b_inner;
-  const int q0 = blockIdx.x * (32 * NW) + wave * 32;
-  const int frow = lane & 31, fhalf = lane >> 5;
-
-  const f16* qb = p.q + bo * p.sq_out + bi * p.sq_in + head * D;
-  const f16* kb = p.k + bo * p.sk_out + bi * p.sk_in + head * D;
-  const f16* vtb = vt + ((long)blockIdx.z * p.heads + head) * 64 * n_pad;
-  f16* ob = p.o + bo * p.so_out + bi * p.so_in + head * D;
-
-  const int qrow = q0 + frow;
-  f16x8 qf[NKK];
-#pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) {
-    if (qrow < p.nq) qf[kk] = *reinterpret_cast<const f16x8*>(qb + (long)qrow * p.sq_seq + kk * 16 + fhalf * 8);
-    else for (int e = 0; e < 8; ++e) qf[kk][e] = (f16)0.f;
-  }
-  f32x16 oacc[NDT];
-#pragma unroll
-  for (int d = 0; d < NDT; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-
-  // per-lane DMA sources of this wave's pieces: piece j < 8 = keys 8 j .. 8 j + 7 of the tile, j >= 8 = rows d = 8 (j - 8) .. of V^T
-  const int lrow = lane >> 3, pch = lane & 7;
-  const f16* src0[PPW];        // source of tile 0 (K: advanced by 64 keys per tile; V^T: by 64 columns)
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const int j = wave + NW * i, row = 8 * (j & 7) + lrow, lc = pch ^ ((row >> 1) & 7);
-    src0[i] = j < 8 ? kb + (long)row * p.sk_seq + lc * 8 : vtb + (long)row * n_pad + lc * 8;
-  }
-  auto stage = [&](int t, bool want_k, bool want_v) {          // K(t) -> K ring slot t % 3, V^T(t) -> V ring slot t & 1
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      const int j = wave + NW * i;                            // wave-uniform
-      if (j < 8 ? !want_k : !want_v) continue;
-      const f16* src = src0[i] + (long)t * (j < 8 ? (long)KT * p.sk_seq : (long)KT);
-      if (j < 8 && t * KT + 8 * (j & 7) + lrow >= p.nk) src = reinterpret_cast<const f16*>(attn_zero_page);
-      unsigned char* dst = j < 8 ? smem + (t % 3) * 8192 + (j & 7) * 1024 : smem + 3 * 8192 + (t & 1) * 8192 + (j & 7) * 1024;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-    }
-  };
-  const int nt = (p.nk + KT - 1) / KT;
-  const int sw = ((frow >> 1) & 7);
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  auto scores = [&](int t, f32x16 (&s)[NKT]) {                // S^T of tile t from its K ring slot
-    const unsigned char* kl = smem + (t % 3) * 8192;
-    const bool t1_live = (t * KT + 32) < p.nk;
-#pragma unroll
-    for (int T = 0; T < NKT; ++T) {
-      s[T] = zero16;
-      if (T == 1 && !t1_live) continue;
-#pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) {
-        const f16x8 kf = *reinterpret_cast<const f16x8*>(kl + (T * 32 + frow) * 128 + (((kk * 2 + fhalf) ^ sw) << 4));
-        s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], kk == 0 ? zero16 : s[T], 0, 0, 0);
-      }
-    }
-  };
-  stage(0, true, true);
-  if (nt > 1) stage(1, true, false);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  f32x16 s[NKT], sn[NKT];
-  scores(0, s);
-  for (int t = 0; t < nt; ++t) {
-    const int kt0 = t * KT;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // K(t + 1), V^T(t): this wave's pieces have landed
-    __builtin_amdgcn_s_barrier();                             // ... everyone's; everyone is done with K(t) [scores issued last iteration], V^T(t - 1)
-    asm volatile("" ::: "memory");
-    if (t + 2 < nt) stage(t + 2, true, false);
-    if (t + 1 < nt) stage(t + 1, false, true);
-    if (t + 1 < nt) scores(t + 1, sn);                        // in the matrix pipe while the VALU below works on tile t
-    const unsigned char* vl = smem + 3 * 8192 + (t & 1) * 8192;
-    const bool t1_live = (kt0 + 32) < p.nk;                   // wave-uniform
-    if (kt0 + KT > p.nk) {                                    // ragged last tile (wave-uniform)
-#pragma unroll
-      for (int T = 0; T < NKT; ++T)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kt0 + T * 32 + (r & 3) + 8 * (r >> 2) + 4 * fhalf >= p.nk) s[T][r] = -INFINITY;
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int T = 0; T < NKT; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[T][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_tile = mx * p.scale_log2;
-    const bool grow = m_tile - m_run > 8.0f;
-    if (__builtin_amdgcn_ballot_w64(grow) != 0) {
-      const float alpha = grow ? __builtin_amdgcn_exp2f(m_run - m_tile) : 1.0f;
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < NDT; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-      m_run = grow ? m_tile : m_run;
-    }
-    float psum = 0.f;
-    const float neg_m = -m_run;
-#pragma unroll
-    for (int T = 0; T < NKT; ++T)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[T][r], p.scale_log2, neg_m));
-        s[T][r] = pv;
-        psum += pv;
-      }
-    psum += __shfl_xor(psum, 32);
-    l_run += psum;
-#pragma unroll
-    for (int T = 0; T < NKT; ++T) {
-      if (T == 1 && !t1_live) continue;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        f16x8 pf;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pf[e] = (f16)s[T][8 * u + e];
-#pragma unroll
-        for (int d = 0; d < NDT; ++d) {
-          const f16x8 vf = *reinterpret_cast<const f16x8*>(vl + (d * 32 + frow) * 128 + (((4 * T + 2 * u + fhalf) ^ sw) << 4));
-          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[d], 0, 0, 0);
-        }
-      }
-    }
-#pragma unroll
-    for (int T = 0; T < NKT; ++T) s[T] = sn[T];
-  }
-  if (qrow < p.nq) {
-    const float inv = 1.0f / l_run;
-    f16* orow = ob + (long)qrow * p.so_seq;
-#pragma unroll
-    for (int d = 0; d < NDT; ++d)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int col = d * 32 + 8 * qd + 4 * fhalf;
-        f16x4 o, lo;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float val = oacc[d][4 * qd + r] * inv;
-          o[r] = (f16)val;
-          lo[r] = (f16)(val - (float)o[r]);
-        }
-        *reinterpret_cast<f16x4*>(orow + col) = o;
-        if (p.lo_off) *reinterpret_cast<f16x4*>(orow + p.lo_off + col) = lo;
-      }
-  }
+  if (qrow < p.nq) store_o_hilo<D>(ob + (long)qrow * p.so_seq, oacc, 1.0f / l_run, p.lo_off, fhalf);
 }
 
 // ---- attention over the <= 32 frames of one pixel (ModelScope temporal self-attention, t2v_model.py:716-767, and
@@ -879,35 +659,11 @@ __global__ __launch_bounds__(256) void relpos_mfma_kernel(const RelMfmaParams pp
   const f16* vb = p.v + bo * p.sk_out + bi * p.sk_in + head * D;
   f16* ob = p.o + bo * p.so_out + bi * p.so_in + head * D;
   const int frow = lane & 31, fhalf = lane >> 5;
-  // ---- V^T into LDS: unit = (key pair, 4 d)
-  for (int u = lane; u < 16 * (DV / 4); u += 64) {
-    const int kp = u / (DV / 4), dq = u - kp * (DV / 4);
-    const int key = 2 * kp;
-    const bool dok = dq * 4 < D;
-    f16x4 a, b;
-    if (dok && key < T) a = *reinterpret_cast<const f16x4*>(vb + (long)key * p.sk_seq + dq * 4);
-    else for (int e = 0; e < 4; ++e) a[e] = (f16)0.f;
-    if (dok && key + 1 < T) b = *reinterpret_cast<const f16x4*>(vb + (long)(key + 1) * p.sk_seq + dq * 4);
-    else for (int e = 0; e < 4; ++e) b[e] = (f16)0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      typedef f16 f16x2 __attribute__((ext_vector_type(2)));
-      f16x2 w = {a[e], b[e]};
-      *reinterpret_cast<f16x2*>(vt + (dq * 4 + e) * VT_PITCH + kp * 4) = w;
-    }
-  }
+  stage_vt<D, 32, 64>(vt, VT_PITCH, vb, p.sk_seq, 0, T, lane);
   // ---- Q (B operand) and K (A operand) fragments from global
   f16x8 qf[NKK], kf[NKK];
-#pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) {
-    const int d0 = kk * 16 + fhalf * 8;
-    if (frow < T && d0 < D) {
-      qf[kk] = *reinterpret_cast<const f16x8*>(qb + (long)frow * p.sq_seq + d0);
-      kf[kk] = *reinterpret_cast<const f16x8*>(kb + (long)frow * p.sk_seq + d0);
-    } else {
-      for (int e = 0; e < 8; ++e) { qf[kk][e] = (f16)0.f; kf[kk][e] = (f16)0.f; }
-    }
-  }
+  load_row_frags<D>(qf, qb, frow, T, p.sq_seq, fhalf);
+  load_row_frags<D>(kf, kb, frow, T, p.sk_seq, fhalf);
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   // ---- S^T = K Q^T
   f32x16 sc = zero16;
@@ -961,56 +717,15 @@ __global__ __launch_bounds__(256) void relpos_mfma_kernel(const RelMfmaParams pp
 #pragma unroll
   for (int d = 0; d < NDT; ++d) oacc[d] = zero16;
 #pragma unroll
-  for (int t2 = 0; t2 < 2; ++t2) {
-    f16x8 pf;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) pf[e] = (f16)sc[8 * t2 + e];
-    const int kofs = (t2 * 16 + 4 * fhalf) * 2;
-#pragma unroll
-    for (int d = 0; d < NDT; ++d) {
-      const unsigned char* vrow = vt + (d * 32 + frow) * VT_PITCH + kofs;
-      const f16x4 lo = *reinterpret_cast<const f16x4*>(vrow);
-      const f16x4 hi = *reinterpret_cast<const f16x4*>(vrow + 16);
-      const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[d], 0, 0, 0);
-    }
-  }
+  for (int t2 = 0; t2 < 2; ++t2) pv_step(oacc, vt, VT_PITCH, (t2 * 16 + 4 * fhalf) * 2, p_frag(sc, t2), frow);
   for (int u = 0; u < 2 * pp.nblk; ++u) {            // 16 table-row slots per step: slot = 16 u + 4 fhalf + (e & 3) + 8 (e >> 2)
     f16x8 pf;
     const f16* prow = pb + frow * P_PITCH + 32 + 16 * u + 4 * fhalf - (T - 1) + frow;     // column of slot e = 0 (s = slot + t - (T-1))
 #pragma unroll
     for (int e = 0; e < 8; ++e) pf[e] = prow[(e & 3) + 8 * (e >> 2)];
-    const int jofs = (16 * u + 4 * fhalf) * 2;
-#pragma unroll
-    for (int d = 0; d < NDT; ++d) {
-      const unsigned char* erow = evt + (d * 32 + frow) * EV_PITCH + jofs;
-      const f16x4 lo = *reinterpret_cast<const f16x4*>(erow);
-      const f16x4 hi = *reinterpret_cast<const f16x4*>(erow + 16);
-      const f16x8 ef = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ef, pf, oacc[d], 0, 0, 0);
-    }
+    pv_step(oacc, evt, EV_PITCH, (16 * u + 4 * fhalf) * 2, pf, frow);
   }
-  if (frow < T) {
-    const float inv = 1.0f / psum;
-    f16* orow = ob + (long)frow * p.so_seq;
-#pragma unroll
-    for (int d = 0; d < NDT; ++d)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int col = d * 32 + 8 * qd + 4 * fhalf;
-        if (col < D) {
-          f16x4 o, lo;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float val = oacc[d][4 * qd + r] * inv;
-            o[r] = (f16)val;
-            lo[r] = (f16)(val - (float)o[r]);
-          }
-          *reinterpret_cast<f16x4*>(orow + col) = o;
-          if (p.lo_off) *reinterpret_cast<f16x4*>(orow + p.lo_off + col) = lo;
-        }
-      }
-  }
+  if (frow < T) store_o_hilo<D>(ob + (long)frow * p.so_seq, oacc, 1.0f / psum, p.lo_off, fhalf);
 }
 
 template <int D>
@@ -1095,23 +810,7 @@ __global__ __launch_bounds__(256) void relpos16_kernel(const Rel16Params pp) {
     const f16* kb = p.k + bo * p.sk_out + bi * p.sk_in + head * D;
     const f16* vb = p.v + bo * p.sk_out + bi * p.sk_in + head * D;
     f16* ob = p.o + bo * p.so_out + bi * p.so_in + head * D;
-    // ---- V^T into LDS: unit = (key pair, 4 d)
-    for (int u = lane; u < 8 * (DV / 4); u += 64) {
-      const int kp = u / (DV / 4), dq = u - kp * (DV / 4);
-      const int key = 2 * kp;
-      const bool dok = dq * 4 < D;
-      f16x4 a, b;
-      if (dok && key < T) a = *reinterpret_cast<const f16x4*>(vb + (long)key * p.sk_seq + dq * 4);
-      else for (int e = 0; e < 4; ++e) a[e] = (f16)0.f;
-      if (dok && key + 1 < T) b = *reinterpret_cast<const f16x4*>(vb + (long)(key + 1) * p.sk_seq + dq * 4);
-      else for (int e = 0; e < 4; ++e) b[e] = (f16)0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        typedef f16 f16x2 __attribute__((ext_vector_type(2)));
-        f16x2 w = {a[e], b[e]};
-        *reinterpret_cast<f16x2*>(vt + (dq * 4 + e) * VT_PITCH + kp * 4) = w;
-      }
-    }
+    stage_vt<D, 16, 64>(vt, VT_PITCH, vb, p.sk_seq, 0, T, lane);
     // ---- S^T = K Q^T (K fragments are used once, Q fragments again for the table product)
     f16x8 qf[NKK];
     f32x16 sc = zero16;
@@ -1177,56 +876,16 @@ __global__ __launch_bounds__(256) void relpos16_kernel(const Rel16Params pp) {
     f32x16 oacc[NDT];
 #pragma unroll
     for (int d = 0; d < NDT; ++d) oacc[d] = zero16;
-    {
-      f16x8 pf;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pf[e] = (f16)sc[e];
-#pragma unroll
-      for (int d = 0; d < NDT; ++d) {
-        const unsigned char* vrow = vt + (d * 32 + frow) * VT_PITCH + 8 * fhalf;
-        const f16x4 lo = *reinterpret_cast<const f16x4*>(vrow);
-        const f16x4 hi = *reinterpret_cast<const f16x4*>(vrow + 16);
-        const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[d], 0, 0, 0);
-      }
-    }
+    pv_step(oacc, vt, VT_PITCH, 8 * fhalf, p_frag(sc, 0), frow);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {                       // 16 table slots per step: slot = 16 u + 4 fhalf + (e & 3) + 8 (e >> 2)
       f16x8 pf;
       const f16* prow = pb + trow * P_PITCH + 16 + 16 * u + 4 * fhalf - (T - 1) + trow;       // column of slot e = 0 (s = slot + t - (T-1))
 #pragma unroll
       for (int e = 0; e < 8; ++e) pf[e] = prow[(e & 3) + 8 * (e >> 2)];
-      const int jofs = (16 * u + 4 * fhalf) * 2;
-#pragma unroll
-      for (int d = 0; d < NDT; ++d) {
-        const unsigned char* erow = evt + (d * 32 + frow) * EV_PITCH + jofs;
-        const f16x4 lo = *reinterpret_cast<const f16x4*>(erow);
-        const f16x4 hi = *reinterpret_cast<const f16x4*>(erow + 16);
-        const f16x8 ef = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ef, pf, oacc[d], 0, 0, 0);
-      }
+      pv_step(oacc, evt, EV_PITCH, (16 * u + 4 * fhalf) * 2, pf, frow);
     }
-    if (frow < T) {
-      const float inv = 1.0f / psum;
-      f16* orow = ob + (long)frow * p.so_seq;
-#pragma unroll
-      for (int d = 0; d < NDT; ++d)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          const int col = d * 32 + 8 * qd + 4 * fhalf;
-          if (col < D) {
-            f16x4 o, lo;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float val = oacc[d][4 * qd + r] * inv;
-              o[r] = (f16)val;
-              lo[r] = (f16)(val - (float)o[r]);
-            }
-            *reinterpret_cast<f16x4*>(orow + col) = o;
-            if (p.lo_off) *reinterpret_cast<f16x4*>(orow + p.lo_off + col) = lo;
-          }
-        }
-    }
+    if (frow < T) store_o_hilo<D>(ob + (long)frow * p.so_seq, oacc, 1.0f / psum, p.lo_off, fhalf);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");        // this item's LDS reads before the next item's writes
   }
 }
@@ -1310,12 +969,7 @@ __global__ __launch_bounds__(256) void relpos_long_kernel(const RelLongParams pp
   const int tq = t0 + frow;                                      // this lane's query (local)
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   f16x8 qf[NKK];
-#pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) {
-    const int d0 = kk * 16 + fhalf * 8;
-    if (tq < Tq && d0 < D) qf[kk] = *reinterpret_cast<const f16x8*>(qb + (long)tq * p.sq_seq + d0);
-    else for (int e = 0; e < 8; ++e) qf[kk][e] = (f16)0.f;
-  }
+  load_row_frags<D>(qf, qb, tq, Tq, p.sq_seq, fhalf);
   // q_t . Ek[0] and q_t . Ek[2R]: A rows 0..15 = table row 0, rows 16..31 = table row 2R; accumulator r = 0 / 8 is row 4 fhalf / 16 + 4 fhalf
   float qe_lo, qe_hi;
   {
@@ -1337,25 +991,9 @@ __global__ __launch_bounds__(256) void relpos_long_kernel(const RelLongParams pp
     const int dmin = s0 - (t0a + 31), dmax = s0 + 31 - t0a;     // range of s - t' over the tile
     const int edge = dmin >= R ? 1 : (dmax <= -R ? -1 : 0);      // wave-uniform: +-1 = every pair clips to row 2R / row 0
     any_edge |= edge != 0;
-    // ---- V^T tile into LDS: unit = (key pair, 4 d)
-    for (int u = lane; u < 16 * (DV / 4); u += 64) {
-      const int kp = u / (DV / 4), dq = u - kp * (DV / 4);
-      const int key = s0 + 2 * kp;
-      const bool dok = dq * 4 < D;
-      f16x4 a, b;
-      if (dok && key < T) a = *reinterpret_cast<const f16x4*>(vb + (long)key * p.sk_seq + dq * 4);
-      else for (int e = 0; e < 4; ++e) a[e] = (f16)0.f;
-      if (dok && key + 1 < T) b = *reinterpret_cast<const f16x4*>(vb + (long)(key + 1) * p.sk_seq + dq * 4);
-      else for (int e = 0; e < 4; ++e) b[e] = (f16)0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        typedef f16 f16x2 __attribute__((ext_vector_type(2)));
-        f16x2 w = {a[e], b[e]};
-        *reinterpret_cast<f16x2*>(vt + (dq * 4 + e) * VT_PITCH + kp * 4) = w;
-      }
-    }
+    stage_vt<D, 32, 64>(vt, VT_PITCH, vb, p.sk_seq, s0, T, lane);
     // ---- S^T = K Q^T
-    f32x16 sc = zero16;
+    f32x16 sc[1] = {zero16};
     {
       const int key = s0 + frow;
 #pragma unroll
@@ -1364,7 +1002,7 @@ __global__ __launch_bounds__(256) void relpos_long_kernel(const RelLongParams pp
         f16x8 kf;
         if (key < T && d0 < D) kf = *reinterpret_cast<const f16x8*>(kb + (long)key * p.sk_seq + d0);
         else for (int e = 0; e < 8; ++e) kf[e] = (f16)0.f;
-        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], sc, 0, 0, 0);
+        sc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], sc[0], 0, 0, 0);
       }
     }
     const int jb = s0 - t0a - 31 + R;                            // table row of window slot 0
@@ -1386,64 +1024,25 @@ __global__ __launch_bounds__(256) void relpos_long_kernel(const RelLongParams pp
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // V^T / QE written by this wave, read back below by other lanes
-    // ---- scores of this lane's query t = frow: keys s0 + (r & 3) + 8 (r >> 2) + 4 fhalf
-    float mx = -INFINITY;
+    // ---- scores of this lane's query t = frow: keys s0 + (r & 3) + 8 (r >> 2) + 4 fhalf (finite maximum: key s0 < T exists)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int kl = (r & 3) + 8 * (r >> 2) + 4 * fhalf;
       const float rel = edge > 0 ? qe_hi : (edge < 0 ? qe_lo : qeb[(kl - frow + 31) * QE_PITCH + frow]);
-      const float v = (s0 + kl < T) ? sc[r] + rel : -INFINITY;
-      sc[r] = v;
-      mx = fmaxf(mx, v);
+      sc[0][r] = (s0 + kl < T) ? sc[0][r] + rel : -INFINITY;
     }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));                          // finite: key s0 < T exists
     // online softmax as attn_kernel: the running maximum only advances by more than 2^8; O, l and W carry the same stale factor
-    const float m_tile = mx * sl2;                               // scale > 0 (checked at launch)
-    const bool grow = m_tile - m_run > 8.0f;
-    if (__builtin_amdgcn_ballot_w64(grow) != 0) {
-      const float alpha = grow ? __builtin_amdgcn_exp2f(m_run - m_tile) : 1.0f;
-      l_run *= alpha;
-      w_lo *= alpha;
-      w_hi *= alpha;
-#pragma unroll
-      for (int d = 0; d < NDT; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-      m_run = grow ? m_tile : m_run;
-    }
-    const float neg_m = -m_run;
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], sl2, neg_m));
-      sc[r] = pv;
-      psum += pv;
-    }
-    psum += __shfl_xor(psum, 32);
-    l_run += psum;
+    const float psum = online_softmax_step(sc, sl2, m_run, l_run, oacc, [&](float alpha) { w_lo *= alpha; w_hi *= alpha; });
     if (edge > 0) w_hi += psum;
     if (edge < 0) w_lo += psum;
     // ---- O^T += V^T P^T
 #pragma unroll
-    for (int t2 = 0; t2 < 2; ++t2) {
-      f16x8 pf;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pf[e] = (f16)sc[8 * t2 + e];
-      const int kofs = (t2 * 16 + 4 * fhalf) * 2;
-#pragma unroll
-      for (int d = 0; d < NDT; ++d) {
-        const unsigned char* vrow = vt + (d * 32 + frow) * VT_PITCH + kofs;
-        const f16x4 lo = *reinterpret_cast<const f16x4*>(vrow);
-        const f16x4 hi = *reinterpret_cast<const f16x4*>(vrow + 16);
-        const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[d], 0, 0, 0);
-      }
-    }
+    for (int t2 = 0; t2 < 2; ++t2) pv_step(oacc, vt, VT_PITCH, (t2 * 16 + 4 * fhalf) * 2, p_frag(sc[0], t2), frow);
     if (edge == 0) {
       // ---- O^T += Ev_win^T Pskew^T: probabilities of query t at [t][key - s0] (over the QE rows, all read above)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const f16x4 pw = {(f16)sc[4 * g], (f16)sc[4 * g + 1], (f16)sc[4 * g + 2], (f16)sc[4 * g + 3]};
+        const f16x4 pw = {(f16)sc[0][4 * g], (f16)sc[0][4 * g + 1], (f16)sc[0][4 * g + 2], (f16)sc[0][4 * g + 3]};
         *reinterpret_cast<f16x4*>(pb + frow * P_PITCH + 8 * g + 4 * fhalf) = pw;
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1479,27 +1078,7 @@ __global__ __launch_bounds__(256) void relpos_long_kernel(const RelLongParams pp
         oacc[d][r] += w_lo * (float)ecol[0] + w_hi * (float)ecol[2 * R];
       }
   }
-  if (tq < Tq) {
-    const float inv = 1.0f / l_run;
-    f16* orow = ob + (long)tq * p.so_seq;
-#pragma unroll
-    for (int d = 0; d < NDT; ++d)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int col = d * 32 + 8 * qd + 4 * fhalf;
-        if (col < D) {
-          f16x4 o, lo;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float val = oacc[d][4 * qd + r] * inv;
-            o[r] = (f16)val;
-            lo[r] = (f16)(val - (float)o[r]);
-          }
-          *reinterpret_cast<f16x4*>(orow + col) = o;
-          if (p.lo_off) *reinterpret_cast<f16x4*>(orow + p.lo_off + col) = lo;
-        }
-      }
-  }
+  if (tq < Tq) store_o_hilo<D>(ob + (long)tq * p.so_seq, oacc, 1.0f / l_run, p.lo_off, fhalf);
 }
 
 template <int D>
@@ -1634,6 +1213,16 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* in, f16*
   for (int c = tid; c < cols; c += 256) y[c] = (f16)(__expf(x[c] * scale - mx) * inv);
 }
 
+// attn_kernel for head_dim D: one wave per (batch, head) for <= 32 queries (with the 32-key tile if the keys fit one), else 4 waves / 128 queries
+template <int D>
+void launch_attn(const AttnParams& p, int nbatch, hipStream_t s) {
+  const bool small = p.nq <= 32;
+  const dim3 g1(1, p.heads, nbatch), g4((p.nq + 127) / 128, p.heads, nbatch);
+  if (small && p.nk <= 32) hipLaunchKernelGGL((attn_kernel<1, D, 32>), g1, dim3(64), 0, s, p);
+  else if (small) hipLaunchKernelGGL((attn_kernel<1, D, 64>), g1, dim3(64), 0, s, p);
+  else hipLaunchKernelGGL((attn_kernel<4, D, 64>), g4, dim3(256), 0, s, p);
+}
+
 }  // namespace
 
 hipError_t t2v_launch_attention(const t2v_op& op, hipStream_t s) {
@@ -1660,44 +1249,15 @@ hipError_t t2v_launch_attention(const t2v_op& op, hipStream_t s) {
     const int n_pad = op.i[17];
     hipLaunchKernelGGL(vt_transpose_kernel, dim3(n_pad / 64, p.heads, nbatch), dim3(256), 0, s, p, vt, n_pad);
     if (op.i[18] == 4) hipLaunchKernelGGL((attn2_kernel<4>), dim3((p.nq + 127) / 128, p.heads, nbatch), dim3(256), 0, s, p, vt, n_pad);
-#ifdef T2V_ATTN2_EXPERIMENTS   // the score-pipelined variant: i[18] = 12 (4 waves, 3 per SIMD) / 16 (8 waves, 2 per SIMD) / 20 (8 waves, 3 per SIMD)
-    else if (op.i[18] == 12) hipLaunchKernelGGL((attn2p_kernel<4, 3>), dim3((p.nq + 127) / 128, p.heads, nbatch), dim3(256), 0, s, p, vt, n_pad);
-    else if (op.i[18] == 16) hipLaunchKernelGGL((attn2p_kernel<8, 2>), dim3((p.nq + 255) / 256, p.heads, nbatch), dim3(512), 0, s, p, vt, n_pad);
-    else if (op.i[18] == 20) hipLaunchKernelGGL((attn2p_kernel<8, 3>), dim3((p.nq + 255) / 256, p.heads, nbatch), dim3(512), 0, s, p, vt, n_pad);
-#endif
     else hipLaunchKernelGGL((attn2_kernel<8>), dim3((p.nq + 255) / 256, p.heads, nbatch), dim3(512), 0, s, p, vt, n_pad);
     return hipGetLastError();
   }
-  const bool small = p.nq <= 32;
-  static const bool prefetch_env = [] { const char* e = getenv("T2V_ATTN_PREFETCH"); return e ? atoi(e) != 0 : false; }();
-  const bool prefetch = prefetch_env && p.nk > KT_MAIN;
-  const dim3 g1(1, p.heads, nbatch), g4((p.nq + 127) / 128, p.heads, nbatch);
   switch (hd) {
-    case 40:
-      if (small && p.nk <= 32) hipLaunchKernelGGL((attn_kernel<1, 40, 32>), g1, dim3(64), 0, s, p);
-      else if (small) hipLaunchKernelGGL((attn_kernel<1, 40>), g1, dim3(64), 0, s, p);
-      else if (prefetch) hipLaunchKernelGGL((attn_kernel<4, 40, 64, true>), g4, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((attn_kernel<4, 40>), g4, dim3(256), 0, s, p);
-      break;
-    case 64:
-      if (small && p.nk <= 32) hipLaunchKernelGGL((attn_kernel<1, 64, 32>), g1, dim3(64), 0, s, p);
-      else if (small) hipLaunchKernelGGL((attn_kernel<1, 64>), g1, dim3(64), 0, s, p);
-      else if (prefetch) hipLaunchKernelGGL((attn_kernel<4, 64, 64, true>), g4, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((attn_kernel<4, 64>), g4, dim3(256), 0, s, p);
-      break;
-    case 80:
-      if (small && p.nk <= 32) hipLaunchKernelGGL((attn_kernel<1, 80, 32>), g1, dim3(64), 0, s, p);
-      else if (small) hipLaunchKernelGGL((attn_kernel<1, 80>), g1, dim3(64), 0, s, p);
-      else if (prefetch) hipLaunchKernelGGL((attn_kernel<4, 80, 64, true>), g4, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((attn_kernel<4, 80>), g4, dim3(256), 0, s, p);
-      break;
-    case 160:
-      if (small && p.nk <= 32) hipLaunchKernelGGL((attn_kernel<1, 160, 32>), g1, dim3(64), 0, s, p);
-      else if (small) hipLaunchKernelGGL((attn_kernel<1, 160>), g1, dim3(64), 0, s, p);
-      else hipLaunchKernelGGL((attn_kernel<4, 160>), g4, dim3(256), 0, s, p);
-      break;
-    default:
-      return hipErrorInvalidValue;
+    case 40: launch_attn<40>(p, nbatch, s); break;
+    case 64: launch_attn<64>(p, nbatch, s); break;
+    case 80: launch_attn<80>(p, nbatch, s); break;
+    case 160: launch_attn<160>(p, nbatch, s); break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }

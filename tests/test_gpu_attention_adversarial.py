@@ -12,8 +12,7 @@ interpreter.  Outputs are NaN-filled first and must come back finite; the rows a
 Tolerances are the suite's own for these kernels against an explicit reference on randn inputs: 2e-3 for the fp16 output, 1e-3 for hi + lo,
 with hi + lo closer than hi.  Measured values: profiles/attention_adversarial.txt.
 
-Out of scope: attn2p_kernel (built only under T2V_ATTN2_EXPERIMENTS), the T2V_ATTN_PREFETCH variants (the switch is read once per process)
-and the fused QKV + temporal-attention GEMM record (its logits come out of a GEMM and cannot be placed)."""
+Out of scope: the fused QKV + temporal-attention GEMM record (its logits come out of a GEMM and cannot be placed)."""
 import pytest
 import torch
 

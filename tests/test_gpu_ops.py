@@ -219,7 +219,7 @@ def test_layernorm(M, C):
 
 @pytest.mark.parametrize("kind,B,F,hw,heads,Lc", [("spatial", 1, 2, 1024, 5, 0), ("spatial", 2, 3, 256, 2, 0),
                                                   ("spatial", 1, 2, 16, 4, 0), ("spatial", 1, 1, 144, 3, 0),
-                                                  ("cross", 2, 3, 64, 2, 77), ("cross", 1, 2, 256, 5, 7),
+                                                  ("cross", 2, 3, 64, 2, 77), ("cross", 1, 2, 256, 5, 7), ("cross", 1, 2, 16, 5, 77),
                                                   ("temporal", 2, 24, 16, 3, 0), ("temporal", 1, 125, 4, 2, 0),
                                                   ("temporal", 1, 3, 64, 8, 0)])
 def test_attention(kind, B, F, hw, heads, Lc):
@@ -257,7 +257,7 @@ def test_attention(kind, B, F, hw, heads, Lc):
 
 @pytest.mark.parametrize("D", [40, 80, 160])
 @pytest.mark.parametrize("kind,B,F,hw,Lc", [("spatial", 1, 2, 256, 0), ("spatial", 1, 3, 20, 0), ("cross", 2, 2, 64, 77),
-                                             ("cross", 1, 1, 1024, 9)])
+                                             ("cross", 1, 1, 1024, 9), ("cross", 1, 2, 16, 77)])
 def test_attention_lvdm_head_dims(D, kind, B, F, hw, Lc):
     """8 heads of C/8 channels (VideoCrafter LVDM: head_dim 40 / 80 / 160); the zero-padding to the MFMA
     granularity must stay inside the kernel (the neighbouring head's columns are live data)."""
