@@ -26,20 +26,13 @@
 // (guide rule 21) and again on the read.
 #include "t2v_kernels.h"
 
-#define AS1 __attribute__((address_space(1)))
-#define AS3 __attribute__((address_space(3)))
-
 __device__ __attribute__((aligned(256))) unsigned char t2v_zero_page[256];
 
 namespace {
 
 constexpr int BK = 64;
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const AS1 void*)gsrc, (AS3 void*)lds_wave_base, 16, 0, 0);
-}
-
-// ---- fused epilogue on 4 consecutive output channels of one token ---------------------
+// ---- fused epilogue on 4 consecutive output channels of one token (splitk_reduce_kernel) ---
 __device__ __forceinline__ void epilogue_store(const GemmParams& p, int m, int n, float v0, float v1,
                                                float v2, float v3) {
   if (p.bias) {
@@ -210,13 +203,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
           src = p.A + row * p.lda + ci0 + xlchunk[j] * 8;
         }
       }
-      glds16(src, xt + (wave * XS + j) * 1024);
+      t2v_glds16(src, xt + (wave * XS + j) * 1024);
     }
 #pragma unroll
     for (int j = 0; j < WS; ++j) {
       const int kc = k0 + wlchunk[j] * 8;
       const void* src = (wrow[j] != nullptr && kc < p.K) ? (const void*)(wrow[j] + kc) : (const void*)zero;
-      glds16(src, wt + (wave * WS + j) * 1024);
+      t2v_glds16(src, wt + (wave * WS + j) * 1024);
     }
   };
 
@@ -267,6 +260,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
   }
 
   // ---- epilogue: lane holds token (lane & 31), channels 8q + 4*(lane>>5) + {0..3} -------
+  // Invariant (enforced on the host, t2v_launch_gemm): in here p.epi is T2V_EPI_NONE or T2V_EPI_GEGLU (T2V_EPI_TATTN exists only in
+  // gemm2.hip's TAT instantiation); everything else the executor has folded into NONE plus the pointers of the XE epilogues.
   if (p.epi == T2V_EPI_NONE) {      // row-coalesced through a per-wave LDS buffer (t2v_kernels.h); also the split-K slabs
     __syncthreads();                // every wave is done reading the operand stages
     if constexpr (XE == 2) {
@@ -285,6 +280,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
                               n0 + wn * TN * 32, blockIdx.y, tile_m * tiles_n + tile_n);
     return;
   }
+  if (p.splitk > 1) {               // GEGLU with split-K: the slab of this split; value * gelu(gate) runs in splitk_reduce_kernel
+    t2v_store_splitk_slab<TM, TN>(p, acc, lane, m0 + wm * TM * 32, n0 + wn * TN * 32, blockIdx.y);
+    return;
+  }
   const int mlane = lane & 31, nhalf = (lane >> 5) * 4;
 #pragma unroll
   for (int a = 0; a < TM; ++a) {
@@ -293,34 +292,14 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
 #pragma unroll
     for (int b = 0; b < TN; ++b) {
       const int nt = n0 + (wn * TN + b) * 32;  // first packed channel of this MFMA tile
-      if (p.splitk > 1) {
-        float* ws = p.ws + ((size_t)blockIdx.y * p.M + m) * p.N;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int n = nt + 8 * q + nhalf;
-          if (n < p.N) {
-            f32x4 o = {acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]};
-            *reinterpret_cast<f32x4*>(ws + n) = o;
-          }
-        }
-      } else if (p.epi == T2V_EPI_GEGLU) {
+      for (int qq = 0; qq < 2; ++qq) {
+        const int n_val = nt + 16 * qq + nhalf;
+        if (n_val < p.N) {
+          float v[4], g[4];
 #pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-          const int n_val = nt + 16 * qq + nhalf;
-          if (n_val < p.N) {
-            float v[4], g[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { v[r] = acc[a][b][8 * qq + r]; g[r] = acc[a][b][8 * qq + 4 + r]; }
-            epilogue_store_geglu(p, m, n_val, (nt >> 1) + 8 * qq + nhalf, v, g);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int n = nt + 8 * q + nhalf;
-          if (n < p.N)
-            epilogue_store(p, m, n, acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2],
-                           acc[a][b][4 * q + 3]);
+          for (int r = 0; r < 4; ++r) { v[r] = acc[a][b][8 * qq + r]; g[r] = acc[a][b][8 * qq + 4 + r]; }
+          epilogue_store_geglu(p, m, n_val, (nt >> 1) + 8 * qq + nhalf, v, g);
         }
       }
     }
@@ -355,86 +334,70 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) 
   }
 }
 
+constexpr int lds_of(int bm, int bn) { return 2 * (bm + bn) * BK * 2; }      // the two operand stages
+
+// One launch of one instantiation; the function-local flag = once per (instantiation, device).
+template <int BM, int BN, int WM, int WN, int GATHER, int XE = 0>
+hipError_t launch_one(const GemmParams& p, hipStream_t s) {
+  constexpr int lds = lds_of(BM, BN);
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+  auto k = gemm_kernel<BM, BN, WM, WN, GATHER, XE>;
+  static t2v_device_flags once;
+  (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once, s);
+  hipLaunchKernelGGL(k, dim3(tiles, p.splitk > 1 ? p.splitk : 1), dim3(WM * WN * 64), lds, s, p);
+  return hipGetLastError();
+}
+
+// The fused-norm instantiations (XE = 2 GroupNorm, 3 cross-tile LayerNorm): the grid barrier needs the whole launch resident — the grid
+// within what the occupancy API grants this instantiation on the stream's device (cached per instantiation and device); a grid the device
+// does not hold co-resident is cut into row chunks of whole tiles and whole instances (round 6)
+template <int BM, int BN, int WM, int WN, int GATHER, int XE>
+hipError_t launch_norm(const GemmParams& p, hipStream_t s) {
+  constexpr int lds = lds_of(BM, BN);
+  auto k = gemm_kernel<BM, BN, WM, WN, GATHER, XE>;
+  static t2v_device_flags once;
+  static int occ[T2V_MAX_DEVICES] = {};
+  (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once, s);
+  const long cap = t2v_grid_capacity(reinterpret_cast<const void*>(k), WM * WN * 64, lds, s, occ);
+  return t2v_launch_coresident(p, BM, (p.N + BN - 1) / BN, cap, XE == 3 ? BM : t2v_lcm(BM, p.gn_rows), XE == 3 ? BM * 16 : 2 * T2V_GN_PIECES * 16,
+                               [&](const GemmParams& q, int nwg) {
+    hipLaunchKernelGGL(k, dim3(nwg, 1), dim3(WM * WN * 64), lds, s, q);
+    return hipGetLastError();
+  });
+}
+
 template <int BM, int BN, int WM, int WN>
 hipError_t launch_tile(const GemmParams& pin, hipStream_t s) {
   GemmParams p = pin;
   p.panel = t2v_choose_panel(p, (p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  const dim3 grid(tiles, p.splitk > 1 ? p.splitk : 1);
-  const dim3 block(WM * WN * 64);
-  constexpr int lds = 2 * (BM + BN) * BK * 2;
   if (p.xa_k != nullptr) {         // fused to_q + text cross-attention (T2V_EPI_XATTN): the 128x128 tile = two heads per column tile, plain gather
     if constexpr (BM == 128 && BN == 128) {
-      static_assert(t2v_xattn_epilogue_lds(BM, BN) <= lds, "Q [BM][BN] fp16 re-uses the operand stages");
+      static_assert(t2v_xattn_epilogue_lds(BM, BN) <= lds_of(BM, BN), "Q [BM][BN] fp16 re-uses the operand stages");
       if (p.splitk != 1 || p.gather != T2V_GATHER_PLAIN) return hipErrorInvalidValue;
-      auto k = gemm_kernel<BM, BN, WM, WN, T2V_GATHER_PLAIN, 4>;
-      static t2v_device_flags once_xa;
-      (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once_xa, s);
-      hipLaunchKernelGGL(k, grid, block, lds, s, p);
-      return hipGetLastError();
+      return launch_one<BM, BN, WM, WN, T2V_GATHER_PLAIN, 4>(p, s);
     }
     return hipErrorInvalidValue;
   }
   if ((p.gn_out != nullptr && p.splitk == 1) || p.ln_x) {
-    // GroupNorm inside the epilogue: the 128x128 tile only; the grid barrier needs the whole launch resident (no split-K, the grid
-    // within what the occupancy API grants this instantiation on the stream's device)
+    // GroupNorm / cross-tile LayerNorm inside the epilogue: the 128x128 tile only, no split-K
     if constexpr (BM == 128 && BN == 128) {
-      static_assert(t2v_gn_epilogue_lds(WM * WN, BM / 32, BN) <= lds && t2v_lnx_epilogue_lds(WM * WN, WN, BM) <= lds, "the norm epilogues re-use the operand stages");
+      static_assert(t2v_gn_epilogue_lds(WM * WN, BM / 32, BN) <= lds_of(BM, BN) && t2v_lnx_epilogue_lds(WM * WN, WN, BM) <= lds_of(BM, BN),
+                    "the norm epilogues re-use the operand stages");
       if (p.splitk != 1 || !t2v_coop_allowed() || p.gather == T2V_GATHER_CONV3X3_C8) return hipErrorInvalidValue;
-      auto launch = [&](auto k, int* occ, t2v_device_flags& once) {
-        (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once, s);
-        // (round 6: a grid the device does not hold co-resident is cut into row chunks of whole tiles and whole instances)
-        const long cap = t2v_grid_capacity(reinterpret_cast<const void*>(k), WM * WN * 64, lds, s, occ);
-        return t2v_launch_coresident(p, BM, (p.N + BN - 1) / BN, cap, p.ln_x ? BM : t2v_lcm(BM, p.gn_rows), p.ln_x ? BM * 16 : 2 * T2V_GN_PIECES * 16,
-                                     [&](const GemmParams& q, int nwg) {
-          hipLaunchKernelGGL(k, dim3(nwg, 1), block, lds, s, q);
-          return hipGetLastError();
-        });
-      };
-      static int occ0[T2V_MAX_DEVICES] = {}, occ1[T2V_MAX_DEVICES] = {}, occ2[T2V_MAX_DEVICES] = {};
-      static t2v_device_flags g0, g1, g2;
-      static int occ3[T2V_MAX_DEVICES] = {};
-      static t2v_device_flags g3;
-      if (p.ln_x) return p.gather == T2V_GATHER_PLAIN ? launch(gemm_kernel<BM, BN, WM, WN, T2V_GATHER_PLAIN, 3>, occ3, g3) : hipErrorInvalidValue;
-      if (p.gather == T2V_GATHER_PLAIN) return launch(gemm_kernel<BM, BN, WM, WN, T2V_GATHER_PLAIN, 2>, occ0, g0);
-      if (p.gather == T2V_GATHER_CONV3X3) return launch(gemm_kernel<BM, BN, WM, WN, T2V_GATHER_CONV3X3, 2>, occ1, g1);
-      if (p.gather == T2V_GATHER_TCONV3) return launch(gemm_kernel<BM, BN, WM, WN, T2V_GATHER_TCONV3, 2>, occ2, g2);
+      if (p.ln_x) return p.gather == T2V_GATHER_PLAIN ? launch_norm<BM, BN, WM, WN, T2V_GATHER_PLAIN, 3>(p, s) : hipErrorInvalidValue;
+      if (p.gather == T2V_GATHER_PLAIN) return launch_norm<BM, BN, WM, WN, T2V_GATHER_PLAIN, 2>(p, s);
+      if (p.gather == T2V_GATHER_CONV3X3) return launch_norm<BM, BN, WM, WN, T2V_GATHER_CONV3X3, 2>(p, s);
+      if (p.gather == T2V_GATHER_TCONV3) return launch_norm<BM, BN, WM, WN, T2V_GATHER_TCONV3, 2>(p, s);
     }
     return hipErrorInvalidValue;
   }
   switch (p.gather) {
-    case T2V_GATHER_PLAIN: {
-      auto k = gemm_kernel<BM, BN, WM, WN, T2V_GATHER_PLAIN>;
-      static t2v_device_flags once0;
-      (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once0, s);
-      hipLaunchKernelGGL(k, grid, block, lds, s, p);
-      break;
-    }
-    case T2V_GATHER_CONV3X3: {
-      auto k = gemm_kernel<BM, BN, WM, WN, T2V_GATHER_CONV3X3>;
-      static t2v_device_flags once1;
-      (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once1, s);
-      hipLaunchKernelGGL(k, grid, block, lds, s, p);
-      break;
-    }
-    case T2V_GATHER_TCONV3: {
-      auto k = gemm_kernel<BM, BN, WM, WN, T2V_GATHER_TCONV3>;
-      static t2v_device_flags once2;
-      (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once2, s);
-      hipLaunchKernelGGL(k, grid, block, lds, s, p);
-      break;
-    }
-    case T2V_GATHER_CONV3X3_C8: {
-      auto k = gemm_kernel<BM, BN, WM, WN, T2V_GATHER_CONV3X3_C8>;
-      static t2v_device_flags once3;
-      (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once3, s);
-      hipLaunchKernelGGL(k, grid, block, lds, s, p);
-      break;
-    }
-    default:
-      return hipErrorInvalidValue;
+    case T2V_GATHER_PLAIN: return launch_one<BM, BN, WM, WN, T2V_GATHER_PLAIN>(p, s);
+    case T2V_GATHER_CONV3X3: return launch_one<BM, BN, WM, WN, T2V_GATHER_CONV3X3>(p, s);
+    case T2V_GATHER_TCONV3: return launch_one<BM, BN, WM, WN, T2V_GATHER_TCONV3>(p, s);
+    case T2V_GATHER_CONV3X3_C8: return launch_one<BM, BN, WM, WN, T2V_GATHER_CONV3X3_C8>(p, s);
+    default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 }  // namespace
@@ -448,23 +411,14 @@ hipError_t t2v_launch_splitk_reduce(const GemmParams& p, hipStream_t s) {
 
 hipError_t t2v_launch_gemm(const GemmParams& pin, hipStream_t s) {
   GemmParams p = pin;
-  {
-    const int KT = (p.K + BK - 1) / BK;
-    if (p.splitk > KT) p.splitk = KT;
-    if (p.splitk < 1) p.splitk = 1;
-    p.kt_per_split = (KT + p.splitk - 1) / p.splitk;
-    p.splitk = (KT + p.kt_per_split - 1) / p.kt_per_split;  // no empty splits
-  }
+  // the kernel's epilogue knows these and no other (the executor folds STATS / GN / XATTN into NONE + their pointers before it launches)
+  if (p.epi != T2V_EPI_NONE && p.epi != T2V_EPI_GEGLU) return hipErrorInvalidValue;
   hipError_t e;
   // Tile choice: 128x128 by default; 128x64 when the last 128-wide column tile would be at
   // most half full (N = 320, 960, 4, 8 ...), to avoid 25-97 % padded columns.
   const bool narrow = (p.N % 128 != 0) && (p.N % 128 <= 64);
-  {
-    const int bn = narrow ? 64 : 128;
-    const long tiles = (long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn);
-    // in-kernel fold by the last-arriving workgroup of a tile (t2v_epilogue_rows) where a ticket buffer is given; else the reduction kernel
-    if (p.splitk <= 1 || p.epi != T2V_EPI_NONE || tiles > T2V_SYNC_INTS || p.gn_out != nullptr) p.tickets = nullptr;
-  }
+  const int bn = narrow ? 64 : 128;
+  t2v_normalize_splitk(p, BK, (long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn));
   if (narrow)
     e = launch_tile<128, 64, 4, 1>(p, s);
   else

@@ -21,10 +21,6 @@
 // lane-linear) and again on the read.
 #include "t2v_kernels.h"
 
-#define AS1 __attribute__((address_space(1)))
-#define AS3 __attribute__((address_space(3)))
-
-
 namespace {
 
 __device__ __attribute__((aligned(256))) unsigned char g2_zero_page[256];
@@ -33,153 +29,15 @@ __device__ __attribute__((aligned(256))) unsigned char g2_zero_page[256];
 constexpr int G_CONV_UP = 100;
 constexpr int BM_OF(int wm, int tm) { return wm * tm * 32; }
 
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const AS1 void*)gsrc, (AS3 void*)lds_wave_base, 16, 0, 0);
-}
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// the same with a count that is a constant only after loop unrolling (the switch folds away); n < 0: no wait
-__device__ __forceinline__ void wait_vmcnt_n(int n) {
-#define T2V_W(N) case N: wait_vmcnt<N>(); break;
-  switch (n) {
-    T2V_W(0) T2V_W(1) T2V_W(2) T2V_W(3) T2V_W(4) T2V_W(5) T2V_W(6) T2V_W(7) T2V_W(8) T2V_W(9) T2V_W(10) T2V_W(11) T2V_W(12) T2V_W(13) T2V_W(14) T2V_W(15)
-    T2V_W(16) T2V_W(17) T2V_W(18) T2V_W(19) T2V_W(20) T2V_W(21) T2V_W(22) T2V_W(23) T2V_W(24) T2V_W(25) T2V_W(26) T2V_W(27) T2V_W(28) T2V_W(29) T2V_W(30)
-    T2V_W(31) T2V_W(32) T2V_W(33) T2V_W(34) T2V_W(35) T2V_W(36) T2V_W(37) T2V_W(38) T2V_W(39) T2V_W(40)
-    default: break;
-  }
-#undef T2V_W
-}
-
-// ---- epilogue helpers (identical semantics to gemm.hip) ----------------------------------
-__device__ __forceinline__ void epi_store(const GemmParams& p, int m, int n, float v0, float v1, float v2, float v3) {
-  if (p.bias) {
-    if (p.bias_m) {
-      const float b = p.bias[m];
-      v0 += b; v1 += b; v2 += b; v3 += b;
-    } else {
-      const f32x4 b = *reinterpret_cast<const f32x4*>(p.bias + n);
-      v0 += b[0]; v1 += b[1]; v2 += b[2]; v3 += b[3];
-    }
-  }
-  if (p.rowbias) {
-    const f32x4 b = *reinterpret_cast<const f32x4*>(p.rowbias + (size_t)(m / p.rows_per_batch) * p.ldrb + n);
-    v0 += b[0]; v1 += b[1]; v2 += b[2]; v3 += b[3];
-  }
-  if (p.act == 1) {
-    v0 = t2v_silu(v0); v1 = t2v_silu(v1); v2 = t2v_silu(v2); v3 = t2v_silu(v3);
-  } else if (p.act == 2) {      // ReLU (the depth adapter's ResnetBlock)
-    v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f);
-  }
-  if (p.res) {
-    const int mr = (p.res_wrap && m >= p.res_wrap) ? m - p.res_wrap : m;      // a residual shared by the cond | uncond pair: rows wrap once
-    const f32x4 r = *reinterpret_cast<const f32x4*>(p.res + (size_t)mr * p.ldr + n);
-    v0 += r[0]; v1 += r[1]; v2 += r[2]; v3 += r[3];
-  }
-  if (p.out_f32) {
-    f32x4 o = {v0, v1, v2, v3};
-    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n) = o;
-  } else {
-    f16x4 o = {(f16)v0, (f16)v1, (f16)v2, (f16)v3};
-    f16* dst = reinterpret_cast<f16*>(p.out) + (size_t)m * p.ldc + n;
-    *reinterpret_cast<f16x4*>(dst) = o;
-    if (p.out_lo) {       // low-order image of the rounding, beside the row's N values (GemmParams::out_lo)
-      const f16x4 l = {(f16)(v0 - (float)o[0]), (f16)(v1 - (float)o[1]), (f16)(v2 - (float)o[2]), (f16)(v3 - (float)o[3])};
-      *reinterpret_cast<f16x4*>(dst + p.N) = l;
-    }
-  }
-}
-
-__device__ __forceinline__ void epi_store_geglu(const GemmParams& p, int m, int n_val, int n_out, const float* v,
-                                                const float* g) {
-  float bv[4] = {0, 0, 0, 0}, bg[4] = {0, 0, 0, 0};
-  if (p.bias) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p.bias + n_val);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(p.bias + n_val + 8);
-    for (int r = 0; r < 4; ++r) { bv[r] = a[r]; bg[r] = b[r]; }
-  }
-  f16x4 o;
-  for (int r = 0; r < 4; ++r) o[r] = (f16)((v[r] + bv[r]) * t2v_gelu_erf(g[r] + bg[r]));
-  *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.out) + (size_t)m * p.ldc + n_out) = o;
-}
-
-#ifndef T2V_G2_PRIO
-#define T2V_G2_PRIO 1          // experiment switch: 0 no priorities, 1 the MFMA segment at priority 1, 2 the load segment at priority 1
-#endif
-#ifndef T2V_G2_DMAFIRST
-#define T2V_G2_DMAFIRST 0      // experiment switch: 1 = the phase's DMA pieces before its fragment reads
-#endif
-// ---- region schedule of the staggered two-group main loop (PP == 4, round 6) -----------------------------------------------------------
-// A k-tile is cut into P = (TM / 2) * TN phases of 8 MFMAs (one PAIR of token sub-tiles x one weight sub-tile x BK); the operands of a
-// k-tile are staged as REGIONS — X pair a (read by every wave in phase a * TN only) and W sub-tile b (read in phase b only: the
-// fragments stay in registers for the second pair) — so that a region's LDS can be refilled for k-tile t + 2 two phases after its
-// only read in k-tile t, long before the rest of the buffer is free.  The table below places every DMA piece of a wave in the
-// earliest phase its region allows (at most CAP pieces per phase) and derives, per phase, the `s_waitcnt vmcnt(N)` that retires
-// exactly the regions first read in the NEXT phase: nothing is ever drained, every piece has about one whole k-tile to land.
-template <int WM, int WN, int TM, int TN>
-struct G2Sched {
-  static constexpr int NAP = TM / 2, P = NAP * TN;
-  static constexpr int XR = WM, WR = WN / 2;                 // DMA pieces per wave per X-pair region / per W region
-  static constexpr int NREG = NAP + TN, LPS = NAP * XR + TN * WR;
-  static constexpr int CAP = (LPS + P - 1) / P;
-  int u[LPS] = {};           // piece j is staged in phase u % P of k-tile T for k-tile T + 2 - u / P
-  int pos[LPS] = {};         // position of piece j in the issue stream of one period
-  int vm[P] = {};            // vmcnt after the staging of phase q (-1: no region becomes due)
-  static constexpr int first_of(int r) { return r < NAP ? r * TN : r - NAP; }
-  static constexpr int region_of(int j) { return j < NAP * XR ? j / XR : NAP + (j - NAP * XR) / WR; }
-  constexpr G2Sched() {
-    int order[NREG] = {};
-    bool used[NREG] = {};
-    for (int i = 0; i < NREG; ++i) {             // regions by the phase they become free (= read phase + 2), X before W
-      int best = -1;
-      for (int r = 0; r < NREG; ++r)
-        if (!used[r] && (best < 0 || first_of(r) < first_of(best))) best = r;
-      used[best] = true;
-      order[i] = best;
-    }
-    int cur = 0, cnt = 0, n = 0;
-    for (int i = 0; i < NREG; ++i) {
-      const int r = order[i], f = first_of(r) + 2;
-      for (int j = 0; j < LPS; ++j) {
-        if (region_of(j) != r) continue;
-        if (f > cur) { cur = f; cnt = 0; }
-        u[j] = cur;
-        pos[j] = n++;
-        if (++cnt == CAP) { ++cur; cnt = 0; }
-      }
-    }
-    for (int q = 0; q < P; ++q) {
-      const int due = (q + 1) % P, t_req = (q + 1) / P;       // regions first read in the next phase (of k-tile t_req relative to this one)
-      int best = -1;
-      for (int j = 0; j < LPS; ++j) {
-        if (first_of(region_of(j)) != due) continue;
-        const int gj = P * (t_req - 2) + u[j];              // when piece j of that k-tile was issued (this k-tile's phase 0 = 0)
-        int c = 0;
-        for (int k = 0; k < LPS; ++k)
-          for (int m = -4; m <= 2; ++m) {
-            const int g = u[k] + P * m;
-            if ((g > gj && g <= q) || (g == gj && pos[k] > pos[j])) ++c;
-          }
-        if (best < 0 || c < best) best = c;
-      }
-      vm[q] = best;
-    }
-  }
-  constexpr bool feasible() const {
-    for (int j = 0; j < LPS; ++j)
-      if (u[j] > 2 * P + first_of(region_of(j)) - 1 || u[j] >= 2 * P) return false;
-    return true;
-  }
-};
-
 // WM x WN waves; each wave owns TM x TN MFMA tiles (32 tokens x 32 channels each).
 // XE: extra epilogue of the plain (T2V_EPI_NONE) path — 0 none, 1 fused LayerNorm second output (whole-row tiles), 2 fused GroupNorm
 // (+SiLU) of the result with a grid barrier (T2V_EPI_GN); separate instantiations, so the plain kernels keep their register budgets.
-template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int PP, int XE = 0, bool TAT = false>
+template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int XE = 0, bool TAT = false>
 __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmParams p) {
   constexpr int NW = WM * WN;
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -191,8 +49,6 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
   constexpr int XPW = XSLABS / NW;
   constexpr int WPW = (WSLABS + NW - 1) / NW;                // the last may be a dummy piece
   constexpr int LPS = XPW + WPW;                             // DMA instructions per wave per stage
-  constexpr bool REGION = PP == 4;                           // pieces grouped by region (G2Sched) instead of interleaved over the tile
-  static_assert(!REGION || (NW == 8 && TM % 2 == 0 && (WN == 2 || WN == 4) && WSLABS % NW == 0), "region schedule: 8 waves, token sub-tiles in pairs");
   constexpr int STAGE_BYTES = (XSLABS + WSLABS) * 1024;
   constexpr int DUMMY_OFF = STAGES * STAGE_BYTES;            // 1 KiB scratch for dummy pieces
   static_assert(LPS * (STAGES - 1) < 64, "vmcnt is a 6-bit counter");
@@ -235,25 +91,9 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
   unsigned xmask[XPW];             // conv: bit t set <=> tap t of this row is inside the image / clip
   long xoff[general ? XPW : 1];    // only the upsample path keeps per-row coordinates
   int xy[general ? XPW : 1], xx[general ? XPW : 1];
-  // first tile row of DMA piece j of this wave.  Interleaved: piece s = wave + j * NW of the tile.  Region order (PP == 4): X piece
-  // j = a * WM + i is piece idx = wave + 8 i of the WM * 8 pieces of pair a (rows wm' * TM * 32 + a * 64 + ...), W piece j = b * (WN / 2) + i
-  // piece idx = wave + 8 i of the WN * 4 pieces of weight sub-tile b (rows wn' * TN * 32 + b * 32 + ...)
-  auto xrow0 = [&](int j) {
-    if constexpr (REGION) {
-      const int a = j / WM, idx = wave + 8 * (j % WM);
-      return (idx >> 3) * (TM * 32) + a * 64 + (idx & 7) * 8;
-    } else {
-      return (wave + j * NW) * RPS;
-    }
-  };
-  auto wrow0 = [&](int j) {
-    if constexpr (REGION) {
-      const int b = j / (WN / 2), idx = wave + 8 * (j % (WN / 2));
-      return (idx >> 2) * (TN * 32) + b * 32 + (idx & 3) * 8;
-    } else {
-      return (wave + j * NW) * RPS;
-    }
-  };
+  // first tile row of DMA piece j of this wave: the pieces are interleaved over the tile, piece s = wave + j * NW
+  auto xrow0 = [&](int j) { return (wave + j * NW) * RPS; };
+  auto wrow0 = [&](int j) { return (wave + j * NW) * RPS; };
 #pragma unroll
   for (int j = 0; j < XPW; ++j) {
     const int r = xrow0(j) + lrow;                // row inside the token tile
@@ -273,11 +113,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
           xptr[j] = reinterpret_cast<const unsigned char*>(p.A + mm * p.lda + (long)kt_begin * BK + lc * 8);
           xstep[j] = STEP;
         }
-      } else if (valid || REGION) {
-        // (region schedule: rows past M read the last row instead of the zero page — their results are never stored — so that every
-        //  pointer advances by the same constant and no per-piece step register is needed)
-        const int mc = REGION ? min(m, p.M - 1) : m;
-        const int ma = (p.a_wrap && mc >= p.a_wrap) ? mc - p.a_wrap : mc;     // shared (one-sample) operand: rows wrap once
+      } else if (valid) {
+        const int ma = (p.a_wrap && m >= p.a_wrap) ? m - p.a_wrap : m;     // shared (one-sample) operand: rows wrap once
         xptr[j] = reinterpret_cast<const unsigned char*>(p.A + (long)ma * p.lda + (long)kt_begin * BK + lc * 8);
         xstep[j] = STEP;
       }
@@ -321,9 +158,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
     const int r = wrow0(j) + lrow;               // row inside the weight tile
     const int n = n0 + r;
     wdummy[j] = wrow0(j) >= BN;                  // wave-uniform
-    const bool ok = REGION || (!wdummy[j] && n < p.N);
-    const int nc = REGION ? min(n, p.N - 1) : n;     // (region schedule: channels past N read the last row, see the token rows above)
-    wptr[j] = ok ? reinterpret_cast<const unsigned char*>(p.W + (size_t)nc * p.ldw + kt_begin * BK + (pchunk ^ swz(r)) * 8) : zero;
+    const bool ok = !wdummy[j] && n < p.N;
+    wptr[j] = ok ? reinterpret_cast<const unsigned char*>(p.W + (size_t)n * p.ldw + kt_begin * BK + (pchunk ^ swz(r)) * 8) : zero;
     wstep[j] = ok ? STEP : 0;
   }
 
@@ -380,11 +216,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
     return wdummy[jw] ? (smem + DUMMY_OFF) : (base + (XSLABS + wrow0(jw) / RPS) * 1024);
   };
   auto stage_piece = [&](int slot, int j) {
-#ifdef T2V_G2_NODMA      // timing experiment only (wrong results): the main loop WITHOUT its operand DMA — what do the LDS-DMA instructions cost?
-    if (staged >= STAGES - 1) return;
-#endif
     const void* src = piece_src(j);
-    glds16(src, piece_dst(slot, j));
+    t2v_glds16(src, piece_dst(slot, j));
   };
   auto stage_end = [&]() {
     if (GATHER != T2V_GATHER_PLAIN && live) {
@@ -401,15 +234,13 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-  // prologue: STAGES-1 k-tiles in flight (the register-staged schedule, PP == 3, has its own)
-  if constexpr (PP != 3 && PP != 4) {
+  // prologue: STAGES-1 k-tiles in flight
 #pragma unroll
-    for (int g = 0; g < STAGES - 1; ++g) {
-      stage_begin();
+  for (int g = 0; g < STAGES - 1; ++g) {
+    stage_begin();
 #pragma unroll
-      for (int j = 0; j < LPS; ++j) stage_piece(g, j);
-      stage_end();
-    }
+    for (int j = 0; j < LPS; ++j) stage_piece(g, j);
+    stage_end();
   }
 
   // fragment read addressing: lane reads row (tile_row0 + lane&31), logical chunk kk*2 + (lane>>5);
@@ -429,74 +260,56 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
     wsw[b] = swz(r) << 4;
   }
 
+  // Main loop: ONE schedule, lock-step — every wave waits for its own pieces, meets the barrier, then interleaves the next tile's DMA with
+  // this tile's fragment reads and MFMAs.  Four other schedules were built, parity-tested, measured against it and not selected:
+  //   round 1: two wave groups one barrier apart, the next k-tile's DMA drained with vmcnt(0) (tiles 6 / 7)                     = lock-step +-3 %
+  //   round 5: the next k-tile's first fragments prefetched across the barrier (tiles 13-17)                                       -1.5 .. +3.7 %
+  //   round 5: operands staged through registers instead of LDS-DMA (tiles 18-21)                                                    +4 % / -1 .. -11 %
+  //   round 6: two staggered groups, region-granular staging two k-tiles ahead, counted vmcnt only (tiles 22-24)                    +-3 % long K, -7 .. -20 % short K
+  // Why none of them moves the number: profiles/r05_gemm_mainloop_findings.txt and profiles/r06_gemm_mainloop_findings.txt (the loop
+  // runs the same cycles at ~62 % MFMA busy under every schedule; on random operands the chip clocks 1.55-1.68 GHz against 2.3 GHz on
+  // zeros — the ceiling is power).  Their code (this file's experiments .inc and the build switches around this loop) last existed
+  // in commit d7cc668.
   constexpr int KSTEPS = BK / 16;
-  if constexpr (PP == 0) {
-    int slot = 0;
-#ifdef T2V_G2_TIMING     // experiment build (tools/build_variant.py): where does a wave park in a k-tile?  cycles -> p.ws[wave slot][4]
-    unsigned long long tm_vm = 0, tm_bar = 0, tm_lds = 0;
-    const unsigned long long tm_begin = clock64();
-#endif
-    for (int t = 0; t < nkt; ++t) {
-#ifdef T2V_G2_TIMING
-      const unsigned long long tm0 = clock64();
-#endif
-      wait_vmcnt<LPS*(STAGES - 2)>();
-#ifdef T2V_G2_TIMING
-      const unsigned long long tm1 = clock64();
-#endif
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-#ifdef T2V_G2_TIMING
-      const unsigned long long tm2 = clock64();
-      tm_vm += tm1 - tm0; tm_bar += tm2 - tm1;
-#endif
-      int fs = slot + STAGES - 1;
-      if (fs >= STAGES) fs -= STAGES;
-      stage_begin();
-      const unsigned char* st = smem + slot * STAGE_BYTES;
-  #pragma unroll
-      for (int kk = 0; kk < KSTEPS; ++kk) {
-        const int lc4 = (kk * 2 + fhalf) << 4;
-        f16x8 xf[TM], wf[TN];
-  #pragma unroll
-        for (int a = 0; a < TM; ++a) xf[a] = *reinterpret_cast<const f16x8*>(st + xbase[a] + (lc4 ^ xsw[a]));
-  #pragma unroll
-        for (int b = 0; b < TN; ++b) wf[b] = *reinterpret_cast<const f16x8*>(st + wbase[b] + (lc4 ^ wsw[b]));
-#ifdef T2V_G2_TIMING
-        if (kk == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tm_lds += clock64() - tm2; }
-#endif
-        // this k-step's share of the next tile's DMA, issued between the fragment reads and the MFMAs.
-        // With a 2-deep ring the pieces must land before the next barrier, so they go out in the first
-        // half of the k-tile; with 3 stages they have a whole extra k-tile and are spread over all steps.
-        constexpr int SPREAD = STAGES == 2 ? KSTEPS / 2 : KSTEPS;
-        if (kk < SPREAD) {
-  #pragma unroll
-          for (int j = (LPS * kk) / SPREAD; j < (LPS * (kk + 1)) / SPREAD; ++j) stage_piece(fs, j);
-        }
-  #pragma unroll
-        for (int a = 0; a < TM; ++a)
-  #pragma unroll
-          for (int b = 0; b < TN; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[b], xf[a], acc[a][b], 0, 0, 0);
+  int slot = 0;
+  for (int t = 0; t < nkt; ++t) {
+    wait_vmcnt<LPS*(STAGES - 2)>();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    int fs = slot + STAGES - 1;
+    if (fs >= STAGES) fs -= STAGES;
+    stage_begin();
+    const unsigned char* st = smem + slot * STAGE_BYTES;
+#pragma unroll
+    for (int kk = 0; kk < KSTEPS; ++kk) {
+      const int lc4 = (kk * 2 + fhalf) << 4;
+      f16x8 xf[TM], wf[TN];
+#pragma unroll
+      for (int a = 0; a < TM; ++a) xf[a] = *reinterpret_cast<const f16x8*>(st + xbase[a] + (lc4 ^ xsw[a]));
+#pragma unroll
+      for (int b = 0; b < TN; ++b) wf[b] = *reinterpret_cast<const f16x8*>(st + wbase[b] + (lc4 ^ wsw[b]));
+      // this k-step's share of the next tile's DMA, issued between the fragment reads and the MFMAs.
+      // With a 2-deep ring the pieces must land before the next barrier, so they go out in the first
+      // half of the k-tile; with 3 stages they have a whole extra k-tile and are spread over all steps.
+      constexpr int SPREAD = STAGES == 2 ? KSTEPS / 2 : KSTEPS;
+      if (kk < SPREAD) {
+#pragma unroll
+        for (int j = (LPS * kk) / SPREAD; j < (LPS * (kk + 1)) / SPREAD; ++j) stage_piece(fs, j);
       }
-      stage_end();
-      slot = slot + 1 == STAGES ? 0 : slot + 1;
+#pragma unroll
+      for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[b], xf[a], acc[a][b], 0, 0, 0);
     }
-#ifdef T2V_G2_TIMING
-    if (lane == 0 && p.ws != nullptr && p.splitk == 1) {
-      float* dst = p.ws + ((size_t)blockIdx.x * NW + wave) * 4;
-      dst[0] = (float)tm_vm; dst[1] = (float)tm_bar; dst[2] = (float)tm_lds; dst[3] = (float)(clock64() - tm_begin);
-    }
-#endif
+    stage_end();
+    slot = slot + 1 == STAGES ? 0 : slot + 1;
   }
-#ifdef T2V_G2_EXPERIMENTS
-#include "gemm2_experiments.inc"
-#else
-  static_assert(PP == 0, "experimental schedules: build with -DT2V_G2_EXPERIMENTS");
-#endif
   wait_vmcnt<0>();   // drain the zero-page loads of the dead stages before the LDS goes away
 
   // ---- epilogue ---------------------------------------------------------------------------------
+  // Invariant (enforced on the host, launch_cfg): in here p.epi is T2V_EPI_NONE or T2V_EPI_GEGLU — or T2V_EPI_TATTN, in the TAT
+  // instantiation only.  Everything else the executor has folded into NONE plus the pointers of the XE epilogues.
   if constexpr (TAT) {
     // Fused temporal self-attention (t2v_model.py:716-767 with CrossAttention :540-584): this tile holds q | k | v (64 channels
     // each: ONE head, the weight rows are packed head-major) of all F frames of p.tpix pixels.  The accumulators go to LDS as
@@ -675,47 +488,11 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
     }
     return;
   }
-#pragma unroll
-  for (int a = 0; a < TM; ++a) {
-    const int m = m0 + (wm * TM + a) * 32 + mlane;
-    if (m >= p.M) continue;
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-      const int nt = n0 + (wn * TN + b) * 32;
-      if (p.splitk > 1) {
-        float* ws = p.ws + ((size_t)blockIdx.y * p.M + m) * p.N;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int n = nt + 8 * q + nhalf;
-          if (n < p.N) {
-            f32x4 o = {acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]};
-            *reinterpret_cast<f32x4*>(ws + n) = o;
-          }
-        }
-      } else if (p.epi == T2V_EPI_GEGLU) {
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-          const int n_val = nt + 16 * qq + nhalf;
-          if (n_val < p.N) {
-            float v[4], g[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { v[r] = acc[a][b][8 * qq + r]; g[r] = acc[a][b][8 * qq + 4 + r]; }
-            epi_store_geglu(p, m, n_val, (nt >> 1) + 8 * qq + nhalf, v, g);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int n = nt + 8 * q + nhalf;
-          if (n < p.N)
-            epi_store(p, m, n, acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]);
-        }
-      }
-    }
-  }
+  // GEGLU with split-K: the slab of this split; value * gelu(gate) runs in splitk_reduce_kernel (gemm.hip)
+  t2v_store_splitk_slab<TM, TN>(p, acc, lane, m0 + wm * TM * 32, n0 + wn * TN * 32, blockIdx.y);
 }
 
-template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int PP, int XE = 0, bool TAT = false>
+template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int XE = 0, bool TAT = false>
 hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   // TAT: the attention epilogue re-uses the operand ring for q | k (BM x 272 B) and V^T (<= 12 pixels x 64 x 72 B)
@@ -727,7 +504,7 @@ hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
                           : (XE == 2 && gn_lds > ring ? gn_lds : (XE == 3 && lnx_lds > ring ? lnx_lds : (XE == 4 && xa_lds > ring ? xa_lds : ring)));
   const int tiles_n = (p.N + BN - 1) / BN;
   const int tiles = ((p.M - p.m_begin + BM - 1) / BM) * tiles_n;
-  auto k = gemm2_kernel<WM, WN, TM, TN, BK, STAGES, MINW, GATHER, PP, XE, TAT>;
+  auto k = gemm2_kernel<WM, WN, TM, TN, BK, STAGES, MINW, GATHER, XE, TAT>;
   static t2v_device_flags attr_set;     // once per (instantiation, device): the call costs microseconds on the host
   {
     const hipError_t e = t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, attr_set, s);
@@ -750,89 +527,75 @@ hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int PP = 0>
+template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW>
 hipError_t launch_cfg(const GemmParams& pin, hipStream_t s) {
   GemmParams p = pin;
-  const int KT = (p.K + BK - 1) / BK;
-  if (p.splitk > KT) p.splitk = KT;
-  if (p.splitk < 1) p.splitk = 1;
-  p.kt_per_split = (KT + p.splitk - 1) / p.splitk;
-  p.splitk = (KT + p.kt_per_split - 1) / p.kt_per_split;  // no empty splits
+  // the kernel's epilogue knows these and no other (the executor folds STATS / GN / XATTN into NONE + their pointers before it launches);
+  // TATTN: the plain gather only, and below only the 192x192 configuration takes it
+  if (p.epi != T2V_EPI_NONE && p.epi != T2V_EPI_GEGLU && !(p.epi == T2V_EPI_TATTN && p.gather == T2V_GATHER_PLAIN)) return hipErrorInvalidValue;
   {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    p.panel = t2v_choose_panel(p, (p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
-    const long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    // in-kernel fold by the last-arriving workgroup of a tile (t2v_epilogue_rows) where a ticket buffer is given; else the reduction kernel
-    if (p.splitk <= 1 || p.epi != T2V_EPI_NONE || tiles > T2V_SYNC_INTS || p.gn_out != nullptr) p.tickets = nullptr;
+    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    p.panel = t2v_choose_panel(p, tiles_m, tiles_n);
+    t2v_normalize_splitk(p, BK, (long)tiles_m * tiles_n);
   }
   // tiles with a T2V_EPI_GN instantiation (validated by the executor): the whole-row tiles 8 / 11, and the 128-row tiles 3 / 5
-  constexpr bool GN_TILE = PP != 1 && PP != 4 && (((WM == 6 || WM == 4) && WN == 2 && TM == 1 && TN == 5) || (WM == 2 && WN == 4 && TM == 2 && (TN == 1 || TN == 2)));
+  constexpr bool GN_TILE = ((WM == 6 || WM == 4) && WN == 2 && TM == 1 && TN == 5) || (WM == 2 && WN == 4 && TM == 2 && (TN == 1 || TN == 2));
   // (with split-K the norm runs in the reduction's launch instead: any tile, t2v_launch_splitk_reduce_gn below)
   const bool gn_here = p.gn_out != nullptr && p.splitk == 1;
   if (gn_here && (!GN_TILE || (p.gather == T2V_GATHER_CONV3X3 && p.up))) return hipErrorInvalidValue;
   // ... and with a cross-tile LayerNorm instantiation: 5 (128x128), 12 (64x64), 9 (192x256), 3 (128x256); plain gather only
-  constexpr bool LNX_TILE = PP != 1 && PP != 4 && ((WM == 2 && WN == 4 && TM == 2 && (TN == 1 || TN == 2)) || (WM == 2 && WN == 2 && TM == 1 && TN == 1) ||
-                                    (WM == 6 && WN == 2 && TM == 1 && TN == 4));
+  constexpr bool LNX_TILE = (WM == 2 && WN == 4 && TM == 2 && (TN == 1 || TN == 2)) || (WM == 2 && WN == 2 && TM == 1 && TN == 1) ||
+                            (WM == 6 && WN == 2 && TM == 1 && TN == 4);
   if (p.ln_x && (!LNX_TILE || p.gather != T2V_GATHER_PLAIN)) return hipErrorInvalidValue;
   hipError_t e;
-#ifdef T2V_G2_DEV        // development build (seconds instead of minutes): the plain gather and the 3x3 convolution, no fused-norm instantiations
-  if (p.gather == T2V_GATHER_PLAIN && p.epi != T2V_EPI_TATTN && p.xa_k == nullptr && p.ln_out == nullptr && !gn_here && !p.ln_x)
-    e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, PP>(p, s);
-  else if (p.gather == T2V_GATHER_CONV3X3 && !p.up && !gn_here)
-    e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, PP>(p, s);
-  else
-    return hipErrorInvalidValue;
-  if (e != hipSuccess) return e;
-  if (p.splitk > 1 && p.tickets == nullptr) e = p.gn_out != nullptr ? t2v_launch_splitk_reduce_gn(p, s) : t2v_launch_splitk_reduce(p, s);
-  return e;
-#else
   switch (p.gather) {
     case T2V_GATHER_PLAIN:
-      if constexpr (WM == 6 && WN == 2 && TM == 1 && TN == 3 && PP == 0) {
+      if constexpr (WM == 6 && WN == 2 && TM == 1 && TN == 3) {
         if (p.epi != T2V_EPI_TATTN || p.splitk != 1 || p.tpix < 1 || p.tpix > 12 || p.tpix * p.F > BM_OF(WM, TM) || p.F > 32) return hipErrorInvalidValue;
-        e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, PP, 0, true>(p, s);
+        e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 0, true>(p, s);
         break;
       }
       if (p.epi == T2V_EPI_TATTN) return hipErrorInvalidValue;
-      if constexpr ((WM == 6 || WM == 4) && WN == 2 && TM == 1 && TN == 5 && PP == 0) {      // whole-row tiles: 192x320 / 128x320
+      if constexpr ((WM == 6 || WM == 4) && WN == 2 && TM == 1 && TN == 5) {      // whole-row tiles: 192x320 / 128x320
         if (p.xa_k != nullptr) {      // fused to_q + text cross-attention (validated: N == 320 = 5 heads, fp16 out, no split-K)
-          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, PP, 4>(p, s);
+          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 4>(p, s);
           break;
         }
       }
-      if constexpr (WM == 2 && WN == 4 && TM == 2 && TN == 1 && PP == 0) {                  // 128x128 on 8 waves (tile 5): two heads per column tile
+      if constexpr (WM == 2 && WN == 4 && TM == 2 && TN == 1) {                  // 128x128 on 8 waves (tile 5): two heads per column tile
         if (p.xa_k != nullptr) {
-          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, PP, 4>(p, s);
+          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 4>(p, s);
           break;
         }
       }
       if (p.xa_k != nullptr) return hipErrorInvalidValue;
-      if constexpr ((WM == 6 || WM == 4) && WN == 2 && (TM == 1 || (WM == 4 && TM == 2)) && TN == 5 && PP != 1) {      // whole-row tiles: 192x320 / 128x320 / 256x320
+      if constexpr ((WM == 6 || WM == 4) && WN == 2 && (TM == 1 || (WM == 4 && TM == 2)) && TN == 5) {      // whole-row tiles: 192x320 / 128x320 / 256x320
         if (p.ln_out != nullptr) {
-          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, PP, 1>(p, s);
+          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 1>(p, s);
           break;
         }
       }
       if constexpr (GN_TILE) {
-        if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, PP, 2>(p, s); break; }
+        if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 2>(p, s); break; }
       }
       if constexpr (LNX_TILE) {
-        if (p.ln_x) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, PP, 3>(p, s); break; }
+        if (p.ln_x) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 3>(p, s); break; }
       }
-      e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, PP>(p, s);
+      e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN>(p, s);
       break;
     case T2V_GATHER_CONV3X3:
       if constexpr (GN_TILE) {
-        if (gn_here && !p.up) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, PP, 2>(p, s); break; }
+        if (gn_here && !p.up) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, 2>(p, s); break; }
       }
-      if (p.up) e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, G_CONV_UP, PP>(p, s);
-      else e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, PP>(p, s);
+      if (p.up) e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, G_CONV_UP>(p, s);
+      else e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3>(p, s);
       break;
     case T2V_GATHER_TCONV3:
       if constexpr (GN_TILE) {
-        if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_TCONV3, PP, 2>(p, s); break; }
+        if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_TCONV3, 2>(p, s); break; }
       }
-      e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_TCONV3, PP>(p, s);
+      e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_TCONV3>(p, s);
       break;
     default: return hipErrorInvalidValue;
   }
@@ -840,7 +603,6 @@ hipError_t launch_cfg(const GemmParams& pin, hipStream_t s) {
   // (split-K whose result feeds a fused GroupNorm: the reduction is the loader of a cooperative GroupNorm launch, norm.hip)
   if (p.splitk > 1 && p.tickets == nullptr) e = p.gn_out != nullptr ? t2v_launch_splitk_reduce_gn(p, s) : t2v_launch_splitk_reduce(p, s);
   return e;
-#endif
 }
 
 }  // namespace
@@ -849,41 +611,6 @@ hipError_t launch_cfg(const GemmParams& pin, hipStream_t s) {
 // (few-row levels: latency-bound, keep 96 KiB per CU in flight) — 64-wide k-tiles
 // (full 128-byte lines per row = one conv reduction chunk), 2-3 stage ring, one workgroup per CU.
 hipError_t t2v_launch_gemm2(const GemmParams& p, int tile, hipStream_t s) {
-#ifdef T2V_G2_DEVMIN
-  switch (tile) {
-    case 1: return launch_cfg<2, 4, 4, 2, 64, 2, 2>(p, s);
-    case 22: return launch_cfg<2, 4, 4, 2, 64, 2, 2, 4>(p, s);
-    default: return hipErrorInvalidValue;
-  }
-#endif
-#ifdef T2V_G2_DEV
-  switch (tile) {
-    case 1: return launch_cfg<2, 4, 4, 2, 64, 2, 2>(p, s);
-    case 2: return launch_cfg<4, 2, 2, 5, 64, 2, 2>(p, s);
-    case 3: return launch_cfg<2, 4, 2, 2, 64, 3, 2>(p, s);
-    case 22: return launch_cfg<2, 4, 4, 2, 64, 2, 2, 4>(p, s);
-    case 23: return launch_cfg<4, 2, 2, 5, 64, 2, 2, 4>(p, s);
-    case 24: return launch_cfg<2, 4, 2, 2, 64, 2, 2, 4>(p, s);
-    default: return hipErrorInvalidValue;
-  }
-#endif
-#ifdef T2V_G2_FEW        // experiment build (with -DT2V_G2_EXPERIMENTS): only the tiles under study (compile time)
-  switch (tile) {
-    case 1: return launch_cfg<2, 4, 4, 2, 64, 2, 2>(p, s);
-    case 2: return launch_cfg<4, 2, 2, 5, 64, 2, 2>(p, s);
-    case 3: return launch_cfg<2, 4, 2, 2, 64, 3, 2>(p, s);
-    case 8: return launch_cfg<6, 2, 1, 5, 64, 2, 3>(p, s);
-    case 13: return launch_cfg<2, 4, 4, 2, 64, 2, 2, 2>(p, s);
-    case 14: return launch_cfg<4, 2, 2, 5, 64, 2, 2, 2>(p, s);
-    case 15: return launch_cfg<2, 4, 2, 2, 64, 3, 2, 2>(p, s);
-    case 17: return launch_cfg<6, 2, 1, 5, 64, 2, 3, 2>(p, s);
-    case 18: return launch_cfg<2, 4, 4, 2, 64, 2, 2, 3>(p, s);
-    case 19: return launch_cfg<4, 2, 2, 5, 64, 2, 2, 3>(p, s);
-    case 20: return launch_cfg<6, 2, 1, 5, 64, 2, 3, 3>(p, s);
-    case 21: return launch_cfg<2, 4, 2, 2, 64, 2, 2, 3>(p, s);
-    default: return hipErrorInvalidValue;
-  }
-#endif
   switch (tile) {
     case 1: return launch_cfg<2, 4, 4, 2, 64, 2, 2>(p, s);   // 2 x 64 KiB
     case 2: return launch_cfg<4, 2, 2, 5, 64, 2, 2>(p, s);   // 2 x 72 KiB
@@ -897,35 +624,6 @@ hipError_t t2v_launch_gemm2(const GemmParams& p, int tile, hipStream_t s) {
                                                              // FULL reduction each — no split-K slabs, no reduction launch (experiment, round 4)
     case 11: return launch_cfg<4, 2, 1, 5, 64, 2, 2>(p, s);  // 128x320, 8 waves (2 per SIMD), 2 x 56 KiB: M = 32768 (VideoCrafter, 16 frames) -> exactly
                                                              // 256 workgroups where 192-row tiles make 171; also the b = 1 per-GPU shapes (M = 24576 -> 192)
-#ifdef T2V_G2_EXPERIMENTS   // round-5 schedule experiments, measured and NOT selected (tools/gemm_pf_probe.py): instantiated on request only
-    // 13 .. 17 = 1, 2, 3, 5, 8 with the next k-tile's first fragments prefetched across the barrier: +-0 (-1.5 % .. +3.7 %)
-    case 13: return launch_cfg<2, 4, 4, 2, 64, 2, 2, 2>(p, s);
-    case 14: return launch_cfg<4, 2, 2, 5, 64, 2, 2, 2>(p, s);
-    case 15: return launch_cfg<2, 4, 2, 2, 64, 3, 2, 2>(p, s);
-    case 16: return launch_cfg<2, 4, 2, 1, 64, 4, 2, 2>(p, s);
-    case 17: return launch_cfg<6, 2, 1, 5, 64, 2, 3, 2>(p, s);
-    // 18 .. 21 = 1, 2, 8 and the 128x256 tile with the operands staged through registers instead of LDS-DMA: +4 % on 8192^3, -1 .. -8 % on the UNet's shapes
-    case 18: return launch_cfg<2, 4, 4, 2, 64, 2, 2, 3>(p, s);
-    case 19: return launch_cfg<4, 2, 2, 5, 64, 2, 2, 3>(p, s);
-    case 20: return launch_cfg<6, 2, 1, 5, 64, 2, 3, 3>(p, s);
-    case 21: return launch_cfg<2, 4, 2, 2, 64, 2, 2, 3>(p, s);
-#endif
-#ifdef T2V_G2_EXPERIMENTS
-    // 22 / 23 / 24 = 256x256 / 256x320 / 128x256 on the round-6 schedule: two wave groups one barrier apart, region staging two k-tiles
-    // ahead, counted vmcnt (PP == 4).  Correct, and measured equal to lock-step (+-3 % long K, -7 .. -20 % short K): the calibration GEMM
-    // spends the same cycles at 62 % MFMA busy under either schedule and the chip clocks 1.55-1.68 GHz on random operands (2.3 GHz on
-    // zeros) — power, not the issue schedule, is the ceiling (profiles/r06_gemm_mainloop_findings.txt)
-    case 22: return launch_cfg<2, 4, 4, 2, 64, 2, 2, 4>(p, s);
-    case 23:
-      if (p.gather == T2V_GATHER_CONV3X3 && p.up) return launch_cfg<4, 2, 2, 5, 64, 2, 2>(p, s);   // (upsample gather: register budget)
-      return launch_cfg<4, 2, 2, 5, 64, 2, 2, 4>(p, s);
-    case 24: return launch_cfg<2, 4, 2, 2, 64, 2, 2, 4>(p, s);
-    // 6 / 7 = 256x256 / 256x320 on the round-1 ping-pong (the next k-tile's DMA drained with vmcnt(0)): equal to lock-step
-    case 6: return launch_cfg<2, 4, 4, 2, 64, 2, 2, 1>(p, s);
-    case 7:
-      if (p.gather == T2V_GATHER_CONV3X3 && p.up) return launch_cfg<4, 2, 2, 5, 64, 2, 2>(p, s);   // (upsample gather: register budget)
-      return launch_cfg<4, 2, 2, 5, 64, 2, 2, 1>(p, s);
-#endif
     default: return hipErrorInvalidValue;
   }
 }

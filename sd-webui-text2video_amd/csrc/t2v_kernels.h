@@ -227,6 +227,18 @@ inline hipError_t t2v_launch_coresident(const GemmParams& p, int BM, int tiles_n
 }
 inline long t2v_lcm(long a, long b) { long x = a, y = b; while (y) { const long t = x % y; x = y; y = t; } return a / x * b; }
 
+// Split-K state of a GEMM launch (both launchers): `splitk` clamped to [1, k-tiles of `bk`], `kt_per_split` derived from it, empty
+// splits removed.  The ticket buffer survives only where the in-kernel fold applies (t2v_epilogue_rows: the last-arriving workgroup
+// of a tile folds the slabs) — plain epilogue, one counter per output tile, no GroupNorm behind it; elsewhere the reduction kernel runs.
+inline void t2v_normalize_splitk(GemmParams& p, int bk, long tiles) {
+  const int KT = (p.K + bk - 1) / bk;
+  if (p.splitk > KT) p.splitk = KT;
+  if (p.splitk < 1) p.splitk = 1;
+  p.kt_per_split = (KT + p.splitk - 1) / p.splitk;
+  p.splitk = (KT + p.kt_per_split - 1) / p.kt_per_split;  // no empty splits
+  if (p.splitk <= 1 || p.epi != T2V_EPI_NONE || tiles > T2V_SYNC_INTS || p.gn_out != nullptr) p.tickets = nullptr;
+}
+
 // Each returns hipSuccess or the launch error.
 hipError_t t2v_launch_gemm(const GemmParams& p, hipStream_t s);             // 128x128 / 128x64 tiles (any N, C8 stem)
 hipError_t t2v_launch_gemm2(const GemmParams& p, int tile, hipStream_t s);  // 256/128 x 256/320 tiles, deep DMA ring
@@ -253,6 +265,38 @@ hipError_t t2v_launch_embed_rows(const t2v_op& op, hipStream_t s);
 // x * sigmoid(x) as 5 VALU instructions (v_exp_f32 and v_rcp_f32 are 1-ulp; an IEEE divide would be ~12 more)
 __device__ __forceinline__ float t2v_silu(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f));
+}
+
+// 16-byte LDS-DMA of the GEMM operand stages: lane l's 16 bytes at gsrc land at lds_wave_base + 16 l
+#define T2V_AS1 __attribute__((address_space(1)))
+#define T2V_AS3 __attribute__((address_space(3)))
+__device__ __forceinline__ void t2v_glds16(const void* gsrc, void* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const T2V_AS1 void*)gsrc, (T2V_AS3 void*)lds_wave_base, 16, 0, 0);
+}
+
+// Per-lane split-K slab store of a wave's TM x TN accumulator blocks (rows from m_wave, packed columns from n_wave) into slab
+// `split_idx` of p.ws: the whole tail of both GEMM kernels — the epilogue proper then runs in splitk_reduce_kernel.  (The plain
+// epilogue writes its slabs row-coalesced in t2v_epilogue_rows below and never gets here.)
+template <int TM, int TN>
+__device__ __forceinline__ void t2v_store_splitk_slab(const GemmParams& p, const f32x16 (&acc)[TM][TN], int lane, int m_wave, int n_wave,
+                                                      int split_idx) {
+  const int mlane = lane & 31, nhalf = (lane >> 5) * 4;
+#pragma unroll
+  for (int a = 0; a < TM; ++a) {
+    const int m = m_wave + a * 32 + mlane;
+    if (m >= p.M) continue;
+    float* ws = p.ws + ((size_t)split_idx * p.M + m) * p.N;
+#pragma unroll
+    for (int b = 0; b < TN; ++b)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n_wave + b * 32 + 8 * q + nhalf;
+        if (n < p.N) {
+          f32x4 o = {acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]};
+          *reinterpret_cast<f32x4*>(ws + n) = o;
+        }
+      }
+  }
 }
 
 // ---- row-coalesced GEMM epilogue (shared by gemm.hip and gemm2.hip) -----------------------------------

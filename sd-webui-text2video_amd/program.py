@@ -243,8 +243,8 @@ class Program:
     def choose_tile(self, M: int, n: int, k: int, gather: int, allow_splitk: bool = True):
         """-> (tile id, split_k).  Tile ids as in t2v_op.i[22]: 0 = 128x128-class kernel (any N, the C8
         stem); 1 256x256, 2 256x320, 3 128x256, 4/5 128x128 with a 4-deep ring, 8 / 9 / 11 / 12 192x320 / 192x256 /
-        128x320 / 64x64 (csrc/gemm2.hip); 6 / 7 / 13-24 exist only in -DT2V_G2_EXPERIMENTS builds (other main-loop
-        schedules, csrc/gemm2_experiments.inc).
+        128x320 / 64x64 (csrc/gemm2.hip); 6 / 7 / 13-24 were other main-loop schedules, measured, not selected and
+        removed from the sources: the executor rejects them.
         Policy for a 256-CU chip: the widest tile whose grid still gives >= ~0.75 wave of
         workgroups; otherwise the 128x256 tile, then split-K over the (long) reduction."""
         cus = self.target_cus

@@ -13,7 +13,7 @@ from sd_webui_text2video_amd.program import BoundProgram, Buf, Program, Ref
 
 pytestmark = pytest.mark.gpu
 
-GEMM2_TILES = [1, 2, 3, 4, 5, 8, 9, 11, 12]     # csrc/gemm2.hip configurations (t2v_op.i[22]); 6 / 7 / 13-24: experiment builds only
+GEMM2_TILES = [1, 2, 3, 4, 5, 8, 9, 11, 12]     # csrc/gemm2.hip configurations (t2v_op.i[22]); 10 is the fused QKV + temporal attention tile
 
 
 def _g(seed=0):
@@ -111,6 +111,25 @@ def test_gemm_split_k(split):
         fill(it, a, g); fill(it, res, g)
     it, got, _, _ = run_both(P, w, {}, init)
     _check(it, got, out, 2e-5, f"split-K {op.i[19]}")
+
+
+@pytest.mark.parametrize("tile", [0, 3, 5])
+def test_gemm_geglu_split_k(tile):
+    """GEGLU with split-K: the GEMM kernels only store their split's slab (their whole per-lane tail), value * gelu(gate) runs in the
+    reduction.  32 k-tiles; packed N = 256 = 128 output channels, so a 128-column tile boundary falls inside the value | gate interleave."""
+    M, K, N = 96, 2048, 256
+    P = Program()
+    P.force_tile = tile
+    P.target_cus = 8                              # steer the heuristic: 1-2 output tiles -> split-K 2 (tile 0) / 4
+    g = _g(25)
+    a, out = P.alloc(M, K, "f16"), P.alloc(M, N // 2, "f16")
+    wsrc, bsrc = torch.randn(N, K, generator=g) / math.sqrt(K), torch.randn(N, generator=g) * 0.1
+    perm = pk.geglu_perm(N // 2)
+    w = {"w": wsrc[perm].half(), "b": bsrc[perm].contiguous()}
+    op = P.gemm("g", a, Ref("weight", 0, "w"), N, K, out, bias=Ref("weight", 0, "b"), epi=L.EPI_GEGLU)
+    assert op.i[19] > 1 and op.i[22] == tile
+    it, got, _, _ = run_both(P, w, {}, lambda it: fill(it, a, g))
+    _check(it, got, out, 1e-3, f"geglu split-K tile {tile}")
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,stride,up", [(3, 16, 16, 64, 128, 1, 0), (2, 8, 8, 128, 64, 2, 0),

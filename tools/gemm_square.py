@@ -1,5 +1,5 @@
 """Square plain GEMMs (fp16 in, fp16 out, no epilogue extras) for comparison with published gfx950 numbers:
-4096^3 and 8192^3, uniform [-1, 1) and zero operands, tiles 1 / 6 (256x256 lock-step / ping-pong) and 2 / 7."""
+4096^3 and 8192^3, uniform [-1, 1), N(0, 1) and zero operands, tiles 1 (256x256) and 3 (128x256)."""
 import os
 import sys
 
@@ -13,7 +13,7 @@ dev = torch.device("cuda:0")
 for n in (4096, 8192):
     for data in ("uniform", "normal", "zeros"):
         row = []
-        for tile in (1, 6, 3):
+        for tile in (1, 3):
             P = Program()
             P.force_tile = tile
             a, out = P.alloc(n, n, "f16"), P.alloc(n, n, "f16")
