@@ -9,40 +9,47 @@
 //
 // A statistics "instance" is a contiguous run of `rows` token rows (one frame, or all F frames
 // of one sample) x one of 32 channel groups.  Input is the fp32 (or fp16) residual stream
-// [rows, C]; output is fp16 — the operand format of the following MFMA GEMM.
-//   launch 1: per-thread fp32 partial sums over a chunk of rows (8 rows in flight per thread) -> LDS ->
-//             ordered fp64 fold per group -> one partial per (instance, block, group); no atomics.
-//   launch 2: one wave per (instance, group): ordered fold of the block partials -> {mean, rstd}
-//             (a ticket-elected in-kernel fold was measured: same-line L2 atomics serialise at ~25 ns
-//             each and the fence + fold tail costs as much as this 4-5 us launch — not kept).
-//   launch 3: normalise + affine (+SiLU): scale/shift per channel built once per workgroup in LDS,
-//             then 8 rows x 8 channels per thread, 16-byte loads issued together, 16-byte stores.
-// Bitwise reproducible run to run.
-// (T-sharded clips: statistics / all-gather of the partials / fold + normalise, see phase below.)
-// HBM-bound: 4 B + 4 B read, 2 B written per element.
+// [rows, C]; output is fp16 — the operand format of the following MFMA GEMM.  Four forms, all selected by the lowering:
+//   three launches   gn_stats_kernel (block partials) -> gn_finalize_kernel ({mean, rstd}) -> gn_apply_kernel; the statistics may instead
+//                    come from the producing GEMM's strips (gn_finalize_strips*_kernel) or, T-sharded clips, from the gathered parts of
+//                    all ranks (phases 1 / 2, see t2v_launch_groupnorm).  4 B + 4 B read, 2 B written per element: HBM-bound.
+//   single launch    gn_fused_kernel, one workgroup per (instance, group), for small statistics slices.
+//   cooperative      gn_coop_kernel: one pass, the tensor in registers across a statistics exchange between the launch's workgroups.
+//   split-K + GN     splitk_gn_kernel: the same with the split-K slab reduction as its loader.
+// Every form is built from the helpers below, each written ONCE — LoadN, t2v_mean_rstd / t2v_norm_store (t2v_kernels.h, shared with the GEMM
+// epilogues), gn_cast_store, gn_fold_parked, gn_publish, gn_scale_shift, gn_coop_core: the statistics of an instance must be bit-identical
+// in every workgroup and on every T-shard rank, and no two copies of the arithmetic exist that could drift apart.
+// No atomics on data, every fold in a fixed order in fp64: bitwise reproducible run to run.
+#include <climits>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include "t2v_kernels.h"
 
 namespace {
 
-// 8 consecutive channels of one token row as fp32 (one 16-byte load for fp16, two for fp32)
-template <typename T> struct Load8;
-template <> struct Load8<float> {
-  static __device__ __forceinline__ f32x8 ld(const float* __restrict__ p) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    f32x8 r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+// N (4 / 8) consecutive channels of one token row as fp32: 16-byte loads for fp32, one 2N-byte load for fp16
+template <typename T, int N> struct LoadN;
+template <int N> struct LoadN<float, N> {
+  static __device__ __forceinline__ f32xN<N> ld(const float* __restrict__ p) {
+    f32xN<N> r;
+#pragma unroll
+    for (int i = 0; i < N; i += 4) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(p + i);
+      r[i] = a[0]; r[i + 1] = a[1]; r[i + 2] = a[2]; r[i + 3] = a[3];
+    }
     return r;
   }
 };
-template <> struct Load8<f16> {
-  static __device__ __forceinline__ f32x8 ld(const f16* __restrict__ p) {
-    const f16x8 h = *reinterpret_cast<const f16x8*>(p);
-    f32x8 r;
+template <int N> struct LoadN<f16, N> {
+  static __device__ __forceinline__ f32xN<N> ld(const f16* __restrict__ p) {
+    const f16xN<N> h = *reinterpret_cast<const f16xN<N>*>(p);
+    f32xN<N> r;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (float)h[e];
+    for (int e = 0; e < N; ++e) r[e] = (float)h[e];
     return r;
   }
 };
@@ -54,14 +61,14 @@ struct GnCast {
   f16* out;      // null: none
   int ld, lo;    // leading dimension; column offset of the low-order image (0: none)
 };
-template <typename V>
-__device__ __forceinline__ void gn_cast_store8(const GnCast& c, size_t row, int col, const V& v) {
-  f16x8 o, l;
+template <int N>
+__device__ __forceinline__ void gn_cast_store(const GnCast& c, size_t row, int col, const f32xN<N>& v) {
+  f16xN<N> o, l;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) { o[e] = (f16)v[e]; l[e] = (f16)(v[e] - (float)o[e]); }
+  for (int e = 0; e < N; ++e) { o[e] = (f16)v[e]; l[e] = (f16)(v[e] - (float)o[e]); }
   f16* dst = c.out + row * c.ld + col;
-  *reinterpret_cast<f16x8*>(dst) = o;
-  if (c.lo) *reinterpret_cast<f16x8*>(dst + c.lo) = l;
+  *reinterpret_cast<f16xN<N>*>(dst) = o;
+  if (c.lo) *reinterpret_cast<f16xN<N>*>(dst + c.lo) = l;
 }
 
 __device__ __forceinline__ void gn_store_pair(double* st, double s, double q) {
@@ -69,12 +76,52 @@ __device__ __forceinline__ void gn_store_pair(double* st, double s, double q) {
   st[1] = q;
 }
 
+// The per-thread fp32 sums of a workgroup, parked in LDS as psum / psq [R][C], folded per group in fp64 in a fixed order: LANES adjacent
+// lanes per group (group tid / LANES) each take a fixed strided subset of the group's R x cpg sums, then a fixed xor tree.  Every thread
+// calls (the shuffles are wave-wide); the sums are complete in the first lane of each group.
+template <int LANES>
+__device__ __forceinline__ void gn_fold_parked(const float* psum, const float* psq, int R, int C, int cpg, int groups, int tid, double& s,
+                                               double& q) {
+  const int g = tid / LANES, sub = tid % LANES;
+  s = 0.0;
+  q = 0.0;
+  if (g < groups) {
+    const int n = R * cpg;
+    for (int i = sub; i < n; i += LANES) {
+      const int k = i / cpg, c = g * cpg + (i - k * cpg);
+      s += (double)psum[k * C + c];
+      q += (double)psq[k * C + c];
+    }
+  }
+  for (int o = 1; o < LANES; o <<= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
+}
+
+// Tail of the three finalize kernels, (instance, group) pair idx: {mean, rstd} into finals[], or — raw != nullptr: a T-sharded clip's local
+// fold — this rank's {sum, sum of squares} for the all-gather.
+__device__ __forceinline__ void gn_publish(int idx, double s, double q, double inv_n, float eps, float* finals, double* raw) {
+  if (raw != nullptr) { gn_store_pair(raw + 2 * idx, s, q); return; }
+  const float2 mr = t2v_mean_rstd(s, q, inv_n, eps);
+  finals[2 * idx] = mr.x;
+  finals[2 * idx + 1] = mr.y;
+}
+
+// scale[c] = rstd * gamma[c] and shift[c] = beta[c] - mean * scale[c] of one instance into LDS, from stat = {mean, rstd}[groups], by the
+// `nthreads` threads of the workgroup (the caller synchronises before and after).
+__device__ __forceinline__ void gn_scale_shift(float* sc, float* sf, const float* stat, const float* __restrict__ gamma,
+                                               const float* __restrict__ beta, int C, int cpg, int nthreads) {
+  for (int c = threadIdx.x; c < C; c += nthreads) {
+    const int grp = c / cpg;
+    const float a = stat[2 * grp + 1] * gamma[c];
+    sc[c] = a;
+    sf[c] = beta[c] - stat[2 * grp] * a;
+  }
+}
+
 constexpr int GN_UNROLL = 8;   // token rows a thread keeps in flight (HBM-bound: ~48 KiB per CU must be outstanding)
 
-// Launch 1 — grid (nblk, n_inst), nblk = ceil(rows / rpb).  Threads form R row-replicas x TPR column slots of
-// 8 channels.  Deterministic: per-thread fp32 partials are parked in LDS [R][C]; `groups` threads then fold
-// replicas + the channels of their group in a fixed order in fp64 and store ONE partial per (instance,
-// block, group).  No atomics: bitwise reproducible run to run.
+// Launch 1 — grid (nblk, n_inst), nblk = ceil(rows / rpb).  Threads form R row-replicas x TPR column slots of 8 channels.  Per-thread fp32
+// partials are parked in LDS [2][R][C]; gn_fold_parked (8 lanes per group; more than 32 groups: one thread per group walks its sums in
+// order) then stores ONE partial per (instance, block, group).
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, double* partials, int rows, int C,
                                                        int ld, int groups, int rpb) {
@@ -93,19 +140,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
   if (rr < R) {
     for (int u = cs; u < cv; u += TPR) {
       const int c8 = u * 8;
-      f32x8 s, q;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
+      f32x8 s = 0.f, q = 0.f;
       for (int r = r0 + rr; r < r1; r += R * GN_UNROLL) {
         f32x8 v[GN_UNROLL];
 #pragma unroll
         for (int k = 0; k < GN_UNROLL; ++k) {
           const int rk = r + k * R;
-          if (rk < r1) v[k] = Load8<T>::ld(base + (size_t)rk * ld + c8);
-          else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[k][e] = 0.f;
-          }
+          if (rk < r1) v[k] = LoadN<T, 8>::ld(base + (size_t)rk * ld + c8);
+          else v[k] = 0.f;
         }
 #pragma unroll
         for (int k = 0; k < GN_UNROLL; ++k) { s += v[k]; q += v[k] * v[k]; }
@@ -116,31 +158,24 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
   }
   __syncthreads();
   const int cpg = C / groups;
+  double* part = partials + ((size_t)inst * gridDim.x + blockIdx.x) * groups * 2;
   if (groups * 8 <= 256) {
-    // 8 adjacent lanes per group: each folds a fixed strided subset of the R x cpg parked sums, then a fixed xor-tree
-    const int g = tid >> 3, sub = tid & 7;
-    double s = 0.0, q = 0.0;
-    if (g < groups) {
-      const int n = R * cpg;
-      for (int i = sub; i < n; i += 8) {
-        const int k = i / cpg, c = g * cpg + (i - k * cpg);
-        s += (double)psum[k * C + c];
-        q += (double)psq[k * C + c];
-      }
-    }
-    for (int o = 1; o < 8; o <<= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
-    if (g < groups && sub == 0) gn_store_pair(partials + (((size_t)inst * gridDim.x + blockIdx.x) * groups + g) * 2, s, q);
+    double s, q;
+    gn_fold_parked<8>(psum, psq, R, C, cpg, groups, tid, s, q);
+    if (tid < groups * 8 && (tid & 7) == 0) gn_store_pair(part + (tid >> 3) * 2, s, q);
   } else if (tid < groups) {
     double s = 0.0, q = 0.0;
     for (int k = 0; k < R; ++k)
       for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { s += (double)psum[k * C + c]; q += (double)psq[k * C + c]; }
-    gn_store_pair(partials + (((size_t)inst * gridDim.x + blockIdx.x) * groups + tid) * 2, s, q);
+    gn_store_pair(part + tid * 2, s, q);
   }
 }
 
-// Pass 2 — one wave per (instance, group): ordered fold of the block partials -> {mean, rstd}.
+// Launch 2 — one wave per (instance, group): ordered fold of the block partials, then gn_publish.
 // `nparts` > 1: the partials of all T-shard ranks, gathered as [part][inst][blk][group][2]; the fold
 // order (part-major, then block) is the same on every rank, so all ranks get identical statistics.
+// (A ticket-elected fold inside launch 1 was measured: same-line L2 atomics serialise at ~25 ns each and the fence + fold tail costs as
+// much as this 4-5 us launch — not kept.)
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* partials, float* finals, int n_inst, int nblk,
                                                           int groups, double inv_n, float eps, int nparts, double* raw) {
   const int lane = threadIdx.x & 63;
@@ -165,21 +200,12 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* partials
     q += st[1];
   }
   for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
-  if (lane == 0 && raw != nullptr) {        // T-shard, local fold: this rank's {sum, sum of squares} for the all-gather
-    raw[2 * idx] = s;
-    raw[2 * idx + 1] = q;
-  } else if (lane == 0) {
-    const double m = s * inv_n;
-    double var = q * inv_n - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    finals[2 * idx] = (float)m;
-    finals[2 * idx + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
+  if (lane == 0) gn_publish(idx, s, q, inv_n, eps, finals, raw);
 }
 
 // Phase 3 — statistics from the producing GEMM's epilogue (T2V_EPI_STATS): strips[(inst * nstrips + s)][0 | 1][c] = sum / sum of squares
-// of one 32-row strip of column c.  One wave per (instance, group) folds nstrips x cpg pairs in a fixed order in fp64 -> {mean, rstd}.
-// raw != nullptr (T-sharded clip, round 6): this rank's {sum, sum of squares} per (instance, group) for the exchange instead of {mean, rstd}.
+// of one 32-row strip of column c.  One wave per (instance, group) folds nstrips x cpg pairs in a fixed order in fp64, then gn_publish
+// (raw: a T-sharded clip's part, round 6).
 __global__ __launch_bounds__(256) void gn_finalize_strips_kernel(const float* __restrict__ strips, float* finals, int n_inst, int nstrips,
                                                                  int groups, int cpg, int ldn, double inv_n, float eps, double* raw) {
   const int lane = threadIdx.x & 63;
@@ -196,16 +222,7 @@ __global__ __launch_bounds__(256) void gn_finalize_strips_kernel(const float* __
     q += (double)p[ldn];
   }
   for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
-  if (lane == 0 && raw != nullptr) {
-    raw[2 * idx] = s;
-    raw[2 * idx + 1] = q;
-  } else if (lane == 0) {
-    const double m = s * inv_n;
-    double var = q * inv_n - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    finals[2 * idx] = (float)m;
-    finals[2 * idx + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
+  if (lane == 0) gn_publish(idx, s, q, inv_n, eps, finals, raw);
 }
 
 // The same fold with a whole workgroup per (instance, group), for instances of many strips (cross-frame statistics: 768 strips x 10
@@ -231,21 +248,16 @@ __global__ __launch_bounds__(256) void gn_finalize_strips_wg_kernel(const float*
   if (tid == 0) {
     double a = 0.0, b = 0.0;
     for (int w = 0; w < 4; ++w) { a += red[2 * w]; b += red[2 * w + 1]; }
-    if (raw != nullptr) { raw[2 * idx] = a; raw[2 * idx + 1] = b; return; }
-    const double m = a * inv_n;
-    double var = b * inv_n - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    finals[2 * idx] = (float)m;
-    finals[2 * idx + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    gn_publish(idx, a, b, inv_n, eps, finals, raw);
   }
 }
 
-// Launch 2 — grid (ceil(rows / (R*GN_UNROLL)), n_inst), same thread layout.  The workgroup first builds
-// scale[c] = rstd*gamma[c] and shift[c] = beta[c] - mean*scale[c] for the instance in LDS; every thread then
-// normalises GN_UNROLL rows of its 8 channels per column unit (16-byte loads issued together, 16-byte stores).
-// parts != nullptr (phase 2 of a T-sharded norm, round 6): the gathered {sum, sum of squares} parts of all ranks ([part][inst][group][2]
-// doubles, part stride part_len) are folded HERE, in rank order, by `groups` threads of every workgroup — no finalize launch in front of
-// the pass; every rank and every workgroup folds the same values in the same order: identical statistics everywhere.
+// Launch 3 — grid (ceil(rows / (R*GN_UNROLL)), n_inst), the thread layout of launch 1.  The workgroup takes the instance's {mean, rstd}
+// from `finals`, builds scale / shift in LDS (gn_scale_shift), and every thread then normalises GN_UNROLL rows of its 8 channels per
+// column unit (16-byte loads issued together, t2v_norm_store, the raw cast beside it).
+// parts != nullptr (phase 2 of a T-sharded norm, round 6): {mean, rstd} come instead from the gathered {sum, sum of squares} parts of all
+// ranks ([part][inst][group][2] doubles, part stride part_len), folded HERE, in rank order, by `groups` threads of every workgroup — no
+// finalize launch in front of the pass; every rank and every workgroup folds the same values in the same order.
 template <typename T, bool SILU>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, const float* __restrict__ finals,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -253,12 +265,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
                                                        int groups, int lo_off, GnCast cast, const double* parts, int nparts, long part_len,
                                                        double inv_n, float eps) {
   extern __shared__ float sh[];   // scale[C], shift[C] (+ {mean, rstd}[groups] with parts)
-  float* sc = sh;
-  float* sf = sh + C;
   const int tid = threadIdx.x;
   const int inst = blockIdx.y;
   const int cv = C >> 3;
-  const int cpg = C / groups;
+  const float* stat = finals + (size_t)inst * groups * 2;
   if (parts != nullptr) {
     float* fin = sh + 2 * C;
     for (int g = tid; g < groups; g += 256) {
@@ -268,28 +278,14 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
         s += st[0];
         q += st[1];
       }
-      const double m = s * inv_n;
-      double var = q * inv_n - m * m;
-      var = var < 0.0 ? 0.0 : var;
-      fin[2 * g] = (float)m;
-      fin[2 * g + 1] = (float)(1.0 / sqrt(var + (double)eps));
+      const float2 mr = t2v_mean_rstd(s, q, inv_n, eps);
+      fin[2 * g] = mr.x;
+      fin[2 * g + 1] = mr.y;
     }
     __syncthreads();
-    for (int c = tid; c < C; c += 256) {
-      const int grp = c / cpg;
-      const float a = fin[2 * grp + 1] * gamma[c];
-      sc[c] = a;
-      sf[c] = beta[c] - fin[2 * grp] * a;
-    }
-  } else {
-    const float* fin = finals + (size_t)inst * groups * 2;
-    for (int c = tid; c < C; c += 256) {
-      const int grp = c / cpg;
-      const float a = fin[2 * grp + 1] * gamma[c];
-      sc[c] = a;
-      sf[c] = beta[c] - fin[2 * grp] * a;
-    }
+    stat = fin;
   }
+  gn_scale_shift(sh, sh + C, stat, gamma, beta, C, C / groups, 256);
   __syncthreads();
   const int TPR = cv < 256 ? cv : 256;
   const int R = 256 / TPR;
@@ -304,24 +300,15 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
 #pragma unroll
     for (int k = 0; k < GN_UNROLL; ++k) {
       const int rk = r0 + k * R;
-      if (rk < rows) v[k] = Load8<T>::ld(xb + (size_t)rk * ld_in + c8);
+      if (rk < rows) v[k] = LoadN<T, 8>::ld(xb + (size_t)rk * ld_in + c8);
     }
-    const f32x8 a = Load8<float>::ld(sc + c8), b = Load8<float>::ld(sf + c8);
+    const f32x8 a = LoadN<float, 8>::ld(sh + c8), b = LoadN<float, 8>::ld(sh + C + c8);
 #pragma unroll
     for (int k = 0; k < GN_UNROLL; ++k) {
       const int rk = r0 + k * R;
       if (rk < rows) {
-        f16x8 o, l;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float y = v[k][e] * a[e] + b[e];
-          if (SILU) y = t2v_silu(y);
-          o[e] = (f16)y;
-          l[e] = (f16)(y - (float)o[e]);
-        }
-        *reinterpret_cast<f16x8*>(ob + (size_t)rk * ld_out + c8) = o;
-        if (lo_off) *reinterpret_cast<f16x8*>(ob + (size_t)rk * ld_out + lo_off + c8) = l;     // hi + lo operand split (op.i[16])
-        if (cast.out) gn_cast_store8(cast, (size_t)inst * rows + rk, c8, v[k]);
+        t2v_norm_store<8>(ob + (size_t)rk * ld_out + c8, lo_off, v[k], a, b, SILU);     // lo_off: hi + lo operand split (op.i[16])
+        if (cast.out) gn_cast_store<8>(cast, (size_t)inst * rows + rk, c8, v[k]);
       }
     }
   }
@@ -331,21 +318,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
 // launches above cost more than the data movement): one workgroup per (instance, group), XCD-contiguous, streams its
 // [rows x C/groups] slice twice — sums, then normalise; the second pass hits L2.  4-channel units (C/groups % 4 == 0),
 // 4 rows in flight per thread, fp32 per-thread sums folded in fp64 in a fixed order (wave xor-tree, then waves in
-// order): bitwise reproducible.
+// order); scale / shift of the thread's 4 channels stay in registers.
 constexpr int GNF_THREADS = 512;
 constexpr int GNF_UNROLL = 4;
-
-template <typename T> struct Load4;
-template <> struct Load4<float> {
-  static __device__ __forceinline__ f32x4 ld(const float* __restrict__ p) { return *reinterpret_cast<const f32x4*>(p); }
-};
-template <> struct Load4<f16> {
-  static __device__ __forceinline__ f32x4 ld(const f16* __restrict__ p) {
-    const f16x4 h = *reinterpret_cast<const f16x4*>(p);
-    f32x4 r = {(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-    return r;
-  }
-};
 
 template <typename T, bool SILU>
 __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
@@ -366,15 +341,15 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const T* __restri
   const bool live = rr < R;
   const int c0 = g * cpg + cs * 4;
   const T* xb = x + (size_t)inst * rows * ld_in + c0;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
+  f32x4 s = 0.f, q = 0.f;
   if (live) {
     for (int r = rr; r < rows; r += R * GNF_UNROLL) {
       f32x4 v[GNF_UNROLL];
 #pragma unroll
       for (int k = 0; k < GNF_UNROLL; ++k) {
         const int rk = r + k * R;
-        if (rk < rows) v[k] = Load4<T>::ld(xb + (size_t)rk * ld_in);
-        else v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (rk < rows) v[k] = LoadN<T, 4>::ld(xb + (size_t)rk * ld_in);
+        else v[k] = 0.f;
       }
 #pragma unroll
       for (int k = 0; k < GNF_UNROLL; ++k) { s += v[k]; q += v[k] * v[k]; }
@@ -388,12 +363,9 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const T* __restri
   if (tid == 0) {
     double a = 0.0, b = 0.0;
     for (int w = 0; w < GNF_THREADS / 64; ++w) { a += red[2 * w]; b += red[2 * w + 1]; }
-    const double inv_n = 1.0 / ((double)rows * cpg);
-    const double m = a * inv_n;
-    double var = b * inv_n - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    stat[0] = (float)m;
-    stat[1] = (float)(1.0 / sqrt(var + (double)eps));
+    const float2 mr = t2v_mean_rstd(a, b, 1.0 / ((double)rows * cpg), eps);
+    stat[0] = mr.x;
+    stat[1] = mr.y;
   }
   __syncthreads();
   if (!live) return;
@@ -408,164 +380,204 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const T* __restri
 #pragma unroll
     for (int k = 0; k < GNF_UNROLL; ++k) {
       const int rk = r + k * R;
-      if (rk < rows) v[k] = Load4<T>::ld(xb + (size_t)rk * ld_in);
+      if (rk < rows) v[k] = LoadN<T, 4>::ld(xb + (size_t)rk * ld_in);
     }
 #pragma unroll
     for (int k = 0; k < GNF_UNROLL; ++k) {
       const int rk = r + k * R;
       if (rk < rows) {
-        f16x4 o, l;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float y = v[k][e] * sc[e] + sf[e];
-          if (SILU) y = t2v_silu(y);
-          o[e] = (f16)y;
-          l[e] = (f16)(y - (float)o[e]);
-        }
-        *reinterpret_cast<f16x4*>(ob + (size_t)rk * ld_out) = o;
-        if (lo_off) *reinterpret_cast<f16x4*>(ob + (size_t)rk * ld_out + lo_off) = l;
-        if (cast.out) {
-          f16x4 co, cl;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { co[e] = (f16)v[k][e]; cl[e] = (f16)(v[k][e] - (float)co[e]); }
-          f16* cd = cast.out + ((size_t)inst * rows + rk) * cast.ld + c0;
-          *reinterpret_cast<f16x4*>(cd) = co;
-          if (cast.lo) *reinterpret_cast<f16x4*>(cd + cast.lo) = cl;
-        }
+        t2v_norm_store<4>(ob + (size_t)rk * ld_out, lo_off, v[k], sc, sf, SILU);
+        if (cast.out) gn_cast_store<4>(cast, (size_t)inst * rows + rk, c0, v[k]);
       }
     }
   }
 }
 
 
-// ---- single-pass cooperative GroupNorm (op.i[15] = 1) ---------------------------------------------------------------------
+// ---- single-pass cooperative GroupNorm (op.i[15] = 1) and split-K reduction + GroupNorm: one core, two loaders ---------------------------
 // The three launches above read the tensor twice (4 + 4 B read, 2 B written per element at 2.6 TB/s aggregate) and pay two
 // launch boundaries per site.  Here the grid is at most ONE workgroup per CU, every workgroup loads its rows x C chunk ONCE into
 // registers (KR rows x 8 channels per thread: the chip's register files hold the whole tensor, 63 MB at the 32x32 level against
-// 128 MB of VGPRs), publishes its {sum, sum of squares} partial per group, meets the others at a grid-wide barrier, folds the
-// partials of its instance (every workgroup the same values in the same order: bit-identical statistics everywhere, no atomics
-// on data), and normalises from registers: 4 B read + 2 B written per element, one launch.
+// 128 MB of VGPRs), publishes its {sum, sum of squares} partial per group, meets the others at a grid-wide barrier (or waits for their
+// tagged records), folds the partials of its instance (every workgroup the same values in the same order: bit-identical statistics
+// everywhere, no atomics on data), and normalises from registers: 4 B read + 2 B written per element, one launch.
 // Co-residency: grid <= number of CUs and <= half a CU's threads / registers per workgroup, so all workgroups of the launch
 // are resident once earlier kernels on the GPU drain (a spinning workgroup never waits for one that cannot be scheduled).
 // With MORE than two processes sharing one GPU that guarantee is gone — such set-ups (the one-GPU multi-process rehearsals)
 // select the three-launch path with T2V_GN_COOP=0.
+// The grid barrier (sense-reversing, two levels, bounded wait) and the tagged records are t2v_grid_barrier / t2v_rec_* of t2v_kernels.h,
+// shared with the fused-norm GEMM epilogues.
 constexpr int GNC_THREADS = 512;
 
-// The grid barrier (sense-reversing, two levels, bounded wait) is t2v_grid_barrier of t2v_kernels.h, shared with the fused-norm GEMM epilogues.
+// A workgroup's place in the launch: chunk `chunk` (rows r0 .. r1 - 1, rc rows per chunk) of instance `inst`; its threads form R
+// row-replicas x C / 8 column slots, thread (rr, c8) holds rows r0 + rr + k * R, k < KR, of channels c8 .. c8 + 7 (live: rr < R).
+struct GnCoopTile {
+  int inst, chunk, R, rr, c8, r0, r1;
+  bool live;
+};
+__device__ __forceinline__ GnCoopTile gn_coop_tile(int rows, int C, int nchunk, int rc) {
+  const int tid = threadIdx.x, cv = C >> 3;
+  GnCoopTile t;
+  t.inst = blockIdx.x / nchunk;
+  t.chunk = blockIdx.x - t.inst * nchunk;
+  t.R = GNC_THREADS / cv;
+  t.rr = tid / cv;
+  t.c8 = (tid % cv) * 8;
+  t.live = t.rr < t.R;
+  t.r0 = t.chunk * rc;
+  t.r1 = min(rows, t.r0 + rc);
+  return t;
+}
+struct GnExchange {
+  double* partials;          // records [inst][chunk][group], 16 bytes each
+  unsigned *bar, *fault;     // grid barrier words (seq == 0); the host-mapped fault word of the bounded waits
+  unsigned seq, want;        // tagged records instead of the grid barrier: this launch's tag / the tag to wait for (0: barrier)
+  unsigned gen0;             // barrier mode, thread 0: t2v_grid_epoch, read by the kernel BEFORE its loads
+};
+struct GnAffine {
+  const float *gamma, *beta;
+  f16* out;                  // row 0 of the op's output [n_inst * rows, ld]
+  int ld, lo_off;
+};
+
+// Everything after the loader: v[KR] holds the thread's rows (zeros beyond r1).
+//   per-thread sums -> LDS [2][R][C] -> gn_fold_parked, 16 lanes per group (groups <= 32) -> ONE tagged 16-byte record per (chunk, group);
+//   grid barrier, or nothing (tags: the fetch below re-polls a record until it carries this launch's number);
+//   fold of the instance's nchunk records in a fixed order (the same on every workgroup), EIGHT 16-byte device-scope loads in flight per
+//   round — one load-use round trip at a time made this fold the longest phase of the kernel (8 dependent ~2 us latencies);
+//   t2v_mean_rstd -> gn_scale_shift into the LDS the parked sums occupied -> t2v_norm_store (and the raw cast, stand-alone op only) per row.
+template <bool SILU, int KR>
+__device__ __forceinline__ void gn_coop_core(const f32x8 (&v)[KR], const GnCoopTile& t, float* sh, int rows, int C, int groups, int cpg,
+                                             int nchunk, const GnExchange& x, double inv_n, float eps, const GnAffine& o, const GnCast& cast) {
+  __shared__ float stat[2 * 32];           // {mean, rstd} per group
+  const int tid = threadIdx.x;
+  const bool tags = x.seq != 0u;
+  if (t.live) {
+    f32x8 s = 0.f, q = 0.f;
+#pragma unroll
+    for (int k = 0; k < KR; ++k) { s += v[k]; q += v[k] * v[k]; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { sh[t.rr * C + t.c8 + e] = s[e]; sh[(t.R + t.rr) * C + t.c8 + e] = q[e]; }
+  }
+  __syncthreads();
+  const int g = tid >> 4, sub = tid & 15;
+  double ds, dq;
+  gn_fold_parked<16>(sh, sh + t.R * C, t.R, C, cpg, groups, tid, ds, dq);
+  if (g < groups && sub == 0) {
+    double* st = x.partials + (((size_t)t.inst * nchunk + t.chunk) * groups + g) * 2;
+    t2v_st_dev(reinterpret_cast<float*>(st), t2v_rec_pack(ds, dq, x.seq));         // one 16-byte device-scope (write-through) store,
+    if (!tags) t2v_wait_vm0();                                                     // (barrier mode) complete before this workgroup arrives
+  }
+  if (!tags) t2v_grid_barrier(x.bar, gridDim.x, x.gen0, x.fault);
+  ds = 0.0;
+  dq = 0.0;
+  if (g < groups) {
+    const double* base = x.partials + ((size_t)t.inst * nchunk * groups + g) * 2;
+    for (int c = sub; c < nchunk; c += 128) {
+      f32x4 rec[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) rec[j] = 0.f;
+      const int nrec = min(8, (nchunk - c + 15) / 16);
+      t2v_rec_fetch8([&](int j) { return reinterpret_cast<const float*>(base + (size_t)(c + 16 * j) * groups * 2); }, nrec, x.want, x.fault, rec);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < nrec) t2v_rec_add(rec[j], ds, dq);
+    }
+  }
+  for (int o2 = 1; o2 < 16; o2 <<= 1) { ds += __shfl_xor(ds, o2); dq += __shfl_xor(dq, o2); }
+  if (g < groups && sub == 0) {
+    const float2 mr = t2v_mean_rstd(ds, dq, inv_n, eps);
+    stat[2 * g] = mr.x;
+    stat[2 * g + 1] = mr.y;
+  }
+  __syncthreads();                                            // (also: everyone is done with the parked sums)
+  gn_scale_shift(sh, sh + C, stat, o.gamma, o.beta, C, cpg, GNC_THREADS);
+  __syncthreads();
+  if (!t.live) return;
+  const f32x8 a = LoadN<float, 8>::ld(sh + t.c8), b = LoadN<float, 8>::ld(sh + C + t.c8);
+#pragma unroll
+  for (int k = 0; k < KR; ++k) {
+    const int r = t.r0 + t.rr + k * t.R;
+    if (r < t.r1) {
+      const size_t row = (size_t)t.inst * rows + r;
+      t2v_norm_store<8>(o.out + row * o.ld + t.c8, o.lo_off, v[k], a, b, SILU);
+      if (cast.out) gn_cast_store<8>(cast, row, t.c8, v[k]);
+    }
+  }
+}
+
+// Loader: plain rows of x.
 template <typename T, bool SILU, int KR>
 __global__ __launch_bounds__(GNC_THREADS) void gn_coop_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, f16* __restrict__ out, double* partials,
                                                               unsigned* bar, unsigned* fault, int rows, int C, int ld_in, int ld_out,
                                                               int groups, int nchunk, int rc, double inv_n, float eps, int lo_off,
                                                               unsigned seq, unsigned want, GnCast cast) {
-  extern __shared__ float sh[];            // phase 1: parked sums [2][R][C]; phase 2: scale[C] | shift[C]
-  __shared__ float stat[2 * 32];           // {mean, rstd} per group (groups <= 32)
-  const int tid = threadIdx.x;
-  const int inst = blockIdx.x / nchunk, chunk = blockIdx.x - inst * nchunk;
-  const int cv = C >> 3;
-  const int R = GNC_THREADS / cv;
-  const int cs = tid % cv, rr = tid / cv;
-  const bool live = rr < R;
-  const int r0 = chunk * rc, r1 = min(rows, r0 + rc);
-  const int c8 = cs * 8;
-  const T* xb = x + (size_t)inst * rows * ld_in + c8;
-  const bool tags = seq != 0u;            // tagged records instead of the grid barrier (t2v_kernels.h)
-  unsigned gen0 = 0;
-  if (!tags && tid == 0) gen0 = t2v_grid_epoch(bar);
+  extern __shared__ float sh[];            // parked sums [2][R][C], then scale[C] | shift[C]
+  const GnCoopTile t = gn_coop_tile(rows, C, nchunk, rc);
+  GnExchange ex = {partials, bar, fault, seq, want, 0u};
+  if (seq == 0u && threadIdx.x == 0) ex.gen0 = t2v_grid_epoch(bar);
   f32x8 v[KR];
-  f32x8 s, q;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
-  if (live) {
+  if (t.live) {
+    const T* xb = x + (size_t)t.inst * rows * ld_in + t.c8;
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
-      const int r = r0 + rr + k * R;
-      if (r < r1) v[k] = Load8<T>::ld(xb + (size_t)r * ld_in);
-      else {
+      const int r = t.r0 + t.rr + k * t.R;
+      if (r < t.r1) v[k] = LoadN<T, 8>::ld(xb + (size_t)r * ld_in);
+      else v[k] = 0.f;
+    }
+  }
+  gn_coop_core<SILU, KR>(v, t, sh, rows, C, groups, C / groups, nchunk, ex, inv_n, eps, GnAffine{gamma, beta, out, ld_out, lo_off}, cast);
+}
+
+// Loader: the split-K reduction (T2V_EPI_GN on a split-K GEMM, round 5).  The long-K convolutions of the 8x8 / 4x4 levels run split-K: fp32
+// slabs, then splitk_reduce_kernel (sum + bias + row bias + residual -> the result), then the GroupNorm that consumes it (one more launch,
+// one more read).  Here every thread sums its rows x 8 channels over the slabs into registers (+ bias / row bias / wrapped residual) and
+// stores the fp32 (fp16) result only if someone else reads it.
+template <bool SILU, int KR>
+__global__ __launch_bounds__(GNC_THREADS) void splitk_gn_kernel(const GemmParams p, int nchunk, int rc) {
+  extern __shared__ float sh[];            // parked sums [2][R][C], then scale[C] | shift[C]
+  const int C = p.N, rows = p.gn_rows;
+  const GnCoopTile t = gn_coop_tile(rows, C, nchunk, rc);
+  GnExchange ex = {p.gn_part, p.gn_bar, p.gn_fault, p.gn_seq, p.gn_want, 0u};
+  if (p.gn_seq == 0u && threadIdx.x == 0) ex.gen0 = t2v_grid_epoch(p.gn_bar);
+  f32x8 v[KR];
+  if (t.live) {
+    const int c8 = t.c8;
+    f32x8 cb = 0.f;
+    if (p.bias) cb = LoadN<float, 8>::ld(p.bias + c8);
+    const size_t zs = (size_t)p.M * p.N;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[k][e] = 0.f;
+    for (int k = 0; k < KR; ++k) {
+      const int r = t.r0 + t.rr + k * t.R;
+      if (r < t.r1) {
+        const size_t m = (size_t)t.inst * rows + r;
+        const float* col = p.ws + m * p.N + c8;
+        f32x8 a = LoadN<float, 8>::ld(col);
+        for (int z = 1; z < p.splitk; ++z) a += LoadN<float, 8>::ld(col + (size_t)z * zs);      // split order, as the reduction kernel
+        a += cb;
+        if (p.rowbias) a += LoadN<float, 8>::ld(p.rowbias + (m / p.rows_per_batch) * p.ldrb + c8);
+        if (p.res) a += LoadN<float, 8>::ld(p.res + ((p.res_wrap && m >= (size_t)p.res_wrap) ? m - (size_t)p.res_wrap : m) * p.ldr + c8);
+        if (p.gn_store_out) {
+          if (p.out_f32) {
+            float* dst = reinterpret_cast<float*>(p.out) + m * p.ldc + c8;
+            *reinterpret_cast<f32x4*>(dst) = f32x4{a[0], a[1], a[2], a[3]};
+            *reinterpret_cast<f32x4*>(dst + 4) = f32x4{a[4], a[5], a[6], a[7]};
+          } else {
+            f16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (f16)a[e];
+            *reinterpret_cast<f16x8*>(reinterpret_cast<f16*>(p.out) + m * p.ldc + c8) = o;
+          }
+        }
+        v[k] = a;
+      } else {
+        v[k] = 0.f;
       }
     }
-#pragma unroll
-    for (int k = 0; k < KR; ++k) { s += v[k]; q += v[k] * v[k]; }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sh[rr * C + c8 + e] = s[e]; sh[(R + rr) * C + c8 + e] = q[e]; }
   }
-  __syncthreads();
-  const int cpg = C / groups;
-  const int g = tid >> 4, sub = tid & 15;          // 16 lanes per group (groups <= 32)
-  {
-    double ds = 0.0, dq = 0.0;
-    if (g < groups) {
-      const int n = R * cpg;
-      for (int i = sub; i < n; i += 16) {
-        const int k = i / cpg, c = g * cpg + (i - k * cpg);
-        ds += (double)sh[k * C + c];
-        dq += (double)sh[(R + k) * C + c];
-      }
-    }
-    for (int o = 1; o < 16; o <<= 1) { ds += __shfl_xor(ds, o); dq += __shfl_xor(dq, o); }
-    if (g < groups && sub == 0) {
-      double* st = partials + (((size_t)inst * nchunk + chunk) * groups + g) * 2;
-      t2v_st_dev(reinterpret_cast<float*>(st), t2v_rec_pack(ds, dq, seq));           // one 16-byte device-scope (write-through) store,
-      if (!tags) t2v_wait_vm0();                                                     // (barrier mode) complete before this workgroup arrives
-    }
-  }
-  if (!tags) t2v_grid_barrier(bar, gridDim.x, gen0, fault);
-  {
-    double ds = 0.0, dq = 0.0;
-    if (g < groups) {
-      // fixed order (the same on every workgroup of the instance); EIGHT 16-byte device-scope loads in flight per round —
-      // one load-use round trip at a time made this fold the longest phase of the kernel (8 dependent ~2 us latencies)
-      const double* base = partials + ((size_t)inst * nchunk * groups + g) * 2;
-      for (int c = sub; c < nchunk; c += 128) {
-        f32x4 t[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int nrec = min(8, (nchunk - c + 15) / 16);
-        t2v_rec_fetch8([&](int j) { return reinterpret_cast<const float*>(base + (size_t)(c + 16 * j) * groups * 2); }, nrec, want, fault, t);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (j < nrec) t2v_rec_add(t[j], ds, dq);
-      }
-    }
-    for (int o = 1; o < 16; o <<= 1) { ds += __shfl_xor(ds, o); dq += __shfl_xor(dq, o); }
-    if (g < groups && sub == 0) {
-      const double m = ds * inv_n;
-      double var = dq * inv_n - m * m;
-      var = var < 0.0 ? 0.0 : var;
-      stat[2 * g] = (float)m;
-      stat[2 * g + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-  }
-  __syncthreads();                                            // (also: everyone is done with the parked sums)
-  for (int c = tid; c < C; c += GNC_THREADS) {
-    const int grp = c / cpg;
-    const float a = stat[2 * grp + 1] * gamma[c];
-    sh[c] = a;
-    sh[C + c] = beta[c] - stat[2 * grp] * a;
-  }
-  __syncthreads();
-  if (!live) return;
-  const f32x8 a = Load8<float>::ld(sh + c8), b = Load8<float>::ld(sh + C + c8);
-  f16* ob = out + (size_t)inst * rows * ld_out + c8;
-#pragma unroll
-  for (int k = 0; k < KR; ++k) {
-    const int r = r0 + rr + k * R;
-    if (r < r1) {
-      f16x8 o, l;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float y = v[k][e] * a[e] + b[e];
-        if (SILU) y = t2v_silu(y);
-        o[e] = (f16)y;
-        l[e] = (f16)(y - (float)o[e]);
-      }
-      *reinterpret_cast<f16x8*>(ob + (size_t)r * ld_out) = o;
-      if (lo_off) *reinterpret_cast<f16x8*>(ob + (size_t)r * ld_out + lo_off) = l;
-      if (cast.out) gn_cast_store8(cast, (size_t)inst * rows + r, c8, v[k]);
-    }
-  }
+  gn_coop_core<SILU, KR>(v, t, sh, rows, C, C / p.gn_cpg, p.gn_cpg, nchunk, ex, 1.0 / ((double)rows * p.gn_cpg), p.gn_eps,
+                         GnAffine{p.gn_gb, p.gn_gb + C, p.gn_out, p.ld_gn, p.gn_lo}, GnCast{nullptr, 0, 0});
 }
 
 // Host-side state of the cooperative path: the fault word (host-mapped, one per process), and per (instantiation, device) the
@@ -592,179 +604,56 @@ unsigned* coop_fault_word() {
   return g_coop.fault;
 }
 
-// true when the launch may rely on co-residency: the flag word exists, no earlier fault, and `nwg` workgroups of this
+// true when the launch may rely on co-residency: t2v_coop_allowed() (the flag word exists, no earlier fault), and `nwg` workgroups of this
 // instantiation fit the stream's device at the occupancy the runtime computes for it (registers, LDS, waves)
 template <typename K>
 bool coop_fits(K kernel, int nwg, size_t lds, hipStream_t s, int* cache) {
-  if (g_coop.disabled || coop_fault_word() == nullptr) return false;
-  if (__atomic_load_n(g_coop.fault, __ATOMIC_RELAXED) != 0u) { g_coop.disabled = true; return false; }
-  return t2v_grid_fits(reinterpret_cast<const void*>(kernel), GNC_THREADS, lds, nwg, s, cache);
+  return t2v_coop_allowed() && t2v_grid_fits(reinterpret_cast<const void*>(kernel), GNC_THREADS, lds, nwg, s, cache);
 }
 
-template <typename T, bool SILU>
-bool gn_coop_launch(int kr, dim3 grid, size_t lds, hipStream_t s, const T* x, const float* gamma, const float* beta, f16* out,
+// Run-time value -> template argument: f(std::true_type / std::false_type), and f(std::integral_constant<int, K>) for the K of KS... that
+// equals kr (false: none does).  A `static` inside the generic lambda f is one object per instantiation — the per-device occupancy caches.
+template <typename F>
+void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <int... KS, typename F>
+bool dispatch_kr(int kr, std::integer_sequence<int, KS...>, F&& f) {
+  return ((kr == KS && (f(std::integral_constant<int, KS>{}), true)) || ...);
+}
+
+// Chunking of the cooperative kernels: with kr rows per thread a workgroup covers rc = (GNC_THREADS / cv) * kr rows of an instance.  Returns
+// the first kr of kr_list (ascending) whose grid, n_inst * nchunk workgroups, is at most one workgroup per CU with at most max_chunk
+// chunks per instance; 0: none.
+int coop_chunking(int rows, int n_inst, int cv, int ncu, int max_chunk, std::initializer_list<int> kr_list, int* rc_out, int* nchunk_out) {
+  for (int kr : kr_list) {
+    const int rc = (GNC_THREADS / cv) * kr, nchunk = (rows + rc - 1) / rc;
+    if ((long)n_inst * nchunk <= ncu && nchunk <= max_chunk) { *rc_out = rc; *nchunk_out = nchunk; return kr; }
+  }
+  return 0;
+}
+
+template <typename T>
+bool gn_coop_launch(bool silu, int kr, dim3 grid, size_t lds, hipStream_t s, const T* x, const float* gamma, const float* beta, f16* out,
                     double* partials, unsigned* bar, int rows, int C, int ld_in, int ld_out, int groups, int nchunk, int rc, double inv_n,
                     float eps, int lo_off, double* records, GnCast cast) {
-  // tagged records need a region that only ever holds records (a recycled arena block could hold a matching bit pattern by chance):
-  // op.p[7], the program's exchange scratch; without it the grid barrier synchronises and the per-op scratch carries the partials
-  unsigned seq = 0, want = 0;
-#define GNC_CASE(K)                                                                                                              \
-  case K: {                                                                                                                      \
-    static int occ[T2V_MAX_DEVICES] = {};                                                                                        \
-    auto kern = gn_coop_kernel<T, SILU, K>;                                                                                      \
-    if (!coop_fits(kern, (int)grid.x, lds, s, occ)) return false;                                                                \
-    if (records != nullptr) t2v_exchange_ids(&seq, &want);                                                                       \
-    hipLaunchKernelGGL(kern, grid, dim3(GNC_THREADS), lds, s, x, gamma, beta, out, seq != 0u ? records : partials, bar,           \
-                       g_coop.fault, rows, C, ld_in, ld_out, groups, nchunk, rc, inv_n, eps, lo_off, seq, want, cast);           \
-    return true;                                                                                                                 \
-  }
-  switch (kr) {
-    GNC_CASE(4) GNC_CASE(8) GNC_CASE(12) GNC_CASE(16) GNC_CASE(20)
-    default: break;
-  }
-#undef GNC_CASE
-  return false;
-}
-
-// ---- split-K reduction + GroupNorm (+SiLU) in ONE cooperative launch (T2V_EPI_GN on a split-K GEMM, round 5) ------------------------
-// The long-K convolutions of the 8x8 / 4x4 levels run split-K: fp32 slabs, then splitk_reduce_kernel (sum + bias + row bias + residual
-// -> the result), then the GroupNorm that consumes it (one more launch, one more read).  Here the reduction IS the loader of the
-// single-pass GroupNorm above: every thread sums its rows x 8 channels over the slabs into registers (+ bias / row bias / residual),
-// stores the fp32 (fp16) result only if someone else reads it, and the statistics / barrier / normalise phases are gn_coop_kernel's.
-template <bool SILU, int KR>
-__global__ __launch_bounds__(GNC_THREADS) void splitk_gn_kernel(const GemmParams p, int nchunk, int rc) {
-  extern __shared__ float sh[];            // phase 1: parked sums [2][R][C]; phase 2: scale[C] | shift[C]
-  __shared__ float stat[2 * 32];
-  const int tid = threadIdx.x;
-  const int C = p.N, rows = p.gn_rows, groups = C / p.gn_cpg;
-  const int inst = blockIdx.x / nchunk, chunk = blockIdx.x - inst * nchunk;
-  const int cv = C >> 3;
-  const int R = GNC_THREADS / cv;
-  const int cs = tid % cv, rr = tid / cv;
-  const bool live = rr < R;
-  const int r0 = chunk * rc, r1 = min(rows, r0 + rc);
-  const int c8 = cs * 8;
-  const bool tags = p.gn_seq != 0u;
-  unsigned gen0 = 0;
-  if (!tags && tid == 0) gen0 = t2v_grid_epoch(p.gn_bar);
-  f32x8 v[KR];
-  f32x8 s, q;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
-  if (live) {
-    f32x8 cb;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) cb[e] = 0.f;
-    if (p.bias) cb = Load8<float>::ld(p.bias + c8);
-    const size_t zs = (size_t)p.M * p.N;
-#pragma unroll
-    for (int k = 0; k < KR; ++k) {
-      const int r = r0 + rr + k * R;
-      if (r < r1) {
-        const size_t m = (size_t)inst * rows + r;
-        const float* col = p.ws + m * p.N + c8;
-        f32x8 a = Load8<float>::ld(col);
-        for (int z = 1; z < p.splitk; ++z) a += Load8<float>::ld(col + (size_t)z * zs);      // split order, as the reduction kernel
-        a += cb;
-        if (p.rowbias) a += Load8<float>::ld(p.rowbias + (m / p.rows_per_batch) * p.ldrb + c8);
-        if (p.res) a += Load8<float>::ld(p.res + ((p.res_wrap && m >= (size_t)p.res_wrap) ? m - (size_t)p.res_wrap : m) * p.ldr + c8);
-        if (p.gn_store_out) {
-          if (p.out_f32) {
-            float* dst = reinterpret_cast<float*>(p.out) + m * p.ldc + c8;
-            *reinterpret_cast<f32x4*>(dst) = f32x4{a[0], a[1], a[2], a[3]};
-            *reinterpret_cast<f32x4*>(dst + 4) = f32x4{a[4], a[5], a[6], a[7]};
-          } else {
-            f16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (f16)a[e];
-            *reinterpret_cast<f16x8*>(reinterpret_cast<f16*>(p.out) + m * p.ldc + c8) = o;
-          }
-        }
-        v[k] = a;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[k][e] = 0.f;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < KR; ++k) { s += v[k]; q += v[k] * v[k]; }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sh[rr * C + c8 + e] = s[e]; sh[(R + rr) * C + c8 + e] = q[e]; }
-  }
-  __syncthreads();
-  const int cpg = p.gn_cpg;
-  const int g = tid >> 4, sub = tid & 15;          // 16 lanes per group (groups <= 32)
-  double* partials = p.gn_part;
-  {
-    double ds = 0.0, dq = 0.0;
-    if (g < groups) {
-      const int n = R * cpg;
-      for (int i = sub; i < n; i += 16) {
-        const int k = i / cpg, c = g * cpg + (i - k * cpg);
-        ds += (double)sh[k * C + c];
-        dq += (double)sh[(R + k) * C + c];
-      }
-    }
-    for (int o = 1; o < 16; o <<= 1) { ds += __shfl_xor(ds, o); dq += __shfl_xor(dq, o); }
-    if (g < groups && sub == 0) {
-      double* st = partials + (((size_t)inst * nchunk + chunk) * groups + g) * 2;
-      t2v_st_dev(reinterpret_cast<float*>(st), t2v_rec_pack(ds, dq, p.gn_seq));
-      if (!tags) t2v_wait_vm0();
-    }
-  }
-  if (!tags) t2v_grid_barrier(p.gn_bar, gridDim.x, gen0, p.gn_fault);
-  {
-    double ds = 0.0, dq = 0.0;
-    if (g < groups) {
-      const double* base = partials + ((size_t)inst * nchunk * groups + g) * 2;
-      for (int c = sub; c < nchunk; c += 128) {
-        f32x4 t[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int nrec = min(8, (nchunk - c + 15) / 16);
-        t2v_rec_fetch8([&](int j) { return reinterpret_cast<const float*>(base + (size_t)(c + 16 * j) * groups * 2); }, nrec, p.gn_want, p.gn_fault, t);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (j < nrec) t2v_rec_add(t[j], ds, dq);
-      }
-    }
-    for (int o = 1; o < 16; o <<= 1) { ds += __shfl_xor(ds, o); dq += __shfl_xor(dq, o); }
-    if (g < groups && sub == 0) {
-      const double inv_n = 1.0 / ((double)rows * cpg);
-      const double m = ds * inv_n;
-      double var = dq * inv_n - m * m;
-      var = var < 0.0 ? 0.0 : var;
-      stat[2 * g] = (float)m;
-      stat[2 * g + 1] = (float)(1.0 / sqrt(var + (double)p.gn_eps));
-    }
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += GNC_THREADS) {
-    const int grp = c / cpg;
-    const float a = stat[2 * grp + 1] * p.gn_gb[c];
-    sh[c] = a;
-    sh[C + c] = p.gn_gb[C + c] - stat[2 * grp] * a;
-  }
-  __syncthreads();
-  if (!live) return;
-  const f32x8 a = Load8<float>::ld(sh + c8), b = Load8<float>::ld(sh + C + c8);
-#pragma unroll
-  for (int k = 0; k < KR; ++k) {
-    const int r = r0 + rr + k * R;
-    if (r < r1) {
-      f16x8 o, l;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float y = v[k][e] * a[e] + b[e];
-        if (SILU) y = t2v_silu(y);
-        o[e] = (f16)y;
-        l[e] = (f16)(y - (float)o[e]);
-      }
-      f16* dst = p.gn_out + ((size_t)inst * rows + r) * p.ld_gn + c8;
-      *reinterpret_cast<f16x8*>(dst) = o;
-      if (p.gn_lo) *reinterpret_cast<f16x8*>(dst + p.gn_lo) = l;
-    }
-  }
+  bool done = false;
+  dispatch_kr(kr, std::integer_sequence<int, 4, 8, 12, 16, 20>{}, [&](auto K) {
+    dispatch_bool(silu, [&](auto S) {
+      static int occ[T2V_MAX_DEVICES] = {};
+      auto kern = gn_coop_kernel<T, decltype(S)::value, decltype(K)::value>;
+      if (!coop_fits(kern, (int)grid.x, lds, s, occ)) return;
+      // tagged records need a region that only ever holds records (a recycled arena block could hold a matching bit pattern by chance):
+      // op.p[7], the program's exchange scratch; without it the grid barrier synchronises and the per-op scratch carries the partials
+      unsigned seq = 0, want = 0;
+      if (records != nullptr) t2v_exchange_ids(&seq, &want);
+      hipLaunchKernelGGL(kern, grid, dim3(GNC_THREADS), lds, s, x, gamma, beta, out, seq != 0u ? records : partials, bar, g_coop.fault, rows, C,
+                         ld_in, ld_out, groups, nchunk, rc, inv_n, eps, lo_off, seq, want, cast);
+      done = true;
+    });
+  });
+  return done;
 }
 
 // LayerNorm: one wave per row, row held in registers (C <= 64*4*MAXV).  A wave walks several rows (grid-stride): gamma / beta
@@ -888,47 +777,29 @@ int t2v_num_cus(hipStream_t s) {
   return ncu[d];
 }
 
-// rows per thread of the split-K + GroupNorm launch for this geometry on the stream's device (0: no co-resident grid exists)
-static int splitk_gn_kr(const GemmParams& p, hipStream_t s, int* rc_out, int* nchunk_out) {
+hipError_t t2v_launch_splitk_reduce_gn(const GemmParams& p, hipStream_t s) {
   const int cv = p.N / 8;
-  if (p.N % 8 != 0 || cv > GNC_THREADS || p.gn_cpg <= 0 || p.N / p.gn_cpg > 32 || p.gn_rows <= 0 || p.M % p.gn_rows != 0) return 0;
-  const int Rc = GNC_THREADS / cv, ncu = t2v_num_cus(s), n_inst = p.M / p.gn_rows;
+  if (p.N % 8 != 0 || cv > GNC_THREADS || p.gn_cpg <= 0 || p.N / p.gn_cpg > 32 || p.gn_rows <= 0 || p.M % p.gn_rows != 0)
+    return hipErrorCooperativeLaunchTooLarge;
+  const int n_inst = p.M / p.gn_rows;
   // the FEWEST rows per thread whose grid is still resident at once: the loader sums `splitk` slabs per element, and at the 4x4 level
   // (768 rows) 4 rows per thread left 64 workgroups to read 8 slabs — measured slower than the reduction kernel + the norm it replaces
-  for (int kr : {1, 2, 4, 8, 12, 16, 20}) {
-    const int rc = Rc * kr, nchunk = (p.gn_rows + rc - 1) / rc;
-    if ((long)n_inst * nchunk <= ncu) { *rc_out = rc; *nchunk_out = nchunk; return kr; }
-  }
-  return 0;
-}
-
-hipError_t t2v_launch_splitk_reduce_gn(const GemmParams& p, hipStream_t s) {
   int rc = 0, nchunk = 0;
-  const int kr = splitk_gn_kr(p, s, &rc, &nchunk);
+  const int kr = coop_chunking(p.gn_rows, n_inst, cv, t2v_num_cus(s), INT_MAX, {1, 2, 4, 8, 12, 16, 20}, &rc, &nchunk);
   if (kr == 0 || !t2v_coop_allowed() || p.epi != T2V_EPI_NONE || p.act != 0 || p.bias_m) return hipErrorCooperativeLaunchTooLarge;
-  const int cv = p.N / 8, n_inst = p.M / p.gn_rows;
   const size_t lds = (size_t)2 * (GNC_THREADS / cv) * p.N * sizeof(float);
   const dim3 grid(n_inst * nchunk);
-#define SKG_CASE(K)                                                                                                         \
-  case K: {                                                                                                                 \
-    static int occ_s[T2V_MAX_DEVICES] = {}, occ_n[T2V_MAX_DEVICES] = {};                                                    \
-    if (p.gn_silu) {                                                                                                        \
-      auto kern = splitk_gn_kernel<true, K>;                                                                                \
-      if (!t2v_grid_fits(reinterpret_cast<const void*>(kern), GNC_THREADS, lds, grid.x, s, occ_s)) return hipErrorCooperativeLaunchTooLarge; \
-      hipLaunchKernelGGL(kern, grid, dim3(GNC_THREADS), lds, s, p, nchunk, rc);                                             \
-    } else {                                                                                                                \
-      auto kern = splitk_gn_kernel<false, K>;                                                                               \
-      if (!t2v_grid_fits(reinterpret_cast<const void*>(kern), GNC_THREADS, lds, grid.x, s, occ_n)) return hipErrorCooperativeLaunchTooLarge; \
-      hipLaunchKernelGGL(kern, grid, dim3(GNC_THREADS), lds, s, p, nchunk, rc);                                             \
-    }                                                                                                                       \
-    return hipGetLastError();                                                                                               \
-  }
-  switch (kr) {
-    SKG_CASE(1) SKG_CASE(2) SKG_CASE(4) SKG_CASE(8) SKG_CASE(12) SKG_CASE(16) SKG_CASE(20)
-    default: break;
-  }
-#undef SKG_CASE
-  return hipErrorInvalidValue;
+  hipError_t err = hipErrorInvalidValue;
+  dispatch_kr(kr, std::integer_sequence<int, 1, 2, 4, 8, 12, 16, 20>{}, [&](auto K) {
+    dispatch_bool(p.gn_silu != 0, [&](auto S) {
+      static int occ[T2V_MAX_DEVICES] = {};
+      auto kern = splitk_gn_kernel<decltype(S)::value, decltype(K)::value>;
+      if (!t2v_grid_fits(reinterpret_cast<const void*>(kern), GNC_THREADS, lds, grid.x, s, occ)) { err = hipErrorCooperativeLaunchTooLarge; return; }
+      hipLaunchKernelGGL(kern, grid, dim3(GNC_THREADS), lds, s, p, nchunk, rc);
+      err = hipGetLastError();
+    });
+  });
+  return err;
 }
 
 // Sequence numbers of the tagged-record exchange: process-wide, never 0, never repeated within 2^32 fused-norm launches (a record slot
@@ -1035,15 +906,11 @@ hipError_t t2v_launch_groupnorm(const t2v_op& op, hipStream_t s) {
   if (cast.out != nullptr && (phase == 1 || cast.ld < C + (cast.lo ? C : 0) || cast.ld % 8 != 0 || cast.lo % 8 != 0)) return hipErrorInvalidValue;
   if (lo_off && (phase == 1 || ld_out < 2 * C)) return hipErrorInvalidValue;
   if (fused && (phase != 0 || (C / groups) % 4 != 0 || (C / groups) / 4 > GNF_THREADS)) return hipErrorInvalidValue;
-  // single-pass cooperative variant: the smallest rows-per-thread count whose grid still fits one workgroup per CU
+  // single-pass cooperative variant: the smallest rows-per-thread count whose grid still fits one workgroup per CU, with no more chunks than
+  // the three-launch path has blocks (its scratch carries the partials in barrier mode)
   int coop_kr = 0, coop_rc = 0, coop_nchunk = 0;
-  if (op.i[15] != 0 && op.p[5] != 0 && phase == 0 && !fused && groups <= 32 && cv <= GNC_THREADS) {
-    const int Rc = GNC_THREADS / cv, ncu = t2v_num_cus(s);
-    for (int kr : {4, 8, 12, 16, 20}) {
-      const int rc = Rc * kr, nchunk = (rows + rc - 1) / rc;
-      if ((long)n_inst * nchunk <= ncu && nchunk <= nblk) { coop_kr = kr; coop_rc = rc; coop_nchunk = nchunk; break; }
-    }
-  }
+  if (op.i[15] != 0 && op.p[5] != 0 && phase == 0 && !fused && groups <= 32 && cv <= GNC_THREADS)
+    coop_kr = coop_chunking(rows, n_inst, cv, t2v_num_cus(s), nblk, {4, 8, 12, 16, 20}, &coop_rc, &coop_nchunk);
   auto run = [&](auto* x) {
     using T = typename std::remove_cv<typename std::remove_pointer<decltype(x)>::type>::type;
     if (coop_kr) {
@@ -1051,17 +918,15 @@ hipError_t t2v_launch_groupnorm(const t2v_op& op, hipStream_t s) {
       unsigned* bar = reinterpret_cast<unsigned*>(op.p[5]);
       const dim3 grid(n_inst * coop_nchunk);
       double* records = ((size_t)n_inst * coop_nchunk * groups * 16 <= (size_t)op.i[18]) ? reinterpret_cast<double*>(op.p[7]) : nullptr;
-      const bool done = silu ? gn_coop_launch<T, true>(coop_kr, grid, ldsc, s, x, gamma, beta, out, partials, bar, rows, C, ld_in, ld_out, groups,
-                                                       coop_nchunk, coop_rc, inv_n, op.f[0], lo_off, records, cast)
-                             : gn_coop_launch<T, false>(coop_kr, grid, ldsc, s, x, gamma, beta, out, partials, bar, rows, C, ld_in, ld_out, groups,
-                                                        coop_nchunk, coop_rc, inv_n, op.f[0], lo_off, records, cast);
-      if (done) return;             // else: not provably co-resident (or a fault was raised earlier) -> the three launches below
+      if (gn_coop_launch(silu != 0, coop_kr, grid, ldsc, s, x, gamma, beta, out, partials, bar, rows, C, ld_in, ld_out, groups, coop_nchunk, coop_rc,
+                         inv_n, op.f[0], lo_off, records, cast))
+        return;                     // else: not provably co-resident (or a fault was raised earlier) -> the three launches below
     }
     if (fused) {
-      if (silu) hipLaunchKernelGGL((gn_fused_kernel<T, true>), dim3(groups * n_inst), dim3(GNF_THREADS), 0, s, x, gamma, beta, out, rows,
-                                   C, ld_in, ld_out, groups, op.f[0], lo_off, cast);
-      else hipLaunchKernelGGL((gn_fused_kernel<T, false>), dim3(groups * n_inst), dim3(GNF_THREADS), 0, s, x, gamma, beta, out, rows, C,
-                              ld_in, ld_out, groups, op.f[0], lo_off, cast);
+      dispatch_bool(silu != 0, [&](auto S) {
+        hipLaunchKernelGGL((gn_fused_kernel<T, decltype(S)::value>), dim3(groups * n_inst), dim3(GNF_THREADS), 0, s, x, gamma, beta, out, rows, C,
+                           ld_in, ld_out, groups, op.f[0], lo_off, cast);
+      });
       return;
     }
     double* raw_part = strips1 ? partials + part_len * part : nullptr;
@@ -1091,10 +956,10 @@ hipError_t t2v_launch_groupnorm(const t2v_op& op, hipStream_t s) {
       f16* aout = out - (size_t)before * ld_out;
       const dim3 g3((arows + rpa - 1) / rpa, n_inst);
       const size_t lds3 = (2 * (size_t)C + (parts2 ? 2 * (size_t)groups : 0)) * sizeof(float);
-      if (silu) hipLaunchKernelGGL((gn_apply_kernel<T, true>), g3, dim3(256), lds3, s, ax, finals, gamma, beta, aout, arows, C, ld_in, ld_out, groups, lo_off, cast,
-                                   parts2, nparts, (long)part_len, inv_n, op.f[0]);
-      else hipLaunchKernelGGL((gn_apply_kernel<T, false>), g3, dim3(256), lds3, s, ax, finals, gamma, beta, aout, arows, C, ld_in, ld_out, groups, lo_off, cast,
-                              parts2, nparts, (long)part_len, inv_n, op.f[0]);
+      dispatch_bool(silu != 0, [&](auto S) {
+        hipLaunchKernelGGL((gn_apply_kernel<T, decltype(S)::value>), g3, dim3(256), lds3, s, ax, finals, gamma, beta, aout, arows, C, ld_in, ld_out, groups,
+                           lo_off, cast, parts2, nparts, (long)part_len, inv_n, op.f[0]);
+      });
     }
   };
   if (in_dt == T2V_F32) run(reinterpret_cast<const float*>(op.p[0]));
@@ -1114,13 +979,10 @@ hipError_t t2v_launch_layernorm(const t2v_op& op, hipStream_t s) {
   const int wgs = (M + 3) / 4;
   const int cap = op.i[4] > 0 ? op.i[4] : 8 * 256;
   const dim3 grid_rows(wgs < cap ? wgs : cap), grid(wgs);
-  if (C <= 64 * 4 * 2)
-    hipLaunchKernelGGL(layernorm_rows_kernel<2>, grid_rows, dim3(256), 0, s, x, gamma, beta, out, M, C, ld_in, ld_out, op.f[0]);
-  else if (C <= 64 * 4 * 3)
-    hipLaunchKernelGGL(layernorm_rows_kernel<3>, grid_rows, dim3(256), 0, s, x, gamma, beta, out, M, C, ld_in, ld_out, op.f[0]);
-  else if (C <= 64 * 4 * 5)
-    hipLaunchKernelGGL(layernorm_kernel<5>, grid, dim3(256), 0, s, x, gamma, beta, out, M, C, ld_in, ld_out, op.f[0]);
-  else
-    hipLaunchKernelGGL(layernorm_kernel<8>, grid, dim3(256), 0, s, x, gamma, beta, out, M, C, ld_in, ld_out, op.f[0]);
+  auto launch = [&](auto kern, dim3 g) { hipLaunchKernelGGL(kern, g, dim3(256), 0, s, x, gamma, beta, out, M, C, ld_in, ld_out, op.f[0]); };
+  if (C <= 64 * 4 * 2) launch(layernorm_rows_kernel<2>, grid_rows);
+  else if (C <= 64 * 4 * 3) launch(layernorm_rows_kernel<3>, grid_rows);
+  else if (C <= 64 * 4 * 5) launch(layernorm_kernel<5>, grid);
+  else launch(layernorm_kernel<8>, grid);
   return hipGetLastError();
 }

@@ -267,6 +267,33 @@ __device__ __forceinline__ float t2v_silu(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f));
 }
 
+// ---- the two pieces every GroupNorm form shares (norm.hip's kernels, t2v_epilogue_rows_gn; t2v_mean_rstd also t2v_epilogue_rows_lnx) ----
+template <int N> using f32xN = float __attribute__((ext_vector_type(N)));
+template <int N> using f16xN = f16 __attribute__((ext_vector_type(N)));
+// {mean, rstd} of n = 1 / inv_n values from their fp64 sum and sum of squares.  The statistics of one instance must come out bit-identical
+// in every workgroup of a launch and on every T-shard rank: this is the ONLY place the expression is written.
+__device__ __forceinline__ float2 t2v_mean_rstd(double s, double q, double inv_n, float eps) {
+  const double m = s * inv_n;
+  double var = q * inv_n - m * m;
+  var = var < 0.0 ? 0.0 : var;
+  return float2{(float)m, (float)(1.0 / sqrt(var + (double)eps))};
+}
+// y = v * a + b (+SiLU) for N = 4 / 8 consecutive channels of one row -> fp16 at dst, and, lo_off != 0, the low-order image y - (float)hi
+// at dst + lo_off (hi + lo operand split): one or two N-wide stores.  `silu` is a constant at every call site but the GEMM epilogue's.
+template <int N>
+__device__ __forceinline__ void t2v_norm_store(f16* dst, int lo_off, const f32xN<N>& v, const f32xN<N>& a, const f32xN<N>& b, bool silu) {
+  f16xN<N> o, l;
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    float y = v[e] * a[e] + b[e];
+    if (silu) y = t2v_silu(y);
+    o[e] = (f16)y;
+    l[e] = (f16)(y - (float)o[e]);
+  }
+  *reinterpret_cast<f16xN<N>*>(dst) = o;
+  if (lo_off) *reinterpret_cast<f16xN<N>*>(dst + lo_off) = l;
+}
+
 // 16-byte LDS-DMA of the GEMM operand stages: lane l's 16 bytes at gsrc land at lds_wave_base + 16 l
 #define T2V_AS1 __attribute__((address_space(1)))
 #define T2V_AS3 __attribute__((address_space(3)))
@@ -728,8 +755,9 @@ __device__ __forceinline__ void t2v_rec_fetch8(F addr, int n, unsigned want, uns
 //      {sum, sum of squares} pair with a device-scope store: [tile_m][slot][tile_n][piece];
 //   C  bounded grid barrier (every workgroup of the launch is resident: checked by the launcher);
 //   D  8 lanes per (slot, group) fold the published pairs of every tile of the instance (and of both column tiles of a cut group)
-//      in a fixed order — every workgroup the same values in the same order: bit-identical statistics, no atomics on data;
-//   E  scale / shift per (slot, column) in LDS, normalise (+SiLU) from registers, fp16 out (+ low-order image).
+//      in a fixed order — every workgroup the same values in the same order: bit-identical statistics, no atomics on data — then
+//      t2v_mean_rstd, the expression the stand-alone kernels of norm.hip use;
+//   E  scale / shift per (slot, column) in LDS, normalise (+SiLU) from registers, fp16 out (+ low-order image): t2v_norm_store.
 // Rows >= M / columns >= N contribute zeros to the sums and are not stored.
 template <int WM, int WN, int TM, int TN>
 __device__ __forceinline__ void t2v_epilogue_rows_gn(const GemmParams& p, f32x16 (&acc)[TM][TN], unsigned char* smem, int lane, int wave,
@@ -901,11 +929,9 @@ __device__ __forceinline__ void t2v_epilogue_rows_gn(const GemmParams& p, f32x16
     }
     for (int o = 1; o < lpi; o <<= 1) { ds += __shfl_xor(ds, o); dq += __shfl_xor(dq, o); }      // (lpi is workgroup-uniform)
     if (active && sub == 0) {
-      const double m = ds * inv_n;
-      double var = dq * inv_n - m * m;
-      var = var < 0.0 ? 0.0 : var;
-      stat[(slot * T2V_GN_PIECES + pc) * 2] = (float)m;
-      stat[(slot * T2V_GN_PIECES + pc) * 2 + 1] = (float)(1.0 / sqrt(var + (double)p.gn_eps));
+      const float2 mr = t2v_mean_rstd(ds, dq, inv_n, p.gn_eps);
+      stat[(slot * T2V_GN_PIECES + pc) * 2] = mr.x;
+      stat[(slot * T2V_GN_PIECES + pc) * 2 + 1] = mr.y;
     }
   }
   __syncthreads();
@@ -934,19 +960,9 @@ __device__ __forceinline__ void t2v_epilogue_rows_gn(const GemmParams& p, f32x16
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int m = mt + rrow + 8 * i;
-        if (m < p.M) {
-          f16x4 o, l;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float y = acc[a][b][4 * i + e] * sc[e] + sf[e];
-            if (p.gn_silu) y = t2v_silu(y);
-            o[e] = (f16)y;
-            l[e] = (f16)(y - (float)o[e]);
-          }
-          f16* dst = p.gn_out + (size_t)m * p.ld_gn + n;
-          *reinterpret_cast<f16x4*>(dst) = o;
-          if (p.gn_lo) *reinterpret_cast<f16x4*>(dst + p.gn_lo) = l;
-        }
+        if (m < p.M)
+          t2v_norm_store<4>(p.gn_out + (size_t)m * p.ld_gn + n, p.gn_lo, f32x4{acc[a][b][4 * i], acc[a][b][4 * i + 1], acc[a][b][4 * i + 2], acc[a][b][4 * i + 3]},
+                            sc, sf, p.gn_silu != 0);
       }
     }
   }
@@ -1074,12 +1090,9 @@ __device__ __forceinline__ void t2v_epilogue_rows_lnx(const GemmParams& p, f32x1
       for (int j = 0; j < 8; ++j)
         if (j < nrec) t2v_rec_add(t[j], ds, dq);
     }
-    const double inv_n = 1.0 / (double)p.N;
-    const double m = ds * inv_n;
-    double var = dq * inv_n - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    rowstat[tid * 2] = (float)m;
-    rowstat[tid * 2 + 1] = (float)(1.0 / sqrt(var + (double)p.ln_eps));
+    const float2 mr = t2v_mean_rstd(ds, dq, 1.0 / (double)p.N, p.ln_eps);
+    rowstat[tid * 2] = mr.x;
+    rowstat[tid * 2 + 1] = mr.y;
   }
   __syncthreads();
 #pragma unroll

@@ -1600,23 +1600,37 @@ def test_groupnorm_in_splitk_reduction_against_torch(kind, C, per_frame, dead, l
         assert rel_l2(read(got, out).float(), ref.permute(0, 2, 1).reshape(M, C)) < 1e-3
 
 
-@pytest.mark.parametrize("n_inst,rows,C,dt,lo", [(2, 1536, 640, "f32", True), (6, 64, 1280, "f32", True), (2, 24576, 640, "f32", False), (4, 256, 320, "f32", True)])
-def test_groupnorm_cast_second_output(n_inst, rows, C, dt, lo):
+# (3, 100, 640, f16): 80 column units x 3 row replicas (16 idle threads), rows ragged against both unroll factors, C/groups = 20 (4-wide units);
+# (2, 77, 128, f32): C/groups = 4, ONE 4-channel unit per group in the single-launch kernel, ragged last chunk
+_GN_CAST_CASES = [(2, 1536, 640, "f32", True), (6, 64, 1280, "f32", True), (2, 24576, 640, "f32", False), (4, 256, 320, "f32", True),
+                  (3, 100, 640, "f16", True), (2, 77, 128, "f32", False)]
+
+
+@pytest.mark.parametrize("n_inst,rows,C,dt,lo,variant", [c + (v,) for c in _GN_CAST_CASES for v in ("three_launch", "cooperative", "single_launch")
+                                                         if v != "single_launch" or (c[2] // 32) % 4 == 0])   # single launch: 4-channel units
+def test_groupnorm_cast_second_output(n_inst, rows, C, dt, lo, variant):
     """Round 5: a GroupNorm whose input also feeds a 1x1 skip convolution writes the raw input's fp16 cast (+ low-order image) as a second
-    output (single-pass cooperative kernel / one-workgroup-per-group kernel / the three-launch path)."""
+    output, from each of the three forms (the three-launch path / single-pass cooperative kernel / one-workgroup-per-group kernel), 8-wide
+    and 4-wide, fp32 and fp16 input."""
     M = n_inst * rows
     P = Program()
+    P.gn_coop = variant == "cooperative"
+    P.gn_fused_slice_bytes = 1 << 30 if variant == "single_launch" else 0
+    P.gn_fused_total_bytes = 1 << 30
     g = _g(800 + C)
     x, out, cast = P.alloc(M, C, dt), P.alloc(M, C, "f16"), P.alloc(M, 2 * C if lo else C, "f16")
     w = {"g": 1 + 0.1 * torch.randn(C, generator=g), "be": 0.1 * torch.randn(C, generator=g)}
     op = P.groupnorm("gn", x, Ref("weight", 0, "g"), Ref("weight", 0, "be"), out, n_inst=n_inst, eps=1e-5, silu=True, cast=cast, cast_lo=lo)
     assert op.kind == L.OP_GROUPNORM and len(P.ops) == 1
+    assert op.i[12] == (variant == "single_launch") and op.i[15] == (variant == "cooperative")
     it, got = _gpu_run(P, w, lambda it: fill(it, x, g, 3.0))
     _check(it, got, out, 1e-3, "normalised output")
     xv = read(got, x).float()
     hi = read(got, cast.col_slice(0, C)).float()
     assert torch.equal(hi, xv.half().float()), "the cast output is not the rounded input"
-    if lo:
+    if lo and dt == "f16":
+        assert torch.equal(hi, xv) and not read(got, cast.col_slice(C, 2 * C)).any(), "an fp16 input is its own cast and has no low-order part"
+    elif lo:
         assert rel_l2(hi + read(got, cast.col_slice(C, 2 * C)).float(), xv) < 1e-6
 
 
