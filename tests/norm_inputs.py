@@ -1,0 +1,637 @@
+"""TEST INFRASTRUCTURE — adversarial inputs for every normalisation path (csrc/norm.hip, the norm epilogues of t2v_kernels.h), a float64
+reference, and the case list with the programs that run them.  No test functions here: tests/test_norm_inputs_cpu.py proves on the CPU
+what the inputs do (and runs every program through the interpreter), tests/test_gpu_norm_adversarial.py runs the same programs on the
+GPU.  Both import CASES / build(), so they cannot drift apart.  Nothing here touches a GPU or imports tests/interp.py: whoever executes a
+program hands its arena view (`it`, anything with Interp's `mat`) to `Built.init` / `verify`, and every expected value is `groupnorm_ref`.
+
+Why these inputs.  The other norm tests fill x with scale * randn + const: every (instance, group) block then has the same mean and
+variance and every row weighs the same, so statistics taken from the neighbouring block, a row lost at a chunk tail or an inv_n that is
+off by a row disappear in one rel-L2 over the tensor.  Here
+  distinct  x = mu[i, g] + sigma[i, g] z: sigma a power of two in [1/8, 8] that differs between neighbouring instances and groups, mu
+            distinct in [-8, 8] with |mu| <= 8 sigma and alternating sign; z is standardised per block, so mu and sigma ARE the block's
+            statistics (LayerNorm: per row);
+  marked    distinct, and in every instance the first and the last row each carry a quarter of the block's sum of squares, the rows either
+            side of every multiple of 32 (strip, tile, chunk seams) are scaled by 4;
+  offset    mean / std = 32 (fp32 inputs) or 8 (fp16 inputs) in every block, sigma as above.
+Inputs are rounded to the input dtype before the reference sees them.  All errors are one rel-L2 per block (`block_rel_l2`); asserts are on
+the maximum over blocks.
+
+Fencing.  Every tensor a norm reads or writes is a window of a larger allocation: rows in front and behind and 8 columns to the right
+(ld = C + 8) are NaN, outputs are NaN-filled, and `verify` wants every window finite and every fence element still NaN."""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn.functional as F
+
+from sd_webui_text2video_amd import _lib as L
+from sd_webui_text2video_amd import packing as pk
+from sd_webui_text2video_amd.program import NULL, Program, Ref, TShardSpec
+
+TOL_F16 = 1e-3          # fp16 output against an explicit reference: the suite's figure for norms
+TOL_HILO = 2e-5         # hi + lo / fp32 results: the suite's figure
+TOL_ROUNDED = 4e-4      # the float64 reference rounded to fp16
+EPS = 1e-5
+GROUPS = 32
+NAN = float("nan")
+TD = {"f16": torch.float16, "f32": torch.float32}
+PAD_ROWS, PAD_COLS = 3, 8
+
+
+# ---- the float64 reference ---------------------------------------------------------------------------------------------------------------
+def _silu(y):
+    return y * torch.sigmoid(y)
+
+
+def group_sums(x, n_inst, groups):
+    """s1, s2 [n_inst, groups] (float64 sums / sums of squares) and n = rows * cpg."""
+    C = x.shape[1]
+    xv = x.double().view(n_inst, -1, groups, C // groups)
+    return xv.sum(dim=(1, 3)), (xv * xv).sum(dim=(1, 3)), xv.shape[1] * xv.shape[3]
+
+
+def mean_var_of(s1, s2, n):
+    mean = s1 / n
+    return mean, (s2 / n - mean * mean).clamp_min(0.0)
+
+
+def groupnorm_ref(x, gamma, beta, n_inst, groups, eps, silu, mean_var=None):
+    """GroupNorm (+ SiLU) of x [n_inst * rows, C] (channels last) in float64, written out: per (instance, group) the mean and the biased
+    variance over rows x C / groups, (x - mean) / sqrt(var + eps) * gamma + beta.  mean_var = (mean, var) [n_inst, groups] replaces the
+    statistics (the mutations of tests/test_norm_inputs_cpu.py)."""
+    M, C = x.shape
+    xv = x.double().view(n_inst, M // n_inst, groups, C // groups)
+    if mean_var is None:
+        mean = xv.mean(dim=(1, 3))
+        var = ((xv - mean[:, None, :, None]) ** 2).mean(dim=(1, 3))
+    else:
+        mean, var = mean_var
+    y = (xv - mean[:, None, :, None]) / torch.sqrt(var[:, None, :, None] + eps)
+    y = y.reshape(M, C) * gamma.double() + beta.double()
+    return _silu(y) if silu else y
+
+
+def layernorm_ref(x, gamma, beta, eps, mean_var=None):
+    """LayerNorm of the rows of x [M, C] in float64: a GroupNorm of M one-row instances with one group."""
+    return groupnorm_ref(x, gamma, beta, x.shape[0], 1, eps, False, mean_var)
+
+
+def blocks(y, n_inst, groups):
+    """[n_inst * rows, C] -> [n_inst, groups, rows * cpg]: one statistics block per (instance, group)."""
+    M, C = y.shape
+    return y.reshape(n_inst, M // n_inst, groups, C // groups).permute(0, 2, 1, 3).reshape(n_inst, groups, -1)
+
+
+def block_rel_l2(got, ref):
+    """One rel-L2 per block: got, ref [..., n] -> [...]."""
+    got, ref = got.double(), ref.double()
+    return (got - ref).norm(dim=-1) / ref.norm(dim=-1).clamp_min(1e-30)
+
+
+def block_err(got, ref, n_inst, groups):
+    return block_rel_l2(blocks(got, n_inst, groups), blocks(ref, n_inst, groups))
+
+
+def torch_block_err(x, gamma, beta, n_inst, groups, eps, silu, ref):
+    """e_torch: the per-block error of torch.nn.functional.group_norm in fp32 on the CPU (the class the project is judged against)."""
+    M, C = x.shape
+    y = F.group_norm(x.float().view(n_inst, M // n_inst, C).permute(0, 2, 1).contiguous(), groups, gamma.float(), beta.float(), eps)
+    y = y.permute(0, 2, 1).reshape(M, C)
+    return block_err(F.silu(y) if silu else y, ref, n_inst, groups)
+
+
+# ---- the inputs ---------------------------------------------------------------------------------------------------------------------------
+def block_params(variant, n_inst, groups, dtype, seed):
+    """mu, sigma [n_inst, groups] (float64)."""
+    i, g = torch.arange(n_inst)[:, None], torch.arange(groups)[None, :]
+    sigma = torch.exp2((((g + 3 * i + seed) % 7) - 3).double())              # neighbours along i and along g differ
+    if variant == "offset":
+        return (32.0 if dtype == "f32" else 8.0) * sigma, sigma
+    nb = n_inst * groups
+    gen = torch.Generator().manual_seed(seed)
+    frac = torch.linspace(0.25, 1.0, nb, dtype=torch.float64)[torch.randperm(nb, generator=gen)].view(n_inst, groups)
+    sign = (1 - 2 * ((i + g) % 2)).double()
+    return sign * frac * 8.0 * sigma.clamp(max=1.0), sigma
+
+
+def row_scales(variant, rows):
+    s = torch.ones(rows, dtype=torch.float64)
+    if variant == "marked" and rows >= 3:
+        for k in range(32, rows, 32):
+            s[k - 1] = s[k] = 4.0
+        s[0] = s[-1] = math.sqrt(float((s[1:-1] ** 2).sum()) / 2.0)          # a quarter of the sum of squares each
+    return s
+
+
+def gn_input(variant, n_inst, rows, C, groups, dtype, seed):
+    """x [n_inst * rows, C] in float64, representable in `dtype`."""
+    assert variant in ("distinct", "marked", "offset")
+    mu, sigma = block_params(variant, n_inst, groups, dtype, seed)
+    gen = torch.Generator().manual_seed(seed + 1)
+    cpg = C // groups
+    z = torch.randn(n_inst, rows, groups, cpg, generator=gen, dtype=torch.float64) * row_scales(variant, rows)[None, :, None, None]
+    if variant == "marked" and rows >= 3 and cpg >= 2:
+        # exactly: the first and the last row sum to zero within a group and carry n / 4 of the block's sum of squares each, the rows between
+        # them n / 2 around a zero mean — block mean 0, variance 1
+        n = rows * cpg
+        for r in (0, rows - 1):
+            e = z[:, r] - z[:, r].mean(dim=-1, keepdim=True)
+            z[:, r] = e * torch.sqrt(n / 4.0 / (e * e).sum(dim=-1, keepdim=True))
+        mid = z[:, 1:-1] - z[:, 1:-1].mean(dim=(1, 3), keepdim=True)
+        z[:, 1:-1] = mid * torch.sqrt(n / 2.0 / (mid * mid).sum(dim=(1, 3), keepdim=True))
+    elif rows * cpg >= 2:
+        z = (z - z.mean(dim=(1, 3), keepdim=True)) / z.std(dim=(1, 3), unbiased=False, keepdim=True)
+    x = mu[:, None, :, None] + sigma[:, None, :, None] * z
+    return x.reshape(n_inst * rows, C).to(TD[dtype]).double()
+
+
+def ln_input(variant, M, C, seed):
+    """Rows for a LayerNorm (fp32 input): mu / sigma per row."""
+    return gn_input(variant, M, 1, C, 1, "f32", seed)
+
+
+def affine(C, seed):
+    g = torch.Generator().manual_seed(seed + 2)
+    return 1 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+
+
+# ---- mirrors of the launchers' chunking (csrc/norm.hip coop_chunking, program.Program.groupnorm) -----------------------------------------
+GNC_THREADS = 512
+COOP_KRS = (4, 8, 12, 16, 20)
+SPLITK_KRS = (1, 2, 4, 8, 12, 16, 20)
+
+
+def coop_chunking(rows, n_inst, cv, ncu, max_chunk, kr_list):
+    """-> (kr, rc, nchunk): the first kr whose grid of n_inst * nchunk workgroups is at most one per CU, nchunk <= max_chunk; (0, 0, 0)."""
+    for kr in kr_list:
+        rc = (GNC_THREADS // cv) * kr
+        nchunk = -(-rows // rc)
+        if n_inst * nchunk <= ncu and nchunk <= max_chunk:
+            return kr, rc, nchunk
+    return 0, 0, 0
+
+
+def stats_blocks(rows, n_inst, target_cus=256):
+    """nblk of Program.groupnorm: the rows per statistics workgroup double from 4 until the grid is within 4 workgroups per CU."""
+    rpb = 4
+    while n_inst * -(-rows // rpb) > 4 * target_cus:
+        rpb *= 2
+    return -(-rows // rpb)
+
+
+def rows_for_kr(target, n_inst, C, ncu, kr_list, standalone):
+    """The smallest row count at which the launcher picks `target` rows per thread (every smaller kr overflows the device), plus 5."""
+    cv = C // 8
+    pick = lambda r: coop_chunking(r, n_inst, cv, ncu, stats_blocks(r, n_inst) if standalone else 1 << 30, kr_list)[0]
+    rows = 1
+    while pick(rows) != target:
+        rows += 1
+        assert rows < 1 << 16, (target, n_inst, C, ncu)
+    assert pick(rows + 5) == target
+    return rows + 5
+
+
+# ---- programs -----------------------------------------------------------------------------------------------------------------------------
+class Built:
+    """A case's program, weights, initial arena contents, fences and expectations."""
+
+    def __init__(self, case):
+        self.case = case
+        self.P = Program()
+        self.w = {}
+        self.fences = []        # (allocation, r0, r1, c1): rows r0 .. r1 - 1 x columns 0 .. c1 - 1 are the window, the rest stays NaN
+        self.sets = []          # (window, tensor) written before the run
+        self.outs = []          # dict(name, hi, lo, ref, n_inst, groups, tol): norm outputs
+        self.exact = []         # (name, window, expected tensor): bit-equal
+        self.probs = []         # dict(X, gamma, beta, n_inst, groups, silu, tol, parts): the norm problems, for the CPU proofs
+        self.path = ""          # what the op records were asserted to say
+        self.kr = None
+
+    def fenced(self, rows, cols, dtype, window=None):
+        assert cols % 8 == 0
+        big = self.P.alloc(rows + 2 * PAD_ROWS, cols + PAD_COLS, dtype)
+        r0, r1 = (0, rows) if window is None else window
+        self.fences.append((big, PAD_ROWS + r0, PAD_ROWS + r1, cols))
+        return big.row_slice(PAD_ROWS, PAD_ROWS + rows).col_slice(0, cols)
+
+    def put(self, win, t):
+        assert (win.rows, win.cols) == tuple(t.shape), (win.rows, win.cols, t.shape)
+        self.sets.append((win, t))
+
+    def weight(self, name, t):
+        self.w[name] = t
+        return Ref("weight", 0, name)
+
+    def init(self, it):
+        for big, _, _, _ in self.fences:
+            it.mat(big.ref, big.rows, big.ld, big.ld, TD[big.dtype], {}).fill_(NAN)
+        for win, t in self.sets:
+            it.mat(win.ref, win.rows, win.cols, win.ld, TD[win.dtype], {}).copy_(t.to(TD[win.dtype]))
+
+    def hilo_tol(self, lo, X, gamma, beta, n_inst, groups, silu, full):
+        """Per-block bound of hi + lo (None without a low-order output) and, on `offset` rows, the worst e_torch behind it."""
+        if not lo:
+            return None, None
+        tol = torch.full((n_inst, groups), TOL_HILO, dtype=torch.float64)
+        if self.case["variant"] != "offset":
+            return tol, None
+        et = torch_block_err(X, gamma, beta, n_inst, groups, EPS, silu, full)      # another fp32 summation order (up to 20 rows per lane): 4 x
+        return torch.maximum(tol, 4.0 * et), float(et.max())
+
+    def expect(self, name, hi, lo, X, gamma, beta, n_inst, groups, silu, parts=None):
+        """Register a norm output (window `hi`, low-order window `lo` or None) of input X."""
+        full = groupnorm_ref(X, gamma, beta, n_inst, groups, EPS, silu)
+        tol, et = self.hilo_tol(lo is not None, X, gamma, beta, n_inst, groups, silu, full)
+        self.outs.append(dict(name=name, hi=hi, lo=lo, ref=full, n_inst=n_inst, groups=groups, tol=tol, e_torch=et))
+        self.probs.append(dict(name=name, X=X, gamma=gamma, beta=beta, n_inst=n_inst, groups=groups, silu=silu,
+                               tol=TOL_F16 if lo is None else TOL_HILO, parts=parts))
+
+
+def _rd(it, win):
+    return it.mat(win.ref, win.rows, win.cols, win.ld, TD[win.dtype], {}).clone()
+
+
+def verify(it, b):
+    """Fences, bit-equal side outputs and per-block errors of a finished run; -> dict(hi, hilo, e_torch): maxima over blocks and outputs."""
+    tag = b.case["id"]
+    for big, r0, r1, c1 in b.fences:
+        full = it.mat(big.ref, big.rows, big.ld, big.ld, TD[big.dtype], {}).clone()
+        assert torch.isfinite(full[r0:r1, :c1]).all(), f"{tag}: non-finite values inside a window"
+        full[r0:r1, :c1] = NAN
+        assert torch.isnan(full).all(), f"{tag}: {int((~torch.isnan(full)).sum())} fence elements written"
+    for name, win, want in b.exact:
+        assert torch.equal(_rd(it, win), want.to(TD[win.dtype])), f"{tag}: {name} is not bit-equal"
+    figs = dict(hi=0.0, hilo=None, e_torch=None)
+    for o in b.outs:
+        hi = _rd(it, o["hi"]).double()
+        assert hi.shape == o["ref"].shape, (tag, o["name"], hi.shape, o["ref"].shape)
+        e = block_err(hi, o["ref"], o["n_inst"], o["groups"])
+        figs["hi"] = max(figs["hi"], float(e.max()))
+        assert float(e.max()) < TOL_F16, (tag, o["name"], "hi", float(e.max()))
+        if o["lo"] is not None:
+            e2 = block_err(hi + _rd(it, o["lo"]).double(), o["ref"], o["n_inst"], o["groups"])
+            figs["hilo"] = max(figs["hilo"] or 0.0, float(e2.max()))
+            if o["e_torch"] is not None:
+                figs["e_torch"] = max(figs["e_torch"] or 0.0, o["e_torch"])
+            assert bool((e2 < o["tol"]).all()), (tag, o["name"], "hi+lo", float(e2.max()), float(o["tol"].max()))
+            assert float(e2.max()) < float(e.max()), (tag, o["name"], "hi + lo is no closer than hi", float(e2.max()), float(e.max()))
+    return figs
+
+
+def figures_line(b, figs):
+    f = lambda v: "-" if v is None else f"{v:.2e}"
+    return f"NORMADV {b.case['id']}: path [{b.path}] KR {b.kr if b.kr else '-'} hi {f(figs['hi'])} hi+lo {f(figs['hilo'])} e_torch {f(figs['e_torch'])}"
+
+
+# -- stand-alone OP_GROUPNORM ---------------------------------------------------------------------------------------------------------------
+def _gn_case(form, n_inst, rows, C, dt, variant, **kw):
+    c = dict(family="gn", id=f"gn-{form}-{n_inst}x{rows}x{C}-{dt}-{variant}", form=form, n_inst=n_inst, rows=rows, C=C, dt=dt, variant=variant,
+             barrier=False, kr=None, seed=100 + n_inst + rows + C)
+    c.update(kw)
+    return c
+
+
+def _build_gn(c, ncu):
+    b = Built(c)
+    P, form, n_inst, C, dt = b.P, c["form"], c["n_inst"], c["C"], c["dt"]
+    rows = c["rows"] if c["kr"] is None else rows_for_kr(c["kr"], n_inst, C, ncu, COOP_KRS, True)
+    P.gn_coop = form == "cooperative"
+    P.gn_fused_slice_bytes = 1 << 30 if form == "single_launch" else 0
+    P.gn_fused_total_bytes = 1 << 30
+    M = n_inst * rows
+    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, dt, c["seed"])
+    gamma, beta = affine(C, c["seed"])
+    g, be = b.weight("g", gamma), b.weight("be", beta)
+    x = b.fenced(M, C, dt)
+    b.put(x, X)
+    # every buffer before the first op: an op's scratch is freed when it is emitted, a later allocation would land on it
+    combos = [(True, "lo")] if c["kr"] is not None else [(True, "lo"), (False, "lo"), (True, "cast"), (False, "cast")]
+    bufs = []
+    for silu, second in combos:
+        if second == "lo":
+            bufs.append((b.fenced(M, 2 * C, "f16"), None))
+        else:
+            bufs.append((b.fenced(M, C, "f16"), b.fenced(M, 2 * C, "f16")))
+    for (silu, second), (out, cast) in zip(combos, bufs):
+        name = f"{'silu' if silu else 'plain'}-{second}"
+        if second == "lo":
+            op = P.groupnorm(name, x, g, be, out.col_slice(0, C), n_inst=n_inst, eps=EPS, silu=silu, lo=True)
+            b.expect(name, out.col_slice(0, C), out.col_slice(C, 2 * C), X, gamma, beta, n_inst, GROUPS, silu)
+            assert op.i[16] == 1 and op.p[8].space == "null"
+        else:
+            op = P.groupnorm(name, x, g, be, out, n_inst=n_inst, eps=EPS, silu=silu, cast=cast, cast_lo=True)
+            b.expect(name, out, None, X, gamma, beta, n_inst, GROUPS, silu)
+            hi = X.half()
+            b.exact.append((name + " cast", cast.col_slice(0, C), hi))
+            b.exact.append((name + " cast lo", cast.col_slice(C, 2 * C), (X.float() - hi.float()).half()))
+            assert op.i[16] == 0 and op.p[8].space == "arena" and op.i[20] == C
+        assert op.kind == L.OP_GROUPNORM and op.i[8] == 0 and op.i[12] == (form == "single_launch") and op.i[15] == (form == "cooperative")
+        if form == "cooperative":
+            assert op.p[7].space == "arena" and op.i[18] > 0            # tagged records in the program's exchange region
+            if c["barrier"]:
+                op.p[7], op.i[18] = NULL, 0                              # grid-barrier mode: partials in the op's own scratch
+        if c["kr"] is not None:
+            nblk = -(-rows // op.i[11])
+            kr, rc, nchunk = coop_chunking(rows, n_inst, C // 8, ncu, nblk, COOP_KRS)
+            assert kr == c["kr"] and rows % rc != 0, (kr, rows, rc)
+            b.kr = kr
+    assert len(P.ops) == len(combos)
+    b.path = f"OP_GROUPNORM i[8]=0 i[12]={int(form == 'single_launch')} i[15]={int(form == 'cooperative')}" + \
+             (" barrier" if c["barrier"] else " records" if form == "cooperative" else "") + f" rows={rows}"
+    return b
+
+
+# -- the GEMM in front of a fused / strip-fed norm: an identity weight, so that its result IS the designed tensor ----------------------------
+def _identity_gemm(b, name, kind, X, out_dt, *, geo=None, k_extra=0, res=True, **kw):
+    """out [M, C] = X exactly: A = fp16(X), W = identity (on the centre tap of a convolution; `k_extra` more operand columns meet zero
+    weights), and — fp32 results — a residual that carries X - fp16(X).  Returns (op, y window)."""
+    P = b.P
+    M, C = X.shape
+    hi = X.half()
+    eye = torch.eye(C)
+    if kind == "conv":
+        w4 = torch.zeros(C, C, 3, 3)
+        w4[:, :, 1, 1] = eye
+        W, K, gather, conv = pk.conv3x3(w4).half(), 9 * C, L.GATHER_CONV3X3, dict(Hin=geo[1], Win=geo[2], Cin=C, stride=1, up=0, Hout=geo[1], Wout=geo[2])
+    elif kind == "tconv":
+        w5 = torch.zeros(C, C, 3, 1, 1)
+        w5[:, :, 1, 0, 0] = eye
+        W, K, gather, conv = pk.tconv3(w5).half(), 3 * C, L.GATHER_TCONV3, dict(F=geo[0], HW=geo[1] * geo[2], Cin=C)
+    else:
+        W, K, gather, conv = torch.cat([eye, torch.zeros(C, k_extra)], dim=1).half(), C + k_extra, L.GATHER_PLAIN, None
+    a = P.alloc(M, C + k_extra, "f16")
+    A = hi if not k_extra else torch.cat([hi, torch.randn(M, k_extra, generator=torch.Generator().manual_seed(7)).half()], dim=1)
+    b.put(a, A)
+    r = None
+    if out_dt == "f32" and res:
+        r = P.alloc(M, C, "f32")
+        b.put(r, X.float() - hi.float())
+    y = b.fenced(M, C, out_dt, window=(0, 0) if kw.pop("dead", False) else None)
+    op = P.gemm(name, a, b.weight(name + ".w", W), C, K, y, gather=gather, conv=conv, residual=r, **kw)
+    return op, y
+
+
+def _case(family, id, variant, **kw):
+    c = dict(family=family, id=f"{id}-{variant}", variant=variant)
+    c.update(kw)
+    return c
+
+
+# -- strips, phase 3 ---------------------------------------------------------------------------------------------------------------------
+def _build_strips(c, ncu):
+    b = Built(c)
+    n_inst, rows, C = c["n_inst"], c["rows"], c["C"]
+    M = n_inst * rows
+    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, "f32", c["seed"])
+    gamma, beta = affine(C, c["seed"])
+    # The strips are fp32 sums of x and x^2 over 32 rows (the ABI of T2V_EPI_STATS), so the single-pass variance they give carries at least
+    # 2^-24 (1 + (mean / std)^2) = 6e-5 at mean / std = 32, 3e-5 in the output, whatever the fold does: beyond the hi + lo figure by the
+    # number format alone.  The `offset` rows therefore run without a low-order output and are held to the fp16 figure.
+    lo = c["variant"] != "offset"
+    st = b.P.alloc(M // 32, 2 * C, "f32")
+    out = b.fenced(M, 2 * C if lo else C, "f16")
+    gop, y = _identity_gemm(b, "l", "plain", X, "f32", stats=st, allow_splitk=False)
+    assert gop.i[16] == L.EPI_STATS and gop.meta["stats"] == 1 and gop.meta["split"] == 1
+    b.exact.append(("stored x", y, X.float()))
+    op = b.P.groupnorm("gn", y, b.weight("g", gamma), b.weight("be", beta), out.col_slice(0, C), n_inst=n_inst, eps=EPS, silu=True, lo=lo, stats=st)
+    wide = rows // 32 * (C // GROUPS) > 1024
+    assert op.i[8] == 3 and op.p[6].space == "arena" and op.i[17] == C and wide == c["wide"] and len(b.P.ops) == 2
+    b.expect("gn", out.col_slice(0, C), out.col_slice(C, 2 * C) if lo else None, X, gamma, beta, n_inst, GROUPS, True)
+    b.path = f"OP_GROUPNORM i[8]=3 behind EPI_STATS, {'workgroup' if wide else 'wave'} fold"
+    return b
+
+
+# -- sharded phases 1 / 2 ----------------------------------------------------------------------------------------------------------------
+def _build_shard(c, ncu):
+    b = Built(c)
+    P, C, fr, size, total, dt = b.P, c["C"], c["frame_rows"], c["size"], c["frames"], c["dt"]
+    P.target_cus = 1          # several statistics workgroups per part
+    specs = [TShardSpec.make(total, size, q) for q in range(size)]
+    prow = [s.frames * fr for s in specs]
+    assert len(set(prow)) > 1, "the slices must be uneven"
+    Xp = [gn_input(c["variant"], 1, prow[q], C, GROUPS, dt, c["seed"] + 10 * q) for q in range(size)]      # own mu / sigma per part
+    X = torch.cat(Xp)
+    if c["variant"] == "marked":
+        # the clip's first and last row against the CLIP's statistics (the parts' own marks weigh little once the parts' means differ)
+        xv = X.view(sum(prow), GROUPS, C // GROUPS).clone()
+        m = xv.mean(dim=(0, 2), keepdim=True)
+        d = xv - m
+        others = (d[1:-1] ** 2).sum(dim=(0, 2))
+        for r in (0, -1):
+            xv[r] = m[0] + d[r] * torch.sqrt(others / 2.0 / (d[r] ** 2).sum(-1))[:, None]
+        X = xv.reshape(sum(prow), C).to(TD[dt]).double()
+        Xp = list(X.split(prow))
+    gamma, beta = affine(C, c["seed"])
+    g, be = b.weight("g", gamma), b.weight("be", beta)
+    halo, strips, lo = c["halo"], c["strips"], not c["halo"]
+    xs, outs, sts, raws = [], [], [], []
+    off = 0
+    for q in range(size):
+        before, after = (fr if q > 0 else 0, fr if q + 1 < size else 0) if halo else (0, 0)
+        if strips:
+            sts.append(P.alloc(prow[q] // 32, 2 * C, "f32"))
+            outs.append(b.fenced(prow[q], 2 * C, "f16"))
+            gop, y = _identity_gemm(b, f"l{q}", "plain", Xp[q], "f32", stats=sts[q], allow_splitk=False)
+            assert gop.i[16] == L.EPI_STATS
+            xs.append(y)
+        elif halo:
+            raw = b.fenced(prow[q] + 2 * fr, C, dt, window=(fr - before, fr + prow[q] + after))
+            raws.append(raw)
+            b.put(raw.row_slice(fr - before, fr + prow[q] + after), X[off - before: off + prow[q] + after])
+            xs.append(raw.row_slice(fr, fr + prow[q]))
+            outs.append(b.fenced(prow[q] + 2 * fr, C, "f16", window=(fr - before, fr + prow[q] + after)))
+        else:
+            xs.append(b.fenced(prow[q], C, dt))
+            b.put(xs[q], Xp[q])
+            outs.append(b.fenced(prow[q], 2 * C, "f16"))
+        off += prow[q]
+    for q in range(size):
+        o = outs[q].row_slice(fr, fr + prow[q]) if halo else outs[q].col_slice(0, C)
+        P.groupnorm(f"p{q}", xs[q], g, be, o, n_inst=1, eps=EPS, silu=True, shard=specs[q], lo=lo, stats=sts[q] if strips else None,
+                    halo_raw=raws[q] if halo else None)
+    gn = [op for op in P.ops if op.kind == L.OP_GROUPNORM]          # p0.stats, p0.apply, p1.stats, ...
+    assert len(gn) == 2 * size
+    scratch = gn[2 * max(range(size), key=lambda q: prow[q])].p[4]      # one scratch for all parts: the longest part's
+    for op in gn:
+        op.p[4] = scratch
+    st_ops, ap_ops = gn[0::2], gn[1::2]
+    off = 0
+    for q in range(size):
+        before, after = (fr if q > 0 else 0, fr if q + 1 < size else 0) if halo else (0, 0)
+        assert st_ops[q].i[8] == 1 and ap_ops[q].i[8] == 2 and st_ops[q].i[9] == size and st_ops[q].i[10] == q and ap_ops[q].i[14] == sum(prow)
+        assert (st_ops[q].p[6].space == "arena") == strips and (ap_ops[q].i[21], ap_ops[q].i[22]) == (before, after)
+        sl = slice(off - before, off + prow[q] + after)
+        hi = outs[q].row_slice(fr - before, fr + prow[q] + after) if halo else outs[q].col_slice(0, C)
+        full = groupnorm_ref(X, gamma, beta, 1, GROUPS, EPS, True)
+        tol, et = b.hilo_tol(lo, X, gamma, beta, 1, GROUPS, True, full)
+        b.outs.append(dict(name=f"p{q}", hi=hi, lo=outs[q].col_slice(C, 2 * C) if lo else None, ref=full[sl], n_inst=1, groups=GROUPS, tol=tol, e_torch=et))
+        off += prow[q]
+    b.probs.append(dict(name="clip", X=X, gamma=gamma, beta=beta, n_inst=1, groups=GROUPS, silu=True, tol=TOL_HILO if lo else TOL_F16, parts=prow))
+    gemms = [op for op in P.ops if op.kind == L.OP_GEMM]
+    P.ops = gemms + st_ops + ap_ops                                   # the collectives are the test's: one scratch, every part's slot filled
+    b.path = f"OP_GROUPNORM i[8]=1 x{size} then i[8]=2 x{size}" + (" strips (p[6])" if strips else "") + (" halo i[21]/i[22]" if halo else "")
+    return b
+
+
+# -- T2V_EPI_GN ----------------------------------------------------------------------------------------------------------------------------
+_EPI_BM = {8: 192, 11: 128, 3: 128, 5: 128, 0: 128}
+
+
+def _build_epi(c, ncu):
+    b = Built(c)
+    P, kind, tile, C, dead, lo = b.P, c["kind"], c["tile"], c["C"], c["dead"], c["lo"]
+    B, Fr, H, W = c["geo"]
+    M = B * Fr * H * W
+    n_inst = B * Fr if c["per_frame"] else B
+    rows = M // n_inst
+    P.force_tile = tile
+    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, "f16" if dead else "f32", c["seed"])
+    gamma, beta = affine(C, c["seed"])
+    full = b.fenced(M, 2 * C if lo else C, "f16")
+    op, y = _identity_gemm(b, "g", kind, X, "f16" if dead else "f32", geo=(Fr, H, W), allow_splitk=False, dead=dead)
+    assert op.meta["tile"] == tile and op.meta["split"] == 1
+    out = full.col_slice(0, C)
+    fused = P.groupnorm("gn", y, b.weight("g", gamma), b.weight("be", beta), out, n_inst=n_inst, eps=EPS, silu=True, lo=lo,
+                        gb=b.weight("gb", torch.cat([gamma, beta])), x_dead=dead)
+    assert fused is op and op.i[16] == L.EPI_GN and len(P.ops) == 1, "the norm did not become the GEMM's epilogue"
+    assert (op.i[24], op.i[27], op.i[28], op.i[29], op.i[22]) == (rows, int(lo), GROUPS, int(dead), tile)
+    bm = _EPI_BM[tile]
+    assert c["seam"] == ("half" if 2 * rows == bm else "whole" if rows % bm == 0 else "straddle")
+    if not dead:
+        b.exact.append(("stored x", y, X.float()))
+    b.expect("gn", out, full.col_slice(C, 2 * C) if lo else None, X, gamma, beta, n_inst, GROUPS, True)
+    b.path = f"EPI_GN tile {tile} {kind} rows={rows} ({c['seam']}) dead={int(dead)} lo={int(lo)}"
+    return b
+
+
+# -- splitk_gn_kernel ------------------------------------------------------------------------------------------------------------------------
+def _build_splitk(c, ncu):
+    b = Built(c)
+    P, C, n_inst, dead, lo = b.P, c["C"], c["n_inst"], c["dead"], c["lo"]
+    # KR = 1 is the list's first entry: any short instance runs it (101 rows); otherwise the smallest count + 5, and one row more where
+    # that is a whole number of chunks (the last chunk must be ragged)
+    rows = 101 if c["kr"] == SPLITK_KRS[0] else rows_for_kr(c["kr"], n_inst, C, ncu, SPLITK_KRS, False)
+    if rows % coop_chunking(rows, n_inst, C // 8, ncu, 1 << 30, SPLITK_KRS)[1] == 0:
+        rows += 1
+    M = n_inst * rows
+    P.force_tile = 5
+    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, "f16" if dead else "f32", c["seed"])
+    gamma, beta = affine(C, c["seed"])
+    full = b.fenced(M, 2 * C if lo else C, "f16")
+    op, y = _identity_gemm(b, "g", "plain", X, "f16" if dead else "f32", k_extra=2048 - C, dead=dead)
+    assert op.meta["split"] > 1, op.meta
+    out = full.col_slice(0, C)
+    fused = P.groupnorm("gn", y, b.weight("g", gamma), b.weight("be", beta), out, n_inst=n_inst, eps=EPS, silu=True, lo=lo,
+                        gb=b.weight("gb", torch.cat([gamma, beta])), x_dead=dead)
+    assert fused is op and op.i[16] == L.EPI_GN and op.meta["split"] > 1 and len(P.ops) == 1
+    kr, rc, nchunk = coop_chunking(rows, n_inst, C // 8, ncu, 1 << 30, SPLITK_KRS)
+    assert kr == c["kr"] and rows % rc != 0
+    b.kr = kr
+    if not dead:
+        b.exact.append(("stored x", y, X.float()))
+    b.expect("gn", out, full.col_slice(C, 2 * C) if lo else None, X, gamma, beta, n_inst, GROUPS, True)
+    b.path = f"EPI_GN split={op.meta['split']} rows={rows} dead={int(dead)} lo={int(lo)}"
+    return b
+
+
+# -- LayerNorm ---------------------------------------------------------------------------------------------------------------------------
+def _build_ln(c, ncu):
+    b = Built(c)
+    M, C = c["M"], c["C"]
+    X = ln_input(c["variant"], M, C, c["seed"])
+    gamma, beta = affine(C, c["seed"])
+    x, out = b.fenced(M, C, "f32"), b.fenced(M, C, "f16")
+    b.put(x, X)
+    op = b.P.layernorm("ln", x, b.weight("g", gamma), b.weight("be", beta), out, EPS)
+    op.i[4] = c["cap"]
+    assert op.kind == L.OP_LAYERNORM and (op.i[0], op.i[1]) == (M, C) and (c["cap"] == 0 or -(-M // 4) > c["cap"])
+    b.expect("ln", out, None, X, gamma, beta, M, 1, False)
+    b.path = f"OP_LAYERNORM C={C} i[4]={c['cap']}" + (" grid-stride" if c["cap"] else "")
+    return b
+
+
+def _build_lnfused(c, ncu):
+    b = Built(c)
+    M, N, tile = c["M"], c["N"], c["tile"]
+    b.P.force_tile = tile
+    X = ln_input(c["variant"], M, N, c["seed"])
+    gamma, beta = affine(N, c["seed"])
+    ln_out = b.fenced(M, N, "f16")
+    op, y = _identity_gemm(b, "g", "plain", X, "f32", allow_splitk=False,
+                           ln=(b.weight("gb", torch.cat([gamma, beta])), b.weight("g", gamma), b.weight("be", beta), ln_out, EPS))
+    assert op.i[22] == tile and op.i[8] == c["mode"] and len(b.P.ops) == 1, "the LayerNorm did not become the GEMM's epilogue"
+    b.exact.append(("stored x", y, X.float()))
+    b.expect("ln", ln_out, None, X, gamma, beta, M, 1, False)
+    b.path = f"GEMM tile {tile} i[8]={c['mode']} ({'across column tiles' if c['mode'] == 2 else 'whole rows'}) N={N}"
+    return b
+
+
+_BUILDERS = dict(gn=_build_gn, strips=_build_strips, shard=_build_shard, epi=_build_epi, splitk=_build_splitk, ln=_build_ln, lnfused=_build_lnfused)
+
+
+def build(case, ncu=None):
+    """The program of a case.  ncu: the device's CU count (the chunking of the cooperative kernels depends on it); None: the lowering's own
+    figure (256 without a device)."""
+    return _BUILDERS[case["family"]](case, Program.device_cus() if ncu is None else ncu)
+
+
+# ---- the case list --------------------------------------------------------------------------------------------------------------------------
+VARIANTS = ("distinct", "marked", "offset")
+CASES = []
+# stand-alone GroupNorm: C = 2560 takes the column loop of gn_stats_kernel (cv > 256) and R = 1 in the cooperative tile; rows = 1: one row
+# per instance.  The single-launch kernel needs C / groups % 4 == 0: it has no C = 320 form (the launcher refuses the record).
+for _form in ("three_launch", "cooperative", "single_launch"):
+    for _n, _r, _C, _dt in ((3, 101, 320, "f32"), (2, 37, 2560, "f16"), (5, 1, 128, "f32")):
+        if _form == "single_launch" and (_C // GROUPS) % 4:
+            continue
+        # (5, 1, 128) has blocks of 4 values: their squares, rounded to fp32, leave the single-pass variance up to 2^-24 (1 + 32^2) = 6e-5 off
+        # at mean / std = 32 — 3e-5 in the output whatever the summation order, beyond the hi + lo figure by the number format alone (torch's
+        # fp32 group_norm does not form x^2 - mean^2, so e_torch does not pay it): no `offset` rows on that shape
+        CASES += [_gn_case(_form, _n, _r, _C, _dt, v) for v in VARIANTS if not (v == "offset" and _r * (_C // GROUPS) < 32)]
+CASES.append(_gn_case("cooperative", 3, 101, 320, "f32", "marked", barrier=True, id="gn-cooperative-barrier-3x101x320-f32-marked"))
+# gn_coop_kernel at every rows-per-thread count: the row count depends on the device (rows_for_kr), ~2054 at KR = 20 on 256 CUs
+CASES += [_gn_case("cooperative", 2, 0, 2560, "f32", "marked", kr=kr, id=f"gn-coop-KR{kr}-2x2560-marked") for kr in COOP_KRS]
+for _v in VARIANTS:
+    CASES.append(_case("strips", "strips-wave-3x96x320", _v, n_inst=3, rows=96, C=320, wide=False, seed=301))
+    CASES.append(_case("strips", "strips-wg-2x832x1280", _v, n_inst=2, rows=832, C=1280, wide=True, seed=302))
+    CASES.append(_case("shard", "shard-2parts-48+24", _v, C=320, frame_rows=24, frames=3, size=2, dt="f32", halo=False, strips=False, seed=311))
+    CASES.append(_case("shard", "shard-3parts-40+40+20", _v, C=320, frame_rows=20, frames=5, size=3, dt="f16", halo=False, strips=False, seed=312))
+    CASES.append(_case("shard", "shard-3parts-strips-64+64+32", _v, C=320, frame_rows=32, frames=5, size=3, dt="f32", halo=False, strips=True, seed=313))
+    CASES.append(_case("shard", "shard-2parts-halo-48+24", _v, C=320, frame_rows=24, frames=3, size=2, dt="f32", halo=True, strips=False, seed=314))
+# T2V_EPI_GN: 256-row frames (B, F, H, W = 2, 3, 16, 16): per frame they straddle the 192-row tiles and are two 128-row tiles, per clip
+# (768 rows) a whole number of either; 64- / 96-row frames are half a tile
+# The epilogue folds 32-row column sums of x and x^2 in fp32 (as the strips): `offset` rows go to the cases without a low-order output, for
+# the reason given in _build_strips
+_EPI_KTC = [("conv", 8, 320), ("tconv", 8, 320), ("plain", 8, 320), ("tconv", 11, 320), ("plain", 11, 320), ("tconv", 0, 640), ("conv", 0, 640),
+            ("plain", 0, 640), ("tconv", 5, 640), ("plain", 5, 1280), ("conv", 3, 640), ("plain", 3, 640)]
+_EPI_MODES = [(True, True, False), (False, False, True), (False, True, False), (True, False, False)]      # per_frame, dead, lo
+_n = 0
+for _kind, _tile, _C in _EPI_KTC:
+    for _pf, _dead, _lo in _EPI_MODES:
+        _seam = "whole" if (not _pf or _EPI_BM[_tile] == 128) else "straddle"
+        CASES.append(_case("epi", f"epi-{_kind}-t{_tile}-C{_C}-{'frame' if _pf else 'clip'}-{_seam}{'-dead' if _dead else ''}{'-lo' if _lo else ''}",
+                           VARIANTS[_n % (2 if _lo else 3)], kind=_kind, tile=_tile, C=_C, per_frame=_pf, dead=_dead, lo=_lo, geo=(2, 3, 16, 16), seam=_seam,
+                           seed=400 + _n))
+        _n += 1
+for _kind, _tile, _C, _geo in (("plain", 0, 640, (2, 3, 8, 8)), ("conv", 3, 640, (2, 3, 8, 8)), ("tconv", 5, 640, (2, 3, 8, 8)),
+                               ("plain", 11, 320, (2, 3, 8, 8)), ("conv", 8, 320, (2, 3, 8, 12)), ("tconv", 8, 320, (2, 3, 8, 12))):
+    _dead, _lo = _n % 2 == 0, _n % 2 == 1
+    CASES.append(_case("epi", f"epi-{_kind}-t{_tile}-C{_C}-frame-half{'-dead' if _dead else '-lo'}", VARIANTS[_n % (2 if _lo else 3)], kind=_kind, tile=_tile, C=_C,
+                       per_frame=True, dead=_dead, lo=_lo, geo=_geo, seam="half", seed=400 + _n))
+    _n += 1
+# splitk_gn_kernel: two rows-per-thread counts per width
+for _C, _kr, _dead, _v in ((640, 1, True, "marked"), (640, 2, False, "distinct"), (1280, 1, False, "offset"), (1280, 2, True, "marked"),
+                           (640, 2, False, "offset"), (1280, 2, False, "marked")):
+    CASES.append(_case("splitk", f"splitk-C{_C}-KR{_kr}{'-dead' if _dead else '-lo'}", _v, C=_C, n_inst=2, kr=_kr, dead=_dead, lo=not _dead, seed=500 + _C + _kr))
+# LayerNorm: one width per instantiation (rows kernel <2>, <3>, wide kernel <5>, <8>), ragged against the 4 rows of a workgroup
+for _v in ("distinct", "offset"):
+    for _C in (320, 768, 1280, 2048):
+        for _M in (77, 513):
+            CASES.append(_case("ln", f"ln-{_M}x{_C}", _v, M=_M, C=_C, cap=0, seed=600 + _C + _M))
+    CASES.append(_case("ln", "ln-77x320-cap2", _v, M=77, C=320, cap=2, seed=601))
+    for _tile in (8, 11, 2):
+        CASES.append(_case("lnfused", f"lnfused-t{_tile}-397x320", _v, M=397, N=320, tile=_tile, mode=1, seed=610 + _tile))
+    for _tile, _N in ((0, 640), (3, 768), (5, 1280), (9, 512), (12, 1280)):
+        CASES.append(_case("lnfused", f"lnx-t{_tile}-397x{_N}", _v, M=397, N=_N, tile=_tile, mode=2, seed=620 + _tile))
+assert len({c["id"] for c in CASES}) == len(CASES)
