@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import os
 from functools import partial
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -31,7 +31,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import packing as pk
-from .program import COLLECTIVE_KINDS, BoundProgram, Buf, Program, Ref, TShardSpec
+from .lowering import _UNetLowering
+from .program import COLLECTIVE_KINDS, BoundProgram, Buf, Program, Ref
 
 
 # ------------------------------------------------------------------------------------------
@@ -596,197 +597,24 @@ class _Compiled:
 # ------------------------------------------------------------------------------------------
 # lowering: network + geometry -> denoise program
 # ------------------------------------------------------------------------------------------
-class _Lowering:
-    def __init__(self, net: UNetSD, B, F, H, W, Lctx, x_dt, out_dt, ctx_dt, keep_taps=False, shard=None, x_batch=0):
-        """F = frames held by THIS rank.  shard = TShardSpec: the clip's frames are split contiguously over the ranks
-        of a T group (slices of ceil(F_total / R) frames, a shorter last one); temporal ops then exchange data
-        (SURVEY §5.7): cross-frame GroupNorm -> all-gather of statistics partials, temporal conv -> +-1 frame halo,
-        temporal attention -> all-gather of K/V.  Everything else is frame-local."""
-        self.shard: Optional[TShardSpec] = shard if (shard is not None and shard.size > 1) else None
-        if self.shard is not None:
-            assert B == 1, "T-sharded forwards run one sample per rank (the CFG pair is split over ranks)"
-            assert F == self.shard.frames
-        self.net, self.B, self.F, self.H, self.W, self.Lctx = net, B, F, H, W, Lctx
-        # cond | uncond prefix sharing (UNetSD.share_cfg_prefix): while `sharing`, activations hold Bc = 1 sample; the first spatial
-        # transformer's text cross-attention is where the two samples part (transformer_block) and Bc becomes B
-        # (`_share_now`: forward() sets it from `share_cfg_prefix` AND the single-timestep hint; a direct _compile keeps the attribute's value)
-        self.sharing = bool(getattr(net, "_share_now", False)) and B == 2 and x_batch == 1 and self.shard is None
-        self.Bc = 1 if self.sharing else B
-        self.x_dt, self.out_dt, self.ctx_dt = x_dt, out_dt, ctx_dt
-        self.x_batch = x_batch if 0 < x_batch < B else 0      # x holds fewer samples than the batch: sample b reads x[b % x_batch]
-        self.precise = bool(getattr(net, "precise_operands", False))
-        # round 4: the two next classes of the operand ranking (DESIGN.md "Precision") — GroupNorm -> proj_in and x4 -> proj_out.
-        # Their consumers are the C -> C linears (HBM-bound at the 32x32 level: a doubled K costs bytes, not MFMA time)
-        # Measured on MI355X (same box): every doubled C -> C linear costs ~12 us at every level (+1.04 ms per step for all 66), and the
-        # probe by level (tests/precision_probe.py ... levels) puts 9.7 of the 10 % / 10.7 of the 13 % of these two classes' gain at
-        # the INPUT resolution (its 11 + 11 sites) -> by default only the transformers of the top level are split; "all" = every level
-        level = getattr(net, "precise_operands", False)
-        self.precise_gn = self.precise and level != "r3"
-        self.precise_ff = self.precise and level != "r3"
-        self.precise_all_levels = level == "all"
-        self.precise_attn = self.precise and bool(getattr(net, "precise_attn_out", False))
-        self.precise_rs = self.precise and bool(getattr(net, "precise_resample", False))
-        # GroupNorm statistics from the producing GEMM's epilogue (ResBlock conv -> norm, the temporal-conv chain): opt-in (measured slower)
-        self.gn_strips = bool(getattr(net, "gn_producer_stats", False))
-        self.last_stats: Optional[Buf] = None
+class _Lowering(_UNetLowering):
+    def __init__(self, net: UNetSD, *args, **kwargs):
+        super().__init__(net, *args, **kwargs)
         self.fused_tattn = bool(getattr(net, "fused_temporal_attention", False))
-        self.stem_dup = False
-        self.P = Program(f"unet b{B} f{F} {H}x{W}")
-        self.P.keep_taps = keep_taps
-        self.P.small_rank_tiles = self.shard is not None       # (Program.choose_tile: no temporal convolution of a rank program carries a norm epilogue)
-        self.packer = pk.WeightPacker()
-        prefixes = tuple(getattr(net, "split_weight_prefixes", ()) or ())
-        if prefixes:
-            self.P.weight_lo = lambda ref: (Ref("weight", ref.off, self.packer.add_lo(ref.name))
-                                            if ref.name.startswith(prefixes) and ref.name.rsplit(":", 1)[-1] in ("lin", "lin2", "c3", "c3d", "t3", "qkv", "kv")
-                                            else None)
-        self.emb_slices: Dict[str, Tuple[int, int]] = {}
-        self.kv_slices: Dict[str, Tuple[int, int]] = {}
         # fused to_q + text cross-attention (T2V_EPI_XATTN, round 5): V^T of every site, [B][sum of inner][keys padded], step-invariant
         self.vt_all: Optional[Buf] = None
         self.vt_slices: Dict[str, int] = {}
 
     # -- packed-weight declarations ------------------------------------------------------------
-    def w_linear(self, key) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":lin", "f16", lambda sd, k=key: pk.pad_rows(pk.linear(sd[k + ".weight"]))))
-
-    def precise_at(self, flag: bool, h: int, w: int) -> bool:
-        """Is a round-4 operand split (flag) applied at the level whose frames are h x w?"""
-        return bool(flag) and (self.precise_all_levels or (h == self.H and w == self.W))
-
-    def w_proj(self, key, copies: int) -> Ref:
-        """Linear weights for an operand stored as `copies` column blocks (1: plain; 2: rows [hi | lo] -> [W | W])."""
-        assert copies in (1, 2)
-        return self.w_linear(key) if copies == 1 else self.w_linear_dup(key)
-
-    def w_linear_dup(self, key) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":lin2", "f16", lambda sd, k=key: pk.pad_rows(pk.linear_dup(sd[k + ".weight"]))))
-
-    def w_conv3_c8dup(self, key) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":c3d", "f16", lambda sd, k=key: pk.pad_rows(pk.conv3x3_c8_dup(sd[k + ".weight"]))))
-
-    def w_conv3(self, key, cin_pad=0) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":c3", "f16", lambda sd, k=key, c=cin_pad: pk.pad_rows(pk.conv3x3(sd[k + ".weight"], c))))
-
-    def w_conv3_hilo(self, key) -> Ref:
-        """3x3 conv weights for an operand of 2 Cin channels = [hi (Cin) | lo (Cin)]: [W | W] along the input channels."""
-        return Ref("weight", 0, self.packer.add(key + ":c3hl", "f16", lambda sd, k=key: pk.pad_rows(pk.conv3x3(torch.cat([sd[k + ".weight"]] * 2, dim=1)))))
-
     def w_tconv(self, key) -> Ref:
         return Ref("weight", 0, self.packer.add(key + ":t3", "f16", lambda sd, k=key: pk.tconv3(sd[k + ".weight"])))
-
-    def w_qkv(self, prefix) -> Ref:
-        def fn(sd, p=prefix):
-            return torch.cat([sd[p + ".to_q.weight"], sd[p + ".to_k.weight"], sd[p + ".to_v.weight"]], dim=0)
-        return Ref("weight", 0, self.packer.add(prefix + ":qkv", "f16", fn))
 
     def w_qkv_heads(self, prefix) -> Ref:
         def fn(sd, p=prefix):
             return pk.qkv_head_major(sd[p + ".to_q.weight"], sd[p + ".to_k.weight"], sd[p + ".to_v.weight"])
         return Ref("weight", 0, self.packer.add(prefix + ":qkvh", "f16", fn))
 
-    def w_kv(self, prefix) -> Ref:
-        def fn(sd, p=prefix):
-            return torch.cat([sd[p + ".to_k.weight"], sd[p + ".to_v.weight"]], dim=0)
-        return Ref("weight", 0, self.packer.add(prefix + ":kv", "f16", fn))
-
-    def w_geglu(self, key) -> Tuple[Ref, Ref]:
-        def wfn(sd, k=key):
-            w = sd[k + ".weight"]
-            return w[pk.geglu_perm(w.shape[0] // 2, w.device)]
-        def bfn(sd, k=key):
-            b = sd[k + ".bias"]
-            return b[pk.geglu_perm(b.shape[0] // 2, b.device)]
-        return (Ref("weight", 0, self.packer.add(key + ":geglu", "f16", wfn)),
-                Ref("weight", 0, self.packer.add(key + ":geglu_b", "f32", bfn)))
-
-    def ln_arg(self, key, out: Buf, eps: float = 1e-5) -> tuple:
-        """`ln=` argument of Program.gemm for the LayerNorm `key` applied to a GEMM's fp32 result: fused into the epilogue of the
-        192x320 tile (one fp32 [2C] vector gamma | beta), a separate LayerNorm op otherwise."""
-        gb = Ref("weight", 0, self.packer.add(key + ":ln_gb", "f32", lambda sd, k=key: torch.cat([sd[k + ".weight"], sd[k + ".bias"]])))
-        return (gb, self.vec(key + ".weight"), self.vec(key + ".bias"), out, eps)
-
-    def vec(self, key) -> Ref:
-        """fp32 vector (bias / norm affine), zero-padded to a multiple of 4."""
-        return Ref("weight", 0, self.packer.add(key + ":v", "f32", lambda sd, k=key: pk.pad_rows(sd[k])))
-
-    # -- geometry helpers ----------------------------------------------------------------------
-    def M(self, h, w):
-        """Token rows of an activation at h x w in the CURRENT batch (one sample while the cond | uncond prefix is shared)."""
-        return self.Bc * self.F * h * w
-
     # -- building blocks ------------------------------------------------------------------------
-    def gn_gb(self, key) -> Ref:
-        """gamma | beta of the GroupNorm `key` as ONE fp32 [2C] vector (the T2V_EPI_GN epilogue reads both from one pointer)."""
-        return Ref("weight", 0, self.packer.add(key + ":gn_gb", "f32", lambda sd, k=key: torch.cat([sd[k + ".weight"], sd[k + ".bias"]])))
-
-    def gn(self, name, x: Buf, key, *, per_frame: bool, eps, silu, out: Optional[Buf] = None, lo: bool = False,
-           stats: Optional[Buf] = None, x_dead: bool = False, cast: Optional[Buf] = None, cast_lo: bool = False,
-           halo_raw: Optional[Buf] = None) -> Buf:
-        """lo (precise_operands): the result is a [rows, 2C] buffer of rows [hi | lo] — fp16(y) and the low-order image of that
-        rounding — for a consumer GEMM with weights [W | W] (K = 2C)."""
-        if lo:
-            assert out is None
-            full = self.P.alloc(x.rows, 2 * x.cols, "f16")
-            out = full.col_slice(0, x.cols)
-        else:
-            full = out = self.P.alloc(x.rows, x.cols, "f16") if out is None else out
-        n_inst = self.Bc * self.F if per_frame else self.Bc
-        shard = None if per_frame else self.shard
-        if stats is not None and (x.rows // n_inst) % 32 != 0:
-            stats = None                  # (strips are 32 rows; a T-sharded cross-frame norm folds ITS part from them, round 6)
-        # (x produced by the op emitted last, on a tile with the instantiation: the norm becomes that GEMM's epilogue — Program._fuse_groupnorm;
-        #  x_dead: only this norm reads x)
-        self.P.groupnorm(name, x, self.vec(key + ".weight"), self.vec(key + ".bias"), out, n_inst=n_inst, eps=eps, silu=silu,
-                         shard=shard, lo=lo, stats=stats, gb=self.gn_gb(key) if shard is None and x.cols % 4 == 0 else None, x_dead=x_dead,
-                         cast=cast, cast_lo=cast_lo, halo_raw=halo_raw if shard is not None else None)
-        return full
-
-    def strips_for(self, rows: int, n: int, inst_rows: int, k: Optional[int] = None, gather: int = L.GATHER_PLAIN) -> Optional[Buf]:
-        """Buffer for the column statistics a GEMM's epilogue leaves for the GroupNorm that consumes its output (T2V_EPI_STATS:
-        fp32 [rows / 32][2][n]) — round 4, VERDICT r03 next #4: that GroupNorm then needs neither a statistics pass over the
-        tensor nor a grid barrier.  None when the option is off or the consumer's statistics instances (`inst_rows` rows each) are
-        not whole 32-row strips."""
-        if inst_rows % 32 != 0:
-            return None
-        if self.shard is not None and inst_rows == self.F * (rows // (self.Bc * self.F)):
-            # T-sharded cross-frame norm (never an epilogue: its statistics cross ranks): this rank's part folded from the producer's
-            # strips instead of a statistics pass over the tensor (round 6) — one small launch instead of two, per norm
-            if L.knob("T2V_TSHARD_STRIPS", "1") == "0":
-                return None
-        elif not self.gn_strips:
-            # round 6: automatically where the consuming norm can NOT run in its producer's epilogue because ONE statistics instance
-            # has more row tiles than the device holds co-resident (cross-frame norms of 125-frame / 1024x576 clips): strips + fold +
-            # one apply pass instead of the three-launch GroupNorm (two passes over the tensor + one)
-            if k is None or not self.P.gn_instance_too_large(rows, n, k, gather, inst_rows) or L.knob("T2V_GN_STRIPS_AUTO", "1") == "0":
-                return None
-        return self.P.alloc(-(-rows // 32), 2 * n, "f32")
-
-    def conv3(self, name, a: Buf, key, cout, h, w, *, stride=1, up=0, out_dtype="f32", rowbias=None,
-              residual=None, cin=None, dest: Optional[Buf] = None, dup_c8: bool = False, stats: Optional[Buf] = None,
-              hilo: bool = False) -> Buf:
-        """`dest`: write the result into this (sub-)buffer instead of a fresh allocation — the producers of the two
-        halves of a skip-connection concat write straight into the concat buffer (no copy ops)."""
-        cin = a.cols if cin is None else cin
-        ho, wo = (h * 2, w * 2) if up else ((h + 1) // 2 if stride == 2 else h, (w + 1) // 2 if stride == 2 else w)
-        Mo = self.Bc * self.F * ho * wo
-        n = (cout + 3) // 4 * 4
-        out = self._dest(dest, Mo, n, out_dtype)
-        gather = L.GATHER_CONV3X3_C8 if cin == 8 else L.GATHER_CONV3X3
-        wref = self.w_conv3_hilo(key) if hilo else (self.w_conv3_c8dup(key) if dup_c8 else self.w_conv3(key, 8 if cin == 8 else 0))
-        op = self.P.gemm(name, a, wref, n, 9 * cin, out, bias=self.vec(key + ".bias"),
-                         gather=gather, conv=dict(Hin=h, Win=w, Cin=cin, stride=stride, up=up, Hout=ho, Wout=wo),
-                         rowbias=rowbias, rows_per_batch=self.F * ho * wo if rowbias is not None else 0,
-                         residual=residual, stats=stats, k_alg=9 * cin // 2 if hilo else None)
-        self.last_stats = stats if (stats is not None and op.meta.get("stats")) else None     # None: the op ran with split-K
-        return out
-
-    def _dest(self, dest: Optional[Buf], rows, cols, dtype) -> Buf:
-        if dest is None:
-            return self.P.alloc(rows, cols, dtype)
-        assert (dest.rows, dest.cols, dest.dtype) == (rows, cols, dtype), (dest, rows, cols, dtype)
-        return dest
-
     def res_block(self, prefix, x: Buf, cin, cout, h, w, dest: Optional[Buf] = None) -> Buf:
         P = self.P
         # The 1x1 skip convolution (cin != cout) reads the block input as an fp16 operand.  Where the in_layers norm is its own op anyway
@@ -797,32 +625,8 @@ class _Lowering:
                         and not (P.ops and P.ops[-1].kind == L.OP_GEMM and P.ops[-1].out is x))
         if cast_in_norm:
             x16 = P.alloc(x.rows, 2 * cin if self.precise else cin, "f16")
-        a = self.gn(prefix + ".in_layers.0", x, prefix + ".in_layers.0", per_frame=True, eps=1e-5, silu=True, cast=x16, cast_lo=self.precise and cast_in_norm)
-        e0, e1 = self.emb_slices[prefix]
-        st = self.strips_for(x.rows, cout, h * w, 9 * cin, L.GATHER_CONV3X3)
-        h1 = self.conv3(prefix + ".in_layers.2", a, prefix + ".in_layers.2", cout, h, w,
-                        rowbias=self.emb_out.col_slice(e0, e1), out_dtype=self.net.norm_input_dtype, stats=st)
-        P.free(a)
-        b = self.gn(prefix + ".out_layers.0", h1, prefix + ".out_layers.0", per_frame=True, eps=1e-5, silu=True, stats=self.last_stats, x_dead=True)
-        P.free(h1, st)
-        if cin != cout:
-            skip = P.alloc(x.rows, cout, "f32")
-            if self.precise:
-                # hi + lo operand split in ONE pass: rows [hi (cin) | lo (cin)], weights [W | W], K = 2 cin
-                if x16 is None:
-                    x16 = P.alloc(x.rows, 2 * cin, "f16")
-                    P.copy2d(prefix + ".skip.cast", x, x16.col_slice(0, cin), lo=x16.col_slice(cin, 2 * cin))
-                P.gemm(prefix + ".skip_connection", x16, self.w_linear_dup(prefix + ".skip_connection"), cout, 2 * cin, skip,
-                       bias=self.vec(prefix + ".skip_connection.bias"), k_alg=cin)
-            else:
-                if x16 is None:
-                    x16 = P.alloc(x.rows, cin, "f16")
-                    P.copy2d(prefix + ".skip.cast", x, x16)
-                P.gemm(prefix + ".skip_connection", x16, self.w_linear(prefix + ".skip_connection"), cout, cin, skip,
-                       bias=self.vec(prefix + ".skip_connection.bias"))
-            P.free(x16)
-        else:
-            skip = x
+        b = self.res_front(prefix, x, cout, h, w, per_frame=True, strips_k=9 * cin, cast=x16, cast_lo=self.precise and cast_in_norm)
+        skip = self.skip_projection(prefix, x, cin, cout, x16) if cin != cout else x
         st = self.strips_for(x.rows, cout, self.F * h * w, 9 * cout, L.GATHER_CONV3X3)
         # T-sharded: every tensor a cross-frame GroupNorm + (3,1,1) convolution pair reads lives in a buffer with one halo frame either
         # side, RAW: the statistics exchange of that norm carries the boundary frames along (T2V_OP_STATS_HALO) and the norm's apply pass
@@ -891,36 +695,6 @@ class _Lowering:
             assert B == 1 and Mrows == F * hw
         scale = 64 ** -0.5
 
-        def self_attention_sharded(tag, xin: Buf) -> Buf:
-            """Temporal self-attention over a T-sharded clip: queries = local frames, keys/values = ALL
-            frames (K/V projections of the local tokens are all-gathered along T)."""
-            R, r = self.shard.size, self.shard.index
-            Mmax, Ftot = self.shard.max_frames * hw, self.shard.total     # rows of the largest slice; frames of the clip
-            n = P.alloc(Mrows, inner, "f16")
-            P.layernorm(f"{prefix}.norm{tag}", xin, self.vec(f"{prefix}.norm{tag}.weight"), self.vec(f"{prefix}.norm{tag}.bias"), n)
-            q = P.alloc(Mrows, inner, "f16")
-            P.gemm(f"{prefix}.attn{tag}.to_q", n, self.w_linear(f"{prefix}.attn{tag}.to_q"), inner, inner, q)
-            # slice q of the gathered buffer starts at frame q * max_frames: only the LAST slice can be short, so the
-            # clip's frames are contiguous from row 0 and the padding rows at the very end are never addressed
-            kv_all = P.alloc(R * Mmax, 2 * inner, "f16")
-            mine = kv_all.row_slice(r * Mmax, r * Mmax + Mrows)
-            P.gemm(f"{prefix}.attn{tag}.kv", n, self.w_kv(f"{prefix}.attn{tag}"), 2 * inner, inner, mine)
-            P.free(n)
-            full = Buf(kv_all.ref, R * Mmax * 2 * inner * 2, 1, 1, "u8", kv_all.alloc_off)
-            P.allgather(f"{prefix}.attn{tag}.kv.allgather", full, Mmax * 2 * inner * 2, self.shard)
-            a = P.alloc(Mrows, inner, "f16")
-            ldk = 2 * inner
-            k, v = kv_all.col_slice(0, inner), kv_all.col_slice(inner, 2 * inner)
-            P.attention(f"{prefix}.attn{tag}", q.ref, k.ref, v.ref, a.ref, out_buf=a, nq=F, nk=Ftot, heads=heads,
-                        b_outer=1, b_inner=hw, q_strides=(hw * inner, 0, inner), kv_strides=(hw * ldk, 0, ldk),
-                        o_strides=(hw * inner, 0, inner), scale=scale)
-            P.free(q, kv_all)
-            xo = P.alloc(Mrows, inner, "f32")
-            P.gemm(f"{prefix}.attn{tag}.to_out", a, self.w_linear(f"{prefix}.attn{tag}.to_out.0"), inner, inner, xo,
-                   bias=self.vec(f"{prefix}.attn{tag}.to_out.0.bias"), residual=xin)
-            P.free(a, xin)
-            return xo
-
         def self_attention(tag, xin: Buf, n: Buf, next_norm: str) -> Tuple[Buf, Buf]:
             """n = LayerNorm{tag}(xin) (made by the op that produced xin).  Returns (x + attention, LayerNorm{next_norm} of it):
             the to_out GEMM writes the fp32 stream AND — fused into its epilogue where the tile holds whole rows — the next
@@ -979,45 +753,15 @@ class _Lowering:
         sharded_temporal = kind == "temporal" and self.shard is not None and not local
         if sharded_temporal:
             # K/V-gather lowering (pixel count not divisible by the T group): LayerNorms as separate ops
-            x2 = self_attention_sharded(1, x1)
-            x3 = self_attention_sharded(2, x2)
+            x2 = self.kv_gather_attention(f"{prefix}.attn1", f"{prefix}.norm1", x1, inner, heads, hw, scale)
+            x3 = self.kv_gather_attention(f"{prefix}.attn2", f"{prefix}.norm2", x2, inner, heads, hw, scale)
             n3 = P.alloc(Mrows, inner, "f16")
             P.layernorm(f"{prefix}.norm3", x3, self.vec(f"{prefix}.norm3.weight"), self.vec(f"{prefix}.norm3.bias"), n3)
         else:
             x2, n2 = self_attention(1, x1, n1, "norm2")
             if kind == "spatial":
-                k0, k1 = self.kv_slices[prefix + ".attn2"]
-                kv = self.kv_all
-                kbuf, vbuf = kv.col_slice(k0, k0 + inner), kv.col_slice(k0 + inner, k1)
-                Lc = self.Lctx
-                # The text cross-attention is where cond and uncond part.  While the prefix is shared, q / x2 hold ONE sample's rows:
-                # the attention reads q with a zero sample stride against each sample's own K / V, and to_out adds x2 through the
-                # residual row wrap — from here on every tensor has B samples.
-                parting = self.sharing
-                Bq, q_b_stride, Mshared = (self.B, 0, Mrows) if parting else (B, F * hw * inner, 0)
-                Mq = Mrows
-                if parting:
-                    self.sharing, self.Bc = False, self.B
-                    B, Mrows = self.B, self.B * Mrows
-                a = P.alloc(Mrows, inner, "f16")
-                fused_op = None
-                if self.vt_all is not None and (F * hw) % 32 == 0 and Lc <= 96:
-                    # to_q + the 77-key attention as ONE launch (round 5): q never reaches HBM.  (At the parting site the projection runs
-                    # for both samples from the one sample's rows: the A-operand row wrap.)
-                    v0 = self.vt_slices[prefix + ".attn2"]
-                    vt = self.vt_all.row_slice(v0, self.vt_all.rows)           # this site's rows first; sample stride = all rows of a sample
-                    vt_site = Buf(vt.ref, self.vt_all.rows, self.vt_all.cols, self.vt_all.ld, "f16", owns=False)
-                    fused_op = P.to_q_cross_attention(f"{prefix}.attn2.q_attn", n2, self.w_linear(f"{prefix}.attn2.to_q"), a, k=inner, heads=heads,
-                                                      kbuf=kbuf, vt=vt_site, n_keys=Lc, rows_per_sample=F * hw, samples=self.B, scale=scale,
-                                                      a_wrap=Mq if parting else 0)
-                if fused_op is None:
-                    q = P.alloc(Mq, inner, "f16")
-                    P.gemm(f"{prefix}.attn2.to_q", n2, self.w_linear(f"{prefix}.attn2.to_q"), inner, inner, q)
-                    P.attention(f"{prefix}.attn2", q.ref, kbuf.ref, vbuf.ref, a.ref, out_buf=a, nq=hw, nk=Lc, heads=heads,
-                                b_outer=Bq, b_inner=F, q_strides=(inner, q_b_stride, hw * inner),
-                                kv_strides=(kv.ld, Lc * kv.ld, 0), o_strides=(inner, F * hw * inner, hw * inner), scale=scale)
-                    P.free(q)
-                P.free(n2)
+                a, Mshared = self.text_cross_attention(f"{prefix}.attn2", inner, heads, hw, scale, nrm=n2)
+                Mrows = a.rows                # (B samples from here on, also where the block's input was the shared single sample)
                 x3 = P.alloc(Mrows, inner, "f32")
                 n3 = P.alloc(Mrows, inner, "f16")
                 P.gemm(f"{prefix}.attn2.to_out", a, self.w_linear(f"{prefix}.attn2.to_out.0"), inner, inner, x3,
@@ -1025,24 +769,19 @@ class _Lowering:
                 P.free(a, x2)
             else:
                 x3, n3 = self_attention(2, x2, n2, "norm3")
-        # feed-forward: GEGLU fused in the first GEMM's epilogue
-        n = n3
-        wg, bg = self.w_geglu(f"{prefix}.ff.net.0.proj")
-        g = P.alloc(Mrows, 4 * inner, "f16")
-        P.gemm(f"{prefix}.ff.geglu", n, wg, 8 * inner, inner, g, bias=bg, epi=L.EPI_GEGLU)
-        P.free(n)
-        # x4 = x3 + FF feeds proj_out as an fp16 operand: with precise_operands it is stored as rows [hi | lo] (the low-order image
-        # of the fp16 rounding beside the value) and proj_out runs with K doubled against [W | W]
-        if self.precise_at(self.precise_ff, h, w):
-            x4 = P.alloc(Mrows, 2 * inner, "f16")
-            P.gemm(f"{prefix}.ff.net.2", g, self.w_linear(f"{prefix}.ff.net.2"), inner, 4 * inner, x4.col_slice(0, inner),
-                   bias=self.vec(f"{prefix}.ff.net.2.bias"), residual=x3, out_lo=True)
-        else:
-            x4 = P.alloc(Mrows, inner, "f16")
-            P.gemm(f"{prefix}.ff.net.2", g, self.w_linear(f"{prefix}.ff.net.2"), inner, 4 * inner, x4,
-                   bias=self.vec(f"{prefix}.ff.net.2.bias"), residual=x3)
-        P.free(g, x3)
-        return x4
+        return self.ff_tail(prefix, n3, x3, inner, h, w)
+
+    def to_q_attention(self, attn, nrm: Buf, a: Buf, inner, heads, hw, scale, wrap: int) -> bool:
+        """to_q + the 77-key attention as ONE launch (round 5): q never reaches HBM.  (At the parting site the projection runs
+        for both samples from the one sample's rows: the A-operand row wrap.)"""
+        if self.vt_all is None or (self.F * hw) % 32 != 0 or self.Lctx > 96:
+            return False
+        k0, _ = self.kv_slices[attn]
+        vt = self.vt_all.row_slice(self.vt_slices[attn], self.vt_all.rows)           # this site's rows first; sample stride = all rows of a sample
+        vt_site = Buf(vt.ref, self.vt_all.rows, self.vt_all.cols, self.vt_all.ld, "f16", owns=False)
+        return self.P.to_q_cross_attention(attn + ".q_attn", nrm, self.w_linear(attn + ".to_q"), a, k=inner, heads=heads,
+                                           kbuf=self.kv_all.col_slice(k0, k0 + inner), vt=vt_site, n_keys=self.Lctx, rows_per_sample=self.F * hw,
+                                           samples=self.B, scale=scale, a_wrap=wrap) is not None
 
     def spatial_transformer(self, prefix, x: Buf, c, h, w, dest: Optional[Buf] = None) -> Buf:
         P = self.P
@@ -1121,202 +860,65 @@ class _Lowering:
         P.free(yp, back)
         return out
 
-    def resample(self, prefix, attr, x: Buf, c, h, w, *, up, dest: Optional[Buf] = None) -> Buf:
-        P = self.P
-        if self.precise_rs and c % 64 == 0:
-            # the stream's fp16 cast as rows [hi | lo] (2c channels), the convolution on K = 9 * 2c against [W | W]
-            x16 = P.alloc(x.rows, 2 * c, "f16")
-            P.copy2d(prefix + ".cast", x, x16.col_slice(0, c), lo=x16.col_slice(c, 2 * c))
-            out = self.conv3(f"{prefix}.{attr}", x16, f"{prefix}.{attr}", c, h, w, stride=1 if up else 2, up=1 if up else 0, dest=dest, hilo=True)
-        else:
-            x16 = P.alloc(x.rows, c, "f16")
-            P.copy2d(prefix + ".cast", x, x16)
-            out = self.conv3(f"{prefix}.{attr}", x16, f"{prefix}.{attr}", c, h, w, stride=1 if up else 2, up=1 if up else 0, dest=dest)
-        P.free(x16)
-        return out
+    # -- whole network: the hooks of _UNetLowering.build -----------------------------------------------
+    def layout(self):
+        inputs, middle, outputs, _ = self.net._layout
+        norm = lambda blocks: [(prefix, [(prefix if bare else f"{prefix}.{i}", *part) for i, part in enumerate(parts)])
+                               for prefix, parts, bare in blocks]
+        inputs, (middle,), outputs = norm(inputs), norm([("middle_block", middle, False)]), norm(outputs)
+        return inputs, middle, outputs, inputs + [middle] + outputs
 
-    # -- whole network ------------------------------------------------------------------------------
-    def build(self) -> Program:
-        net, P, B, F = self.net, self.P, self.B, self.F
-        inputs, middle, outputs, last = net._layout
-        dim, emb = net.dim, net.embed_dim
-        h, w = self.H, self.W
-        P.begin()
-        if self.sharing and not any(kind == "st" for _, parts, _ in inputs for kind, _, _ in parts):
-            self.sharing, self.Bc = False, B           # no text cross-attention on the way down: nothing to share up to
+    def time_freqs(self) -> Ref:
+        return Ref("weight", 0, self.packer.add("time_freqs", "f32", lambda sd, d=self.net.dim: torch.pow(
+            10000, -torch.arange(d // 2).to(torch.float32).div(d // 2))))
 
-        # ---- step-level prologue: time embedding, all ResBlock emb projections, all cross-attn K/V
-        res_prefixes, st_prefixes = [], []
-        for prefix, parts, bare in inputs + [("middle_block", middle, False)] + outputs:
-            for i, (kind, cin, cout) in enumerate(parts):
-                p = prefix if bare else f"{prefix}.{i}"
-                if kind == "res":
-                    res_prefixes.append((p, cout))
-                elif kind == "st":
-                    st_prefixes.append((p, cout))
-        off = 0
-        for p, cout in res_prefixes:
-            self.emb_slices[p] = (off, off + cout)
-            off += cout
-        n_emb = off
-        off = 0
-        for p, c in st_prefixes:
-            self.kv_slices[p + ".transformer_blocks.0.attn2"] = (off, off + 2 * c)
-            off += 2 * c
-        n_kv = off
-
-        # The text-context K/V projections do not depend on x or t: they are the program's step-invariant prologue
-        # (Op.meta['step_invariant']), skipped when the caller vouches that the context is the one of the previous run
-        # (UNetSD.context_token).  Their buffer is allocated FIRST and freed last, so no other
-        # buffer of the program can alias it between two runs.
-        if n_kv:
-            self.kv_all = P.alloc(B * self.Lctx, n_kv, "f16")
+    def prologue_alloc(self, sites):
         # V^T of the text context for the fused to_q + cross-attention launches: rows = the value channels of every site, keys contiguous
         # (padded to a multiple of 32, zero beyond the context length: allocated here, never freed before the end, zero from the bind)
-        n_vt = n_kv // 2
-        xattn = (n_kv and self.shard is None and self.Lctx <= 96 and bool(getattr(net, "fused_cross_attention", True))
-                 and all(c % 64 == 0 for _, c in st_prefixes))
-        if xattn:
-            off = 0
-            for p, c in st_prefixes:
-                self.vt_slices[p + ".transformer_blocks.0.attn2"] = off
-                off += c
-            self.vt_all = P.alloc(B * n_vt, -(-self.Lctx // 32) * 32, "f16")
-        freqs = Ref("weight", 0, self.packer.add("time_freqs", "f32", lambda sd, d=dim: torch.pow(
-            10000, -torch.arange(d // 2).to(torch.float32).div(d // 2))))
-        te = P.alloc(B, dim, "f16")
-        P.time_embed("time_embed.sincos", Ref("ext", L.EXT_T), freqs, te)
-        e1 = P.alloc(B, emb, "f16")
-        P.gemm("time_embed.0", te, self.w_linear("time_embed.0"), emb, dim, e1, bias=self.vec("time_embed.0.bias"), act=1)
-        P.free(te)
-        e_silu = P.alloc(B, emb, "f16")       # SiLU(e): the only form in which e is consumed (emb_layers = SiLU -> Linear)
-        P.gemm("time_embed.2", e1, self.w_linear("time_embed.2"), emb, emb, e_silu, bias=self.vec("time_embed.2.bias"), act=1)
-        P.free(e1)
-        w_emb = Ref("weight", 0, self.packer.add("emb_all:lin", "f16", lambda sd, ps=tuple(p for p, _ in res_prefixes):
-                                                 torch.cat([sd[p + ".emb_layers.1.weight"] for p in ps], dim=0)))
-        b_emb = Ref("weight", 0, self.packer.add("emb_all:v", "f32", lambda sd, ps=tuple(p for p, _ in res_prefixes):
-                                                 torch.cat([sd[p + ".emb_layers.1.bias"] for p in ps], dim=0)))
-        self.emb_out = P.alloc(B, n_emb, "f32")
-        P.gemm("emb_layers.all", e_silu, w_emb, n_emb, emb, self.emb_out, bias=b_emb)
-        P.free(e_silu)
+        if not (self.shard is None and self.Lctx <= 96 and bool(getattr(self.net, "fused_cross_attention", True))
+                and all(c % 64 == 0 for _, c in sites)):
+            return []
+        off = 0
+        for p, c in sites:
+            self.vt_slices[p + ".transformer_blocks.0.attn2"] = off
+            off += c
+        self.vt_all = self.P.alloc(self.B * off, -(-self.Lctx // 32) * 32, "f16")
+        return [self.vt_all]
 
+    def prologue_extra(self, sites, ctx16: Buf):
+        if self.vt_all is None:
+            return
+        P, B, net = self.P, self.B, self.net
+        n_vt = self.vt_all.rows // B
         n4 = -(-self.Lctx // 4) * 4                 # keys of the V^T GEMMs (N % 4 == 0)
-        ctx_all = P.alloc(B * self.Lctx, net.context_dim, "f16")
-        ctx16 = ctx_all
-        ctx_src = Buf(Ref("ext", L.EXT_CTX), B * self.Lctx, net.context_dim, net.context_dim, self.ctx_dt)
-        P.copy2d("context.cast", ctx_src, ctx16).meta["step_invariant"] = True
-        if n_kv:
-            w_kv = Ref("weight", 0, self.packer.add("kv_all:lin", "f16", lambda sd, ps=tuple(p for p, _ in st_prefixes): torch.cat(
-                [torch.cat([sd[p + ".transformer_blocks.0.attn2.to_k.weight"], sd[p + ".transformer_blocks.0.attn2.to_v.weight"]], dim=0)
-                 for p in ps], dim=0)))
-            P.gemm("attn2.kv.all", ctx16, w_kv, n_kv, net.context_dim, self.kv_all, step_invariant=True)
-        if self.vt_all is not None:
-            # V^T [value channels of all sites, keys] = W_v x context^T per sample: swapped operands (the weights are the "token" operand).
-            # The GEMM wants N % 4 == 0 keys: every sample's tokens are copied into its own zero-padded [n4, ctx] block, and the whole V^T
-            # buffer is zeroed first, so that key columns Lctx .. lcp-1 are exactly 0 whatever the arena held and whatever the NEXT
-            # sample's context contains (0 x Inf = NaN: a non-finite context must not leak into its neighbour's output).
-            P.memset("attn2.vT.zero", self.vt_all).meta["step_invariant"] = True
-            ctx_pad = ctx16
-            if n4 > self.Lctx:
-                ctx_pad = P.alloc(B * n4, net.context_dim, "f16")
-                P.memset("context.pad", ctx_pad).meta["step_invariant"] = True
-                for b in range(B):
-                    P.copy2d(f"context.pad.{b}", ctx16.row_slice(b * self.Lctx, (b + 1) * self.Lctx),
-                             ctx_pad.row_slice(b * n4, b * n4 + self.Lctx)).meta["step_invariant"] = True
-            w_v = Ref("weight", 0, self.packer.add("v_all:lin", "f16", lambda sd, ps=tuple(p for p, _ in st_prefixes): torch.cat(
-                [sd[p + ".transformer_blocks.0.attn2.to_v.weight"] for p in ps], dim=0)))
-            wv_as_a = Buf(w_v, n_vt, net.context_dim, net.context_dim, "f16")
+        # V^T [value channels of all sites, keys] = W_v x context^T per sample: swapped operands (the weights are the "token" operand).
+        # The GEMM wants N % 4 == 0 keys: every sample's tokens are copied into its own zero-padded [n4, ctx] block, and the whole V^T
+        # buffer is zeroed first, so that key columns Lctx .. lcp-1 are exactly 0 whatever the arena held and whatever the NEXT
+        # sample's context contains (0 x Inf = NaN: a non-finite context must not leak into its neighbour's output).
+        P.memset("attn2.vT.zero", self.vt_all).meta["step_invariant"] = True
+        ctx_pad = ctx16
+        if n4 > self.Lctx:
+            ctx_pad = P.alloc(B * n4, net.context_dim, "f16")
+            P.memset("context.pad", ctx_pad).meta["step_invariant"] = True
             for b in range(B):
-                P.gemm(f"attn2.vT.all.{b}", wv_as_a, ctx_pad.row_slice(b * n4, (b + 1) * n4).ref, n4, net.context_dim,
-                       self.vt_all.row_slice(b * n_vt, (b + 1) * n_vt).col_slice(0, n4), ldw=net.context_dim, allow_splitk=False,
-                       step_invariant=True)
-            if ctx_pad is not ctx16:
-                P.free(ctx_pad)
-        P.free(ctx_all)
+                P.copy2d(f"context.pad.{b}", ctx16.row_slice(b * self.Lctx, (b + 1) * self.Lctx),
+                         ctx_pad.row_slice(b * n4, b * n4 + self.Lctx)).meta["step_invariant"] = True
+        w_v = Ref("weight", 0, self.packer.add("v_all:lin", "f16", lambda sd, ps=tuple(p for p, _ in sites): torch.cat(
+            [sd[p + ".transformer_blocks.0.attn2.to_v.weight"] for p in ps], dim=0)))
+        wv_as_a = Buf(w_v, n_vt, net.context_dim, net.context_dim, "f16")
+        for b in range(B):
+            P.gemm(f"attn2.vT.all.{b}", wv_as_a, ctx_pad.row_slice(b * n4, (b + 1) * n4).ref, n4, net.context_dim,
+                   self.vt_all.row_slice(b * n_vt, (b + 1) * n_vt).col_slice(0, n4), ldw=net.context_dim, allow_splitk=False,
+                   step_invariant=True)
+        if ctx_pad is not ctx16:
+            P.free(ctx_pad)
 
-        # ---- entry layout conversion: b c f h w -> tokens x 8 channels (4 real + 4 zero)
-        xin = P.alloc(self.M(h, w), 8, "f16")
-        # precise operands: the low-order fp16 images of the 4 latent channels ride in the 4 padding channels of the 8-channel
-        # token rows, the stem's weights repeat W there — (x_hi + x_lo) . W in the one GEMM pass, no extra launch
-        self.stem_dup = self.precise and self.x_dt == "f32" and net.in_dim == 4
-        P.ncthw_to_cl("x.to_tokens", Ref("ext", L.EXT_X), self.x_dt, xin, B=self.Bc, C=net.in_dim, F=F, HW=h * w,
-                      src_batch=self.x_batch if self.x_batch != self.Bc else 0, lo_in_pad=self.stem_dup)
-
-        def run_parts(prefix, parts, bare, x, h, w, dest=None):
-            for i, (kind, cin, cout) in enumerate(parts):
-                p = prefix if bare else f"{prefix}.{i}"
-                d = dest if i == len(parts) - 1 else None         # the block's result goes straight into a concat buffer
-                # shared cond | uncond prefix: this part's result has ONE sample's rows; a skip-connection window wants it for every
-                # sample -> the part writes its own buffer and two row-block copies fill the window (one site: input_blocks.0)
-                spread = d if (self.sharing and d is not None and kind != "st") else None
-                if spread is not None:
-                    d = None
-                if kind == "stem":
-                    y = self.conv3(p, x, p, cout, h, w, cin=8, dest=d, dup_c8=self.stem_dup)
-                elif kind == "res":
-                    y = self.res_block(p, x, cin, cout, h, w, dest=d)
-                elif kind == "st":
-                    y = self.spatial_transformer(p, x, cout, h, w, dest=d)
-                elif kind == "tt":
-                    heads = net.num_heads if p == "input_blocks.0.1" else cout // 64
-                    y = self.temporal_transformer(p, x, cout, heads, h, w, dest=d)
-                elif kind == "down":
-                    y = self.resample(p, "op", x, cout, h, w, up=False, dest=d)
-                    h, w = (h + 1) // 2, (w + 1) // 2
-                elif kind == "up":
-                    y = self.resample(p, "conv", x, cout, h, w, up=True, dest=d)
-                    h, w = h * 2, w * 2
-                else:
-                    raise ValueError(kind)
-                if spread is not None:
-                    assert spread.rows == self.B * y.rows and spread.cols == y.cols
-                    for b in range(self.B):
-                        P.copy2d(f"{p}.to_skip.{b}", y, spread.row_slice(b * y.rows, (b + 1) * y.rows))
-                P.tap(p, y)
-                P.free(x)              # borrowed windows of a concat buffer are ignored by free()
-                x = y
-            return x, h, w
-
-        def out_hw(parts, h, w):
-            for kind, _, _ in parts:
-                if kind == "down":
-                    h, w = (h + 1) // 2, (w + 1) // 2
-                elif kind == "up":
-                    h, w = h * 2, w * 2
-            return h, w
-
-        # Skip connections (t2v_model.py:447-452 `torch.cat([x, xs.pop()], dim=1)`): the concat buffer of decoder block j
-        # is allocated when its encoder half is produced; encoder block k writes the right window, the op that produces
-        # the decoder stream (middle block / previous decoder block) writes the left one — no copy kernels.
-        n_skip = len(inputs)
-        cats: List[Buf] = []
-        x = xin
-        for k, (prefix, parts, bare) in enumerate(inputs):
-            sc = parts[-1][2]
-            cin_total = outputs[n_skip - 1 - k][1][0][1]            # input channels of the consuming decoder ResBlock
-            ho, wo = out_hw(parts, h, w)
-            cat = P.alloc(self.B * self.F * ho * wo, cin_total, "f32")        # (every sample, whatever the current batch of the prefix)
-            cats.append(cat)
-            x, h, w = run_parts(prefix, parts, bare, x, h, w, dest=cat.borrow_cols(cin_total - sc, cin_total))
-        cat = cats.pop()
-        x, h, w = run_parts("middle_block", middle, False, x, h, w, dest=cat.borrow_cols(0, cat.cols - inputs[-1][1][-1][2]))
-        for j, (prefix, parts, bare) in enumerate(outputs):
-            nxt = cats.pop() if cats else None
-            dest = nxt.borrow_cols(0, nxt.cols - inputs[n_skip - 2 - j][1][-1][2]) if nxt is not None else None
-            x, h, w = run_parts(prefix, parts, bare, cat, h, w, dest=dest)
-            cat = nxt
-
-        assert not self.sharing and self.Bc == B, "the shared cond | uncond prefix never reached a text cross-attention"
-        # ---- head: GN + SiLU + conv 3x3 -> out_dim, then tokens -> b c f h w
-        a = self.gn("out.0", x, "out.0", per_frame=True, eps=1e-5, silu=True)
-        P.free(x)
-        y = self.conv3("out.2", a, "out.2", net.out_dim, h, w)
-        P.free(a)
-        P.cl_to_ncthw("eps.from_tokens", y, Ref("ext", L.EXT_OUT), self.out_dt, B=B, C=net.out_dim, F=F, HW=h * w)
-        P.free(y, self.emb_out)
-        if n_kv:
-            P.free(self.kv_all)
-        if self.vt_all is not None:
-            P.free(self.vt_all)
-        P.finish()
-        return P
+    def lower_part(self, kind, p, x: Buf, cin, cout, h, w, dest, inject) -> Buf:
+        if kind == "res":
+            return self.res_block(p, x, cin, cout, h, w, dest=dest)
+        if kind == "st":
+            return self.spatial_transformer(p, x, cout, h, w, dest=dest)
+        if kind == "tt":
+            heads = self.net.num_heads if p == "input_blocks.0.1" else cout // 64
+            return self.temporal_transformer(p, x, cout, heads, h, w, dest=dest)
+        return super().lower_part(kind, p, x, cin, cout, h, w, dest, inject)

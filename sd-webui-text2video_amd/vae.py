@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import packing as pk
+from .lowering import _Declarations
 from .program import Buf, Program, Ref
 from .unet import _Compiled, _dt
 
@@ -282,21 +283,10 @@ class AutoencoderKL(nn.Module):
         raise NotImplementedError("only decode() is on the hot path")
 
 
-class _VaeLowering:
+class _VaeLowering(_Declarations):
     def __init__(self, vae: AutoencoderKL, n, h, w, z_dt, out_dt, keep_taps=False):
+        super().__init__(f"vae n{n} {h}x{w}", keep_taps)
         self.vae, self.n, self.h, self.w, self.z_dt, self.out_dt = vae, n, h, w, z_dt, out_dt
-        self.P = Program(f"vae n{n} {h}x{w}")
-        self.P.keep_taps = keep_taps
-        self.packer = pk.WeightPacker()
-
-    def w_linear(self, key) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":lin", "f16", lambda sd, k=key: pk.pad_rows(pk.linear(sd[k + ".weight"]))))
-
-    def w_conv3(self, key, cin_pad=0) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":c3", "f16", lambda sd, k=key, c=cin_pad: pk.pad_rows(pk.conv3x3(sd[k + ".weight"], c))))
-
-    def vec(self, key) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":v", "f32", lambda sd, k=key: pk.pad_rows(sd[k])))
 
     def gn(self, key, x: Buf, silu: bool) -> Buf:
         out = self.P.alloc(x.rows, x.cols, "f16")

@@ -27,7 +27,8 @@ import torch.nn as nn
 from . import _lib as L
 from . import packing as pk
 from .program import Buf, Program, Ref
-from .unet import UNetSD, _Compiled, _Lowering, _attn_params
+from .lowering import _UNetLowering
+from .unet import UNetSD, _Compiled, _attn_params
 
 
 # ------------------------------------------------------------------------------------------
@@ -294,20 +295,20 @@ class UNetModel(UNetSD):
 # ------------------------------------------------------------------------------------------
 # lowering
 # ------------------------------------------------------------------------------------------
-class _LvdmLowering(_Lowering):
+class _LvdmLowering(_UNetLowering):
+    head_per_frame = False         # every GroupNorm32 of this UNet spans all frames of a sample
+
     def __init__(self, *args, adapter: int = 0, **kwargs):
         """adapter: samples of the adapter features this program adds at its injection sites (0: none — the op list is then exactly
         the one of a lowering that knows nothing of adapters)."""
         super().__init__(*args, **kwargs)
         self.adapter_fb = int(adapter)
+        self.n_feat = 0               # injection sites met so far
         assert not self.adapter_fb or self.shard is None, "adapter features are not sharded along T"
 
-    def w_conv133(self, key, cin_pad=0) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":c133", "f16", lambda sd, k=key, c=cin_pad:
-                                                pk.pad_rows(pk.conv3x3(sd[k + ".weight"][:, :, 0], c))))
-
-    def w_conv133_dup(self, key) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":c133d", "f16", lambda sd, k=key: pk.pad_rows(pk.conv3x3_c8_dup(sd[k + ".weight"][:, :, 0]))))
+    def conv3_kernel(self, key):
+        """Conv3d (1, 3, 3): the 3x3 kernel of its one temporal tap."""
+        return (lambda sd, k=key: sd[k + ".weight"][:, :, 0]), ":c133"
 
     def table(self, key) -> Ref:
         return Ref("weight", 0, self.packer.add(key + ":tab", "f32", lambda sd, k=key: sd[k]))
@@ -327,25 +328,6 @@ class _LvdmLowering(_Lowering):
         return Ref("weight", 0, self.packer.add(f"{key}:tabL{'T' if transposed else ''}", "f16",
                                                 lambda sd, k=key, t=transposed: pk.relpos_table_long(sd[k].float(), t)))
 
-    def w_conv133_hilo(self, key) -> Ref:
-        return Ref("weight", 0, self.packer.add(key + ":c133hl", "f16", lambda sd, k=key: pk.pad_rows(pk.conv3x3(torch.cat([sd[k + ".weight"][:, :, 0]] * 2, dim=1)))))
-
-    def conv133(self, name, a: Buf, key, cout, h, w, *, stride=1, up=0, out_dtype="f32", rowbias=None, residual=None, cin=None,
-                dest: Optional[Buf] = None, dup_c8: bool = False, stats: Optional[Buf] = None, hilo: bool = False, res_wrap: int = 0) -> Buf:
-        cin = a.cols if cin is None else cin
-        ho, wo = (h * 2, w * 2) if up else ((h + 1) // 2 if stride == 2 else h, (w + 1) // 2 if stride == 2 else w)
-        n = (cout + 3) // 4 * 4
-        out = self._dest(dest, self.Bc * self.F * ho * wo, n, out_dtype)
-        kw = dict(res_wrap=res_wrap) if res_wrap else {}
-        gather = L.GATHER_CONV3X3_C8 if cin == 8 else L.GATHER_CONV3X3
-        wref = self.w_conv133_hilo(key) if hilo else (self.w_conv133_dup(key) if dup_c8 else self.w_conv133(key, 8 if cin == 8 else 0))
-        op = self.P.gemm(name, a, wref, n, 9 * cin, out, bias=self.vec(key + ".bias"),
-                         gather=gather, conv=dict(Hin=h, Win=w, Cin=cin, stride=stride, up=up, Hout=ho, Wout=wo),
-                         rowbias=rowbias, rows_per_batch=self.F * ho * wo if rowbias is not None else 0, residual=residual, stats=stats,
-                         k_alg=9 * cin // 2 if hilo else None, **kw)
-        self.last_stats = stats if (stats is not None and op.meta.get("stats")) else None
-        return out
-
     def plus_feature(self, name, res: Buf, feat: Buf) -> Buf:
         """res + adapter feature as a new fp32 buffer (ONE launch: T2V_OP_RESHARD_ROWS with a zero source stride — the feature's rows repeat
         for every role of a [cond | uncond] batch).  It becomes the residual of the block's last GEMM, so the block's result, written in
@@ -358,35 +340,14 @@ class _LvdmLowering(_Lowering):
     def res_block(self, prefix, x: Buf, cin, cout, h, w, dest: Optional[Buf] = None, inject: Optional[Buf] = None) -> Buf:
         """ResBlock._forward (openaimodel3d.py:244-271): GroupNorm32 statistics span all frames of a sample."""
         P = self.P
-        a = self.gn(prefix + ".in_layers.0", x, prefix + ".in_layers.0", per_frame=False, eps=1e-5, silu=True)
-        e0, e1 = self.emb_slices[prefix]
-        st = self.strips_for(x.rows, cout, self.F * h * w)       # column statistics from the conv's epilogue for the norm that follows (unet.py)
-        h1 = self.conv133(prefix + ".in_layers.2", a, prefix + ".in_layers.2", cout, h, w,
-                          rowbias=self.emb_out.col_slice(e0, e1), out_dtype=self.net.norm_input_dtype, stats=st)
-        P.free(a)
-        b = self.gn(prefix + ".out_layers.0", h1, prefix + ".out_layers.0", per_frame=False, eps=1e-5, silu=True, stats=self.last_stats, x_dead=True)
-        P.free(h1, st)
-        if cin != cout:
-            skip = P.alloc(x.rows, cout, "f32")
-            if self.precise:         # hi + lo operand split in one pass (UNetSD.precise_operands): rows [hi | lo], weights [W | W]
-                x16 = P.alloc(x.rows, 2 * cin, "f16")
-                P.copy2d(prefix + ".skip.cast", x, x16.col_slice(0, cin), lo=x16.col_slice(cin, 2 * cin))
-                P.gemm(prefix + ".skip_connection", x16, self.w_linear_dup(prefix + ".skip_connection"), cout, 2 * cin, skip,
-                       bias=self.vec(prefix + ".skip_connection.bias"), k_alg=cin)
-            else:
-                x16 = P.alloc(x.rows, cin, "f16")
-                P.copy2d(prefix + ".skip.cast", x, x16)
-                P.gemm(prefix + ".skip_connection", x16, self.w_linear(prefix + ".skip_connection"), cout, cin, skip,
-                       bias=self.vec(prefix + ".skip_connection.bias"))
-            P.free(x16)
-        else:
-            skip = x
+        b = self.res_front(prefix, x, cout, h, w, per_frame=False)
+        skip = self.skip_projection(prefix, x, cin, cout) if cin != cout else x
         if inject is not None:
             with_feat = self.plus_feature(prefix + ".adapter", skip, inject)
             if skip is not x:
                 P.free(skip)
             skip = with_feat
-        out = self.conv133(prefix + ".out_layers.3", b, prefix + ".out_layers.3", cout, h, w, residual=skip, dest=dest)
+        out = self.conv3(prefix + ".out_layers.3", b, prefix + ".out_layers.3", cout, h, w, residual=skip, dest=dest)
         P.free(b)
         if skip is not x:
             P.free(skip)
@@ -434,36 +395,21 @@ class _LvdmLowering(_Lowering):
             P.free(a, res)
             return o, (ln[3] if ln is not None else None)
 
-        def temporal_attn_sharded(attn, norm, src: Buf, next_norm: str):
-            """Queries = this rank's frames, keys / values = all frames of the clip (K/V projections all-gathered along T);
-            the relative position of key s to local query t is s - (t + first frame of this slice)."""
+        def temporal_attn_sharded(attn, norm, src: Buf):
+            """The K/V-gather form; the relative position of key s to local query t is s - (t + first frame of this slice)."""
             sh = self.shard
-            Mmax, Ftot = sh.max_frames * hw, sh.total
-            nrm = layer_norm(norm, src)
-            q = P.alloc(M, c, "f16")
-            P.gemm(f"{tb}.{attn}.to_q", nrm, self.w_linear(f"{tb}.{attn}.to_q"), c, c, q)
-            kv_all = P.alloc(sh.size * Mmax, 2 * c, "f16")
-            mine = kv_all.row_slice(sh.index * Mmax, sh.index * Mmax + M)
-            P.gemm(f"{tb}.{attn}.kv", nrm, self.w_kv(f"{tb}.{attn}"), 2 * c, c, mine)
-            P.free(nrm)
-            full = Buf(kv_all.ref, sh.size * Mmax * 2 * c * 2, 1, 1, "u8", kv_all.alloc_off)
-            P.allgather(f"{tb}.{attn}.kv.allgather", full, Mmax * 2 * c * 2, sh)
-            a = attn_out()
-            ldk, lo = 2 * c, a.ld
-            P.attention(f"{tb}.{attn}", q.ref, kv_all.col_slice(0, c).ref, kv_all.col_slice(c, 2 * c).ref, a.ref, out_buf=a,
-                        nq=F, nk=Ftot, heads=heads, b_outer=1, b_inner=hw, q_strides=(hw * c, 0, c), kv_strides=(hw * ldk, 0, ldk),
-                        o_strides=(hw * lo, 0, lo), scale=scale, head_dim=d, lo_off=c if attn_lo else 0,
-                        rel_k=self.table(f"{tb}.{attn}.relative_position_k.embeddings_table"),
-                        rel_v=self.table(f"{tb}.{attn}.relative_position_v.embeddings_table"),
-                        rel_k_long=self.table_long(f"{tb}.{attn}.relative_position_k.embeddings_table", Ftot, False),
-                        rel_vT_long=self.table_long(f"{tb}.{attn}.relative_position_v.embeddings_table", Ftot, True),
-                        max_rel=net.temporal_length, q_offset=sh.offset)
-            P.free(q, kv_all)
-            return out_proj(attn, a, src, next_norm)
+            return self.kv_gather_attention(f"{tb}.{attn}", f"{tb}.{norm}", src, c, heads, hw, scale, out_cols=2 * c if attn_lo else c,
+                                            extras=lambda: dict(
+                head_dim=d, lo_off=c if attn_lo else 0,
+                rel_k=self.table(f"{tb}.{attn}.relative_position_k.embeddings_table"),
+                rel_v=self.table(f"{tb}.{attn}.relative_position_v.embeddings_table"),
+                rel_k_long=self.table_long(f"{tb}.{attn}.relative_position_k.embeddings_table", sh.total, False),
+                rel_vT_long=self.table_long(f"{tb}.{attn}.relative_position_v.embeddings_table", sh.total, True),
+                max_rel=net.temporal_length, q_offset=sh.offset)), None
 
         def self_attn(attn, norm, src: Buf, nrm: Optional[Buf], temporal: bool, next_norm: str):
             if temporal and self.shard is not None:
-                return temporal_attn_sharded(attn, norm, src, next_norm)
+                return temporal_attn_sharded(attn, norm, src)
             nrm = layer_norm(norm, src) if nrm is None else nrm
             qkv = P.alloc(M, 3 * c, "f16")
             P.gemm(f"{tb}.{attn}.qkv", nrm, self.w_qkv(f"{tb}.{attn}"), 3 * c, c, qkv)
@@ -496,36 +442,12 @@ class _LvdmLowering(_Lowering):
         q = P.alloc(M, c, "f16")
         P.gemm(f"{tb}.attn2.to_q", nrm, self.w_linear(f"{tb}.attn2.to_q"), c, c, q)
         P.free(nrm)
-        k0, k1 = self.kv_slices[tb + ".attn2"]
-        kv = self.kv_all
-        # cond and uncond part at the text cross-attention (unet.py transformer_block): q / cur hold ONE sample's rows while the prefix
-        # is shared — q is read with a zero sample stride, to_out adds `cur` through the residual row wrap, M becomes B samples' rows
-        parting = self.sharing
-        q_b_stride, shared_rows = (0, M) if parting else (F * hw * c, 0)
-        if parting:
-            self.sharing, self.Bc = False, self.B
-            B, M = self.B, self.B * M
-        a = attn_out()
-        Lc, lo = self.Lctx, a.ld
-        P.attention(f"{tb}.attn2", q.ref, kv.col_slice(k0, k0 + c).ref, kv.col_slice(k0 + c, k1).ref, a.ref, out_buf=a, nq=hw,
-                    nk=Lc, heads=heads, b_outer=B, b_inner=F, q_strides=(c, q_b_stride, hw * c), kv_strides=(kv.ld, Lc * kv.ld, 0),
-                    o_strides=(lo, F * hw * lo, hw * lo), scale=scale, head_dim=d, lo_off=c if attn_lo else 0)
-        P.free(q)
+        a, shared_rows = self.text_cross_attention(f"{tb}.attn2", c, heads, hw, scale, q=q, out_cols=2 * c if attn_lo else c, head_dim=d,
+                                                   lo_off=c if attn_lo else 0)
+        B, M = self.Bc, a.rows         # (cond and uncond have parted: B samples' rows from here on)
         cur, nxt = out_proj("attn2", a, cur, "norm5", res_wrap=shared_rows)
         cur, nxt = self_attn("attn2_tmp", "norm5", cur, nxt, temporal=True, next_norm="norm3")
-        nrm = layer_norm("norm3", cur) if nxt is None else nxt
-        wg, bg = self.w_geglu(f"{tb}.ff.net.0.proj")
-        g = P.alloc(M, 4 * c, "f16")
-        P.gemm(f"{tb}.ff.geglu", nrm, wg, 8 * c, c, g, bias=bg, epi=L.EPI_GEGLU)
-        P.free(nrm)
-        if self.precise_at(self.precise_ff, h, w):          # x4 as rows [hi | lo], proj_out against [W | W] (unet.py transformer_block)
-            x4 = P.alloc(M, 2 * c, "f16")
-            P.gemm(f"{tb}.ff.net.2", g, self.w_linear(f"{tb}.ff.net.2"), c, 4 * c, x4.col_slice(0, c), bias=self.vec(f"{tb}.ff.net.2.bias"),
-                   residual=cur, out_lo=True)
-        else:
-            x4 = P.alloc(M, c, "f16")
-            P.gemm(f"{tb}.ff.net.2", g, self.w_linear(f"{tb}.ff.net.2"), c, 4 * c, x4, bias=self.vec(f"{tb}.ff.net.2.bias"), residual=cur)
-        P.free(g, cur)
+        x4 = self.ff_tail(tb, layer_norm("norm3", cur) if nxt is None else nxt, cur, c, h, w)
         out = self._dest(dest, M, c, "f32")
         res = x
         if inject is not None:
@@ -538,148 +460,31 @@ class _LvdmLowering(_Lowering):
             P.free(res)
         return out
 
-    def build(self) -> Program:
-        net, P, B, F = self.net, self.P, self.B, self.F
-        inputs, middle, outputs, last = net._layout
-        mc, emb = net.model_channels, net.time_embed_dim
-        h, w = self.H, self.W
-        P.begin()
-        if self.sharing and not any(kind == "st" for _, parts in inputs for kind, _, _ in parts):
-            self.sharing, self.Bc = False, B
-        blocks = [(f"{pre}.{j}", part) for pre, parts in inputs + outputs for j, part in enumerate(parts)] + \
-                 [(f"middle_block.{j}", part) for j, part in enumerate(middle)]
-        res_prefixes = [(p, part[2]) for p, part in blocks if part[0] == "res"]
-        st_prefixes = [(p, part[2]) for p, part in blocks if part[0] == "st"]
-        off = 0
-        for p, cout in res_prefixes:
-            self.emb_slices[p] = (off, off + cout)
-            off += cout
-        n_emb = off
-        off = 0
-        for p, c in st_prefixes:
-            self.kv_slices[p + ".transformer_blocks.0.attn2"] = (off, off + 2 * c)
-            off += 2 * c
-        n_kv = off
+    # -- whole network: the hooks of _UNetLowering.build -----------------------------------------------
+    def layout(self):
+        inputs, middle, outputs, _ = self.net._layout
+        norm = lambda blocks: [(prefix, [(f"{prefix}.{j}", *part) for j, part in enumerate(parts)]) for prefix, parts in blocks]
+        inputs, (middle,), outputs = norm(inputs), norm([("middle_block", middle)]), norm(outputs)
+        return inputs, middle, outputs, inputs + outputs + [middle]
 
-        self.kv_all = P.alloc(B * self.Lctx, n_kv, "f16")     # first allocation, freed last: survives between runs (see unet.py)
-        # ---- timestep embedding (util.py:142-162 cos|sin, base 10000) -> MLP; every ResBlock's emb projection in one GEMM
-        freqs = Ref("weight", 0, self.packer.add("time_embed.freqs", "f32", lambda sd, half=mc // 2: torch.exp(
+    def time_freqs(self) -> Ref:
+        """util.py:142-162: cos | sin, base 10000."""
+        return Ref("weight", 0, self.packer.add("time_embed.freqs", "f32", lambda sd, half=self.net.model_channels // 2: torch.exp(
             -math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half)))
-        te = P.alloc(B, mc, "f16")
-        P.time_embed("time_embed.sincos", Ref("ext", L.EXT_T), freqs, te)
-        e1 = P.alloc(B, emb, "f16")
-        P.gemm("time_embed.0", te, self.w_linear("time_embed.0"), emb, mc, e1, bias=self.vec("time_embed.0.bias"), act=1)
-        P.free(te)
-        e_silu = P.alloc(B, emb, "f16")      # emb is consumed only through emb_layers = SiLU -> Linear
-        P.gemm("time_embed.2", e1, self.w_linear("time_embed.2"), emb, emb, e_silu, bias=self.vec("time_embed.2.bias"), act=1)
-        P.free(e1)
-        ps = tuple(p for p, _ in res_prefixes)
-        w_emb = Ref("weight", 0, self.packer.add("emb_all:lin", "f16", lambda sd, ps=ps: torch.cat([sd[p + ".emb_layers.1.weight"] for p in ps], dim=0)))
-        b_emb = Ref("weight", 0, self.packer.add("emb_all:v", "f32", lambda sd, ps=ps: torch.cat([sd[p + ".emb_layers.1.bias"] for p in ps], dim=0)))
-        self.emb_out = P.alloc(B, n_emb, "f32")
-        P.gemm("emb_layers.all", e_silu, w_emb, n_emb, emb, self.emb_out, bias=b_emb)
-        P.free(e_silu)
 
-        ctx16 = P.alloc(B * self.Lctx, net.context_dim, "f16")
-        P.copy2d("context.cast", Buf(Ref("ext", L.EXT_CTX), B * self.Lctx, net.context_dim, net.context_dim, self.ctx_dt),
-                 ctx16).meta["step_invariant"] = True
-        sts = tuple(p for p, _ in st_prefixes)
-        w_kv = Ref("weight", 0, self.packer.add("kv_all:lin", "f16", lambda sd, sts=sts: torch.cat(
-            [torch.cat([sd[p + ".transformer_blocks.0.attn2.to_k.weight"], sd[p + ".transformer_blocks.0.attn2.to_v.weight"]], dim=0)
-             for p in sts], dim=0)))
-        P.gemm("attn2.kv.all", ctx16, w_kv, n_kv, net.context_dim, self.kv_all).meta["step_invariant"] = True
-        P.free(ctx16)
+    def lower_part(self, kind, p, x: Buf, cin, cout, h, w, dest, inject) -> Buf:
+        if kind == "res":
+            return self.res_block(p, x, cin, cout, h, w, dest=dest, inject=inject)
+        if kind == "st":
+            return self.st_transformer(p, x, cout, h, w, dest=dest, inject=inject)
+        return super().lower_part(kind, p, x, cin, cout, h, w, dest, inject)
 
-        xin = P.alloc(self.M(h, w), 8, "f16")
-        self.stem_dup = self.precise and self.x_dt == "f32" and net.in_dim == 4
-        P.ncthw_to_cl("x.to_tokens", Ref("ext", L.EXT_X), self.x_dt, xin, B=self.Bc, C=net.in_dim, F=F, HW=h * w,
-                      src_batch=self.x_batch if self.x_batch != self.Bc else 0, lo_in_pad=self.stem_dup)
-
-        def run_parts(prefix, parts, x, h, w, dest=None, inject=None):
-            """inject: the adapter feature added to this block's result (a residual operand of its last GEMM — the result lands in
-            the concat buffer with the feature in it: openaimodel3d.py:657-660 adds it before `hs.append`)."""
-            for j, (kind, cin, cout) in enumerate(parts):
-                p = f"{prefix}.{j}"
-                d = dest if j == len(parts) - 1 else None
-                inj = inject if j == len(parts) - 1 else None
-                # a convolution has no residual of its own: the feature IS its residual (no extra launch), wrapped over the batch's roles
-                conv_res = dict(residual=inj, res_wrap=inj.rows if self.Bc > self.adapter_fb else 0) \
-                    if (inj is not None and kind in ("stem", "down")) else {}
-                spread = d if (self.sharing and d is not None and kind != "st") else None      # shared cond | uncond prefix: unet.py run_parts
-                if spread is not None:
-                    d = None
-                if kind == "stem":
-                    y = self.conv133(p, x, p, cout, h, w, cin=8, dest=d, dup_c8=self.stem_dup, **conv_res)
-                elif kind == "res":
-                    y = self.res_block(p, x, cin, cout, h, w, dest=d, inject=inj)
-                elif kind == "st":
-                    y = self.st_transformer(p, x, cout, h, w, dest=d, inject=inj)
-                elif kind in ("down", "up"):
-                    attr = "op" if kind == "down" else "conv"
-                    if self.precise_rs and cin % 64 == 0:        # the cast as rows [hi | lo], the convolution against [W | W] (unet.py resample)
-                        x16 = P.alloc(x.rows, 2 * cin, "f16")
-                        P.copy2d(p + ".cast", x, x16.col_slice(0, cin), lo=x16.col_slice(cin, 2 * cin))
-                        y = self.conv133(f"{p}.{attr}", x16, f"{p}.{attr}", cout, h, w, stride=2 if kind == "down" else 1,
-                                         up=1 if kind == "up" else 0, dest=d, hilo=True, **conv_res)
-                    else:
-                        x16 = P.alloc(x.rows, cin, "f16")
-                        P.copy2d(p + ".cast", x, x16)
-                        y = self.conv133(f"{p}.{attr}", x16, f"{p}.{attr}", cout, h, w, stride=2 if kind == "down" else 1,
-                                         up=1 if kind == "up" else 0, dest=d, **conv_res)
-                    P.free(x16)
-                    h, w = ((h + 1) // 2, (w + 1) // 2) if kind == "down" else (h * 2, w * 2)
-                else:
-                    raise ValueError(kind)
-                if spread is not None:
-                    assert spread.rows == self.B * y.rows and spread.cols == y.cols
-                    for b in range(self.B):
-                        P.copy2d(f"{p}.to_skip.{b}", y, spread.row_slice(b * y.rows, (b + 1) * y.rows))
-                P.tap(p, y)
-                P.free(x)              # borrowed windows of a concat buffer are ignored by free()
-                x = y
-            return x, h, w
-
-        def out_hw(parts, h, w):
-            for kind, _, _ in parts:
-                if kind == "down":
-                    h, w = (h + 1) // 2, (w + 1) // 2
-                elif kind == "up":
-                    h, w = h * 2, w * 2
-            return h, w
-
-        # `th.cat([h, hs.pop()], dim=1)` (openaimodel3d.py:665): both halves are written in place by their producers
-        n_skip = len(inputs)
-        cats: List[Buf] = []
-        x = xin
-        n_feat = 0
-        for k, (prefix, parts) in enumerate(inputs):
-            sc = parts[-1][2]
-            cin_total = outputs[n_skip - 1 - k][1][0][1]
-            ho, wo = out_hw(parts, h, w)
-            cat = P.alloc(self.B * self.F * ho * wo, cin_total, "f32")
-            cats.append(cat)
-            feat = None
-            if self.adapter_fb and (k + 1) % 3 == 0:          # openaimodel3d.py:657
-                feat = Buf(Ref("ext", L.EXT_ADAPTER + n_feat), self.adapter_fb * self.F * ho * wo, sc, sc, "f32")
-                n_feat += 1
-            x, h, w = run_parts(prefix, parts, x, h, w, dest=cat.borrow_cols(cin_total - sc, cin_total), inject=feat)
-        cat = cats.pop()
-        x, h, w = run_parts("middle_block", middle, x, h, w, dest=cat.borrow_cols(0, cat.cols - inputs[-1][1][-1][2]))
-        for j, (prefix, parts) in enumerate(outputs):
-            nxt = cats.pop() if cats else None
-            dest = nxt.borrow_cols(0, nxt.cols - inputs[n_skip - 2 - j][1][-1][2]) if nxt is not None else None
-            x, h, w = run_parts(prefix, parts, cat, h, w, dest=dest)
-            cat = nxt
-
-        assert not self.sharing and self.Bc == B, "the shared cond | uncond prefix never reached a text cross-attention"
-        a = self.gn("out.0", x, "out.0", per_frame=False, eps=1e-5, silu=True)
-        P.free(x)
-        y = self.conv133("out.2", a, "out.2", net.out_dim, h, w)
-        P.free(a)
-        P.cl_to_ncthw("eps.from_tokens", y, Ref("ext", L.EXT_OUT), self.out_dt, B=B, C=net.out_dim, F=F, HW=h * w)
-        P.free(y, self.emb_out, self.kv_all)
-        P.finish()
-        return P
+    def inject_for(self, k: int, c, h, w) -> Optional[Buf]:
+        """The adapter feature of encoder block k (openaimodel3d.py:657-660 adds it to the block's result before `hs.append`)."""
+        if not self.adapter_fb or (k + 1) % 3 != 0:
+            return None
+        self.n_feat += 1
+        return Buf(Ref("ext", L.EXT_ADAPTER + self.n_feat - 1), self.adapter_fb * self.F * h * w, c, c, "f32")
 
 
 # ------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """Shared helpers for the parity tests (test infrastructure)."""
 from __future__ import annotations
 
+import hashlib
+
 import torch
 
 from interp import Interp
@@ -13,6 +15,24 @@ TD = {"f16": torch.float16, "f32": torch.float32}
 def rel_l2(a: torch.Tensor, b: torch.Tensor) -> float:
     a, b = a.double(), b.double()
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
+
+
+def program_digest(comp, state_dict=None) -> str:
+    """SHA-256 of everything a lowering decides (`comp` has .prog and .packer): every op record — kind, name, the integer slots, the float
+    slots bit for bit, the pointer slots as (space, offset, weight name) — and its step-invariant mark, the arena's high-water mark and the
+    packer's images (name, dtype) in declaration order; with a state dict also the bytes of every materialised image, in name order.
+    Two lowerings with the same digest hand the library the same bytes."""
+    h = hashlib.sha256()
+    for op in comp.prog.ops:
+        h.update(repr((op.kind, op.name, list(op.i), [float(v).hex() for v in op.f], [(r.space, r.off, r.name) for r in op.p],
+                       bool(op.meta.get("step_invariant", False)))).encode())
+    h.update(repr((comp.prog.arena.high, [(name, dtype) for name, dtype, _ in comp.packer.recipes])).encode())
+    if state_dict is not None:
+        packed = comp.packer.materialise(state_dict, "cpu")
+        for name in sorted(packed):
+            h.update(name.encode())
+            h.update(packed[name].contiguous().numpy().tobytes())
+    return h.hexdigest()
 
 
 def fill(it: Interp, buf: Buf, gen: torch.Generator, scale: float = 1.0, total_cols=None):

@@ -8,11 +8,11 @@ import numpy as np
 import pytest
 import torch
 
-from harness import rel_l2
+from harness import program_digest, rel_l2
 from interp import Interp
 from oracle import configs, synth, torch_port as tp
 from sd_webui_text2video_amd import _lib as L
-from sd_webui_text2video_amd import samplers, videocrafter as VC
+from sd_webui_text2video_amd import samplers, unet as U, videocrafter as VC
 from test_samplers_cpu import _ddim_update_cpu, _lincomb_cpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -82,6 +82,30 @@ def test_program_matches_golden_in_interpreter(tiny):
     kinds = [op.kind for op in comp.prog.ops]
     n_st = sum(1 for p in net.state_dict() if p.endswith("attn1_tmp.to_q.weight"))      # transformer sites
     assert kinds.count(L.OP_RELPOS_ATTN) == 2 * n_st and kinds.count(L.OP_ATTENTION) == 2 * n_st
+
+
+def test_modelscope_only_fusions_do_not_reach_the_lvdm_program(tiny, monkeypatch):
+    """The two UNets share one lowering skeleton; the fused to_q + text cross-attention and the fused QKV + temporal attention are
+    ModelScope's alone: their options must not move a bit of the LVDM program — records, arena and packed images."""
+    net, _ = tiny
+
+    def digest(attr, value):
+        monkeypatch.setattr(net, attr, value)
+        return program_digest(net._compile(2, 5, 8, 8, 9, "f32", "f32", "f32"), net.state_dict())
+
+    assert digest("fused_cross_attention", True) == digest("fused_cross_attention", False)
+    assert digest("fused_temporal_attention", False) == digest("fused_temporal_attention", "force")
+
+
+def test_program_digest_sees_the_program():
+    """The shared cond | uncond prefix changes the rows of some thirty ops and nothing else: the digest must tell the two programs apart."""
+    m = U.UNetSD(**configs.TINY_UNET)
+    synth.load_synth(m, seed=0)
+    digests = []
+    for share in (False, True):
+        m._share_now = share
+        digests.append(program_digest(m._compile(2, 3, 16, 16, 7, "f32", "f32", "f32", x_batch=1), m.state_dict()))
+    assert digests[0] != digests[1]
 
 
 def test_ddim_sampler_host_logic(tiny, monkeypatch):
