@@ -29,6 +29,8 @@ extern "C" {
 #define T2V_ABI_VERSION 11  /* 11: VideoCrafter depth adapter (additive: no existing record changes) — T2V_OP_DEPTH_TOKENS (depth frames -> PixelUnshuffle(8)
                                tokens, optional per-frame min-max normalisation), T2V_OP_AVGPOOL2 (2x2 mean of channels-last fp32 tokens), GEMM i[18] = 2
                                (ReLU), GEMM i[30] (residual row wrap for every gather mode, split-K allowed), T2V_EXT_ADAPTER (feature slots);
+                               still 11: DDIM_STEP i[7] / p[4..6] / f[6..7] (mask blend of a VideoCrafter step) — additive on fields that every earlier
+                               record leaves zero, so the version does not move;
                                10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
                                optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
                                9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
@@ -252,6 +254,12 @@ enum t2v_gather {
  *      mode 1 (LDM DDIM, samplers/ddim/sampler.py:197-219):  x0 = (x - f0*e)/f1;  out = f2*x0 + f3*e + f4*noise
  *        f: 0 sqrt(1-a_t), 1 sqrt(a_t), 2 sqrt(a_prev), 3 sqrt(1-a_prev-sigma^2), 4 sigma, 5 guidance scale
  *      p: 0 xt, 1 eps pair, 2 noise, 3 out
+ *      i[7] = 1 (mode 1, fp32 x): the known-region blend of a masked step (lvdm/samplers/ddim.py:188-195) in the same launch, after
+ *        the update above (eta noise included), in fp32 and in the reference's order:
+ *          known = f6 * x0 + f7 * qnoise;   out = known * mask + (1 - mask) * out
+ *        f: 6 sqrt_alphas_cumprod[t'], 7 sqrt_one_minus_alphas_cumprod[t'] (t' = step - 1: q_sample of the known content)
+ *        p: 4 known x0, 5 mask, 6 q-noise (may be null when f7 == 0) — fp32, dense, shaped like x [samples, channels, inner]
+ *        i[7] = 0: p[4..6] and f[6..7] are not read
  * LINCOMB: i: 0 n elements, 1 n terms (<= 6), 2 out dtype, 3..8 term dtypes; f: 0..5 coefficients;
  *      p: 0..5 terms, 6 out
  * MEMSET: i: 0 bytes (lo), 1 bytes (hi); p: 0 dst

@@ -7,7 +7,8 @@
 //   copy2d        strided 2-D copy / fp32->fp16 cast / SiLU: torch.cat of skip connections
 //                 (t2v_model.py:444), operand staging, SiLU(e) of emb_layers (:936)
 //   ddim_step     DDIM_Gaussian update incl. half-channel classifier-free guidance
-//                 (samplers/ddim/gaussian_sampler.py:125-136, 103-108, 199-211, 269-283)
+//                 (samplers/ddim/gaussian_sampler.py:125-136, 103-108, 199-211, 269-283); a compile-time variant adds the
+//                 known-region blend of a masked LVDM step (lvdm/samplers/ddim.py:188-195) to the same launch
 //   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
 //                 (process_modelscope.py:116-120, 174-178); the last pass can write the VAE encoder's tokens
 //   depth_tokens  entry of the VideoCrafter depth adapter: per-frame min-max normalisation (ddpm3d.py:1463-1464) + PixelUnshuffle(8)
@@ -124,8 +125,15 @@ struct DdimParams {
   float a_recip, a_recipm1, sqrt_aprev, dir_coef, sigma, gscale;
 };
 
-template <typename TX, typename TE>
-__global__ __launch_bounds__(256) void ddim_step_kernel(const DdimParams p) {
+// i[7] = 1: the known-region blend of a masked LVDM step (lvdm/samplers/ddim.py:188-195), all fp32 and dense like x
+struct DdimBlend {
+  const float* x0; const float* mask; const float* qnoise;
+  float sqrt_ac, sqrt_1mac;
+};
+
+// BLEND is empty (the plain step: no extra kernel argument, no extra instruction) or one DdimBlend
+template <typename TX, typename TE, typename... BLEND>
+__global__ __launch_bounds__(256) void ddim_step_kernel(const DdimParams p, const BLEND... blend) {
   // x_t [S,Cs,inner] with C = S*Cs rows; eps [2,S,Cs,inner] (0 = conditional, 1 = unconditional); S videos per batch
   const TX* xt = reinterpret_cast<const TX*>(p.xt);
   const TE* ec = reinterpret_cast<const TE*>(p.eps);
@@ -152,6 +160,13 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const DdimParams p) {
       xn = p.sqrt_aprev * x0 + p.dir_coef * o;
     }
     if (p.noise != nullptr && p.sigma != 0.f) xn += p.sigma * p.noise[idx];
+    if constexpr (sizeof...(BLEND) != 0) {     // img_known = q_sample(x0, t'); img = img_known * mask + (1 - mask) * img
+      const DdimBlend& b = (blend, ...);
+      float known = b.sqrt_ac * b.x0[idx];
+      if (b.qnoise != nullptr && b.sqrt_1mac != 0.f) known += b.sqrt_1mac * b.qnoise[idx];
+      const float m = b.mask[idx];
+      xn = known * m + (1.f - m) * xn;
+    }
     out[idx] = (TX)xn;
   }
 }
@@ -663,6 +678,17 @@ hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s) {
   p.a_recip = op.f[0]; p.a_recipm1 = op.f[1]; p.sqrt_aprev = op.f[2]; p.dir_coef = op.f[3]; p.sigma = op.f[4];
   p.gscale = op.f[5];
   const int g = grid_for((long)p.C * p.inner);
+  if (op.i[7] != 0) {                          // masked step: the blend is a compile-time variant (fp32 x only; the executor checked)
+    if (!p.x_f32) return hipErrorInvalidValue;
+    DdimBlend b;
+    b.x0 = reinterpret_cast<const float*>(op.p[4]);
+    b.mask = reinterpret_cast<const float*>(op.p[5]);
+    b.qnoise = reinterpret_cast<const float*>(op.p[6]);
+    b.sqrt_ac = op.f[6]; b.sqrt_1mac = op.f[7];
+    if (p.eps_f32) hipLaunchKernelGGL((ddim_step_kernel<float, float, DdimBlend>), dim3(g), dim3(256), 0, s, p, b);
+    else hipLaunchKernelGGL((ddim_step_kernel<float, f16, DdimBlend>), dim3(g), dim3(256), 0, s, p, b);
+    return hipGetLastError();
+  }
   if (p.x_f32 && p.eps_f32) hipLaunchKernelGGL((ddim_step_kernel<float, float>), dim3(g), dim3(256), 0, s, p);
   else if (p.x_f32) hipLaunchKernelGGL((ddim_step_kernel<float, f16>), dim3(g), dim3(256), 0, s, p);
   else if (p.eps_f32) hipLaunchKernelGGL((ddim_step_kernel<f16, float>), dim3(g), dim3(256), 0, s, p);

@@ -224,6 +224,13 @@ int validate_op(const t2v_op& op, int idx) {
       if (C <= 0 || op.i[1] <= 0 || cps <= 0 || C % cps != 0) return bad("DDIM step needs C > 0, inner > 0, C % channels-per-sample == 0");
       if (op.i[2] < 0 || op.i[2] > cps || (op.i[5] != 0 && op.i[5] != 1)) return bad("DDIM step: guided channels / mode");
       if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return bad("null DDIM step pointer");
+      if (op.i[7] != 0 && op.i[7] != 1) return bad("DDIM step: blend flag i[7] must be 0 or 1");
+      if (op.i[7] == 1) {
+        if (op.i[5] != 1) return bad("DDIM step: the mask blend i[7] exists for mode 1 (LDM DDIM) only");
+        if (op.i[4] != T2V_F32) return bad("DDIM step: the mask blend i[7] needs an fp32 x");
+        if (op.p[4] == 0 || op.p[5] == 0) return bad("DDIM step: the mask blend i[7] needs the known x0 p[4] and the mask p[5]");
+        if (op.p[6] == 0 && op.f[7] != 0.f) return bad("DDIM step: the mask blend i[7] needs the q-noise p[6] unless f[7] == 0");
+      }
       return 0;
     }
     case T2V_OP_MEMSET:

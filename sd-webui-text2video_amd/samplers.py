@@ -308,6 +308,32 @@ def _ddim_update(out, xt, eps_pair, noise, coef, guided: int, mode: int):
     return out
 
 
+def _ddim_update_blend(out, xt, eps_pair, noise, coef, guided: int, known, mask, qnoise, qcoef):
+    """T2V_OP_DDIM_STEP mode 1 with i[7] = 1: the LDM DDIM update of `_ddim_update` and, in the same launch, the known-region blend
+    of a masked step (lvdm/samplers/ddim.py:188-195): out = (qcoef[0] * known + qcoef[1] * qnoise) * mask + (1 - mask) * x_{t-1}.
+    known, mask, qnoise: fp32, contiguous, shaped like xt (qnoise may be None when qcoef[1] == 0)."""
+    lib = L.load()
+    op = L.T2VOp()
+    op.kind = L.OP_DDIM_STEP
+    B, C = xt.shape[0], xt.shape[1]
+    op.i[0], op.i[1], op.i[2] = B * C, xt.numel() // (B * C), guided
+    op.i[6] = C
+    op.i[3], op.i[4], op.i[5], op.i[7] = _dt_tag(eps_pair), _dt_tag(xt), 1, 1
+    for k in range(6):
+        op.f[k] = float(coef[k])
+    op.f[6], op.f[7] = float(qcoef[0]), float(qcoef[1])
+    for t in (known, mask, qnoise):
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.shape == xt.shape and t.device == xt.device):
+            raise L.T2VError("the blend operands of a masked DDIM step must be fp32, contiguous, on the device and shaped like x")
+    op.p[0], op.p[1], op.p[3] = xt.data_ptr(), eps_pair.data_ptr(), out.data_ptr()
+    op.p[2] = noise.data_ptr() if (noise is not None and float(coef[4]) != 0.0) else 0
+    op.p[4], op.p[5] = known.data_ptr(), mask.data_ptr()
+    op.p[6] = qnoise.data_ptr() if qnoise is not None else 0
+    stream = torch.cuda.current_stream(xt.device).cuda_stream
+    L.check(lib.t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(stream)))
+    return out
+
+
 _RUN_COUNTER = itertools.count(1)
 
 

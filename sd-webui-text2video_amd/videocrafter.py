@@ -815,6 +815,53 @@ class LatentDiffusion(nn.Module):
         out = self.model(x_noisy, t, **cond, **kwargs)
         return out[0] if isinstance(out, tuple) and not return_ids else out
 
+    def q_sample(self, x_start, t, noise=None):
+        """ddpm3d.py:283-286: sqrt(ac[t]) * x_start + sqrt(1 - ac[t]) * noise, t a long tensor [b], from the fp32 schedule buffers.
+        noise=None draws torch.randn(x_start.shape) from the CPU default generator and moves it to x_start's device: the stream the
+        reference's `randn_like` gives on its CPU path, and the same on any device (the convention of DDIMSampler.noise_gen)."""
+        if noise is None:
+            noise = torch.randn(tuple(x_start.shape)).to(x_start.device)
+        t = t.to(device=self.sqrt_alphas_cumprod.device, dtype=torch.long)
+        bshape = (t.shape[0],) + (1,) * (x_start.dim() - 1)          # extract_into_tensor (util.py)
+        a = self.sqrt_alphas_cumprod.gather(-1, t).reshape(bshape).to(x_start.device)
+        s = self.sqrt_one_minus_alphas_cumprod.gather(-1, t).reshape(bshape).to(x_start.device)
+        return a * x_start + s * noise
+
+    def get_first_stage_encoding(self, encoder_posterior, noise=None):
+        """ddpm3d.py:636-644: a posterior is sampled (with `noise` if given), a tensor is taken as z; -> scale_factor * (z + shift_factor)."""
+        from .vae import DiagonalGaussianDistribution
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            z = encoder_posterior.sample(noise=noise)
+        elif isinstance(encoder_posterior, torch.Tensor):
+            z = encoder_posterior
+        else:
+            raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
+        return self.scale_factor * (z + self.shift_factor)
+
+    @torch.no_grad()
+    def encode_first_stage_2DAE(self, x, encode_bs=16):
+        """ddpm3d.py:796-810: x [b, 3, t, H, W] in [-1, 1] -> sampled, scaled latent [b, 4, t, H/8, W/8].  The reference encodes the
+        (b t) frames in chunks of encode_bs and samples each chunk's posterior with torch.randn on the CPU default generator
+        (distributions.py:16-21).  Here ONE encoder program covers all frames (frames are independent); the posterior noise is
+        still drawn chunk by chunk, in the reference's chunk shapes and order — chunked draws need not equal one big draw."""
+        if encode_bs is None:
+            raise NotImplementedError("encode_first_stage_2DAE(encode_bs=None) hands a posterior object to rearrange "
+                                      "(autoencoder.py:95-100, ddpm3d.py:799-800, :809): the reference fails too")
+        if x.dim() != 5:
+            raise ValueError(f"x must be [b, 3, t, H, W], got {tuple(x.shape)}")
+        b, _, t, _, _ = x.shape
+        frames = x.permute(0, 2, 1, 3, 4).reshape(b * t, x.shape[1], x.shape[3], x.shape[4])
+        posterior = self.first_stage_model.encode(frames)
+        n, shape = b * t, tuple(posterior.mean.shape[1:])
+        noise = torch.cat([torch.randn((min(encode_bs, n - k),) + shape) for k in range(0, n, encode_bs)], dim=0)
+        z = self.get_first_stage_encoding(posterior, noise=noise.to(device=posterior.mean.device, dtype=posterior.mean.dtype))
+        return z.reshape(b, t, *z.shape[1:]).permute(0, 2, 1, 3, 4)
+
+    @torch.no_grad()
+    def encode_first_stage(self, x):
+        raise NotImplementedError("encode_first_stage hands a posterior object to rearrange (autoencoder.py:95-100, "
+                                  "ddpm3d.py:817-818): the reference fails too — use encode_first_stage_2DAE(x, encode_bs)")
+
     @torch.no_grad()
     def decode(self, z, **kwargs):
         z = 1.0 / self.scale_factor * z - self.shift_factor
@@ -920,20 +967,32 @@ class DDIMSampler(object):
                verbose=True, schedule_verbose=False, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
                unconditional_conditioning=None, postprocess_fn=None, sample_noise=None, cond_fn=None, **kwargs):
         """ddim.py:56-132 -> (samples, intermediates)."""
-        if mask is not None or quantize_x0 or noise_dropout or score_corrector is not None or postprocess_fn is not None \
+        if quantize_x0 or noise_dropout or score_corrector is not None or postprocess_fn is not None \
                 or cond_fn is not None or kwargs.get("uc_type") is not None:
-            raise NotImplementedError("mask blending / quantisation / noise dropout / score correctors are not on the hot path")
+            raise NotImplementedError("quantisation / noise dropout / score correctors are not on the hot path")
+        size = (batch_size, *shape)
+        assert len(size) == 5
+        if mask is not None:
+            # mask blending (ddim.py:188-195): img = q_sample(x0, step - 1) * mask + (1 - mask) * img after every step.  The mask is
+            # 5-D and broadcastable to the latent, [b|1, c|1, t|1, h|1, w|1], any float values; a mask of another rank would
+            # broadcast from the right (a 1-D one along the width) and is refused
+            if not isinstance(mask, torch.Tensor) or mask.dim() != 5:
+                raise NotImplementedError("mask blending needs a 5-D mask [b|1, c|1, t|1, h|1, w|1]; masks of another rank are not on the hot path")
+            if x0 is None:
+                raise ValueError("mask needs x0: the known latent that the masked region is held to")
+            if any(m not in (1, s) for m, s in zip(mask.shape, size)):
+                raise ValueError(f"mask {tuple(mask.shape)} does not broadcast to the latent {size}")
+            if not isinstance(x0, torch.Tensor) or tuple(x0.shape) != size:
+                raise ValueError(f"x0 must have the latent's shape {size}, got {tuple(getattr(x0, 'shape', ()))}")
         # features_adapter: forwarded to every apply_model call (ddim.py:221-229 passes its **kwargs on for both evaluations of a
         # guided step); temporal_length: accepted and ignored, as in the reference (ddim.py:80: the shape carries the length)
         if kwargs.get("conditional_guidance_scale_temporal") is not None:
             raise NotImplementedError("conditional_guidance_scale_temporal (temporal guidance) is not on the hot path")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=schedule_verbose)
-        size = (batch_size, *shape)
-        assert len(size) == 5
         return self.ddim_sampling(conditioning, size, callback=callback, img_callback=img_callback, temperature=temperature,
                                   x_T=x_T, log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, sample_noise=sample_noise, verbose=verbose,
-                                  features_adapter=kwargs.get("features_adapter"))
+                                  features_adapter=kwargs.get("features_adapter"), mask=mask, x0=x0 if mask is not None else None)
 
     @staticmethod
     def _ctx(c):
@@ -946,8 +1005,9 @@ class DDIMSampler(object):
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100, temperature=1.0,
                       unconditional_guidance_scale=1.0, unconditional_conditioning=None, sample_noise=None, verbose=True,
-                      features_adapter=None, **kw):
-        """ddim.py:135-206, p_sample_ddim :209-279 fused into one kernel launch per step (T2V_OP_DDIM_STEP mode 1)."""
+                      features_adapter=None, mask=None, x0=None, **kw):
+        """ddim.py:135-206, p_sample_ddim :209-279 fused into one kernel launch per step (T2V_OP_DDIM_STEP mode 1).  With a mask
+        (5-D, broadcastable to `shape`; x0 of `shape`) the blend of :188-195 rides in the same launch (i[7] = 1)."""
         from . import samplers as S
         device = self.model.betas.device
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
@@ -966,6 +1026,10 @@ class DDIMSampler(object):
         extra = {} if features_adapter is None else {"features_adapter": features_adapter}     # the same list object every step: converted once
         nb, C = img.shape[0], img.shape[1]          # nb videos per batch (sample_text2video's batch_size)
         f32 = torch.float32
+        if mask is not None:                        # expanded once per call: the kernel reads x0, mask and q-noise dense, like x
+            known = x0.to(device=device, dtype=f32).contiguous()
+            mask_d = mask.to(device=device, dtype=f32).expand(img.shape).contiguous()
+            q_a, q_s = self.model.sqrt_alphas_cumprod.detach().cpu(), self.model.sqrt_one_minus_alphas_cumprod.detach().cpu()
         S.state.sampling_steps = total_steps
         iterator = np.flip(timesteps)
         if verbose and S.tqdm is not None:
@@ -1004,7 +1068,15 @@ class DDIMSampler(object):
                         S._lincomb(px0, [(ia, img), (-coef[0] * g * ia, eps[0:nb]), (-coef[0] * (1.0 - g) * ia, eps[nb:2 * nb])])
                     else:
                         S._lincomb(px0, [(ia, img), (-coef[0] * ia, eps[0:nb])])
-                S._ddim_update(nxt, img, eps, noise, coef, C if guided else 0, mode=1)
+                if mask is None:
+                    S._ddim_update(nxt, img, eps, noise, coef, C if guided else 0, mode=1)
+                else:
+                    # q_sample(x0, step - 1) (ddim.py:193-194): its noise is `randn_like(x0)` on the default generator, drawn after
+                    # the UNet forward — from the CPU generator here, the same stream on any device
+                    qnoise = torch.randn(tuple(known.shape)).to(device)
+                    tq = int(step) - 1
+                    qcoef = (float(q_a[tq]), float(q_s[tq]))
+                    S._ddim_update_blend(nxt, img, eps, noise, coef, C if guided else 0, known, mask_d, qnoise, qcoef)
                 img, nxt = nxt, img
                 if callback:
                     callback(i)
@@ -1048,10 +1120,16 @@ def torch_to_np(x):
 @torch.no_grad()
 def sample_text2video(model, prompt, n_prompt, n_samples, batch_size, sample_type="ddim", sampler=None, ddim_steps=50, eta=1.0,
                       cfg_scale=7.5, decode_frame_bs=1, ddp=False, all_gather=True, batch_progress=True,
-                      show_denoising_progress=False, num_frames=None):
-    """-> np.uint8 [n, T, H, W, 3].  `decode_frame_bs=None` decodes all frames in one VAE launch sequence."""
+                      show_denoising_progress=False, num_frames=None, *, mask=None, x0=None, init_video=None):
+    """-> np.uint8 [n, T, H, W, 3].  `decode_frame_bs=None` decodes all frames in one VAE launch sequence.
+    mask / x0 (not in the reference's signature): held regions, as `DDIMSampler.sample` takes them, applied to every batch;
+    init_video [b, 3, t, H, W] in [-1, 1] is encoded with `encode_first_stage_2DAE` and stands in for x0."""
     if sample_type != "ddim" or sampler is None:
         raise NotImplementedError("only the DDIM path of the webui (process_videocrafter.py:57-79) is built")
+    if init_video is not None:
+        if x0 is not None:
+            raise ValueError("give x0 (a latent) or init_video (frames to encode), not both")
+        x0 = model.encode_first_stage_2DAE(init_video.to(model.device))
     cond = get_conditions(prompt, model, batch_size)
     uncond = get_conditions(n_prompt, model, batch_size) if cfg_scale != 1.0 else None
     videos = []
@@ -1059,7 +1137,7 @@ def sample_text2video(model, prompt, n_prompt, n_samples, batch_size, sample_typ
         noise_shape = make_model_input_shape(model, batch_size, T=num_frames)
         latent, _ = sampler.sample(S=ddim_steps, conditioning=cond, batch_size=noise_shape[0], shape=noise_shape[1:],
                                    verbose=show_denoising_progress, unconditional_guidance_scale=cfg_scale,
-                                   unconditional_conditioning=uncond, eta=eta)
+                                   unconditional_conditioning=uncond, eta=eta, mask=mask, x0=x0)
         samples = model.decode_first_stage(latent, decode_bs=decode_frame_bs, return_cpu=False)
         videos.append(torch_to_np(samples).numpy())
     out = np.concatenate(videos, axis=0)
