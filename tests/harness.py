@@ -47,10 +47,11 @@ def read(arena_or_interp, buf: Buf) -> torch.Tensor:
     return it.mat(buf.ref, buf.rows, buf.cols, buf.ld, TD[buf.dtype], {}).clone()
 
 
-def run_both(prog: Program, weights_cpu: dict, ext_cpu: dict, init):
+def run_both(prog: Program, weights_cpu: dict, ext_cpu: dict, init, interp=Interp):
     """Run `prog` in the CPU interpreter and on the GPU from identical initial arena contents.
-    Returns (interp_after, gpu_arena_as_interp_view, ext_gpu_back_on_cpu)."""
-    it = Interp(prog, weights_cpu, poison=False)
+    Returns (interp_after, gpu_arena_as_interp_view, ext_gpu_back_on_cpu).  interp: the interpreter class (interp_adapter.AdapterInterp
+    for programs with the adapter's records)."""
+    it = interp(prog, weights_cpu, poison=False)
     init(it)
     arena0 = it.arena.clone()
     ext_ref = {k: v.clone() for k, v in ext_cpu.items()}
@@ -63,7 +64,7 @@ def run_both(prog: Program, weights_cpu: dict, ext_cpu: dict, init):
     bound = BoundProgram(prog, arena_gpu.data_ptr(), {k: v.data_ptr() for k, v in w_gpu.items()})
     bound.run({k: v.data_ptr() for k, v in ext_gpu.items()}, torch.cuda.current_stream(dev).cuda_stream)
     torch.cuda.synchronize()
-    got = Interp(prog, weights_cpu, poison=False)
+    got = interp(prog, weights_cpu, poison=False)
     got.arena = arena_gpu.cpu()
     return it, got, ext_ref, {k: v.cpu() for k, v in ext_gpu.items()}
 

@@ -374,13 +374,14 @@ class Interp:
     def _op10(self, op, ext):
         C, inner, guided, edt, xdt = op.i[0:5]
         cps = op.i[6] if op.i[6] > 0 else C
-        a_recip, a_recipm1, sqrt_aprev, dir_coef, sigma, gscale = op.f[0:6]
+        a_recip, a_recipm1, sqrt_aprev, dir_coef, sigma, gscale = [torch.tensor(v, dtype=torch.float32) for v in op.f[0:6]]
         xt = self.view(op.p[0], (C, inner), (inner, 1), _TD[xdt], ext).float()
-        e = self.view(op.p[1], (2, C, inner), (C * inner, inner, 1), _TD[edt], ext).float()
-        y, u = e[0], e[1]
+        y = self.view(op.p[1], (C, inner), (inner, 1), _TD[edt], ext).float()
         o = y.clone()
         g = (torch.arange(C) % cps) < guided
-        o[g] = u[g] + gscale * (y[g] - u[g])
+        if bool(g.any()):                                # the unconditional half exists for guided steps only
+            u = self.view(op.p[1], (2, C, inner), (C * inner, inner, 1), _TD[edt], ext)[1].float()
+            o[g] = u[g] + gscale * (y[g] - u[g])
         if op.i[5] == 0:
             x0 = a_recip * xt - a_recipm1 * o
             eps = (a_recip * xt - x0) / a_recipm1
@@ -388,8 +389,14 @@ class Interp:
         else:
             x0 = (xt - a_recip * o) / a_recipm1
             xn = sqrt_aprev * x0 + dir_coef * o
-        if op.p[2].space != "null" and sigma != 0.0 and ext.get(L.EXT_NOISE) is not None:
+        if op.p[2].space != "null" and float(sigma) != 0.0 and ext.get(op.p[2].off) is not None:
             xn = xn + sigma * self.view(op.p[2], (C, inner), (inner, 1), torch.float32, ext)
+        if op.i[7]:                                      # known-region blend of a masked LVDM step
+            known = torch.tensor(op.f[6], dtype=torch.float32) * self.view(op.p[4], (C, inner), (inner, 1), torch.float32, ext)
+            if op.p[6].space != "null" and op.f[7] != 0.0:
+                known = known + torch.tensor(op.f[7], dtype=torch.float32) * self.view(op.p[6], (C, inner), (inner, 1), torch.float32, ext)
+            m = self.view(op.p[5], (C, inner), (inner, 1), torch.float32, ext)
+            xn = known * m + (1.0 - m) * xn
         out = self.view(op.p[3], (C, inner), (inner, 1), _TD[xdt], ext)
         out.copy_(xn.to(out.dtype))
 
@@ -444,9 +451,12 @@ class Interp:
         u8 = v.to(torch.uint8).permute(2, 3, 0, 4, 1).reshape(Fr, H, NI * W, C)
         if bgr:
             u8 = u8.flip(-1)
-        out = ext[op.p[1].off] if op.p[1].space == "ext" else None
-        assert out is not None and out.dtype == torch.uint8
-        out.view(Fr, H, NI * W, C).copy_(u8)
+        if op.p[1].space == "ext":
+            out = ext[op.p[1].off]
+            assert out.dtype == torch.uint8
+            out.view(Fr, H, NI * W, C).copy_(u8)
+        else:
+            self.view(op.p[1], (Fr * H * NI * W * C,), (1,), torch.uint8, ext).copy_(u8.reshape(-1))
 
     def _op11(self, op, ext):
         nbytes = (op.i[0] & 0xFFFFFFFF) | (op.i[1] << 32)
