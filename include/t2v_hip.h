@@ -31,6 +31,8 @@ extern "C" {
                                (ReLU), GEMM i[30] (residual row wrap for every gather mode, split-K allowed), T2V_EXT_ADAPTER (feature slots);
                                still 11: DDIM_STEP i[7] / p[4..6] / f[6..7] (mask blend of a VideoCrafter step) — additive on fields that every earlier
                                record leaves zero, so the version does not move;
+                               still 11: T2V_OP_EMPHASIS (a new kind: no existing record changes, and a library without it refuses the record as an unknown op kind) and
+                               ATTENTION i[19..21] / p[4..5] (a second role; additive on fields every earlier record leaves zero);
                                10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
                                optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
                                9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
@@ -85,7 +87,8 @@ enum t2v_op_kind {
   T2V_OP_RESAMPLE = 21,      /* one separable pass of a table-driven uint8 image resize (Pillow's 8-bit resampler, bit-exact); optional float token output */
   T2V_OP_DEPTH_TOKENS = 22,  /* depth frames [n,1,H,W] -> PixelUnshuffle(8) channels-last fp16 tokens, optional per-frame min-max normalisation (T2I-Adapter entry) */
   T2V_OP_AVGPOOL2 = 23,      /* 2x2 / stride 2 average pooling of channels-last fp32 tokens (mean in fp32), fp32 and / or fp16 out */
-  T2V_OP_KIND_MAX = 24
+  T2V_OP_EMPHASIS = 24,      /* prompt emphasis of a batch of text-encoder chunks: per-token multipliers, then the batch mean restored (fp64 sums, one workgroup) */
+  T2V_OP_KIND_MAX = 25
 };
 
 /* GEMM gather modes: how row m / reduction index k of the A operand are addressed          */
@@ -221,6 +224,11 @@ enum t2v_gather {
  *      ABI 7, optional: p 6 = scratch fp16 [batch_outer * batch_inner * heads * 64, i[17]] with i[17] = nk rounded up to a multiple of 64
  *      (head_dim 64, not causal): V is transposed into it once per launch and the K / V^T tiles are staged by LDS-DMA (same bits as without
  *      the scratch; pays from ~512 keys); i[18] = waves per 64-key tile (0 = 8 | 4 | 8)
+ *      Second role, optional (all zero = none): i[19] = alt_from (0 < alt_from < batch_outer), i[20] = its key count, i[21] = its K / V stride
+ *      per outer sample (elements), p[4] / p[5] = its K / V bases — outer samples s >= alt_from attend to i[20] keys at
+ *      p[4] / p[5] + (s - alt_from) * i[21] + inner * i[10] (sequence stride i[8] as the first role); everything else as for the other
+ *      samples, in the same launch (the cond | uncond pair of a guided step whose prompts have different lengths).  Not for causal
+ *      launches, the p[6] scratch path or RELPOS_ATTN: refused at plan creation.
  * RELPOS_ATTN: i: as ATTENTION with nk == frames of the clip (<= 32 for i[17] = 0 | 1 | 2; <= T2V_RELPOS_MAX_FRAMES for i[17] = 3),
  *      14 head_dim (multiple of 8, <= 160; 40 | 64 | 80 | 160 for i[17] = 3),
  *      15 max relative position R, 16 q_off: the nq queries are frames [q_off, q_off + nq) of the clip (nq == nk, q_off == 0
@@ -316,6 +324,11 @@ enum t2v_gather {
  *      in[2y+1, 2x+1])[c] in fp32, Ho = H / 2, Wo = W / 2 (a last odd row / column is dropped, as torch does)
  *      i: 0 n images, 1 H, 2 W, 3 C (% 4 == 0), 4 ld_in, 5 ld of the fp32 output, 6 ld of the fp16 output;
  *      p: 0 in fp32, 1 out fp32 (optional), 2 out fp16 (optional; the fp16 rounding of the fp32 mean) — at least one
+ * EMPHASIS: prompt emphasis of one batch of text-encoder chunks with the mean restored (clip_hardcode.py:413-420):
+ *      out[r, c] = fp32(fp32(z[r, c] * m[r]) * ratio),  ratio = fp32(sum z / sum (z * m)), both sums over ALL rows and columns (the reference's
+ *      z.mean() of the batch), accumulated in fp64 in a fixed order by ONE workgroup: results repeat bit for bit, and with every m = 1 the
+ *      ratio is exactly 1.  A zero sum of z * m is not special-cased (IEEE inf / NaN, as the reference).
+ *      i: 0 rows (B * L), 1 W (% 4 == 0), 2 ld of z, 3 ld of out (% 4 == 0), 4 dtype of z;  p: 0 z, 1 m fp32 [rows], 2 out fp32 (16-byte aligned)
  */
 typedef struct t2v_op {
   int32_t kind;

@@ -42,6 +42,7 @@ OP_TO_UINT8, OP_ALLGATHER, OP_HALO_EXCHANGE = 15, 16, 17
 OP_RESHARD_ROWS, OP_ALLTOALL, OP_STATS_HALO = 18, 19, 20
 OP_RESAMPLE = 21
 OP_DEPTH_TOKENS, OP_AVGPOOL2 = 22, 23
+OP_EMPHASIS = 24
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2     # GEMM i[18]
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_TCONV3, GATHER_CONV3X3_C8 = 0, 1, 2, 3
 EPI_NONE, EPI_GEGLU, EPI_TATTN, EPI_STATS, EPI_GN, EPI_XATTN = 0, 1, 2, 3, 4, 5

@@ -46,6 +46,11 @@ struct AttnParams {
   float scale_log2;
   int causal;   // 1: key s is visible to query t only if s <= t (CLIP text towers)
   int lo_off;   // != 0: also store fp16(o - float(fp16(o))) at o + lo_off (elements): rows [hi | lo] for a K-doubled to_out (precise_operands)
+  // second role (attn_kernel only; alt_from == 0: none): outer samples >= alt_from attend to nk2 keys at k2 / v2, sample stride sk2_out —
+  // the cond | uncond pair of a guided step whose prompts have different lengths, in one launch
+  int alt_from, nk2;
+  long sk2_out;
+  const f16* k2; const f16* v2;
 };
 
 // ---- the shared flash-attention core -----------------------------------------------------------------------------------------------
@@ -227,8 +232,12 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
   const int frow = lane & 31, fhalf = lane >> 5;
 
   const f16* qb = p.q + bo * p.sq_out + bi * p.sq_in + head * D;
-  const f16* kb = p.k + bo * p.sk_out + bi * p.sk_in + head * D;
-  const f16* vb = p.v + bo * p.sk_out + bi * p.sk_in + head * D;
+  // the sample's role (workgroup-uniform): its own key count and K / V rows; everything below works on `nk`
+  const bool alt = p.alt_from > 0 && bo >= p.alt_from;
+  const int nk = alt ? p.nk2 : p.nk;
+  const long kv_off = (alt ? (bo - p.alt_from) * p.sk2_out : bo * p.sk_out) + bi * p.sk_in + head * D;
+  const f16* kb = (alt ? p.k2 : p.k) + kv_off;
+  const f16* vb = (alt ? p.v2 : p.v) + kv_off;
   f16* ob = p.o + bo * p.so_out + bi * p.so_in + head * D;
 
   const int qrow = q0 + frow;
@@ -242,26 +251,26 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
     for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
   // last visible key of this lane's query; key 0 is visible to every query, so m_run is finite after the first tile
-  const int key_end = p.causal ? min(p.nk, qrow + 1) : p.nk;
+  const int key_end = p.causal ? min(nk, qrow + 1) : nk;
 
-  for (int kt0 = 0; kt0 < p.nk; kt0 += KT) {
+  for (int kt0 = 0; kt0 < nk; kt0 += KT) {
     __syncthreads();  // previous tile fully consumed
     // straight global -> LDS (few registers: the single-wave variants live on occupancy).  K tile: KT rows x KCH chunks of 16 B
     for (int u = tid; u < KT * KCH; u += NT) {
       const int row = u / KCH, c = u - row * KCH;
       const int key = kt0 + row;
       f16x8 val;
-      if (key < p.nk && c * 8 < D)
+      if (key < nk && c * 8 < D)
         val = *reinterpret_cast<const f16x8*>(kb + (long)key * p.sk_seq + c * 8);
       else
         for (int e = 0; e < 8; ++e) val[e] = (f16)0.f;
       *reinterpret_cast<f16x8*>(k_lds + row * K_ROW + (c << 4)) = val;
     }
-    stage_vt<D, KT, NT>(vt_lds, VT_ROW, vb, p.sk_seq, kt0, p.nk, tid);
+    stage_vt<D, KT, NT>(vt_lds, VT_ROW, vb, p.sk_seq, kt0, nk, tid);
     __syncthreads();
 
     // ---- S^T = K Q^T : NKT 32-key tiles --------------------------------------------
-    const bool t1_live = (kt0 + 32) < p.nk;   // wave-uniform
+    const bool t1_live = (kt0 + 32) < nk;   // wave-uniform
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     f32x16 s[NKT];
 #pragma unroll
@@ -276,7 +285,7 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
       }
     }
     // ---- online softmax for this lane's query; keys are masked only in tiles that need it (ragged end, causal diagonal)
-    if (kt0 + KT > p.nk || (p.causal && kt0 + KT - 1 > q0)) mask_keys(s, kt0, key_end, fhalf);     // wave-uniform
+    if (kt0 + KT > nk || (p.causal && kt0 + KT - 1 > q0)) mask_keys(s, kt0, key_end, fhalf);     // wave-uniform
     online_softmax_step(s, p.scale_log2, m_run, l_run, oacc);
 
     // ---- O^T += V^T P^T -----------------------------------------------------------
@@ -1214,11 +1223,12 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* in, f16*
 }
 
 // attn_kernel for head_dim D: one wave per (batch, head) for <= 32 queries (with the 32-key tile if the keys fit one), else 4 waves / 128 queries
+// (two roles: the tile of the larger key count serves both)
 template <int D>
 void launch_attn(const AttnParams& p, int nbatch, hipStream_t s) {
   const bool small = p.nq <= 32;
   const dim3 g1(1, p.heads, nbatch), g4((p.nq + 127) / 128, p.heads, nbatch);
-  if (small && p.nk <= 32) hipLaunchKernelGGL((attn_kernel<1, D, 32>), g1, dim3(64), 0, s, p);
+  if (small && (p.nk > p.nk2 ? p.nk : p.nk2) <= 32) hipLaunchKernelGGL((attn_kernel<1, D, 32>), g1, dim3(64), 0, s, p);
   else if (small) hipLaunchKernelGGL((attn_kernel<1, D, 64>), g1, dim3(64), 0, s, p);
   else hipLaunchKernelGGL((attn_kernel<4, D, 64>), g4, dim3(256), 0, s, p);
 }
@@ -1240,6 +1250,11 @@ hipError_t t2v_launch_attention(const t2v_op& op, hipStream_t s) {
   p.lo_off = op.i[16];
   if (p.lo_off < 0) return hipErrorInvalidValue;
   if (p.nq <= 0 || p.nk <= 0 || !(op.f[0] > 0.f)) return hipErrorInvalidValue;
+  p.alt_from = op.i[19]; p.nk2 = p.alt_from > 0 ? op.i[20] : 0; p.sk2_out = op.i[21];
+  p.k2 = reinterpret_cast<const f16*>(op.p[4]);
+  p.v2 = reinterpret_cast<const f16*>(op.p[5]);
+  if (p.alt_from != 0 && (p.alt_from < 0 || p.alt_from >= p.b_outer || p.nk2 <= 0 || p.sk2_out < 0 || p.k2 == nullptr || p.v2 == nullptr || p.causal || op.p[6] != 0))
+    return hipErrorInvalidValue;
   const int nbatch = p.b_outer * p.b_inner;
   const int hd = op.i[14] > 0 ? op.i[14] : 64;
   if (op.p[6] != 0) {

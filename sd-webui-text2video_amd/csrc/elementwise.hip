@@ -302,6 +302,55 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float* in, float* o
   }
 }
 
+// Prompt emphasis with mean restoration (clip_hardcode.py:413-420): out = (z * m[row]) * (sum z / sum (z * m[row])), both sums over the WHOLE
+// tensor (the reference's z.mean() of a batch of chunks).  ONE workgroup of 1024 threads, two passes over z: every thread adds its
+// elements (index = thread + k * 1024 groups of 4, ascending k) into fp64 partials, the partials meet in a fixed LDS tree — the same
+// order on every run, so results repeat bit for bit; with every multiplier 1.0 the two sums are the same sequence of additions and
+// the ratio is exactly 1.  A zero sum of z * m gives what IEEE gives (inf / NaN), as the reference.
+template <typename TZ>
+__global__ __launch_bounds__(1024) void emphasis_kernel(const TZ* z, const float* mult, float* out, int rows, int W, int ldz, int ldo) {
+  __shared__ double red[2][1024];
+  const int cv = W >> 2, t = threadIdx.x;
+  const long total = (long)rows * cv;
+  double s_z = 0.0, s_zm = 0.0;
+  for (long u = t; u < total; u += 1024) {
+    const long r = u / cv;
+    const int c = (int)(u - r * cv) * 4;
+    const TZ* s = z + r * ldz + c;
+    const double m = (double)mult[r];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double v = (double)(float)s[e];
+      s_z += v;
+      s_zm += v * m;
+    }
+  }
+  red[0][t] = s_z;
+  red[1][t] = s_zm;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if (t < w) {
+      red[0][t] += red[0][t + w];
+      red[1][t] += red[1][t + w];
+    }
+    __syncthreads();
+  }
+  const float ratio = (float)(red[0][0] / red[1][0]);
+  for (long u = t; u < total; u += 1024) {
+    const long r = u / cv;
+    const int c = (int)(u - r * cv) * 4;
+    const TZ* s = z + r * ldz + c;
+    const float m = mult[r];
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float zm = (float)s[e] * m;
+      v[e] = zm * ratio;
+    }
+    *reinterpret_cast<f32x4*>(out + r * ldo + c) = v;
+  }
+}
+
 // tensor2vid (t2v_pipeline.py:447-460): video[i,c,f,y,x] -> uint8 out[f, y, i*W + x, c]: v*0.5 + 0.5 (two roundings, as
 // mul_ / add_), clamp to [0,1], *255, TRUNCATED like `(image.numpy()*255).astype('uint8')`.  HALF: the reference's
 // 'GPU (half precision)' VAE hands tensor2vid an fp16 video, so every intermediate is rounded to fp16 (the input too
@@ -647,6 +696,18 @@ hipError_t t2v_launch_copy2d(const t2v_op& op, hipStream_t s) {
   else
     hipLaunchKernelGGL((copy2d_kernel<f16, float>), dim3(g), dim3(256), 0, s, reinterpret_cast<const f16*>(op.p[0]),
                        reinterpret_cast<float*>(op.p[1]), rows, cols, lds_, ldd, act, static_cast<f16*>(nullptr));
+  return hipGetLastError();
+}
+
+hipError_t t2v_launch_emphasis(const t2v_op& op, hipStream_t s) {
+  const int rows = op.i[0], W = op.i[1], ldz = op.i[2], ldo = op.i[3];
+  if (rows <= 0 || W <= 0 || W % 4 != 0 || ldz < W || ldo < W || ldo % 4 != 0) return hipErrorInvalidValue;
+  const float* mult = reinterpret_cast<const float*>(op.p[1]);
+  float* out = reinterpret_cast<float*>(op.p[2]);
+  if (op.i[4] == T2V_F32)
+    hipLaunchKernelGGL((emphasis_kernel<float>), dim3(1), dim3(1024), 0, s, reinterpret_cast<const float*>(op.p[0]), mult, out, rows, W, ldz, ldo);
+  else
+    hipLaunchKernelGGL((emphasis_kernel<f16>), dim3(1), dim3(1024), 0, s, reinterpret_cast<const f16*>(op.p[0]), mult, out, rows, W, ldz, ldo);
   return hipGetLastError();
 }
 

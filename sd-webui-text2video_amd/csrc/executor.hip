@@ -182,6 +182,11 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[3] == 0) return bad("null attention pointer");
       if (op.p[6] != 0 && (d != 64 || op.i[15] != 0 || op.i[17] < op.i[1] || op.i[17] % 64 != 0 || (op.i[18] != 0 && op.i[18] != 4 && op.i[18] != 8)))
         return bad("attention with a V^T scratch (p[6]): head_dim 64, not causal, i[17] = keys padded to a multiple of 64, i[18] = 0 | 4 | 8 waves");
+      if (op.i[19] != 0) {       // second role: outer samples >= i[19] have their own key count and K / V rows
+        if (op.i[19] < 0 || op.i[19] >= op.i[3] || op.i[20] <= 0 || op.i[21] < 0 || op.p[4] == 0 || op.p[5] == 0)
+          return bad("attention second role: 0 < i[19] < batch_outer, i[20] keys > 0, sample stride i[21] >= 0, K / V bases p[4], p[5]");
+        if (op.i[15] != 0 || op.p[6] != 0) return bad("attention second role: not for causal launches or the V^T scratch path");
+      }
       return 0;
     }
     case T2V_OP_RELPOS_ATTN:
@@ -198,6 +203,7 @@ int validate_op(const t2v_op& op, int idx) {
         if (op.i[k] < 0) return bad("negative attention stride");
       for (int k = 0; k < 6; ++k)
         if (op.p[k] == 0) return bad("null relative-position attention pointer");
+      if (op.i[19] != 0 || op.i[20] != 0 || op.i[21] != 0) return bad("relative-position attention takes no second role (i[19..21])");
       if (op.i[17] < 0 || op.i[17] > 3) return bad("relative-position attention kernel selector i[17]: 0 | 1 | 2 | 3");
       if (op.i[17] == 2 && (op.p[6] == 0 || op.p[7] == 0)) return bad("relative-position attention i[17] = 2 needs the packed fp16 tables p[6], p[7]");
       if (op.i[17] == 3 && (op.p[6] == 0 || op.p[7] == 0)) return bad("relative-position attention i[17] = 3 needs the packed fp16 tables p[6], p[7]");
@@ -280,6 +286,13 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.p[0] == 0 || (op.p[1] == 0 && op.p[2] == 0)) return bad("average pooling: an input and at least one output");
       if ((op.p[1] != 0 && (op.i[5] < op.i[3] || op.i[5] % 4 != 0)) || (op.p[2] != 0 && (op.i[6] < op.i[3] || op.i[6] % 4 != 0)))
         return bad("average pooling: output leading dimensions >= C and multiples of 4");
+      return 0;
+    case T2V_OP_EMPHASIS:
+      if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[1] % 4 != 0 || (long)op.i[0] * op.i[1] > (1L << 28)) return bad("emphasis: rows > 0, W a positive multiple of 4, rows * W <= 2^28");
+      if (op.i[2] < op.i[1] || op.i[3] < op.i[1] || op.i[3] % 4 != 0 || (op.i[4] != T2V_F16 && op.i[4] != T2V_F32))
+        return bad("emphasis: leading dimensions >= W (the output's a multiple of 4), input dtype fp16 | fp32");
+      if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0) return bad("null emphasis pointer");
+      if (op.p[2] >= T2V_EXT_SLOTS && op.p[2] % 16 != 0) return bad("emphasis: the output must be 16-byte aligned");
       return 0;
     case T2V_OP_ALLGATHER:
       if (op.i[2] < 1 || op.i[3] < 0 || op.i[3] >= op.i[2] || op.p[0] == 0) return bad("bad all-gather record");
@@ -401,6 +414,7 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
     case T2V_OP_RESHARD_ROWS: return t2v_launch_reshard_rows(op, s);
     case T2V_OP_DEPTH_TOKENS: return t2v_launch_depth_tokens(op, s);
     case T2V_OP_AVGPOOL2: return t2v_launch_avgpool2(op, s);
+    case T2V_OP_EMPHASIS: return t2v_launch_emphasis(op, s);
     case T2V_OP_MEMSET: {
       const size_t bytes = (size_t)(uint32_t)op.i[0] | ((size_t)(uint32_t)op.i[1] << 32);
       return hipMemsetAsync(reinterpret_cast<void*>(op.p[0]), 0, bytes, s);

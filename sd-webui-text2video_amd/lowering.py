@@ -52,8 +52,22 @@ class _UNetLowering(_Declarations):
         """F = frames held by THIS rank.  shard = TShardSpec: the clip's frames are split contiguously over the ranks
         of a T group (slices of ceil(F_total / R) frames, a shorter last one); temporal ops then exchange data
         (SURVEY §5.7): cross-frame GroupNorm -> all-gather of statistics partials, temporal conv -> +-1 frame halo,
-        temporal attention -> all-gather of K/V.  Everything else is frame-local."""
+        temporal attention -> all-gather of K/V.  Everything else is frame-local.
+        Lctx: the context length of every sample, or a pair (Lc, Lu) — the first B / 2 samples (cond) have Lc context rows each, the
+        others (uncond) Lu; the context then arrives packed, B / 2 * Lc rows followed by B / 2 * Lu rows.  Equal lengths are the int."""
         super().__init__(f"unet b{B} f{F} {H}x{W}", keep_taps)
+        self.Lpair: Optional[Tuple[int, int]] = None
+        if isinstance(Lctx, (tuple, list)):
+            Lc, Lu = (int(v) for v in Lctx)
+            if Lc == Lu:
+                Lctx = Lc
+            else:
+                if shard is not None and shard.size > 1:
+                    raise L.T2VError(f"a T-sharded forward takes one context length for cond and uncond, got {Lc} and {Lu}")
+                assert B % 2 == 0, "a pair of context lengths describes a [cond | uncond] batch"
+                self.Lpair, Lctx = (Lc, Lu), max(Lc, Lu)
+        # rows of the text context (and of its K / V projections) over the whole batch
+        self.ctx_rows = B * Lctx if self.Lpair is None else B // 2 * sum(self.Lpair)
         self.shard: Optional[TShardSpec] = shard if (shard is not None and shard.size > 1) else None
         if self.shard is not None:
             assert B == 1, "T-sharded forwards run one sample per rank (the CFG pair is split over ranks)"
@@ -300,6 +314,11 @@ class _UNetLowering(_Declarations):
             q = P.alloc(Mq, inner, "f16")
             P.gemm(attn + ".to_q", nrm, self.w_linear(attn + ".to_q"), inner, inner, q)
         if q is not None:
+            if self.Lpair is not None:
+                # cond | uncond with their own context lengths, still ONE launch: samples V .. B-1 read the rows behind the V * Lc cond rows
+                V, (Lc, Lu) = self.B // 2, self.Lpair
+                k2, v2 = kbuf.row_slice(V * Lc, V * (Lc + Lu)), vbuf.row_slice(V * Lc, V * (Lc + Lu))
+                attn_kw = dict(attn_kw, alt=(V, Lu, k2.ref, v2.ref, Lu * kv.ld))
             P.attention(attn, q.ref, kbuf.ref, vbuf.ref, a.ref, out_buf=a, nq=hw, nk=Lc, heads=heads,
                         b_outer=self.Bc, b_inner=F, q_strides=(inner, q_b_stride, hw * inner),
                         kv_strides=(kv.ld, Lc * kv.ld, 0), o_strides=(lo, F * hw * lo, hw * lo), scale=scale, **attn_kw)
@@ -395,7 +414,7 @@ class _UNetLowering(_Declarations):
         # (UNetSD.context_token).  Their buffer is allocated FIRST and freed last, so no other
         # buffer of the program can alias it between two runs.
         if n_kv:
-            self.kv_all = P.alloc(B * self.Lctx, n_kv, "f16")
+            self.kv_all = P.alloc(self.ctx_rows, n_kv, "f16")
         kept = self.prologue_alloc(st_prefixes) if n_kv else []
         te = P.alloc(B, dim, "f16")
         P.time_embed("time_embed.sincos", Ref("ext", L.EXT_T), self.time_freqs(), te)
@@ -413,8 +432,8 @@ class _UNetLowering(_Declarations):
         P.gemm("emb_layers.all", e_silu, w_emb, n_emb, emb, self.emb_out, bias=b_emb)
         P.free(e_silu)
 
-        ctx16 = P.alloc(B * self.Lctx, net.context_dim, "f16")
-        ctx_src = Buf(Ref("ext", L.EXT_CTX), B * self.Lctx, net.context_dim, net.context_dim, self.ctx_dt)
+        ctx16 = P.alloc(self.ctx_rows, net.context_dim, "f16")
+        ctx_src = Buf(Ref("ext", L.EXT_CTX), self.ctx_rows, net.context_dim, net.context_dim, self.ctx_dt)
         P.copy2d("context.cast", ctx_src, ctx16).meta["step_invariant"] = True
         if n_kv:
             w_kv = Ref("weight", 0, self.packer.add("kv_all:lin", "f16", lambda sd, ps=tuple(p for p, _ in st_prefixes): torch.cat(

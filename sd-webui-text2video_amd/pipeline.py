@@ -90,11 +90,13 @@ def create_infotext(vars_: dict) -> str:
 class TextToVideoSynthesis(object):
     def __init__(self, model_dir: Optional[str] = None, *, sd_model: Optional[UNetSD] = None,
                  autoencoder: Optional[AutoencoderKL] = None, clip_encoder=None, betas=None,
-                 device=None, tokenizer=None):
+                 device=None, tokenizer=None, enable_emphasis=None, comma_padding_backtrack=None):
         """Either `model_dir` (configuration.json + checkpoints, as t2v_pipeline.py:45-146) or
         ready-made `sd_model` / `autoencoder` modules.  With a `model_dir` and no `clip_encoder`, the OpenCLIP text
         tower is built from `ckpt_clip` (t2v_pipeline.py:137-141) and runs on the GPU (text_encoder.py); `tokenizer` =
-        open_clip's `_tokenizer` (BPE vocabulary; not part of this package)."""
+        open_clip's `_tokenizer` (BPE vocabulary; not part of this package).  `enable_emphasis` / `comma_padding_backtrack`: the two
+        webui options of the reference's prompt syntax (`opts.enable_emphasis`, `opts.comma_padding_backtrack`; clip_hardcode.py:153,203),
+        handed to the text encoder (None = leave the encoder's own setting: off / 0 for the one built here)."""
         self.model_dir = model_dir
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self.keep_in_vram = "All"
@@ -121,6 +123,7 @@ class TextToVideoSynthesis(object):
                 from .text_encoder import FrozenOpenCLIPEmbedder
                 self.clip_encoder = FrozenOpenCLIPEmbedder(version=clip_path, device=self.device, layer="penultimate",
                                                            tokenizer=tokenizer)
+        self.set_prompt_options(enable_emphasis, comma_padding_backtrack)
         if betas is None:
             betas = beta_schedule("linear_sd", 1000, init_beta=0.00085, last_beta=0.0120)
         self.sd_model = sd_model
@@ -131,7 +134,15 @@ class TextToVideoSynthesis(object):
         self.noise_gen = torch.Generator(device="cpu")
         self.last_tensor = None
 
-    # ---- conditioning (out of scope: delegated) --------------------------------------------------
+    # ---- conditioning ----------------------------------------------------------------------------
+    def set_prompt_options(self, enable_emphasis=None, comma_padding_backtrack=None):
+        """Hand the prompt-syntax options to a text encoder that takes them (text_encoder.FrozenOpenCLIPEmbedder); None = unchanged."""
+        enc = self.clip_encoder
+        if enable_emphasis is not None and hasattr(enc, "enable_emphasis"):
+            enc.enable_emphasis = bool(enable_emphasis)
+        if comma_padding_backtrack is not None and hasattr(enc, "comma_padding_backtrack"):
+            enc.comma_padding_backtrack = int(comma_padding_backtrack)
+
     def preprocess(self, prompt, n_prompt, steps):
         if self.clip_encoder is None:
             raise RuntimeError("no text encoder attached: pass clip_encoder=... (the reference's "
@@ -312,6 +323,7 @@ def process_modelscope(args_dict: dict, extra_args=None):
     URL per video, made from the mp4 that ffmpeg stitched (:248-266).  Here:
       args_dict = {model_dir | pipe, prompt, n_prompt, steps, frames, seed, cfg_scale, width, height, eta, sampler,
                    batch_count, clip_encoder | (cond, uncond), stitch,
+                   enable_emphasis, comma_padding_backtrack,                  # webui's opts of the prompt syntax (clip_hardcode.py:153,203)
                    do_vid2vid, vid2vid_frames, strength,                      # :80-147
                    inpainting_frames, inpainting_image, inpainting_weights}   # :170-217
     * `stitch(frames_bgr, infotext) -> bytes` (the ffmpeg stage, out of scope — e.g. the reference's own
@@ -338,6 +350,8 @@ def process_modelscope(args_dict: dict, extra_args=None):
         pipe = a.pipe
     elif pipe is None:
         pipe = TextToVideoSynthesis(a.model_dir, clip_encoder=getattr(a, "clip_encoder", None))
+    if hasattr(pipe, "set_prompt_options"):
+        pipe.set_prompt_options(getattr(a, "enable_emphasis", None), getattr(a, "comma_padding_backtrack", None))
     width, height = getattr(a, "width", 256), getattr(a, "height", 256)
     common = dict(frames=a.frames, scale=a.cfg_scale, width=width, height=height, eta=getattr(a, "eta", 0.0),
                   sampler=getattr(a, "sampler", available_samplers[0].name))

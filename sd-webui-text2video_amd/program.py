@@ -949,13 +949,15 @@ class Program:
                   rel_k: Optional[Ref] = None, rel_v: Optional[Ref] = None, max_rel: int = 0, causal: bool = False,
                   q_offset: int = 0, relpos_mfma: Optional[int] = None, lo_off: int = 0,
                   rel_k16: Optional[Ref] = None, rel_vT16: Optional[Ref] = None, rel_k_long: Optional[Ref] = None,
-                  rel_vT_long: Optional[Ref] = None, vt_scratch: Optional[Buf] = None, waves: int = 0) -> Op:
+                  rel_vT_long: Optional[Ref] = None, vt_scratch: Optional[Buf] = None, waves: int = 0, alt: Optional[tuple] = None) -> Op:
         """softmax(q k^T scale) v over strided (sequence, outer, inner) batches.  With rel_k / rel_v (fp32
         [2*max_rel+1, head_dim] tables) the LVDM relative-position temporal attention op is emitted instead.
         lo_off (elements): also store the low-order fp16 image of every output value at o + lo_off (rows [hi | lo] for a K-doubled
         output projection, precise_operands).
         rel_k_long / rel_vT_long: the same tables packed for the kernel of clips of any length (packing.relpos_table_long); required
-        for clips of more than 32 frames, which only that kernel runs."""
+        for clips of more than 32 frames, which only that kernel runs.
+        alt = (alt_from, nk2, k2, v2, sample_stride2): a second role in the same launch — outer samples >= alt_from attend to nk2 keys at
+        k2 / v2 (outer sample s at + (s - alt_from) * sample_stride2 elements; sequence and inner strides as the first role)."""
         assert head_dim in (40, 64, 80, 160) or rel_k is not None
         op = Op(L.OP_ATTENTION if rel_k is None else L.OP_RELPOS_ATTN, name)
         op.i[0:5] = [nq, nk, heads, b_outer, b_inner]
@@ -1003,6 +1005,11 @@ class Program:
                 assert head_dim == 64 and not causal and vt_scratch.dtype == "f16" and vt_scratch.ld == n_pad
                 assert vt_scratch.rows >= b_outer * b_inner * heads * 64 and waves in (0, 4, 8)
                 op.p[6], op.i[17], op.i[18] = vt_scratch.ref, n_pad, waves
+        if alt is not None:
+            alt_from, nk2, k2, v2, stride2 = alt
+            assert rel_k is None and not causal and vt_scratch is None and 0 < alt_from < b_outer and nk2 > 0 and 0 <= stride2 < 2 ** 31
+            op.i[19], op.i[20], op.i[21] = alt_from, nk2, stride2
+            op.p[4], op.p[5] = k2, v2
         op.i[5:8] = list(q_strides)
         op.i[8:11] = list(kv_strides)
         op.i[11:14] = list(o_strides)
@@ -1011,6 +1018,8 @@ class Program:
         op.f[0] = scale
         op.p[0:4] = [q, k, v, o]
         op.flops = 4.0 * nq * nk * head_dim * heads * b_outer * b_inner
+        if alt is not None:
+            op.flops = 4.0 * nq * head_dim * heads * b_inner * (nk * alt[0] + alt[1] * (b_outer - alt[0]))
         op.out = out_buf
         return self._emit(op)
 
@@ -1156,6 +1165,15 @@ class Program:
         op = Op(L.OP_EMBED_ROWS, name)
         op.i[0:5] = [out.rows, out.cols, L_pos, vocab, _DT[table_dtype]]
         op.p[0:4] = [ids, table, pos, out.ref]
+        op.out = out
+        return self._emit(op)
+
+    def emphasis(self, name: str, z: Buf, mult: Ref, out: Buf) -> Op:
+        """T2V_OP_EMPHASIS: out = z * mult[row] * (sum z / sum (z * mult[row])) over the whole [rows, W] batch (fp32 out; mult fp32 [rows])."""
+        assert out.dtype == "f32" and (z.rows, z.cols) == (out.rows, out.cols) and z.cols % 4 == 0 and out.ld % 4 == 0
+        op = Op(L.OP_EMPHASIS, name)
+        op.i[0:5] = [z.rows, z.cols, z.ld, out.ld, _DT[z.dtype]]
+        op.p[0:3] = [z.ref, mult, out.ref]
         op.out = out
         return self._emit(op)
 

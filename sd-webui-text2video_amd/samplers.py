@@ -233,9 +233,10 @@ class GaussianDiffusion(object):
                         # swap them between steps, reconstruct_cond_batch); x_t is read twice by the entry op
                         ident = (run_nonce, id(c0), c0._version, id(uc0), uc0._version, Bx)
                         if pair_key != ident:
-                            pair_key, pair_ctx, pair_refs = ident, torch.cat([c, uc], dim=0), (c0, uc0)
+                            # (contexts of different lengths go in as the pair: one program with two key counts, forward_cfg_pair)
+                            pair_key, pair_ctx, pair_refs = ident, (c, uc) if c.shape[1] != uc.shape[1] else torch.cat([c, uc], dim=0), (c0, uc0)
                         eps = model.forward_cfg_pair(xt, tt_all[step], pair_ctx, context_token=pair_key, single_t=True)   # (one timestep per step)
-                    elif getattr(model, "supports_cfg_batch", False):
+                    elif getattr(model, "supports_cfg_batch", False) and c.shape[1] == uc.shape[1]:
                         eps = model(torch.cat([xt, xt], dim=0), torch.cat([tt, tt]), torch.cat([c, uc], dim=0))
                     else:
                         eps = torch.cat([model(xt, tt, c), model(xt, tt, uc)], dim=0)
@@ -398,12 +399,14 @@ def _eval_eps_pair(model, x, t_value, c, uc, guide, cfg_parallel=None, cache: Op
     if cfg_parallel is not None and cfg_parallel.size == 2:
         mine = c if cfg_parallel.role == 0 else uc
         return cfg_parallel.exchange_eps(model(x, tt, mine)).contiguous(), True
+    ragged = c.shape[1] != uc.shape[1]        # a prompt of more 77-token chunks than the negative prompt (or fewer): no padding, as the reference
     if cache is not None and hasattr(model, "forward_cfg_pair") and c.shape[0] == uc.shape[0] == x.shape[0]:
         ident = (cache.setdefault("nonce", next(_RUN_COUNTER)), id(c), c._version, id(uc), uc._version)
         if cache.get("key") != ident:
-            cache.update(key=ident, ctx=torch.cat([c, uc], dim=0), refs=(c, uc))
+            # equal lengths: the [cond | uncond] batch; unequal: the pair itself — the model packs it once per token (forward_cfg_pair)
+            cache.update(key=ident, ctx=(c, uc) if ragged else torch.cat([c, uc], dim=0), refs=(c, uc))
         return model.forward_cfg_pair(x, tt, cache["ctx"], context_token=ident, single_t=True).contiguous(), True
-    if getattr(model, "supports_cfg_batch", False):
+    if getattr(model, "supports_cfg_batch", False) and not ragged:
         return model(torch.cat([x, x], dim=0), torch.cat([tt, tt]), torch.cat([c, uc], dim=0)).contiguous(), True
     return torch.cat([model(x, tt, c), model(x, tt, uc)], dim=0).contiguous(), True
 

@@ -11,9 +11,10 @@ Reference call sites:
 `open_clip` itself is a third-party dependency that the reference does not vendor and this image does not carry; its
 text tower is the published pre-LN transformer (`ResidualAttentionBlock`: x += MHA(ln_1 x, causal); x += c_proj(GELU(c_fc
 (ln_2 x)))) with `nn.MultiheadAttention` parameter names, which `OpenClipTextModel` below reproduces as a parameter
-holder so that `open_clip_pytorch_model.bin` state dicts load unchanged.  Tokenisation, the prompt-emphasis parser and
-textual-inversion fixes are webui plumbing (`modules.prompt_parser`, `modules.textual_inversion`) and stay outside: the
-boundary is a batch of token ids.
+holder so that `open_clip_pytorch_model.bin` state dicts load unchanged.  The BPE tokenizer is the caller's (open_clip's
+`_tokenizer`); the webui prompt syntax the reference honours — `(word:1.3)`, `[word]`, `BREAK`, comma back-tracking — is parsed
+here (`parse_prompt_attention`, `FrozenOpenCLIPEmbedder.tokenize_line`) and the emphasis multipliers are applied by
+`T2V_OP_EMPHASIS` as the last op of the tower program.  Textual-inversion fixes and prompt-editing schedules stay outside.
 
 One block of the tower per 77-token chunk: LayerNorm → one QKV GEMM (bias) → causal attention (`T2V_OP_ATTENTION`,
 i[15] = 1, 64-wide heads) → out-projection GEMM with bias + fp32 residual → LayerNorm → fc GEMM → GELU / quick-GELU
@@ -22,9 +23,11 @@ No CPU fallback: device tensors only.
 """
 from __future__ import annotations
 
+import math
 import os
+import re
 from collections import OrderedDict
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 from torch import nn
@@ -130,12 +133,15 @@ def _detect(sd_keys) -> _Names:
 # ------------------------------------------------------------------------------------------
 # lowering
 # ------------------------------------------------------------------------------------------
+EXT_MULT = L.EXT_T          # the text programs have no timestep: its slot carries the emphasis multipliers
+
+
 class _TextLowering:
-    def __init__(self, names: _Names, *, B, Lseq, width, heads, layers, vocab, act, eps, keep_taps=False):
+    def __init__(self, names: _Names, *, B, Lseq, width, heads, layers, vocab, act, eps, keep_taps=False, emphasis=False):
         assert width % heads == 0 and width // heads == 64, "CLIP text towers use 64-wide heads"
         self.nm, self.B, self.Lseq, self.W, self.H, self.layers = names, B, Lseq, width, heads, layers
-        self.vocab, self.act, self.eps = vocab, act, eps
-        self.P = Program(f"clip-text b{B} l{Lseq} w{width} x{layers}")
+        self.vocab, self.act, self.eps, self.emphasis = vocab, act, eps, emphasis
+        self.P = Program(f"clip-text b{B} l{Lseq} w{width} x{layers}" + (" emphasis" if emphasis else ""))
         self.P.keep_taps = keep_taps
         self.packer = pk.WeightPacker()
 
@@ -186,7 +192,10 @@ class _TextLowering:
         n = P.alloc(M, W, "f16")
         P.layernorm("ln_final", x, self.vec(nm.final() + ".weight"), self.vec(nm.final() + ".bias"), n, eps=self.eps)
         P.free(x)
-        P.copy2d("z", n, Buf(Ref("ext", L.EXT_OUT), M, W, W, "f32"))
+        if self.emphasis:        # per-token multipliers (fp32 [B * Lseq] at slot EXT_MULT) + the batch mean restored: clip_hardcode.py:413-420
+            P.emphasis("z", n, Ref("ext", EXT_MULT), Buf(Ref("ext", L.EXT_OUT), M, W, W, "f32"))
+        else:
+            P.copy2d("z", n, Buf(Ref("ext", L.EXT_OUT), M, W, W, "f32"))
         P.free(n)
         P.finish()
         return P
@@ -196,10 +205,10 @@ ACT_GELU, ACT_QUICK_GELU = 2, 3
 
 
 class ClipTextTower:
-    """tokens int [B, L] (device) -> z fp32 [B, L, width]: the transformer part of either embedder, run from the
+    """tokens int [B, L] (device) (+ multipliers fp32 [B, L]) -> z fp32 [B, L, width]: the transformer part of either embedder, run from the
     parameters of `holder` (an open_clip CLIP / `OpenClipTextModel`, or a transformers `CLIPTextModel` /
     `CLIPTextTransformer`).  `skip_last` = number of trailing blocks left out (`layer_idx` of the reference: 1 for
-    'penultimate')."""
+    'penultimate').  With `multipliers` the program's last op applies the prompt emphasis (`T2V_OP_EMPHASIS`) instead of the plain cast."""
 
     def __init__(self, holder: nn.Module, *, heads: Optional[int] = None, act: Optional[str] = None, skip_last: int = 0,
                  eps: float = 1e-5):
@@ -230,10 +239,10 @@ class ClipTextTower:
     def _signature(self):
         return tuple((id(p), p._version, p.device.type, p.dtype) for p in self.holder.parameters())
 
-    def _compile(self, B, Lseq) -> _Compiled:
+    def _compile(self, B, Lseq, emphasis=False) -> _Compiled:
         low = _TextLowering(self.names, B=B, Lseq=Lseq, width=self.width, heads=self.heads,
                             layers=self.n_layers - self.skip_last, vocab=self.vocab, act=self.act, eps=self.eps,
-                            keep_taps=self.debug_taps)
+                            keep_taps=self.debug_taps, emphasis=emphasis)
         return _Compiled(low.build(), low.packer)
 
     def refresh_weights(self, comp: _Compiled, device):
@@ -245,36 +254,108 @@ class ClipTextTower:
         for c in self._programs.values():
             c.bound = None
 
-    def __call__(self, tokens: torch.Tensor) -> torch.Tensor:
+    def __call__(self, tokens: torch.Tensor, multipliers: Optional[torch.Tensor] = None) -> torch.Tensor:
         if not tokens.is_cuda:
             raise L.T2VError("ClipTextTower needs device tensors on an AMD GPU (no CPU fallback)")
         assert tokens.ndim == 2 and tokens.shape[1] <= self.max_len
         B, Lseq = tokens.shape
         ids = tokens.to(torch.int32).contiguous()
-        comp = self._programs.get((B, Lseq))
+        key = (B, Lseq) if multipliers is None else (B, Lseq, True)
+        comp = self._programs.get(key)
         if comp is None:
-            comp = self._programs[(B, Lseq)] = self._compile(B, Lseq)
+            comp = self._programs[key] = self._compile(B, Lseq, emphasis=multipliers is not None)
         self.refresh_weights(comp, tokens.device)
         comp.ensure_bound(self._packed, tokens.device)
         z = torch.empty((B, Lseq, self.width), device=tokens.device, dtype=torch.float32)
-        comp.bound.run({L.EXT_X: ids.data_ptr(), L.EXT_OUT: z.data_ptr()}, torch.cuda.current_stream(tokens.device).cuda_stream)
+        ext = {L.EXT_X: ids.data_ptr(), L.EXT_OUT: z.data_ptr()}
+        if multipliers is not None:
+            assert multipliers.shape == tokens.shape and multipliers.device == tokens.device
+            mult = multipliers.to(torch.float32).contiguous()
+            ext[EXT_MULT] = mult.data_ptr()
+        comp.bound.run(ext, torch.cuda.current_stream(tokens.device).cuda_stream)
         return z
+
+
+# ------------------------------------------------------------------------------------------
+# webui's prompt-attention syntax (`modules.prompt_parser.parse_prompt_attention`, which clip_hardcode.py:153-154 calls)
+# ------------------------------------------------------------------------------------------
+_RE_ATTENTION = re.compile(r"""
+    \\[()\[\]\\]              |   # an escaped bracket or backslash: a literal
+    \\                          |   # a lone backslash
+    [(\[]                        |   # an opening bracket
+    :\s*([+-]?[.\d]+)\s*\)       |   # ':w)' closes a round bracket with an explicit weight
+    [)\]]                        |   # a closing bracket
+    [^\\()\[\]:]+               |   # plain text
+    :                                 # a colon that is no weight
+""", re.X)
+_RE_BREAK = re.compile(r"\s*\bBREAK\b\s*", re.S)
+_ROUND, _SQUARE = 1.1, 1 / 1.1
+
+
+def parse_prompt_attention(text: str) -> List[list]:
+    """text -> [[piece, weight], ...].  `( )` multiplies the enclosed pieces by 1.1, `[ ]` by 1 / 1.1, `( :w)` by w; `\\(` `\\)` `\\[`
+    `\\]` `\\\\` are literals; a `:` without a weight and `)` behind it, and closers without an opener, are text; brackets left open
+    apply to the end; plain text is split at the word BREAK into pieces with `["BREAK", -1]` between them; neighbours of equal weight
+    are merged; an empty prompt is `[["", 1.0]]`."""
+    res: List[list] = []
+    open_round: List[int] = []
+    open_square: List[int] = []
+
+    def scale(start, factor):
+        for piece in res[start:]:
+            piece[1] *= factor
+
+    for m in _RE_ATTENTION.finditer(text):
+        tok, weight = m.group(0), m.group(1)
+        if tok[0] == "\\":
+            res.append([tok[1:], 1.0])
+        elif tok == "(":
+            open_round.append(len(res))
+        elif tok == "[":
+            open_square.append(len(res))
+        elif weight is not None and open_round:
+            scale(open_round.pop(), float(weight))
+        elif tok == ")" and open_round:
+            scale(open_round.pop(), _ROUND)
+        elif tok == "]" and open_square:
+            scale(open_square.pop(), _SQUARE)
+        else:
+            for k, part in enumerate(_RE_BREAK.split(tok)):
+                if k:
+                    res.append(["BREAK", -1])
+                res.append([part, 1.0])
+    for start in open_round:
+        scale(start, _ROUND)
+    for start in open_square:
+        scale(start, _SQUARE)
+    if not res:
+        return [["", 1.0]]
+    merged = [res[0]]
+    for piece in res[1:]:
+        if piece[1] == merged[-1][1]:
+            merged[-1][0] += piece[0]
+        else:
+            merged.append(piece)
+    return merged
 
 
 # ------------------------------------------------------------------------------------------
 # the reference's two embedder classes
 # ------------------------------------------------------------------------------------------
 class FrozenOpenCLIPEmbedder(nn.Module):
-    """Mirror of clip_hardcode.py:59-422 for everything from token ids onwards.  `version` = path of an
+    """Mirror of clip_hardcode.py:59-422 from the prompt text onwards.  `version` = path of an
     `open_clip_pytorch_model.bin` (text keys are loaded, `visual.*` ignored); `tokenizer` = an object with
     `.encode(text) -> List[int]` and an `.encoder` vocabulary (open_clip's `_tokenizer`), needed only by `forward(texts)`.
-    `device` is where the tower runs (the reference keeps its encoder on the CPU; this one has no CPU path)."""
+    `device` is where the tower runs (the reference keeps its encoder on the CPU; this one has no CPU path).
+    `enable_emphasis` / `comma_padding_backtrack` are the two webui options the reference reads from `opts` in `tokenize_line`
+    (webui's defaults: True and 20); the defaults here tokenise a prompt as plain text in 75-token chunks."""
     LAYERS = ["last", "penultimate"]
 
     def __init__(self, arch="ViT-H-14", version=None, device="cuda", max_length=77, freeze=True, layer="last",
-                 tokenizer=None, model: Optional[nn.Module] = None):
+                 tokenizer=None, model: Optional[nn.Module] = None, enable_emphasis: bool = False, comma_padding_backtrack: int = 0):
         super().__init__()
         assert layer in self.LAYERS
+        self.enable_emphasis, self.comma_padding_backtrack = bool(enable_emphasis), int(comma_padding_backtrack or 0)
         if model is None:
             model = OpenClipTextModel(**OPEN_CLIP_TEXT[arch])
             if version is not None and os.path.exists(version):
@@ -325,28 +406,67 @@ class FrozenOpenCLIPEmbedder(nn.Module):
     def empty_chunk(self):                            # :132-138
         return [self.id_start] + [self.id_end] * (self.chunk_length + 1), [1.0] * (self.chunk_length + 2)
 
+    def get_target_prompt_token_count(self, token_count):          # :140-143
+        """The most tokens a prompt of `token_count` tokens can grow to before it needs one more chunk."""
+        return math.ceil(max(token_count, 1) / self.chunk_length) * self.chunk_length
+
     def tokenize_line(self, line):
-        """:147-242 with emphasis off, no textual-inversion embeddings and comma_padding_backtrack = 0 (those are
-        webui options served by webui modules): 75-token chunks, start / end framed, end-padded."""
-        tokens = self.tokenize([line])[0]
-        chunks, count = [], 0
-        for c0 in range(0, max(len(tokens), 1), self.chunk_length):
-            body = tokens[c0:c0 + self.chunk_length]
-            last = c0 + self.chunk_length >= len(tokens)
-            count += len(body) if last else self.chunk_length
-            body = body + [self.id_end] * (self.chunk_length - len(body))
-            chunks.append(([self.id_start] + body + [self.id_end], [1.0] * (self.chunk_length + 2)))
-        return chunks, count
+        """:146-239 — one prompt -> ([(tokens, multipliers), ...], token_count): 77-token chunks (start + 75 + end, end-padded),
+        each token carrying the weight of its piece of `parse_prompt_attention` (with `enable_emphasis`; else the whole line at 1.0).
+        `BREAK` closes the current chunk; with `comma_padding_backtrack` = n, a chunk that fills up no more than n tokens behind
+        its last comma hands the text after that comma to the next chunk.  A chunk closed early counts as 75 tokens, the last one
+        as what it holds.
+        Textual-inversion fixes are not built.  In the reference they are inert: `hijack.fixes` is assigned in `forward` but nothing
+        reads it, `token_embedding` is never wrapped (`encode_with_transformer`, :110-117, looks up raw ids) and
+        `HijackDummy.embedding_db` is an empty database, so no prompt ever matches an embedding."""
+        parsed = parse_prompt_attention(line) if self.enable_emphasis else [[line, 1.0]]
+        tokenized = self.tokenize([text for text, _ in parsed])
+        chunks = []
+        tokens, mults = [], []
+        token_count, last_comma = 0, -1
+
+        def next_chunk(is_last=False):
+            nonlocal tokens, mults, token_count, last_comma
+            token_count += len(tokens) if is_last else self.chunk_length
+            pad = self.chunk_length - len(tokens)
+            chunks.append(([self.id_start] + tokens + [self.id_end] * (pad + 1), [1.0] + mults + [1.0] * (pad + 1)))
+            tokens, mults, last_comma = [], [], -1
+
+        backtrack = self.comma_padding_backtrack
+        for piece, (text, weight) in zip(tokenized, parsed):
+            if text == "BREAK" and weight == -1:
+                next_chunk()
+                continue
+            for token in piece:
+                if token == self.comma_token:
+                    last_comma = len(tokens)
+                elif backtrack != 0 and len(tokens) == self.chunk_length and last_comma != -1 and len(tokens) - last_comma <= backtrack:
+                    cut = last_comma + 1
+                    moved_t, moved_m = tokens[cut:], mults[cut:]
+                    tokens, mults = tokens[:cut], mults[:cut]
+                    next_chunk()
+                    tokens, mults = moved_t, moved_m
+                if len(tokens) == self.chunk_length:
+                    next_chunk()
+                tokens.append(token)
+                mults.append(weight)
+        if tokens or not chunks:
+            next_chunk(is_last=True)
+        return chunks, token_count
 
     def process_tokens(self, remade_batch_tokens, batch_multipliers):
         """:392-421 — one 77-token chunk per row; tokens after the first <end> become pad (SD2 convention), the
-        multipliers scale z and the original mean is restored."""
+        multipliers scale z and the original mean (of the whole batch) is restored.  On the device that arithmetic is the last op
+        of the tower program (`T2V_OP_EMPHASIS`); the torch lines below serve host tensors only."""
         dev = torch.device(self.device)
-        tokens = torch.as_tensor(remade_batch_tokens).to(dev)
+        tokens = torch.as_tensor(remade_batch_tokens)
         if self.id_end != self.id_pad:
             for row, toks in enumerate(remade_batch_tokens):
                 index = list(toks).index(self.id_end)
                 tokens[row, index + 1:tokens.shape[1]] = self.id_pad
+        tokens = tokens.to(dev)
+        if dev.type != "cpu":
+            return self.tower(tokens, torch.as_tensor(batch_multipliers, dtype=torch.float32).to(dev))
         z = self.encode_with_transformers(tokens)
         mult = torch.as_tensor(batch_multipliers, dtype=z.dtype).to(dev)
         original_mean = z.mean()

@@ -230,6 +230,8 @@ class UNetSD(nn.Module):
         # 8x8, GroupNorm 3.40 vs 3.21 ms per step) — two launches cost what one grid barrier costs — so it is OFF by default.
         self.gn_producer_stats = L.knob("T2V_GN_STRIPS", "0") != "0"
         self.context_token = None     # one-shot hint consumed by the next forward (see forward_cfg_pair)
+        self._pair_lens = None        # one-shot: (Lc, Lu) of a packed [cond | uncond] context (forward_cfg_pair)
+        self._pair_ctx = None         # (context token, packed context, lengths) of the last unequal pair
         # one-shot hint consumed by the next forward: every sample of the batch has the SAME timestep (forward_cfg_pair and the samplers
         # of this package set it).  Only then may the cond | uncond pair share its prefix — the shared ops use sample 0's time embedding,
         # and forward(x[1], t = [t0, t1], ctx[2]) with t0 != t1 must keep each sample's own t
@@ -442,13 +444,19 @@ class UNetSD(nn.Module):
         # one-shot hint of the samplers ("every sample of this call has the same timestep"): consumed before anything can raise, so that
         # a failed call never leaves it set for a later call with genuinely different timesteps
         hint_single, self.single_timestep = bool(self.single_timestep), False
+        # one-shot too (`forward_cfg_pair` with unequal lengths): y is the packed context [V * Lc + V * Lu, ctx] of a [cond | uncond] batch
+        pair_lens, self._pair_lens = getattr(self, "_pair_lens", None), None
         if not x.is_cuda:
             raise L.T2VError("UNetSD.forward needs device tensors on an AMD GPU (no CPU fallback); "
                              "use oracle/torch_port.py for a CPU reference")
         Bx, C, F, H, W = x.shape
-        B = y.shape[0]
+        if pair_lens is None:
+            B, Lctx = y.shape[0], y.shape[1]
+        else:
+            assert y.ndim == 2 and y.shape[0] % sum(pair_lens) == 0
+            B, Lctx = 2 * (y.shape[0] // sum(pair_lens)), tuple(pair_lens)
         # x with fewer samples than the context: sample b of the batch reads x[b % Bx] (`forward_cfg_pair`)
-        assert C == self.in_dim and B % Bx == 0 and y.shape[2] == self.context_dim
+        assert C == self.in_dim and B % Bx == 0 and y.shape[-1] == self.context_dim
         x = x.contiguous()
         y = y.contiguous()
         if x.dtype not in (torch.float16, torch.float32):
@@ -467,16 +475,19 @@ class UNetSD(nn.Module):
             shard = self.t_shard.spec                             # x holds only this rank's frames
             if shard.frames != F:
                 raise L.T2VError(f"T-sharded forward: this rank holds {shard.frames} of {shard.total} frames, got {F}")
+            if pair_lens is not None:
+                raise L.T2VError(f"T-sharded forward: cond and uncond contexts of different lengths ({pair_lens[0]} and {pair_lens[1]} tokens) "
+                                 "are not supported; run one role per rank, or pad the prompts to one length")
         single = hint_single or tf.numel() == 1 or t.ndim == 0
         if not single and not tf.is_cuda:
             single = bool((tf == tf.reshape(-1)[0]).all())
         self._share_now = bool(getattr(self, "share_cfg_prefix", False)) and single
-        key = self._program_key(B, F, H, W, y.shape[1], x.dtype, y.dtype, out_dtype, shard, Bx) + ((("adapter", adapter[0]),) if adapter else ())
+        key = self._program_key(B, F, H, W, Lctx, x.dtype, y.dtype, out_dtype, shard, Bx) + ((("adapter", adapter[0]),) if adapter else ())
         comp = self._programs.get(key)
         if comp is not None and comp.prog.gn_epilogue and L.exchange_disabled():
             comp = None        # an asynchronous fault was reported: lower again, without the norms fused into GEMM epilogues (_lib.exchange_disabled)
         if comp is None:
-            comp = self._compile(B, F, H, W, y.shape[1], _dt(x.dtype), _dt(out_dtype), _dt(y.dtype), shard=shard,
+            comp = self._compile(B, F, H, W, Lctx, _dt(x.dtype), _dt(out_dtype), _dt(y.dtype), shard=shard,
                                  x_batch=Bx if Bx != B else 0, **({"adapter": adapter[0]} if adapter else {}))
             self._programs[key] = comp
             self._evict_programs(keep=key)
@@ -517,13 +528,33 @@ class UNetSD(nn.Module):
         """One guided step's two evaluations (gaussian_sampler.py:161-162) as ONE forward: x [V,4,F,h,w] is read twice by
         the entry op (no torch.cat([x, x])), ctx_pair = [cond (V) | uncond (V)]; -> eps [2V,...].  `context_token`: any
         hashable the caller changes whenever ctx_pair's CONTENT changes — equal to the previous call's token, the
-        text-context K/V projections of that call are reused (they do not depend on x or t)."""
+        text-context K/V projections of that call are reused (they do not depend on x or t).
+        ctx_pair may also be the pair (cond [V, Lc, ctx], uncond [V, Lu, ctx]).  Equal lengths: the same as their concatenation.
+        Unequal lengths (a prompt of several 77-token chunks against a short negative prompt): still ONE program — the two contexts
+        are packed without padding (V * Lc rows, then V * Lu rows; built once per `context_token`), every text cross-attention is one
+        launch whose samples take the key count and K / V rows of their role, as the reference's two forwards do."""
+        pair_lens = None
+        if isinstance(ctx_pair, (tuple, list)):
+            c, uc = ctx_pair
+            assert c.ndim == 3 and uc.ndim == 3 and c.shape[0] == uc.shape[0] and c.shape[2] == uc.shape[2]
+            if c.shape[1] == uc.shape[1]:
+                ctx_pair = torch.cat([c, uc], dim=0)
+            else:
+                pair_lens = (c.shape[1], uc.shape[1])
+                held = getattr(self, "_pair_ctx", None)
+                if context_token is None or held is None or held[0] != context_token or held[2] != pair_lens:
+                    dt = torch.promote_types(c.dtype, uc.dtype)
+                    packed = torch.cat([c.to(dt).reshape(-1, c.shape[2]), uc.to(dt).reshape(-1, uc.shape[2])], dim=0)
+                    held = self._pair_ctx = (context_token, packed, pair_lens)
+                ctx_pair = held[1]
+        B = ctx_pair.shape[0] if pair_lens is None else 2 * (ctx_pair.shape[0] // sum(pair_lens))
         tt = t.to(device=x.device, dtype=torch.float32).reshape(-1)
         if single_t is None:          # one t for every sample?  (a [1] tensor: yes; per-sample values: compared — the samplers say it outright)
             single_t = tt.shape[0] == 1 or bool((tt == tt[0]).all())
-        tt = tt.repeat(ctx_pair.shape[0] // tt.shape[0]) if tt.shape[0] != ctx_pair.shape[0] else tt
+        tt = tt.repeat(B // tt.shape[0]) if tt.shape[0] != B else tt
         self.context_token = context_token
         self.single_timestep = bool(single_t)
+        self._pair_lens = pair_lens
         return UNetSD.forward(self, x, tt, ctx_pair)
 
     max_programs = 4      # compiled geometries kept (each owns a device arena: 0.4 GiB per 24-frame sample, GiBs for long clips)
@@ -774,7 +805,7 @@ class _Lowering(_UNetLowering):
     def to_q_attention(self, attn, nrm: Buf, a: Buf, inner, heads, hw, scale, wrap: int) -> bool:
         """to_q + the 77-key attention as ONE launch (round 5): q never reaches HBM.  (At the parting site the projection runs
         for both samples from the one sample's rows: the A-operand row wrap.)"""
-        if self.vt_all is None or (self.F * hw) % 32 != 0 or self.Lctx > 96:
+        if self.vt_all is None or (self.F * hw) % 32 != 0 or self.Lctx > 96 or self.Lpair is not None:
             return False
         k0, _ = self.kv_slices[attn]
         vt = self.vt_all.row_slice(self.vt_slices[attn], self.vt_all.rows)           # this site's rows first; sample stride = all rows of a sample
@@ -875,7 +906,7 @@ class _Lowering(_UNetLowering):
     def prologue_alloc(self, sites):
         # V^T of the text context for the fused to_q + cross-attention launches: rows = the value channels of every site, keys contiguous
         # (padded to a multiple of 32, zero beyond the context length: allocated here, never freed before the end, zero from the bind)
-        if not (self.shard is None and self.Lctx <= 96 and bool(getattr(self.net, "fused_cross_attention", True))
+        if not (self.shard is None and self.Lctx <= 96 and self.Lpair is None and bool(getattr(self.net, "fused_cross_attention", True))
                 and all(c % 64 == 0 for _, c in sites)):
             return []
         off = 0
