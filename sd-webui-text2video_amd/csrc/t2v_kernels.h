@@ -1155,6 +1155,10 @@ __device__ __forceinline__ void t2v_epilogue_xattn(const GemmParams& p, const f3
   __syncthreads();
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const int Lc = p.xa_lc;
+  // 32-key blocks that hold a key (uniform over the launch).  The blocks behind them are not loaded: V^T has only ceil32(Lc) columns, so for
+  // Lc <= 64 their fragments would come from the following V^T rows — past the end of the buffer for the last rows of the last sample — and
+  // a NaN there survives its zero probability (0 x NaN).  Their scores stay 0 and are masked below: no part in the maximum or the sum.
+  const int nkb = (Lc + 31) >> 5;
   for (int item = wave; item < S * HEADS; item += NW) {
     const int st = item / HEADS, hh = item - st * HEADS;
     const int mt = m0 + st * 32, h = n0 / 64 + hh;
@@ -1169,6 +1173,7 @@ __device__ __forceinline__ void t2v_epilogue_xattn(const GemmParams& p, const f3
       const f16x8 qf = *reinterpret_cast<const f16x8*>(qrow + ((kk * 2 + fhalf) << 4));
 #pragma unroll
       for (int kb = 0; kb < 3; ++kb) {
+        if (kb >= nkb) continue;
         const int key = min(kb * 32 + frow, Lc - 1);               // rows past the last key: a finite copy, masked below
         const f16x8 kf = *reinterpret_cast<const f16x8*>(K + (size_t)key * p.xa_ldk + (kk * 2 + fhalf) * 8);
         sc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf, sc[kb], 0, 0, 0);
@@ -1199,6 +1204,7 @@ __device__ __forceinline__ void t2v_epilogue_xattn(const GemmParams& p, const f3
 #pragma unroll
     for (int t = 0; t < 6; ++t) {
       const int kb = t >> 1, tt = t & 1;
+      if (kb >= nkb) continue;
       f16x8 pf;
 #pragma unroll
       for (int e = 0; e < 8; ++e) pf[e] = (f16)sc[kb][8 * tt + e];

@@ -12,7 +12,8 @@ interpreter.  Outputs are NaN-filled first and must come back finite; the rows a
 Tolerances are the suite's own for these kernels against an explicit reference on randn inputs: 2e-3 for the fp16 output, 1e-3 for hi + lo,
 with hi + lo closer than hi.  Measured values: profiles/attention_adversarial.txt.
 
-Out of scope: the fused QKV + temporal-attention GEMM record (its logits come out of a GEMM and cannot be placed)."""
+Not here: the fused QKV + temporal-attention GEMM record, the fused to_q + text cross-attention record and the second role of
+T2V_OP_ATTENTION — tests/test_gpu_fused_attention_adversarial.py (the logits are placed through the GEMMs with selection weights)."""
 import pytest
 import torch
 
