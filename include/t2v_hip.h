@@ -193,6 +193,13 @@ enum t2v_gather {
  *      7 split-K (epilogue NONE): T2V_SYNC_INTS zeroed int32 tile tickets -> the last workgroup of a tile to arrive folds the
  *        slabs in split order and applies the epilogue (no reduction launch); 0 -> a reduction kernel follows;
  *      8 .. 11 and i[24 .. 29], f[2]: T2V_EPI_GN (above)
+ *   Fused feed-forward pair (plans only; env T2V_FF_FUSE, read once, default on; 0 = off): when a plan is created, records k, k + 1 that
+ *      are a GEGLU GEMM (plain gather, no split-K, N = 2560, K = 320, fp16 out, nothing but a bias) and a projection whose A operand is
+ *      EXACTLY that result (same pointer, leading dimension and M; plain gather and epilogue, no split-K, N = 320, K = 1280, no fused
+ *      norm) run as ONE launch, bit-identical to the two, provided M >= 49152, the result not lying over the GEGLU GEMM's operands, and no later record of the plan reads an address inside
+ *      the hidden tensor before some record writes one.  THE HIDDEN BUFFER (record k's p[5]) IS NOT WRITTEN BY A FUSED PAIR.
+ *      t2v_plan_run_timed reports the launch on record k and exactly 0.0f on record k + 1.  t2v_run_ops never fuses.
+ *      i[31] = 1 on the GEGLU record (a word no validation reads; test hook): the M cut-off is waived.
  * GROUPNORM: i: 0 n_inst, 1 rows_per_inst, 2 C, 3 ld_in, 4 groups, 5 in dtype, 6 silu,
  *      7 ld_out, 8 phase (0 whole op | 1 statistics only | 2 fold gathered parts + normalise | 3 statistics from the producing GEMM:
  *         p[6] = its T2V_EPI_STATS strips fp32 [n_inst * rows / 32][2][i[17]], rows % 32 == 0 — a fold of the strips + ONE apply pass),

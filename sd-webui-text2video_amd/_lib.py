@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("T2V_LIB_PATH") or os.path.join(_HERE, "libt2v_hip.so"
 #                     SHARED with other work (the fused norms need every workgroup of a launch co-resident)
 #   T2V_PRECISE       0 | 1 | r3 | all: which fp16 operand classes are split hi + lo (unet.py)
 #   T2V_EXCHANGE      records | barrier (csrc/norm.hip)
+#   T2V_FF_FUSE       0: a plan runs the C = 320 GEGLU feed-forward pair as two launches (csrc/executor.hip ff_pair)
 # Everything else that starts with T2V_ is the A/B switch of a measured experiment and is read ONLY when
 # T2V_EXPERIMENTAL=1 (tests/conftest.py and the tools/ scripts set it): a deployment cannot land on an untested combination by accident.
 EXPERIMENTAL = os.environ.get("T2V_EXPERIMENTAL", "0") == "1"

@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -321,45 +323,51 @@ int validate_op(const t2v_op& op, int idx) {
   }
 }
 
+// The parameter block of a GEMM record, up to what every epilogue shares (launch_op adds the fused attention / LayerNorm parts)
+GemmParams gemm_params(const t2v_op& op) {
+  GemmParams p;
+  memset(&p, 0, sizeof p);
+  p.M = op.i[0]; p.N = op.i[1]; p.K = op.i[2];
+  p.lda = op.i[3]; p.ldw = op.i[4]; p.ldc = op.i[5]; p.ldr = op.i[6];
+  p.gather = op.i[7];
+  if (p.gather == T2V_GATHER_TCONV3) { p.F = op.i[8]; p.HW = op.i[9]; }
+  else { p.Hin = op.i[8]; p.Win = op.i[9]; }
+  p.Cin = op.i[10]; p.stride = op.i[11]; p.up = op.i[12]; p.Hout = op.i[13]; p.Wout = op.i[14];
+  p.rows_per_batch = op.i[15] > 0 ? op.i[15] : 1;
+  p.epi = op.i[16]; p.out_f32 = op.i[17] == T2V_F32; p.act = op.i[18];
+  if (p.epi == T2V_EPI_STATS) { p.epi = T2V_EPI_NONE; p.stats = reinterpret_cast<float*>(op.p[7]); }   // (validated: no split-K -> p[7] is not a ticket buffer)
+  if (p.epi == T2V_EPI_GN) {                                  // GroupNorm (+SiLU) of the result inside the epilogue (validated above)
+    p.epi = T2V_EPI_NONE;
+    p.gn_gb = reinterpret_cast<const float*>(op.p[8]);
+    p.gn_out = reinterpret_cast<f16*>(op.p[9]);
+    p.gn_part = reinterpret_cast<double*>(op.p[10]);
+    p.gn_bar = reinterpret_cast<unsigned*>(op.p[11]);
+    p.gn_fault = t2v_coop_fault_word();
+    p.gn_rows = op.i[24]; p.ld_gn = op.i[25]; p.gn_silu = op.i[26]; p.gn_lo = op.i[27] ? op.i[1] : 0;
+    p.gn_cpg = op.i[1] / op.i[28]; p.gn_store_out = op.i[29] ? 0 : 1;
+    p.gn_eps = op.f[2];
+    t2v_exchange_ids(&p.gn_seq, &p.gn_want);
+  }
+  p.splitk = op.i[19] > 1 ? op.i[19] : 1;
+  p.bias_m = op.i[20]; p.ldrb = op.i[21];
+  p.A = reinterpret_cast<const f16*>(op.p[0]);
+  p.W = reinterpret_cast<const f16*>(op.p[1]);
+  p.bias = reinterpret_cast<const float*>(op.p[2]);
+  p.rowbias = reinterpret_cast<const float*>(op.p[3]);
+  p.res = reinterpret_cast<const float*>(op.p[4]);
+  p.out = reinterpret_cast<void*>(op.p[5]);
+  p.ws = reinterpret_cast<float*>(op.p[6]);
+  p.halo = op.i[23];
+  p.out_lo = (p.gather == T2V_GATHER_PLAIN && op.i[11] == 1) ? 1 : 0;
+  if (p.gather == T2V_GATHER_PLAIN && op.i[16] != T2V_EPI_TATTN) { p.res_wrap = op.i[12]; p.a_wrap = op.i[13]; }
+  if (op.i[30] > 0) p.res_wrap = op.i[30];                    // (validated: not beside i[12])
+  return p;
+}
+
 hipError_t launch_op(const t2v_op& op, hipStream_t s) {
   switch (op.kind) {
     case T2V_OP_GEMM: {
-      GemmParams p;
-      memset(&p, 0, sizeof p);
-      p.M = op.i[0]; p.N = op.i[1]; p.K = op.i[2];
-      p.lda = op.i[3]; p.ldw = op.i[4]; p.ldc = op.i[5]; p.ldr = op.i[6];
-      p.gather = op.i[7];
-      if (p.gather == T2V_GATHER_TCONV3) { p.F = op.i[8]; p.HW = op.i[9]; }
-      else { p.Hin = op.i[8]; p.Win = op.i[9]; }
-      p.Cin = op.i[10]; p.stride = op.i[11]; p.up = op.i[12]; p.Hout = op.i[13]; p.Wout = op.i[14];
-      p.rows_per_batch = op.i[15] > 0 ? op.i[15] : 1;
-      p.epi = op.i[16]; p.out_f32 = op.i[17] == T2V_F32; p.act = op.i[18];
-      if (p.epi == T2V_EPI_STATS) { p.epi = T2V_EPI_NONE; p.stats = reinterpret_cast<float*>(op.p[7]); }   // (validated: no split-K -> p[7] is not a ticket buffer)
-      if (p.epi == T2V_EPI_GN) {                                  // GroupNorm (+SiLU) of the result inside the epilogue (validated above)
-        p.epi = T2V_EPI_NONE;
-        p.gn_gb = reinterpret_cast<const float*>(op.p[8]);
-        p.gn_out = reinterpret_cast<f16*>(op.p[9]);
-        p.gn_part = reinterpret_cast<double*>(op.p[10]);
-        p.gn_bar = reinterpret_cast<unsigned*>(op.p[11]);
-        p.gn_fault = t2v_coop_fault_word();
-        p.gn_rows = op.i[24]; p.ld_gn = op.i[25]; p.gn_silu = op.i[26]; p.gn_lo = op.i[27] ? op.i[1] : 0;
-        p.gn_cpg = op.i[1] / op.i[28]; p.gn_store_out = op.i[29] ? 0 : 1;
-        p.gn_eps = op.f[2];
-        t2v_exchange_ids(&p.gn_seq, &p.gn_want);
-      }
-      p.splitk = op.i[19] > 1 ? op.i[19] : 1;
-      p.bias_m = op.i[20]; p.ldrb = op.i[21];
-      p.A = reinterpret_cast<const f16*>(op.p[0]);
-      p.W = reinterpret_cast<const f16*>(op.p[1]);
-      p.bias = reinterpret_cast<const float*>(op.p[2]);
-      p.rowbias = reinterpret_cast<const float*>(op.p[3]);
-      p.res = reinterpret_cast<const float*>(op.p[4]);
-      p.out = reinterpret_cast<void*>(op.p[5]);
-      p.ws = reinterpret_cast<float*>(op.p[6]);
-      p.halo = op.i[23];
-      p.out_lo = (p.gather == T2V_GATHER_PLAIN && op.i[11] == 1) ? 1 : 0;
-      if (p.gather == T2V_GATHER_PLAIN && op.i[16] != T2V_EPI_TATTN) { p.res_wrap = op.i[12]; p.a_wrap = op.i[13]; }
-      if (op.i[30] > 0) p.res_wrap = op.i[30];                    // (validated: not beside i[12])
+      GemmParams p = gemm_params(op);
       const int tile = op.i[22];
       if (p.epi == T2V_EPI_TATTN) {                              // fused QKV projection + temporal attention (tile 10)
         p.F = op.i[8]; p.HW = op.i[9]; p.tpix = op.i[10];
@@ -423,7 +431,108 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
   }
 }
 
-int run_resolved(const t2v_op* ops, int n, const uint64_t* ext, int n_ext, hipStream_t s, float* ms, t2v_comm* comm = nullptr) {
+// ---- the fused C = 320 GEGLU feed-forward pair (gemm2.hip, t2v_launch_ff_fused) --------------------------------------------------------
+// T2V_FF_FUSE (read once): 0 = every plan runs its records one launch each; T2V_FF_FUSE_MIN_M: the row cut-off of the recognition.
+constexpr int FF_FUSE_DEFAULT = 1;
+constexpr int FF_MIN_M_DEFAULT = 49152;      // a whole round of 192-row workgroups on 256 CUs.  Measured (profiles/ff_fused.txt): at 32768 rows (171
+                                             // workgroups) the pair's time is unchanged and the VideoCrafter line 0.5 - 1 % slower, at 24576 the pair is 15 us slower
+bool ff_fuse_enabled() {
+  static int mode = -1;
+  if (mode < 0) {
+    const char* e = getenv("T2V_FF_FUSE");
+    mode = e != nullptr ? (strcmp(e, "0") != 0 ? 1 : 0) : FF_FUSE_DEFAULT;
+  }
+  return mode == 1;
+}
+int ff_min_m() {
+  static int min_m = -1;
+  if (min_m < 0) {
+    const char* e = getenv("T2V_FF_FUSE_MIN_M");
+    const long v = e != nullptr ? atol(e) : 0;
+    min_m = v > 0 && v < (1L << 30) ? (int)v : FF_MIN_M_DEFAULT;
+  }
+  return min_m;
+}
+
+// Pointer slots of a record that are ONLY written (outputs, workspaces, synchronisation words), as a bit mask — from the field lists
+// validate_op checks.  Every other non-null slot counts as read: a slot whose role is in doubt (in-place collectives, the own part of
+// a resharding, the K / V^T operands that share numbers with the fused GroupNorm's output) is an input.
+unsigned output_slots(const t2v_op& op) {
+  auto bits = [](std::initializer_list<int> l) { unsigned m = 0; for (int k : l) m |= 1u << k; return m; };
+  switch (op.kind) {
+    case T2V_OP_GEMM: return bits({5, 6, 7, 10, 11}) | (op.i[16] == T2V_EPI_GN ? bits({9}) : 0u);
+    case T2V_OP_GROUPNORM: return bits({3, 4, 5, 7, 8});
+    case T2V_OP_LAYERNORM: return bits({3});
+    case T2V_OP_ATTENTION: return bits({3, 6});
+    case T2V_OP_RELPOS_ATTN: return bits({3});
+    case T2V_OP_SOFTMAX: return bits({1});
+    case T2V_OP_NCTHW_TO_CL: return bits({1, 2});
+    case T2V_OP_CL_TO_NCTHW: return bits({1});
+    case T2V_OP_TIME_EMBED: return bits({2});
+    case T2V_OP_COPY2D: return bits({1, 2});
+    case T2V_OP_DDIM_STEP: return bits({3});
+    case T2V_OP_MEMSET: return bits({0});
+    case T2V_OP_LINCOMB: return bits({6});
+    case T2V_OP_EMBED_ROWS: return bits({3});
+    case T2V_OP_TO_UINT8: return bits({1});
+    case T2V_OP_RESAMPLE: return bits({1});
+    case T2V_OP_DEPTH_TOKENS: return bits({1});
+    case T2V_OP_AVGPOOL2: return bits({1, 2});
+    case T2V_OP_EMPHASIS: return bits({2});
+    case T2V_OP_RESHARD_ROWS: return bits({1});
+    case T2V_OP_ALLTOALL: return bits({1});
+    default: return 0u;      // ALLGATHER / HALO_EXCHANGE / STATS_HALO work in place: their slots are read
+  }
+}
+
+// Are ops[k] and ops[k + 1] the GEGLU GEMM and the projection of a C = 320 feed-forward whose hidden tensor nothing else reads?  When in
+// doubt: no.  (i[31] = 1 on the GEGLU record, a word no validation reads: the row cut-off is waived — the tests' way to the kernel at
+// a few hundred rows.)
+bool ff_pair(const t2v_op* ops, int n, int k) {
+  if (!ff_fuse_enabled() || k + 1 >= n) return false;
+  const t2v_op &a = ops[k], &b = ops[k + 1];
+  if (a.kind != T2V_OP_GEMM || b.kind != T2V_OP_GEMM) return false;
+  const int M = a.i[0];
+  // the GEGLU GEMM: plain gather, no split-K, N = 2560, K = 320, fp16 out, nothing but a bias beside it
+  if (a.i[16] != T2V_EPI_GEGLU || a.i[7] != T2V_GATHER_PLAIN || a.i[19] > 1 || a.i[1] != 2560 || a.i[2] != 320 || a.i[17] != T2V_F16) return false;
+  if (a.i[3] < 320 || a.i[4] < 320 || a.i[5] < 1280 || a.i[8] != 0 || a.i[11] != 0 || a.i[12] != 0 || a.i[13] != 0 || a.i[18] != 0 || a.i[20] != 0 || a.i[30] != 0) return false;
+  if (a.p[0] == 0 || a.p[1] == 0 || a.p[3] != 0 || a.p[4] != 0 || a.p[5] < T2V_EXT_SLOTS) return false;
+  // the projection: plain gather and epilogue, no split-K, N = 320, K = 1280, no fused norm, A = exactly that hidden tensor
+  if (b.i[16] != T2V_EPI_NONE || b.i[7] != T2V_GATHER_PLAIN || b.i[19] > 1 || b.i[1] != 320 || b.i[2] != 1280 || b.i[8] != 0) return false;
+  if (b.i[0] != M || b.p[0] != a.p[5] || b.i[3] != a.i[5] || b.i[4] < 1280 || b.i[13] != 0 || b.i[20] != 0 || b.p[1] == 0 || b.p[5] == 0) return false;
+  if (b.i[12] != 0 && b.i[30] != 0) return false;
+  if (M < (a.i[31] == 1 ? 1 : ff_min_m())) return false;
+  // One launch reads X, W1 and b1 until its last workgroup is done, while the first ones already store their rows of the result: the
+  // result must not lie over them.  (The lowerings do hand the projection the dead X buffer as its output, with rows twice as long:
+  // as two launches that is safe, as one launch a workgroup would store over rows another one has yet to read.)
+  {
+    if (a.p[0] < T2V_EXT_SLOTS || a.p[1] < T2V_EXT_SLOTS || (a.p[2] != 0 && a.p[2] < T2V_EXT_SLOTS) || b.p[5] < T2V_EXT_SLOTS) return false;
+    const uint64_t o0 = b.p[5], o1 = o0 + ((uint64_t)(M - 1) * b.i[5] + 320 * (b.i[11] == 1 ? 2 : 1)) * (b.i[17] == T2V_F32 ? 4 : 2);
+    auto apart = [&](uint64_t r0, uint64_t bytes) { return r0 == 0 || o1 <= r0 || o0 >= r0 + bytes; };
+    if (!apart(a.p[0], ((uint64_t)(M - 1) * a.i[3] + 320) * 2) || !apart(a.p[1], ((uint64_t)2559 * a.i[4] + 320) * 2) || !apart(a.p[2], 2560 * 4)) return false;
+  }
+  // nothing else may read the hidden tensor: scan the records behind the GEGLU GEMM until one names the buffer as an output
+  const uint64_t lo = a.p[5], hi = lo + ((uint64_t)(M - 1) * a.i[5] + 1280) * 2;
+  for (int j = k + 1; j < n; ++j) {
+    const unsigned outs = output_slots(ops[j]);
+    bool rewritten = false;
+    for (int q = 0; q < T2V_OP_NP; ++q) {
+      const uint64_t v = ops[j].p[q];
+      if (v < lo || v >= hi) continue;
+      if (j == k + 1 && q == 0) continue;                  // the projection's A operand
+      if (!((outs >> q) & 1u) || j == k + 1) return false; // read by someone else (or the projection writes into its own operand)
+      rewritten = true;
+    }
+    if (rewritten) break;
+  }
+  return true;
+}
+
+hipError_t launch_ff_pair(const t2v_op& a, const t2v_op& b, hipStream_t s) { return t2v_launch_ff_fused(gemm_params(a), gemm_params(b), s); }
+
+// fused (plans only): fused[k] != 0 -> ops k and k + 1 run as ONE launch (ff_pair); ms[k] is that launch, ms[k + 1] exactly 0
+int run_resolved(const t2v_op* ops, int n, const uint64_t* ext, int n_ext, hipStream_t s, float* ms, t2v_comm* comm = nullptr,
+                 const unsigned char* fused = nullptr) {
   {
     // a kernel of an EARLIER run gave up at a grid barrier (norm.hip): that run's results are invalid — say so now, once
     std::string why;
@@ -463,7 +572,23 @@ int run_resolved(const t2v_op* ops, int n, const uint64_t* ext, int n_ext, hipSt
       if (ms) (void)hipEventRecord(ev[k + 1], s);
       continue;
     }
-    const hipError_t e = launch_op(op, s);
+    hipError_t e;
+    if (fused != nullptr && fused[k]) {
+      t2v_op nxt = ops[k + 1];
+      if (!resolve_ptrs(nxt, ext, n_ext)) {
+        char buf[96];
+        snprintf(buf, sizeof buf, "op %d (tag %d): unresolved external pointer slot", k + 1, nxt.tag);
+        return fail(T2V_ERR_BAD_ARG, buf);
+      }
+      e = launch_ff_pair(op, nxt, s);
+      if (e == hipSuccess) {
+        if (ms) { (void)hipEventRecord(ev[k + 1], s); (void)hipEventRecord(ev[k + 2], s); }
+        ++k;
+        continue;
+      }
+    } else {
+      e = launch_op(op, s);
+    }
     if (e == hipErrorCooperativeLaunchTooLarge) {
       // A launch that needs its whole grid co-resident was refused.  Either a workgroup of an EARLIER launch of this run gave up waiting
       // and raised the fault word (the co-resident path switches off mid-run): that is the asynchronous fault, report it as such now —
@@ -485,6 +610,8 @@ int run_resolved(const t2v_op* ops, int n, const uint64_t* ext, int n_ext, hipSt
   if (ms) {
     if (hipStreamSynchronize(s) != hipSuccess) return fail(T2V_ERR_LAUNCH, "stream sync failed");
     for (int k = 0; k < n; ++k) (void)hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+    for (int k = 0; fused != nullptr && k + 1 < n; ++k)
+      if (fused[k]) ms[k + 1] = 0.0f;
     for (auto& e : ev) (void)hipEventDestroy(e);
   }
   return T2V_OK;
@@ -494,6 +621,7 @@ int run_resolved(const t2v_op* ops, int n, const uint64_t* ext, int n_ext, hipSt
 
 struct t2v_plan {
   std::vector<t2v_op> ops;
+  std::vector<unsigned char> fused;   // fused[k]: ops k, k + 1 are a feed-forward pair that runs as one launch (ff_pair)
   t2v_comm* comm = nullptr;   // borrowed (t2v_plan_set_comm)
 };
 
@@ -547,6 +675,9 @@ int t2v_plan_create(const t2v_op* ops, int n, t2v_plan** out) {
   }
   t2v_plan* p = new t2v_plan();
   p->ops.assign(ops, ops + n);
+  p->fused.assign(n, 0);
+  for (int k = 0; k + 1 < n; ++k)
+    if (ff_pair(ops, n, k)) { p->fused[k] = 1; ++k; }
   *out = p;
   return T2V_OK;
 }
@@ -555,12 +686,12 @@ int t2v_plan_num_ops(const t2v_plan* plan) { return plan ? (int)plan->ops.size()
 
 int t2v_plan_run(t2v_plan* plan, const uint64_t* ext, int n_ext, void* stream) {
   if (!plan) return fail(T2V_ERR_BAD_ARG, "null plan");
-  return run_resolved(plan->ops.data(), (int)plan->ops.size(), ext, n_ext, reinterpret_cast<hipStream_t>(stream), nullptr, plan->comm);
+  return run_resolved(plan->ops.data(), (int)plan->ops.size(), ext, n_ext, reinterpret_cast<hipStream_t>(stream), nullptr, plan->comm, plan->fused.data());
 }
 
 int t2v_plan_run_timed(t2v_plan* plan, const uint64_t* ext, int n_ext, void* stream, float* ms) {
   if (!plan || !ms) return fail(T2V_ERR_BAD_ARG, "null plan / ms");
-  return run_resolved(plan->ops.data(), (int)plan->ops.size(), ext, n_ext, reinterpret_cast<hipStream_t>(stream), ms, plan->comm);
+  return run_resolved(plan->ops.data(), (int)plan->ops.size(), ext, n_ext, reinterpret_cast<hipStream_t>(stream), ms, plan->comm, plan->fused.data());
 }
 
 void t2v_plan_destroy(t2v_plan* plan) { delete plan; }

@@ -605,7 +605,190 @@ hipError_t launch_cfg(const GemmParams& pin, hipStream_t s) {
   return e;
 }
 
+// ---- fused GEGLU feed-forward pair (C = 320, hidden = 1280) ---------------------------------------------------------------------------
+// out = epilogue2(geglu(X W1^T + b1) W2^T): the GEGLU GEMM (N = 2560, K = 320) and the projection that consumes its result (N = 320,
+// K = 1280) as ONE launch — the [M, 1280] fp16 hidden tensor (126 MB written and read back at M = 49152) never reaches HBM.  A workgroup
+// owns 192 rows like tile 8 (12 waves, 6 row strips x 2 column halves) and keeps the 192x320 fp32 result in accumulators for the whole
+// launch (80 registers per lane); the hidden dimension is walked in 20 chunks of 64 channels = 128 packed value | gate columns:
+//   stage 1   5 k-tiles of 64: X rows (24 KiB) + the chunk's 128 W1 rows (16 KiB) -> a 192x128 accumulator (32 registers per lane), in
+//             ascending k like the GEGLU GEMM; then bias, value * gelu(gate) and the fp16 rounding of the hidden tensor, exactly where
+//             the two-launch form rounds it, into a 192x64 fp16 LDS buffer;
+//   stage 2   ONE k-tile of 64: that buffer against the chunk's W2 columns (320 rows x 64 = 40 KiB) into the result accumulators — the
+//             same MFMA and the same k order as the projection on tile 8.
+// Both kinds of k-tile are 40 KiB, so they go through ONE 3-deep LDS-DMA ring as a stream of 120 tiles with the schedule of
+// gemm2_kernel (two tiles in flight, one barrier per tile, counted vmcnt): chunk j + 1's first operands arrive under chunk j's GELU
+// and stage 2.  X is streamed again per chunk (from L2).  The tail is the projection's own (t2v_epilogue_rows: bias, row bias, fp32
+// residual with its wrap, fp16 hi + lo / fp32 store).  Because no rounding point and no accumulation order moves, the result is
+// bit-identical to the two launches.
+constexpr int FF_C = 320, FF_HID = 1280, FF_BM = 192, FF_CH = 64, FF_NCHUNK = FF_HID / FF_CH, FF_KT1 = FF_C / 64, FF_TPC = FF_KT1 + 1;
+constexpr int FF_NW = 12, FF_SLOT = 40 * 1024, FF_STAGES = 3, FF_LPS = 4;       // 40 1-KiB DMA pieces per tile: 4 per wave, the last 8 are dummies
+constexpr int FF_W1_OFF = FF_BM * 128;                                          // W1 rows of a stage-1 tile, behind the 192 X rows
+constexpr int FF_HP = FF_CH * 2 + 16;                                           // bytes per row of the hidden chunk (+16: rows start on different banks)
+constexpr int FF_H_OFF = FF_STAGES * FF_SLOT, FF_B_OFF = FF_H_OFF + FF_BM * FF_HP, FF_DUMMY_OFF = FF_B_OFF + 2 * FF_HID * 4;
+constexpr int FF_LDS = FF_DUMMY_OFF + 1024;                                      // 158 KiB: ring 120, hidden chunk 27, b1 10, dummy piece 1
+static_assert(FF_NW * 32 * T2V_EPI_SP * 4 <= FF_H_OFF, "the epilogue strips alias the ring");
+
+__global__ __launch_bounds__(FF_NW * 64, 3) void ff_fused_kernel(const GemmParams p1, const GemmParams p2) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int m0 = blockIdx.x * FF_BM;
+
+  // b1 (value | gate interleaved by eights, as the weight rows) -> LDS once: the GELU phase reads it 20 times
+  float* b1s = reinterpret_cast<float*>(smem + FF_B_OFF);
+  for (int i = tid; i < 2 * FF_HID; i += FF_NW * 64) b1s[i] = p1.bias ? p1.bias[i] : 0.f;
+
+  // ---- per-lane DMA sources (LDS image of gemm2_kernel with 128-byte rows: row r, chunk c at r * 128 + ((c ^ ((r >> 1) & 7)) << 4)) ----
+  // piece s = wave + 12 j, j = 0 .. 3, covers rows 8 s .. 8 s + 7 of the tile; stage-1 tile: pieces 0 .. 23 X, 24 .. 39 W1; stage-2 tile:
+  // pieces 0 .. 39 W2; pieces 40 .. 47 (j = 3 of waves 4 .. 11) are dummies in both
+  const int lrow = lane >> 3, pchunk = lane & 7;
+  auto swz = [](int r) { return (r >> 1) & 7; };
+  const bool last_real = wave < 4;                             // wave-uniform
+  // (a piece's rows move by 96 from j to j + 1: the same swizzle term, so the W offsets of j > 0 are wave-uniform steps from j = 0;
+  //  X rows past M read row M - 1 instead — finite operands for rows the epilogue never stores)
+  unsigned xoffs[2];               // (unsigned 32-bit lane offsets from wave-uniform bases: the DMA addresses stay scalar base + lane offset)
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int r = (wave + FF_NW * j) * 8 + lrow;
+    xoffs[j] = (min(m0 + r, p1.M - 1) * p1.lda + (pchunk ^ swz(r)) * 8) * 2;
+  }
+  const int wr0 = wave * 8 + lrow, wlc = (pchunk ^ swz(wr0)) * 8;
+  const unsigned w1off = (wr0 * p1.ldw + wlc) * 2, w2off = (wr0 * p2.ldw + wlc) * 2;
+  const int w1step = 96 * p1.ldw * 2, w2step = 96 * p2.ldw * 2;
+  const unsigned char* xb = reinterpret_cast<const unsigned char*>(p1.A);
+  const unsigned char* w1b = reinterpret_cast<const unsigned char*>(p1.W);
+  const unsigned char* w2b = reinterpret_cast<const unsigned char*>(p2.W);
+  const long w1chunk = (long)(2 * FF_CH) * p1.ldw * 2;         // bytes between the W1 rows of consecutive chunks
+  // piece j of tile (chunk sc, k-tile sk; sk == FF_KT1: the W2 tile) into ring slot `slot`.  The two tiles staged past the end read the last
+  // chunk's again (into slots nobody computes on): the outstanding-load count stays constant and no address needs a per-lane select.
+  auto stage_piece = [&](int slot, int sc, int sk, int j) {
+    unsigned char* dst = smem + slot * FF_SLOT + (wave + FF_NW * j) * 1024;
+    const int scl = min(sc, FF_NCHUNK - 1);
+    const bool dummy = j == 3 && !last_real;                  // wave-uniform: rows 320 .. 383 do not exist — the piece re-reads piece 0's source
+    const int jj = dummy ? 0 : j;
+    const unsigned char* base;                                // wave-uniform part of the address
+    unsigned off;                                             // this lane's part
+    if (sk == FF_KT1) { base = w2b + (scl * (FF_CH * 2) + jj * w2step); off = w2off; }
+    else if (jj < 2) { base = xb + sk * 128; off = xoffs[jj]; }
+    else { base = w1b + (scl * w1chunk + sk * 128 + (jj - 2) * w1step); off = w1off; }
+    if (dummy) dst = smem + FF_DUMMY_OFF;
+    // the base stays in scalar registers and the sum is formed by the instruction (a per-lane 64-bit sum hoisted out of the loop would
+    // cost two registers per piece, which this kernel does not have)
+    asm volatile("" : "+s"(base));
+    const unsigned char* src = base + (size_t)off;
+    t2v_glds16(src, dst);
+  };
+
+  f32x16 acc2[1][5], acc1[2];
+#pragma unroll
+  for (int b = 0; b < 5; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc2[0][b][r] = 0.f;
+
+  // prologue: tiles 0 and 1 in flight
+#pragma unroll
+  for (int g = 0; g < FF_STAGES - 1; ++g)
+#pragma unroll
+    for (int j = 0; j < FF_LPS; ++j) stage_piece(g, 0, g, j);
+
+  // fragment addressing: every tile row base of a wave is a multiple of 32, so the swizzle term depends on the lane alone
+  const int frow = lane & 31, fhalf = lane >> 5;
+  const int fsw = swz(frow) << 4;
+  const int xoff = (wm * 32 + frow) * 128;                     // X rows of a stage-1 tile and rows of the hidden chunk
+  const int w1o = FF_W1_OFF + (wn * 64 + frow) * 128;          // + b * 4096
+  const int w2o = (wn * 160 + frow) * 128;                     // + b * 4096
+  unsigned char* hrow = smem + FF_H_OFF + (wm * 32 + frow) * FF_HP + fhalf * 16;   // this lane's row of the hidden chunk, its half of a k-step
+
+  int slot = 0;
+  for (int chunk = 0; chunk < FF_NCHUNK; ++chunk) {
+#pragma unroll
+    for (int kt = 0; kt < FF_TPC; ++kt) {
+      wait_vmcnt<FF_LPS*(FF_STAGES - 2)>();                    // this wave's pieces of the tile to compute have landed
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // ... and its stores into the hidden chunk / b1 are done
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      int fs = slot + FF_STAGES - 1;
+      if (fs >= FF_STAGES) fs -= FF_STAGES;
+      const int sk = (kt + FF_STAGES - 1) % FF_TPC, sc = chunk + (kt + FF_STAGES - 1) / FF_TPC;
+      const unsigned char* st = smem + slot * FF_SLOT;
+      if (kt < FF_KT1) {
+        if (kt == 0) {
+#pragma unroll
+          for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc1[b][r] = 0.f;
+        }
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          const int lc4 = ((kk * 2 + fhalf) << 4) ^ fsw;
+          const f16x8 xf = *reinterpret_cast<const f16x8*>(st + xoff + lc4);
+          f16x8 wf[2];
+#pragma unroll
+          for (int b = 0; b < 2; ++b) wf[b] = *reinterpret_cast<const f16x8*>(st + w1o + b * 4096 + lc4);
+          stage_piece(fs, sc, sk, kk);
+#pragma unroll
+          for (int b = 0; b < 2; ++b) acc1[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[b], xf, acc1[b], 0, 0, 0);
+        }
+        if (kt == FF_KT1 - 1) {
+          // GEGLU of the chunk (the arithmetic of gemm2_kernel's GEGLU epilogue): a lane holds value and gate of 4 hidden channels of
+          // ONE row per (b, qq); the fp16 results go to the hidden chunk in the operand image stage 2 reads
+#pragma unroll
+          for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int qq = 0; qq < 2; ++qq) {
+              const int n_val = chunk * (2 * FF_CH) + wn * 64 + b * 32 + 16 * qq + 4 * fhalf;
+              const f32x4 bv = *reinterpret_cast<const f32x4*>(b1s + n_val);
+              const f32x4 bg = *reinterpret_cast<const f32x4*>(b1s + n_val + 8);
+              f16x4 o;
+#pragma unroll
+              for (int r = 0; r < 4; ++r) o[r] = (f16)((acc1[b][8 * qq + r] + bv[r]) * t2v_gelu_erf(acc1[b][8 * qq + 4 + r] + bg[r]));
+              const int lc = wn * 4 + b * 2 + qq;              // 16-byte chunk of hidden channels 8 lc .. 8 lc + 7 of the chunk
+              *reinterpret_cast<f16x4*>(hrow + lc * 16 - fhalf * 8) = o;
+            }
+        }
+      } else {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          const int lc4 = ((kk * 2 + fhalf) << 4) ^ fsw;
+          const f16x8 xf = *reinterpret_cast<const f16x8*>(hrow + kk * 32);
+          f16x8 wf[5];
+#pragma unroll
+          for (int b = 0; b < 5; ++b) wf[b] = *reinterpret_cast<const f16x8*>(st + w2o + b * 4096 + lc4);
+          stage_piece(fs, sc, sk, kk);
+#pragma unroll
+          for (int b = 0; b < 5; ++b) acc2[0][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[b], xf, acc2[0][b], 0, 0, 0);
+        }
+      }
+      slot = slot + 1 == FF_STAGES ? 0 : slot + 1;
+    }
+  }
+  wait_vmcnt<0>();   // drain the loads of the dead stages before the strips alias the ring
+  __builtin_amdgcn_s_barrier();
+  int elane = lane;
+  asm volatile("" : "+v"(elane));      // the tail's per-lane addresses are formed here, not ahead of the loop (where they would be spilled)
+  GemmParams q = p2;
+  q.splitk = 1; q.tickets = nullptr; q.stats = nullptr;       // (checked by the launcher: the tail's split-K and statistics branches fold away)
+  t2v_epilogue_rows<1, 5>(q, acc2, reinterpret_cast<float*>(smem) + wave * (32 * T2V_EPI_SP), elane, m0 + wm * 32, wn * 160, 0, 0);
+}
+
 }  // namespace
+
+// The GEGLU GEMM p1 (N = 2560, K = 320, fp16 hidden out) and the projection p2 that reads exactly that result (N = 320, K = 1280) in one
+// launch; p1.out is NOT written.  The executor has checked the shapes (executor.hip, ff_pair); anything else is refused here too.
+hipError_t t2v_launch_ff_fused(const GemmParams& p1, const GemmParams& p2, hipStream_t s) {
+  if (p1.N != 2 * FF_HID || p1.K != FF_C || p2.N != FF_C || p2.K != FF_HID || p1.M != p2.M || p1.M <= 0 || p1.epi != T2V_EPI_GEGLU ||
+      p2.epi != T2V_EPI_NONE || p1.splitk != 1 || p2.splitk != 1 || p1.gather != T2V_GATHER_PLAIN || p2.gather != T2V_GATHER_PLAIN ||
+      p1.a_wrap || p2.a_wrap || p1.lda < FF_C || p1.ldw < FF_C || p2.ldw < FF_HID || p1.out_f32 || p2.stats != nullptr || p2.tickets != nullptr ||
+      (long)p1.M * p1.lda >= (1L << 30) || p2.ldw > 65536 || p1.ldw > 65536)        // (the DMA's lane offsets are 32-bit byte counts)
+    return hipErrorInvalidValue;
+  static t2v_device_flags attr_set;
+  const hipError_t e = t2v_set_dynamic_lds(reinterpret_cast<const void*>(ff_fused_kernel), FF_LDS, attr_set, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ff_fused_kernel, dim3((p1.M + FF_BM - 1) / FF_BM), dim3(FF_NW * 64), FF_LDS, s, p1, p2);
+  return hipGetLastError();
+}
 
 // tile ids (t2v_op.i[22]):  1 = 256x256, 2 = 256x320, 8 = 192x320 / 9 = 192x256 (12 waves), 11 = 128x320 (8 waves), 3 = 128x256 (8 waves), 4 / 5 = 128x128 with a 4-deep ring
 // (few-row levels: latency-bound, keep 96 KiB per CU in flight) — 64-wide k-tiles

@@ -242,6 +242,7 @@ inline void t2v_normalize_splitk(GemmParams& p, int bk, long tiles) {
 // Each returns hipSuccess or the launch error.
 hipError_t t2v_launch_gemm(const GemmParams& p, hipStream_t s);             // 128x128 / 128x64 tiles (any N, C8 stem)
 hipError_t t2v_launch_gemm2(const GemmParams& p, int tile, hipStream_t s);  // 256/128 x 256/320 tiles, deep DMA ring
+hipError_t t2v_launch_ff_fused(const GemmParams& geglu, const GemmParams& proj, hipStream_t s);   // the C = 320 GEGLU feed-forward pair as one launch (gemm2.hip)
 hipError_t t2v_launch_splitk_reduce(const GemmParams& p, hipStream_t s);
 hipError_t t2v_launch_splitk_reduce_gn(const GemmParams& p, hipStream_t s);   // split-K reduction + the GroupNorm (+SiLU) that consumes the result, one cooperative launch (norm.hip)
 hipError_t t2v_launch_groupnorm(const t2v_op& op, hipStream_t s);
