@@ -33,6 +33,7 @@ extern "C" {
                                record leaves zero, so the version does not move;
                                still 11: T2V_OP_EMPHASIS (a new kind: no existing record changes, and a library without it refuses the record as an unknown op kind) and
                                ATTENTION i[19..21] / p[4..5] (a second role; additive on fields every earlier record leaves zero);
+                               still 11: T2V_OP_FINGERPRINT (a new kind, stand-alone: 64-bit fingerprints of a table of byte ranges; no existing record changes);
                                10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
                                optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
                                9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
@@ -62,6 +63,10 @@ extern "C" {
 #define T2V_RELPOS_LONG_PADL 72
 #define T2V_RELPOS_LONG_COLS(R) ((2 * (R) + 158) / 8 * 8)
 
+/* FINGERPRINT: bytes of one segment that one workgroup reads (the unit of the host's chunk table), and the multiplier of the length term */
+#define T2V_FINGERPRINT_CHUNK 65536
+#define T2V_FINGERPRINT_LEN 0x9E3779B97F4A7C15ull
+
 /* ---- op kinds ------------------------------------------------------------------------- */
 enum t2v_op_kind {
   T2V_OP_GEMM = 1,        /* implicit-GEMM conv / linear on MFMA, fused epilogue            */
@@ -88,7 +93,8 @@ enum t2v_op_kind {
   T2V_OP_DEPTH_TOKENS = 22,  /* depth frames [n,1,H,W] -> PixelUnshuffle(8) channels-last fp16 tokens, optional per-frame min-max normalisation (T2I-Adapter entry) */
   T2V_OP_AVGPOOL2 = 23,      /* 2x2 / stride 2 average pooling of channels-last fp32 tokens (mean in fp32), fp32 and / or fp16 out */
   T2V_OP_EMPHASIS = 24,      /* prompt emphasis of a batch of text-encoder chunks: per-token multipliers, then the batch mean restored (fp64 sums, one workgroup) */
-  T2V_OP_KIND_MAX = 25
+  T2V_OP_FINGERPRINT = 25,   /* one 64-bit fingerprint per byte range of a device table (in-place edits of packed parameters); stand-alone, never part of a plan */
+  T2V_OP_KIND_MAX = 26
 };
 
 /* GEMM gather modes: how row m / reduction index k of the A operand are addressed          */
@@ -336,6 +342,15 @@ enum t2v_gather {
  *      z.mean() of the batch), accumulated in fp64 in a fixed order by ONE workgroup: results repeat bit for bit, and with every m = 1 the
  *      ratio is exactly 1.  A zero sum of z * m is not special-cased (IEEE inf / NaN, as the reference).
  *      i: 0 rows (B * L), 1 W (% 4 == 0), 2 ld of z, 3 ld of out (% 4 == 0), 4 dtype of z;  p: 0 z, 1 m fp32 [rows], 2 out fp32 (16-byte aligned)
+ * FINGERPRINT (ABI 11, t2v_run_ops only: t2v_plan_create refuses it): out[s] = a 64-bit function of the bytes of segment s of a device table, every segment
+ *      by itself.  A segment {address, nbytes} (both even, nbytes may be 0) is read as n = nbytes / 2 little-endian 16-bit words v_0 .. v_{n-1}:
+ *          out[s] = sum_j v_j * (2 j + 1)  +  2^32 * sum_j v_j^2  +  (n + 1) * T2V_FINGERPRINT_LEN      (mod 2^64)
+ *      One changed word always changes the value ((a - b) times an odd number is not 0 mod 2^64), two unequal words swapped too (2 (a - b)(j - k)),
+ *      and equal bytes of different lengths differ by the last term.  Wrap-around integer adds only: bitwise reproducible, independent of the
+ *      grid and of the alignment of the address.  The chunk table lists {uint32 segment, uint32 chunk} pairs: chunk c of segment s = its bytes
+ *      [c * T2V_FINGERPRINT_CHUNK, (c + 1) * T2V_FINGERPRINT_CHUNK), one workgroup each; EVERY chunk of every segment exactly once, and chunk 0 of
+ *      every segment (an empty one included: it carries the length term).  `out` is zeroed by the op (a memset on the stream), then one launch.
+ *      i: 0 n segments, 1 n chunks (>= n);  p: 0 table: n x {uint64 address, uint64 nbytes}, 1 out uint64 [n], 2 chunk table: n chunks x {uint32, uint32} (all 8-byte aligned)
  */
 typedef struct t2v_op {
   int32_t kind;

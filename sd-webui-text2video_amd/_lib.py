@@ -44,6 +44,9 @@ OP_RESHARD_ROWS, OP_ALLTOALL, OP_STATS_HALO = 18, 19, 20
 OP_RESAMPLE = 21
 OP_DEPTH_TOKENS, OP_AVGPOOL2 = 22, 23
 OP_EMPHASIS = 24
+OP_FINGERPRINT = 25
+FINGERPRINT_CHUNK = 65536           # T2V_FINGERPRINT_CHUNK: bytes of one segment per workgroup (the unit of the chunk table)
+FINGERPRINT_LEN = 0x9E3779B97F4A7C15   # T2V_FINGERPRINT_LEN: multiplier of the length term
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2     # GEMM i[18]
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_TCONV3, GATHER_CONV3X3_C8 = 0, 1, 2, 3
 EPI_NONE, EPI_GEGLU, EPI_TATTN, EPI_STATS, EPI_GN, EPI_XATTN = 0, 1, 2, 3, 4, 5

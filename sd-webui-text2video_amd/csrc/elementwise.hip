@@ -14,6 +14,8 @@
 //   depth_tokens  entry of the VideoCrafter depth adapter: per-frame min-max normalisation (ddpm3d.py:1463-1464) + PixelUnshuffle(8)
 //                 (adapter.py:93-99) of the depth frames, as the fp16 tokens conv_in reads
 //   avgpool2      the adapter's Downsample(use_conv=False): nn.AvgPool2d(2, 2) on channels-last fp32 tokens
+//   fingerprint   one 64-bit value per byte range of a table (the parameters of a model): which tensors were edited in place since
+//                 the weight images were packed (packing.ParamFingerprint)
 #include "t2v_kernels.h"
 
 namespace {
@@ -349,6 +351,79 @@ __global__ __launch_bounds__(1024) void emphasis_kernel(const TZ* z, const float
     }
     *reinterpret_cast<f32x4*>(out + r * ldo + c) = v;
   }
+}
+
+// Fingerprint of byte ranges (T2V_OP_FINGERPRINT): one 64-bit value per segment {address, nbytes} of a table, a function of the segment's
+// bytes and of nothing else.  A segment is read as n = nbytes / 2 little-endian 16-bit words v_0 .. v_{n-1} (address and nbytes even):
+//     value = sum_j v_j * (2 j + 1)  +  2^32 * sum_j v_j^2  +  (n + 1) * T2V_FINGERPRINT_LEN      (mod 2^64)
+// Word j contributes f(v, j) = v * ((2 j + 1) + 2^32 v): f(a, j) - f(b, j) = (a - b) * (odd number), which is 0 mod 2^64 only for a = b, so
+// ONE changed word always changes the value; two unequal words a, b swapped between j and k move it by 2 (a - b)(j - k) != 0; the last
+// term separates equal bytes of different lengths (trailing zero words add nothing to the sums).  Integer wrap-around adds only: the
+// order of the fold is free, the value does not depend on the grid or on the run.
+// One workgroup per chunk {segment, chunk index} of the host's chunk table (T2V_FINGERPRINT_CHUNK bytes of ONE segment; every segment has
+// a chunk 0, an empty one too, which adds the length term): 16-byte loads on the part of the chunk between 16-byte boundaries of the
+// ADDRESS, single words in front of and behind it, so the start may sit at any even address; per 16-byte vector at word j0 the sum is
+// (2 j0 + 1) * sum v_i + 2 * sum i v_i (v_dot2_u32_u16 on the packed words, no unpacking).  One 64-bit atomic add per workgroup into
+// out[segment], which the launcher zeroed on the same stream.  Nothing else is written.
+struct FpSeg { unsigned long long addr, nbytes; };
+
+__global__ __launch_bounds__(256) void fingerprint_kernel(const FpSeg* segs, const uint2* chunks, unsigned long long* out, int n) {
+  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+  typedef unsigned long long u64;
+  __shared__ u64 red[256];
+  const int t = threadIdx.x;
+  const uint2 ck = chunks[blockIdx.x];
+  if (ck.x >= (unsigned)n) return;
+  const FpSeg sg = segs[ck.x];
+  if ((sg.addr | sg.nbytes) & 1ull) return;                       // (the host refuses odd ranges; never read one)
+  const u64 b0 = (u64)ck.y * T2V_FINGERPRINT_CHUNK;
+  u64 lin = 0;         // sum v_j (2 j + 1)
+  unsigned sq = 0;     // sum v_j^2 mod 2^32 (it enters shifted left by 32)
+  if (b0 < sg.nbytes) {
+    const u64 b1 = b0 + T2V_FINGERPRINT_CHUNK < sg.nbytes ? b0 + T2V_FINGERPRINT_CHUNK : sg.nbytes;
+    const u64 p0 = sg.addr + b0, p1 = sg.addr + b1;
+    u64 a0 = (p0 + 15) & ~15ull;                                  // the 16-byte aligned interior [a0, a1) of [p0, p1)
+    if (a0 > p1) a0 = p1;
+    u64 a1 = p1 & ~15ull;
+    if (a1 < a0) a1 = a0;
+    const int head = (int)((a0 - p0) >> 1), tail = (int)((p1 - a1) >> 1);        // <= 7 words each
+    if (t < head + tail) {
+      const u64 at = t < head ? p0 + 2 * (u64)t : a1 + 2 * (u64)(t - head);
+      const unsigned v = *reinterpret_cast<const unsigned short*>(at);
+      lin += (u64)v * (((at - sg.addr) >> 1) * 2 + 1);
+      sq += v * v;
+    }
+    const long nvec = (long)((a1 - a0) >> 4);
+    const u16x2 ones = __builtin_bit_cast(u16x2, 0x00010001u);
+    for (long q = t; q < nvec; q += 256) {
+      const u64 at = a0 + 16 * (u64)q;
+      const uint4 w = *reinterpret_cast<const uint4*>(at);
+      const u16x2 w0 = __builtin_bit_cast(u16x2, w.x), w1 = __builtin_bit_cast(u16x2, w.y);
+      const u16x2 w2 = __builtin_bit_cast(u16x2, w.z), w3 = __builtin_bit_cast(u16x2, w.w);
+      unsigned s = __builtin_amdgcn_udot2(w0, ones, 0u, false);                  // sum v_i        < 2^19
+      s = __builtin_amdgcn_udot2(w1, ones, s, false);
+      s = __builtin_amdgcn_udot2(w2, ones, s, false);
+      s = __builtin_amdgcn_udot2(w3, ones, s, false);
+      unsigned m = __builtin_amdgcn_udot2(w0, __builtin_bit_cast(u16x2, 0x00010000u), 0u, false);   // sum i v_i, i = 0 .. 7   < 2^21
+      m = __builtin_amdgcn_udot2(w1, __builtin_bit_cast(u16x2, 0x00030002u), m, false);
+      m = __builtin_amdgcn_udot2(w2, __builtin_bit_cast(u16x2, 0x00050004u), m, false);
+      m = __builtin_amdgcn_udot2(w3, __builtin_bit_cast(u16x2, 0x00070006u), m, false);
+      sq = __builtin_amdgcn_udot2(w0, w0, sq, false);
+      sq = __builtin_amdgcn_udot2(w1, w1, sq, false);
+      sq = __builtin_amdgcn_udot2(w2, w2, sq, false);
+      sq = __builtin_amdgcn_udot2(w3, w3, sq, false);
+      lin += (((at - sg.addr) >> 1) * 2 + 1) * (u64)s + 2 * (u64)m;
+    }
+  }
+  u64 acc = lin + ((u64)sq << 32);
+  if (ck.y == 0 && t == 0) acc += ((sg.nbytes >> 1) + 1) * T2V_FINGERPRINT_LEN;
+  red[t] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  if (t == 0) atomicAdd(out + ck.x, red[0]);
 }
 
 // tensor2vid (t2v_pipeline.py:447-460): video[i,c,f,y,x] -> uint8 out[f, y, i*W + x, c]: v*0.5 + 0.5 (two roundings, as
@@ -708,6 +783,17 @@ hipError_t t2v_launch_emphasis(const t2v_op& op, hipStream_t s) {
     hipLaunchKernelGGL((emphasis_kernel<float>), dim3(1), dim3(1024), 0, s, reinterpret_cast<const float*>(op.p[0]), mult, out, rows, W, ldz, ldo);
   else
     hipLaunchKernelGGL((emphasis_kernel<f16>), dim3(1), dim3(1024), 0, s, reinterpret_cast<const f16*>(op.p[0]), mult, out, rows, W, ldz, ldo);
+  return hipGetLastError();
+}
+
+hipError_t t2v_launch_fingerprint(const t2v_op& op, hipStream_t s) {
+  const int n = op.i[0], n_chunks = op.i[1];
+  if (n <= 0 || n_chunks < n || op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0) return hipErrorInvalidValue;
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(op.p[1]);
+  const hipError_t e = hipMemsetAsync(out, 0, sizeof(unsigned long long) * (size_t)n, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fingerprint_kernel, dim3(n_chunks), dim3(256), 0, s, reinterpret_cast<const FpSeg*>(op.p[0]),
+                     reinterpret_cast<const uint2*>(op.p[2]), out, n);
   return hipGetLastError();
 }
 

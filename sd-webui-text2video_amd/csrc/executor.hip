@@ -296,6 +296,12 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0) return bad("null emphasis pointer");
       if (op.p[2] >= T2V_EXT_SLOTS && op.p[2] % 16 != 0) return bad("emphasis: the output must be 16-byte aligned");
       return 0;
+    case T2V_OP_FINGERPRINT:
+      if (op.i[0] <= 0 || op.i[1] < op.i[0]) return bad("fingerprint: n segments > 0, at least one chunk per segment");
+      if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0) return bad("null fingerprint pointer");
+      for (int k = 0; k < 3; ++k)
+        if (op.p[k] >= T2V_EXT_SLOTS && op.p[k] % 8 != 0) return bad("fingerprint: the tables and the output must be 8-byte aligned");
+      return 0;
     case T2V_OP_ALLGATHER:
       if (op.i[2] < 1 || op.i[3] < 0 || op.i[3] >= op.i[2] || op.p[0] == 0) return bad("bad all-gather record");
       return 0;
@@ -423,6 +429,7 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
     case T2V_OP_DEPTH_TOKENS: return t2v_launch_depth_tokens(op, s);
     case T2V_OP_AVGPOOL2: return t2v_launch_avgpool2(op, s);
     case T2V_OP_EMPHASIS: return t2v_launch_emphasis(op, s);
+    case T2V_OP_FINGERPRINT: return t2v_launch_fingerprint(op, s);
     case T2V_OP_MEMSET: {
       const size_t bytes = (size_t)(uint32_t)op.i[0] | ((size_t)(uint32_t)op.i[1] << 32);
       return hipMemsetAsync(reinterpret_cast<void*>(op.p[0]), 0, bytes, s);
@@ -479,6 +486,7 @@ unsigned output_slots(const t2v_op& op) {
     case T2V_OP_DEPTH_TOKENS: return bits({1});
     case T2V_OP_AVGPOOL2: return bits({1, 2});
     case T2V_OP_EMPHASIS: return bits({2});
+    case T2V_OP_FINGERPRINT: return bits({1});
     case T2V_OP_RESHARD_ROWS: return bits({1});
     case T2V_OP_ALLTOALL: return bits({1});
     default: return 0u;      // ALLGATHER / HALO_EXCHANGE / STATS_HALO work in place: their slots are read
@@ -672,6 +680,7 @@ int t2v_plan_create(const t2v_op* ops, int n, t2v_plan** out) {
   for (int k = 0; k < n; ++k) {
     const int rc = validate_op(ops[k], k);
     if (rc != 0) return rc;
+    if (ops[k].kind == T2V_OP_FINGERPRINT) return fail(T2V_ERR_BAD_ARG, "fingerprint: a stand-alone op (t2v_run_ops), not part of a plan");
   }
   t2v_plan* p = new t2v_plan();
   p->ops.assign(ops, ops + n);

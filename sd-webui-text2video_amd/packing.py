@@ -295,3 +295,111 @@ class WeightPacker:
         for name, t in fresh:
             packed[name].copy_(t)
         return len(fresh)
+
+
+# ---- byte-level fingerprints of the parameters (T2V_OP_FINGERPRINT) ------------------------------------------------------------------
+# The signature the repack decision rests on, (id, _version, device, dtype, shape), cannot see a write through `.data` (the VideoCrafter
+# LoRA loaders of the reference, lvdm/models/modules/lora.py:656-740: `weight.data += ...`, `weight.data = origin.clone()`): neither the
+# object nor its version counter moves.  The fingerprint looks at the bytes.  A tensor's storage is read as n little-endian 16-bit words:
+#     value = sum_j v_j (2 j + 1) + 2^32 sum_j v_j^2 + (n + 1) FINGERPRINT_LEN   (mod 2^64)          (include/t2v_hip.h)
+FINGERPRINT_CHUNK = 65536                       # T2V_FINGERPRINT_CHUNK: bytes of one tensor per workgroup
+FINGERPRINT_LEN = 0x9E3779B97F4A7C15            # T2V_FINGERPRINT_LEN
+_M64 = (1 << 64) - 1
+
+
+def _as_words(t: torch.Tensor) -> torch.Tensor:
+    """The bytes of a contiguous tensor as int16 words (a view)."""
+    flat = t.detach().reshape(-1)
+    if (flat.numel() * flat.element_size()) % 2 != 0:
+        raise ValueError(f"fingerprint: a byte range of odd length ({flat.numel() * flat.element_size()} bytes)")
+    return flat.view(torch.int16) if flat.numel() else flat.new_zeros(0, dtype=torch.int16)
+
+
+def fingerprint_torch(t: torch.Tensor) -> int:
+    """The fingerprint of one tensor's bytes with torch integer ops (int64 arithmetic wraps like the kernel's unsigned adds) — the
+    implementation for parameters that live on the CPU beside a CPU pack, and the reference of the kernel's tests."""
+    w = _as_words(t.contiguous())
+    n = w.numel()
+    total = ((n + 1) * FINGERPRINT_LEN) & _M64
+    step = 1 << 20                              # pieces keep every partial sum far below 2^63: the fold to 64 bits is done in Python
+    for j0 in range(0, n, step):
+        v = w[j0:j0 + step].to(torch.int64) & 0xFFFF
+        j = torch.arange(j0, j0 + v.numel(), dtype=torch.int64, device=v.device)
+        hi = v >> 8                             # v (2 j + 1) < 2^49 per word: split so that 2^20 of them sum below 2^63
+        lin = int((hi * (2 * j + 1)).sum()) * 256 + int(((v & 0xFF) * (2 * j + 1)).sum())
+        sq = int((v * v).sum())                 # < 2^32 * 2^20
+        total = (total + lin + (sq << 32)) & _M64
+    return total
+
+
+class ParamFingerprint:
+    """Fingerprints of a list of named tensors, one value each.  Tensors on a GPU: ONE launch of T2V_OP_FINGERPRINT over a device table
+    {address, nbytes} per tensor and a chunk table (FINGERPRINT_CHUNK bytes of one tensor per workgroup), both rebuilt only when an
+    address or a size changes; tensors on the CPU: `fingerprint_torch`.  `recorded` holds the values of the last pack (the owner
+    stores them there)."""
+
+    def __init__(self):
+        self._key = None
+        self._tables = None
+        self.recorded = None            # name -> value at the end of the last full / partial pack (None: nothing recorded)
+        self.last_bytes = 0             # bytes the last device launch read
+
+    @staticmethod
+    def chunk_table(sizes):
+        """[(segment, chunk)] of byte sizes: every chunk of every segment once; an empty segment keeps its chunk 0."""
+        out = []
+        for s, nb in enumerate(sizes):
+            out.extend((s, c) for c in range(max(1, -(-nb // FINGERPRINT_CHUNK))))
+        return out
+
+    def compute_ranges(self, ranges, device, stream=None):
+        """ranges: [(address, nbytes)] on `device` (even, readable for the duration of the call) -> [int]; one launch, then one copy back."""
+        import ctypes
+        import numpy as np
+        from . import _lib as L
+        if not ranges:
+            return []
+        for a, nb in ranges:
+            if (a | nb) & 1 or nb < 0:
+                raise L.T2VError(f"fingerprint: byte range ({a:#x}, {nb}) is not 2-byte aligned")
+        key = tuple(ranges)
+        if key != self._key or self._tables is None or self._tables[0].device != device:
+            chunks = self.chunk_table([nb for _, nb in ranges])
+            if len(chunks) >= 1 << 31:
+                raise L.T2VError("fingerprint: too many chunks for one launch")
+            seg = torch.from_numpy(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2).view(np.int64)).to(device)
+            chk = torch.from_numpy(np.asarray(chunks, dtype=np.uint32).reshape(-1, 2).view(np.int32)).to(device)
+            out = torch.empty(len(ranges), dtype=torch.int64, device=device)
+            self._key, self._tables = key, (seg, chk, out)
+        seg, chk, out = self._tables
+        op = L.T2VOp()
+        op.kind = L.OP_FINGERPRINT
+        op.i[0], op.i[1] = len(ranges), chk.shape[0]
+        op.p[0], op.p[1], op.p[2] = seg.data_ptr(), out.data_ptr(), chk.data_ptr()
+        if stream is None:
+            stream = torch.cuda.current_stream(device).cuda_stream
+        L.check(L.load().t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(stream)))
+        self.last_bytes = sum(nb for _, nb in ranges)
+        return [int(v) & _M64 for v in out.cpu().tolist()]
+
+    def compute(self, named, device):
+        """named: [(name, tensor)]; device: where the pack lives.  -> {name: value}, or None when the tensors are not fingerprinted:
+        they live on the CPU while the pack is on a GPU (hashing gigabytes on the host per call is not acceptable), or on several devices."""
+        device = torch.device(device)
+        named = [(n, t) for n, t in named if t is not None]
+        if not named:
+            return {}
+        devs = {t.device for _, t in named}
+        if len(devs) != 1:
+            return None
+        src = next(iter(devs))
+        if src.type == "cpu":
+            if device.type != "cpu":
+                return None
+            return {n: fingerprint_torch(t) for n, t in named}
+        if device.type == "cpu" or src != device:
+            return None
+        keep = [t if t.is_contiguous() else t.detach().contiguous() for _, t in named]     # (a strided parameter: a dense copy, alive until the copy back)
+        ranges = [(t.data_ptr() if t.numel() else 0, t.numel() * t.element_size()) for t in keep]
+        vals = self.compute_ranges(ranges, src)
+        return {n: v for (n, _), v in zip(named, vals)}

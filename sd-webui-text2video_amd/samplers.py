@@ -195,6 +195,8 @@ class GaussianDiffusion(object):
 
         ac = self.alphas_cumprod
         f32 = torch.float32
+        if hasattr(model, "verify_weights"):
+            model.verify_weights(dev)           # the bytes: in-place edits (`w.data += d`) that no version counter shows — once per call
         if hasattr(model, "refresh_weights"):
             model.refresh_weights(dev)
         prev_auto = getattr(model, "auto_refresh", None)
@@ -449,6 +451,8 @@ class DDIMSampler(object):
         model, dev = self.model, img.device
         C = img.shape[1]
         nxt = torch.empty_like(img)
+        if hasattr(model, "verify_weights"):
+            model.verify_weights(dev)           # the bytes: in-place edits (`w.data += d`) that no version counter shows — once per call
         if hasattr(model, "refresh_weights"):
             model.refresh_weights(dev)
         prev_auto = getattr(model, "auto_refresh", None)
@@ -615,6 +619,8 @@ class UniPCSampler(object):
         ts = torch.linspace(t_T, t_0, steps + 1, dtype=torch.float32).to(torch.float64).tolist()   # 'time_uniform', fp32 grid
         guide = unconditional_guidance_scale
         self._pair_cache = {}                      # per sampling run (its nonce keeps cached context K/V from leaking across runs)
+        if hasattr(model, "verify_weights"):
+            model.verify_weights(dev)           # the bytes: in-place edits (`w.data += d`) that no version counter shows — once per call
         if hasattr(model, "refresh_weights"):
             model.refresh_weights(dev)
         prev_auto = getattr(model, "auto_refresh", None)

@@ -223,6 +223,10 @@ class ClipTextTower:
             n_layers += 1
         self.n_layers, self.skip_last = n_layers, skip_last
         assert 0 <= skip_last < n_layers
+        for i in range(n_layers):      # the program's MLP GEMMs are [4 width, width] / [width, 4 width]: another size would be read out of bounds
+            if tuple(sd[nm.fc(i) + ".weight"].shape) != (4 * self.width, self.width) or tuple(sd[nm.proj(i) + ".weight"].shape) != (self.width, 4 * self.width):
+                raise L.T2VError(f"unsupported CLIP text tower: the MLP of block {i} is {tuple(sd[nm.fc(i) + '.weight'].shape)}, "
+                                 f"the lowering is built for 4 x width = {(4 * self.width, self.width)}")
         cfg = getattr(holder, "config", None)
         if heads is None:
             heads = getattr(cfg, "num_attention_heads", None) or getattr(holder, "heads", None) or self.width // 64
@@ -234,6 +238,7 @@ class ClipTextTower:
         self.eps = float(getattr(cfg, "layer_norm_eps", eps))
         self._programs: Dict[tuple, _Compiled] = {}
         self._packed, self._packed_sig, self._packed_device = None, None, None
+        self._fingerprint = pk.ParamFingerprint()      # byte-level values of the parameters at the last pack (verify_weights)
         self.debug_taps = False
 
     def _signature(self):
@@ -245,12 +250,29 @@ class ClipTextTower:
                             keep_taps=self.debug_taps, emphasis=emphasis)
         return _Compiled(low.build(), low.packer)
 
+    def verify_weights(self, device=None) -> list:
+        """The parameters whose BYTES differ from what the packed images were made of (an edit through `.data` moves neither identity nor
+        version: packing.ParamFingerprint); any such edit drops the pack, and the encode that follows packs again.  Nothing before the first
+        pack, nothing for CPU parameters beside a GPU pack."""
+        device = torch.device(device) if device is not None else self._packed_device
+        fp = self._fingerprint
+        if self._packed is None or fp.recorded is None or device != self._packed_device:
+            return []
+        fresh = fp.compute(list(self.holder.named_parameters()), device)
+        if fresh is None:
+            return []
+        changed = [n for n, v in fresh.items() if fp.recorded.get(n) != v]
+        if changed:
+            self._packed, self._packed_sig, fp.recorded = None, None, None
+        return changed
+
     def refresh_weights(self, comp: _Compiled, device):
         sig = self._signature()
         if self._packed is not None and sig == self._packed_sig and device == self._packed_device:
             return
         self._packed = comp.packer.materialise(self.holder.state_dict(), device)
         self._packed_sig, self._packed_device = sig, device
+        self._fingerprint.recorded = self._fingerprint.compute(list(self.holder.named_parameters()), device)
         for c in self._programs.values():
             c.bound = None
 
@@ -264,6 +286,7 @@ class ClipTextTower:
         comp = self._programs.get(key)
         if comp is None:
             comp = self._programs[key] = self._compile(B, Lseq, emphasis=multipliers is not None)
+        self.verify_weights(tokens.device)
         self.refresh_weights(comp, tokens.device)
         comp.ensure_bound(self._packed, tokens.device)
         z = torch.empty((B, Lseq, self.width), device=tokens.device, dtype=torch.float32)

@@ -218,6 +218,7 @@ class UNetSD(nn.Module):
         self._packed_deps = None
         self._param_slots = None
         self.last_repack = None       # images rewritten by the last refresh_weights (-1 = full pack)
+        self._fingerprint = pk.ParamFingerprint()   # byte-level values of the parameters at the last pack (verify_weights)
         self.debug_taps = False
         # Storage type of tensors that are consumed ONLY by a GroupNorm (ResBlock's first conv output
         # and the three inner temporal-conv outputs): "f16" halves their HBM traffic (what the
@@ -363,8 +364,37 @@ class UNetSD(nn.Module):
         self._packed = None
         self._packed_sig = None
 
+    def _named_params(self):
+        if self._param_slots is None:
+            self._param_signature()
+        return [(prefix + k, p) for prefix, pd in self._param_slots for k, p in pd.items() if p is not None]
+
+    def verify_weights(self, device=None) -> list:
+        """Look at the BYTES of the parameters: fingerprint every tensor (one launch, packing.ParamFingerprint), compare with the values
+        recorded when the images were last packed, and re-pack the images that read a changed tensor through the partial path of
+        `refresh_weights` (same device addresses, cached text K/V dropped; `last_repack` reports it).  -> the changed names.
+        This is what sees an edit through `.data` (`w.data += d`, `w.data = saved.clone()`: the reference's VideoCrafter LoRA loaders),
+        which moves neither the parameter's identity nor its version.  The samplers call it once per sampling call; code that edits
+        weights in place between bare forwards calls it itself.  Does nothing before the first pack, and nothing for parameters that
+        live on the CPU while the pack is on a GPU (they are not fingerprinted: `invalidate()` is the call for that arrangement)."""
+        device = torch.device(device) if device is not None else self._packed_device
+        fp = getattr(self, "_fingerprint", None)
+        if fp is None or self._packed is None or device is None or device != self._packed_device or fp.recorded is None:
+            return []
+        fresh = fp.compute(self._named_params(), device)
+        if fresh is None:
+            return []
+        changed = [n for n, v in fresh.items() if fp.recorded.get(n) != v]
+        if changed:
+            self._refresh_weights(device, also_changed=changed, fingerprints=fresh)
+        return changed
+
     def refresh_weights(self, device=None):
-        """(Re)pack weights if any parameter object / version changed since the last pack.  When only some
+        self._refresh_weights(device)
+
+    def _refresh_weights(self, device=None, also_changed=(), fingerprints=None):
+        """(Re)pack weights if any parameter object / version changed since the last pack (or `also_changed` names a parameter whose
+        bytes changed: `verify_weights`).  When only some
         parameters changed (the LoRA merge / un-merge of lora_processor.py:202-246 replaces `.weight` of the
         matched Linear / Conv modules), only the packed images that read them are rewritten, in place
         (`last_repack` = number of images, -1 for a full pack).  The packed set is the UNION of the images of every
@@ -375,12 +405,12 @@ class UNetSD(nn.Module):
             return
         sig = self._param_signature()
         same_dev = self._packed is not None and device == self._packed_device
-        if same_dev and sig == self._packed_sig:
+        if same_dev and sig == self._packed_sig and not also_changed:
             return
         packer = self._union_packer()
         sd = {k: v for k, v in self.state_dict().items()}
         if same_dev and sig.keys() == self._packed_sig.keys():
-            changed = [n for n, v in sig.items() if self._packed_sig[n] != v]
+            changed = [n for n, v in sig.items() if self._packed_sig[n] != v] + list(also_changed)
             n = packer.update(self._packed, sd, device, changed, deps=self._packed_deps)
             if n >= 0:
                 # images that only an EVICTED program declared are not refreshed by `update`: drop them, a re-compiled
@@ -391,6 +421,7 @@ class UNetSD(nn.Module):
                 self._packed_sig, self.last_repack = sig, n
                 for c in self._programs.values():
                     c.ctx_token = None          # cached context K/V were made with the old projection weights
+                self._record_fingerprints(device, fingerprints)
                 return
         elif same_dev:
             extra = sorted(set(sig) - set(self._packed_sig))
@@ -405,6 +436,13 @@ class UNetSD(nn.Module):
         for c in self._programs.values():
             c.bound = None
             c.ctx_token = None
+        self._record_fingerprints(device, fingerprints)
+
+    def _record_fingerprints(self, device, values=None):
+        """End of a full or partial pack: the parameters' fingerprints as of now (None when they are not fingerprinted)."""
+        fp = getattr(self, "_fingerprint", None)
+        if fp is not None:
+            fp.recorded = values if values is not None else fp.compute(self._named_params(), device)
 
     def _union_packer(self) -> pk.WeightPacker:
         if not self._programs:

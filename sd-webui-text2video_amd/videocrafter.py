@@ -1019,6 +1019,8 @@ class DDIMSampler(object):
         guide = unconditional_guidance_scale
         guided = uc is not None and guide != 1.0
         unet = self.model.model.diffusion_model
+        if hasattr(unet, "verify_weights"):
+            unet.verify_weights(device)         # the bytes: a LoRA merged the reference's way (`weight.data += ...`) moves no version counter
         unet.refresh_weights(device)
         prev_auto, unet.auto_refresh = unet.auto_refresh, False
         prev_eps = S._want_fp32_eps(unet)            # eps in fp32 inside the loop: the CFG combination amplifies fp16 output roundings
@@ -1091,6 +1093,121 @@ class DDIMSampler(object):
             unet.auto_refresh = prev_auto
             S._restore_eps(unet, prev_eps)
         return img, intermediates
+
+
+# ------------------------------------------------------------------------------------------
+# merged LoRA (lvdm/models/modules/lora.py:620-755)
+# ------------------------------------------------------------------------------------------
+def _lora_resolve(net, state_dict):
+    """First half of the reference's loop, for ALL keys before any weight is touched: -> ([(key, layer, up, down)], visited keys).
+    Keys with '.alpha' are skipped unread; the target is reached from `net` by the names of key.split('.')[:-2] (module children, so
+    ModuleList / Sequential indices too); a target whose class is not exactly nn.Linear / nn.Conv2d prints 'missing param at:' and is
+    skipped; the partner key swaps lora_down <-> lora_up and a pair is taken once, at whichever key comes first.  A name that does not
+    resolve, a missing partner or factors that do not fit the weight raise T2VError naming the key (the reference dies half-merged)."""
+    visited, todo = [], []
+    for key in state_dict:
+        if ".alpha" in key or key in visited:
+            continue
+        names = key.split(".")[:-2]
+        if not names:
+            raise L.T2VError(f"LoRA key {key!r} names no layer")
+        layer = net
+        for k, name in enumerate(names):
+            try:
+                if not isinstance(layer, nn.Module):
+                    raise AttributeError(name)
+                layer = nn.Module.__getattr__(layer, name)
+            except AttributeError:
+                where = ".".join(names[:k]) or "the model"
+                raise L.T2VError(f"LoRA key {key!r} cannot be resolved: {where} ({type(layer).__name__}) has no module {name!r}; "
+                                 "no weight was changed") from None
+        if layer.__class__ not in [nn.Linear, nn.Conv2d]:
+            print("missing param at:", key)
+            continue
+        if "lora_down" in key:
+            pair = [key.replace("lora_down", "lora_up"), key]
+        else:
+            pair = [key, key.replace("lora_up", "lora_down")]
+        for k in pair:
+            if k not in state_dict:
+                raise L.T2VError(f"LoRA key {key!r} has no partner {k!r}; no weight was changed")
+        up, down = state_dict[pair[0]], state_dict[pair[1]]
+        if len(up.shape) == 4:
+            up, down = up.squeeze(3).squeeze(2), down.squeeze(3).squeeze(2)
+        w = layer.weight
+        if (len(state_dict[pair[0]].shape) == 4) != (w.dim() == 4):      # (the reference picks the conv form by the FACTORS' rank)
+            raise L.T2VError(f"LoRA key {key!r}: {len(state_dict[pair[0]].shape)}-D factors for a {w.dim()}-D weight; no weight was changed")
+        if up.dim() != 2 or down.dim() != 2 or up.shape[1] != down.shape[0] or (up.shape[0], down.shape[1]) != tuple(w.shape[:2]):
+            raise L.T2VError(f"LoRA key {key!r}: factors {tuple(up.shape)} x {tuple(down.shape)} do not fit the weight {tuple(w.shape)}; "
+                             "no weight was changed")
+        todo.append((key, layer, up, down))
+        visited.extend(pair)
+    return todo, visited
+
+
+def _lora_load(checkpoint_path, device):
+    state_dict = torch.load(checkpoint_path)
+    return {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in state_dict.items()}
+
+
+def _lora_delta(layer, up, down, alpha):
+    delta = alpha * torch.mm(up.to(torch.float32), down.to(torch.float32))
+    return delta.unsqueeze(2).unsqueeze(3) if layer.weight.dim() == 4 else delta      # a k x k kernel receives it on every tap (broadcast)
+
+
+@torch.no_grad()
+def net_load_lora(net, checkpoint_path, alpha=1.0, remove=False):
+    """lora.py:620-672: merge (remove=True: subtract) the LoRA file's `alpha * up @ down` into the Linear / Conv2d weights it names,
+    in the parameter's own dtype.  Two differences from the reference: every key is resolved before any weight changes (`_lora_resolve`),
+    and the weights are written with in-place ops on the parameter instead of through `.data` — the same bytes, but the version counter
+    moves, so the next `refresh_weights` re-packs exactly the images that read the touched tensors."""
+    state_dict = _lora_load(checkpoint_path, net.device)
+    todo, visited = _lora_resolve(net, state_dict)
+    for key, layer, up, down in todo:
+        delta = _lora_delta(layer, up, down, alpha)
+        if remove:
+            layer.weight.sub_(delta)
+        else:
+            layer.weight.add_(delta)
+    print("load_weight_num:", len(visited))
+    return
+
+
+def change_lora(model, inject_lora=False, lora_scale=1.0, lora_path='', last_time_lora='', last_time_lora_scale=1.0):
+    """lora.py:674-680: take the previous LoRA out (at its scale), then put the new one in."""
+    if last_time_lora != '':
+        net_load_lora(model, last_time_lora, alpha=last_time_lora_scale, remove=True)
+    if inject_lora:
+        net_load_lora(model, lora_path, alpha=lora_scale)
+
+
+@torch.no_grad()
+def net_load_lora_v2(net, checkpoint_path, alpha=1.0, remove=False, origin_weight=None):
+    """lora.py:683-746: like `net_load_lora`, but the weight of every target is cloned into `origin_weight` (under the key with
+    lora_down / lora_up replaced by 'lora') the first time it is touched, and remove=True restores the clone.  -> origin_weight."""
+    state_dict = _lora_load(checkpoint_path, net.device)
+    todo, visited = _lora_resolve(net, state_dict)
+    for key, layer, up, down in todo:
+        if origin_weight is None:
+            origin_weight = dict()
+        storage_key = key.replace("lora_down", "lora").replace("lora_up", "lora")
+        if storage_key not in origin_weight.keys():
+            origin_weight[storage_key] = layer.weight.detach().clone()
+        if remove:
+            layer.weight.copy_(origin_weight[storage_key])
+        else:
+            layer.weight.add_(_lora_delta(layer, up, down, alpha))
+    print("load_weight_num:", len(visited))
+    return origin_weight
+
+
+def change_lora_v2(model, inject_lora=False, lora_scale=1.0, lora_path='', last_time_lora='', last_time_lora_scale=1.0, origin_weight=None):
+    """lora.py:748-755."""
+    if last_time_lora != '':
+        origin_weight = net_load_lora_v2(model, last_time_lora, alpha=last_time_lora_scale, remove=True, origin_weight=origin_weight)
+    if inject_lora:
+        origin_weight = net_load_lora_v2(model, lora_path, alpha=lora_scale, origin_weight=origin_weight)
+    return origin_weight
 
 
 # ------------------------------------------------------------------------------------------
