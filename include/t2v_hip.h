@@ -183,7 +183,8 @@ enum t2v_gather {
  *      17 out dtype, 18 act (0 none, 1 SiLU, 2 ReLU), 19 split_k, 20 bias_along_m, 21 ldrb,
  *      22 tile (0 = 128x128-class kernel; 1 256x256, 2 256x320, 3 128x256 (8 waves, 3-stage ring), 4 / 5 128x128 with a 4-deep
  *         ring on 4 / 8 waves, 8 / 9 192x320 / 192x256 on 12 waves, 10 = 192x192 on 12 waves, T2V_EPI_TATTN only; 11 = 128x320
- *         on 8 waves, 12 = 64x64 on 4 waves with a 4-deep ring; any other id is refused),
+ *         on 8 waves, 12 = 64x64 on 4 waves with a 4-deep ring; any other id is refused; which tile has which fused epilogue:
+ *         T2V_TILES in csrc/t2v_kernels.h, the table the library dispatches and validates from),
  *      23 tconv halo (input rows are [clip][F+2][HW]: one halo frame either side, T-sharding);
  *         for CONV3X3: 1 = zero padding (0,1,0,1) instead of (1,1,1,1) (LDM encoder Downsample, taps at +0..+2)
  *      30 = R > 0 (ABI 11; every gather mode, split-K allowed, plain / statistics / GroupNorm epilogues): the residual has R rows and row

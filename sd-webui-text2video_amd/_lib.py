@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T2V_LIB_PATH") or os.path.join(_HERE, "libt2v_hip.so")   # T2V_LIB_PATH: A/B builds of the same ABI (tools/build_variant.py)
@@ -60,6 +61,60 @@ GN_ROWS_PER_BLOCK = 64           # T2V_GN_ROWS_PER_BLOCK
 SYNC_INTS = 4096                 # T2V_SYNC_INTS
 SYNC_BARRIER_INTS = 512          # T2V_SYNC_BARRIER_INTS
 GN_PART_BYTES = 2 << 20          # T2V_GN_PART_BYTES
+
+# ---- the GEMM tiles (GEMM i[22]): the mirror of T2V_TILES in csrc/t2v_kernels.h — geometry of every tile id that has a kernel and the
+# fused epilogues it has an instantiation for (tests/test_tile_table.py holds the two tables together through the library's validator)
+TILE_GN, TILE_LNX, TILE_LN, TILE_XATTN, TILE_TATTN_ONLY, TILE_GEMM2 = 1, 2, 4, 8, 16, 32
+
+
+class GemmTile(NamedTuple):
+    bm: int                # rows
+    bn: int                # columns
+    waves: int
+    per_cu: int            # workgroups per CU the co-residency bound of the fused norms assumes
+    features: int          # TILE_GN: T2V_EPI_GN; TILE_LNX: LayerNorm output across column tiles; TILE_LN: LayerNorm output on a whole-row
+    #                        tile (N == bn); TILE_XATTN: T2V_EPI_XATTN; TILE_TATTN_ONLY: T2V_EPI_TATTN and nothing else; TILE_GEMM2: csrc/gemm2.hip
+
+    def has(self, feature: int) -> bool:
+        return bool(self.features & feature)
+
+    def grid(self, M: int, n: int) -> int:
+        """Workgroups of an M x n problem (before split-K)."""
+        return -(-M // self.bm) * -(-n // self.bn)
+
+    def fuses(self, feature: int, n: int) -> bool:
+        """May a GEMM of n columns run fused epilogue `feature` (ONE bit) here?  (t2v_tile_fuses, csrc/t2v_kernels.h)"""
+        if not self.has(feature):
+            return False
+        if feature == TILE_LN or (feature == TILE_XATTN and self.has(TILE_LN)):
+            return n == self.bn                                  # whole rows in the tile
+        if feature == TILE_XATTN:
+            return n % self.bn == 0                              # whole heads per column tile
+        return self.has(TILE_GEMM2) or n % self.bn == 0          # tile 0's narrow form has no fused epilogue: whole 128-wide column tiles only
+
+
+GEMM_TILES = {
+    # tile 0 is csrc/gemm.hip's 128x128-class kernel (any N, the C8 stem); it also has a narrow 128x64 form without fused epilogues (tile0_bn)
+    0: GemmTile(128, 128, 4, 2, TILE_GN | TILE_LNX | TILE_XATTN),
+    1: GemmTile(256, 256, 8, 1, TILE_GEMM2),
+    2: GemmTile(256, 320, 8, 1, TILE_GEMM2 | TILE_LN),
+    3: GemmTile(128, 256, 8, 1, TILE_GEMM2 | TILE_GN | TILE_LNX),                  # 3-stage ring
+    4: GemmTile(128, 128, 4, 1, TILE_GEMM2),                                       # 4-deep ring
+    5: GemmTile(128, 128, 8, 1, TILE_GEMM2 | TILE_GN | TILE_LNX | TILE_XATTN),     # 4-deep ring
+    8: GemmTile(192, 320, 12, 1, TILE_GEMM2 | TILE_GN | TILE_LN | TILE_XATTN),
+    9: GemmTile(192, 256, 12, 1, TILE_GEMM2 | TILE_LNX),
+    10: GemmTile(192, 192, 12, 1, TILE_GEMM2 | TILE_TATTN_ONLY),
+    11: GemmTile(128, 320, 8, 1, TILE_GEMM2 | TILE_GN | TILE_LN | TILE_XATTN),
+    12: GemmTile(64, 64, 4, 2, TILE_GEMM2 | TILE_LNX),                             # 4-deep ring
+}
+GEMM_BK = 64                       # k-tile of every GEMM kernel
+GEMM2_TILES = tuple(t for t, g in GEMM_TILES.items() if g.has(TILE_GEMM2) and not g.has(TILE_TATTN_ONLY))   # gemm2.hip's general-purpose configurations
+
+
+def tile0_bn(n: int) -> int:
+    """The width csrc/gemm.hip's launcher picks: 128x64 when the last 128-wide column tile would be at most half full."""
+    return 64 if (n % 128 != 0 and n % 128 <= 64) else 128
+
 
 EXPORTS = [
     "t2v_abi_version", "t2v_last_error", "t2v_device_info", "t2v_run_ops", "t2v_plan_create",

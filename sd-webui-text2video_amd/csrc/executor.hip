@@ -69,16 +69,17 @@ int validate_op(const t2v_op& op, int idx) {
         return bad("column statistics (T2V_EPI_STATS): strips pointer p[7], no split-K, no fused LayerNorm");
       if (op.i[16] < 0 || op.i[16] > T2V_EPI_XATTN) return bad("unknown epilogue");
       if (op.i[18] < 0 || op.i[18] > 2) return bad("unknown activation (0 none, 1 SiLU, 2 ReLU)");
+      const t2v_tile* tile = t2v_tile_of(op.i[22]);          // geometry and fused epilogues of the tile: the table in t2v_kernels.h
+      if (tile == nullptr) return bad("unknown tile id");
       if (op.i[30] != 0) {       // residual row wrap for every gather mode (ABI 11)
         if (op.i[30] < 0 || M > 2 * op.i[30] || op.p[4] == 0) return bad("residual row wrap i[30]: positive, M <= 2 * wrap, and a residual");
         if (op.i[16] == T2V_EPI_GEGLU || op.i[16] == T2V_EPI_TATTN || op.i[16] == T2V_EPI_XATTN || (g == T2V_GATHER_PLAIN && (op.i[12] != 0 || op.i[8] != 0)))
           return bad("residual row wrap i[30]: plain / statistics / GroupNorm epilogues only, not beside i[12] or a fused LayerNorm");
       }
       if (op.i[16] == T2V_EPI_XATTN) {
-        const int tile = op.i[22];
         if (g != T2V_GATHER_PLAIN || N % 64 != 0 || K % 64 != 0 || op.i[17] != T2V_F16 || op.i[19] > 1 || op.i[18] != 0 || op.i[8] != 0 || op.i[11] == 1)
           return bad("fused cross-attention: plain gather, N = 64 * heads, K % 64 == 0, fp16 out, no split-K / activation / LayerNorm / hi + lo output");
-        if (!(((tile == 8 || tile == 11) && N == 320) || ((tile == 0 || tile == 5) && N % 128 == 0))) return bad("fused cross-attention: tile 8 / 11 with N == 320, or tile 0 / 5 with N % 128 == 0");
+        if (!t2v_tile_fuses(tile, T2V_TILE_XATTN, N)) return bad("fused cross-attention: tile 8 / 11 with N == 320, or tile 0 / 5 with N % 128 == 0");
         if (op.p[2] != 0 || op.p[3] != 0 || op.p[4] != 0 || op.p[8] == 0 || op.p[9] == 0 || !(op.f[1] > 0.f)) return bad("fused cross-attention: no bias / row bias / residual; K, V^T and a positive scale are required");
         if (op.i[25] < 1 || op.i[25] > 96 || op.i[24] < N || op.i[24] % 8 != 0 || op.i[26] < ((op.i[25] + 31) / 32) * 32 || op.i[26] % 8 != 0 || op.i[15] <= 0 || op.i[15] % 32 != 0 || op.i[27] < 0 || op.i[28] < 0)
           return bad("fused cross-attention: 1 .. 96 keys, ld(K) >= N, V^T rows of >= ceil32(keys) halfs, rows per sample a multiple of 32");
@@ -89,8 +90,7 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.i[16] == T2V_EPI_GN) {
         // GroupNorm (+SiLU) of the result inside the epilogue: the tiles with an instantiation, whole 32-row strips per statistics
         // instance, at most two instances per row tile, whole groups, every pointer of the exchange
-        const int tile = op.i[22], rows = op.i[24], groups = op.i[28];
-        const int bm = tile == 8 ? 192 : 128, bn = (tile == 8 || tile == 11) ? 320 : (tile == 3 ? 256 : 128);
+        const int rows = op.i[24], groups = op.i[28], bm = tile->bm, bn = tile->bn;
         if (g == T2V_GATHER_CONV3X3_C8 || (g == T2V_GATHER_CONV3X3 && op.i[12] != 0)) return bad("fused GroupNorm: not for the C8 stem / the upsampling gather");
         if (op.i[20] != 0 || K % 64 != 0 || op.i[18] != 0) return bad("fused GroupNorm: no bias along M, no activation, K % 64 == 0");
         if (g == T2V_GATHER_PLAIN && (op.i[8] != 0 || op.i[11] == 1)) return bad("fused GroupNorm: no fused LayerNorm / hi + lo output on the same op");
@@ -99,8 +99,8 @@ int validate_op(const t2v_op& op, int idx) {
           // split-K: the norm runs in the reduction's launch (one thread per row x 8 channels, any tile)
           if (groups > 32 || N % 8 != 0 || N / 8 > 512 || op.p[6] == 0) return bad("fused GroupNorm on a split-K GEMM: groups <= 32, N % 8 == 0, N <= 4096, a slab workspace");
         } else {
-          if (tile != 8 && tile != 11 && tile != 3 && tile != 5 && tile != 0) return bad("fused GroupNorm: tile must be 8, 11, 3, 5 or 0");
-          if (tile == 0 && N % 128 != 0) return bad("fused GroupNorm on the 128x128-class kernel: N % 128 == 0");
+          if (!tile->has(T2V_TILE_GN)) return bad("fused GroupNorm: tile must be 8, 11, 3, 5 or 0");
+          if (!t2v_tile_fuses(tile, T2V_TILE_GN, N)) return bad("fused GroupNorm on the 128x128-class kernel: N % 128 == 0");
           if (N / groups > bn || (bn + N / groups - 1) / (N / groups) + 1 > T2V_GN_PIECES) return bad("fused GroupNorm: a group no wider than the tile");
           if (rows % 32 != 0 || !(rows >= bm || 2 * rows == bm))
             return bad("fused GroupNorm: rows per instance must be a multiple of 32 and >= the tile's rows (or exactly half of them): at most two instances per row tile");
@@ -112,8 +112,7 @@ int validate_op(const t2v_op& op, int idx) {
       }
       if (op.i[19] > 1 && op.p[6] == 0) return bad("split-K without workspace");
       if (op.p[3] != 0 && op.i[15] <= 0 && !(g == T2V_GATHER_PLAIN && (op.i[8] == 1 || op.i[8] == 2))) return bad("rowbias without rows_per_batch");
-      if (op.i[22] < 0 || op.i[22] > 12 || op.i[22] == 6 || op.i[22] == 7) return bad("unknown tile id");      // the ids with a kernel: 0-5, 8-12
-      if ((op.i[16] == T2V_EPI_TATTN) != (op.i[22] == 10)) return bad("tile 10 is the fused QKV + temporal attention tile (T2V_EPI_TATTN), and only that");
+      if ((op.i[16] == T2V_EPI_TATTN) != tile->has(T2V_TILE_TATTN_ONLY)) return bad("tile 10 is the fused QKV + temporal attention tile (T2V_EPI_TATTN), and only that");
       if (op.i[16] == T2V_EPI_TATTN) {
         const int F = op.i[8], HW = op.i[9], tpix = op.i[10];
         if (g != T2V_GATHER_PLAIN || N % 192 != 0 || K % 64 != 0 || op.i[17] != T2V_F16 || op.i[19] > 1 || op.i[18] != 0)
@@ -135,8 +134,7 @@ int validate_op(const t2v_op& op, int idx) {
           return bad("hi + lo output: fp16 out, plain epilogue, no fused LayerNorm, ldc >= 2 N");
       }
       if (g == T2V_GATHER_PLAIN && op.i[8] == 2) {         // LayerNorm second output across the column tiles (grid barrier)
-        const int tile = op.i[22];
-        if ((tile != 0 && tile != 5 && tile != 12 && tile != 9 && tile != 3) || (tile == 0 && N % 128 != 0) || op.i[19] > 1 || op.i[16] != T2V_EPI_NONE ||
+        if (!t2v_tile_fuses(tile, T2V_TILE_LNX, N) || op.i[19] > 1 || op.i[16] != T2V_EPI_NONE ||
             op.i[17] != T2V_F32 || op.i[18] != 0 || op.i[20] != 0 || K % 64 != 0 || op.i[11] == 1)
           return bad("cross-tile LayerNorm output: tile 0 (N % 128 == 0), 3, 5, 9 or 12, fp32 out, plain epilogue, no split-K / activation");
         if (op.p[3] == 0 || op.p[7] == 0 || op.p[10] == 0 || op.p[11] == 0 || op.i[9] < N || op.i[9] % 4 != 0)
@@ -144,7 +142,7 @@ int validate_op(const t2v_op& op, int idx) {
         if (op.i[5] < N || (op.p[4] != 0 && (op.i[6] < N || op.i[6] % 4 != 0))) return bad("cross-tile LayerNorm output: ldc / ldr must be >= N and multiples of 4");
       }
       if (g == T2V_GATHER_PLAIN && op.i[8] == 1) {
-        if ((op.i[22] != 8 && op.i[22] != 11 && op.i[22] != 2) || N != 320 || op.i[19] > 1 || op.i[16] != T2V_EPI_NONE || op.i[17] != T2V_F32 || op.i[18] != 0 || op.i[20] != 0 ||
+        if (!t2v_tile_fuses(tile, T2V_TILE_LN, N) || op.i[19] > 1 || op.i[16] != T2V_EPI_NONE || op.i[17] != T2V_F32 || op.i[18] != 0 || op.i[20] != 0 ||
             K % 64 != 0)
           return bad("fused LayerNorm output needs a whole-row tile (192x320, 128x320 or 256x320), N == 320, fp32 out, no split-K / activation");
         if (op.p[3] == 0 || op.p[7] == 0 || op.i[9] < N || op.i[9] % 4 != 0) return bad("fused LayerNorm output: gamma|beta, output pointer or leading dimension");
@@ -375,7 +373,8 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
     case T2V_OP_GEMM: {
       GemmParams p = gemm_params(op);
       const int tile = op.i[22];
-      if (p.epi == T2V_EPI_TATTN) {                              // fused QKV projection + temporal attention (tile 10)
+      const t2v_tile* tt = t2v_tile_of(tile);
+      if (p.epi == T2V_EPI_TATTN) {                              // fused QKV projection + temporal attention (validated: its own tile)
         p.F = op.i[8]; p.HW = op.i[9]; p.tpix = op.i[10];
         p.tiles_ps = (p.HW + p.tpix - 1) / p.tpix;
         p.attn_scale_log2 = op.f[1] * 1.44269504088896340736f;
@@ -392,7 +391,7 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
       }
       const bool ln_any = p.gather == T2V_GATHER_PLAIN && (op.i[8] == 1 || op.i[8] == 2);
       if (p.splitk > 1 && !ln_any) p.tickets = reinterpret_cast<int*>(op.p[7]);
-      if (ln_any) {       // fused LayerNorm second output (validated: tile 8 / 11, N == 320 — or, i[8] == 2, across column tiles; TATTN returned above)
+      if (ln_any) {       // fused LayerNorm second output (validated: a whole-row tile, N == its columns — or, i[8] == 2, across column tiles; TATTN returned above)
         p.ln_gb = reinterpret_cast<const float*>(op.p[3]);
         p.rowbias = nullptr;
         p.ln_out = reinterpret_cast<f16*>(op.p[7]);
@@ -408,7 +407,7 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
         }
       }
       // the large-tile kernel advances its source pointers by whole k-tiles: needs K % BK == 0
-      if (tile >= 1 && tile != 10 && p.gather != T2V_GATHER_CONV3X3_C8 && p.K % 64 == 0) return t2v_launch_gemm2(p, tile, s);
+      if (tt != nullptr && tt->has(T2V_TILE_GEMM2) && !tt->has(T2V_TILE_TATTN_ONLY) && p.gather != T2V_GATHER_CONV3X3_C8 && p.K % 64 == 0) return t2v_launch_gemm2(p, tile, s);
       return t2v_launch_gemm(p, s);
     }
     case T2V_OP_GROUPNORM: return t2v_launch_groupnorm(op, s);

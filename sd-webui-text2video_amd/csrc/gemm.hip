@@ -86,10 +86,9 @@ __device__ __forceinline__ void epilogue_store_geglu(const GemmParams& p, int m,
   *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.out) + (size_t)m * p.ldc + n_out) = o;
 }
 
-// XE = 2: the plain epilogue is t2v_epilogue_rows_gn — GroupNorm (+SiLU) of the result inside the epilogue, statistics across the launch's
-// workgroups at a grid barrier (T2V_EPI_GN; its own instantiations, launched only on a co-resident grid); XE = 3: t2v_epilogue_rows_lnx, the
-// LayerNorm second output across the launch's column tiles (same exchange along the rows)
-template <int BM, int BN, int WM, int WN, int GATHER, int XE = 0>
+// XE: extra epilogue of the plain path, one of T2V_XE_* (t2v_kernels.h) — T2V_XE_GN and T2V_XE_LNX exchange statistics across the
+// launch's workgroups at a grid barrier (their own instantiations, launched only on a co-resident grid)
+template <int BM, int BN, int WM, int WN, int GATHER, int XE = T2V_XE_NONE>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) {
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM / 32;       // 32-row token tiles per wave
@@ -264,15 +263,15 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
   // gemm2.hip's TAT instantiation); everything else the executor has folded into NONE plus the pointers of the XE epilogues.
   if (p.epi == T2V_EPI_NONE) {      // row-coalesced through a per-wave LDS buffer (t2v_kernels.h); also the split-K slabs
     __syncthreads();                // every wave is done reading the operand stages
-    if constexpr (XE == 2) {
+    if constexpr (XE == T2V_XE_GN) {
       t2v_epilogue_rows_gn<WM, WN, TM, TN>(p, acc, smem, lane, wave, m0, n0, tile_m, tile_n, tiles_m, tiles_n);
       return;
     }
-    if constexpr (XE == 3) {
+    if constexpr (XE == T2V_XE_LNX) {
       t2v_epilogue_rows_lnx<WM, WN, TM, TN>(p, acc, smem, lane, wave, m0, n0, tile_m, tile_n, tiles_n);
       return;
     }
-    if constexpr (XE == 4) {
+    if constexpr (XE == T2V_XE_XATTN) {
       t2v_epilogue_xattn<WM, WN, TM, TN>(p, acc, smem, lane, wave, m0, n0);
       return;
     }
@@ -337,7 +336,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) 
 constexpr int lds_of(int bm, int bn) { return 2 * (bm + bn) * BK * 2; }      // the two operand stages
 
 // One launch of one instantiation; the function-local flag = once per (instantiation, device).
-template <int BM, int BN, int WM, int WN, int GATHER, int XE = 0>
+template <int BM, int BN, int WM, int WN, int GATHER, int XE = T2V_XE_NONE>
 hipError_t launch_one(const GemmParams& p, hipStream_t s) {
   constexpr int lds = lds_of(BM, BN);
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
@@ -348,7 +347,7 @@ hipError_t launch_one(const GemmParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-// The fused-norm instantiations (XE = 2 GroupNorm, 3 cross-tile LayerNorm): the grid barrier needs the whole launch resident — the grid
+// The fused-norm instantiations (T2V_XE_GN, T2V_XE_LNX): the grid barrier needs the whole launch resident — the grid
 // within what the occupancy API grants this instantiation on the stream's device (cached per instantiation and device); a grid the device
 // does not hold co-resident is cut into row chunks of whole tiles and whole instances (round 6)
 template <int BM, int BN, int WM, int WN, int GATHER, int XE>
@@ -359,35 +358,39 @@ hipError_t launch_norm(const GemmParams& p, hipStream_t s) {
   static int occ[T2V_MAX_DEVICES] = {};
   (void)t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, once, s);
   const long cap = t2v_grid_capacity(reinterpret_cast<const void*>(k), WM * WN * 64, lds, s, occ);
-  return t2v_launch_coresident(p, BM, (p.N + BN - 1) / BN, cap, XE == 3 ? BM : t2v_lcm(BM, p.gn_rows), XE == 3 ? BM * 16 : 2 * T2V_GN_PIECES * 16,
+  return t2v_launch_coresident(p, BM, (p.N + BN - 1) / BN, cap, XE == T2V_XE_LNX ? BM : t2v_lcm(BM, p.gn_rows), XE == T2V_XE_LNX ? BM * 16 : 2 * T2V_GN_PIECES * 16,
                                [&](const GemmParams& q, int nwg) {
     hipLaunchKernelGGL(k, dim3(nwg, 1), dim3(WM * WN * 64), lds, s, q);
     return hipGetLastError();
   });
 }
 
+// Tile 0 of the table (t2v_kernels.h) in its two forms; only the full-width one carries the entry's fused epilogues
 template <int BM, int BN, int WM, int WN>
 hipError_t launch_tile(const GemmParams& pin, hipStream_t s) {
+  constexpr t2v_tile T = *t2v_tile_of(0);
+  constexpr bool FUSED = BN == T.bn;
+  static_assert(!T.has(T2V_TILE_GEMM2) && T.bm == BM && T.waves == WM * WN && (FUSED || BN == T2V_TILE0_NARROW_BN), "the configuration is not the table's tile");
   GemmParams p = pin;
   p.panel = t2v_choose_panel(p, (p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
-  if (p.xa_k != nullptr) {         // fused to_q + text cross-attention (T2V_EPI_XATTN): the 128x128 tile = two heads per column tile, plain gather
-    if constexpr (BM == 128 && BN == 128) {
+  if (p.xa_k != nullptr) {         // fused to_q + text cross-attention (T2V_EPI_XATTN): two heads per column tile, plain gather
+    if constexpr (FUSED && T.has(T2V_TILE_XATTN)) {
       static_assert(t2v_xattn_epilogue_lds(BM, BN) <= lds_of(BM, BN), "Q [BM][BN] fp16 re-uses the operand stages");
       if (p.splitk != 1 || p.gather != T2V_GATHER_PLAIN) return hipErrorInvalidValue;
-      return launch_one<BM, BN, WM, WN, T2V_GATHER_PLAIN, 4>(p, s);
+      return launch_one<BM, BN, WM, WN, T2V_GATHER_PLAIN, T2V_XE_XATTN>(p, s);
     }
     return hipErrorInvalidValue;
   }
   if ((p.gn_out != nullptr && p.splitk == 1) || p.ln_x) {
-    // GroupNorm / cross-tile LayerNorm inside the epilogue: the 128x128 tile only, no split-K
-    if constexpr (BM == 128 && BN == 128) {
+    // GroupNorm / cross-tile LayerNorm inside the epilogue: no split-K
+    if constexpr (FUSED && T.has(T2V_TILE_GN) && T.has(T2V_TILE_LNX)) {
       static_assert(t2v_gn_epilogue_lds(WM * WN, BM / 32, BN) <= lds_of(BM, BN) && t2v_lnx_epilogue_lds(WM * WN, WN, BM) <= lds_of(BM, BN),
                     "the norm epilogues re-use the operand stages");
       if (p.splitk != 1 || !t2v_coop_allowed() || p.gather == T2V_GATHER_CONV3X3_C8) return hipErrorInvalidValue;
-      if (p.ln_x) return p.gather == T2V_GATHER_PLAIN ? launch_norm<BM, BN, WM, WN, T2V_GATHER_PLAIN, 3>(p, s) : hipErrorInvalidValue;
-      if (p.gather == T2V_GATHER_PLAIN) return launch_norm<BM, BN, WM, WN, T2V_GATHER_PLAIN, 2>(p, s);
-      if (p.gather == T2V_GATHER_CONV3X3) return launch_norm<BM, BN, WM, WN, T2V_GATHER_CONV3X3, 2>(p, s);
-      if (p.gather == T2V_GATHER_TCONV3) return launch_norm<BM, BN, WM, WN, T2V_GATHER_TCONV3, 2>(p, s);
+      if (p.ln_x) return p.gather == T2V_GATHER_PLAIN ? launch_norm<BM, BN, WM, WN, T2V_GATHER_PLAIN, T2V_XE_LNX>(p, s) : hipErrorInvalidValue;
+      if (p.gather == T2V_GATHER_PLAIN) return launch_norm<BM, BN, WM, WN, T2V_GATHER_PLAIN, T2V_XE_GN>(p, s);
+      if (p.gather == T2V_GATHER_CONV3X3) return launch_norm<BM, BN, WM, WN, T2V_GATHER_CONV3X3, T2V_XE_GN>(p, s);
+      if (p.gather == T2V_GATHER_TCONV3) return launch_norm<BM, BN, WM, WN, T2V_GATHER_TCONV3, T2V_XE_GN>(p, s);
     }
     return hipErrorInvalidValue;
   }
@@ -416,8 +419,8 @@ hipError_t t2v_launch_gemm(const GemmParams& pin, hipStream_t s) {
   hipError_t e;
   // Tile choice: 128x128 by default; 128x64 when the last 128-wide column tile would be at
   // most half full (N = 320, 960, 4, 8 ...), to avoid 25-97 % padded columns.
-  const bool narrow = (p.N % 128 != 0) && (p.N % 128 <= 64);
-  const int bn = narrow ? 64 : 128;
+  const bool narrow = t2v_tile0_narrow(p.N);
+  const int bn = narrow ? T2V_TILE0_NARROW_BN : 128;
   t2v_normalize_splitk(p, BK, (long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn));
   if (narrow)
     e = launch_tile<128, 64, 4, 1>(p, s);

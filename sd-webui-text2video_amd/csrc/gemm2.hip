@@ -27,7 +27,6 @@ __device__ __attribute__((aligned(256))) unsigned char g2_zero_page[256];
 
 // internal gather id: 3x3 conv with the nearest-2x upsample folded in (no affine tap offset)
 constexpr int G_CONV_UP = 100;
-constexpr int BM_OF(int wm, int tm) { return wm * tm * 32; }
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -35,9 +34,9 @@ __device__ __forceinline__ void wait_vmcnt() {
 }
 
 // WM x WN waves; each wave owns TM x TN MFMA tiles (32 tokens x 32 channels each).
-// XE: extra epilogue of the plain (T2V_EPI_NONE) path — 0 none, 1 fused LayerNorm second output (whole-row tiles), 2 fused GroupNorm
-// (+SiLU) of the result with a grid barrier (T2V_EPI_GN); separate instantiations, so the plain kernels keep their register budgets.
-template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int XE = 0, bool TAT = false>
+// XE: extra epilogue of the plain (T2V_EPI_NONE) path, one of T2V_XE_* (t2v_kernels.h); separate instantiations, so the plain kernels
+// keep their register budgets.
+template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int XE = T2V_XE_NONE, bool TAT = false>
 __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmParams p) {
   constexpr int NW = WM * WN;
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -411,19 +410,19 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
   }
   if (p.epi == T2V_EPI_NONE) {      // row-coalesced through a per-wave LDS buffer (t2v_kernels.h); also the split-K slabs
     __builtin_amdgcn_s_barrier();   // every wave is done reading the operand stages
-    if constexpr (XE == 2) {        // GroupNorm (+SiLU) of the result inside the epilogue: statistics meet at a grid barrier (t2v_kernels.h)
+    if constexpr (XE == T2V_XE_GN) {        // GroupNorm (+SiLU) of the result inside the epilogue: statistics meet at a grid barrier (t2v_kernels.h)
       t2v_epilogue_rows_gn<WM, WN, TM, TN>(p, acc, smem, lane, wave, m0, n0, tile_m, tile_n, tiles_m, tiles_n);
       return;
     }
-    if constexpr (XE == 4) {        // to_q projection + text cross-attention: the accumulators are Q (T2V_EPI_XATTN, t2v_kernels.h)
+    if constexpr (XE == T2V_XE_XATTN) {        // to_q projection + text cross-attention: the accumulators are Q (T2V_EPI_XATTN, t2v_kernels.h)
       t2v_epilogue_xattn<WM, WN, TM, TN>(p, acc, smem, lane, wave, m0, n0);
       return;
     }
-    if constexpr (XE == 3) {        // LayerNorm second output across the column tiles of the launch (partial row sums meet at the grid barrier)
+    if constexpr (XE == T2V_XE_LNX) {        // LayerNorm second output across the column tiles of the launch (partial row sums meet at the grid barrier)
       t2v_epilogue_rows_lnx<WM, WN, TM, TN>(p, acc, smem, lane, wave, m0, n0, tile_m, tile_n, tiles_n);
       return;
     }
-    if constexpr (XE == 1) {        // whole rows in this tile (192x320, N == 320, validated by the executor): fused LayerNorm output
+    if constexpr (XE == T2V_XE_LN) {        // whole rows in this tile (N == its columns, validated by the executor): fused LayerNorm output
       float* fs = reinterpret_cast<float*>(smem);
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) {            // (TM == 2: the 256x320 tile, round 6 — a wave's two 32-row blocks one after the other)
@@ -492,7 +491,7 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
   t2v_store_splitk_slab<TM, TN>(p, acc, lane, m0 + wm * TM * 32, n0 + wn * TN * 32, blockIdx.y);
 }
 
-template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int XE = 0, bool TAT = false>
+template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int XE = T2V_XE_NONE, bool TAT = false>
 hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   // TAT: the attention epilogue re-uses the operand ring for q | k (BM x 272 B) and V^T (<= 12 pixels x 64 x 72 B)
@@ -501,7 +500,7 @@ hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
   constexpr int lnx_lds = t2v_lnx_epilogue_lds(WM * WN, WN, BM);
   constexpr int xa_lds = t2v_xattn_epilogue_lds(BM, BN);
   constexpr int lds = TAT ? (BM * 272 + 12 * 64 * 72 > ring ? BM * 272 + 12 * 64 * 72 : ring)
-                          : (XE == 2 && gn_lds > ring ? gn_lds : (XE == 3 && lnx_lds > ring ? lnx_lds : (XE == 4 && xa_lds > ring ? xa_lds : ring)));
+                          : (XE == T2V_XE_GN && gn_lds > ring ? gn_lds : (XE == T2V_XE_LNX && lnx_lds > ring ? lnx_lds : (XE == T2V_XE_XATTN && xa_lds > ring ? xa_lds : ring)));
   const int tiles_n = (p.N + BN - 1) / BN;
   const int tiles = ((p.M - p.m_begin + BM - 1) / BM) * tiles_n;
   auto k = gemm2_kernel<WM, WN, TM, TN, BK, STAGES, MINW, GATHER, XE, TAT>;
@@ -510,14 +509,14 @@ hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
     const hipError_t e = t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, attr_set, s);
     if (e != hipSuccess) return e;
   }
-  if constexpr (XE == 2 || XE == 3) {
+  if constexpr (XE == T2V_XE_GN || XE == T2V_XE_LNX) {
     // the epilogue's grid barrier needs every workgroup of the launch resident: no split-K, and the grid within what the occupancy
     // API grants this instantiation on the stream's device (cached); a process in which a barrier already timed out stays off it
     // (round 6: a grid larger than that is cut into row chunks of whole tiles AND whole statistics instances, one launch each)
     static int occ[T2V_MAX_DEVICES] = {};
     if (p.splitk != 1 || !t2v_coop_allowed()) return hipErrorCooperativeLaunchTooLarge;
     const long cap = t2v_grid_capacity(reinterpret_cast<const void*>(k), WM * WN * 64, lds, s, occ);
-    return t2v_launch_coresident(p, BM, tiles_n, cap, XE == 2 ? t2v_lcm(BM, p.gn_rows) : BM, XE == 2 ? 2 * T2V_GN_PIECES * 16 : BM * 16,
+    return t2v_launch_coresident(p, BM, tiles_n, cap, XE == T2V_XE_GN ? t2v_lcm(BM, p.gn_rows) : BM, XE == T2V_XE_GN ? 2 * T2V_GN_PIECES * 16 : BM * 16,
                                  [&](const GemmParams& q, int nwg) {
       hipLaunchKernelGGL(k, dim3(nwg, 1), dim3(WM * WN * 64), lds, s, q);
       return hipGetLastError();
@@ -527,73 +526,65 @@ hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW>
+// One configuration of the kernel = one entry of the tile table (t2v_kernels.h): which fused epilogues it is instantiated with is the
+// entry's feature mask, and the executor has validated the record against the same entry.
+template <int TILE, int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW>
 hipError_t launch_cfg(const GemmParams& pin, hipStream_t s) {
+  constexpr t2v_tile T = *t2v_tile_of(TILE);
+  static_assert(T.has(T2V_TILE_GEMM2) && T.bm == WM * TM * 32 && T.bn == WN * TN * 32 && T.waves == WM * WN, "the configuration is not the table's tile");
   GemmParams p = pin;
   // the kernel's epilogue knows these and no other (the executor folds STATS / GN / XATTN into NONE + their pointers before it launches);
-  // TATTN: the plain gather only, and below only the 192x192 configuration takes it
+  // TATTN: the plain gather only, and below only the temporal-attention tile takes it
   if (p.epi != T2V_EPI_NONE && p.epi != T2V_EPI_GEGLU && !(p.epi == T2V_EPI_TATTN && p.gather == T2V_GATHER_PLAIN)) return hipErrorInvalidValue;
   {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    const int tiles_m = (p.M + T.bm - 1) / T.bm, tiles_n = (p.N + T.bn - 1) / T.bn;
     p.panel = t2v_choose_panel(p, tiles_m, tiles_n);
     t2v_normalize_splitk(p, BK, (long)tiles_m * tiles_n);
   }
-  // tiles with a T2V_EPI_GN instantiation (validated by the executor): the whole-row tiles 8 / 11, and the 128-row tiles 3 / 5
-  constexpr bool GN_TILE = ((WM == 6 || WM == 4) && WN == 2 && TM == 1 && TN == 5) || (WM == 2 && WN == 4 && TM == 2 && (TN == 1 || TN == 2));
   // (with split-K the norm runs in the reduction's launch instead: any tile, t2v_launch_splitk_reduce_gn below)
   const bool gn_here = p.gn_out != nullptr && p.splitk == 1;
-  if (gn_here && (!GN_TILE || (p.gather == T2V_GATHER_CONV3X3 && p.up))) return hipErrorInvalidValue;
-  // ... and with a cross-tile LayerNorm instantiation: 5 (128x128), 12 (64x64), 9 (192x256), 3 (128x256); plain gather only
-  constexpr bool LNX_TILE = (WM == 2 && WN == 4 && TM == 2 && (TN == 1 || TN == 2)) || (WM == 2 && WN == 2 && TM == 1 && TN == 1) ||
-                            (WM == 6 && WN == 2 && TM == 1 && TN == 4);
-  if (p.ln_x && (!LNX_TILE || p.gather != T2V_GATHER_PLAIN)) return hipErrorInvalidValue;
+  if (gn_here && (!T.has(T2V_TILE_GN) || (p.gather == T2V_GATHER_CONV3X3 && p.up))) return hipErrorInvalidValue;
+  if (p.ln_x && (!T.has(T2V_TILE_LNX) || p.gather != T2V_GATHER_PLAIN)) return hipErrorInvalidValue;      // cross-tile LayerNorm: plain gather only
   hipError_t e;
   switch (p.gather) {
     case T2V_GATHER_PLAIN:
-      if constexpr (WM == 6 && WN == 2 && TM == 1 && TN == 3) {
-        if (p.epi != T2V_EPI_TATTN || p.splitk != 1 || p.tpix < 1 || p.tpix > 12 || p.tpix * p.F > BM_OF(WM, TM) || p.F > 32) return hipErrorInvalidValue;
-        e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 0, true>(p, s);
+      if constexpr (T.has(T2V_TILE_TATTN_ONLY)) {
+        if (p.epi != T2V_EPI_TATTN || p.splitk != 1 || p.tpix < 1 || p.tpix > 12 || p.tpix * p.F > T.bm || p.F > 32) return hipErrorInvalidValue;
+        e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, T2V_XE_NONE, true>(p, s);
         break;
       }
       if (p.epi == T2V_EPI_TATTN) return hipErrorInvalidValue;
-      if constexpr ((WM == 6 || WM == 4) && WN == 2 && TM == 1 && TN == 5) {      // whole-row tiles: 192x320 / 128x320
-        if (p.xa_k != nullptr) {      // fused to_q + text cross-attention (validated: N == 320 = 5 heads, fp16 out, no split-K)
-          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 4>(p, s);
-          break;
-        }
-      }
-      if constexpr (WM == 2 && WN == 4 && TM == 2 && TN == 1) {                  // 128x128 on 8 waves (tile 5): two heads per column tile
-        if (p.xa_k != nullptr) {
-          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 4>(p, s);
+      if constexpr (T.has(T2V_TILE_XATTN)) {
+        if (p.xa_k != nullptr) {      // fused to_q + text cross-attention (validated: whole heads per column tile, fp16 out, no split-K)
+          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, T2V_XE_XATTN>(p, s);
           break;
         }
       }
       if (p.xa_k != nullptr) return hipErrorInvalidValue;
-      if constexpr ((WM == 6 || WM == 4) && WN == 2 && (TM == 1 || (WM == 4 && TM == 2)) && TN == 5) {      // whole-row tiles: 192x320 / 128x320 / 256x320
+      if constexpr (T.has(T2V_TILE_LN)) {
         if (p.ln_out != nullptr) {
-          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 1>(p, s);
+          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, T2V_XE_LN>(p, s);
           break;
         }
       }
-      if constexpr (GN_TILE) {
-        if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 2>(p, s); break; }
+      if constexpr (T.has(T2V_TILE_GN)) {
+        if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, T2V_XE_GN>(p, s); break; }
       }
-      if constexpr (LNX_TILE) {
-        if (p.ln_x) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, 3>(p, s); break; }
+      if constexpr (T.has(T2V_TILE_LNX)) {
+        if (p.ln_x) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN, T2V_XE_LNX>(p, s); break; }
       }
       e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN>(p, s);
       break;
     case T2V_GATHER_CONV3X3:
-      if constexpr (GN_TILE) {
-        if (gn_here && !p.up) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, 2>(p, s); break; }
+      if constexpr (T.has(T2V_TILE_GN)) {
+        if (gn_here && !p.up) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, T2V_XE_GN>(p, s); break; }
       }
       if (p.up) e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, G_CONV_UP>(p, s);
       else e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3>(p, s);
       break;
     case T2V_GATHER_TCONV3:
-      if constexpr (GN_TILE) {
-        if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_TCONV3, 2>(p, s); break; }
+      if constexpr (T.has(T2V_TILE_GN)) {
+        if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_TCONV3, T2V_XE_GN>(p, s); break; }
       }
       e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_TCONV3>(p, s);
       break;
@@ -790,23 +781,23 @@ hipError_t t2v_launch_ff_fused(const GemmParams& p1, const GemmParams& p2, hipSt
   return hipGetLastError();
 }
 
-// tile ids (t2v_op.i[22]):  1 = 256x256, 2 = 256x320, 8 = 192x320 / 9 = 192x256 (12 waves), 11 = 128x320 (8 waves), 3 = 128x256 (8 waves), 4 / 5 = 128x128 with a 4-deep ring
-// (few-row levels: latency-bound, keep 96 KiB per CU in flight) — 64-wide k-tiles
-// (full 128-byte lines per row = one conv reduction chunk), 2-3 stage ring, one workgroup per CU.
+// One case per gemm2.hip entry of the tile table (t2v_kernels.h: geometry and fused epilogues; launch_cfg checks the numbers below
+// against it): waves as WM x WN, MFMA tiles per wave as TM x TN, 64-wide k-tiles (full 128-byte lines per row = one conv reduction
+// chunk), ring depth, waves per SIMD.
 hipError_t t2v_launch_gemm2(const GemmParams& p, int tile, hipStream_t s) {
   switch (tile) {
-    case 1: return launch_cfg<2, 4, 4, 2, 64, 2, 2>(p, s);   // 2 x 64 KiB
-    case 2: return launch_cfg<4, 2, 2, 5, 64, 2, 2>(p, s);   // 2 x 72 KiB
-    case 3: return launch_cfg<2, 4, 2, 2, 64, 3, 2>(p, s);   // 3 x 48 KiB
-    case 4: return launch_cfg<2, 2, 2, 2, 64, 4, 1>(p, s);   // 128x128, 4 waves, 4 x 32 KiB: 3 k-tiles in flight
-    case 5: return launch_cfg<2, 4, 2, 1, 64, 4, 2>(p, s);   // 128x128, 8 waves, 4 x 32 KiB
-    case 8: return launch_cfg<6, 2, 1, 5, 64, 2, 3>(p, s);   // 192x320, 12 waves (3 per SIMD), 2 x 64 KiB: M = 49152 -> exactly 256 workgroups
-    case 9: return launch_cfg<6, 2, 1, 4, 64, 2, 3>(p, s);   // 192x256, 12 waves, 2 x 56 KiB (N = 256 * j where 256-row grids fill badly)
-    case 10: return launch_cfg<6, 2, 1, 3, 64, 2, 3>(p, s);  // 192x192, 12 waves: fused QKV projection + temporal attention (T2V_EPI_TATTN only)
-    case 12: return launch_cfg<2, 2, 1, 1, 64, 4, 2>(p, s);  // 64x64, 4 waves, 4 x 16 KiB (2 workgroups per CU): the 4x4 level (M = 768) as 240 tiles with the
-                                                             // FULL reduction each — no split-K slabs, no reduction launch (experiment, round 4)
-    case 11: return launch_cfg<4, 2, 1, 5, 64, 2, 2>(p, s);  // 128x320, 8 waves (2 per SIMD), 2 x 56 KiB: M = 32768 (VideoCrafter, 16 frames) -> exactly
-                                                             // 256 workgroups where 192-row tiles make 171; also the b = 1 per-GPU shapes (M = 24576 -> 192)
+    case 1: return launch_cfg<1, 2, 4, 4, 2, 64, 2, 2>(p, s);   // 2 x 64 KiB
+    case 2: return launch_cfg<2, 4, 2, 2, 5, 64, 2, 2>(p, s);   // 2 x 72 KiB
+    case 3: return launch_cfg<3, 2, 4, 2, 2, 64, 3, 2>(p, s);   // 3 x 48 KiB
+    case 4: return launch_cfg<4, 2, 2, 2, 2, 64, 4, 1>(p, s);   // 4 x 32 KiB: 3 k-tiles in flight (few-row levels: latency-bound, keep 96 KiB per CU in flight)
+    case 5: return launch_cfg<5, 2, 4, 2, 1, 64, 4, 2>(p, s);   // 4 x 32 KiB
+    case 8: return launch_cfg<8, 6, 2, 1, 5, 64, 2, 3>(p, s);   // 3 waves per SIMD, 2 x 64 KiB: M = 49152 -> exactly 256 workgroups
+    case 9: return launch_cfg<9, 6, 2, 1, 4, 64, 2, 3>(p, s);   // 2 x 56 KiB (N = 256 * j where 256-row grids fill badly)
+    case 10: return launch_cfg<10, 6, 2, 1, 3, 64, 2, 3>(p, s); // fused QKV projection + temporal attention
+    case 12: return launch_cfg<12, 2, 2, 1, 1, 64, 4, 2>(p, s); // 4 x 16 KiB (2 workgroups per CU): the 4x4 level (M = 768) as 240 tiles with the
+                                                                // FULL reduction each — no split-K slabs, no reduction launch (experiment, round 4)
+    case 11: return launch_cfg<11, 4, 2, 1, 5, 64, 2, 2>(p, s); // 2 per SIMD, 2 x 56 KiB: M = 32768 (VideoCrafter, 16 frames) -> exactly
+                                                                // 256 workgroups where 192-row tiles make 171; also the b = 1 per-GPU shapes (M = 24576 -> 192)
     default: return hipErrorInvalidValue;
   }
 }

@@ -239,6 +239,63 @@ inline void t2v_normalize_splitk(GemmParams& p, int bk, long tiles) {
   if (p.splitk <= 1 || p.epi != T2V_EPI_NONE || tiles > T2V_SYNC_INTS || p.gn_out != nullptr) p.tickets = nullptr;
 }
 
+// ---- the GEMM tiles (t2v_op.i[22]) ----------------------------------------------------------------------------------------------------
+// ONE entry per tile id that has a kernel: its geometry and the fused epilogues it has an instantiation for.  The dispatchers (gemm.hip,
+// gemm2.hip) instantiate from it and executor.hip validates against it; GEMM_TILES in program.py is the same table for the lowering
+// (tests/test_tile_table.py holds the two together through the validator).
+// XE, the extra epilogue of a T2V_EPI_NONE instantiation (an int template parameter of gemm_kernel / gemm2_kernel):
+enum : int {
+  T2V_XE_NONE = 0,
+  T2V_XE_LN = 1,       // LayerNorm second output, whole rows in the tile (t2v_epilogue_rows_ln)
+  T2V_XE_GN = 2,       // GroupNorm (+SiLU) of the result, statistics across the launch at a grid barrier (T2V_EPI_GN, t2v_epilogue_rows_gn)
+  T2V_XE_LNX = 3,      // LayerNorm second output across the column tiles of the launch (t2v_epilogue_rows_lnx)
+  T2V_XE_XATTN = 4,    // to_q projection + text cross-attention (T2V_EPI_XATTN, t2v_epilogue_xattn)
+};
+enum : unsigned {
+  T2V_TILE_GN = 1u << 0,           // has the T2V_XE_GN instantiations (plain, 3x3 and temporal gathers)
+  T2V_TILE_LNX = 1u << 1,          // ... T2V_XE_LNX (plain gather)
+  T2V_TILE_LN = 1u << 2,           // ... T2V_XE_LN: a whole-row tile (N == columns)
+  T2V_TILE_XATTN = 1u << 3,        // ... T2V_XE_XATTN
+  T2V_TILE_TATTN_ONLY = 1u << 4,   // runs T2V_EPI_TATTN and nothing else
+  T2V_TILE_GEMM2 = 1u << 5,        // a configuration of gemm2.hip (else gemm.hip's kernel)
+};
+struct t2v_tile {
+  int id, bm, bn, waves;
+  int per_cu;                      // workgroups per CU the lowering's co-residency bound assumes
+  unsigned features;
+  constexpr bool has(unsigned f) const { return (features & f) != 0; }
+};
+inline constexpr t2v_tile T2V_TILES[] = {
+    // Tile 0 is the 128x128-class kernel of gemm.hip.  It ALSO has a narrow 128x64 form, taken when the last 128-wide column tile would
+    // be at most half full (t2v_tile0_narrow); that form has no fused instantiation, so the fused epilogues of tile 0 need N % 128 == 0.
+    {0, 128, 128, 4, 2, T2V_TILE_GN | T2V_TILE_LNX | T2V_TILE_XATTN},
+    {1, 256, 256, 8, 1, T2V_TILE_GEMM2},
+    {2, 256, 320, 8, 1, T2V_TILE_GEMM2 | T2V_TILE_LN},
+    {3, 128, 256, 8, 1, T2V_TILE_GEMM2 | T2V_TILE_GN | T2V_TILE_LNX},
+    {4, 128, 128, 4, 1, T2V_TILE_GEMM2},
+    {5, 128, 128, 8, 1, T2V_TILE_GEMM2 | T2V_TILE_GN | T2V_TILE_LNX | T2V_TILE_XATTN},
+    {8, 192, 320, 12, 1, T2V_TILE_GEMM2 | T2V_TILE_GN | T2V_TILE_LN | T2V_TILE_XATTN},
+    {9, 192, 256, 12, 1, T2V_TILE_GEMM2 | T2V_TILE_LNX},
+    {10, 192, 192, 12, 1, T2V_TILE_GEMM2 | T2V_TILE_TATTN_ONLY},
+    {11, 128, 320, 8, 1, T2V_TILE_GEMM2 | T2V_TILE_GN | T2V_TILE_LN | T2V_TILE_XATTN},
+    {12, 64, 64, 4, 2, T2V_TILE_GEMM2 | T2V_TILE_LNX},
+};
+constexpr int T2V_TILE0_NARROW_BN = 64;
+constexpr bool t2v_tile0_narrow(int N) { return N % 128 != 0 && N % 128 <= T2V_TILE0_NARROW_BN; }
+// the entry of a tile id; nullptr for an id without a kernel
+constexpr const t2v_tile* t2v_tile_of(int id) {
+  for (const t2v_tile& t : T2V_TILES)
+    if (t.id == id) return &t;
+  return nullptr;
+}
+// May a GEMM of N columns run fused epilogue `feature` (ONE bit) on tile t?
+constexpr bool t2v_tile_fuses(const t2v_tile* t, unsigned feature, int N) {
+  if (t == nullptr || !t->has(feature)) return false;
+  if (feature == T2V_TILE_LN || (feature == T2V_TILE_XATTN && t->has(T2V_TILE_LN))) return N == t->bn;   // whole rows in the tile
+  if (feature == T2V_TILE_XATTN) return N % t->bn == 0;                                                   // whole heads per column tile
+  return t->has(T2V_TILE_GEMM2) || N % t->bn == 0;                                                        // gemm.hip's kernel: see tile 0 above
+}
+
 // Each returns hipSuccess or the launch error.
 hipError_t t2v_launch_gemm(const GemmParams& p, hipStream_t s);             // 128x128 / 128x64 tiles (any N, C8 stem)
 hipError_t t2v_launch_gemm2(const GemmParams& p, int tile, hipStream_t s);  // 256/128 x 256/320 tiles, deep DMA ring

@@ -155,6 +155,15 @@ class Op:
     out2: Optional["Buf"] = None  # second output (the normalised tensor of a T2V_EPI_GN op)
 
 
+def _fill(workgroups: int, cus: int) -> float:
+    """How full the last round of a grid's workgroups is on `cus` compute units (1.0 = every round full)."""
+    return workgroups / (math.ceil(workgroups / cus) * cus)
+
+
+def _tile_has(tile, feature: int) -> bool:
+    return tile in L.GEMM_TILES and L.GEMM_TILES[tile].has(feature)
+
+
 class Program:
     def __init__(self, label: str = ""):
         self.label = label
@@ -214,9 +223,9 @@ class Program:
         if not getattr(self, "gn_epilogue", False) or not self.ops:
             return False
         op = self.ops[-1]
-        if op.kind != L.OP_GEMM or op.i[16] != L.EPI_NONE or (op.meta.get("tile") not in self._GN_EPI_TILES and op.meta.get("tile") != 12) \
-                or op.meta.get("split", 1) != 1:
-            return False                                # (tile 12: _fuse_groupnorm may move the GEMM to the 128x128 tile)
+        tile = op.meta.get("tile")
+        if op.kind != L.OP_GEMM or op.i[16] != L.EPI_NONE or not _tile_has(self._GN_RETILE.get(tile, tile), L.TILE_GN) or op.meta.get("split", 1) != 1:
+            return False
         lo, hi = b.alloc_off, b.alloc_off + self.arena.live.get(b.alloc_off, 0)
         # every arena-space input of the launch: A, an arena-resident weight operand (V^T / q k^T GEMMs), bias, row bias, residual
         return any(r is not None and r.space == "arena" and lo <= r.off < hi for r in (op.p[0], op.p[1], op.p[2], op.p[3], op.p[4]))
@@ -241,13 +250,11 @@ class Program:
 
     # ---- GEMM tiling policy ----------------------------------------------------------------
     def choose_tile(self, M: int, n: int, k: int, gather: int, allow_splitk: bool = True):
-        """-> (tile id, split_k).  Tile ids as in t2v_op.i[22]: 0 = 128x128-class kernel (any N, the C8
-        stem); 1 256x256, 2 256x320, 3 128x256, 4/5 128x128 with a 4-deep ring, 8 / 9 / 11 / 12 192x320 / 192x256 /
-        128x320 / 64x64 (csrc/gemm2.hip); 6 / 7 / 13-24 were other main-loop schedules, measured, not selected and
-        removed from the sources: the executor rejects them.
+        """-> (tile id, split_k).  Tile ids as in t2v_op.i[22]; their geometry and fused epilogues: _lib.GEMM_TILES.
         Policy for a 256-CU chip: the widest tile whose grid still gives >= ~0.75 wave of
         workgroups; otherwise the 128x256 tile, then split-K over the (long) reduction."""
-        cus = self.target_cus
+        cus, T = self.target_cus, L.GEMM_TILES
+        fill = lambda wgs: _fill(wgs, cus)
         forced = self.force_tile is not None
         conv_like = gather in (L.GATHER_CONV3X3, L.GATHER_TCONV3)
         r6 = L.knob("T2V_TILE_R6", "1") != "0"          # round-6 additions for the rows of T-shard ranks / VideoCrafter (A/B switch)
@@ -263,23 +270,20 @@ class Program:
             # 256 rows on 256 CUs; measured (tools/gemm_sweep.py L0) +13 % / +6 % on the C -> C and QKV linears, +3-6 % on the
             # K = 960 .. 2880 convolutions, -7 % on the 8-wave-deep GEGLU GEMM (LDS traffic per MFMA is higher) -> only where
             # the 256-row grid is a few, badly filled waves
-            if n % 320 == 0 and math.ceil(M / 256) * (n // 320) <= int(L.knob("T2V_TILE8_LIMIT", 640)) and L.knob("T2V_TILE8", "1") != "0" \
+            if n % 320 == 0 and T[2].grid(M, n) <= int(L.knob("T2V_TILE8_LIMIT", 640)) and L.knob("T2V_TILE8", "1") != "0" \
                     and not (r6 and n != 320 and k > 320 and M > 49152):
                 # (round 6, SWEEP_FRAMES=125: at (64000, 640, 640 .. 17280) — several column tiles, several rounds of workgroups — 256x320 is
                 #  ahead of the 12-wave / 8-wave tiles by 6-19 %: 411 / 778 / 991 / 720 / 1110 vs 389 / 661 / 848 / 649 / 934 TF/s)
                 tile = 8
                 # 128x320 on 8 waves (tile 11, round 4): VideoCrafter's M = 32768 makes 171 / 513 workgroups of 192 rows for N = 320 / 960
                 # (0.67 of the last wave of CUs) and exactly 256 / 768 of 128 rows; M = 49152 never gets here (192 rows fill it)
-                w8, w11 = math.ceil(M / 192) * (n // 320), math.ceil(M / 128) * (n // 320)
-                fill = lambda wgs: wgs / (math.ceil(wgs / cus) * cus)
-                if fill(w11) > fill(w8) + 0.05 and L.knob("T2V_TILE11", "1") != "0":
+                if fill(T[11].grid(M, n)) > fill(T[8].grid(M, n)) + 0.05 and L.knob("T2V_TILE11", "1") != "0":
                     tile = 11
             elif r6 and n == 960 and k <= 320 and M > 65536 and L.knob("T2V_TILE8", "1") != "0":
                 tile = 8               # (256000, 960, 320), the QKV projection of a 125-frame clip: 308 vs 275 TF/s on 256x256
             elif tile == 1 and n % 256 == 0 and L.knob("T2V_TILE8", "1") != "0":
                 # the stem TemporalTransformer (inner = 512): 192 x 2 tiles of 256x256 = 384 workgroups, 192x256 gives 512
-                w1, w9 = math.ceil(M / 256) * (n // 256), math.ceil(M / 192) * (n // 256)
-                fill = lambda wgs: wgs / (math.ceil(wgs / cus) * cus)
+                w1, w9 = T[1].grid(M, n), T[9].grid(M, n)
                 if w1 <= 1280 and fill(w9) > fill(w1) + 0.05:
                     tile = 9
         elif M >= 8192:                                # 16x16 level (b=2) / 32x32 level of a single CFG role (b=1)
@@ -301,8 +305,7 @@ class Program:
                 if r6 and tile == 2 and k <= 640 and L.knob("T2V_TILE8", "1") != "0":
                     # (12288, 2560, 320), the GEGLU projection of a 12-frame rank: 48 x 8 = 384 workgroups of 256x320 (1.5 rounds) against
                     # 512 of 192x320 (two full rounds): 518 vs 418 TF/s
-                    fill = lambda wgs: wgs / (math.ceil(wgs / cus) * cus)
-                    if fill(math.ceil(M / 192) * (n // 320)) > fill(math.ceil(M / 256) * (n // 320)) + 0.05:
+                    if fill(T[8].grid(M, n)) > fill(T[2].grid(M, n)) + 0.05:
                         tile = 8
             elif n >= 1536:
                 tile = 9 if L.knob("T2V_TILE8", "1") != "0" else 3      # 16x16-level QKV (12288, 1920, 640): 492 vs 452 TF/s
@@ -310,7 +313,7 @@ class Program:
                     tile = 1                                            # (8192, 1920, 640): 256x256 463 vs 373 TF/s
             else:
                 tile = 0               # (the 4-deep-ring 128x128 tile measured 640 vs 668 TF/s on the K = 2560 feed-forward GEMM)
-                if r6 and n % 320 == 0 and math.ceil(M / 256) * (n // 320) >= 200:
+                if r6 and n % 320 == 0 and T[2].grid(M, n) >= 200:
                     # several rounds of 256x320 tiles (125 frames: M = 16000, 1024x576: M = 27648; N = 1280): C -> C 686 vs 491, ff2 917 vs
                     # 687, temporal conv 945 vs 726 TF/s
                     tile = 2
@@ -324,9 +327,7 @@ class Program:
                 if r6 and M >= 1024 and n % 320 == 0:
                     # 256x320 where its grid fills the last round of workgroups better than 256x256's: (2048, 10240, 1280) 256 against 320
                     # workgroups, 862 vs 652 TF/s; (4000, ...) 884 vs 797; (1536, ...) 192 against 240: 256x256 825 vs 711; (3072, ...) 853 on 256x256
-                    fill = lambda wgs: wgs / (math.ceil(wgs / cus) * cus)
-                    w1, w2 = math.ceil(M / 256) * math.ceil(n / 256), math.ceil(M / 256) * (n // 320)
-                    tile = 2 if fill(w2) > fill(w1) else 1
+                    tile = 2 if fill(T[2].grid(M, n)) > fill(T[1].grid(M, n)) else 1
                 elif r6 and 512 <= M < 1024:
                     tile = 3           # (512, 10240, 1280): 508 vs 465; (768, 10240, 1280): 667 vs 613
                 elif r6 and 64 <= M <= 256:
@@ -339,9 +340,7 @@ class Program:
                     tile = 12          # (512 / 384 / 96, 3840, 1280): 303 / 234 / 76 vs 257 / 204 / 59
                 # 256-row tiles of M = 3072 x N = 3840 are 180 workgroups for 256 CUs; 192-row tiles give 240
                 if tile == 1 and n % 256 == 0 and L.knob("T2V_TILE8", "1") != "0":
-                    w1, w9 = math.ceil(M / 256) * (n // 256), math.ceil(M / 192) * (n // 256)
-                    fill = lambda wgs: wgs / (math.ceil(wgs / cus) * cus)
-                    if fill(w9) > fill(w1) + 0.05:
+                    if fill(T[9].grid(M, n)) > fill(T[1].grid(M, n)) + 0.05:
                         tile = 9
             elif gather == L.GATHER_CONV3X3 and k >= 8192:
                 tile = 2 if (M >= 4096 and n % 320 == 0) else 3
@@ -353,18 +352,18 @@ class Program:
                     # 1024x576 clips, 8x8 level (M = 6912): ONE round of 128x320 (216 workgroups) / 192x256 (180) tiles — C -> C 516, ff2 775 on
                     # 128x320, temporal conv 718 on 192x256 vs 392 / 556 / 520 on 128x256 (270 workgroups: a second, nearly empty round)
                     tile = 11 if gather == L.GATHER_PLAIN else 9
-                elif r6 and math.ceil(M / 128) * math.ceil(n / 128) >= 256 and n % 256 == 0:
+                elif r6 and T[5].grid(M, n) >= 256 and n % 256 == 0:
                     tile = 3                           # (4000, 1280, 1280 / 3840 tconv / 5120): 128x256 411 / 595 / 647 vs 362 / 467 / 537 (M = 3072: 240 tiles, stays)
                 if M <= 1024 and n <= 1280 and k <= 1280 and L.knob("T2V_TILE12", "1") != "0":
                     # the 4x4 level's C -> C linears (768, 1280, 1280): 64x64 tiles with the FULL reduction = 240 workgroups, no
                     # split-K slabs and no reduction launch: 201 vs 146 TF/s (tools/gemm_sweep.py L3, round 4); longer K / wider N
                     # stay on the split-K configurations (ff2 381 vs 341, conv3x3 525 vs 410, qkv 365 vs 331)
                     tile = 12
-                elif r6 and gather == L.GATHER_PLAIN and k <= 320 and M >= 4096 and math.ceil(M / 128) * math.ceil(n / 128) > 150:
+                elif r6 and gather == L.GATHER_PLAIN and k <= 320 and M >= 4096 and T[5].grid(M, n) > 150:
                     tile = 0           # (6144, 960, 320), the QKV projection of a 6-frame rank: 219 vs 173 TF/s
                 elif r6 and gather == L.GATHER_PLAIN and n == 1920 and 4096 <= M < 8192:
                     tile = 9           # (6144, 1920, 640), one CFG role's 16x16-level QKV: 192x256 432 vs 335 TF/s
-                elif r6 and k <= 2880 and math.ceil(M / 128) * math.ceil(n / 128) <= 150 and L.knob("T2V_TILE12", "1") != "0" and \
+                elif r6 and k <= 2880 and T[5].grid(M, n) <= 150 and L.knob("T2V_TILE12", "1") != "0" and \
                         (gather in (L.GATHER_PLAIN, L.GATHER_CONV3X3) or (gather == L.GATHER_TCONV3 and self.small_rank_tiles)) and \
                         (gather != L.GATHER_CONV3X3 or k > 2560):
                     # round 6 (SWEEP_BATCH=1 SWEEP_FRAMES=6 tools/gemm_sweep.py: the rows of a 6-frame T-shard rank): where 128x128 tiles
@@ -374,16 +373,10 @@ class Program:
                     # a temporal convolution is never that GEMM's epilogue (64x64 tiles have no GroupNorm epilogue); the 3x3 convolution
                     # (6144, 320, 2880) 378 vs 333
                     tile = 12
-        if tile == 0:
-            bm, bn, bk = 128, (64 if (n % 128 != 0 and n % 128 <= 64) else 128), 64
-        else:
-            bm, bn, bk = {1: (256, 256, 64), 2: (256, 320, 64), 3: (128, 256, 64), 4: (128, 128, 64), 5: (128, 128, 64),
-                          6: (256, 256, 64), 7: (256, 320, 64), 8: (192, 320, 64), 9: (192, 256, 64), 11: (128, 320, 64), 12: (64, 64, 64),
-                          13: (256, 256, 64), 14: (256, 320, 64), 15: (128, 256, 64), 16: (128, 128, 64), 17: (192, 320, 64),
-                          18: (256, 256, 64), 19: (256, 320, 64), 20: (192, 320, 64), 21: (128, 256, 64),
-                          22: (256, 256, 64), 23: (256, 320, 64), 24: (128, 256, 64)}[tile]
-        tiles = math.ceil(M / bm) * math.ceil(n / bn)
-        kt = math.ceil(k / bk)
+        if tile not in T or T[tile].has(L.TILE_TATTN_ONLY):
+            raise KeyError(tile)                       # no general-purpose kernel (the temporal-attention tile: temporal_attention_fused)
+        tiles = math.ceil(M / T[tile].bm) * math.ceil(n / (L.tile0_bn(n) if tile == 0 else T[tile].bn))
+        kt = math.ceil(k / L.GEMM_BK)
         split = 1
         if allow_splitk and kt >= 16:
             # measured with tools/gemm_sweep.py on MI355X (256 CUs)
@@ -407,13 +400,12 @@ class Program:
         against 128 x 2 = 256)."""
         if L.knob("T2V_TILE8", "1") == "0":
             return 2
-        cus, kt = self.target_cus, math.ceil(k / 64)
+        cus, kt = self.target_cus, math.ceil(k / L.GEMM_BK)
         best, best_fill = 2, -1.0
-        for tile, bm in ((2, 256), (8, 192)):
-            tiles = math.ceil(M / bm) * (n // 320)
+        for tile in (2, 8):
+            tiles = L.GEMM_TILES[tile].grid(M, n)
             split = max(1, min(cus // tiles, kt // 8, 32)) if (kt >= 16 and tiles < 0.6 * cus) else 1
-            wgs = tiles * split
-            fill = wgs / (math.ceil(wgs / cus) * cus)
+            fill = _fill(tiles * split, cus)
             if fill > best_fill + 0.05:
                 best, best_fill = tile, fill
         return best
@@ -520,16 +512,17 @@ class Program:
             gb, gamma, beta, ln_out, ln_eps = ln
             assert out.dtype == "f32" and ln_out.dtype == "f16" and ln_out.cols == n and ln_out.rows >= M
             # (tile 2 = 256x320, round 6: the several-round grids of 125-frame / 1024x576 clips — a wave's two 32-row blocks one after the other)
-            ln_fused = (tile in ((8, 11, 2) if L.knob("T2V_LN_TILE2", "1") != "0" else (8, 11)) and split == 1 and n == 320 and gather == L.GATHER_PLAIN and epi == L.EPI_NONE and act == 0
+            geo = L.GEMM_TILES[tile]
+            ln_fused = (geo.fuses(L.TILE_LN, n) and (tile != 2 or L.knob("T2V_LN_TILE2", "1") != "0") and split == 1 and gather == L.GATHER_PLAIN and epi == L.EPI_NONE and act == 0
                         and rowbias is None and not bias_along_m and k % 64 == 0 and L.knob("T2V_LN_FUSE", "1") != "0")
             # ... or ACROSS the column tiles of the launch (round 5, t2v_epilogue_rows_lnx): the partial row sums meet at a grid barrier, so
             # the whole grid must be resident at once (the 16x16 / 8x8 / 4x4-level C -> C linears: 480 / 240 / 240 workgroups)
             ln_x = False
-            if not ln_fused and self.gn_epilogue and tile in self._LNX_TILES and L.knob("T2V_LN_X", "1") != "0":
-                bm, bn, per_cu = self._LNX_TILES[tile]
-                tiles_m, tiles_n = -(-M // bm), -(-n // bn)
+            if not ln_fused and self.gn_epilogue and geo.has(L.TILE_LNX) and L.knob("T2V_LN_X", "1") != "0":
+                bm, per_cu = geo.bm, geo.per_cu
+                tiles_m, tiles_n = -(-M // bm), -(-n // geo.bn)
                 ln_x = (split == 1 and gather == L.GATHER_PLAIN and epi == L.EPI_NONE and act == 0 and rowbias is None and not bias_along_m
-                        and k % 64 == 0 and not out_lo and (tile != 0 or n % 128 == 0) and ln_out.ld % 4 == 0)
+                        and k % 64 == 0 and not out_lo and geo.fuses(L.TILE_LNX, n) and ln_out.ld % 4 == 0)
                 if ln_x:
                     # rows are independent: a grid larger than the device holds (or the scratch has records for) runs as row chunks (round 6)
                     cap = min(per_cu * self.device_cus(), self._gn_part.rows // (bm * 16))
@@ -580,7 +573,7 @@ class Program:
         M = out.rows
         assert a.dtype == "f16" and out.dtype == "f16" and out.cols == n and k % 64 == 0 and n_keys <= 96 and rows_per_sample % 32 == 0
         tile, split = self.choose_tile(M, n, k, L.GATHER_PLAIN, allow_splitk=False)
-        if not (((tile in (8, 11)) and n == 320) or (tile in (0, 5) and n % 128 == 0)) or split != 1:
+        if not L.GEMM_TILES[tile].fuses(L.TILE_XATTN, n) or split != 1:
             return None
         op = Op(L.OP_GEMM, name)
         I = op.i
@@ -626,10 +619,9 @@ class Program:
                        frames=frames, hw=hw, heads=heads)
         return self._emit(op)
 
-    # (rows, columns) of the tiles that have a T2V_EPI_GN instantiation, workgroups per CU they are resident with
-    _GN_EPI_TILES = {8: (192, 320, 1), 11: (128, 320, 1), 3: (128, 256, 1), 5: (128, 128, 1), 0: (128, 128, 2)}
-    # ... with a cross-tile LayerNorm instantiation (t2v_epilogue_rows_lnx)
-    _LNX_TILES = {0: (128, 128, 2), 5: (128, 128, 1), 12: (64, 64, 2), 9: (192, 256, 1), 3: (128, 256, 1)}
+    # 64x64 tiles (chosen for a small grid, choose_tile) have no GroupNorm epilogue; the 128x128 tile with the 4-deep ring — what such a
+    # GEMM ran on before round 6 — has: the fused norm is worth more than the tile (a launch and two passes), so _fuse_groupnorm moves it
+    _GN_RETILE = {12: 5}
 
     def gn_instance_too_large(self, M: int, n: int, k: int, gather: int, inst_rows: int) -> bool:
         """Would the GroupNorm that consumes this GEMM's [M, n] result (statistics instances of `inst_rows` rows) be refused as the GEMM's
@@ -638,9 +630,10 @@ class Program:
         if not self.gn_epilogue:
             return False
         tile, split = self.choose_tile(M, n, k, gather, True)
-        if split != 1 or tile not in self._GN_EPI_TILES:
+        if split != 1 or not _tile_has(tile, L.TILE_GN):
             return False
-        bm, bn, per_cu = self._GN_EPI_TILES[tile]
+        geo = L.GEMM_TILES[tile]
+        bm, bn, per_cu = geo.bm, geo.bn, geo.per_cu
         tiles_n = -(-n // bn)
         cap = min(per_cu * self.device_cus(), self._gn_part.rows // (2 * L.GN_PIECES * 16))
         return -(-M // bm) * tiles_n > cap and math.lcm(bm, inst_rows) // bm * tiles_n > cap
@@ -693,14 +686,13 @@ class Program:
                 return None
         else:
             retile = None
-            if tile == 12 and self.force_tile is None:
-                # 64x64 tiles (chosen for a small grid, choose_tile) have no GroupNorm epilogue; the 128x128 tile with the 4-deep ring —
-                # what such a GEMM ran on before round 6 — has: the fused norm is worth more than the tile (a launch and two passes)
-                tile = retile = 5
-            if tile not in self._GN_EPI_TILES or L.knob(f"T2V_GN_EPI_TILE{tile}", "1") == "0":
+            if tile in self._GN_RETILE and self.force_tile is None:
+                tile = retile = self._GN_RETILE[tile]
+            if not _tile_has(tile, L.TILE_GN) or L.knob(f"T2V_GN_EPI_TILE{tile}", "1") == "0":
                 return None
-            bm, bn, per_cu = self._GN_EPI_TILES[tile]
-            if tile == 0 and N % 128 != 0:
+            geo = L.GEMM_TILES[tile]
+            bm, bn, per_cu = geo.bm, geo.bn, geo.per_cu
+            if not geo.fuses(L.TILE_GN, N):
                 return None                               # (the narrow 128x64 form of the 128x128-class kernel has no instantiation)
             if N // groups > bn or rows % 32 or not (rows >= bm or 2 * rows == bm):
                 return None                               # (a row tile may touch at most two statistics instances)

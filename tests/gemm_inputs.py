@@ -40,6 +40,7 @@ import torch
 import torch.nn.functional as F
 
 from sd_webui_text2video_amd import _lib as L
+from sd_webui_text2video_amd._lib import GEMM2_TILES, tile0_bn          # the tile table: gemm2.hip's general-purpose ids, tile 0's width by N
 from sd_webui_text2video_amd.program import NULL, Buf, Program, Ref
 
 TOL_F32 = 2e-5          # fp32 results, strips, hi + lo: the suite's figure
@@ -47,15 +48,9 @@ TOL_F16 = 1e-3          # fp16 outputs: the suite's figure
 NAN = float("nan")
 TD = {"f16": torch.float16, "f32": torch.float32}
 PAD_ROWS, PAD_COLS = 3, 8
-BM = {0: 128, 1: 256, 2: 256, 3: 128, 4: 128, 5: 128, 8: 192, 9: 192, 11: 128, 12: 64}
-BN = {1: 256, 2: 320, 3: 256, 4: 128, 5: 128, 8: 320, 9: 256, 11: 320, 12: 64}          # tile 0: 64 or 128 by N (tile0_bn)
-GEMM2_TILES = (1, 2, 3, 4, 5, 8, 9, 11, 12)
+BM = {t: L.GEMM_TILES[t].bm for t in (0,) + GEMM2_TILES}
+BN = {t: L.GEMM_TILES[t].bn for t in GEMM2_TILES}          # tile 0: 64 or 128 by N (tile0_bn)
 VARIANTS = ("scaled", "marked", "offset")
-
-
-def tile0_bn(n):
-    """The width gemm.hip's launcher picks: 128x64 when the last 128-wide column tile would be at most half full."""
-    return 64 if (n % 128 != 0 and n % 128 <= 64) else 128
 
 
 # ---- the inputs ---------------------------------------------------------------------------------------------------------------------------

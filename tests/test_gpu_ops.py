@@ -13,8 +13,6 @@ from sd_webui_text2video_amd.program import BoundProgram, Buf, Program, Ref
 
 pytestmark = pytest.mark.gpu
 
-GEMM2_TILES = [1, 2, 3, 4, 5, 8, 9, 11, 12]     # csrc/gemm2.hip configurations (t2v_op.i[22]); 10 is the fused QKV + temporal attention tile
-
 
 def _g(seed=0):
     return torch.Generator().manual_seed(seed)
@@ -441,7 +439,7 @@ def test_layout_time_embed_copy_ddim():
 
 
 # ---- second-generation GEMM (csrc/gemm2.hip): 256/128 x 256/320 tiles, 4-/3-stage DMA ring --------
-@pytest.mark.parametrize("tile", GEMM2_TILES)
+@pytest.mark.parametrize("tile", L.GEMM2_TILES)
 @pytest.mark.parametrize("M,N,K", [(512, 640, 320), (300, 320, 192), (1000, 960, 1280), (256, 512, 64), (77, 1280, 128),
                                    (2304, 320, 2880)])
 def test_gemm2_plain_tiles(tile, M, N, K):
@@ -456,7 +454,7 @@ def test_gemm2_plain_tiles(tile, M, N, K):
     _check(it, got, out, 2e-5, f"gemm2 tile {tile} {M}x{N}x{K}")
 
 
-@pytest.mark.parametrize("tile", GEMM2_TILES)
+@pytest.mark.parametrize("tile", L.GEMM2_TILES)
 def test_gemm2_epilogues_and_geglu(tile):
     M, C, rpb = 384, 320, 96
     P = Program()
@@ -480,7 +478,7 @@ def test_gemm2_epilogues_and_geglu(tile):
     _check(it, got, gout, 1e-3, f"gemm2 geglu tile {tile}")
 
 
-@pytest.mark.parametrize("tile", GEMM2_TILES)
+@pytest.mark.parametrize("tile", L.GEMM2_TILES)
 @pytest.mark.parametrize("B,H,W,Cin,Cout,stride,up", [(3, 16, 16, 64, 320, 1, 0), (2, 8, 8, 128, 256, 2, 0),
                                                       (2, 6, 10, 64, 640, 1, 1)])
 def test_gemm2_conv3x3(tile, B, H, W, Cin, Cout, stride, up):
@@ -497,7 +495,7 @@ def test_gemm2_conv3x3(tile, B, H, W, Cin, Cout, stride, up):
     _check(it, got, out, 2e-5, f"gemm2 conv3x3 tile {tile}")
 
 
-@pytest.mark.parametrize("tile", GEMM2_TILES)
+@pytest.mark.parametrize("tile", L.GEMM2_TILES)
 def test_gemm2_temporal_conv_and_split_k(tile):
     B, F, HW, C = 2, 5, 16, 640
     P = Program()
@@ -554,7 +552,7 @@ def test_groupnorm_split_phases_two_parts():
     assert rel_l2(torch.cat([read(got, o0), read(got, o1)]).float(), ref) < 1e-3
 
 
-@pytest.mark.parametrize("tile", [0] + GEMM2_TILES)
+@pytest.mark.parametrize("tile", (0,) + L.GEMM2_TILES)
 def test_temporal_conv_halo_layout(tile):
     B, F, HW, C = 1, 3, 64, 320
     P = Program()
@@ -1508,7 +1506,8 @@ def test_fused_groupnorm_on_a_grid_larger_than_the_device_runs_in_row_chunks(kin
     assert op.meta["tile"] == tile and op.meta["split"] == 1
     fused = P.groupnorm("gn", y, Ref("weight", 0, "g"), Ref("weight", 0, "be"), out, n_inst=frames, eps=1e-5, silu=True, gb=Ref("weight", 0, "gb"))
     assert fused is op and op.i[16] == L.EPI_GN and len(P.ops) == 1, "the norm did not become the GEMM's epilogue"
-    bm, bn, per_cu = Program._GN_EPI_TILES[tile]
+    assert L.GEMM_TILES[tile].has(L.TILE_GN)
+    bm, bn, per_cu = L.GEMM_TILES[tile].bm, L.GEMM_TILES[tile].bn, L.GEMM_TILES[tile].per_cu
     assert -(-M // bm) * -(-C // bn) > 256 * per_cu, "the grid must exceed what the device holds"
 
     def init(it):
@@ -1537,7 +1536,8 @@ def test_layernorm_across_column_tiles_on_a_grid_larger_than_the_device(tile, N,
     op = P.gemm("l", a, Ref("weight", 0, "w"), N, K, out, bias=Ref("weight", 0, "b"), residual=res, allow_splitk=False,
                 ln=(Ref("weight", 0, "gb"), Ref("weight", 0, "g"), Ref("weight", 0, "be"), ln_out, 1e-5))
     assert op.meta["tile"] == tile and op.i[8] == 2 and len(P.ops) == 1, "the LayerNorm did not become the GEMM's epilogue"
-    bm, bn, per_cu = Program._LNX_TILES[tile]
+    assert L.GEMM_TILES[tile].has(L.TILE_LNX)
+    bm, bn, per_cu = L.GEMM_TILES[tile].bm, L.GEMM_TILES[tile].bn, L.GEMM_TILES[tile].per_cu
     assert -(-M // bm) * -(-N // bn) > per_cu * 256
     it, got = _gpu_run(P, w, lambda it: (fill(it, a, g), fill(it, res, g, 3.0)))
     _check(it, got, out, 2e-5, "fp32 stream")
