@@ -203,8 +203,8 @@ enum t2v_gather {
  *   Fused feed-forward pair (plans only; env T2V_FF_FUSE, read once, default on; 0 = off): when a plan is created, records k, k + 1 that
  *      are a GEGLU GEMM (plain gather, no split-K, N = 2560, K = 320, fp16 out, nothing but a bias) and a projection whose A operand is
  *      EXACTLY that result (same pointer, leading dimension and M; plain gather and epilogue, no split-K, N = 320, K = 1280, no fused
- *      norm) run as ONE launch, bit-identical to the two, provided M >= 49152, the result not lying over the GEGLU GEMM's operands, and no later record of the plan reads an address inside
- *      the hidden tensor before some record writes one.  THE HIDDEN BUFFER (record k's p[5]) IS NOT WRITTEN BY A FUSED PAIR.
+ *      norm) run as ONE launch, bit-identical to the two, provided M >= 49152, the result not lying over the GEGLU GEMM's operands, and no later record of the plan reaches — by the extent of
+ *      any of its pointer slots, a window that starts below the tensor included — into bytes of the hidden tensor that no record has rewritten since.  THE HIDDEN BUFFER (record k's p[5]) IS NOT WRITTEN BY A FUSED PAIR.
  *      t2v_plan_run_timed reports the launch on record k and exactly 0.0f on record k + 1.  t2v_run_ops never fuses.
  *      i[31] = 1 on the GEGLU record (a word no validation reads; test hook): the M cut-off is waived.
  * GROUPNORM: i: 0 n_inst, 1 rows_per_inst, 2 C, 3 ld_in, 4 groups, 5 in dtype, 6 silu,
@@ -388,6 +388,8 @@ int t2v_run_ops(const t2v_op* ops, int n, const uint64_t* ext, int n_ext, void* 
 /* Plans: validate + copy a program once, run it many times. */
 int t2v_plan_create(const t2v_op* ops, int n, t2v_plan** out);
 int t2v_plan_num_ops(const t2v_plan* plan);
+/* records minus the feed-forward pairs that run as one launch (the GEMM section above): what the plan-time recognition decided */
+int t2v_plan_num_launches(const t2v_plan* plan);
 int t2v_plan_run(t2v_plan* plan, const uint64_t* ext, int n_ext, void* stream);
 /* Same, bracketing every op with HIP events on `stream`; ms[i] = duration of op i.
  * Synchronises the stream.  Used by bench.py for the live roofline measurement. */

@@ -118,7 +118,7 @@ def tile0_bn(n: int) -> int:
 
 EXPORTS = [
     "t2v_abi_version", "t2v_last_error", "t2v_device_info", "t2v_run_ops", "t2v_plan_create",
-    "t2v_plan_num_ops", "t2v_plan_run", "t2v_plan_run_timed", "t2v_plan_destroy",
+    "t2v_plan_num_ops", "t2v_plan_num_launches", "t2v_plan_run", "t2v_plan_run_timed", "t2v_plan_destroy",
     "t2v_unet_forward", "t2v_vae_decode", "t2v_ddim_step",
     "t2v_comm_unique_id", "t2v_comm_create", "t2v_comm_size", "t2v_comm_destroy", "t2v_plan_set_comm", "t2v_comm_all_gather",
     "t2v_comm_window_create", "t2v_comm_window_open", "t2v_comm_counters", "t2v_comm_window_kind",
@@ -159,6 +159,7 @@ def load():
     lib.t2v_run_ops.argtypes = [opp, ctypes.c_int, u64p, ctypes.c_int, vp]
     lib.t2v_plan_create.argtypes = [opp, ctypes.c_int, ctypes.POINTER(vp)]
     lib.t2v_plan_num_ops.argtypes = [vp]
+    lib.t2v_plan_num_launches.argtypes = [vp]
     lib.t2v_plan_run.argtypes = [vp, u64p, ctypes.c_int, vp]
     lib.t2v_plan_run_timed.argtypes = [vp, u64p, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float)]
     lib.t2v_plan_destroy.argtypes = [vp]

@@ -492,6 +492,202 @@ unsigned output_slots(const t2v_op& op) {
   }
 }
 
+// The bytes a record addresses through pointer slot q, as a bounding range [b, e) from the field lists of include/t2v_hip.h, and whether the
+// range is DENSE (every byte of it belongs to the slot: a flat run, or rows whose leading dimension equals their length).  false: the slot
+// is not used by this record.  The bound is never smaller than what the kernels touch; only a dense range proves that bytes were written.
+// rows > 0: the range is exactly `rows` rows of `rowb` bytes, `pitch` bytes apart (rows == 1: one flat run); rows == 0: only the bound is known.
+struct SlotRange { uint64_t b, e; bool dense; int64_t rows, pitch, rowb; };
+// Is every byte of r inside w (both with known geometry)?  Sufficient, never wrong: what a record reads there, an earlier record wrote.
+bool range_inside(const SlotRange& r, const SlotRange& w) {
+  if (r.rows <= 0 || w.rows <= 0 || r.b < w.b || r.e > w.e) return false;
+  if (w.rows == 1) return true;
+  const uint64_t off = r.b - w.b, i0 = off / (uint64_t)w.pitch, c = off % (uint64_t)w.pitch;
+  if (c + (uint64_t)r.rowb > (uint64_t)w.rowb) return false;
+  if (r.rows == 1) return i0 < (uint64_t)w.rows;
+  return r.pitch == w.pitch && i0 + (uint64_t)r.rows <= (uint64_t)w.rows;
+}
+bool slot_range(const t2v_op& op, int q, SlotRange* out) {
+  const uint64_t v = op.p[q];
+  if (v == 0) return false;
+  const int32_t* I = op.i;
+  auto u64 = [&](int lo, int hi) { return (uint64_t)(uint32_t)I[lo] | ((uint64_t)(uint32_t)I[hi] << 32); };
+  auto flat = [&](uint64_t bytes) { const uint64_t n = bytes > 0 ? bytes : 1; *out = {v, v + n, true, 1, 0, (int64_t)n}; return true; };
+  auto mat = [&](int64_t rows, int64_t cols, int64_t ld, int item) {
+    if (rows <= 0 || cols <= 0) return false;
+    if (rows == 1 || ld == cols) return flat((uint64_t)((rows - 1) * ld + cols) * item);
+    *out = {v, v + (uint64_t)((rows - 1) * ld + cols) * item, false, rows, ld * item, cols * item};
+    return true;
+  };
+  auto span = [&](uint64_t bytes) { *out = {v, v + (bytes > 0 ? bytes : 1), false, 0, 0, 0}; return true; };
+  const int f32 = T2V_F32;
+  switch (op.kind) {
+    case T2V_OP_GEMM: {
+      const int64_t M = I[0], N = I[1], K = I[2], lda = I[3], ldw = I[4], ldc = I[5], ldr = I[6];
+      const int g = I[7], epi = I[16], oitem = I[17] == f32 ? 4 : 2, split = I[19] > 1 ? I[19] : 1;
+      if (epi == T2V_EPI_TATTN) {
+        const int64_t tiles_ps = (I[9] + I[10] - 1) / I[10], T = M / 192 / tiles_ps * I[8] * I[9];
+        if (q == 0) return mat(T, K, lda, 2);
+        if (q == 1) return mat(N, K, ldw, 2);
+        if (q == 5) return mat(T, N / 192 * 64, ldc, 2);
+        return span(~0ull >> 2);
+      }
+      if (epi == T2V_EPI_XATTN) {
+        const int64_t samples = M / I[15], Lc = I[25];
+        if (q == 0) return mat(I[13] ? I[13] : M, K, lda, 2);
+        if (q == 1) return mat(N, K, ldw, 2);
+        if (q == 5) return mat(M, N, ldc, 2);
+        if (q == 8) return span((uint64_t)((samples - 1) * I[27] + (Lc - 1) * I[24] + N) * 2);
+        if (q == 9) return span((uint64_t)((samples - 1) * I[28] + (N - 1) * I[26] + I[26]) * 2);
+        return span(~0ull >> 2);
+      }
+      const int64_t n_out = epi == T2V_EPI_GEGLU ? N / 2 : N;
+      const bool ln = g == T2V_GATHER_PLAIN && (I[8] == 1 || I[8] == 2);
+      switch (q) {
+        case 0:
+          if (g == T2V_GATHER_PLAIN) return mat(I[13] ? I[13] : M, K, lda, 2);
+          if (g == T2V_GATHER_TCONV3) return mat(M / ((int64_t)I[8] * I[9]) * (I[8] + (I[23] ? 2 : 0)) * I[9], I[10], lda, 2);
+          return mat(M / ((int64_t)I[13] * I[14]) * I[8] * I[9], I[10], lda, 2);
+        case 1: return mat(N, K, ldw, 2);
+        case 2: return flat((uint64_t)(I[20] ? M : N) * 4);
+        case 3: return ln ? flat((uint64_t)2 * N * 4) : mat((M + (I[15] > 0 ? I[15] : 1) - 1) / (I[15] > 0 ? I[15] : 1), N, I[21], 4);
+        case 4: {
+          const int64_t rw = I[30] > 0 ? I[30] : (g == T2V_GATHER_PLAIN ? I[12] : 0);
+          return mat(rw ? rw : M, n_out, ldr, 4);
+        }
+        case 5:
+          if (g == T2V_GATHER_PLAIN && I[11] == 1) { mat(M, 2 * N, ldc, 2); return true; }
+          return mat(M, n_out, ldc, oitem);
+        case 6: return flat((uint64_t)split * M * N * 4);
+        case 7:
+          if (ln) return mat(M, N, I[9], 2);
+          if (epi == T2V_EPI_STATS) return flat((uint64_t)((M + 31) / 32) * 2 * N * 4);
+          return flat((uint64_t)T2V_SYNC_INTS * 4);
+        case 8: return flat((uint64_t)2 * N * 4);
+        case 9: return mat(M, N * (I[27] ? 2 : 1), I[25], 2);
+        case 10: return flat(T2V_GN_PART_BYTES);
+        case 11: return flat((uint64_t)T2V_SYNC_BARRIER_INTS * 4);
+      }
+      return span(~0ull >> 2);
+    }
+    case T2V_OP_GROUPNORM: {
+      const int64_t n_inst = I[0], rows = I[1], C = I[2], ld_in = I[3], groups = I[4], ld_out = I[7], nparts = I[9] > 0 ? I[9] : 1;
+      const int item = I[5] == f32 ? 4 : 2, phase = I[8];
+      const int64_t before = phase == 2 ? I[21] : 0, after = phase == 2 ? I[22] : 0, total = n_inst * rows + before + after;
+      const int64_t rpb = I[11] > 0 ? I[11] : T2V_GN_ROWS_PER_BLOCK, nblk = (rows + rpb - 1) / rpb;
+      switch (q) {
+        case 0: if (!mat(total, C, ld_in, item)) return false; out->b -= (uint64_t)before * ld_in * item; out->e -= (uint64_t)before * ld_in * item; return true;
+        case 1: case 2: return flat((uint64_t)C * 4);
+        case 3: if (!mat(total, C * (I[16] ? 2 : 1), ld_out, 2)) return false; out->b -= (uint64_t)before * ld_out * 2; out->e -= (uint64_t)before * ld_out * 2; return true;
+        case 4: return flat((uint64_t)((phase == 1 || phase == 2 ? nparts * n_inst * groups * 16 : 0) + n_inst * nblk * groups * 16 + n_inst * groups * 8));
+        case 5: return flat((uint64_t)T2V_SYNC_BARRIER_INTS * 4);
+        case 6: return flat((uint64_t)n_inst * (rows / 32) * 2 * I[17] * 4);
+        case 7: return flat((uint64_t)(I[18] > 0 ? I[18] : 1));
+        case 8: return mat(n_inst * rows, I[20] > 0 ? I[20] + C : C, I[19], 2);
+      }
+      return span(~0ull >> 2);
+    }
+    case T2V_OP_LAYERNORM:
+      if (q == 0) return mat(I[0], I[1], I[2], 4);
+      if (q == 1 || q == 2) return flat((uint64_t)I[1] * 4);
+      if (q == 3) return mat(I[0], I[1], I[3], 2);
+      return span(~0ull >> 2);
+    case T2V_OP_ATTENTION:
+    case T2V_OP_RELPOS_ATTN: {
+      const bool rel = op.kind == T2V_OP_RELPOS_ATTN;
+      const int64_t nq = I[0], nk = I[1], heads = I[2], bo = I[3], bi = I[4], D = I[14] > 0 ? I[14] : 64;
+      auto seq = [&](int64_t n, int s0, int64_t outer, int64_t outer_stride) {
+        return span((uint64_t)((outer - 1) * outer_stride + (bi - 1) * I[s0 + 2] + (n - 1) * I[s0] + heads * D) * 2);
+      };
+      if (q == 0) return seq(nq, 5, bo, I[6]);
+      if (q == 1 || q == 2) return seq(nk, 8, bo, I[9]);
+      if (q == 3) { if (!seq(nq, 11, bo, I[12])) return false; out->e += (uint64_t)(rel ? I[18] : I[16]) * 2; return true; }
+      if (rel) {
+        const int64_t R = I[15], DK = (D + 15) / 16 * 16, DV = (D + 31) / 32 * 32;
+        if (q == 4 || q == 5) return flat((uint64_t)(2 * R + 1) * D * 4);
+        if (q == 6) return flat((uint64_t)(I[17] == 3 ? 2 * R + 1 : 32) * DK * 2);
+        if (q == 7) return flat((uint64_t)DV * (I[17] == 3 ? T2V_RELPOS_LONG_COLS(R) : 32) * 2);
+      } else {
+        if (q == 4 || q == 5) return seq(I[20], 8, bo - I[19], I[21]);
+        if (q == 6) return flat((uint64_t)bo * bi * heads * 64 * I[17] * 2);
+      }
+      return span(~0ull >> 2);
+    }
+    case T2V_OP_SOFTMAX:
+      if (q == 0) return mat(I[0], I[1], I[2], 4);
+      if (q == 1) return mat(I[0], I[1], I[3], 2);
+      return span(~0ull >> 2);
+    case T2V_OP_NCTHW_TO_CL: {
+      const int64_t B = I[0], Bsrc = (I[6] > 0 && I[6] < I[0]) ? I[6] : I[0], tokens = B * I[2] * I[3];
+      if (q == 0) return flat((uint64_t)Bsrc * I[1] * I[2] * I[3] * (I[5] == f32 ? 4 : 2));
+      if (q == 1 || q == 2) return flat((uint64_t)tokens * I[4] * 2);
+      return span(~0ull >> 2);
+    }
+    case T2V_OP_CL_TO_NCTHW:
+      if (q == 0) return mat((int64_t)I[0] * I[2] * I[3], I[1], I[4], 4);
+      if (q == 1) return flat((uint64_t)I[0] * I[1] * I[2] * I[3] * (I[5] == f32 ? 4 : 2));
+      return span(~0ull >> 2);
+    case T2V_OP_TIME_EMBED:
+      if (q == 0) return flat((uint64_t)I[0] * 4);
+      if (q == 1) return flat((uint64_t)I[1] / 2 * 4);
+      if (q == 2) return flat((uint64_t)I[0] * I[1] * 2);
+      return span(~0ull >> 2);
+    case T2V_OP_COPY2D:
+      if (q == 0) return mat(I[0], I[1], I[2], I[4] == f32 ? 4 : 2);
+      if (q == 1) return mat(I[0], I[1], I[3], I[5] == f32 ? 4 : 2);
+      if (q == 2) return mat(I[0], I[1], I[3], 2);
+      return span(~0ull >> 2);
+    case T2V_OP_MEMSET: return flat(u64(0, 1));
+    case T2V_OP_LINCOMB:
+      if (q < I[1]) return flat((uint64_t)I[0] * (I[3 + q] == f32 ? 4 : 2));
+      if (q == 6) return flat((uint64_t)I[0] * (I[2] == f32 ? 4 : 2));
+      return span(~0ull >> 2);
+    case T2V_OP_EMBED_ROWS:
+      if (q == 0) return flat((uint64_t)I[0] * 4);
+      if (q == 1) return flat((uint64_t)I[3] * I[1] * (I[4] == f32 ? 4 : 2));
+      if (q == 2) return flat((uint64_t)I[2] * I[1] * 4);
+      if (q == 3) return flat((uint64_t)I[0] * I[1] * 4);
+      return span(~0ull >> 2);
+    case T2V_OP_ALLGATHER: return flat(u64(0, 1) * (uint64_t)I[2]);
+    case T2V_OP_HALO_EXCHANGE: return flat(u64(0, 1) * (uint64_t)(I[2] + 2));
+    case T2V_OP_STATS_HALO:
+      if (q == 0) return flat(u64(0, 1) * (uint64_t)I[2]);
+      if (q == 1) return flat(u64(4, 5) * (uint64_t)(I[6] + 2));
+      return span(~0ull >> 2);
+    case T2V_OP_ALLTOALL: return flat(u64(0, 1) * (uint64_t)I[2] * (uint64_t)I[4]);
+    case T2V_OP_RESHARD_ROWS: {
+      const int64_t rows = I[0], cols = I[1], P = I[2], chunks = (rows + P - 1) / P, nparts = I[9] > 1 ? I[9] : 1;
+      const int item = I[7] == f32 ? 4 : 2;
+      auto grid = [&](int64_t stride, int64_t ld, int it, int64_t part_stride, int64_t parts) {
+        return span((uint64_t)(((chunks - 1) * stride + (rows < P ? rows : P) - 1) * ld + cols + (parts - 1) * part_stride) * it);
+      };
+      if (q == 0) return grid(I[3], I[5], item, I[10], nparts);
+      if (q == 1) return grid(I[4], I[6], item, I[11], nparts);
+      if (q == 2) return grid(I[4], I[8], 4, I[12], nparts);
+      if (q == 3) return I[14] ? grid(I[3], I[5], item, 0, 1) : grid(I[4], I[6], item, 0, 1);
+      return span(~0ull >> 2);
+    }
+    case T2V_OP_AVGPOOL2: {
+      const int64_t n = I[0], H = I[1], W = I[2], C = I[3], out_rows = n * (H / 2) * (W / 2);
+      if (q == 0) return mat(n * H * W, C, I[4], 4);
+      if (q == 1) return mat(out_rows, C, I[5], 4);
+      if (q == 2) return mat(out_rows, C, I[6], 2);
+      return span(~0ull >> 2);
+    }
+    case T2V_OP_DEPTH_TOKENS:
+      if (q == 0) return flat((uint64_t)I[0] * I[1] * I[2] * (I[3] == f32 ? 4 : 2));
+      if (q == 1) return mat((int64_t)I[0] * (I[1] / 8) * (I[2] / 8), 64, I[5], 2);
+      return span(~0ull >> 2);
+    case T2V_OP_EMPHASIS:
+      if (q == 0) return mat(I[0], I[1], I[2], I[4] == f32 ? 4 : 2);
+      if (q == 1) return flat((uint64_t)I[0] * 4);
+      if (q == 2) return mat(I[0], I[1], I[3], 4);
+      return span(~0ull >> 2);
+    default:
+      // DDIM_STEP, TO_UINT8, RESAMPLE work on the caller's tensors in every lowering; should one name arena memory, its extent is in doubt
+      return span(~0ull >> 2);
+  }
+}
+
 // Are ops[k] and ops[k + 1] the GEGLU GEMM and the projection of a C = 320 feed-forward whose hidden tensor nothing else reads?  When in
 // doubt: no.  (i[31] = 1 on the GEGLU record, a word no validation reads: the row cut-off is waived — the tests' way to the kernel at
 // a few hundred rows.)
@@ -518,19 +714,56 @@ bool ff_pair(const t2v_op* ops, int n, int k) {
     auto apart = [&](uint64_t r0, uint64_t bytes) { return r0 == 0 || o1 <= r0 || o0 >= r0 + bytes; };
     if (!apart(a.p[0], ((uint64_t)(M - 1) * a.i[3] + 320) * 2) || !apart(a.p[1], ((uint64_t)2559 * a.i[4] + 320) * 2) || !apart(a.p[2], 2560 * 4)) return false;
   }
-  // nothing else may read the hidden tensor: scan the records behind the GEGLU GEMM until one names the buffer as an output
+  // nothing else may read the hidden tensor: scan the records behind the GEGLU GEMM, by EXTENT (slot_range), until the whole tensor has
+  // been rewritten.  A record that reaches into bytes of it that no record has rewritten since — through a window that starts below it
+  // as well as through a pointer inside it — reads what a fused pair never stored.  Only a dense output range proves a rewrite.
   const uint64_t lo = a.p[5], hi = lo + ((uint64_t)(M - 1) * a.i[5] + 1280) * 2;
-  for (int j = k + 1; j < n; ++j) {
+  std::vector<std::pair<uint64_t, uint64_t>> left{{lo, hi}};          // bytes of the hidden tensor not rewritten yet
+  std::vector<SlotRange> strided;                                      // strided output ranges that reached into them since
+  for (int j = k + 1; j < n && !left.empty(); ++j) {
     const unsigned outs = output_slots(ops[j]);
-    bool rewritten = false;
+    SlotRange r[T2V_OP_NP];
+    bool used[T2V_OP_NP];
+    for (int q = 0; q < T2V_OP_NP; ++q) used[q] = ops[j].p[q] >= T2V_EXT_SLOTS && slot_range(ops[j], q, &r[q]);
     for (int q = 0; q < T2V_OP_NP; ++q) {
-      const uint64_t v = ops[j].p[q];
-      if (v < lo || v >= hi) continue;
-      if (j == k + 1 && q == 0) continue;                  // the projection's A operand
-      if (!((outs >> q) & 1u) || j == k + 1) return false; // read by someone else (or the projection writes into its own operand)
-      rewritten = true;
+      if (!used[q] || (j == k + 1 && q == 0)) continue;                // (the projection's A operand)
+      bool touches = false;
+      for (const auto& s : left) touches = touches || (r[q].b < s.second && s.first < r[q].e);
+      if (!touches) continue;
+      if (((outs >> q) & 1u) && j != k + 1) continue;                  // an output (the projection's own: never over its operand)
+      bool rewritten = false;                                          // a read: fine if an earlier strided output wrote every byte of it
+      for (const auto& w : strided) rewritten = rewritten || range_inside(r[q], w);
+      if (!rewritten) return false;                                    // read by someone else
     }
-    if (rewritten) break;
+    for (int q = 0; q < T2V_OP_NP; ++q) {
+      if (!used[q] || !((outs >> q) & 1u)) continue;
+      SlotRange w = r[q];
+      if (!w.dense) {
+        if (w.rows <= 0 || w.b >= hi || lo >= w.e) continue;
+        // column slices of one buffer written by several records (a concat, hi | lo halves): adjacent slices of the same rows join, and
+        // slices that fill the pitch are a dense run
+        for (size_t t = 0; t < strided.size();) {
+          const SlotRange& o = strided[t];
+          const bool after = o.rows == w.rows && o.pitch == w.pitch && o.b + (uint64_t)o.rowb == w.b;
+          const bool before = o.rows == w.rows && o.pitch == w.pitch && w.b + (uint64_t)w.rowb == o.b;
+          if (!after && !before) { ++t; continue; }
+          if (after) w.b = o.b;
+          w.rowb += o.rowb;
+          w.e = w.b + (uint64_t)((w.rows - 1) * w.pitch + w.rowb);
+          strided.erase(strided.begin() + t);
+          t = 0;
+        }
+        if (w.rowb < w.pitch) { strided.push_back(w); continue; }
+        w.dense = true;
+      }
+      std::vector<std::pair<uint64_t, uint64_t>> rest;
+      for (const auto& s : left) {
+        if (w.e <= s.first || w.b >= s.second) { rest.push_back(s); continue; }
+        if (s.first < w.b) rest.push_back({s.first, w.b});
+        if (w.e < s.second) rest.push_back({w.e, s.second});
+      }
+      left.swap(rest);
+    }
   }
   return true;
 }
@@ -691,6 +924,13 @@ int t2v_plan_create(const t2v_op* ops, int n, t2v_plan** out) {
 }
 
 int t2v_plan_num_ops(const t2v_plan* plan) { return plan ? (int)plan->ops.size() : 0; }
+
+int t2v_plan_num_launches(const t2v_plan* plan) {
+  if (!plan) return 0;
+  int fused = 0;
+  for (unsigned char f : plan->fused) fused += f;
+  return (int)plan->ops.size() - fused;
+}
 
 int t2v_plan_run(t2v_plan* plan, const uint64_t* ext, int n_ext, void* stream) {
   if (!plan) return fail(T2V_ERR_BAD_ARG, "null plan");

@@ -199,7 +199,8 @@ class Program:
         # (launches are stream-ordered and each rewrites every word it reads), allocated here for the reason given above for the sync words
         self._gn_part: Optional[Buf] = self.alloc(L.GN_PART_BYTES, 1, "u8") if self.gn_epilogue else None
         # Buffers whose free() is postponed: operands of the GEMM emitted last.  If the next groupnorm() makes itself that GEMM's
-        # epilogue, its output is written by the SAME launch that still reads these — it must not be allocated over them.
+        # epilogue, its output is written by the SAME launch that still reads these — it must not be allocated over them.  (A split-K
+        # GEMM: the slabs and the epilogue's operands, which its reduction launch reads while it stores the normalised rows.)
         self._deferred: List[Buf] = []
 
     # ---- memory ---------------------------------------------------------------------------
@@ -224,11 +225,41 @@ class Program:
             return False
         op = self.ops[-1]
         tile = op.meta.get("tile")
-        if op.kind != L.OP_GEMM or op.i[16] != L.EPI_NONE or not _tile_has(self._GN_RETILE.get(tile, tile), L.TILE_GN) or op.meta.get("split", 1) != 1:
+        if op.kind != L.OP_GEMM or op.i[16] != L.EPI_NONE:
             return False
+        if op.meta.get("split", 1) != 1:
+            # split-K: the norm would run in the REDUCTION's launch (_fuse_groupnorm), which reads the slabs, the bias, the row bias and the
+            # residual.  Its statistics instances do not wait for each other (tagged records, no grid barrier): the workgroups of one
+            # instance may store their normalised rows while those of another have yet to load theirs.
+            if not self._splitk_gn_possible(op):
+                return False
+            reads = (op.p[2], op.p[3], op.p[4], op.p[6])
+        elif not _tile_has(self._GN_RETILE.get(tile, tile), L.TILE_GN):
+            return False
+        else:
+            # every arena-space input of the launch: A, an arena-resident weight operand (V^T / q k^T GEMMs), bias, row bias, residual
+            reads = (op.p[0], op.p[1], op.p[2], op.p[3], op.p[4])
         lo, hi = b.alloc_off, b.alloc_off + self.arena.live.get(b.alloc_off, 0)
-        # every arena-space input of the launch: A, an arena-resident weight operand (V^T / q k^T GEMMs), bias, row bias, residual
-        return any(r is not None and r.space == "arena" and lo <= r.off < hi for r in (op.p[0], op.p[1], op.p[2], op.p[3], op.p[4]))
+        return any(r is not None and r.space == "arena" and lo <= r.off < hi for r in reads)
+
+    @staticmethod
+    def _splitk_gn_possible(op: Op) -> bool:
+        """Record-level conditions of the GroupNorm inside a split-K GEMM's reduction launch (the rest: _fuse_groupnorm)."""
+        N = op.i[1]
+        return L.knob("T2V_GN_EPI_SPLITK", "1") != "0" and op.p[7].space == "null" and N % 8 == 0 and N // 8 <= 512
+
+    def _apart_from_live(self, out: Buf, lo: bool, refs) -> bool:
+        """Does the normalised output [out.rows, out.cols (x 2 with its low-order image)] lie apart from the live allocations that hold
+        the arena pointers `refs`?"""
+        o_lo = out.ref.off
+        o_hi = o_lo + ((out.rows - 1) * out.ld + out.cols * (2 if lo else 1)) * 2
+        for r in refs:
+            if r is not None and r.space == "arena":
+                a_lo = max((off for off in self.arena.live if off <= r.off), default=None)
+                a_hi = a_lo + self.arena.live[a_lo] if a_lo is not None else None
+                if a_lo is None or not (o_hi <= a_lo or o_lo >= a_hi):
+                    return False
+        return True
 
     def _flush_deferred(self):
         pending, self._deferred = self._deferred, []
@@ -677,12 +708,15 @@ class Program:
         if split > 1:
             # split-K: the norm runs in the REDUCTION's launch (norm.hip splitk_gn_kernel: 512 threads, a thread = rows x 8 channels in
             # registers) — a co-resident grid of n_inst x chunks workgroups must exist for some rows-per-thread count
-            if L.knob("T2V_GN_EPI_SPLITK", "1") == "0" or op.p[7].space != "null" or N % 8 or N // 8 > 512 or groups > 32:
+            if not self._splitk_gn_possible(op) or groups > 32:
                 return None
             rpass = 512 // (N // 8)
             chunks = [n_inst * -(-rows // (rpass * kr)) for kr in (1, 2, 4, 8, 12, 16, 20)]
             fit = [c for c in chunks if c <= self.device_cus()]
             if not fit or fit[0] * groups * 16 > self._gn_part.rows:
+                return None
+            # the normalised tensor is written by the launch that reads the slabs and the epilogue's operands: never over them
+            if not self._apart_from_live(out, lo, (op.p[2], op.p[3], op.p[4], op.p[6])):
                 return None
         else:
             retile = None
@@ -707,14 +741,8 @@ class Program:
                 if math.lcm(bm, rows) // bm * tiles_n > cap or L.knob("T2V_GN_EPI_CHUNKS", "1") == "0":
                     return None
             # the normalised tensor is written by the launch that reads the GEMM's operands: never over them (free() defers those)
-            o_lo = out.ref.off
-            o_hi = o_lo + ((out.rows - 1) * out.ld + out.cols * (2 if lo else 1)) * 2
-            for r in (op.p[0], op.p[1], op.p[2], op.p[3], op.p[4]):
-                if r is not None and r.space == "arena":
-                    a_lo = max((off for off in self.arena.live if off <= r.off), default=None)
-                    a_hi = a_lo + self.arena.live[a_lo] if a_lo is not None else None
-                    if a_lo is None or not (o_hi <= a_lo or o_lo >= a_hi):
-                        return None
+            if not self._apart_from_live(out, lo, (op.p[0], op.p[1], op.p[2], op.p[3], op.p[4])):
+                return None
         part = self._gn_part
         if split == 1 and retile is not None:
             I[22] = op.meta["tile"] = retile
