@@ -34,6 +34,8 @@ extern "C" {
                                still 11: T2V_OP_EMPHASIS (a new kind: no existing record changes, and a library without it refuses the record as an unknown op kind) and
                                ATTENTION i[19..21] / p[4..5] (a second role; additive on fields every earlier record leaves zero);
                                still 11: T2V_OP_FINGERPRINT (a new kind, stand-alone: 64-bit fingerprints of a table of byte ranges; no existing record changes);
+                               still 11: T2V_OP_LORA_MERGE (a new kind, stand-alone: W += alpha * (B A) over a table of weights, in place, one launch; no existing record
+                               changes, and a library without it refuses the record as an unknown op kind);
                                10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
                                optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
                                9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
@@ -67,6 +69,11 @@ extern "C" {
 #define T2V_FINGERPRINT_CHUNK 65536
 #define T2V_FINGERPRINT_LEN 0x9E3779B97F4A7C15ull
 
+/* LORA_MERGE: elements of one segment (one weight) that one workgroup updates (the unit of the host's tile table), and the two forms of the product */
+#define T2V_LORA_TILE 4096
+#define T2V_LORA_DIRECT 0    /* delta[n, j] = sum_k B[n, k] A[k, j]                                   (Linear, Conv2d)            */
+#define T2V_LORA_TEMPORAL 1  /* delta[n, j] = mean_s d[n, 3 j + s], d = B A of 3 J columns            (Conv3d [o, i, 3, 1, 1])    */
+
 /* ---- op kinds ------------------------------------------------------------------------- */
 enum t2v_op_kind {
   T2V_OP_GEMM = 1,        /* implicit-GEMM conv / linear on MFMA, fused epilogue            */
@@ -94,7 +101,8 @@ enum t2v_op_kind {
   T2V_OP_AVGPOOL2 = 23,      /* 2x2 / stride 2 average pooling of channels-last fp32 tokens (mean in fp32), fp32 and / or fp16 out */
   T2V_OP_EMPHASIS = 24,      /* prompt emphasis of a batch of text-encoder chunks: per-token multipliers, then the batch mean restored (fp64 sums, one workgroup) */
   T2V_OP_FINGERPRINT = 25,   /* one 64-bit fingerprint per byte range of a device table (in-place edits of packed parameters); stand-alone, never part of a plan */
-  T2V_OP_KIND_MAX = 26
+  T2V_OP_LORA_MERGE = 26,    /* W += alpha * (B A) for every weight of a device table, in place (Stable LoRA merge / un-merge); stand-alone, never part of a plan */
+  T2V_OP_KIND_MAX = 27
 };
 
 /* GEMM gather modes: how row m / reduction index k of the A operand are addressed          */
@@ -352,6 +360,19 @@ enum t2v_gather {
  *      [c * T2V_FINGERPRINT_CHUNK, (c + 1) * T2V_FINGERPRINT_CHUNK), one workgroup each; EVERY chunk of every segment exactly once, and chunk 0 of
  *      every segment (an empty one included: it carries the length term).  `out` is zeroed by the op (a memset on the stream), then one launch.
  *      i: 0 n segments, 1 n chunks (>= n);  p: 0 table: n x {uint64 address, uint64 nbytes}, 1 out uint64 [n], 2 chunk table: n chunks x {uint32, uint32} (all 8-byte aligned)
+ * LORA_MERGE (ABI 11, t2v_run_ops only: t2v_plan_create refuses it): the Stable LoRA merge (stable_lora/stable_utils/lora_processor.py:50-101) of every
+ *      weight of a device table in ONE launch, in place.  A segment = one weight W, row-major [N, J] of dtype T (T2V_F16 | T2V_F32), with its factors
+ *      A [r, Jf] and B [N, r] (row-major, dtype T).  Per element, every step rounded once to T (the arithmetic contract):
+ *          d = T(sum over ascending k of B[n, k] * A[k, j'])            fp32 accumulation (fp16 factors: every product is exact in fp32)
+ *          T2V_LORA_DIRECT   (Jf = J):    j' = j
+ *          T2V_LORA_TEMPORAL (Jf = 3 J):  d = T((d(3 j) + d(3 j + 1) + d(3 j + 2)) / 3), summed in fp32 in that order, IEEE division
+ *          e = T(fp32(d) * f[0]);   W[n, j] = T(fp32(W[n, j]) + fp32(e))
+ *      Un-merging is the same record with -f[0] (x - y is x + (-y)).  Any r >= 1 (a loop over k).  W, A and B may sit at any element-aligned address;
+ *      16-byte accesses are used where the addresses allow.  No byte outside [W, W + N J) is written.  The tile table lists {uint32 segment, uint32 tile}
+ *      pairs: tile t of segment s = its elements [t * T2V_LORA_TILE, (t + 1) * T2V_LORA_TILE) of the flat row-major weight, one workgroup each; EVERY
+ *      tile of every segment exactly once (a tile listed twice is merged twice), and the segments of one table must not overlap (the host's check).
+ *      segment record (48 bytes): {uint64 W, uint64 A, uint64 B, int32 N, int32 J, int32 r, int32 form, int32 dtype, int32 0}
+ *      i: 0 n segments, 1 n tiles (>= n);  f: 0 alpha;  p: 0 segment table, 1 tile table: n tiles x {uint32, uint32} (both 8-byte aligned)
  */
 typedef struct t2v_op {
   int32_t kind;

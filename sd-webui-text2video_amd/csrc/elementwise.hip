@@ -16,6 +16,8 @@
 //   avgpool2      the adapter's Downsample(use_conv=False): nn.AvgPool2d(2, 2) on channels-last fp32 tokens
 //   fingerprint   one 64-bit value per byte range of a table (the parameters of a model): which tensors were edited in place since
 //                 the weight images were packed (packing.ParamFingerprint)
+//   lora_merge    W += alpha * (B A) for every weight of a table, in place: the Stable LoRA merge / un-merge of one file in one launch
+//                 (stable_lora/stable_utils/lora_processor.py:50-101, 202-246; stable_lora.py)
 #include "t2v_kernels.h"
 
 namespace {
@@ -426,6 +428,185 @@ __global__ __launch_bounds__(256) void fingerprint_kernel(const FpSeg* segs, con
   if (t == 0) atomicAdd(out + ck.x, red[0]);
 }
 
+// Stable LoRA merge (T2V_OP_LORA_MERGE; stable_lora/stable_utils/lora_processor.py:50-101): W += alpha * (B A) for every weight of a table, in
+// place, one launch.  The contract per element, every step rounded once to the weight's type T (include/t2v_hip.h):
+//     d = T(sum over ascending k of B[n,k] A[k,j'])  (fp32 accumulation; fp16 products are exact in fp32, so the FMA below adds no rounding of its own)
+//     temporal form (Conv3d [o, i, 3, 1, 1], A of 3 J columns):  d = T((d(3j) + d(3j+1) + d(3j+2)) / 3), fp32, that order, IEEE division
+//     e = T(d * alpha);   W = T(W + e)
+// which is bit for bit what the reference's `(lora_B @ lora_A).view(...)`, `torch.mean`, `* alpha` and `+=` give on fp16 tensors.  The products of
+// the last two lines are written with the _rn intrinsics and fenced (lora_f32): the compiler may neither contract them into one FMA (for
+// T = float nothing else would separate them) nor fold an fp32 step into the conversion to fp16 that follows it.
+// One workgroup per tile {segment, tile index} of the host's tile table: T2V_LORA_TILE consecutive elements of ONE weight (flat, row-major).
+// Like the fingerprint: 16-byte accesses of W between 16-byte boundaries of the ADDRESS, single elements in front of and behind them, so a
+// weight may start anywhere and end anywhere; nothing outside [W + t0, W + t1) is touched.  Per vector of one row, A's row k is read as one
+// 16-byte load where its address allows (lanes side by side: coalesced), B[n, k] once per vector; a vector that runs over a row end, and
+// factors at odd addresses, take the element path.  The loops over k are unrolled by 4: the loads of four rows of A are in flight together;
+// the sums stay in ascending k.  Measured (profiles/stable_lora.txt): 3.4 ms for the full UNet at rank 16, bound by the r rows of A that every
+// element of a one-row run re-reads through the vector L1, not by HBM and not by latency (one row per wait: 3.5 ms).
+struct LoraSeg { unsigned long long w, a, b; int N, J, r, form, dtype, pad; };
+template <typename T> struct LoraVec;
+template <> struct LoraVec<f16> { typedef f16x8 type; };
+template <> struct LoraVec<float> { typedef f32x4 type; };
+
+// An fp32 result that the contract rounds to fp32 BEFORE it is rounded to T.  Without the fence the compiler selects v_fma_mixlo_f16 for
+// `(f16)(d * alpha)` (and may for the last FMA of a sum), which rounds the exact product ONCE to fp16: measured on the device, 1.9 % of the
+// products with alpha = 0.7 come out one fp16 ulp away from the reference's `tensor * alpha` (fp32 product, then fp16), which shows in W where
+// W + e cancels.  The empty statement keeps the value in a VGPR as an fp32 number; it costs no instruction.
+__device__ __forceinline__ float lora_f32(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// d = T(s) of an fp32 sum, as an fp32 number
+template <typename T>
+__device__ __forceinline__ float lora_round(float s) { return (float)(T)lora_f32(s); }
+
+template <typename T>
+__device__ __forceinline__ T lora_apply(T w, float d, float alpha) {
+  const float e = lora_round<T>(__fmul_rn(d, alpha));
+  return (T)lora_f32(__fadd_rn((float)w, e));
+}
+
+template <typename T>
+__device__ __forceinline__ float lora_mean3(float s0, float s1, float s2) {
+  const float d0 = lora_round<T>(s0), d1 = lora_round<T>(s1), d2 = lora_round<T>(s2);
+  return lora_round<T>(__fdiv_rn(lora_f32(__fadd_rn(lora_f32(__fadd_rn(d0, d1)), d2)), 3.0f));
+}
+
+// d of one element (n, j): b = row n of B
+template <typename T>
+__device__ float lora_delta(const T* A, const T* b, long Jf, int r, int form, long j) {
+  if (form == T2V_LORA_DIRECT) {
+    const T* a = A + j;
+    float s = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < r; ++k) s = fmaf((float)b[k], (float)a[(long)k * Jf], s);
+    return lora_round<T>(s);
+  }
+  const T* a = A + 3 * j;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll 4
+  for (int k = 0; k < r; ++k) {
+    const float bk = (float)b[k];
+    const T* ak = a + (long)k * Jf;
+    s0 = fmaf(bk, (float)ak[0], s0);
+    s1 = fmaf(bk, (float)ak[1], s1);
+    s2 = fmaf(bk, (float)ak[2], s2);
+  }
+  return lora_mean3<T>(s0, s1, s2);
+}
+
+template <typename T>
+__device__ void lora_merge_tile(const LoraSeg& sg, unsigned tile, float alpha, int t) {
+  typedef unsigned long long u64;
+  typedef typename LoraVec<T>::type vec;
+  constexpr int V = 16 / (int)sizeof(T);
+  if ((sg.w | sg.a | sg.b) % sizeof(T) != 0) return;               // (the host refuses addresses that are not element-aligned; never touch one)
+  const u64 total = (u64)sg.N * (u64)sg.J;
+  const u64 t0 = (u64)tile * T2V_LORA_TILE;
+  if (t0 >= total) return;
+  const u64 t1 = t0 + T2V_LORA_TILE < total ? t0 + T2V_LORA_TILE : total;
+  T* W = reinterpret_cast<T*>(sg.w);
+  const T* A = reinterpret_cast<const T*>(sg.a);
+  const T* B = reinterpret_cast<const T*>(sg.b);
+  const int r = sg.r, form = sg.form;
+  const long J = sg.J, Jf = form == T2V_LORA_TEMPORAL ? 3 * J : J;
+  const u64 p0 = sg.w + t0 * sizeof(T), p1 = sg.w + t1 * sizeof(T);
+  u64 a0 = (p0 + 15) & ~15ull;                                     // the 16-byte aligned interior [a0, a1) of [p0, p1)
+  if (a0 > p1) a0 = p1;
+  const u64 a1 = a0 + ((p1 - a0) & ~15ull);
+  const int head = (int)((a0 - p0) / sizeof(T)), tail = (int)((p1 - a1) / sizeof(T));     // < V elements each
+  if (t < head + tail) {
+    const u64 e = t < head ? t0 + (u64)t : t1 - (u64)tail + (u64)(t - head);
+    const u64 n = e / (u64)J;
+    const float d = lora_delta<T>(A, B + n * (u64)r, Jf, r, form, (long)(e - n * (u64)J));
+    W[e] = lora_apply<T>(W[e], d, alpha);
+  }
+  const u64 e_first = t0 + (u64)head;
+  const long nvec = (long)((a1 - a0) >> 4);
+  const bool rows_aligned = ((u64)Jf * sizeof(T)) % 16 == 0;       // every row of A starts at the same offset from a 16-byte boundary
+  for (long q = t; q < nvec; q += 256) {
+    const u64 e = e_first + (u64)q * V;
+    u64 n = e / (u64)J;
+    long j = (long)(e - n * (u64)J);
+    vec w = *reinterpret_cast<const vec*>(W + e);
+    if (j + V <= J) {                                              // V elements of one row
+      const T* b = B + n * (u64)r;
+      if (form == T2V_LORA_DIRECT) {
+        const T* a = A + j;
+        float s[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) s[i] = 0.f;
+        if (rows_aligned && (u64)a % 16 == 0) {
+#pragma unroll 4
+          for (int k = 0; k < r; ++k) {
+            const float bk = (float)b[k];
+            const vec av = *reinterpret_cast<const vec*>(a + (long)k * Jf);
+#pragma unroll
+            for (int i = 0; i < V; ++i) s[i] = fmaf(bk, (float)av[i], s[i]);
+          }
+        } else {
+#pragma unroll 4
+          for (int k = 0; k < r; ++k) {
+            const float bk = (float)b[k];
+            const T* ak = a + (long)k * Jf;
+#pragma unroll
+            for (int i = 0; i < V; ++i) s[i] = fmaf(bk, (float)ak[i], s[i]);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < V; ++i) w[i] = lora_apply<T>(w[i], lora_round<T>(s[i]), alpha);
+      } else {
+        const T* a = A + 3 * j;
+        float s[3 * V];
+#pragma unroll
+        for (int i = 0; i < 3 * V; ++i) s[i] = 0.f;
+        if (rows_aligned && (u64)a % 16 == 0) {
+#pragma unroll 4
+          for (int k = 0; k < r; ++k) {
+            const float bk = (float)b[k];
+            const vec* ak = reinterpret_cast<const vec*>(a + (long)k * Jf);
+            const vec v0 = ak[0], v1 = ak[1], v2 = ak[2];
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+              s[i] = fmaf(bk, (float)v0[i], s[i]);
+              s[V + i] = fmaf(bk, (float)v1[i], s[V + i]);
+              s[2 * V + i] = fmaf(bk, (float)v2[i], s[2 * V + i]);
+            }
+          }
+        } else {
+#pragma unroll 4
+          for (int k = 0; k < r; ++k) {
+            const float bk = (float)b[k];
+            const T* ak = a + (long)k * Jf;
+#pragma unroll
+            for (int i = 0; i < 3 * V; ++i) s[i] = fmaf(bk, (float)ak[i], s[i]);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < V; ++i) w[i] = lora_apply<T>(w[i], lora_mean3<T>(s[3 * i], s[3 * i + 1], s[3 * i + 2]), alpha);
+      }
+    } else {                                                       // the vector runs over a row end: element by element
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        w[i] = lora_apply<T>(w[i], lora_delta<T>(A, B + n * (u64)r, Jf, r, form, j), alpha);
+        if (++j == J) { j = 0; ++n; }
+      }
+    }
+    *reinterpret_cast<vec*>(W + e) = w;
+  }
+}
+
+__global__ __launch_bounds__(256) void lora_merge_kernel(const LoraSeg* segs, const uint2* tiles, int n, float alpha) {
+  const uint2 tl = tiles[blockIdx.x];
+  if (tl.x >= (unsigned)n) return;
+  const LoraSeg sg = segs[tl.x];
+  if (sg.N <= 0 || sg.J <= 0 || sg.r <= 0 || sg.w == 0 || sg.a == 0 || sg.b == 0) return;      // (the host builds none of these)
+  if (sg.form != T2V_LORA_DIRECT && sg.form != T2V_LORA_TEMPORAL) return;
+  if (sg.dtype == T2V_F16) lora_merge_tile<f16>(sg, tl.y, alpha, threadIdx.x);
+  else if (sg.dtype == T2V_F32) lora_merge_tile<float>(sg, tl.y, alpha, threadIdx.x);
+}
+
 // tensor2vid (t2v_pipeline.py:447-460): video[i,c,f,y,x] -> uint8 out[f, y, i*W + x, c]: v*0.5 + 0.5 (two roundings, as
 // mul_ / add_), clamp to [0,1], *255, TRUNCATED like `(image.numpy()*255).astype('uint8')`.  HALF: the reference's
 // 'GPU (half precision)' VAE hands tensor2vid an fp16 video, so every intermediate is rounded to fp16 (the input too
@@ -794,6 +975,15 @@ hipError_t t2v_launch_fingerprint(const t2v_op& op, hipStream_t s) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fingerprint_kernel, dim3(n_chunks), dim3(256), 0, s, reinterpret_cast<const FpSeg*>(op.p[0]),
                      reinterpret_cast<const uint2*>(op.p[2]), out, n);
+  return hipGetLastError();
+}
+
+hipError_t t2v_launch_lora_merge(const t2v_op& op, hipStream_t s) {
+  static_assert(sizeof(LoraSeg) == 48, "the segment record of include/t2v_hip.h");
+  const int n = op.i[0], n_tiles = op.i[1];
+  if (n <= 0 || n_tiles < n || op.p[0] == 0 || op.p[1] == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lora_merge_kernel, dim3(n_tiles), dim3(256), 0, s, reinterpret_cast<const LoraSeg*>(op.p[0]),
+                     reinterpret_cast<const uint2*>(op.p[1]), n, op.f[0]);
   return hipGetLastError();
 }
 

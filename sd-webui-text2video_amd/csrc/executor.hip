@@ -300,6 +300,12 @@ int validate_op(const t2v_op& op, int idx) {
       for (int k = 0; k < 3; ++k)
         if (op.p[k] >= T2V_EXT_SLOTS && op.p[k] % 8 != 0) return bad("fingerprint: the tables and the output must be 8-byte aligned");
       return 0;
+    case T2V_OP_LORA_MERGE:
+      if (op.i[0] <= 0 || op.i[1] < op.i[0]) return bad("lora merge: n segments > 0, at least one tile per segment");
+      if (op.p[0] == 0 || op.p[1] == 0) return bad("null lora merge pointer");
+      for (int k = 0; k < 2; ++k)
+        if (op.p[k] >= T2V_EXT_SLOTS && op.p[k] % 8 != 0) return bad("lora merge: the tables must be 8-byte aligned");
+      return 0;
     case T2V_OP_ALLGATHER:
       if (op.i[2] < 1 || op.i[3] < 0 || op.i[3] >= op.i[2] || op.p[0] == 0) return bad("bad all-gather record");
       return 0;
@@ -429,6 +435,7 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
     case T2V_OP_AVGPOOL2: return t2v_launch_avgpool2(op, s);
     case T2V_OP_EMPHASIS: return t2v_launch_emphasis(op, s);
     case T2V_OP_FINGERPRINT: return t2v_launch_fingerprint(op, s);
+    case T2V_OP_LORA_MERGE: return t2v_launch_lora_merge(op, s);
     case T2V_OP_MEMSET: {
       const size_t bytes = (size_t)(uint32_t)op.i[0] | ((size_t)(uint32_t)op.i[1] << 32);
       return hipMemsetAsync(reinterpret_cast<void*>(op.p[0]), 0, bytes, s);
@@ -913,6 +920,7 @@ int t2v_plan_create(const t2v_op* ops, int n, t2v_plan** out) {
     const int rc = validate_op(ops[k], k);
     if (rc != 0) return rc;
     if (ops[k].kind == T2V_OP_FINGERPRINT) return fail(T2V_ERR_BAD_ARG, "fingerprint: a stand-alone op (t2v_run_ops), not part of a plan");
+    if (ops[k].kind == T2V_OP_LORA_MERGE) return fail(T2V_ERR_BAD_ARG, "lora merge: a stand-alone op (t2v_run_ops), not part of a plan");
   }
   t2v_plan* p = new t2v_plan();
   p->ops.assign(ops, ops + n);

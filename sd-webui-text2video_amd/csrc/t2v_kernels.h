@@ -315,6 +315,7 @@ hipError_t t2v_launch_depth_tokens(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_avgpool2(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_emphasis(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_fingerprint(const t2v_op& op, hipStream_t s);
+hipError_t t2v_launch_lora_merge(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_reshard_rows(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_time_embed(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_copy2d(const t2v_op& op, hipStream_t s);

@@ -325,7 +325,12 @@ def process_modelscope(args_dict: dict, extra_args=None):
                    batch_count, clip_encoder | (cond, uncond), stitch,
                    enable_emphasis, comma_padding_backtrack,                  # webui's opts of the prompt syntax (clip_hardcode.py:153,203)
                    do_vid2vid, vid2vid_frames, strength,                      # :80-147
-                   inpainting_frames, inpainting_image, inpainting_weights}   # :170-217
+                   inpainting_frames, inpainting_image, inpainting_weights,   # :170-217
+                   stable_lora}                                               # :69-71, below
+    * `stable_lora` = {lora_files_selection, lora_alpha, use_bias, use_linear, use_conv, use_emb, use_multiplier, use_time[, lora_dir]},
+      or the same eight values as an eight-element `extra_args` in that order (the reference's): `stable_lora.StableLoraScript.process`
+      runs on the pipe before sampling — the selected files are merged into `pipe.sd_model` and the text encoder's transformer, or taken
+      out again when the selection, the weight or an option changed since the last call.  With neither present nothing changes.
     * `stitch(frames_bgr, infotext) -> bytes` (the ffmpeg stage, out of scope — e.g. the reference's own
       `ffmpeg_stitch_video` behind a temp directory) given: returns the reference's list of data-URLs, video b from
       seed + b (seed -1 stays random), exactly the reference loop;
@@ -352,6 +357,13 @@ def process_modelscope(args_dict: dict, extra_args=None):
         pipe = TextToVideoSynthesis(a.model_dir, clip_encoder=getattr(a, "clip_encoder", None))
     if hasattr(pipe, "set_prompt_options"):
         pipe.set_prompt_options(getattr(a, "enable_emphasis", None), getattr(a, "comma_padding_backtrack", None))
+    # the Stable LoRA stage (process_modelscope.py:69-71 -> StableLoraScript.process): merge / un-merge before anything is encoded or sampled
+    lora_settings = getattr(a, "stable_lora", None)
+    if lora_settings is None and extra_args is not None and len(extra_args) == 8:
+        lora_settings = list(extra_args)
+    if lora_settings is not None:
+        from . import stable_lora
+        stable_lora.run_for_pipe(pipe, lora_settings)
     width, height = getattr(a, "width", 256), getattr(a, "height", 256)
     common = dict(frames=a.frames, scale=a.cfg_scale, width=width, height=height, eta=getattr(a, "eta", 0.0),
                   sampler=getattr(a, "sampler", available_samplers[0].name))
