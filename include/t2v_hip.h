@@ -36,6 +36,8 @@ extern "C" {
                                still 11: T2V_OP_FINGERPRINT (a new kind, stand-alone: 64-bit fingerprints of a table of byte ranges; no existing record changes);
                                still 11: T2V_OP_LORA_MERGE (a new kind, stand-alone: W += alpha * (B A) over a table of weights, in place, one launch; no existing record
                                changes, and a library without it refuses the record as an unknown op kind);
+                               still 11: RESAMPLE i[9] = 1 / i[10] / i[11] (a float bicubic resize of planar images in one launch — the resizes around the depth
+                               estimator of the VideoCrafter depth adapter; additive on fields that every earlier record leaves zero);
                                10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
                                optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
                                9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
@@ -96,7 +98,7 @@ enum t2v_op_kind {
   T2V_OP_RESHARD_ROWS = 18,  /* chunked row regrouping (pack / unpack of a frame <-> pixel resharding), optional fp32 residual */
   T2V_OP_ALLTOALL = 19,      /* frame <-> pixel resharding of a T-sharded clip over the plan's communicator */
   T2V_OP_STATS_HALO = 20,    /* GroupNorm statistics parts to every rank + raw boundary frames to the two neighbours: one grouped exchange */
-  T2V_OP_RESAMPLE = 21,      /* one separable pass of a table-driven uint8 image resize (Pillow's 8-bit resampler, bit-exact); optional float token output */
+  T2V_OP_RESAMPLE = 21,      /* one separable pass of a table-driven uint8 image resize (Pillow's 8-bit resampler, bit-exact), optional float token output; i[9] = 1: a float bicubic resize of planar images */
   T2V_OP_DEPTH_TOKENS = 22,  /* depth frames [n,1,H,W] -> PixelUnshuffle(8) channels-last fp16 tokens, optional per-frame min-max normalisation (T2I-Adapter entry) */
   T2V_OP_AVGPOOL2 = 23,      /* 2x2 / stride 2 average pooling of channels-last fp32 tokens (mean in fp32), fp32 and / or fp16 out */
   T2V_OP_EMPHASIS = 24,      /* prompt emphasis of a batch of text-encoder chunks: per-token multipliers, then the batch mean restored (fp64 sums, one workgroup) */
@@ -336,6 +338,22 @@ enum t2v_gather {
  *      i: 0 N, 1 H, 2 W (of the source), 3 channels (= 3), 4 output size along the axis, 5 axis (0 horizontal | 1 vertical),
  *      6 table row length (ksize), 7 output form, 8 ld of the token forms (>= 3);
  *      p: 0 src uint8, 1 dst, 2 coef int32 [i[4]][i[6]], 3 bounds int32 [i[4]][2] = {first, count}, 4 lut fp32 [256] (forms 1 / 2)
+ *      i[9] = 0 (every record before this mode): all of the above.  i[9] = 1 (ABI 11): FLOAT BICUBIC mode — P planar single-channel images
+ *      src [P, H, W] (fp16 | fp32) -> dst fp32 [P, Ho, Wo], both axes in ONE launch: torch's F.interpolate(mode="bicubic", align_corners=False)
+ *      without antialiasing, enlarging or reducing (lvdm/models/ddpm3d.py:1443-1468: frames to the depth estimator's size, depth maps back).
+ *      The host builds the tables (packing.bicubic_table, per axis, in float64, weights rounded once to fp32): for output index o,
+ *        real = (in / out) * (o + 0.5) - 0.5 (not clamped at 0), i0 = floor(real), t = real - i0, taps i0 - 1 .. i0 + 2 each clamped to
+ *        [0, in - 1], weights c2(t + 1), c1(t), c1(1 - t), c2(2 - t) with A = -0.75, c1(x) = ((A + 2) x - (A + 3)) x^2 + 1,
+ *        c2(x) = ((A x - 5 A) x + 8 A) x - 4 A.
+ *      One output (the arithmetic contract; tests/interp_bicubic.py mirrors it):
+ *        out[p][y][x] = sum_{a = 0..3} wy[y][a] * ( sum_{b = 0..3} wx[x][b] * fp32(src[p][iy[y][a]][ix[x][b]]) )
+ *      both sums in ascending order starting from the first product, EVERY multiply and add rounded to fp32 on its own (no contraction):
+ *      bitwise reproducible, independent of the grid.  A NaN / inf source pixel reaches exactly the outputs whose 4 x 4 footprint names it
+ *      (nothing is special-cased: 0 * NaN is NaN, as in torch).  The kernel clamps the table's indices to the image again before use: a
+ *      malformed table cannot make it read outside the source.  No byte outside dst [P, Ho, Wo] is written.
+ *      i: 0 P, 1 H, 2 W (of the source), 3 = 1 (channels), 4 Ho, 5 = 0, 6 = 4 (taps), 7 = 1 (fp32 out), 8 unused, 9 = 1, 10 Wo,
+ *         11 input dtype (T2V_F16 | T2V_F32);  H * W and Ho * Wo <= 2^28, P * Ho * ceil(Wo / 256) <= 2^24 - 1 (one launch)
+ *      p: 0 src, 1 dst fp32, 2 weights fp32: wy [Ho][4] followed by wx [Wo][4], 3 indices int32: iy [Ho][4] followed by ix [Wo][4]
  * DEPTH_TOKENS (ABI 11): out[(f*(H/8) + y/8)*(W/8) + x/8, (y%8)*8 + x%8] = fp16(v(f, y, x)) — nn.PixelUnshuffle(8) of n single-channel frames
  *      [n, 1, H, W] as channels-last tokens, the A operand of the adapter's conv_in (lvdm/models/modules/adapter.py:93-99).  With i[4] = 1
  *      v = 2 * (d - min_f) / (max_f - min_f + 1e-7) - 1 with the frame's own minimum / maximum (NaN if any pixel is NaN, as torch.amin / amax), evaluated in fp32 in that operation order

@@ -11,6 +11,8 @@
 //                 known-region blend of a masked LVDM step (lvdm/samplers/ddim.py:188-195) to the same launch
 //   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
 //                 (process_modelscope.py:116-120, 174-178); the last pass can write the VAE encoder's tokens
+//   bicubic       torch's F.interpolate(mode="bicubic", align_corners=False) of planar float images, both axes in one launch: the resizes
+//                 around the depth estimator of the VideoCrafter depth adapter (ddpm3d.py:1443-1462); T2V_OP_RESAMPLE with i[9] = 1
 //   depth_tokens  entry of the VideoCrafter depth adapter: per-frame min-max normalisation (ddpm3d.py:1463-1464) + PixelUnshuffle(8)
 //                 (adapter.py:93-99) of the depth frames, as the fp16 tokens conv_in reads
 //   avgpool2      the adapter's Downsample(use_conv=False): nn.AvgPool2d(2, 2) on channels-last fp32 tokens
@@ -797,6 +799,57 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const unsigned char* sr
   rs_store<FORM>(drow, e0, row_bytes, v, lut, ld);
 }
 
+// Float bicubic resize (T2V_OP_RESAMPLE with i[9] = 1): P planar single-channel images [P, H, W] (fp16 | fp32) -> fp32 [P, Ho, Wo], both
+// axes in one launch, with torch's upsample_bicubic2d semantics (align_corners = False, no antialiasing) carried by host-built tables
+// (packing.bicubic_table): per output row y four weights wy / source rows iy, per output column x four weights wx / source columns ix.
+//   out = sum_{a = 0..3} wy[a] * ( sum_{b = 0..3} wx[b] * fp32(src[iy[a]][ix[b]]) )
+// both sums in ascending order from the first product, every multiply and add rounded to fp32 on its own (no contraction): the bits do
+// not depend on the grid or the compiler, and tests/interp_bicubic.py reproduces them with numpy.  Nothing is special-cased for NaN / inf
+// (0 * NaN is NaN, as in torch).  The indices are clamped to the image again before use: a malformed table gives wrong pixels, never a
+// read outside the source.  A workgroup owns 256 consecutive columns of ONE output row (row weights and indices are uniform, the stores
+// coalesced); the four source rows are shared by neighbouring columns and rows through the cache.
+__device__ __forceinline__ int bc_clamp(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
+// hipcc contracts a * b + c into one fused multiply-add by default, and to it __fmul_rn / __fadd_rn are the plain operators (they
+// only keep a product apart where no sum follows it directly): here a sum follows every product, so the two operations are written
+// under `fp contract(off)`, which the compiler's default contraction mode honours.
+__device__ __forceinline__ float bc_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float bc_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+template <typename TIN>
+__global__ __launch_bounds__(256) void bicubic_kernel(const TIN* src, float* dst, const float* wgt, const int* idx, int H, int W, int Ho,
+                                                      int Wo, int tiles) {
+  const long orow = blockIdx.x / tiles;                 // plane * Ho + y
+  const int x = (int)(blockIdx.x - orow * tiles) * 256 + (int)threadIdx.x;
+  if (x >= Wo) return;
+  const long plane = orow / Ho;
+  const int y = (int)(orow - plane * Ho);
+  const float* wy = wgt + 4 * (long)y;
+  const int* iy = idx + 4 * (long)y;
+  const float* wx = wgt + 4 * ((long)Ho + x);
+  const int* ix = idx + 4 * ((long)Ho + x);
+  const float wx0 = wx[0], wx1 = wx[1], wx2 = wx[2], wx3 = wx[3];
+  const int c0 = bc_clamp(ix[0], W), c1 = bc_clamp(ix[1], W), c2 = bc_clamp(ix[2], W), c3 = bc_clamp(ix[3], W);
+  const TIN* img = src + plane * (long)H * W;
+  float acc = 0.f;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const TIN* row = img + (long)bc_clamp(iy[a], H) * W;
+    float h = bc_mul(wx0, (float)row[c0]);
+    h = bc_add(h, bc_mul(wx1, (float)row[c1]));
+    h = bc_add(h, bc_mul(wx2, (float)row[c2]));
+    h = bc_add(h, bc_mul(wx3, (float)row[c3]));
+    const float t = bc_mul(wy[a], h);
+    acc = a == 0 ? t : bc_add(acc, t);
+  }
+  dst[orow * Wo + x] = acc;
+}
+
 inline int grid_for(long n) {
   const long g = (n + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
@@ -855,6 +908,19 @@ hipError_t t2v_launch_to_uint8(const t2v_op& op, hipStream_t s) {
 
 hipError_t t2v_launch_resample(const t2v_op& op, hipStream_t s) {
   // (shape, pointers and the grid size were checked by the executor's validation)
+  if (op.i[9] == 1) {                                    // float bicubic mode: [P, H, W] -> fp32 [P, Ho, Wo], one launch
+    const int P = op.i[0], H = op.i[1], W = op.i[2], Ho = op.i[4], Wo = op.i[10];
+    const int tiles = (Wo + 255) / 256;
+    const dim3 g((unsigned)((long)P * Ho * tiles));
+    float* dst = reinterpret_cast<float*>(op.p[1]);
+    const float* wgt = reinterpret_cast<const float*>(op.p[2]);
+    const int* idx = reinterpret_cast<const int*>(op.p[3]);
+    if (op.i[11] == T2V_F32)
+      hipLaunchKernelGGL(bicubic_kernel<float>, g, dim3(256), 0, s, reinterpret_cast<const float*>(op.p[0]), dst, wgt, idx, H, W, Ho, Wo, tiles);
+    else
+      hipLaunchKernelGGL(bicubic_kernel<f16>, g, dim3(256), 0, s, reinterpret_cast<const f16*>(op.p[0]), dst, wgt, idx, H, W, Ho, Wo, tiles);
+    return hipGetLastError();
+  }
   const int N = op.i[0], H = op.i[1], W = op.i[2], out = op.i[4], axis = op.i[5], ksize = op.i[6], form = op.i[7], ld = op.i[8];
   const unsigned char* src = reinterpret_cast<const unsigned char*>(op.p[0]);
   void* dst = reinterpret_cast<void*>(op.p[1]);

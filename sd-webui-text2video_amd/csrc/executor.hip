@@ -258,6 +258,20 @@ int validate_op(const t2v_op& op, int idx) {
       return 0;
     case T2V_OP_RESAMPLE: {
       const int out = op.i[4], axis = op.i[5], form = op.i[7], ld = op.i[8];
+      if (op.i[9] != 0 && op.i[9] != 1) return bad("resample: mode i[9] must be 0 (uint8 pass) or 1 (float bicubic)");
+      if (op.i[9] == 1) {          // float bicubic: planes [P, H, W] -> fp32 [P, Ho, Wo], one launch
+        const int Wo = op.i[10];
+        if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[2] <= 0 || out <= 0 || Wo <= 0) return bad("bicubic resample: planes, rows, columns and both output sizes must be positive");
+        if (op.i[3] != 1) return bad("bicubic resample: planar single-channel images only (i[3] = 1)");
+        if (op.i[6] != 4) return bad("bicubic resample: four taps per axis (i[6] = 4)");
+        if (form != 1) return bad("bicubic resample: the output form is fp32 (i[7] = 1)");
+        if (op.i[11] != T2V_F16 && op.i[11] != T2V_F32) return bad("bicubic resample: unknown input dtype i[11] (fp16 | fp32)");
+        if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[3] == 0) return bad("null bicubic resample pointer (source, destination, weights, indices)");
+        if ((long)op.i[1] * op.i[2] > (1L << 28) || (long)out * Wo > (1L << 28)) return bad("bicubic resample: image too large");
+        // one workgroup of 256 threads per (plane, output row, tile of 256 columns): HIP refuses a launch of 2^32 threads or more
+        if ((long)op.i[0] * out * ((Wo + 255) / 256) > 0xffffffL) return bad("bicubic resample: too many rows for one launch (planes x rows x tiles of 256 columns <= 2^24 - 1)");
+        return 0;
+      }
       if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[2] <= 0 || out <= 0 || op.i[6] <= 0) return bad("resample: images, rows, columns, output size and table row length must be positive");
       if (op.i[3] != 3) return bad("resample: interleaved RGB only (3 channels)");
       if (axis != 0 && axis != 1) return bad("resample: axis must be 0 (horizontal) or 1 (vertical)");
@@ -689,8 +703,15 @@ bool slot_range(const t2v_op& op, int q, SlotRange* out) {
       if (q == 1) return flat((uint64_t)I[0] * 4);
       if (q == 2) return mat(I[0], I[1], I[3], 4);
       return span(~0ull >> 2);
+    case T2V_OP_RESAMPLE:
+      if (I[9] == 1) {            // float bicubic: its destination may be an arena buffer (the depth path reads it with DEPTH_TOKENS)
+        if (q == 0) return flat((uint64_t)I[0] * I[1] * I[2] * (I[11] == f32 ? 4 : 2));
+        if (q == 1) return flat((uint64_t)I[0] * I[4] * I[10] * 4);
+        if (q == 2 || q == 3) return flat((uint64_t)(I[4] + I[10]) * 4 * 4);
+      }
+      return span(~0ull >> 2);    // the uint8 passes: as the default below
     default:
-      // DDIM_STEP, TO_UINT8, RESAMPLE work on the caller's tensors in every lowering; should one name arena memory, its extent is in doubt
+      // DDIM_STEP, TO_UINT8, RESAMPLE (uint8 passes) work on the caller's tensors in every lowering; should one name arena memory, its extent is in doubt
       return span(~0ull >> 2);
   }
 }

@@ -310,7 +310,7 @@ hipError_t t2v_launch_softmax(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_ncthw_to_cl(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_cl_to_ncthw(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_to_uint8(const t2v_op& op, hipStream_t s);
-hipError_t t2v_launch_resample(const t2v_op& op, hipStream_t s);
+hipError_t t2v_launch_resample(const t2v_op& op, hipStream_t s);            // uint8 Lanczos pass (i[9] = 0) | float bicubic resize (i[9] = 1)
 hipError_t t2v_launch_depth_tokens(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_avgpool2(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_emphasis(const t2v_op& op, hipStream_t s);

@@ -172,6 +172,39 @@ def resample_lut() -> torch.Tensor:
     return 2 * torch.from_numpy(np.arange(256).astype(np.float32) / 255) - 1
 
 
+BICUBIC_A = -0.75              # torch's cubic convolution coefficient (aten UpSample.h: cubic_convolution1 / 2)
+
+
+def bicubic_table(in_size: int, out_size: int, dtype=None):
+    """Tap table of ONE axis of torch's bicubic resize, `F.interpolate(mode="bicubic", align_corners=False)` without antialiasing
+    (aten upsample_bicubic2d; ddpm3d.py:1443-1468 resizes the frames to the depth estimator's size and the depth maps back), from `in_size`
+    to `out_size` pixels, enlarging or reducing: -> (weights float32 [out, 4], indices int32 [out, 4]).  For output index o:
+    real = (in / out) * (o + 0.5) - 0.5 (NOT clamped at 0), i0 = floor(real), t = real - i0; the taps are i0 - 1 .. i0 + 2, each clamped
+    to [0, in - 1]; the weights c2(t + 1), c1(t), c1(1 - t), c2(2 - t) with c1(x) = ((A + 2) x - (A + 3)) x^2 + 1 and
+    c2(x) = ((A x - 5 A) x + 8 A) x - 4 A, A = -0.75.  Coordinates and weights are evaluated in float64 and the weights rounded ONCE to
+    float32 (torch evaluates them in float32: its coordinate error alone is 1e-5 .. 1e-4 of output error, more than the 16-tap sum's; the
+    float64 table does not depend on how a build contracts that arithmetic).  `dtype=numpy.float64` keeps the unrounded weights (tests).
+    T2V_OP_RESAMPLE with i[9] = 1 evaluates out = sum_a wy[a] * (sum_b wx[b] * src[iy[a]][ix[b]]) with one table per axis."""
+    import numpy as np
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError(f"bicubic_table: sizes must be positive, got {in_size} -> {out_size}")
+    A = BICUBIC_A
+    o = np.arange(out_size, dtype=np.float64)
+    real = (in_size / out_size) * (o + 0.5) - 0.5
+    fl = np.floor(real)
+    t = real - fl
+
+    def c1(x):
+        return ((A + 2) * x - (A + 3)) * x * x + 1
+
+    def c2(x):
+        return ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
+
+    w = np.stack([c2(t + 1), c1(t), c1(1 - t), c2(2 - t)], axis=1)
+    idx = np.clip(fl.astype(np.int64)[:, None] + np.arange(-1, 3)[None, :], 0, in_size - 1).astype(np.int32)
+    return np.ascontiguousarray(w.astype(np.float32 if dtype is None else dtype)), np.ascontiguousarray(idx)
+
+
 def linear_dup(w: torch.Tensor) -> torch.Tensor:
     """[N, K] -> [N, 2K] = [W | W]: consumer of an operand laid out [hi (K) | lo (K)] per row."""
     w = linear(w)

@@ -1134,6 +1134,30 @@ class Program:
             self.free(mid)        # stream order: whatever reuses the block is launched after the last pass
         return ops
 
+    def bicubic(self, name: str, src: Ref, src_dtype: str, dst: Ref, packer, *, planes: int, src_hw, dst_hw) -> Op:
+        """torch's `F.interpolate(mode="bicubic", align_corners=False)` of planar single-channel images src [planes, H, W] (fp16 / fp32)
+        -> dst fp32 [planes, H', W'] as ONE T2V_OP_RESAMPLE record of the float bicubic mode (i[9] = 1): both axes in one launch.  The
+        tables are packed images of `packer` (packing.bicubic_table: weights fp32 and indices int32, rows of the y axis followed by
+        the rows of the x axis), named by the geometry: two passes of the same geometry share them."""
+        from . import packing as pk
+        import numpy as np
+        import torch
+        (H, W), (H2, W2) = (int(v) for v in src_hw), (int(v) for v in dst_hw)
+        assert planes > 0 and min(H, W, H2, W2) > 0
+        if (H, W) == (H2, W2):
+            raise ValueError("bicubic: source and destination sizes are equal, nothing to emit")
+
+        def table(which):
+            def build(sd, k=0 if which == "w" else 1):
+                return torch.from_numpy(np.concatenate([pk.bicubic_table(H, H2)[k], pk.bicubic_table(W, W2)[k]], axis=0))
+            return Ref("weight", 0, packer.add(f"bicubic:{H}x{W}->{H2}x{W2}:{which}", "f32" if which == "w" else "i32", build))
+
+        op = Op(L.OP_RESAMPLE, name)
+        op.i[0:12] = [planes, H, W, 1, H2, 0, 4, 1, 0, 1, W2, _DT[src_dtype]]
+        op.p[0:4] = [src, dst, table("w"), table("idx")]
+        op.meta = dict(mode="bicubic", src=(H, W), dst=(H2, W2))
+        return self._emit(op)
+
     def depth_tokens(self, name: str, src: Ref, src_dtype: str, out: Buf, *, n: int, H: int, W: int, normalise: bool) -> Op:
         """T2V_OP_DEPTH_TOKENS: depth frames src [n, 1, H, W] -> nn.PixelUnshuffle(8) as channels-last fp16 tokens out [n * H/8 * W/8, 64]
         (channel = dy * 8 + dx), the A operand of the adapter's conv_in.  normalise: each frame is first mapped to

@@ -494,6 +494,50 @@ def _pad64(c: int) -> int:
     return (c + 63) // 64 * 64
 
 
+_BICUBIC_PROGRAMS: dict = {}          # (planes, H, W, size, dtype, device) -> (_Compiled, packed tables); at most 4 kept
+
+
+def _bicubic_compile(planes: int, src_hw, dst_hw, x_dt: str) -> _Compiled:
+    prog, packer = Program(f"bicubic p{planes} {src_hw[0]}x{src_hw[1]} -> {dst_hw[0]}x{dst_hw[1]}"), pk.WeightPacker()
+    prog.begin()
+    prog.bicubic("bicubic", Ref("ext", L.EXT_X), x_dt, Ref("ext", L.EXT_OUT), packer, planes=planes, src_hw=src_hw, dst_hw=dst_hw)
+    prog.finish()
+    return _Compiled(prog, packer)
+
+
+@torch.no_grad()
+def bicubic_resize(x, size):
+    """x [n, c, H, W] (fp16 / fp32, on the device) -> fp32 [n, c, *size]: the package's `F.interpolate(x, size=size, mode="bicubic",
+    align_corners=False)` — the resizes the reference wraps around its depth estimator (ddpm3d.py:1443-1462) — as ONE launch of
+    T2V_OP_RESAMPLE's float bicubic mode over all n c planes, both axes at once.  The taps and weights are torch's, built on the host
+    in float64 (packing.bicubic_table); the arithmetic is fixed (include/t2v_hip.h), so results repeat bit for bit.  Equal sizes
+    return `x.float()` without a launch (the tables would give the weights (0, 1, 0, 0): the same values for finite input).
+    Programs are cached per (n c, H, W, size, dtype), at most 4 kept.  There is no CPU fallback."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise L.T2VError("bicubic_resize needs a device tensor on an AMD GPU (no CPU fallback)")
+    size = tuple(int(v) for v in size)
+    if x.dim() != 4 or min(x.shape) < 1 or len(size) != 2 or min(size) < 1:
+        raise ValueError(f"bicubic_resize: x [n, c, H, W] and size (h, w) with positive extents are required, got {tuple(x.shape)} -> {size}")
+    if x.dtype not in (torch.float16, torch.float32):
+        x = x.float()
+    n, c, H, W = x.shape
+    if (H, W) == size:
+        return x.float()
+    x = x.contiguous()
+    key = (n * c, H, W, size, x.dtype, x.device)
+    ent = _BICUBIC_PROGRAMS.get(key)
+    if ent is None:
+        comp = _bicubic_compile(n * c, (H, W), size, "f16" if x.dtype == torch.float16 else "f32")
+        ent = _BICUBIC_PROGRAMS[key] = (comp, comp.packer.materialise({}, x.device))
+        while len(_BICUBIC_PROGRAMS) > 4:
+            del _BICUBIC_PROGRAMS[next(k for k in _BICUBIC_PROGRAMS if k != key)]
+    comp, packed = ent
+    comp.ensure_bound(packed, x.device)
+    out = torch.empty((n, c) + size, dtype=torch.float32, device=x.device)
+    comp.bound.run({L.EXT_X: x.data_ptr(), L.EXT_OUT: out.data_ptr()}, torch.cuda.current_stream(x.device).cuda_stream)
+    return out
+
+
 def _adapter_block_params(in_c, out_c, down, ksize, sk, use_conv):
     """ResnetBlock (adapter.py:39-71): same sub-module names, same registration order."""
     ps = ksize // 2
@@ -552,31 +596,39 @@ class Adapter(nn.Module):
             out.append((c, h, w))
         return out
 
-    def _compile(self, n, H, W, x_dt="f32", normalise=False, front_only=False) -> _Compiled:
-        low = _AdapterLowering(self, n, H, W, x_dt, normalise, front_only)
+    def _compile(self, n, H, W, x_dt="f32", normalise=False, front_only=False, src_hw=None) -> _Compiled:
+        low = _AdapterLowering(self, n, H, W, x_dt, normalise, front_only, src_hw)
         return _Compiled(low.build(), low.packer)
 
     def _signature(self):
         return tuple((k, id(p), p._version, p.device.type, p.dtype) for k, p in self.named_parameters())
 
-    def _run(self, x, normalise: bool, front_only: bool = False):
+    def _run(self, x, normalise: bool, front_only: bool = False, size=None):
+        """size (front end only): the frames arrive at another size and are first resized to `size` with the bicubic pass, in the same program."""
         if not torch.is_tensor(x) or not x.is_cuda:
             raise L.T2VError("Adapter needs a device tensor on an AMD GPU (no CPU fallback)")
-        if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[2] < 8 or x.shape[3] < 8:
+        src_hw = None
+        if size is not None and x.dim() == 4 and tuple(x.shape[2:]) != tuple(size):
+            assert front_only
+            src_hw, size = tuple(int(v) for v in x.shape[2:]), tuple(int(v) for v in size)
+            if x.shape[1] != 1 or min(src_hw) < 1 or len(size) != 2 or size[0] % 8 or size[1] % 8 or min(size) < 8:
+                raise ValueError(f"Adapter: depth frames [n, 1, H', W'] and a target size of multiples of 8 are required, got {tuple(x.shape)} -> {size}")
+        elif x.dim() != 4 or x.shape[1] != 1 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[2] < 8 or x.shape[3] < 8:
             raise ValueError(f"Adapter: depth frames [n, 1, H, W] with H, W multiples of 8 are required, got {tuple(x.shape)}")
         if x.dtype not in (torch.float16, torch.float32):
             x = x.float()
         x = x.contiguous()
-        n, _, H, W = x.shape
+        n = x.shape[0]
+        H, W = size if src_hw is not None else x.shape[2:]
         shapes = self.feature_shapes(H, W)
         if not front_only and min(min(h, w) for _, h, w in shapes) < 1:
             raise ValueError(f"Adapter: {H} x {W} frames are too small for {len(self.channels)} levels")
-        key = (n, H, W, x.dtype, bool(normalise), front_only)
+        key = (n, H, W, x.dtype, bool(normalise), front_only) + ((src_hw,) if src_hw is not None else ())
         comp = self._programs.get(key)
         if comp is None:
             while len(self._programs) >= 4:                    # (each program owns a device arena)
                 del self._programs[next(iter(self._programs))]
-            comp = self._programs[key] = self._compile(n, H, W, "f16" if x.dtype == torch.float16 else "f32", normalise, front_only)
+            comp = self._programs[key] = self._compile(n, H, W, "f16" if x.dtype == torch.float16 else "f32", normalise, front_only, src_hw)
         sig = self._signature()
         if self._packed is None or self._packed_sig != sig or self._packed_device != x.device:
             self._packed, self._packed_sig, self._packed_device = {}, sig, x.device
@@ -610,12 +662,16 @@ class Adapter(nn.Module):
         return [o.view(n, h, w, o.shape[1])[..., :c].permute(0, 3, 1, 2) for o, (c, h, w) in zip(outs, shapes)]
 
     @torch.no_grad()
-    def normalise_depth(self, depth):
+    def normalise_depth(self, depth, size=None):
         """depth [n, 1, H, W] -> the per-frame min-max normalised depth in [-1, 1] (ddpm3d.py:1463-1464) as fp32 [n, 1, H, W]: the
         front-end op alone, its PixelUnshuffle(8) tokens folded back.  The values are the fp16 numbers the adapter's first convolution
-        reads, so `forward(normalise_depth(d))` and `forward(d, normalise=True)` give the same features bit for bit."""
-        (tok,), _ = self._run(depth, True, front_only=True)
-        n, _, H, W = depth.shape
+        reads, so `forward(normalise_depth(d))` and `forward(d, normalise=True)` give the same features bit for bit.
+        size (H, W) other than the depth's own: the depth maps [n, 1, H', W'] of any size are first resized to it as
+        `F.interpolate(mode="bicubic", align_corners=False)` does (ddpm3d.py:1458-1462) by a bicubic pass of the SAME program, into an
+        fp32 arena buffer the front end reads — no host round trip; the bits of `normalise_depth(bicubic_resize(depth, size))`."""
+        (tok,), _ = self._run(depth, True, front_only=True, size=size)
+        n = depth.shape[0]
+        H, W = depth.shape[2:] if size is None else size
         return tok.view(n, H // 8, W // 8, 8, 8).permute(0, 1, 3, 2, 4).reshape(n, 1, H, W).float()
 
 
@@ -625,8 +681,11 @@ class _AdapterLowering:
     [n * h * w, C padded to 64] — fp32 for the residual stream, an fp16 cast of it as the next convolution's operand; padding channels
     meet zero weight rows / columns and stay zero.  The last block2 of level k writes feature k straight to ext slot T2V_EXT_ADAPTER + k."""
 
-    def __init__(self, net: Adapter, n, H, W, x_dt, normalise, front_only=False):
+    def __init__(self, net: Adapter, n, H, W, x_dt, normalise, front_only=False, src_hw=None):
+        """src_hw (front end only; the opt-in depth path): the frames arrive as [n, 1, *src_hw] and a bicubic pass resizes them to H x W first."""
+        assert src_hw is None or (front_only and tuple(src_hw) != (H, W))
         self.net, self.n, self.H, self.W, self.x_dt, self.normalise, self.front_only = net, n, H, W, x_dt, normalise, front_only
+        self.src_hw = src_hw
         self.P = Program(f"adapter n{n} {H}x{W}")
         self.packer = pk.WeightPacker()
 
@@ -662,7 +721,12 @@ class _AdapterLowering:
         P.begin()
         if self.front_only:
             tok = Buf(Ref("ext", L.EXT_ADAPTER), n * h * w, 64, 64, "f16")
-            P.depth_tokens("unshuffle", Ref("ext", L.EXT_X), self.x_dt, tok, n=n, H=self.H, W=self.W, normalise=self.normalise)
+            src, src_dt = Ref("ext", L.EXT_X), self.x_dt
+            if self.src_hw is not None:          # depth maps of another size: the bicubic pass into an fp32 arena buffer, read by the front end
+                big = P.alloc(n * self.H, self.W, "f32")
+                P.bicubic("resize", src, src_dt, big.ref, self.packer, planes=n, src_hw=self.src_hw, dst_hw=(self.H, self.W))
+                src, src_dt = big.ref, "f32"
+            P.depth_tokens("unshuffle", src, src_dt, tok, n=n, H=self.H, W=self.W, normalise=self.normalise)
             P.finish()
             return P
         tok = P.alloc(n * h * w, 64, "f16")
@@ -887,11 +951,15 @@ class T2VAdapterDepth(LatentDiffusion):
     """ddpm3d.py:1436-1484 — LatentDiffusion + the depth adapter ("VideoControl").  The reference builds its parts from configs;
     here `adapter_config` is an `Adapter` or a dict {"params": {Adapter keywords}, "cond_name": "depth"}, and `depth_stage_config`
     an optional depth estimator: any callable frames [n, 3, H, W] -> depth [n, 1, H, W] on the device (the MiDaS network itself is
-    outside this package).  State-dict keys of the adapter: 'adapter.*', as in the released checkpoint."""
+    outside this package).  State-dict keys of the adapter: 'adapter.*', as in the released checkpoint.
+    depth_resize (keyword, or set the attribute later; default None): the size (h, w) the estimator works at — the reference's MiDaS
+    takes (384, 384).  `get_batch_depth(videos, target_size)` then wraps the estimator in the reference's two bicubic resizes
+    (ddpm3d.py:1443-1468), on the GPU.  None: the estimator is called on the frames as they are and must answer at target_size."""
 
-    def __init__(self, depth_stage_config=None, adapter_config=None, *args, **kwargs):
+    def __init__(self, depth_stage_config=None, adapter_config=None, *args, depth_resize=None, **kwargs):
         init_weights = kwargs.get("init_weights", True)
         super().__init__(*args, **kwargs)
+        self.depth_resize = None if depth_resize is None else tuple(int(v) for v in depth_resize)
         if isinstance(adapter_config, Adapter):
             self.adapter, self.condtype = adapter_config, "depth"
         else:
@@ -900,18 +968,27 @@ class T2VAdapterDepth(LatentDiffusion):
             self.condtype = cfg.get("cond_name", "depth")
         self.depth_stage_model = depth_stage_config
 
+    def prepare_midas_input(self, batch_x):
+        """ddpm3d.py:1443-1447: frames [n, 3, H, W] -> fp32 [n, 3, 384, 384], MiDaS' input size, by the bicubic launch."""
+        return bicubic_resize(batch_x, (384, 384))
+
     @torch.no_grad()
     def get_batch_depth(self, batch_x=None, target_size=None, encode_bs=1, depth=None):
         """videos batch_x [b, 3, t, h, w] -> min-max normalised depth [b, 1, t, H, W] in [-1, 1] (ddpm3d.py:1449-1469).
-        `depth_stage_model` is called on all (b t) frames at once and must return [b t, 1, H, W] at `target_size` already: the two
-        bicubic resizes the reference wraps around MiDaS (to 384 x 384 and back) are not part of this package.  Alternatively pass
+        `depth_stage_model` is called ONCE on all (b t) frames.  With `self.depth_resize = (h, w)` (the reference: (384, 384)) the call
+        is the reference's: the frames are resized to h x w (`prepare_midas_input`, one bicubic launch), the estimator may answer
+        [b t, 1, H', W'] at any size, and its answer is resized to `target_size` (multiples of 8) and normalised by ONE program (a
+        bicubic pass into the arena + the front-end kernel; no resize when the answer already has target_size) — bit for bit
+        `adapter.normalise_depth(bicubic_resize(d, target_size))`.  With `depth_resize = None` (the default) the estimator is called on
+        the frames as they are and must return [b t, 1, H, W] at `target_size` already.  Alternatively pass
         the depth itself, `get_batch_depth(depth=d)` with d [b, 1, t, H, W]: only the normalisation runs (the front-end kernel)."""
+        resize = getattr(self, "depth_resize", None) if depth is None else None
         if depth is None:
             if self.depth_stage_model is None:
                 raise RuntimeError("no depth_stage_model attached: pass depth=[b, 1, t, H, W] instead")
             b, _, t, _, _ = batch_x.shape
             merged = batch_x.permute(0, 2, 1, 3, 4).reshape(b * t, batch_x.shape[1], batch_x.shape[3], batch_x.shape[4])
-            d = self.depth_stage_model(merged)
+            d = self.depth_stage_model(merged if resize is None else bicubic_resize(merged, resize))
         else:
             if depth.dim() != 5 or depth.shape[1] != 1:
                 raise ValueError(f"depth must be [b, 1, t, H, W], got {tuple(depth.shape)}")
@@ -919,9 +996,16 @@ class T2VAdapterDepth(LatentDiffusion):
             d = depth.permute(0, 2, 1, 3, 4).reshape(b * t, 1, depth.shape[3], depth.shape[4])
         if d.dim() != 4 or d.shape[0] != b * t or d.shape[1] != 1:
             raise ValueError(f"the depth model must return [{b * t}, 1, H, W], got {tuple(d.shape)}")
+        if resize is not None:
+            H, W = (int(v) for v in (target_size if target_size is not None else d.shape[2:]))
+            if H % 8 or W % 8 or min(H, W) < 8:
+                raise ValueError(f"target_size {(H, W)}: the adapter's PixelUnshuffle(8) front end needs multiples of 8")
+            out = self.adapter.normalise_depth(d, size=(H, W))
+            return out.reshape(b, t, 1, H, W).permute(0, 2, 1, 3, 4).contiguous()
         if target_size is not None and tuple(d.shape[2:]) != tuple(target_size):
-            raise ValueError(f"depth maps of {tuple(d.shape[2:])} for target_size {tuple(target_size)}: the bicubic resizes around the depth "
-                             "model are not part of this package — depth must arrive at target_size")
+            raise ValueError(f"depth maps of {tuple(d.shape[2:])} for target_size {tuple(target_size)}: with depth_resize = None nothing is "
+                             "resized — depth must arrive at target_size (set depth_resize = (h, w), the reference: (384, 384), for the bicubic "
+                             "resizes around the depth model)")
         out = self.adapter.normalise_depth(d)
         return out.reshape(b, t, 1, d.shape[2], d.shape[3]).permute(0, 2, 1, 3, 4).contiguous()
 
