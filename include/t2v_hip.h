@@ -31,6 +31,8 @@ extern "C" {
                                (ReLU), GEMM i[30] (residual row wrap for every gather mode, split-K allowed), T2V_EXT_ADAPTER (feature slots);
                                still 11: DDIM_STEP i[7] / p[4..6] / f[6..7] (mask blend of a VideoCrafter step) — additive on fields that every earlier
                                record leaves zero, so the version does not move;
+                               still 11: DDIM_STEP i[8] / i[9] / p[7..8] / f[6..7] in mode 0 (clamp / percentile restriction of x0 with its measure pass, and the
+                               classifier-guidance term of DDIM_Gaussian) — additive on fields that every earlier record leaves zero;
                                still 11: T2V_OP_EMPHASIS (a new kind: no existing record changes, and a library without it refuses the record as an unknown op kind) and
                                ATTENTION i[19..21] / p[4..5] (a second role; additive on fields every earlier record leaves zero);
                                still 11: T2V_OP_FINGERPRINT (a new kind, stand-alone: 64-bit fingerprints of a table of byte ranges; no existing record changes);
@@ -292,6 +294,22 @@ enum t2v_gather {
  *        f: 6 sqrt_alphas_cumprod[t'], 7 sqrt_one_minus_alphas_cumprod[t'] (t' = step - 1: q_sample of the known content)
  *        p: 4 known x0, 5 mask, 6 q-noise (may be null when f7 == 0) — fp32, dense, shaped like x [samples, channels, inner]
  *        i[7] = 0: p[4..6] and f[6..7] are not read
+ *      i[8] (mode 0, fp32 x, i[7] = 0): restriction of x0 before the update continues from it (restrict_range_x0, gaussian_sampler.py:110-120);
+ *        all of it in fp32 with every operation rounded by itself, as the reference's tensor arithmetic
+ *          0  none — p[7..8] and f[6..7] are not read (unless i[9] = 1), the record is the plain step
+ *          1  x0 = clamp(x0, -f6, f6)                      (a NaN stays a NaN, as torch.clamp)
+ *          2  x0 = min(s, max(-s, x0)) / s,  s = table[sample][0] read from p[7]   (NaN in s or x0 -> NaN, as torch.min / torch.max)
+ *          3  the MEASURE pass: writes table[sample] = {max(q, 1), q, v_lo, v_hi} (four fp32) into p[7] for every sample and nothing else
+ *             (p[3] may be null, p[2] is not read).  Over the n = channels * inner values |x0| of a sample (x0 recomputed from x and the eps
+ *             pair exactly as the apply pass computes it; -0.0 counts as 0, +-inf are ordinary values): rank = f6 * (float)(n - 1) in fp32,
+ *             v_lo / v_hi = the order statistics floor(rank) / ceil(rank), w = rank - floor(rank),
+ *             q = w < 0.5 ? v_lo + w (v_hi - v_lo) : v_hi - (v_hi - v_lo)(1 - w)  — torch.quantile(|x0|, f6) on fp32, by an exact integer radix
+ *             select (no floating-point accumulation: the result does not depend on scheduling); a NaN in the sample gives q = s = NaN.
+ *             n <= 16 777 216 (torch.quantile's limit), f6 = float32(percentile) in (0, 1]
+ *        f: 6 clamp bound (i[8] = 1) or percentile (i[8] = 3);  p: 7 threshold table fp32 [samples, 4] (i[8] = 2 reads, 3 writes)
+ *      i[9] = 1 (mode 0, fp32 x, i[7] = 0): the classifier-guidance term of get_eps (gaussian_sampler.py:199-211), after the restriction and
+ *        eps = (f0 x - x0) / f1:   eps -= f7 * g;   x0 = f0 x - f1 eps;   then the update as above
+ *        f: 7 sqrt(1 - a_t);  p: 8 g = condition_fn(x_t, t), fp32, dense, shaped like x
  * LINCOMB: i: 0 n elements, 1 n terms (<= 6), 2 out dtype, 3..8 term dtypes; f: 0..5 coefficients;
  *      p: 0..5 terms, 6 out
  * MEMSET: i: 0 bytes (lo), 1 bytes (hi); p: 0 dst

@@ -9,6 +9,9 @@
 //   ddim_step     DDIM_Gaussian update incl. half-channel classifier-free guidance
 //                 (samplers/ddim/gaussian_sampler.py:125-136, 103-108, 199-211, 269-283); a compile-time variant adds the
 //                 known-region blend of a masked LVDM step (lvdm/samplers/ddim.py:188-195) to the same launch
+//   ddim_restrict / ddim_measure   the DDIM_Gaussian step with its x0 clamped or thresholded by a per-video quantile of |x0|
+//                 (restrict_range_x0, gaussian_sampler.py:110-120) and / or the classifier-guidance term (get_eps, :199-211); the measure
+//                 pass is torch.quantile on fp32, exactly, by a radix select in one workgroup per video
 //   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
 //                 (process_modelscope.py:116-120, 174-178); the last pass can write the VAE encoder's tokens
 //   bicubic       torch's F.interpolate(mode="bicubic", align_corners=False) of planar float images, both axes in one launch: the resizes
@@ -174,6 +177,199 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const DdimParams p, cons
       xn = known * m + (1.f - m) * xn;
     }
     out[idx] = (TX)xn;
+  }
+}
+
+// ---- mode 0 with a restriction of x0 (i[8]) and / or the classifier-guidance term (i[9]): gaussian_sampler.py:110-120, 199-211 ----------
+// Kernels of their own, so that the plain step above stays the code it was.  Everything below rounds every operation separately
+// (no contraction), like the reference's tensor arithmetic: the x0 that the measure pass ranks IS the x0 that the apply pass thresholds.
+struct DdimRestrict {
+  const float* table;   // i[8] = 2: [samples, 4] fp32, s in column 0 (p[7])
+  const float* grad;    // i[9] = 1: condition_fn's result, fp32, dense like x (p[8])
+  float bound;          // i[8] = 1: clamp bound (f[6])
+  float sqrt_1mat;      // i[9] = 1: sqrt(1 - a_t) (f[7])
+};
+
+// x0 of a mode-0 step from x_t and the eps pair, guidance combine included (guided: element idx lies in one of the sample's first
+// i[2] channels); *ax_out = f0 * x
+template <typename TE>
+__device__ __forceinline__ float ddim_x0_of(const DdimParams& p, const float* xt, const TE* ec, const TE* eu, long idx, bool guided, float* ax_out) {
+#pragma clang fp contract(off)
+  const float x = xt[idx];
+  const float y = (float)ec[idx];
+  float o = y;
+  if (guided) {
+    const float u = (float)eu[idx];
+    const float d = p.gscale * (y - u);
+    o = u + d;
+  }
+  const float ax = p.a_recip * x;
+  const float bo = p.a_recipm1 * o;
+  *ax_out = ax;
+  return ax - bo;
+}
+
+// torch.min / torch.max: a NaN in either operand is the result
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
+__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+
+// RESTRICT: 0 none, 1 clamp to [-bound, bound], 2 dynamic threshold by table[sample][0]; COND: the classifier-guidance term
+template <typename TE, int RESTRICT, bool COND>
+__global__ __launch_bounds__(256) void ddim_restrict_kernel(const DdimParams p, const DdimRestrict r) {
+#pragma clang fp contract(off)
+  const float* xt = reinterpret_cast<const float*>(p.xt);
+  const TE* ec = reinterpret_cast<const TE*>(p.eps);
+  const TE* eu = ec + (size_t)p.C * p.inner;
+  float* out = reinterpret_cast<float*>(p.out);
+  const long total = (long)p.C * p.inner;
+  const long per_sample = (long)p.cps * p.inner, guided_n = (long)p.guided * p.inner;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const long smp = idx / per_sample;
+    float ax;
+    float x0 = ddim_x0_of<TE>(p, xt, ec, eu, idx, idx - smp * per_sample < guided_n, &ax);
+    if constexpr (RESTRICT == 1) {
+      x0 = nan_min(nan_max(x0, -r.bound), r.bound);                    // torch.clamp: a NaN stays a NaN
+    } else if constexpr (RESTRICT == 2) {
+      const float s = r.table[smp * 4];
+      x0 = nan_min(s, nan_max(-s, x0)) / s;
+    }
+    float eps = (ax - x0) / p.a_recipm1;
+    if constexpr (COND) {
+      const float g = r.sqrt_1mat * r.grad[idx];
+      eps = eps - g;
+      const float be = p.a_recipm1 * eps;
+      x0 = ax - be;
+    }
+    const float m0 = p.sqrt_aprev * x0, m1 = p.dir_coef * eps;
+    float xn = m0 + m1;
+    if (p.noise != nullptr && p.sigma != 0.f) {
+      const float m2 = p.sigma * p.noise[idx];
+      xn = xn + m2;
+    }
+    out[idx] = xn;
+  }
+}
+
+// i[8] = 3, the measure pass: per sample the order statistics lo and hi of |x0| by an exact radix select over the keys' bit patterns
+// (|x0| as an unsigned integer orders like the float; a NaN is any key above +inf's), then torch.quantile's interpolation of the two.
+// One workgroup of 1024 threads per sample.  Integer counting only: per-wave LDS histograms, summed in a fixed order.
+constexpr int QT_THREADS = 1024, QT_WAVES = QT_THREADS / 64, QT_UNROLL = 8;     // keys per thread and trip: their loads are in flight together
+struct DdimMeasure {
+  float* table;         // [samples, 4]: max(q, 1), q, v_lo, v_hi
+  unsigned lo, hi;      // floor / ceil of the fp32 rank f[6] * (float)(n - 1)
+  float w;              // rank - lo
+};
+
+template <typename TE>
+__global__ __launch_bounds__(QT_THREADS) void ddim_measure_kernel(const DdimParams p, const DdimMeasure m) {
+  __shared__ unsigned hist[QT_WAVES][256];
+  __shared__ unsigned total[256];
+  __shared__ unsigned sel[4];           // 0 digit, 1 rank inside the digit's bin, 2 count of the bin, 3 smallest key above key_lo
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned n = (unsigned)p.cps * (unsigned)p.inner;              // <= 2^24 (validated)
+  const long base = (long)blockIdx.x * n;
+  const float* xt = reinterpret_cast<const float*>(p.xt);
+  const TE* ec = reinterpret_cast<const TE*>(p.eps);
+  const TE* eu = ec + (size_t)p.C * p.inner;
+  const unsigned guided_n = (unsigned)p.guided * (unsigned)p.inner;
+  auto key_at = [&](unsigned i) -> unsigned {
+    float ax;
+    return __float_as_uint(ddim_x0_of<TE>(p, xt, ec, eu, base + i, i < guided_n, &ax)) & 0x7fffffffu;     // |x0|: -0.0 is 0
+  };
+
+  unsigned prefix = 0, k = m.lo, n_eq = 0;
+  bool any_nan = false;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    const unsigned himask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+    for (int b = tid; b < QT_WAVES * 256; b += QT_THREADS) (&hist[0][0])[b] = 0;
+    __syncthreads();
+    for (unsigned i0 = 0; i0 < n; i0 += QT_THREADS * QT_UNROLL) {     // every lane of a wave makes every trip (ballots below)
+      unsigned keys[QT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < QT_UNROLL; ++u) {                            // the loads of one trip are in flight together
+        const unsigned i = i0 + u * QT_THREADS + tid;
+        keys[u] = i < n ? key_at(i) : 0xffffffffu;                     // (no key is all ones: the sign bit is cleared)
+      }
+#pragma unroll
+      for (int u = 0; u < QT_UNROLL; ++u) {
+        const unsigned key = keys[u];
+        const bool valid = key != 0xffffffffu;
+        if (pass == 0) any_nan |= valid && key > 0x7f800000u;
+        bool pending = valid && (key & himask) == prefix;
+        const unsigned digit = (key >> shift) & 255u;
+        // keys crowd into a few bins (one exponent, a run of ties): the first two distinct digits of a wave are counted by ballot,
+        // one add each; what is left goes bin by bin
+        for (int round = 0; round < 2; ++round) {
+          const unsigned long long live = __ballot(pending);
+          if (live == 0) break;
+          const int leader = __ffsll((long long)live) - 1;                       // wave-uniform: the lane is read without a trip through LDS
+          const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)digit, __builtin_amdgcn_readfirstlane(leader));
+          const unsigned long long same = __ballot(pending && digit == d0);
+          if (lane == leader) atomicAdd(&hist[wave][d0], (unsigned)__popcll(same));
+          pending = pending && digit != d0;
+        }
+        if (pending) atomicAdd(&hist[wave][digit], 1u);
+      }
+    }
+    __syncthreads();
+    if (tid < 256) {
+      unsigned t = 0;
+      for (int wv = 0; wv < QT_WAVES; ++wv) t += hist[wv][tid];
+      total[tid] = t;
+    }
+    __syncthreads();
+    if (tid < 256) {                                                   // the bin that holds rank k: below[tid] <= k < below[tid] + total[tid]
+      unsigned below = 0;
+      for (int j = 0; j < tid; ++j) below += total[j];
+      const unsigned mine = total[tid];
+      if (k >= below && k - below < mine) { sel[0] = (unsigned)tid; sel[1] = k - below; sel[2] = mine; }
+    }
+    __syncthreads();
+    prefix |= sel[0] << shift;
+    k = sel[1];
+    n_eq = sel[2];
+    __syncthreads();
+  }
+  // prefix = the key of rank lo; n_eq keys equal it, and lo is the k-th of them (0-based)
+  const unsigned key_lo = prefix;
+  unsigned key_hi = key_lo;
+  const bool need_above = m.hi > m.lo && k + 1 >= n_eq;                // rank hi = lo + 1 lies past the ties at key_lo
+  if (tid == 0) sel[3] = 0xffffffffu;
+  __syncthreads();
+  if (need_above) {                                                    // uniform over the workgroup
+    unsigned best = 0xffffffffu;
+    for (unsigned i0 = 0; i0 < n; i0 += QT_THREADS * QT_UNROLL) {
+      unsigned keys[QT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < QT_UNROLL; ++u) {
+        const unsigned i = i0 + u * QT_THREADS + tid;
+        keys[u] = i < n ? key_at(i) : 0xffffffffu;
+      }
+#pragma unroll
+      for (int u = 0; u < QT_UNROLL; ++u)
+        if (keys[u] > key_lo && keys[u] < best) best = keys[u];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned o = (unsigned)__shfl_xor((int)best, off);
+      best = o < best ? o : best;
+    }
+    if (lane == 0) atomicMin(&sel[3], best);
+  }
+  __syncthreads();
+  if (need_above) key_hi = sel[3];
+  const int nan_seen = __syncthreads_or(any_nan ? 1 : 0);
+  if (tid == 0) {
+    const float a = __uint_as_float(key_lo), b = __uint_as_float(key_hi);
+    // torch.lerp: w < 0.5 ? a + w (b - a) : b - (b - a)(1 - w), the product and the sum in one rounding as torch's CPU kernel has them
+    const float d = b - a;
+    float q = m.w < 0.5f ? __fmaf_rn(m.w, d, a) : __fmaf_rn(m.w - 1.f, d, b);
+    if (nan_seen) q = __uint_as_float(0x7fc00000u);                    // a NaN anywhere in the sample: torch.quantile gives NaN
+    float* row = m.table + (size_t)blockIdx.x * 4;
+    row[0] = q != q ? q : fmaxf(q, 1.f);                               // s.clamp_(1.0)
+    row[1] = q;
+    row[2] = a;
+    row[3] = b;
   }
 }
 
@@ -1081,7 +1277,40 @@ hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s) {
   p.a_recip = op.f[0]; p.a_recipm1 = op.f[1]; p.sqrt_aprev = op.f[2]; p.dir_coef = op.f[3]; p.sigma = op.f[4];
   p.gscale = op.f[5];
   const int g = grid_for((long)p.C * p.inner);
-  if (op.i[7] != 0) {                          // masked step: the blend is a compile-time variant (fp32 x only; the executor checked)
+  if (op.i[8] != 0 || op.i[9] != 0) {          // restricted x0 / classifier guidance: mode 0, fp32 x, no blend (the executor checked)
+    if (!p.x_f32 || p.mode != 0 || op.i[7] != 0) return hipErrorInvalidValue;
+    if (op.i[8] == 3) {                        // the measure pass: one workgroup per sample, writes table[sample][0..3] only
+      const long n = (long)p.cps * p.inner;
+      if (n > (1L << 24) || !(op.f[6] > 0.f && op.f[6] <= 1.f) || op.p[7] == 0) return hipErrorInvalidValue;
+      DdimMeasure m;
+      m.table = reinterpret_cast<float*>(op.p[7]);
+      volatile float rank = op.f[6] * (float)(n - 1);     // torch.quantile's fp32 rank (one rounded product)
+      const float below = floorf(rank);
+      m.lo = (unsigned)below; m.hi = (unsigned)ceilf(rank); m.w = rank - below;
+      const int samples = p.C / p.cps;
+      if (p.eps_f32) hipLaunchKernelGGL((ddim_measure_kernel<float>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
+      else hipLaunchKernelGGL((ddim_measure_kernel<f16>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
+      return hipGetLastError();
+    }
+    DdimRestrict r;
+    r.table = reinterpret_cast<const float*>(op.p[7]);
+    r.grad = reinterpret_cast<const float*>(op.p[8]);
+    r.bound = op.f[6]; r.sqrt_1mat = op.f[7];
+    const int sel = op.i[8] * 2 + (op.i[9] != 0 ? 1 : 0);
+#define T2V_DDIM_RESTRICT(TE)                                                                                          \
+    switch (sel) {                                                                                                     \
+      case 1: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 0, true>), dim3(g), dim3(256), 0, s, p, r); break;          \
+      case 2: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 1, false>), dim3(g), dim3(256), 0, s, p, r); break;         \
+      case 3: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 1, true>), dim3(g), dim3(256), 0, s, p, r); break;          \
+      case 4: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 2, false>), dim3(g), dim3(256), 0, s, p, r); break;         \
+      case 5: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 2, true>), dim3(g), dim3(256), 0, s, p, r); break;          \
+      default: return hipErrorInvalidValue;                                                                            \
+    }
+    if (p.eps_f32) { T2V_DDIM_RESTRICT(float) } else { T2V_DDIM_RESTRICT(f16) }
+#undef T2V_DDIM_RESTRICT
+    return hipGetLastError();
+  }
+  if (op.i[7] != 0) {                        // masked step: the blend is a compile-time variant (fp32 x only; the executor checked)
     if (!p.x_f32) return hipErrorInvalidValue;
     DdimBlend b;
     b.x0 = reinterpret_cast<const float*>(op.p[4]);

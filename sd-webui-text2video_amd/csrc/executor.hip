@@ -229,8 +229,22 @@ int validate_op(const t2v_op& op, int idx) {
       const int C = op.i[0], cps = op.i[6] > 0 ? op.i[6] : C;
       if (C <= 0 || op.i[1] <= 0 || cps <= 0 || C % cps != 0) return bad("DDIM step needs C > 0, inner > 0, C % channels-per-sample == 0");
       if (op.i[2] < 0 || op.i[2] > cps || (op.i[5] != 0 && op.i[5] != 1)) return bad("DDIM step: guided channels / mode");
-      if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return bad("null DDIM step pointer");
+      if (op.i[8] < 0 || op.i[8] > 3) return bad("DDIM step: x0 restriction i[8] must be 0 (none), 1 (clamp), 2 (threshold) or 3 (measure pass)");
+      if (op.i[9] != 0 && op.i[9] != 1) return bad("DDIM step: classifier-guidance flag i[9] must be 0 or 1");
+      if (op.p[0] == 0 || op.p[1] == 0 || (op.p[3] == 0 && op.i[8] != 3)) return bad("null DDIM step pointer");
       if (op.i[7] != 0 && op.i[7] != 1) return bad("DDIM step: blend flag i[7] must be 0 or 1");
+      if (op.i[8] != 0 || op.i[9] != 0) {
+        if (op.i[5] != 0) return bad("DDIM step: the x0 restriction i[8] and the classifier-guidance term i[9] exist for mode 0 (DDIM_Gaussian) only");
+        if (op.i[7] != 0) return bad("DDIM step: the x0 restriction i[8] / classifier-guidance term i[9] and the mask blend i[7] exclude each other");
+        if (op.i[4] != T2V_F32) return bad("DDIM step: the x0 restriction i[8] and the classifier-guidance term i[9] need an fp32 x");
+        if ((op.i[8] == 2 || op.i[8] == 3) && op.p[7] == 0) return bad("DDIM step: the x0 threshold i[8] = 2 | 3 needs the threshold table p[7]");
+        if (op.i[9] == 1 && op.p[8] == 0) return bad("DDIM step: the classifier-guidance term i[9] needs the gradient p[8]");
+        if (op.i[8] == 1 && !(op.f[6] >= 0.f)) return bad("DDIM step: the x0 clamp i[8] = 1 needs a bound f[6] >= 0");
+        if (op.i[8] == 3) {
+          if ((int64_t)cps * op.i[1] > (int64_t)16777216) return bad("DDIM step: the measure pass i[8] = 3 ranks at most 16 777 216 elements per sample (torch.quantile's limit)");
+          if (!(op.f[6] > 0.f && op.f[6] <= 1.f)) return bad("DDIM step: the measure pass i[8] = 3 needs a percentile f[6] in (0, 1]");
+        }
+      }
       if (op.i[7] == 1) {
         if (op.i[5] != 1) return bad("DDIM step: the mask blend i[7] exists for mode 1 (LDM DDIM) only");
         if (op.i[4] != T2V_F32) return bad("DDIM step: the mask blend i[7] needs an fp32 x");
@@ -486,6 +500,7 @@ int ff_min_m() {
 // a resharding, the K / V^T operands that share numbers with the fused GroupNorm's output) is an input.
 unsigned output_slots(const t2v_op& op) {
   auto bits = [](std::initializer_list<int> l) { unsigned m = 0; for (int k : l) m |= 1u << k; return m; };
+  if (op.kind == T2V_OP_DDIM_STEP && op.i[8] == 3) return bits({7});      // the measure pass writes the threshold table and nothing else
   switch (op.kind) {
     case T2V_OP_GEMM: return bits({5, 6, 7, 10, 11}) | (op.i[16] == T2V_EPI_GN ? bits({9}) : 0u);
     case T2V_OP_GROUPNORM: return bits({3, 4, 5, 7, 8});

@@ -157,8 +157,11 @@ class TextToVideoSynthesis(object):
     def infer_conditioned(self, c, uc, steps, frames, seed, scale, width=256, height=256, eta=0.0,
                           device=None, latents=None, strength=None, mask=None, is_vid2vid=False,
                           sampler=available_samplers[0].name, decode=True, to_host=True, _keep_sampler=False,
-                          videos: int = 1):
+                          videos: int = 1, *, clamp=None, percentile=None):
         """Stages 2-4 of `infer` for given conditioning tensors c, uc [1, 77k, 1024].
+        `clamp` / `percentile` (DDIM_Gaussian only; another sampler raises ValueError): the restriction of the predicted x0 of
+        `GaussianDiffusion.sample` — percentile=0.995 is dynamic thresholding per video, clamp=<anything> clamps x0 to [-1, 1] (the
+        reference's `clamp=True` quirk, gaussian_sampler.py:178); forwarded only when set.
         Returns (frames, last_tensor): frames = list of HxWx3 uint8 BGR arrays (to_host) or a
         uint8 device tensor [F,H,W,3] RGB (to_host=False), or None when decode=False.
         `videos` > 1 (DDIM_Gaussian, txt2vid): that many independent videos of the same prompt in ONE batch — every
@@ -185,7 +188,7 @@ class TextToVideoSynthesis(object):
         x0 = self.diffusion.sample_loop(
             steps=steps, strength=strength, eta=eta, conditioning=c.to(dev), unconditional_conditioning=uc.to(dev),
             batch_size=videos, guidance_scale=scale, latents=latents, shape=shape, noise=noise, is_vid2vid=is_vid2vid,
-            sampler_name=sampler, mask=mask)
+            sampler_name=sampler, mask=mask, **_restriction(clamp, percentile))
         self.last_tensor = x0
         if not decode:
             return None, x0
@@ -270,7 +273,7 @@ class TextToVideoSynthesis(object):
 
     def infer(self, prompt, n_prompt, steps, frames, seed, scale, width=256, height=256, eta=0.0,
               cpu_vae="GPU (half precision)", device=torch.device("cuda"), latents=None, skip_steps=0,
-              strength=0, mask=None, is_vid2vid=False, sampler=available_samplers[0].name):
+              strength=0, mask=None, is_vid2vid=False, sampler=available_samplers[0].name, *, clamp=None, percentile=None):
         vars_ = dict(prompt=prompt, n_prompt=n_prompt, steps=steps, frames=frames, seed=seed, scale=scale,
                      width=width, height=height, eta=eta, cpu_vae=cpu_vae, device=str(device),
                      skip_steps=skip_steps, strength=strength, is_vid2vid=is_vid2vid, sampler=sampler)
@@ -283,8 +286,13 @@ class TextToVideoSynthesis(object):
         c, uc = self.preprocess(prompt, n_prompt, steps)
         strength = None if (strength == 0.0 and not is_vid2vid) else strength
         frames_bgr, x0 = self.infer_conditioned(c, uc, steps, frames, seed, scale, width, height, eta, device,
-                                                latents, strength, mask, is_vid2vid, sampler)
+                                                latents, strength, mask, is_vid2vid, sampler, **_restriction(clamp, percentile))
         return frames_bgr, self.last_tensor, create_infotext(vars_)
+
+
+def _restriction(clamp, percentile) -> dict:
+    """The x0-restriction keywords that are set — nothing is forwarded when neither is, so a call without them is what it was."""
+    return {k: v for k, v in (("clamp", clamp), ("percentile", percentile)) if v is not None}
 
 
 _CPU_VAE_NOTED = False
@@ -323,6 +331,7 @@ def process_modelscope(args_dict: dict, extra_args=None):
     URL per video, made from the mp4 that ffmpeg stitched (:248-266).  Here:
       args_dict = {model_dir | pipe, prompt, n_prompt, steps, frames, seed, cfg_scale, width, height, eta, sampler,
                    batch_count, clip_encoder | (cond, uncond), stitch,
+                   clamp, percentile,                                         # x0 restriction of DDIM_Gaussian (gaussian_sampler.py:110-120), below
                    enable_emphasis, comma_padding_backtrack,                  # webui's opts of the prompt syntax (clip_hardcode.py:153,203)
                    do_vid2vid, vid2vid_frames, strength,                      # :80-147
                    inpainting_frames, inpainting_image, inpainting_weights,   # :170-217
@@ -331,6 +340,9 @@ def process_modelscope(args_dict: dict, extra_args=None):
       or the same eight values as an eight-element `extra_args` in that order (the reference's): `stable_lora.StableLoraScript.process`
       runs on the pipe before sampling — the selected files are merged into `pipe.sd_model` and the text encoder's transformer, or taken
       out again when the selection, the weight or an option changed since the last call.  With neither present nothing changes.
+    * `percentile` (e.g. 0.995: dynamic thresholding, s = max(quantile(|x0|, p), 1) per video) / `clamp` (any value: x0 clamped to [-1, 1],
+      the reference's `clamp=True` quirk) go to `GaussianDiffusion.sample` through `infer` / `infer_conditioned`; DDIM_Gaussian only, and
+      with neither key present the call is what it was.
     * `stitch(frames_bgr, infotext) -> bytes` (the ffmpeg stage, out of scope — e.g. the reference's own
       `ffmpeg_stitch_video` behind a temp directory) given: returns the reference's list of data-URLs, video b from
       seed + b (seed -1 stays random), exactly the reference loop;
@@ -366,7 +378,8 @@ def process_modelscope(args_dict: dict, extra_args=None):
         stable_lora.run_for_pipe(pipe, lora_settings)
     width, height = getattr(a, "width", 256), getattr(a, "height", 256)
     common = dict(frames=a.frames, scale=a.cfg_scale, width=width, height=height, eta=getattr(a, "eta", 0.0),
-                  sampler=getattr(a, "sampler", available_samplers[0].name))
+                  sampler=getattr(a, "sampler", available_samplers[0].name),
+                  **_restriction(getattr(a, "clamp", None), getattr(a, "percentile", None)))
     batch_count = int(getattr(a, "batch_count", 1))
     stitch = getattr(a, "stitch", None)
     cpu_vae = getattr(a, "cpu_vae", "GPU (half precision)")

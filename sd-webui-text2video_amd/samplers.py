@@ -134,6 +134,7 @@ class GaussianDiffusion(object):
         self._step_plans = {}
         self.cfg_parallel = None      # parallel.CfgPair: cond / uncond forwards on two GPUs (parallel.py)
         self.shared_noise = None      # SharedNoise: per-step eta noise of a clip that is split over ranks
+        self.last_thresholds = None   # percentile runs: the thresholds of the last `sample` call (see there)
 
     # -- schedule helpers (gaussian_sampler.py:73-91) --------------------------------------------
     def get_time_steps(self, ddim_timesteps, batch_size=1, step=None):
@@ -171,9 +172,26 @@ class GaussianDiffusion(object):
     def sample(self, x_T=None, S=5, shape=None, conditioning=None, unconditional_conditioning=None,
                model_kwargs={}, clamp=None, percentile=None, condition_fn=None,
                unconditional_guidance_scale=None, eta=0.0, callback=None, mask=None, **kwargs):
-        """gaussian_sampler.py:214-296.  Returns x_0-ish latent after S DDIM steps."""
-        if clamp is not None or percentile is not None or condition_fn is not None or model_kwargs:
-            raise NotImplementedError("clamp / percentile / classifier guidance are not used by the pipeline")
+        """gaussian_sampler.py:214-296.  Returns x_0-ish latent after S DDIM steps.
+
+        Restriction of the predicted x0 (restrict_range_x0, gaussian_sampler.py:110-120, 174-178), the reference's answer to x0 blowing
+        up at high guidance scales; the update continues from the restricted x0 (eps is recomputed from it, :199-202):
+          percentile=p   dynamic thresholding: s = max(torch.quantile(|x0|, p), 1) per video, x0 = clip(x0, -s, s) / s; p in (0, 1].
+                         Two records in one launch call per step — a measure pass (exact radix select, torch.quantile's fp32 rank
+                         arithmetic) that leaves s on the device, and the update that reads it; the host never reads s inside the loop.
+                         After the call `self.last_thresholds` is the [S, videos, 4] device tensor {s, q, v_lo, v_hi} of every step.
+          clamp=c        x0 = clip(x0, -1, 1) WHATEVER the value of c: the reference calls restrict_range_x0(percentile, x0, clamp=True)
+                         (gaussian_sampler.py:178), so clamp=0.3 and clamp=5.0 give the same latent.  Mirrored, not repaired.
+          both given     percentile wins (:175-178).
+        condition_fn(xt, t) -> gradient shaped like xt: classifier guidance (get_eps, :199-211), eps -= sqrt(1 - a_t) * condition_fn(xt, t),
+        x0 recomputed from that eps; called once per step with t as the long tensor [videos] the reference passes.
+        Several videos per batch (this build's extension; the reference's quantile cannot run there): each video has its own s, so the
+        batch equals the single-video runs.  A clip whose frames are split over ranks is refused: the quantile spans all frames."""
+        if model_kwargs:
+            raise NotImplementedError("model_kwargs (conditioning passed as a pair, gaussian_sampler.py:156-159) is not used by the pipeline")
+        if percentile is not None and not (0 < float(percentile) <= 1):
+            raise ValueError(f"percentile must lie in (0, 1] (gaussian_sampler.py:112), got {percentile!r}")
+        restricted = clamp is not None or percentile is not None or condition_fn is not None
         lib = L.load()
         model = self.model
         dev = torch.device(model.device)
@@ -192,6 +210,15 @@ class GaussianDiffusion(object):
         Bx, C, Fr, Hh, Ww = xt.shape
         inner = Fr * Hh * Ww
         x_dt = "f16" if xt.dtype == torch.float16 else "f32"
+        thresholds = None
+        if restricted:
+            if getattr(model, "t_shard", None) is not None or (self.shared_noise is not None and self.shared_noise.total != Fr):
+                raise L.T2VError("clamp / percentile / condition_fn with a clip whose frames are split over ranks: the restriction of x0 "
+                                 "(a quantile over all frames of a video) needs the whole clip on one device")
+            if x_dt != "f32":
+                raise L.T2VError("clamp / percentile / condition_fn need an fp32 latent x_T")
+            if percentile is not None:
+                thresholds = torch.zeros((steps, Bx, 4), dtype=torch.float32, device=dev)    # one row per step, written by the measure pass
 
         ac = self.alphas_cumprod
         f32 = torch.float32
@@ -254,10 +281,21 @@ class GaussianDiffusion(object):
                     float(sigma) if t != 0 else 0.0, gscale)
                 noise = _step_noise(self, xt, float(sigma) if t != 0 else 0.0)     # drawn every step, like the reference (global RNG)
                 _ = torch.randn_like(xt, dtype=f32)         # the (inert) inpaint hook's draw, gaussian_sampler.py:288
-                plan = self._step_plan(C, inner, guided, "f16" if eps.dtype == torch.float16 else "f32", x_dt, samples=Bx)
-                L.check(lib.t2v_ddim_step(plan.handle, xt.data_ptr(), eps.data_ptr(),
-                                          noise.data_ptr() if float(sigma) != 0.0 else None,
-                                          x_next.data_ptr(), coef, ctypes.c_void_p(stream)))
+                if restricted:
+                    grad = None
+                    if condition_fn is not None:
+                        grad = condition_fn(xt, torch.full((Bx,), t, dtype=torch.long, device=dev))
+                        grad = grad.to(device=dev, dtype=f32).expand(xt.shape).contiguous()
+                    # percentile wins over clamp (gaussian_sampler.py:175-178); clamp clamps to [-1, 1] whatever its value (:178)
+                    _ddim_restricted_step(x_next, xt, eps, noise, coef, guided,
+                                          percentile=percentile, table=None if thresholds is None else thresholds[step],
+                                          bound=1.0 if (percentile is None and clamp is not None) else None,
+                                          grad=grad, sqrt_1mat=float(torch.sqrt(1 - a_t)))
+                else:
+                    plan = self._step_plan(C, inner, guided, "f16" if eps.dtype == torch.float16 else "f32", x_dt, samples=Bx)
+                    L.check(lib.t2v_ddim_step(plan.handle, xt.data_ptr(), eps.data_ptr(),
+                                              noise.data_ptr() if float(sigma) != 0.0 else None,
+                                              x_next.data_ptr(), coef, ctypes.c_void_p(stream)))
                 xt, x_next = x_next, xt
                 if callback is not None:
                     callback(step)
@@ -265,6 +303,7 @@ class GaussianDiffusion(object):
             if prev_auto is not None:
                 model.auto_refresh = prev_auto
             _restore_eps(model, prev_eps)
+        self.last_thresholds = thresholds      # [S, videos, 4] {s, q, v_lo, v_hi} on the device (percentile runs), else None
         return xt
 
 
@@ -308,6 +347,54 @@ def _ddim_update(out, xt, eps_pair, noise, coef, guided: int, mode: int):
     op.p[2] = noise.data_ptr() if (noise is not None and float(coef[4]) != 0.0) else 0
     stream = torch.cuda.current_stream(xt.device).cuda_stream
     L.check(lib.t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(stream)))
+    return out
+
+
+def _ddim_restricted_records(out, xt, eps_pair, noise, coef, guided: int, *, percentile=None, table=None, bound=None, grad=None,
+                             sqrt_1mat: float = 0.0):
+    """-> the T2V_OP_DDIM_STEP records (mode 0) of one DDIM_Gaussian step with a restricted x0 and / or the classifier-guidance term:
+    `percentile` (with `table` [videos, 4] fp32): the measure pass (i[8] = 3) and the update that reads its s (i[8] = 2); `bound`: the
+    clamp (i[8] = 1); `grad`: i[9] = 1 with f[7] = sqrt(1 - a_t).  A ctypes array of one or two records."""
+    B, C = xt.shape[0], xt.shape[1]
+    if grad is not None and not (grad.dtype == torch.float32 and grad.is_contiguous() and grad.shape == xt.shape and grad.device == xt.device):
+        raise L.T2VError("the gradient of a classifier-guided DDIM step must be fp32, contiguous, on the device and shaped like x")
+    if percentile is not None and not (table is not None and table.dtype == torch.float32 and table.is_contiguous()
+                                       and tuple(table.shape) == (B, 4) and table.device == xt.device):
+        raise L.T2VError("the threshold table of a percentile DDIM step must be fp32 [videos, 4], contiguous, on the device")
+
+    def record(restrict):
+        op = L.T2VOp()
+        op.kind = L.OP_DDIM_STEP
+        op.i[0], op.i[1], op.i[2] = B * C, xt.numel() // (B * C), guided
+        op.i[6] = C
+        op.i[3], op.i[4], op.i[5] = _dt_tag(eps_pair), _dt_tag(xt), 0
+        op.i[8] = restrict
+        for k in range(6):
+            op.f[k] = float(coef[k])
+        op.p[0], op.p[1], op.p[3] = xt.data_ptr(), eps_pair.data_ptr(), out.data_ptr()
+        op.p[2] = noise.data_ptr() if (noise is not None and float(coef[4]) != 0.0) else 0
+        if restrict in (2, 3):
+            op.p[7] = table.data_ptr()
+        if restrict == 3:
+            op.f[6] = float(percentile)
+        elif restrict == 1:
+            op.f[6] = float(bound)
+        if grad is not None and restrict != 3:          # (the measure pass ranks x0 before the guidance term)
+            op.i[9], op.f[7], op.p[8] = 1, float(sqrt_1mat), grad.data_ptr()
+        return op
+
+    kinds = [3, 2] if percentile is not None else [1] if bound is not None else [0]
+    ops = (L.T2VOp * len(kinds))()
+    for k, r in enumerate(kinds):
+        ops[k] = record(r)
+    return ops
+
+
+def _ddim_restricted_step(out, xt, eps_pair, noise, coef, guided: int, **kw):
+    """One DDIM_Gaussian step with clamp / percentile / classifier guidance (`_ddim_restricted_records`): ONE t2v_run_ops call."""
+    ops = _ddim_restricted_records(out, xt, eps_pair, noise, coef, guided, **kw)
+    stream = torch.cuda.current_stream(xt.device).cuda_stream
+    L.check(L.load().t2v_run_ops(ops, len(ops), None, 0, ctypes.c_void_p(stream)))
     return out
 
 
@@ -748,12 +835,19 @@ class Txt2VideoSampler(object):
 
     def sample_loop(self, steps, strength, conditioning, unconditional_conditioning, batch_size, latents=None,
                     shape=None, noise=None, is_vid2vid=False, guidance_scale=1, eta=0, mask=None,
-                    sampler_name="DDIM"):
+                    sampler_name="DDIM", *, clamp=None, percentile=None):
+        """samplers_common.py:165-207.  `clamp` / `percentile` (keyword, this build's addition to the signature): the x0 restriction of
+        GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set, so every other call is what it was."""
+        restrict = {k: v for k, v in (("clamp", clamp), ("percentile", percentile)) if v is not None}
+        if restrict and not isinstance(self.sampler, GaussianDiffusion):
+            active = next((s.name for s in available_samplers if isinstance(self.sampler, s.Sampler)), type(self.sampler).__name__)
+            raise ValueError(f"{' / '.join(restrict)}: the x0 restriction exists for the DDIM_Gaussian sampler only, not for {active!r}")
         denoise_steps = None
         if latents is not None and is_vid2vid:
             latents, denoise_steps = self.encode_latent(latents, noise, strength, steps)
         sampler_callback = SamplerStepCallback(sampler_name, steps, progress=self.progress)
         x0 = self.sampler.sample(
+            **restrict,
             S=steps, conditioning=conditioning, strength=strength,
             unconditional_conditioning=unconditional_conditioning, batch_size=batch_size,
             x_T=latents if latents is not None else noise, x_latent=latents, t_start=denoise_steps,
