@@ -33,6 +33,8 @@ extern "C" {
                                record leaves zero, so the version does not move;
                                still 11: DDIM_STEP i[8] / i[9] / p[7..8] / f[6..7] in mode 0 (clamp / percentile restriction of x0 with its measure pass, and the
                                classifier-guidance term of DDIM_Gaussian) — additive on fields that every earlier record leaves zero;
+                               still 11: DDIM_STEP i[5] = 2 (UniPC's thresholded data prediction: a measure and an apply record) — a mode value that every earlier
+                               library refuses, records with i[5] in {0, 1} are validated and run as before;
                                still 11: T2V_OP_EMPHASIS (a new kind: no existing record changes, and a library without it refuses the record as an unknown op kind) and
                                ATTENTION i[19..21] / p[4..5] (a second role; additive on fields every earlier record leaves zero);
                                still 11: T2V_OP_FINGERPRINT (a new kind, stand-alone: 64-bit fingerprints of a table of byte ranges; no existing record changes);
@@ -310,6 +312,13 @@ enum t2v_gather {
  *      i[9] = 1 (mode 0, fp32 x, i[7] = 0): the classifier-guidance term of get_eps (gaussian_sampler.py:199-211), after the restriction and
  *        eps = (f0 x - x0) / f1:   eps -= f7 * g;   x0 = f0 x - f1 eps;   then the update as above
  *        f: 7 sqrt(1 - a_t);  p: 8 g = condition_fn(x_t, t), fp32, dense, shaped like x
+ *      mode 2 (UniPC's thresholded data prediction, uni_pc/uni_pc.py:351-364 with the guidance combine of :304-307; fp32 x, i[7] = i[9] = 0):
+ *          e = eu + f5 * (ec - eu)  (i[2] = channels per sample: guided; 0: e = ec);   x0 = (x - f0 * e) / f1
+ *        in fp32 with every operation rounded by itself.  The record is one of two passes, both over that x0:
+ *          i[8] = 3  the MEASURE pass exactly as in mode 0 (same select, same rank arithmetic, same table row), quantile f6
+ *          i[8] = 2  out = min(max(x0, -s), s) / s,  s = table[sample][0]   (torch.clamp with tensor bounds; NaN in s or x0 -> NaN)
+ *        i[8] = 0 | 1 are refused: the plain data prediction is a LINCOMB, and the class has no clamp.  n = channels * inner <= 16 777 216.
+ *        f: 0 sigma_t, 1 alpha_t, 5 guidance scale, 6 quantile (i[8] = 3);  p: 0 x, 1 eps pair, 3 out (i[8] = 2), 7 table [samples, 4]
  * LINCOMB: i: 0 n elements, 1 n terms (<= 6), 2 out dtype, 3..8 term dtypes; f: 0..5 coefficients;
  *      p: 0..5 terms, 6 out
  * MEMSET: i: 0 bytes (lo), 1 bytes (hi); p: 0 dst

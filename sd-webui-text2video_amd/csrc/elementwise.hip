@@ -10,6 +10,7 @@
 //                 (samplers/ddim/gaussian_sampler.py:125-136, 103-108, 199-211, 269-283); a compile-time variant adds the
 //                 known-region blend of a masked LVDM step (lvdm/samplers/ddim.py:188-195) to the same launch
 //   ddim_restrict / ddim_measure   the DDIM_Gaussian step with its x0 clamped or thresholded by a per-video quantile of |x0|
+//   x0_threshold  UniPC's thresholded data prediction (uni_pc/uni_pc.py:351-364): ddim_measure over that x0, then clamp(x0, -s, s) / s
 //                 (restrict_range_x0, gaussian_sampler.py:110-120) and / or the classifier-guidance term (get_eps, :199-211); the measure
 //                 pass is torch.quantile on fp32, exactly, by a radix select in one workgroup per video
 //   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
@@ -23,6 +24,8 @@
 //                 the weight images were packed (packing.ParamFingerprint)
 //   lora_merge    W += alpha * (B A) for every weight of a table, in place: the Stable LoRA merge / un-merge of one file in one launch
 //                 (stable_lora/stable_utils/lora_processor.py:50-101, 202-246; stable_lora.py)
+#include <type_traits>
+
 #include "t2v_kernels.h"
 
 namespace {
@@ -209,6 +212,35 @@ __device__ __forceinline__ float ddim_x0_of(const DdimParams& p, const float* xt
   return ax - bo;
 }
 
+// x0 of a mode-2 record, the thresholded data prediction of UniPC (uni_pc/uni_pc.py:351-364 behind model_wrapper's guidance combine,
+// :304-307): e = e_u + g (e_c - e_u) when guided, x0 = (x - f0 * e) / f1 with f0 = sigma_t, f1 = alpha_t
+template <typename TE>
+__device__ __forceinline__ float unipc_x0_of(const DdimParams& p, const float* xt, const TE* ec, const TE* eu, long idx, bool guided) {
+#pragma clang fp contract(off)
+  const float x = xt[idx];
+  const float y = (float)ec[idx];
+  float e = y;
+  if (guided) {
+    const float u = (float)eu[idx];
+    const float d = p.gscale * (y - u);
+    e = u + d;
+  }
+  const float se = p.a_recip * e;
+  const float num = x - se;
+  return num / p.a_recipm1;
+}
+
+// FORM: which record's x0 the measure pass ranks and the apply pass thresholds — 0 the DDIM_Gaussian step (mode 0), 1 UniPC's data prediction (mode 2)
+template <typename TE, int FORM>
+__device__ __forceinline__ float x0_form(const DdimParams& p, const float* xt, const TE* ec, const TE* eu, long idx, bool guided) {
+  if constexpr (FORM == 0) {
+    float ax;
+    return ddim_x0_of<TE>(p, xt, ec, eu, idx, guided, &ax);
+  } else {
+    return unipc_x0_of<TE>(p, xt, ec, eu, idx, guided);
+  }
+}
+
 // torch.min / torch.max: a NaN in either operand is the result
 __device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
@@ -250,6 +282,25 @@ __global__ __launch_bounds__(256) void ddim_restrict_kernel(const DdimParams p, 
   }
 }
 
+// mode 2, i[8] = 2: out = clamp(x0, -s, s) / s with s = table[sample][0] — torch.clamp with tensor bounds, min(max(x0, -s), s); a NaN in
+// x0 or s is the result.  The x0 is unipc_x0_of's, the one the measure pass ranked.
+template <typename TE>
+__global__ __launch_bounds__(256) void x0_threshold_kernel(const DdimParams p, const float* table) {
+#pragma clang fp contract(off)
+  const float* xt = reinterpret_cast<const float*>(p.xt);
+  const TE* ec = reinterpret_cast<const TE*>(p.eps);
+  const TE* eu = ec + (size_t)p.C * p.inner;
+  float* out = reinterpret_cast<float*>(p.out);
+  const long total = (long)p.C * p.inner;
+  const long per_sample = (long)p.cps * p.inner, guided_n = (long)p.guided * p.inner;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const long smp = idx / per_sample;
+    const float x0 = x0_form<TE, 1>(p, xt, ec, eu, idx, idx - smp * per_sample < guided_n);
+    const float s = table[smp * 4];
+    out[idx] = nan_min(nan_max(x0, -s), s) / s;
+  }
+}
+
 // i[8] = 3, the measure pass: per sample the order statistics lo and hi of |x0| by an exact radix select over the keys' bit patterns
 // (|x0| as an unsigned integer orders like the float; a NaN is any key above +inf's), then torch.quantile's interpolation of the two.
 // One workgroup of 1024 threads per sample.  Integer counting only: per-wave LDS histograms, summed in a fixed order.
@@ -260,7 +311,7 @@ struct DdimMeasure {
   float w;              // rank - lo
 };
 
-template <typename TE>
+template <typename TE, int FORM = 0>
 __global__ __launch_bounds__(QT_THREADS) void ddim_measure_kernel(const DdimParams p, const DdimMeasure m) {
   __shared__ unsigned hist[QT_WAVES][256];
   __shared__ unsigned total[256];
@@ -273,8 +324,7 @@ __global__ __launch_bounds__(QT_THREADS) void ddim_measure_kernel(const DdimPara
   const TE* eu = ec + (size_t)p.C * p.inner;
   const unsigned guided_n = (unsigned)p.guided * (unsigned)p.inner;
   auto key_at = [&](unsigned i) -> unsigned {
-    float ax;
-    return __float_as_uint(ddim_x0_of<TE>(p, xt, ec, eu, base + i, i < guided_n, &ax)) & 0x7fffffffu;     // |x0|: -0.0 is 0
+    return __float_as_uint(x0_form<TE, FORM>(p, xt, ec, eu, base + i, i < guided_n)) & 0x7fffffffu;     // |x0|: -0.0 is 0
   };
 
   unsigned prefix = 0, k = m.lo, n_eq = 0;
@@ -1277,21 +1327,34 @@ hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s) {
   p.a_recip = op.f[0]; p.a_recipm1 = op.f[1]; p.sqrt_aprev = op.f[2]; p.dir_coef = op.f[3]; p.sigma = op.f[4];
   p.gscale = op.f[5];
   const int g = grid_for((long)p.C * p.inner);
+  // the measure pass of a record (i[8] = 3): one workgroup per sample, writes table[sample][0..3] only
+  auto measure = [&](auto form) -> hipError_t {
+    constexpr int FORM = decltype(form)::value;
+    const long n = (long)p.cps * p.inner;
+    if (n > (1L << 24) || !(op.f[6] > 0.f && op.f[6] <= 1.f) || op.p[7] == 0) return hipErrorInvalidValue;
+    DdimMeasure m;
+    m.table = reinterpret_cast<float*>(op.p[7]);
+    volatile float rank = op.f[6] * (float)(n - 1);     // torch.quantile's fp32 rank (one rounded product)
+    const float below = floorf(rank);
+    m.lo = (unsigned)below; m.hi = (unsigned)ceilf(rank); m.w = rank - below;
+    const int samples = p.C / p.cps;
+    if (p.eps_f32) hipLaunchKernelGGL((ddim_measure_kernel<float, FORM>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
+    else hipLaunchKernelGGL((ddim_measure_kernel<f16, FORM>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
+    return hipGetLastError();
+  };
+  if (p.mode == 2) {                           // UniPC's thresholded data prediction: measure (i[8] = 3), then apply (i[8] = 2); the executor checked
+    if (!p.x_f32 || op.i[7] != 0 || op.i[9] != 0 || op.p[7] == 0 || (p.guided != 0 && p.guided != p.cps)) return hipErrorInvalidValue;
+    if ((long)p.cps * p.inner > (1L << 24)) return hipErrorInvalidValue;
+    if (op.i[8] == 3) return measure(std::integral_constant<int, 1>{});
+    if (op.i[8] != 2 || op.p[3] == 0) return hipErrorInvalidValue;
+    const float* table = reinterpret_cast<const float*>(op.p[7]);
+    if (p.eps_f32) hipLaunchKernelGGL((x0_threshold_kernel<float>), dim3(g), dim3(256), 0, s, p, table);
+    else hipLaunchKernelGGL((x0_threshold_kernel<f16>), dim3(g), dim3(256), 0, s, p, table);
+    return hipGetLastError();
+  }
   if (op.i[8] != 0 || op.i[9] != 0) {          // restricted x0 / classifier guidance: mode 0, fp32 x, no blend (the executor checked)
     if (!p.x_f32 || p.mode != 0 || op.i[7] != 0) return hipErrorInvalidValue;
-    if (op.i[8] == 3) {                        // the measure pass: one workgroup per sample, writes table[sample][0..3] only
-      const long n = (long)p.cps * p.inner;
-      if (n > (1L << 24) || !(op.f[6] > 0.f && op.f[6] <= 1.f) || op.p[7] == 0) return hipErrorInvalidValue;
-      DdimMeasure m;
-      m.table = reinterpret_cast<float*>(op.p[7]);
-      volatile float rank = op.f[6] * (float)(n - 1);     // torch.quantile's fp32 rank (one rounded product)
-      const float below = floorf(rank);
-      m.lo = (unsigned)below; m.hi = (unsigned)ceilf(rank); m.w = rank - below;
-      const int samples = p.C / p.cps;
-      if (p.eps_f32) hipLaunchKernelGGL((ddim_measure_kernel<float>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
-      else hipLaunchKernelGGL((ddim_measure_kernel<f16>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
-      return hipGetLastError();
-    }
+    if (op.i[8] == 3) return measure(std::integral_constant<int, 0>{});
     DdimRestrict r;
     r.table = reinterpret_cast<const float*>(op.p[7]);
     r.grad = reinterpret_cast<const float*>(op.p[8]);

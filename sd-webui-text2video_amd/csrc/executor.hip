@@ -228,11 +228,21 @@ int validate_op(const t2v_op& op, int idx) {
     case T2V_OP_DDIM_STEP: {
       const int C = op.i[0], cps = op.i[6] > 0 ? op.i[6] : C;
       if (C <= 0 || op.i[1] <= 0 || cps <= 0 || C % cps != 0) return bad("DDIM step needs C > 0, inner > 0, C % channels-per-sample == 0");
-      if (op.i[2] < 0 || op.i[2] > cps || (op.i[5] != 0 && op.i[5] != 1)) return bad("DDIM step: guided channels / mode");
+      if (op.i[2] < 0 || op.i[2] > cps || op.i[5] < 0 || op.i[5] > 2) return bad("DDIM step: guided channels / mode");
       if (op.i[8] < 0 || op.i[8] > 3) return bad("DDIM step: x0 restriction i[8] must be 0 (none), 1 (clamp), 2 (threshold) or 3 (measure pass)");
       if (op.i[9] != 0 && op.i[9] != 1) return bad("DDIM step: classifier-guidance flag i[9] must be 0 or 1");
       if (op.p[0] == 0 || op.p[1] == 0 || (op.p[3] == 0 && op.i[8] != 3)) return bad("null DDIM step pointer");
       if (op.i[7] != 0 && op.i[7] != 1) return bad("DDIM step: blend flag i[7] must be 0 or 1");
+      if (op.i[5] == 2) {      // UniPC's thresholded data prediction: a measure record and an apply record, nothing else
+        if (op.i[8] != 2 && op.i[8] != 3) return bad("DDIM step: mode 2 (thresholded data prediction) is the measure pass i[8] = 3 or the apply pass i[8] = 2; the clamp i[8] = 1 and the plain prediction (a LINCOMB) are not records of it");
+        if (op.i[7] != 0 || op.i[9] != 0) return bad("DDIM step: mode 2 has no mask blend i[7] and no classifier-guidance term i[9]");
+        if (op.i[4] != T2V_F32) return bad("DDIM step: mode 2 needs an fp32 x");
+        if (op.i[2] != 0 && op.i[2] != cps) return bad("DDIM step: mode 2 combines the guidance over all channels (i[2] = channels per sample) or not at all (0)");
+        if (op.p[7] == 0) return bad("DDIM step: mode 2 needs the threshold table p[7]");
+        if ((int64_t)cps * op.i[1] > (int64_t)16777216) return bad("DDIM step: mode 2 ranks at most 16 777 216 elements per sample (torch.quantile's limit)");
+        if (op.i[8] == 3 && !(op.f[6] > 0.f && op.f[6] <= 1.f)) return bad("DDIM step: the measure pass i[8] = 3 needs a quantile f[6] in (0, 1]");
+        return 0;
+      }
       if (op.i[8] != 0 || op.i[9] != 0) {
         if (op.i[5] != 0) return bad("DDIM step: the x0 restriction i[8] and the classifier-guidance term i[9] exist for mode 0 (DDIM_Gaussian) only");
         if (op.i[7] != 0) return bad("DDIM step: the x0 restriction i[8] / classifier-guidance term i[9] and the mask blend i[7] exclude each other");

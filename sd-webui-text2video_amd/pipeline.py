@@ -157,14 +157,16 @@ class TextToVideoSynthesis(object):
     def infer_conditioned(self, c, uc, steps, frames, seed, scale, width=256, height=256, eta=0.0,
                           device=None, latents=None, strength=None, mask=None, is_vid2vid=False,
                           sampler=available_samplers[0].name, decode=True, to_host=True, _keep_sampler=False,
-                          videos: int = 1, *, clamp=None, percentile=None):
+                          videos: int = 1, *, clamp=None, percentile=None, unipc=None):
         """Stages 2-4 of `infer` for given conditioning tensors c, uc [1, 77k, 1024].
+        `unipc` (UniPC only; another sampler raises ValueError): a dict of the solver options of `samplers.UniPCSampler` (variant,
+        skip_type, order, lower_order_final, initial_corrector, denoise_to_zero, thresholding); forwarded only when set.
         `clamp` / `percentile` (DDIM_Gaussian only; another sampler raises ValueError): the restriction of the predicted x0 of
         `GaussianDiffusion.sample` — percentile=0.995 is dynamic thresholding per video, clamp=<anything> clamps x0 to [-1, 1] (the
         reference's `clamp=True` quirk, gaussian_sampler.py:178); forwarded only when set.
         Returns (frames, last_tensor): frames = list of HxWx3 uint8 BGR arrays (to_host) or a
         uint8 device tensor [F,H,W,3] RGB (to_host=False), or None when decode=False.
-        `videos` > 1 (DDIM_Gaussian, txt2vid): that many independent videos of the same prompt in ONE batch — every
+        `videos` > 1 (every sampler; txt2vid and vid2vid, where the ONE input clip's latents are repeated): that many independent videos of the same prompt in ONE batch — every
         UNet step is a single 2*videos forward; the frames come back side by side ([F, H, videos*W, 3], the layout
         `tensor2vid` gives a batch, t2v_pipeline.py:447-460).  Video v starts from the noise of seed + v, i.e. the batch is
         the reference's `batch_count` loop (process_modelscope.py:152-221: one video at a time, seed + batch) in one pass."""
@@ -176,8 +178,11 @@ class TextToVideoSynthesis(object):
             self.diffusion.get_sampler(sampler, return_sampler=False)
         latents, noise, shape = self.diffusion.get_noise(1, 4, frames, height, width, seed=seed, latents=latents)
         if videos > 1:
-            if sampler != "DDIM_Gaussian" or latents is not None or is_vid2vid:
-                raise NotImplementedError("several videos per batch: DDIM_Gaussian text-to-video only")
+            if mask is not None or (latents is not None and not is_vid2vid):
+                raise NotImplementedError("several videos per batch: text-to-video and vid2vid only — the img2vid route draws every "
+                                          "video's latents from numpy's global generator (process_modelscope.py:205), one call per video")
+            if latents is not None and latents.shape[0] != 1:
+                raise ValueError(f"several videos per batch start from ONE input clip, got latents of batch {latents.shape[0]}")
             one = (1,) + tuple(shape[1:])
             draws = []
             for v in range(videos):                      # each video from its own seed, as the batch_count loop draws them
@@ -188,7 +193,7 @@ class TextToVideoSynthesis(object):
         x0 = self.diffusion.sample_loop(
             steps=steps, strength=strength, eta=eta, conditioning=c.to(dev), unconditional_conditioning=uc.to(dev),
             batch_size=videos, guidance_scale=scale, latents=latents, shape=shape, noise=noise, is_vid2vid=is_vid2vid,
-            sampler_name=sampler, mask=mask, **_restriction(clamp, percentile))
+            sampler_name=sampler, mask=mask, **_restriction(clamp, percentile, unipc))
         self.last_tensor = x0
         if not decode:
             return None, x0
@@ -273,7 +278,7 @@ class TextToVideoSynthesis(object):
 
     def infer(self, prompt, n_prompt, steps, frames, seed, scale, width=256, height=256, eta=0.0,
               cpu_vae="GPU (half precision)", device=torch.device("cuda"), latents=None, skip_steps=0,
-              strength=0, mask=None, is_vid2vid=False, sampler=available_samplers[0].name, *, clamp=None, percentile=None):
+              strength=0, mask=None, is_vid2vid=False, sampler=available_samplers[0].name, *, clamp=None, percentile=None, unipc=None):
         vars_ = dict(prompt=prompt, n_prompt=n_prompt, steps=steps, frames=frames, seed=seed, scale=scale,
                      width=width, height=height, eta=eta, cpu_vae=cpu_vae, device=str(device),
                      skip_steps=skip_steps, strength=strength, is_vid2vid=is_vid2vid, sampler=sampler)
@@ -286,13 +291,14 @@ class TextToVideoSynthesis(object):
         c, uc = self.preprocess(prompt, n_prompt, steps)
         strength = None if (strength == 0.0 and not is_vid2vid) else strength
         frames_bgr, x0 = self.infer_conditioned(c, uc, steps, frames, seed, scale, width, height, eta, device,
-                                                latents, strength, mask, is_vid2vid, sampler, **_restriction(clamp, percentile))
+                                                latents, strength, mask, is_vid2vid, sampler, **_restriction(clamp, percentile, unipc))
         return frames_bgr, self.last_tensor, create_infotext(vars_)
 
 
-def _restriction(clamp, percentile) -> dict:
-    """The x0-restriction keywords that are set — nothing is forwarded when neither is, so a call without them is what it was."""
-    return {k: v for k, v in (("clamp", clamp), ("percentile", percentile)) if v is not None}
+def _restriction(clamp, percentile, unipc=None) -> dict:
+    """The x0-restriction keywords and the UniPC options that are set — nothing is forwarded when none is, so a call without them is
+    what it was."""
+    return {k: v for k, v in (("clamp", clamp), ("percentile", percentile), ("unipc", unipc)) if v is not None}
 
 
 _CPU_VAE_NOTED = False
@@ -332,6 +338,7 @@ def process_modelscope(args_dict: dict, extra_args=None):
       args_dict = {model_dir | pipe, prompt, n_prompt, steps, frames, seed, cfg_scale, width, height, eta, sampler,
                    batch_count, clip_encoder | (cond, uncond), stitch,
                    clamp, percentile,                                         # x0 restriction of DDIM_Gaussian (gaussian_sampler.py:110-120), below
+                   unipc,                                                     # solver options of UniPC (uni_pc/uni_pc.py:314-343), below
                    enable_emphasis, comma_padding_backtrack,                  # webui's opts of the prompt syntax (clip_hardcode.py:153,203)
                    do_vid2vid, vid2vid_frames, strength,                      # :80-147
                    inpainting_frames, inpainting_image, inpainting_weights,   # :170-217
@@ -343,12 +350,15 @@ def process_modelscope(args_dict: dict, extra_args=None):
     * `percentile` (e.g. 0.995: dynamic thresholding, s = max(quantile(|x0|, p), 1) per video) / `clamp` (any value: x0 clamped to [-1, 1],
       the reference's `clamp=True` quirk) go to `GaussianDiffusion.sample` through `infer` / `infer_conditioned`; DDIM_Gaussian only, and
       with neither key present the call is what it was.
+    * `unipc` = a dict of UniPC's solver options (variant, skip_type, order, lower_order_final, initial_corrector, denoise_to_zero,
+      thresholding: `samplers.UniPCSampler`); UniPC only, and without the key the call is what it was.  webui's `shared.opts` is not read.
     * `stitch(frames_bgr, infotext) -> bytes` (the ffmpeg stage, out of scope — e.g. the reference's own
       `ffmpeg_stitch_video` behind a temp directory) given: returns the reference's list of data-URLs, video b from
       seed + b (seed -1 stays random), exactly the reference loop;
     * no `stitch`: returns the BGR uint8 frames of the (last) video — what the reference writes as PNGs (:225-229);
       with (cond, uncond) tensors and batch_count > 1 the videos of seeds seed .. seed + batch_count - 1 are made in ONE
-      batched pass, frames side by side.
+      batched pass, frames side by side — vid2vid (`do_vid2vid`) too: the input clip's latents are repeated, video b gets the noise of
+      seed + b.  The img2vid route stays one call per video: it draws every video's latents from numpy's global generator.
     * vid2vid (`do_vid2vid`, :80-142): `vid2vid_frames` = the input clip as [F, H, W, 3] uint8 RGB frames of ANY size — a numpy
       array or a (device) tensor such as `infer_conditioned(..., to_host=False)` returns; frames not at (height, width) are
       resized on the GPU exactly as the reference's PIL `Image.ANTIALIAS` resize does (:116-120; `pipe.resize_frames`) — or a
@@ -379,7 +389,7 @@ def process_modelscope(args_dict: dict, extra_args=None):
     width, height = getattr(a, "width", 256), getattr(a, "height", 256)
     common = dict(frames=a.frames, scale=a.cfg_scale, width=width, height=height, eta=getattr(a, "eta", 0.0),
                   sampler=getattr(a, "sampler", available_samplers[0].name),
-                  **_restriction(getattr(a, "clamp", None), getattr(a, "percentile", None)))
+                  **_restriction(getattr(a, "clamp", None), getattr(a, "percentile", None), getattr(a, "unipc", None)))
     batch_count = int(getattr(a, "batch_count", 1))
     stitch = getattr(a, "stitch", None)
     cpu_vae = getattr(a, "cpu_vae", "GPU (half precision)")
@@ -437,6 +447,13 @@ def process_modelscope(args_dict: dict, extra_args=None):
 
     if have_cond and stitch is None and not do_vid2vid and not inpainting:
         frames, _ = pipe.infer_conditioned(a.cond, a.uncond, steps=a.steps, seed=a.seed, videos=batch_count, **common)
+        return frames
+    if have_cond and stitch is None and do_vid2vid and not inpainting and batch_count > 1:
+        # the batch_count loop below in ONE pass: the clip's latents repeated, video b from the noise of seed + b
+        if "half precision" in str(cpu_vae) and getattr(pipe, "autoencoder", None) is not None:
+            pipe.autoencoder.half()
+        frames, _ = pipe.infer_conditioned(a.cond, a.uncond, a.steps - skip_steps, seed=a.seed if a.seed != -1 else random.randint(0, 2 ** 32 - 1),
+                                           latents=latents, strength=strength, is_vid2vid=True, device=device, videos=batch_count, **common)
         return frames
     urls, frames = [], None
     inpaint_sized = None

@@ -398,6 +398,42 @@ def _ddim_restricted_step(out, xt, eps_pair, noise, coef, guided: int, **kw):
     return out
 
 
+UNIPC_QUANTILE = 0.995      # the reference's hard-coded ratio (uni_pc/uni_pc.py:360)
+
+
+def _x0_threshold_records(out, x, eps_pair, sigma: float, alpha: float, guide: float, guided: bool, table, quantile: float = UNIPC_QUANTILE):
+    """-> the two T2V_OP_DDIM_STEP records (mode 2) of one thresholded data prediction of UniPC (uni_pc/uni_pc.py:351-364):
+    the measure pass (i[8] = 3) that writes `table` [videos, 4] fp32 = {s, q, v_lo, v_hi}, and the apply pass (i[8] = 2) that writes
+    out = clamp(x0, -s, s) / s with x0 = (x - sigma * e) / alpha, e = e_u + guide * (e_c - e_u) over all channels when `guided`."""
+    B, C = x.shape[0], x.shape[1]
+    if x.dtype != torch.float32 or out.dtype != torch.float32:
+        raise L.T2VError("a thresholded data prediction needs an fp32 latent x")
+    if x.numel() // B > (1 << 24):
+        raise L.T2VError("a thresholded data prediction ranks at most 16 777 216 elements per video (torch.quantile's limit)")
+    if not (table is not None and table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (B, 4)
+            and table.device == x.device):
+        raise L.T2VError("the threshold table of a thresholded data prediction must be fp32 [videos, 4], contiguous, on the device")
+    ops = (L.T2VOp * 2)()
+    for k, restrict in enumerate((3, 2)):
+        op = ops[k]
+        op.kind = L.OP_DDIM_STEP
+        op.i[0], op.i[1], op.i[2] = B * C, x.numel() // (B * C), C if guided else 0
+        op.i[3], op.i[4], op.i[5], op.i[6], op.i[8] = _dt_tag(eps_pair), _dt_tag(x), 2, C, restrict
+        op.f[0], op.f[1], op.f[5] = float(sigma), float(alpha), float(guide)
+        op.p[0], op.p[1], op.p[3], op.p[7] = x.data_ptr(), eps_pair.data_ptr(), out.data_ptr(), table.data_ptr()
+        if restrict == 3:
+            op.f[6] = float(quantile)
+    return ops
+
+
+def _x0_threshold(out, x, eps_pair, sigma: float, alpha: float, guide: float, guided: bool, table):
+    """One thresholded data prediction (`_x0_threshold_records`): ONE t2v_run_ops call; s stays on the device."""
+    ops = _x0_threshold_records(out, x, eps_pair, sigma, alpha, guide, guided, table)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    L.check(L.load().t2v_run_ops(ops, len(ops), None, 0, ctypes.c_void_p(stream)))
+    return out
+
+
 def _ddim_update_blend(out, xt, eps_pair, noise, coef, guided: int, known, mask, qnoise, qcoef):
     """T2V_OP_DDIM_STEP mode 1 with i[7] = 1: the LDM DDIM update of `_ddim_update` and, in the same launch, the known-region blend
     of a masked step (lvdm/samplers/ddim.py:188-195): out = (qcoef[0] * known + qcoef[1] * qnoise) * mask + (1 - mask) * x_{t-1}.
@@ -477,23 +513,39 @@ def _step_noise(sampler, like: torch.Tensor, sigma: float) -> torch.Tensor:
     return torch.randn_like(like, dtype=torch.float32)
 
 
+def _check_batch_layout(sampler, videos: int) -> None:
+    """Several videos per batch exist on one device only: the CFG-pair and T-shard layouts run one video."""
+    if videos > 1:
+        split = getattr(sampler, "cfg_parallel", None) is not None and sampler.cfg_parallel.size == 2
+        assert not split, "the CFG-pair layout runs one video per pair"
+        assert getattr(sampler.model, "t_shard", None) is None, "a clip whose frames are split over ranks runs one video per batch"
+
+
 def _eval_eps_pair(model, x, t_value, c, uc, guide, cfg_parallel=None, cache: Optional[dict] = None):
     """-> (eps [1 or 2, C, F, h, w] (index 0 conditional, 1 unconditional), guided: bool).  One batched
     b=2 forward when the model supports it; t_value may be fractional (UniPC).  `cache` (one dict per sampling run): the
     [cond | uncond] batch is built once while the conditioning objects stay the same, and the UNet reuses their K/V."""
     dev = x.device
-    tt = torch.full((1,), float(t_value), dtype=torch.float32, device=dev)
+    B = x.shape[0]                            # videos per batch: one timestep for all of them, eps = [cond (B), uncond (B)]
+    tt = torch.full((B,), float(t_value), dtype=torch.float32, device=dev)
+    c0, uc0 = c, uc
+    if B > 1:                                 # conditioning of batch 1 is expanded, conditioning of batch B is taken per video
+        c = c.expand(B, *c.shape[1:]) if c.shape[0] == 1 else c
+        if uc is not None:
+            uc = uc.expand(B, *uc.shape[1:]) if uc.shape[0] == 1 else uc
     if guide is None or guide == 1.0 or uc is None:
         return model(x, tt, c).contiguous(), False
     if cfg_parallel is not None and cfg_parallel.size == 2:
+        assert B == 1, "the CFG-pair layout runs one video per pair"
         mine = c if cfg_parallel.role == 0 else uc
         return cfg_parallel.exchange_eps(model(x, tt, mine)).contiguous(), True
     ragged = c.shape[1] != uc.shape[1]        # a prompt of more 77-token chunks than the negative prompt (or fewer): no padding, as the reference
-    if cache is not None and hasattr(model, "forward_cfg_pair") and c.shape[0] == uc.shape[0] == x.shape[0]:
-        ident = (cache.setdefault("nonce", next(_RUN_COUNTER)), id(c), c._version, id(uc), uc._version)
+    if cache is not None and hasattr(model, "forward_cfg_pair") and c.shape[0] == uc.shape[0] == B:
+        # (the conditioning OBJECTS the caller holds name the context: the expanded views of a batch are new objects every step)
+        ident = (cache.setdefault("nonce", next(_RUN_COUNTER)), id(c0), c0._version, id(uc0), uc0._version)
         if cache.get("key") != ident:
             # equal lengths: the [cond | uncond] batch; unequal: the pair itself — the model packs it once per token (forward_cfg_pair)
-            cache.update(key=ident, ctx=(c, uc) if ragged else torch.cat([c, uc], dim=0), refs=(c, uc))
+            cache.update(key=ident, ctx=(c, uc) if ragged else torch.cat([c, uc], dim=0), refs=(c0, uc0))
         return model.forward_cfg_pair(x, tt, cache["ctx"], context_token=ident, single_t=True).contiguous(), True
     if getattr(model, "supports_cfg_batch", False) and not ragged:
         return model(torch.cat([x, x], dim=0), torch.cat([tt, tt]), torch.cat([c, uc], dim=0)).contiguous(), True
@@ -537,6 +589,7 @@ class DDIMSampler(object):
     def _run(self, img, cond, uncond, time_range, total_steps, guide, callback):
         model, dev = self.model, img.device
         C = img.shape[1]
+        _check_batch_layout(self, img.shape[0])     # several videos per batch: one 2V-row forward and one update launch per step
         nxt = torch.empty_like(img)
         if hasattr(model, "verify_weights"):
             model.verify_weights(dev)           # the bytes: in-place edits (`w.data += d`) that no version counter shows — once per call
@@ -572,7 +625,6 @@ class DDIMSampler(object):
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
         img = torch.randn(tuple(shape), device=self.device) if x_T is None else x_T.clone()
         img = img.float().contiguous() if img.dtype not in (torch.float16, torch.float32) else img.contiguous()
-        assert img.shape[0] == 1
         return self._run(img, conditioning, unconditional_conditioning, np.flip(self.ddim_timesteps),
                          self.ddim_timesteps.shape[0], unconditional_guidance_scale, callback)
 
@@ -628,32 +680,101 @@ class _VPSchedule:
         la = self.log_alpha_t(t)
         return la - 0.5 * math.log(1.0 - math.exp(2.0 * la))
 
+    def inverse_lambda(self, lam: float) -> float:
+        """The time label t of a half-logSNR (NoiseScheduleVP.inverse_lambda, 'discrete', uni_pc.py:145-148): log(alpha) =
+        -0.5 * logaddexp(0, -2 lam), then the piecewise-linear log(alpha_t) read backwards (outermost segments extended)."""
+        import math
+        z = -2.0 * lam
+        la = -0.5 * (max(z, 0.0) + math.log1p(math.exp(-abs(z))))
+        xp, yp = self.log_alpha.flip(0), self.t.flip(0)          # log(alpha_t) falls with t: ascending after the flip
+        k = int(torch.searchsorted(xp, torch.tensor(la, dtype=torch.float64)))
+        k = min(max(k, 1), len(xp) - 1)
+        x0, x1, y0, y1 = float(xp[k - 1]), float(xp[k]), float(yp[k - 1]), float(yp[k])
+        return y0 + (la - x0) * (y1 - y0) / (x1 - x0)
+
+
+UNIPC_OPTIONS = ("variant", "skip_type", "order", "lower_order_final", "initial_corrector", "denoise_to_zero", "thresholding")
+_UNIPC_DEFAULTS = dict(variant="bh1", skip_type="time_uniform", order=3, lower_order_final=True, initial_corrector=True,
+                       denoise_to_zero=False, thresholding=False, predict_x0=True, method="multistep", max_val=1.0)
+
+
+def _unipc_options(given: dict) -> dict:
+    """The solver options of UniPC (uni_pc/uni_pc.py:314-343, 683-686) from the keywords that were given (None = not given): the
+    reference wrapper's configuration where nothing is said, a ValueError that names the keyword for a value the class does not
+    know, NotImplementedError for what this build leaves out."""
+    o = dict(_UNIPC_DEFAULTS)
+    o.update({k: v for k, v in given.items() if v is not None})
+    if o["variant"] == "vary_coeff":
+        raise ValueError("variant='vary_coeff': the reference's own implementation cannot run on a video latent (its "
+                         "einsum('bkchw,k->bchw') gets a 6-D tensor, uni_pc/uni_pc.py:448-549), so there is nothing to match; use 'bh1' or 'bh2'")
+    if o["variant"] not in ("bh1", "bh2"):
+        raise ValueError(f"variant must be 'bh1' or 'bh2', got {o['variant']!r}")
+    if o["skip_type"] not in ("time_uniform", "time_quadratic", "logSNR"):
+        raise ValueError(f"skip_type must be 'time_uniform', 'time_quadratic' or 'logSNR', got {o['skip_type']!r}")
+    if isinstance(o["order"], bool) or o["order"] not in (1, 2, 3):
+        raise ValueError(f"order must be 1, 2 or 3, got {o['order']!r}")
+    for k in ("lower_order_final", "initial_corrector", "denoise_to_zero", "thresholding", "predict_x0"):
+        if not isinstance(o[k], bool):
+            raise ValueError(f"{k} must be True or False, got {o[k]!r}")
+    if not o["predict_x0"]:
+        raise NotImplementedError("predict_x0=False (noise prediction) is not built: the pipeline's UniPC predicts x0")
+    if o["method"] != "multistep":
+        raise NotImplementedError(f"method={o['method']!r}: only the multistep solver is built (the reference's other branches raise too, uni_pc.py:738-739)")
+    if float(o["max_val"]) != 1.0:
+        raise NotImplementedError(f"max_val={o['max_val']!r}: the threshold floor is 1.0, as the reference's wrapper leaves it")
+    return o
+
 
 class UniPCSampler(object):
-    """Sampler "UniPC": order-3 multistep unified predictor-corrector, B(h)=h ("bh1"), data prediction,
-    time-uniform steps, lower-order final steps, initial corrector — reference uni_pc/sampler.py:31-90 ->
-    uni_pc/uni_pc.py:683-743, 551-677.  Every latent update is one T2V_OP_LINCOMB launch."""
+    """Sampler "UniPC": multistep unified predictor-corrector with data prediction — reference uni_pc/sampler.py:31-90 ->
+    uni_pc/uni_pc.py:683-743, 551-677.  With no option given it is the configuration the reference's wrapper hard-codes: order 3,
+    B(h) = h ("bh1"), time-uniform steps, lower-order final steps, initial corrector, no thresholding.  The options of the reference's
+    solver class (UNIPC_OPTIONS; `_unipc_options`) are keywords of the constructor and of `sample` — one given to `sample` wins:
+      variant            "bh1" | "bh2" (B(h) = expm1(h), the form the authors recommend for guided sampling at few steps)
+      skip_type          "time_uniform" | "time_quadratic" | "logSNR" (uni_pc.py:385-400)
+      order              1 | 2 | 3; steps >= order
+      lower_order_final  the order falls towards the last step (:715-718)
+      initial_corrector  False: the warm-up steps evaluate the model at the predicted point (:704-707)
+      denoise_to_zero    one more data prediction at t_0 after the loop (:740-741); no extra callback
+      thresholding       every data prediction is thresholded per video: s = max(quantile(|x0|, 0.995), 1), x0 = clamp(x0, -s, s) / s
+                         (:351-364) — two T2V_OP_DDIM_STEP mode-2 records in one launch call; `last_thresholds` keeps the
+                         [evaluations, videos, 4] device tensor {s, q, v_lo, v_hi} of the last run
+    Every other latent update is one T2V_OP_LINCOMB launch; the options change host scalars only.  Several videos per batch (this
+    build's extension; the reference's update cannot run there): one 2V-row forward per evaluation, each video equals its own run."""
 
-    def __init__(self, model, device=None, **kwargs):
+    def __init__(self, model, device=None, variant=None, skip_type=None, order=None, lower_order_final=None, initial_corrector=None,
+                 denoise_to_zero=None, thresholding=None, predict_x0=None, method=None, max_val=None, **kwargs):
         self.model = model
         self.device = torch.device(device) if device is not None else None
         self.alphas_cumprod = model.alphas_cumprod.detach().clone().to(torch.float32)
         self.cfg_parallel = None
         self._pair_cache = {}
+        self.options = dict(variant=variant, skip_type=skip_type, order=order, lower_order_final=lower_order_final,
+                            initial_corrector=initial_corrector, denoise_to_zero=denoise_to_zero, thresholding=thresholding,
+                            predict_x0=predict_x0, method=method, max_val=max_val)
+        _unipc_options(self.options)           # a wrong value is refused where it is given
+        self.last_thresholds = None            # thresholding runs: the thresholds of the last `sample` call (see the class)
+        self._thresholds = None                # (the table of the run in progress, one row per evaluation)
+        self._evaluation = 0
 
     # -- x0 prediction from the (guided) noise prediction: x0 = (x - sigma_t * eps_g) / alpha_t -------------
     def _data_prediction(self, ns, x, t, cond, uncond, guide):
         eps, guided = _eval_eps_pair(self.model, x, (t - 1.0 / ns.total_N) * 1000.0, cond, uncond, guide, self.cfg_parallel,
                                      cache=self._pair_cache)
         a, s = ns.alpha(t), ns.std(t)
+        nb = x.shape[0]
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        if self._thresholds is not None:       # thresholded: measure + apply, the row of this evaluation stays on the device
+            row = self._thresholds[self._evaluation]
+            self._evaluation += 1
+            return _x0_threshold(out, x, eps, s, a, float(guide) if guided else 1.0, guided, row)
         if guided:
             g = float(guide)
-            return _lincomb(out, [(1.0 / a, x), (-s * g / a, eps[0:1]), (-s * (1.0 - g) / a, eps[1:2])])
-        return _lincomb(out, [(1.0 / a, x), (-s / a, eps[0:1])])
+            return _lincomb(out, [(1.0 / a, x), (-s * g / a, eps[0:nb]), (-s * (1.0 - g) / a, eps[nb:2 * nb])])
+        return _lincomb(out, [(1.0 / a, x), (-s / a, eps[0:nb])])
 
-    def _update(self, ns, x, m_prev, t_prev, t, order, use_corrector, cond, uncond, guide):
-        """multistep_uni_pc_bh_update (predict_x0, bh1): returns (x_t, model_t or None)."""
+    def _update(self, ns, x, m_prev, t_prev, t, order, use_corrector, cond, uncond, guide, variant="bh1"):
+        """multistep_uni_pc_bh_update (predict_x0; B(h) = h for "bh1", expm1(h) for "bh2"): returns (x_t, model_t or None)."""
         import math
         lam_t, lam_0 = ns.lam(t), ns.lam(t_prev[-1])
         h = lam_t - lam_0
@@ -662,7 +783,7 @@ class UniPCSampler(object):
         hh = -h
         h_phi_1 = math.expm1(hh)
         h_phi_k = h_phi_1 / hh - 1.0
-        B_h = hh
+        B_h = hh if variant == "bh1" else math.expm1(hh)
         R, b, fact = [], [], 1
         for i in range(1, order + 1):
             R.append([rk ** (i - 1) for rk in rks])
@@ -692,18 +813,42 @@ class UniPCSampler(object):
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, strength=None, eta=0.0, mask=None,
-               x_T=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None, **kwargs):
+               x_T=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None, variant=None, skip_type=None,
+               order=None, lower_order_final=None, initial_corrector=None, denoise_to_zero=None, thresholding=None,
+               predict_x0=None, method=None, max_val=None, **kwargs):
+        given = dict(variant=variant, skip_type=skip_type, order=order, lower_order_final=lower_order_final,
+                     initial_corrector=initial_corrector, denoise_to_zero=denoise_to_zero, thresholding=thresholding,
+                     predict_x0=predict_x0, method=method, max_val=max_val)
+        opt = _unipc_options({k: (self.options[k] if v is None else v) for k, v in given.items()})
         model = self.model
         dev = x_T.device if x_T is not None else (self.device or torch.device(model.device))
         x = torch.randn(tuple(shape), device=dev) if x_T is None else x_T
+        if opt["thresholding"] and x.dtype == torch.float16:
+            raise L.T2VError("thresholding needs an fp32 latent x_T")
         x = x.float().contiguous()
-        assert x.shape[0] == 1
+        _check_batch_layout(self, x.shape[0])
         ns = _VPSchedule(self.alphas_cumprod)
-        order, steps = 3, S
+        order, steps = opt["order"], S
         assert steps >= order
         t_T = ns.T if strength is None else strength
         t_0 = 1.0 / ns.total_N
-        ts = torch.linspace(t_T, t_0, steps + 1, dtype=torch.float32).to(torch.float64).tolist()   # 'time_uniform', fp32 grid
+        f32 = torch.float32
+        if opt["skip_type"] == "time_uniform":         # every grid is the reference's fp32 tensor (uni_pc.py:385-400), read as float64
+            ts = torch.linspace(t_T, t_0, steps + 1, dtype=f32).to(torch.float64).tolist()
+        elif opt["skip_type"] == "time_quadratic":
+            ts = torch.linspace(t_T ** 0.5, t_0 ** 0.5, steps + 1, dtype=f32).pow(2).to(torch.float64).tolist()
+        else:                                          # uniform in half-logSNR, mapped back to time labels
+            lams = torch.linspace(ns.lam(t_T), ns.lam(t_0), steps + 1, dtype=f32).to(torch.float64).tolist()
+            ts = [ns.inverse_lambda(v) for v in lams]
+        self._thresholds, self._evaluation = None, 0
+        if opt["thresholding"]:
+            if getattr(model, "t_shard", None) is not None:
+                raise L.T2VError("thresholding with a clip whose frames are split over ranks: the quantile over all frames of a video "
+                                 "needs the whole clip on one device")
+            if x.numel() // x.shape[0] > (1 << 24):
+                raise L.T2VError("thresholding ranks at most 16 777 216 elements per video (torch.quantile's limit)")
+            # one row per data prediction, written by its measure pass: S evaluations, one more for denoise_to_zero
+            self._thresholds = torch.zeros((steps + (1 if opt["denoise_to_zero"] else 0), x.shape[0], 4), dtype=f32, device=dev)
         guide = unconditional_guidance_scale
         self._pair_cache = {}                      # per sampling run (its nonce keeps cached context K/V from leaking across runs)
         if hasattr(model, "verify_weights"):
@@ -721,25 +866,32 @@ class UniPCSampler(object):
         try:
             c, uc = conds()
             m_prev, t_prev = [self._data_prediction(ns, x, ts[0], c, uc, guide)], [ts[0]]
-            for init_order in range(1, order):                       # warm-up with lower orders + corrector
+            for init_order in range(1, order):                       # warm-up with lower orders (+ corrector: initial_corrector)
                 c, uc = conds()
-                x, mx = self._update(ns, x, m_prev, t_prev, ts[init_order], init_order, True, c, uc, guide)
+                x, mx = self._update(ns, x, m_prev, t_prev, ts[init_order], init_order, opt["initial_corrector"], c, uc, guide,
+                                     variant=opt["variant"])
+                if mx is None:                                       # no corrector: the model at the predicted point (uni_pc.py:705-706)
+                    mx = self._data_prediction(ns, x, ts[init_order], c, uc, guide)
                 m_prev.append(mx)
                 t_prev.append(ts[init_order])
                 if callback is not None:
                     callback()
             for step in range(order, steps + 1):
                 c, uc = conds()
-                step_order = min(order, steps + 1 - step)            # lower_order_final
+                step_order = min(order, steps + 1 - step) if opt["lower_order_final"] else order
                 use_corr = step != steps                             # no corrector (= no model call) at the last step
-                x, mx = self._update(ns, x, m_prev, t_prev, ts[step], step_order, use_corr, c, uc, guide)
+                x, mx = self._update(ns, x, m_prev, t_prev, ts[step], step_order, use_corr, c, uc, guide, variant=opt["variant"])
                 m_prev, t_prev = m_prev[1:] + [mx], t_prev[1:] + [ts[step]]
                 if callback is not None:
                     callback()
+            if opt["denoise_to_zero"]:                               # x0 at t_0 from the last latent (uni_pc.py:433-437, 740-741); no callback
+                c, uc = conds()
+                x = self._data_prediction(ns, x, float(torch.tensor(t_0, dtype=f32)), c, uc, guide)
         finally:
             if prev_auto is not None:
                 model.auto_refresh = prev_auto
             _restore_eps(model, prev_eps)
+            self.last_thresholds, self._thresholds = self._thresholds, None      # [evaluations, videos, 4] {s, q, v_lo, v_hi} on the device, else None
         return x
 
     @torch.no_grad()
@@ -806,6 +958,9 @@ class Txt2VideoSampler(object):
     def encode_latent(self, latent, noise, strength, steps):
         """vid2vid noising (:123-145): dispatch on what the active solver offers."""
         encoded_latent, denoise_steps = None, None
+        if noise is not None and latent.shape[0] == 1 and noise.shape[0] > 1:
+            # several videos per batch from one input clip: its latents are repeated, every video has its own noise
+            latent = latent.expand(noise.shape[0], *latent.shape[1:]).contiguous()
         if hasattr(self.sampler, "unipc_encode"):
             encoded_latent = self.sampler.unipc_encode(latent, self.device, strength, steps, noise=noise)
         if hasattr(self.sampler, "stochastic_encode"):
@@ -835,13 +990,22 @@ class Txt2VideoSampler(object):
 
     def sample_loop(self, steps, strength, conditioning, unconditional_conditioning, batch_size, latents=None,
                     shape=None, noise=None, is_vid2vid=False, guidance_scale=1, eta=0, mask=None,
-                    sampler_name="DDIM", *, clamp=None, percentile=None):
+                    sampler_name="DDIM", *, clamp=None, percentile=None, unipc=None):
         """samplers_common.py:165-207.  `clamp` / `percentile` (keyword, this build's addition to the signature): the x0 restriction of
-        GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set, so every other call is what it was."""
+        GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set, so every other call is what it was.
+        `unipc` (keyword, likewise): a dict of UniPC's solver options (UNIPC_OPTIONS, see UniPCSampler) — UniPC only, forwarded only
+        when set."""
         restrict = {k: v for k, v in (("clamp", clamp), ("percentile", percentile)) if v is not None}
+        active = next((s.name for s in available_samplers if isinstance(self.sampler, s.Sampler)), type(self.sampler).__name__)
         if restrict and not isinstance(self.sampler, GaussianDiffusion):
-            active = next((s.name for s in available_samplers if isinstance(self.sampler, s.Sampler)), type(self.sampler).__name__)
             raise ValueError(f"{' / '.join(restrict)}: the x0 restriction exists for the DDIM_Gaussian sampler only, not for {active!r}")
+        if unipc is not None:
+            if not isinstance(self.sampler, UniPCSampler):
+                raise ValueError(f"unipc: the solver options exist for the UniPC sampler only, not for {active!r}")
+            unknown = [k for k in unipc if k not in _UNIPC_DEFAULTS]
+            if unknown:
+                raise ValueError(f"unipc: unknown option(s) {', '.join(map(repr, unknown))}; the options are {', '.join(UNIPC_OPTIONS)}")
+            restrict.update(unipc)
         denoise_steps = None
         if latents is not None and is_vid2vid:
             latents, denoise_steps = self.encode_latent(latents, noise, strength, steps)
