@@ -299,6 +299,37 @@ RELPOS_SHORT_CASES = [
     _rel("short-d80-T16-masked", 80, 16, 16, 0, 16, False, sels=(0, 1, 2, 3), variant="masked"),
 ]
 
+# ---- the `lowered` family: one case per code path that a lowered program takes and no case above has (tests/record_paths.py is the key, ----
+# ---- tests/test_record_paths_cpu.py the check; profiles/lowered_paths.txt names a deployed op for each).  Head dimension x kernel form x ----
+# ---- one key tile / several x ragged keys x ragged queries x low-order output, at the smallest sizes of each class ----------------------
+ATTN_CASES += [
+    _attn("lowered-cross-d64-nq128-nk40", "cross", 64, 2, 1, 2, 128, 40, 64),                      # 4-wave kernel, whole query blocks, one ragged key tile
+    _attn("lowered-self-d64-hw64", "self", 64, 2, 1, 2, 64, 64, 64),                               # ... half a query block, one whole key tile
+    _attn("lowered-self-d40-hw64", "self", 40, 2, 1, 2, 64, 64, 64),
+    _attn("lowered-self-d40-hw64-lo", "self", 40, 2, 1, 2, 64, 64, 64, lo=True),
+    _attn("lowered-self-d160-hw64", "self", 160, 2, 1, 2, 64, 64, 64),
+    _attn("lowered-cross-d40-nq64-nk9", "cross", 40, 2, 2, 2, 64, 9, 64),                          # VideoCrafter's 9-token context at the tiny size
+    _attn("lowered-cross-d40-nq64-nk9-lo", "cross", 40, 2, 2, 2, 64, 9, 64, lo=True),
+    _attn("lowered-self-d80-hw16", "self", 80, 2, 1, 2, 16, 16, 32),                               # one wave, the 32-key tile, both ragged
+    _attn("lowered-self-d80-hw16-lo", "self", 80, 2, 1, 2, 16, 16, 32, lo=True),
+    _attn("lowered-self-d160-hw16", "self", 160, 2, 1, 2, 16, 16, 32),
+    _attn("lowered-cross-d64-nq20-nk77", "cross", 64, 2, 2, 2, 20, 77, 64, placement="second"),    # one wave, 64 + 13 keys
+    _attn("lowered-cross-d160-nq16-nk77", "cross", 160, 2, 2, 2, 16, 77, 64, placement="second"),
+    _attn("lowered-self-d64-hw192", "self", 64, 2, 1, 2, 192, 192, 64),                            # three whole key tiles, a ragged query block
+    _attn("lowered-self-d40-hw256", "self", 40, 2, 1, 2, 256, 256, 64),                            # whole key tiles and whole query blocks
+    _attn("lowered-self-d80-hw256", "self", 80, 2, 1, 2, 256, 256, 64),
+]
+RELPOS_LONG_CASES += [_rel("lowered-long-d160-T40-R16", 160, 40, 40, 0, 16, False)]               # a 40-frame clip: two key tiles, the clamp live
+RELPOS_SHORT_CASES += [
+    _rel("lowered-short-d40-T5-lo-relpos16", 40, 5, 5, 0, 16, True, sels=(2,)),
+    _rel("lowered-short-d160-T16-relpos16", 160, 16, 16, 0, 16, False, sels=(2,)),
+]
+# T-sharded ranks: the VALU kernel (selector 0) on a slice of the queries at the start, in the middle and at the end of a clip of 5, 8 and
+# 16 frames (TB = 1, 1, 2); the forced long-clip kernel on the same inputs as the second opinion
+for _T, _Tq, _offs, _Ds in ((5, 2, (0, 2, 3), (40,)), (8, 3, (0, 3, 5), (80,)), (16, 4, (0, 6, 12), (40, 80, 160))):
+    for _D in _Ds:
+        RELPOS_SHORT_CASES += [_rel(f"lowered-shard-d{_D}-T{_T}-q{_o}+{_Tq}", _D, _T, _Tq, _o, 16, False, sels=(0, 3)) for _o in _offs]
+
 
 def attn_inputs(c):
     """Item tensors of an ATTN_CASES entry: q [B heads, F nq, D] for the 'cross' layout (the F frames of a sample share its keys) and

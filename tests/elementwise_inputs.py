@@ -1104,4 +1104,10 @@ for _outs in (("f32",), ("f16",), ("f32", "f16")):
     _add("pool", f"pool-2x6x10x68-{'+'.join(_outs)}", n=2, H=6, W=10, C=68, ld_in=72, outs=_outs)
 _add("pool", "pool-1x7x11x8-odd", n=1, H=7, W=11, C=8, ld_in=8, outs=("f32", "f16"))
 _add("pool", "pool-wrap", n=1, H=2, W=2 * 131075, C=68, ld_in=68, outs=("f32",), wrap=True)
+# `lowered`: the combinations the lowerings emit that no case above has (tests/record_paths.py): plain fp32 / fp16 tokens without a low-order
+# image, the shared-sample source with one; the fp32 -> fp16 cast without its second output and the fp16 -> fp32 copy without an activation
+for _B, _Bs, _ld, _dt, _sc, _lo in ((2, 0, 8, "f32", 1.0, "none"), (2, 0, 4, "f16", 1.0, "none"), (4, 2, 8, "f32", 0.5, "pad")):
+    _add("ncthw", f"lowered-ncthw-B{_B}src{_Bs}-ld{_ld}-{_dt}-lo_{_lo}", B=_B, Bsrc=_Bs, C=4, F=3, HW=35, ld=_ld, dt=_dt, scale=_sc, lo=_lo)
+for _s, _d in (("f32", "f16"), ("f16", "f32")):
+    _add("copy", f"lowered-copy-{_s}-{_d}-act0-plain", rows=37, cols=132, sdt=_s, ddt=_d, act=0, lo=False, form="plain")
 assert len({c["id"] for c in CASES}) == len(CASES)

@@ -555,6 +555,11 @@ for _D, _nq, _lens, _V, _var in [(64, 256, (154, 77), 1, "late"), (64, 256, (77,
                                  (64, 256, (77, 154), 1, "masked"), (64, 20, (24, 40), 1, "late"), (64, 20, (40, 24), 2, "late"),
                                  (64, 20, (24, 20), 2, "late"), (64, 64, (33, 32), 1, "late"), (40, 256, (77, 40), 2, "late")]:
     CASES.append(_case("two_role", f"roles-d{_D}-nq{_nq}-k{_lens[0]}+{_lens[1]}-v{_V}-{_var}", D=_D, nq=_nq, lens=_lens, V=_V, variant=_var, F=2, heads=2))
+# `lowered`: the combinations the lowerings emit that no case above has (tests/record_paths.py; tests/test_record_paths_cpu.py demands them):
+# the fused cross-attention on tile 0 with whole row tiles, and the two-role attention with ragged query blocks on the 4-wave and 1-wave kernels
+CASES.append(_case("xattn", "lowered-xattn-t0-n128-b2-r64-k7", tile=0, N=128, K=128, B=2, rows=64, Lc=7, wrap=False))
+for _nq in (64, 20):
+    CASES.append(_case("two_role", f"lowered-roles-d64-nq{_nq}-k154+77-v1-late", D=64, nq=_nq, lens=(154, 77), V=1, variant="late", F=2, heads=2))
 assert len({c["id"] for c in CASES}) == len(CASES)
 
 _BUILDERS = dict(tattn=_build_tattn, xattn=_build_xattn, two_role=_build_two_role)

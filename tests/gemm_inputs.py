@@ -667,8 +667,87 @@ def _build_offset(c):
     return b
 
 
+# -- `lowered`: one case per code path that a lowered program takes and no case above has (tests/record_paths.py is the key, ---------------
+# -- tests/test_record_paths_cpu.py the check that demands them; profiles/lowered_paths.txt names a deployed op for each) ------------------
+def _lowered_geo(s, bm):
+    """(kind, geo, cin, rows per bias batch, residual wrap) of a spec: two row tiles of the tile and — m_ragged — a remainder (8 x 8 images
+    where the row count must be whole tiles, 6 x 10 where it must not; clips of 5 frames, 7 stored in the halo layout)."""
+    kind, ragged, split = s["gather"], s["m_ragged"], s["fold"] != "-"
+    if kind == "plain":
+        M = 2 * bm + (36 if ragged else 0)
+        return dict(M=M), (200 if s["k_tail"] else 1024 if split else 128), M // 2 if ragged else bm // 2, M // 2 + 13
+    if kind in ("conv", "c8"):
+        H, W = (6, 10) if ragged else (8, 8)
+        geo = dict(image=(1, H, W), stride=s["stride"], up=s["up"], pad_after_only=s["i23"])
+        ho, wo = conv_out_hw(geo)
+        B = -(-2 * bm // (ho * wo)) + (1 if ragged else 0)
+        while (B * ho * wo % bm != 0) != bool(ragged):
+            B += 1
+        geo["image"] = (B, H, W)
+        return geo, (8 if kind == "c8" else 128 if split else 64), ho * wo, -(-B // 2) * ho * wo
+    HW = bm // 4 + 3 if ragged else bm // 2
+    Fr = 7 if s["i23"] else 5
+    return dict(clip=(2, Fr, HW), halo=s["i23"]), (384 if split else 128), 5 * HW, 5 * HW
+
+
+def _lowered_n(s):
+    """Two column tiles, or one and 48 columns (a multiple of 16: the GEGLU interleave; three quads past a 32-column block: ReLU leaves no
+    all-zero segment); tile 0: the width class the spec names."""
+    if s["tile"] == 0:
+        return {(128, 0): 256, (128, 1): 240, (64, 0): 192, (64, 1): 176}[(s["w"], s["n_ragged"])]
+    return 2 * BN[s["tile"]] if not s["n_ragged"] else BN[s["tile"]] + 48
+
+
+def _build_lowered(c):
+    """K: two 64-chunks (128; 9 / 3 taps x one or two chunks for the convolutions) without split-K.  With it the lowering's own policy
+    (Program.choose_tile) wants 16 k-tiles before it splits, so K is 1024 / 1152 and the case plans for just enough compute units that the
+    policy takes two splits of 8 / 9 k-tiles — the smallest split-K problem the lowering can emit."""
+    b, s = Built(c), c
+    tile, v = s["tile"], c["variant"]
+    bm = BM[tile]
+    geo, cin, rpb, wrap = _lowered_geo(s, bm)
+    kind, N, split = s["gather"], _lowered_n(s), (2 if s["fold"] != "-" else 1)
+    if kind == "plain":
+        a, X = _plain_operand(b, v, geo["M"], cin, c["seed"])
+        W = weight_like(v, (N, cin), c["seed"])
+    elif kind in ("conv", "c8"):
+        a, X = _conv_operand(b, v, geo["image"], cin, c["seed"], c8=kind == "c8")
+        W = weight_like(v, (N, cin, 3, 3), c["seed"])
+    else:
+        B, Fr, HW = geo["clip"]
+        X = operand_rows(v, B * Fr * HW, cin, c["seed"], clip=geo["clip"])
+        a = b.put(b.fenced(B * Fr * HW, cin, "f16"), X)
+        W = weight_like(v, (N, cin, 3, 1, 1), c["seed"])
+    M = out_rows(kind, geo)
+    cus = None
+    if split > 1:
+        tiles = -(-M // bm) * -(-N // (tile0_bn(N) if tile == 0 else BN[tile]))
+        cus = 2 * tiles + (1 if tile == 0 else 0)
+    r = _Run(b, "op", kind, a, X, W, geo, seed=c["seed"], tile=tile, out_dt="f32" if s["out"] else "f16", bias=s["bias"], rpb=rpb if s["rowbias"] else 0,
+             act=s["act"], res=bool(s["res"]), res_wrap=wrap if s["res_wrap"] != "-" else 0, geglu=s["epi"] == L.EPI_GEGLU, stats=s["epi"] == L.EPI_STATS,
+             out_lo=bool(s["out_lo"]), split=split, tickets=s["fold"] == "tickets", target_cus=cus)
+    op = r.emit()
+    assert (M % bm != 0) == bool(s["m_ragged"]) and M > bm and (op.i[30] > 0) == (s["res_wrap"] == "i30") and (kind != "plain" or (op.i[12] > 0) == (s["res_wrap"] == "i12"))
+    return b
+
+
+def _lowered_case(spec):
+    """spec: the fields of a GEMM path key, in the order of _LOWERED_FIELDS."""
+    s = dict(zip(_LOWERED_FIELDS, spec))
+    s["gather"] = {L.GATHER_PLAIN: "plain", L.GATHER_CONV3X3: "conv", L.GATHER_TCONV3: "tconv", L.GATHER_CONV3X3_C8: "c8"}[s["gather"]]
+    s["bias"] = {0: None, 1: "n", 2: "m"}[s["bias"]]
+    cid = "lowered-t%d%s-%s%s%s%s-%s%s%s-e%d-%s-a%d-b%s%s%s%s%s" % (
+        s["tile"], f"w{s['w']}" if s["tile"] == 0 else "", s["gather"], "-s2" if s["stride"] == 2 else "", "-up" if s["up"] else "", "-i23" if s["i23"] else "",
+        s["fold"].replace("-", "nosplit"), "-ktail" if s["k_tail"] else "", ("-mr" if s["m_ragged"] else "") + ("-nr" if s["n_ragged"] else ""), s["epi"],
+        "f32" if s["out"] else "f16", s["act"], s["bias"] or "0", "-rowbias" if s["rowbias"] else "", "-res" if s["res"] else "",
+        "-wrap_" + s["res_wrap"] if s["res_wrap"] != "-" else "", "-hilo" if s["out_lo"] else "")
+    # (GEGLU multiplies two results: with the marked columns' extra weight a product of two 3-sigma values in a 2^4 row and a 2^2 column passes
+    #  the fp16 range at K = 128, so those cases run `scaled`)
+    return _case("lowered", cid, variant="scaled" if s["epi"] == L.EPI_GEGLU else "marked", **s)
+
+
 _BUILDERS = dict(inst=_build_inst, tail=_build_tail, splitk=_build_splitk, feat=_build_feat, conv=_build_conv, c8=_build_c8, tconv=_build_tconv,
-                 reswrap=_build_reswrap, stats=_build_stats, twopass=_build_twopass, offset=_build_offset)
+                 reswrap=_build_reswrap, stats=_build_stats, twopass=_build_twopass, offset=_build_offset, lowered=_build_lowered)
 
 
 def build(case):
@@ -702,4 +781,265 @@ CASES += [_case("reswrap", "reswrap-conv-t0", kind="conv", tile=0, cin=64, split
 CASES += [_case("stats", f"stats-t{_t}-{_v}", tile=_t, variant=_v, out_lo=_t in (0, 11)) for _t, _v in ((0, "marked"), (8, "scaled"), (11, "marked"), (3, "scaled"))]
 CASES += [_case("twopass", "twopass-a_lo", which="a_lo"), _case("twopass", "twopass-weight_lo", which="weight_lo")]
 CASES += [_case("offset", f"offset-t{_t}", tile=_t, variant="offset") for _t in (0, 1, 12)]
+# the `lowered` family: (tile, tile 0's width, gather, stride, up, i[23], fold, K % 64 != 0, M ragged, N ragged, epilogue, out dtype, activation,
+# bias 0 / 1 along N / 2 along M, row bias, residual, residual wrap, hi + lo) — a split-K GEMM with a reduction launch is two entries: its
+# slab launch (fold "slab": the epilogue fields say how the slabs are folded, any will do) and the reduction's epilogue on tile 5
+_LOWERED_FIELDS = ("tile", "w", "gather", "stride", "up", "i23", "fold", "k_tail", "m_ragged", "n_ragged", "epi", "out", "act", "bias", "rowbias", "res",
+                   "res_wrap", "out_lo")
+_LOWERED = [
+    (0, 128, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (0, 128, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 1, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (0, 128, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (0, 128, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 128, 1, 1, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (0, 128, 1, 1, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (0, 128, 1, 1, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (0, 128, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 1, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 1, 1, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 1, 1, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 2, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 2, 0, 1, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 2, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 128, 2, 0, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 128, 2, 0, 0, 1, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 2, 0, 0, 1, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 3, 1, 0, 0, '-', 1, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 1, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 2, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 1, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, 'i12', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 2, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 1, 0, 1, 0, 0, 0, 1, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 1, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 1, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 1, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 1, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 1, 0, 0, 0, 2, 1, 0, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, 'slab', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 2, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 2, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 2, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 2, 0, 1, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 1, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (0, 64, 2, 0, 0, 1, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 2, 0, 0, 1, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (0, 64, 3, 1, 0, 0, '-', 1, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 3, 1, 0, 0, '-', 1, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (1, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 0, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 1, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 1, 0, 0, 'slab', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 1, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 1, 1, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 2, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (11, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (11, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (11, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (11, 0, 0, 0, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (11, 0, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 1, 1, 1, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 2, 0, 0, 1, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 1, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 2, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 1, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, 'i12', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 0, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (12, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 1, 1, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (12, 0, 0, 0, 0, 0, '-', 0, 1, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (12, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (12, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (12, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (12, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (12, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 1, 0, '-', 0),
+    (12, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (12, 0, 1, 2, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (12, 0, 1, 2, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (12, 0, 1, 2, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (12, 0, 1, 2, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, 'i30', 0),
+    (12, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (12, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (12, 0, 2, 0, 0, 1, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (12, 0, 2, 0, 0, 1, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (2, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 0, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (2, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (2, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (2, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (2, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (2, 0, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 1, 1, 1, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 1, 1, 1, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 1, 1, 1, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 1, 2, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 1, 2, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (2, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (2, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (2, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 0, 0, 'slab', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 0, 0, 'slab', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 1, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 1, 0, 'slab', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 1, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 2, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 2, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 0, 1, 3, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, 'slab', 0, 1, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, 'slab', 0, 1, 1, 0, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, 'slab', 0, 1, 1, 0, 0, 0, 1, 0, 1, '-', 0),
+    (5, 0, 0, 0, 0, 0, 'slab', 0, 1, 1, 0, 0, 0, 1, 0, 1, '-', 1),
+    (5, 0, 0, 0, 0, 0, 'slab', 0, 1, 1, 0, 0, 0, 1, 1, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, 'slab', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, 'slab', 0, 1, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, 'slab', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 1, 1, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 1, 1, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 1, 1, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 0, 'slab', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 1, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 1, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 1, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 1, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 1, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (8, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 1, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (8, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 1, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 1, 1, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 1, 1, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 2, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 2, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 1, 0, 1, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 1, 1, 0, 0, 0, 1, 1, 0, '-', 0),
+    (9, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+]
+CASES += [_lowered_case(_s) for _s in _LOWERED]
 assert len({c["id"] for c in CASES}) == len(CASES)

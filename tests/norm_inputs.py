@@ -383,17 +383,17 @@ def _build_strips(c, ncu):
     b = Built(c)
     n_inst, rows, C = c["n_inst"], c["rows"], c["C"]
     M = n_inst * rows
-    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, "f32", c["seed"])
+    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, c.get("dt", "f32"), c["seed"])
     gamma, beta = affine(C, c["seed"])
     # The strips are fp32 sums of x and x^2 over 32 rows (the ABI of T2V_EPI_STATS), so the single-pass variance they give carries at least
     # 2^-24 (1 + (mean / std)^2) = 6e-5 at mean / std = 32, 3e-5 in the output, whatever the fold does: beyond the hi + lo figure by the
     # number format alone.  The `offset` rows therefore run without a low-order output and are held to the fp16 figure.
-    lo = c["variant"] != "offset"
+    lo, dt = c.get("lo", c["variant"] != "offset"), c.get("dt", "f32")
     st = b.P.alloc(M // 32, 2 * C, "f32")
     out = b.fenced(M, 2 * C if lo else C, "f16")
-    gop, y = _identity_gemm(b, "l", "plain", X, "f32", stats=st, allow_splitk=False)
+    gop, y = _identity_gemm(b, "l", "plain", X, dt, stats=st, allow_splitk=False)
     assert gop.i[16] == L.EPI_STATS and gop.meta["stats"] == 1 and gop.meta["split"] == 1
-    b.exact.append(("stored x", y, X.float()))
+    b.exact.append(("stored x", y, X.float() if dt == "f32" else X.half()))
     op = b.P.groupnorm("gn", y, b.weight("g", gamma), b.weight("be", beta), out.col_slice(0, C), n_inst=n_inst, eps=EPS, silu=True, lo=lo, stats=st)
     wide = rows // 32 * (C // GROUPS) > 1024
     assert op.i[8] == 3 and op.p[6].space == "arena" and op.i[17] == C and wide == c["wide"] and len(b.P.ops) == 2
@@ -406,7 +406,7 @@ def _build_strips(c, ncu):
 def _build_shard(c, ncu):
     b = Built(c)
     P, C, fr, size, total, dt = b.P, c["C"], c["frame_rows"], c["size"], c["frames"], c["dt"]
-    P.target_cus = 1          # several statistics workgroups per part
+    P.target_cus = c.get("target_cus", 1)          # 1: several statistics workgroups per part
     specs = [TShardSpec.make(total, size, q) for q in range(size)]
     prow = [s.frames * fr for s in specs]
     assert len(set(prow)) > 1, "the slices must be uneven"
@@ -424,15 +424,15 @@ def _build_shard(c, ncu):
         Xp = list(X.split(prow))
     gamma, beta = affine(C, c["seed"])
     g, be = b.weight("g", gamma), b.weight("be", beta)
-    halo, strips, lo = c["halo"], c["strips"], not c["halo"]
+    halo, strips, lo, silu = c["halo"], c["strips"], c.get("lo", not c["halo"]), c.get("silu", True)
     xs, outs, sts, raws = [], [], [], []
     off = 0
     for q in range(size):
         before, after = (fr if q > 0 else 0, fr if q + 1 < size else 0) if halo else (0, 0)
         if strips:
             sts.append(P.alloc(prow[q] // 32, 2 * C, "f32"))
-            outs.append(b.fenced(prow[q], 2 * C, "f16"))
-            gop, y = _identity_gemm(b, f"l{q}", "plain", Xp[q], "f32", stats=sts[q], allow_splitk=False)
+            outs.append(b.fenced(prow[q], 2 * C if lo else C, "f16"))
+            gop, y = _identity_gemm(b, f"l{q}", "plain", Xp[q], dt, stats=sts[q], allow_splitk=False)
             assert gop.i[16] == L.EPI_STATS
             xs.append(y)
         elif halo:
@@ -444,11 +444,11 @@ def _build_shard(c, ncu):
         else:
             xs.append(b.fenced(prow[q], C, dt))
             b.put(xs[q], Xp[q])
-            outs.append(b.fenced(prow[q], 2 * C, "f16"))
+            outs.append(b.fenced(prow[q], 2 * C if lo else C, "f16"))
         off += prow[q]
     for q in range(size):
         o = outs[q].row_slice(fr, fr + prow[q]) if halo else outs[q].col_slice(0, C)
-        P.groupnorm(f"p{q}", xs[q], g, be, o, n_inst=1, eps=EPS, silu=True, shard=specs[q], lo=lo, stats=sts[q] if strips else None,
+        P.groupnorm(f"p{q}", xs[q], g, be, o, n_inst=1, eps=EPS, silu=silu, shard=specs[q], lo=lo, stats=sts[q] if strips else None,
                     halo_raw=raws[q] if halo else None)
     gn = [op for op in P.ops if op.kind == L.OP_GROUPNORM]          # p0.stats, p0.apply, p1.stats, ...
     assert len(gn) == 2 * size
@@ -463,11 +463,11 @@ def _build_shard(c, ncu):
         assert (st_ops[q].p[6].space == "arena") == strips and (ap_ops[q].i[21], ap_ops[q].i[22]) == (before, after)
         sl = slice(off - before, off + prow[q] + after)
         hi = outs[q].row_slice(fr - before, fr + prow[q] + after) if halo else outs[q].col_slice(0, C)
-        full = groupnorm_ref(X, gamma, beta, 1, GROUPS, EPS, True)
-        tol, et = b.hilo_tol(lo, X, gamma, beta, 1, GROUPS, True, full)
+        full = groupnorm_ref(X, gamma, beta, 1, GROUPS, EPS, silu)
+        tol, et = b.hilo_tol(lo, X, gamma, beta, 1, GROUPS, silu, full)
         b.outs.append(dict(name=f"p{q}", hi=hi, lo=outs[q].col_slice(C, 2 * C) if lo else None, ref=full[sl], n_inst=1, groups=GROUPS, tol=tol, e_torch=et))
         off += prow[q]
-    b.probs.append(dict(name="clip", X=X, gamma=gamma, beta=beta, n_inst=1, groups=GROUPS, silu=True, tol=TOL_HILO if lo else TOL_F16, parts=prow))
+    b.probs.append(dict(name="clip", X=X, gamma=gamma, beta=beta, n_inst=1, groups=GROUPS, silu=silu, tol=TOL_HILO if lo else TOL_F16, parts=prow))
     gemms = [op for op in P.ops if op.kind == L.OP_GEMM]
     P.ops = gemms + st_ops + ap_ops                                   # the collectives are the test's: one scratch, every part's slot filled
     b.path = f"OP_GROUPNORM i[8]=1 x{size} then i[8]=2 x{size}" + (" strips (p[6])" if strips else "") + (" halo i[21]/i[22]" if halo else "")
@@ -567,7 +567,229 @@ def _build_lnfused(c, ncu):
     return b
 
 
-_BUILDERS = dict(gn=_build_gn, strips=_build_strips, shard=_build_shard, epi=_build_epi, splitk=_build_splitk, ln=_build_ln, lnfused=_build_lnfused)
+# -- `lowered`: one case per code path that a lowered program takes and no case above has (tests/record_paths.py is the key, ---------------
+# -- tests/test_record_paths_cpu.py the check; profiles/lowered_paths.txt names a deployed op for each) ------------------------------------
+def _build_lowered_gn(c, ncu):
+    """Stand-alone OP_GROUPNORM, phase 0, ONE record: launch form x input dtype x SiLU x low-order image x cast output (x its low-order
+    image) x rows per thread of the cooperative kernel x tagged records / grid barrier x the column loop (C = 2560: more than 256 column
+    vectors).  C = 640 otherwise (the single-launch kernel needs C / groups % 4 == 0).  The cooperative cases cannot be smaller: the launcher
+    picks KR as the first count whose grid fits the device, so KR > 4 needs a tensor that overflows the device at every smaller count
+    (256 workgroups x 512 threads x KR rows x 8 channels).  `coop-fallback`: the record asks for the cooperative kernel and no KR fits —
+    two statistics blocks per instance (the lowering planning for one compute unit) against 485 rows = three chunks at KR = 20."""
+    b = Built(c)
+    P, form, dt, silu, lo, cast, barrier = b.P, c["form"], c["dt"], c["silu"], c["lo"], c["cast"], c["barrier"]
+    C = 2560 if c["cols_loop"] else 640
+    n_inst = 64 if (form == "cooperative" and not c["cols_loop"]) else 2
+    rows = 101
+    if form == "cooperative":
+        rows = rows_for_kr(c["kr"], n_inst, C, ncu, COOP_KRS, True)
+    elif form == "coop-fallback":
+        P.target_cus, rows = 1, 485
+    P.gn_coop = form in ("cooperative", "coop-fallback")
+    P.gn_fused_slice_bytes = 1 << 30 if form == "single_launch" else 0
+    P.gn_fused_total_bytes = 1 << 30
+    M = n_inst * rows
+    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, dt, c["seed"])
+    gamma, beta = affine(C, c["seed"])
+    x = b.fenced(M, C, dt)
+    b.put(x, X)
+    out = b.fenced(M, 2 * C if lo else C, "f16")
+    cbuf = b.fenced(M, 2 * C if cast == 2 else C, "f16") if cast else None
+    op = P.groupnorm("gn", x, b.weight("g", gamma), b.weight("be", beta), out.col_slice(0, C), n_inst=n_inst, eps=EPS, silu=silu, lo=lo, cast=cbuf,
+                     cast_lo=cast == 2)
+    assert len(P.ops) == 1 and op.kind == L.OP_GROUPNORM and op.i[8] == 0 and op.i[12] == (form == "single_launch") and op.i[15] == int(P.gn_coop)
+    assert op.i[16] == int(lo) and (op.p[8].space == "arena") == bool(cast) and (op.i[20] != 0) == (cast == 2)
+    nblk = -(-rows // op.i[11])
+    kr = coop_chunking(rows, n_inst, C // 8, ncu, nblk, COOP_KRS)[0] if P.gn_coop else 0
+    assert kr == (c["kr"] if form == "cooperative" else 0), (kr, rows, nblk)
+    if form == "cooperative":
+        assert op.p[7].space == "arena" and op.i[18] > 0
+        if barrier:
+            op.p[7], op.i[18] = NULL, 0
+        b.kr = kr
+    b.expect("gn", out.col_slice(0, C), out.col_slice(C, 2 * C) if lo else None, X, gamma, beta, n_inst, GROUPS, silu)
+    if cast:
+        hi = X.half()
+        b.exact.append(("cast", cbuf.col_slice(0, C), hi))
+        if cast == 2:
+            b.exact.append(("cast lo", cbuf.col_slice(C, 2 * C), (X.float() - hi.float()).half()))
+    b.path = f"OP_GROUPNORM i[8]=0 {form} rows={rows} C={C} {dt} silu={int(silu)} lo={int(lo)} cast={cast}" + (" barrier" if barrier else "")
+    return b
+
+
+def _chain_gemm(b, name, kind, X, out_dt, *, seed, geo=None, stride=1, halo=False, bias=True, rpb=0, res=True, res_wrap=0, k_extra=0, dead=False, **kw):
+    """_identity_gemm with the epilogue terms the deployed GEMMs carry.  The product is fp16(X) exactly (identity weights: on the centre
+    tap of a convolution — stride 2 reads the even pixels of an image four times the size, the halo layout the interior frames — and zero
+    weights against every other operand value, which is randn); the epilogue then adds a bias, a row bias per `rpb` rows and a residual in
+    fp32, in the kernels' order (t2v_kernels.h t2v_epilogue_rows, norm.hip splitk_gn_kernel).  Each addition is one IEEE fp32 operation, so
+    the value the norm sees is reproduced bit for bit on the CPU: X' = ((fp16(X) + bias) + rowbias) + residual, residual = X - (...) in
+    fp32 where there is one (X' = X up to one rounding), else the operand is fp16(X - the bias terms) and X' = X up to that rounding.
+    Returns (op, y window, X' in float64): the reference of the norm is taken from X', the stored tensor must equal it bit for bit."""
+    P = b.P
+    M, C = X.shape
+    g = torch.Generator().manual_seed(seed + 5)
+    eye = torch.eye(C)
+    rnd = lambda *shape: torch.randn(*shape, generator=g).half()
+    bv = 0.5 * torch.randn(C, generator=g) if bias else None
+    rbv = 0.5 * torch.randn(M // rpb, C, generator=g) if rpb else None
+    # without a residual to close the gap the operand is fp16(X - bias terms): X' = X up to that rounding, and the designed rows keep their weight
+    pre = X.float()
+    if not res:
+        pre = pre - (bv if bias else 0.0) - (rbv[torch.arange(M) // rpb] if rpb else 0.0)
+    hi = pre.half()
+    if kind == "conv":
+        Fr, H, W = geo
+        n_img = M // (H * W)
+        w4 = torch.zeros(C, C, 3, 3)
+        w4[:, :, 1, 1] = eye
+        Wt, K, gather = pk.conv3x3(w4).half(), 9 * C, L.GATHER_CONV3X3
+        A = rnd(n_img, stride * H, stride * W, C)
+        A[:, ::stride, ::stride] = hi.view(n_img, H, W, C)
+        A = A.reshape(-1, C)
+        conv = dict(Hin=stride * H, Win=stride * W, Cin=C, stride=stride, up=0, Hout=H, Wout=W)
+    elif kind == "tconv":
+        Fr, H, W = geo
+        HW, clips = H * W, M // (Fr * H * W)
+        w5 = torch.zeros(C, C, 3, 1, 1)
+        w5[:, :, 1, 0, 0] = eye
+        Wt, K, gather, conv = pk.tconv3(w5).half(), 3 * C, L.GATHER_TCONV3, dict(F=Fr, HW=HW, Cin=C)
+        A = hi
+        if halo:
+            A = rnd(clips, Fr + 2, HW, C)
+            A[:, 1:-1] = hi.view(clips, Fr, HW, C)
+            A = A.reshape(-1, C)
+    else:
+        Wt, K, gather, conv = torch.cat([eye, torch.zeros(C, k_extra)], dim=1).half(), C + k_extra, L.GATHER_PLAIN, None
+        A = hi if not k_extra else torch.cat([hi, rnd(M, k_extra)], dim=1)
+    a = P.alloc(A.shape[0], A.shape[1], "f16")
+    b.put(a, A)
+    v = hi.float()
+    bias_ref, rb, r = NULL, None, None
+    if bias:
+        bias_ref, v = b.weight(name + ".bias", bv), v + bv
+    if rpb:
+        assert M % rpb == 0
+        rb = P.alloc(M // rpb, C, "f32")
+        b.put(rb, rbv)
+        v = v + rbv[torch.arange(M) // rpb]
+    if res:
+        rr = res_wrap or M
+        rv = (X.float() - v)[:rr]
+        r = P.alloc(rr, C, "f32")
+        b.put(r, rv)
+        v = v + (torch.cat([rv, rv[:M - rr]]) if res_wrap else rv)
+    y = b.fenced(M, C, out_dt, window=(0, 0) if dead else None)
+    op = P.gemm(name, a, b.weight(name + ".w", Wt), C, K, y, bias=bias_ref, gather=gather, conv=conv, rowbias=rb, rows_per_batch=rpb, residual=r,
+                halo=halo, m=M, res_wrap=res_wrap, **kw)
+    assert (op.p[2].space != "null") == bool(bias) and (op.p[3].space != "null" or "ln" in kw) == bool(rpb or "ln" in kw) and (op.p[4].space != "null") == bool(res)
+    return op, y, v.double()
+
+
+# row geometry of a fused-norm case: (frames, H, W) of one instance against the tile's rows `bm`: half a tile, a whole tile, 1.5 tiles
+# (straddle) or — M ragged — 1.25 tiles; images of 8 / 12 / 16 columns
+def _epi_rows(seam, ragged, bm):
+    return {"half": bm // 2, "whole": bm, "straddle": bm + (bm // 4 if ragged else bm // 2)}[seam]
+
+
+def _build_lowered_epi(c, ncu):
+    """T2V_EPI_GN without split-K on the combinations deployed: tile x gather (stride 2, halo frames) x output dtype x bias / row bias /
+    residual x SiLU x low-order image x dead result x how the instances meet the row tiles x ragged M / N.  C: two column tiles of the tile,
+    or 320 against 128- / 256-wide tiles (ragged).  `chunked`: more tiles than the device holds at once (the lowering's bound: one
+    workgroup of a gemm2 tile per compute unit) — ONE column tile and 256 row tiles + 2: it cannot be smaller."""
+    b = Built(c)
+    P, kind, tile, seam, ragged, dead, lo, silu = b.P, c["kind"], c["tile"], c["seam"], c["m_ragged"], c["x_dead"], c["lo"], c["silu"]
+    bm, bn = L.GEMM_TILES[tile].bm, L.GEMM_TILES[tile].bn
+    C = 320 if c["n_ragged"] else (bn if c["chunked"] and bn % GROUPS == 0 and bn >= 256 else 2 * bn)
+    rows = _epi_rows(seam, ragged, bm)
+    n_inst = (5 if ragged else 4) if seam == "half" else 2
+    if kind == "tconv":          # instances are frames of 5-frame clips
+        n_inst = 5 if (seam == "whole" or ragged) else 10
+    if c["chunked"]:
+        n_inst = 256 * L.GEMM_TILES[tile].per_cu * bm // rows + 2
+        if kind == "tconv":
+            n_inst = -(-n_inst // 5) * 5
+    M = n_inst * rows
+    assert (M % bm != 0) == bool(ragged), (M, bm)
+    geo = (5 if kind == "tconv" else 1, rows // 16 if rows % 16 == 0 else rows // 8, 16 if rows % 16 == 0 else 8)
+    assert geo[1] * geo[2] == rows
+    P.force_tile = tile
+    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, "f32", c["seed"])
+    gamma, beta = affine(C, c["seed"])
+    full = b.fenced(M, 2 * C if lo else C, "f16")
+    op, y, X1 = _chain_gemm(b, "g", kind, X, c["out"], seed=c["seed"], geo=geo, stride=c["stride"], halo=c["halo"], rpb=rows if c["rowbias"] else 0,
+                            res=c["res"], dead=dead, allow_splitk=False)
+    out = full.col_slice(0, C)
+    fused = P.groupnorm("gn", y, b.weight("g", gamma), b.weight("be", beta), out, n_inst=n_inst, eps=EPS, silu=silu, lo=lo,
+                        gb=b.weight("gb", torch.cat([gamma, beta])), x_dead=dead)
+    assert fused is op and op.i[16] == L.EPI_GN and len(P.ops) == 1 and op.i[19] == 1, "the norm did not become the GEMM's epilogue"
+    assert (op.i[24], op.i[27], op.i[28], op.i[29], op.i[22]) == (rows, int(lo), GROUPS, int(dead), tile)
+    if not dead:
+        b.exact.append(("stored x", y, X1.float() if c["out"] == "f32" else X1.half()))
+    b.expect("gn", out, full.col_slice(C, 2 * C) if lo else None, X1, gamma, beta, n_inst, GROUPS, silu)
+    b.path = f"EPI_GN tile {tile} {kind} M={M} C={C} rows={rows} ({seam}) dead={int(dead)} lo={int(lo)}" + (" chunked" if c["chunked"] else "")
+    return b
+
+
+def _build_lowered_splitk(c, ncu):
+    """splitk_gn_kernel (the reduction launch of a split-K GEMM with T2V_EPI_GN) on the epilogue combinations deployed, at the rows-per-thread
+    counts deployed: the launcher picks KR as the first count whose grid fits the device, so the row count is the smallest that overflows
+    it at every smaller count (rows_for_kr) — it cannot be smaller."""
+    b = Built(c)
+    P, C, dead, lo, silu, n_inst = b.P, 640, c["x_dead"], c["lo"], c["silu"], 64
+    rows = 20 if c["kr"] == 1 else rows_for_kr(c["kr"], n_inst, C, ncu, SPLITK_KRS, False)
+    if rows % coop_chunking(rows, n_inst, C // 8, ncu, 1 << 30, SPLITK_KRS)[1] == 0:
+        rows += 1
+    rows += rows % 2
+    M = n_inst * rows
+    P.force_tile = 5
+    P.target_cus = max(256, 4 * -(-M // 128) * (C // 128))          # the lowering splits K only where the tiles leave compute units idle
+    X = gn_input(c["variant"], n_inst, rows, C, GROUPS, "f32", c["seed"])
+    gamma, beta = affine(C, c["seed"])
+    full = b.fenced(M, 2 * C if lo else C, "f16")
+    op, y, X1 = _chain_gemm(b, "g", "plain", X, c["out"], seed=c["seed"], rpb=rows // 2 if c["rowbias"] else 0, res=c["res"], k_extra=2048 - C, dead=dead)
+    out = full.col_slice(0, C)
+    fused = P.groupnorm("gn", y, b.weight("g", gamma), b.weight("be", beta), out, n_inst=n_inst, eps=EPS, silu=silu, lo=lo,
+                        gb=b.weight("gb", torch.cat([gamma, beta])), x_dead=dead)
+    assert fused is op and op.i[16] == L.EPI_GN and op.meta["split"] > 1 and len(P.ops) == 1
+    kr, rc, nchunk = coop_chunking(rows, n_inst, C // 8, ncu, 1 << 30, SPLITK_KRS)
+    assert kr == c["kr"], (kr, rows)
+    b.kr = kr
+    if not dead:
+        b.exact.append(("stored x", y, X1.float() if c["out"] == "f32" else X1.half()))
+    b.expect("gn", out, full.col_slice(C, 2 * C) if lo else None, X1, gamma, beta, n_inst, GROUPS, silu)
+    b.path = f"EPI_GN split={op.meta['split']} rows={rows} x {n_inst} dead={int(dead)} lo={int(lo)}"
+    return b
+
+
+def _build_lowered_ln(c, ncu):
+    """The fused LayerNorm outputs (i[8] = 1: whole rows in the tile; 2: across column tiles) with the bias and the residual the deployed
+    Linears carry: two row tiles (+ 36 rows), N of two column tiles (320 against 256-wide tiles where N is ragged).  `chunked`: more tiles
+    than the lowering's co-residency bound holds, so that the launch is cut into row chunks — it cannot be smaller."""
+    b = Built(c)
+    tile, mode = c["tile"], c["mode"]
+    geo = L.GEMM_TILES[tile]
+    N = geo.bn if mode == 1 else (320 if c["n_ragged"] else 2 * geo.bn)
+    tiles_m = 2
+    if c["chunked"]:
+        cap = min(geo.per_cu * 256, L.GN_PART_BYTES // (geo.bm * 16))
+        tiles_m = cap // -(-N // geo.bn) + 1
+    M = tiles_m * geo.bm + (36 if c["m_ragged"] else 0)
+    b.P.force_tile = tile
+    X = ln_input(c["variant"], M, N, c["seed"])
+    gamma, beta = affine(N, c["seed"])
+    ln_out = b.fenced(M, N, "f16")
+    wrap = M // 2 + 13 if c["wrap"] else 0
+    op, y, X1 = _chain_gemm(b, "g", "plain", X, "f32", seed=c["seed"], res=c["res"], res_wrap=wrap, allow_splitk=False,
+                            ln=(b.weight("gb", torch.cat([gamma, beta])), b.weight("g", gamma), b.weight("be", beta), ln_out, EPS))
+    assert op.i[22] == tile and op.i[8] == mode and len(b.P.ops) == 1 and (op.i[12] > 0) == bool(wrap), "the LayerNorm did not become the GEMM's epilogue"
+    b.exact.append(("stored x", y, X1.float()))
+    b.expect("ln", ln_out, None, X1, gamma, beta, M, 1, False)
+    b.path = f"GEMM tile {tile} i[8]={mode} {M}x{N}" + (" chunked" if c["chunked"] else "") + (" res_wrap" if wrap else "")
+    return b
+
+
+_BUILDERS = dict(gn=_build_gn, strips=_build_strips, shard=_build_shard, epi=_build_epi, splitk=_build_splitk, ln=_build_ln, lnfused=_build_lnfused, lowered_gn=_build_lowered_gn, lowered_epi=_build_lowered_epi, lowered_splitk=_build_lowered_splitk,
+                 lowered_ln=_build_lowered_ln)
 
 
 def build(case, ncu=None):
@@ -634,4 +856,230 @@ for _v in ("distinct", "offset"):
         CASES.append(_case("lnfused", f"lnfused-t{_tile}-397x320", _v, M=397, N=320, tile=_tile, mode=1, seed=610 + _tile))
     for _tile, _N in ((0, 640), (3, 768), (5, 1280), (9, 512), (12, 1280)):
         CASES.append(_case("lnfused", f"lnx-t{_tile}-397x{_N}", _v, M=397, N=_N, tile=_tile, mode=2, seed=620 + _tile))
+# `lowered` LayerNorm paths: row counts that are whole workgroups of 4 rows (the cases above are ragged), with and without the grid-stride walk
+for _C, _cap in ((320, 0), (768, 0), (1280, 0), (320, 2), (768, 2)):
+    CASES.append(_case("ln", f"lowered-ln-76x{_C}" + (f"-cap{_cap}" if _cap else ""), "distinct", M=76, C=_C, cap=_cap, seed=640 + _C + _cap))
+# the `lowered` family, stand-alone GroupNorm records: (launch form, input dtype, SiLU, low-order image, cast output 0 / 1 / 2 = with its low-order
+# image, rows per thread of the cooperative kernel, grid barrier instead of tagged records, column loop)
+_LOWERED_GN = [
+    ('coop-fallback', 'f16', 1, 0, 0, 0, 0, 0),
+    ('coop-fallback', 'f32', 0, 0, 0, 0, 0, 0),
+    ('coop-fallback', 'f32', 0, 1, 0, 0, 0, 0),
+    ('coop-fallback', 'f32', 1, 0, 0, 0, 0, 0),
+    ('coop-fallback', 'f32', 1, 0, 2, 0, 0, 0),
+    ('coop-fallback', 'f32', 1, 0, 2, 0, 0, 1),
+    ('cooperative', 'f16', 1, 0, 0, 4, 0, 0),
+    ('cooperative', 'f16', 1, 0, 0, 4, 1, 0),
+    ('cooperative', 'f16', 1, 0, 0, 8, 0, 0),
+    ('cooperative', 'f16', 1, 0, 0, 12, 0, 0),
+    ('cooperative', 'f16', 1, 0, 0, 16, 0, 0),
+    ('cooperative', 'f32', 0, 0, 0, 4, 0, 0),
+    ('cooperative', 'f32', 0, 0, 0, 8, 0, 0),
+    ('cooperative', 'f32', 0, 0, 0, 16, 0, 0),
+    ('cooperative', 'f32', 0, 1, 0, 8, 0, 0),
+    ('cooperative', 'f32', 0, 1, 0, 16, 0, 0),
+    ('cooperative', 'f32', 1, 0, 0, 4, 0, 0),
+    ('cooperative', 'f32', 1, 0, 0, 4, 0, 1),
+    ('cooperative', 'f32', 1, 0, 0, 4, 1, 0),
+    ('cooperative', 'f32', 1, 0, 0, 8, 0, 0),
+    ('cooperative', 'f32', 1, 0, 0, 8, 0, 1),
+    ('cooperative', 'f32', 1, 0, 0, 12, 0, 0),
+    ('cooperative', 'f32', 1, 0, 0, 16, 0, 0),
+    ('cooperative', 'f32', 1, 0, 0, 20, 0, 0),
+    ('cooperative', 'f32', 1, 0, 0, 20, 0, 1),
+    ('cooperative', 'f32', 1, 0, 1, 4, 0, 0),
+    ('cooperative', 'f32', 1, 0, 2, 12, 0, 0),
+    ('cooperative', 'f32', 1, 0, 2, 16, 0, 0),
+    ('single_launch', 'f16', 1, 0, 0, 0, 0, 0),
+    ('single_launch', 'f32', 0, 0, 0, 0, 0, 0),
+    ('single_launch', 'f32', 1, 0, 0, 0, 0, 0),
+    ('single_launch', 'f32', 1, 0, 0, 0, 0, 1),
+    ('single_launch', 'f32', 1, 0, 1, 0, 0, 0),
+    ('single_launch', 'f32', 1, 0, 2, 0, 0, 1),
+    ('three_launch', 'f16', 1, 0, 0, 0, 0, 0),
+    ('three_launch', 'f32', 1, 0, 0, 0, 0, 0),
+]
+for _form, _dt, _gsilu, _lo, _cast, _kr, _bar, _cl in _LOWERED_GN:
+    CASES.append(_case("lowered_gn", f"lowered-gn-{_form}-{_dt}{'-silu' if _gsilu else ''}{'-lo' if _lo else ''}{('', '-cast', '-cast+lo')[_cast]}"
+                       f"{'-KR' + str(_kr) if _kr else ''}{'-barrier' if _bar else ''}{'-C2560' if _cl else ''}", "marked", form=_form, dt=_dt, silu=bool(_gsilu),
+                       lo=bool(_lo), cast=_cast, kr=_kr, barrier=bool(_bar), cols_loop=_cl, seed=700 + len(CASES)))
+# ... sharded phases 1 / 2 and the strip-fed phase 3: halo rows on both sides (three parts), fp16 inputs, no SiLU, no low-order image, parts of
+# one statistics block (4 + 2 rows), the column loop (C = 2560), strips folded by a workgroup (C = 1280: 26 strips x 40 channels > 1024; 4160
+# rows: one row more or less in n shows only against the hi + lo figure, so those two keep the low-order image).  (`x_dead` in the
+# fused families below: the result is not stored, as `dead` above, but the tensor is the fp32 chain, not an fp16 one)
+for _id, _kw in (("3parts-halo-f32", dict(C=320, frame_rows=20, frames=5, size=3, dt="f32", halo=True, strips=False)),
+                 ("3parts-halo-f16", dict(C=320, frame_rows=20, frames=5, size=3, dt="f16", halo=True, strips=False)),
+                 ("2parts-f32-nolo", dict(C=320, frame_rows=24, frames=3, size=2, dt="f32", halo=False, strips=False, lo=False)),
+                 ("2parts-f32-nosilu-lo", dict(C=320, frame_rows=24, frames=3, size=2, dt="f32", halo=False, strips=False, lo=True, silu=False)),
+                 ("2parts-f32-nosilu-nolo", dict(C=320, frame_rows=24, frames=3, size=2, dt="f32", halo=False, strips=False, lo=False, silu=False)),
+                 ("2parts-4+2rows-f32-nosilu", dict(C=320, frame_rows=2, frames=3, size=2, dt="f32", halo=False, strips=False, lo=False, silu=False, target_cus=256)),
+                 ("2parts-4+2rows-f32", dict(C=320, frame_rows=2, frames=3, size=2, dt="f32", halo=False, strips=False, lo=False, target_cus=256)),
+                 ("2parts-4+2rows-f16", dict(C=320, frame_rows=2, frames=3, size=2, dt="f16", halo=False, strips=False, lo=False, target_cus=256)),
+                 ("2parts-f16-nolo", dict(C=320, frame_rows=24, frames=3, size=2, dt="f16", halo=False, strips=False, lo=False)),
+                 ("2parts-C2560-f32", dict(C=2560, frame_rows=24, frames=3, size=2, dt="f32", halo=False, strips=False, lo=False)),
+                 ("3parts-strips-wg-f32", dict(C=1280, frame_rows=832, frames=5, size=3, dt="f32", halo=False, strips=True, lo=True)),
+                 ("3parts-strips-wg-f16", dict(C=1280, frame_rows=832, frames=5, size=3, dt="f16", halo=False, strips=True, lo=True)),
+                 ("3parts-strips-f16", dict(C=320, frame_rows=32, frames=5, size=3, dt="f16", halo=False, strips=True, lo=True))):
+    CASES.append(_case("shard", "lowered-shard-" + _id, "distinct" if _kw["frame_rows"] < 3 else "marked", seed=800 + len(CASES), **_kw))
+CASES.append(_case("strips", "lowered-strips-wave-3x96x320-f16", "marked", n_inst=3, rows=96, C=320, wide=False, dt="f16", lo=False, seed=303))
+# ... T2V_EPI_GN without split-K: (tile, gather, stride, halo frames, M ragged, N ragged, out dtype, row bias, residual, SiLU, low-order image,
+# dead result, how instances meet the row tiles, more tiles than the device holds)
+_LOWERED_EPI = [
+    (0, 'conv', 1, 0, 0, 0, 'f16', 1, 0, 1, 0, 1, 'half', 0),
+    (0, 'conv', 1, 0, 0, 0, 'f32', 1, 0, 1, 0, 1, 'half', 0),
+    (0, 'conv', 1, 0, 1, 0, 'f16', 1, 0, 1, 0, 1, 'half', 0),
+    (0, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 0, 0, 0, 'straddle', 0),
+    (0, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 0, 0, 0, 'whole', 0),
+    (0, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'straddle', 0),
+    (0, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'half', 0),
+    (0, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'whole', 0),
+    (0, 'plain', 1, 0, 1, 0, 'f32', 0, 1, 0, 0, 0, 'straddle', 0),
+    (0, 'plain', 1, 0, 1, 0, 'f32', 0, 1, 1, 0, 0, 'half', 0),
+    (0, 'tconv', 1, 0, 0, 0, 'f16', 0, 0, 1, 0, 1, 'straddle', 0),
+    (0, 'tconv', 1, 0, 0, 0, 'f16', 0, 0, 1, 0, 1, 'whole', 0),
+    (0, 'tconv', 1, 0, 0, 0, 'f32', 0, 0, 1, 0, 1, 'straddle', 0),
+    (0, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 0, 0, 'half', 0),
+    (0, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 0, 0, 'whole', 0),
+    (0, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'half', 0),
+    (0, 'tconv', 1, 0, 1, 0, 'f16', 0, 0, 1, 0, 1, 'straddle', 0),
+    (0, 'tconv', 1, 0, 1, 0, 'f32', 0, 1, 0, 0, 0, 'half', 0),
+    (0, 'tconv', 1, 1, 0, 0, 'f32', 0, 1, 0, 0, 0, 'half', 0),
+    (0, 'tconv', 1, 1, 1, 0, 'f32', 0, 1, 0, 0, 0, 'half', 0),
+    (11, 'conv', 1, 0, 0, 0, 'f16', 1, 0, 1, 0, 1, 'whole', 0),
+    (11, 'conv', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'whole', 0),
+    (11, 'conv', 2, 0, 0, 0, 'f32', 0, 0, 1, 0, 0, 'whole', 0),
+    (11, 'conv', 2, 0, 0, 0, 'f32', 0, 0, 1, 0, 0, 'whole', 1),
+    (11, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 0, 0, 0, 'whole', 0),
+    (11, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'whole', 0),
+    (11, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'whole', 0),
+    (11, 'tconv', 1, 0, 0, 0, 'f16', 0, 0, 1, 0, 1, 'whole', 0),
+    (11, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'whole', 0),
+    (11, 'tconv', 1, 1, 0, 0, 'f32', 0, 1, 0, 1, 0, 'whole', 0),
+    (3, 'conv', 1, 0, 0, 0, 'f16', 1, 0, 1, 0, 1, 'whole', 0),
+    (3, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'whole', 0),
+    (3, 'plain', 1, 0, 0, 1, 'f32', 0, 1, 1, 0, 0, 'whole', 0),
+    (3, 'tconv', 1, 1, 0, 1, 'f32', 0, 1, 0, 0, 0, 'whole', 0),
+    (5, 'conv', 1, 0, 0, 0, 'f16', 1, 0, 1, 0, 1, 'half', 0),
+    (5, 'conv', 1, 0, 0, 0, 'f16', 1, 0, 1, 0, 1, 'whole', 0),
+    (5, 'conv', 1, 0, 0, 0, 'f16', 1, 0, 1, 0, 1, 'whole', 1),
+    (5, 'conv', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'whole', 0),
+    (5, 'conv', 1, 0, 0, 1, 'f16', 1, 0, 1, 0, 1, 'straddle', 0),
+    (5, 'conv', 1, 0, 0, 1, 'f16', 1, 0, 1, 0, 1, 'whole', 0),
+    (5, 'conv', 1, 0, 0, 1, 'f32', 0, 1, 0, 0, 0, 'straddle', 0),
+    (5, 'conv', 1, 0, 0, 1, 'f32', 0, 1, 0, 1, 0, 'straddle', 0),
+    (5, 'conv', 1, 0, 0, 1, 'f32', 0, 1, 0, 1, 0, 'whole', 0),
+    (5, 'conv', 1, 0, 0, 1, 'f32', 1, 0, 1, 0, 1, 'straddle', 0),
+    (5, 'conv', 1, 0, 1, 0, 'f16', 1, 0, 1, 0, 1, 'half', 0),
+    (5, 'conv', 1, 0, 1, 1, 'f16', 1, 0, 1, 0, 1, 'straddle', 0),
+    (5, 'conv', 1, 0, 1, 1, 'f32', 0, 1, 0, 0, 0, 'straddle', 0),
+    (5, 'conv', 1, 0, 1, 1, 'f32', 0, 1, 0, 1, 0, 'straddle', 0),
+    (5, 'conv', 2, 0, 0, 0, 'f32', 0, 0, 1, 0, 0, 'whole', 0),
+    (5, 'conv', 2, 0, 0, 1, 'f32', 0, 0, 1, 0, 0, 'whole', 0),
+    (5, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 0, 0, 0, 'whole', 0),
+    (5, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'half', 0),
+    (5, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'whole', 0),
+    (5, 'plain', 1, 0, 0, 1, 'f32', 0, 1, 1, 0, 0, 'straddle', 0),
+    (5, 'plain', 1, 0, 0, 1, 'f32', 0, 1, 1, 0, 0, 'whole', 0),
+    (5, 'plain', 1, 0, 1, 1, 'f32', 0, 1, 1, 0, 0, 'straddle', 0),
+    (5, 'tconv', 1, 0, 0, 0, 'f16', 0, 0, 1, 0, 1, 'whole', 0),
+    (5, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 0, 0, 'half', 0),
+    (5, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 0, 0, 'whole', 0),
+    (5, 'tconv', 1, 1, 0, 0, 'f32', 0, 1, 0, 0, 0, 'half', 0),
+    (5, 'tconv', 1, 1, 0, 0, 'f32', 0, 1, 0, 0, 0, 'whole', 0),
+    (5, 'tconv', 1, 1, 0, 0, 'f32', 0, 1, 0, 0, 0, 'whole', 1),
+    (5, 'tconv', 1, 1, 1, 0, 'f32', 0, 1, 0, 0, 0, 'half', 0),
+    (8, 'conv', 1, 0, 0, 0, 'f16', 1, 0, 1, 0, 1, 'straddle', 0),
+    (8, 'conv', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'whole', 0),
+    (8, 'conv', 2, 0, 0, 0, 'f32', 0, 0, 1, 0, 0, 'whole', 1),
+    (8, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'whole', 0),
+    (8, 'plain', 1, 0, 0, 0, 'f32', 0, 1, 1, 0, 0, 'straddle', 0),
+    (8, 'tconv', 1, 0, 0, 0, 'f16', 0, 0, 1, 0, 1, 'whole', 0),
+    (8, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'straddle', 0),
+]
+for _n, _e in enumerate(_LOWERED_EPI):
+    CASES.append(_case("lowered_epi", "lowered-epi-t%d-%s%s%s%s%s-%s%s%s%s%s%s-%s%s" % (
+        _e[0], _e[1], "-s2" if _e[2] == 2 else "", "-halo" if _e[3] else "", "-mr" if _e[4] else "", "-nr" if _e[5] else "", _e[6], "-rowbias" if _e[7] else "",
+        "-res" if _e[8] else "", "-silu" if _e[9] else "", "-lo" if _e[10] else "", "-dead" if _e[11] else "", _e[12], "-chunked" if _e[13] else ""),
+        ("marked", "distinct")[_n % 2], tile=_e[0], kind=_e[1], stride=_e[2], halo=bool(_e[3]), m_ragged=_e[4], n_ragged=_e[5], out=_e[6], rowbias=_e[7],
+        res=bool(_e[8]), silu=bool(_e[9]), lo=bool(_e[10]), x_dead=bool(_e[11]), seam=_e[12], chunked=_e[13], seed=900 + _n))
+# ... the reduction launch of a split-K GEMM with T2V_EPI_GN: (rows per thread, out dtype, row bias, residual, SiLU, low-order image, dead result)
+_LOWERED_SPLITK = [
+    (1, 'f16', 0, 0, 1, 0, 1),
+    (1, 'f16', 1, 0, 1, 0, 1),
+    (1, 'f32', 0, 0, 1, 0, 0),
+    (1, 'f32', 0, 1, 0, 0, 0),
+    (1, 'f32', 0, 1, 0, 1, 0),
+    (1, 'f32', 0, 1, 1, 0, 0),
+    (1, 'f32', 1, 0, 1, 0, 1),
+    (12, 'f16', 1, 0, 1, 0, 1),
+    (12, 'f32', 0, 0, 1, 0, 0),
+    (12, 'f32', 0, 1, 1, 0, 0),
+    (2, 'f16', 0, 0, 1, 0, 1),
+    (2, 'f16', 1, 0, 1, 0, 1),
+    (2, 'f32', 0, 0, 1, 0, 0),
+    (2, 'f32', 0, 1, 0, 0, 0),
+    (2, 'f32', 0, 1, 1, 0, 0),
+    (4, 'f16', 1, 0, 1, 0, 1),
+    (4, 'f32', 0, 0, 1, 0, 0),
+    (4, 'f32', 0, 1, 0, 0, 0),
+    (4, 'f32', 0, 1, 1, 0, 0),
+    (8, 'f16', 1, 0, 1, 0, 1),
+    (8, 'f32', 0, 0, 1, 0, 0),
+    (8, 'f32', 0, 1, 0, 0, 0),
+    (8, 'f32', 0, 1, 1, 0, 0),
+]
+for _n, _e in enumerate(_LOWERED_SPLITK):
+    CASES.append(_case("lowered_splitk", "lowered-splitk-KR%d-%s%s%s%s%s%s" % (_e[0], _e[1], "-rowbias" if _e[2] else "", "-res" if _e[3] else "",
+                                                                               "-silu" if _e[4] else "", "-lo" if _e[5] else "", "-dead" if _e[6] else ""),
+                       ("marked", "distinct")[_n % 2], kr=_e[0], out=_e[1], rowbias=_e[2], res=bool(_e[3]), silu=bool(_e[4]), lo=bool(_e[5]), x_dead=bool(_e[6]),
+                       seed=1100 + _n))
+# ... the fused LayerNorm outputs (`offset` rows only where a residual closes the gap to the designed tensor: an fp16 operand of mean / std = 32
+# rows has lost the designed spread): (tile, i[8], M ragged, N ragged, residual, residual wrap i[12], more tiles than the co-residency bound)
+_LOWERED_LN = [
+    (0, 2, 0, 0, 0, 0, 0),
+    (0, 2, 0, 0, 1, 0, 0),
+    (0, 2, 1, 0, 0, 0, 0),
+    (0, 2, 1, 0, 1, 0, 0),
+    (11, 1, 0, 0, 0, 0, 0),
+    (11, 1, 0, 0, 1, 0, 0),
+    (12, 2, 0, 0, 0, 0, 0),
+    (12, 2, 0, 0, 0, 0, 1),
+    (12, 2, 0, 0, 1, 0, 0),
+    (12, 2, 0, 0, 1, 0, 1),
+    (12, 2, 0, 0, 1, 1, 0),
+    (12, 2, 1, 0, 0, 0, 0),
+    (12, 2, 1, 0, 1, 0, 0),
+    (2, 1, 0, 0, 0, 0, 0),
+    (2, 1, 0, 0, 1, 0, 0),
+    (3, 2, 0, 0, 0, 0, 0),
+    (3, 2, 0, 0, 1, 0, 0),
+    (3, 2, 0, 1, 0, 0, 0),
+    (3, 2, 0, 1, 1, 0, 0),
+    (3, 2, 1, 0, 0, 0, 0),
+    (3, 2, 1, 0, 1, 0, 0),
+    (5, 2, 0, 0, 0, 0, 0),
+    (5, 2, 0, 0, 0, 0, 1),
+    (5, 2, 0, 0, 1, 0, 0),
+    (5, 2, 0, 0, 1, 0, 1),
+    (5, 2, 1, 0, 0, 0, 0),
+    (5, 2, 1, 0, 0, 0, 1),
+    (5, 2, 1, 0, 1, 0, 0),
+    (5, 2, 1, 0, 1, 0, 1),
+    (8, 1, 0, 0, 0, 0, 0),
+    (8, 1, 0, 0, 1, 0, 0),
+    (8, 1, 1, 0, 0, 0, 0),
+    (8, 1, 1, 0, 1, 0, 0),
+    (9, 2, 0, 0, 0, 0, 1),
+    (9, 2, 0, 0, 1, 0, 1),
+    (9, 2, 1, 0, 0, 0, 0),
+    (9, 2, 1, 0, 0, 0, 1),
+    (9, 2, 1, 0, 1, 0, 0),
+    (9, 2, 1, 0, 1, 0, 1),
+    (9, 2, 1, 1, 0, 0, 1),
+    (9, 2, 1, 1, 1, 0, 1),
+]
+for _n, _e in enumerate(_LOWERED_LN):
+    CASES.append(_case("lowered_ln", "lowered-ln%d-t%d%s%s%s%s%s" % (_e[1], _e[0], "-mr" if _e[2] else "", "-nr" if _e[3] else "", "-res" if _e[4] else "",
+                                                                      "-wrap" if _e[5] else "", "-chunked" if _e[6] else ""),
+                       ("distinct", "offset")[_n % 2 if _e[4] else 0], tile=_e[0], mode=_e[1], m_ragged=_e[2], n_ragged=_e[3], res=bool(_e[4]), wrap=_e[5], chunked=_e[6], seed=1200 + _n))
 assert len({c["id"] for c in CASES}) == len(CASES)

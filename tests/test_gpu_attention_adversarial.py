@@ -18,37 +18,11 @@ import pytest
 import torch
 
 import adversarial as A
+import attention_records as R
 from harness import run_both
 from sd_webui_text2video_amd import _lib as L
-from sd_webui_text2video_amd import packing as pk
-from sd_webui_text2video_amd.program import Program, Ref
 
 pytestmark = pytest.mark.gpu
-NAN = float("nan")
-F16 = torch.float16
-
-
-def _padded(P, rows, cols, pad):
-    """rows x cols fp16 with `pad` rows that no item owns on either side: (whole allocation, the window)."""
-    big = P.alloc(rows + 2 * pad, cols, "f16")
-    return big, big.row_slice(pad, pad + rows)
-
-
-def _items_view(it, ref, dims, strides, D):
-    """[b_outer, b_inner, heads, n, D] view of the arena at `ref` with (sequence, outer, inner) element strides."""
-    bo, bi, heads, n = dims
-    return it.view(ref, (bo, bi, heads, n, D), (strides[1], strides[2], D, strides[0], 1), F16, {})
-
-
-def _nan_fill(it, big):
-    it.mat(big.ref, big.rows, big.ld, big.ld, F16, {}).fill_(NAN)
-
-
-def _spare_keys(it, big, win, k_col0, heads, D, spare_k):
-    """The spike of the masked set in the K columns of the spare rows that follow the last item."""
-    pad = (big.rows - win.rows) // 2
-    tail = big.row_slice(big.rows - pad, big.rows)
-    it.mat(tail.ref.shifted(2 * k_col0), pad, heads * D, big.ld, F16, {}).view(pad, heads, D).copy_(spare_k.half())
 
 
 def _check(tag, hi, low, ref, pads):
@@ -69,62 +43,9 @@ def _check(tag, hi, low, ref, pads):
 
 # ---- attn_kernel / attn2_kernel --------------------------------------------------------------------------------------------------------
 def _run_attn(c, x, attn2):
-    D, B, F, heads, nq, nk = c["D"], c["B"], c["F"], c["heads"], c["nq"], c["nk"]
-    inner, lay, lo = heads * D, c["layout"], c["lo"]
-    P = Program()
-    if lay == "cross":
-        pad = 64
-        qbig, qb = _padded(P, B * F * nq, inner, pad)
-        kvbig, kv = _padded(P, B * nk, 2 * inner + 8, pad)
-        q_ref, k_ref, v_ref, k_col0 = qb.ref, kv.col_slice(8, 8 + inner).ref, kv.col_slice(8 + inner, 8 + 2 * inner).ref, 8
-        q_str, kv_str = (inner, F * nq * inner, nq * inner), (kv.ld, nk * kv.ld, 0)
-        o_rows, o_unit = B * F * nq, (1, F * nq, nq)
-        bigs = [qbig, kvbig]
-    else:
-        assert nq == nk and (lay == "temporal" or F == 1)
-        px = F if lay == "temporal" else 1                 # rows per sequence step
-        pad = 64 * px
-        kvbig, kv = _padded(P, B * nq * px, 3 * inner, pad)
-        ld = kv.ld
-        q_ref, k_ref, v_ref, k_col0 = kv.ref, kv.col_slice(inner, 2 * inner).ref, kv.col_slice(2 * inner, 3 * inner).ref, inner
-        q_str = kv_str = (px * ld, nq * px * ld, ld if lay == "temporal" else 0)
-        o_rows, o_unit = B * nq * px, (px, nq * px, 1 if lay == "temporal" else 0)
-        bigs = [kvbig]
-    obig, o = _padded(P, o_rows, 2 * inner if lo else inner, pad)
-    o_str = tuple(u * o.ld for u in o_unit)
-    vt = P.alloc(B * F * heads * 64, -(-nk // 64) * 64, "f16") if attn2 else None
-    op = P.attention("a", q_ref, k_ref, v_ref, o.ref, nq=nq, nk=nk, heads=heads, b_outer=B, b_inner=F, q_strides=q_str, kv_strides=kv_str,
-                     o_strides=o_str, scale=x["scale"], head_dim=D, causal=c["causal"], lo_off=inner if lo else 0, vt_scratch=vt,
-                     waves=c["waves"] if attn2 else 0)
-    # the op record names the kernel the case is about
-    assert op.kind == L.OP_ATTENTION and op.i[14] == D and op.i[15] == int(c["causal"]) and op.i[16] == (inner if lo else 0)
-    if attn2:
-        assert op.p[6].space != "null" and op.i[17] == -(-nk // 64) * 64 and op.i[18] == c["waves"]
-    else:
-        assert op.p[6].space == "null"
-    kv_dims = (B, 1, heads, nk) if lay == "cross" else (B, F, heads, nk)
-
-    def init(it):
-        for b in bigs + [obig]:
-            _nan_fill(it, b)
-        if lay == "cross":
-            _items_view(it, q_ref, (B, F, heads, nq), q_str, D).copy_(x["q"].view(B, heads, F, nq, D).permute(0, 2, 1, 3, 4).half())
-        else:
-            _items_view(it, q_ref, (B, F, heads, nq), q_str, D).copy_(x["q"].view(B, F, heads, nq, D).half())
-        _items_view(it, k_ref, kv_dims, kv_str, D).copy_(x["k"].view(*kv_dims, D).half())
-        _items_view(it, v_ref, kv_dims, kv_str, D).copy_(x["v"].view(*kv_dims, D).half())
-        if x["spare_k"] is not None and not c["causal"]:
-            _spare_keys(it, kvbig, kv, k_col0, heads, D, x["spare_k"])
-    _, got, _, _ = run_both(P, {}, {}, init)
-
-    def out(ref_):
-        t = _items_view(got, ref_, (B, F, heads, nq), o_str, D).float()
-        return (t.permute(0, 2, 1, 3, 4).reshape(B * heads, F * nq, D) if lay == "cross" else t.reshape(B * F * heads, nq, D)).clone()
-    hi = out(o.ref)
-    low = out(o.ref.shifted(2 * inner)) if lo else None
-    allo = got.mat(obig.ref, obig.rows, obig.ld, obig.ld, F16, {})
-    pads = torch.cat([allo[:pad], allo[pad + o_rows:]]).clone()
-    return hi, low, pads
+    b = R.build_attn(c, attn2)
+    _, got, _, _ = run_both(b.P, b.w, {}, lambda it: b.init(it, x))
+    return b.read(got)
 
 
 @pytest.mark.parametrize("c", A.ATTN_CASES, ids=lambda c: c["id"])
@@ -157,41 +78,9 @@ def test_attention_kernels_on_late_maximum_and_masked_spike_inputs(c):
 
 # ---- relative-position temporal attention -----------------------------------------------------------------------------------------------
 def _run_relpos(c, x, sel):
-    D, T, Tq, off, R, lo, hw, b, heads = (c[n] for n in ("D", "T", "Tq", "off", "R", "lo", "hw", "b", "heads"))
-    inner = heads * D
-    ek, ev = x["ek"].float(), x["ev"].float()
-    w = {"ek": ek, "ev": ev, "ekL": pk.relpos_table_long(ek, False), "evL": pk.relpos_table_long(ev, True)}
-    extra = dict(rel_k_long=Ref("weight", 0, "ekL"), rel_vT_long=Ref("weight", 0, "evL"))
-    if sel == 2:
-        w["ek16"], w["ev16"] = pk.relpos_table16(ek, T, False), pk.relpos_table16(ev, T, True)
-        extra.update(rel_k16=Ref("weight", 0, "ek16"), rel_vT16=Ref("weight", 0, "ev16"))
-    pad = 32 * hw
-    P = Program()
-    qbig, q = _padded(P, b * Tq * hw, inner, pad)
-    kvbig, kv = _padded(P, b * T * hw, 2 * inner, pad)
-    obig, o = _padded(P, b * Tq * hw, 2 * inner if lo else inner, pad)
-    q_str, kv_str, o_str = (hw * inner, Tq * hw * inner, inner), (hw * kv.ld, T * hw * kv.ld, kv.ld), (hw * o.ld, Tq * hw * o.ld, o.ld)
-    op = P.attention("a", q.ref, kv.col_slice(0, inner).ref, kv.col_slice(inner, 2 * inner).ref, o.ref, nq=Tq, nk=T, heads=heads,
-                     b_outer=b, b_inner=hw, q_strides=q_str, kv_strides=kv_str, o_strides=o_str, scale=x["scale"], head_dim=D,
-                     rel_k=Ref("weight", 0, "ek"), rel_v=Ref("weight", 0, "ev"), max_rel=R, q_offset=off, relpos_mfma=sel,
-                     lo_off=inner if lo else 0, **extra)
-    want = 3 if T > 32 else sel
-    assert op.kind == L.OP_RELPOS_ATTN and op.i[17] == want and op.i[16] == off and op.i[15] == R and op.i[18] == (inner if lo else 0)
-    assert (op.p[6].space != "null") == (want in (2, 3))
-
-    def init(it):
-        for big in (qbig, kvbig, obig):
-            _nan_fill(it, big)
-        _items_view(it, q.ref, (b, hw, heads, Tq), q_str, D).copy_(x["q"].view(b, hw, heads, Tq, D).half())
-        _items_view(it, kv.ref, (b, hw, heads, T), kv_str, D).copy_(x["k"].view(b, hw, heads, T, D).half())
-        _items_view(it, kv.ref.shifted(2 * inner), (b, hw, heads, T), kv_str, D).copy_(x["v"].view(b, hw, heads, T, D).half())
-        if x["spare_k"] is not None:
-            _spare_keys(it, kvbig, kv, 0, heads, D, x["spare_k"])
-    _, got, _, _ = run_both(P, w, {}, init)
-    out = lambda r: _items_view(got, r, (b, hw, heads, Tq), o_str, D).float().reshape(b * hw * heads, Tq, D).clone()
-    allo = got.mat(obig.ref, obig.rows, obig.ld, obig.ld, F16, {})
-    pads = torch.cat([allo[:pad], allo[pad + o.rows:]]).clone()
-    return out(o.ref), (out(o.ref.shifted(2 * inner)) if lo else None), pads
+    b = R.build_relpos(c, sel, (x["ek"], x["ev"]))
+    _, got, _, _ = run_both(b.P, b.w, {}, lambda it: b.init(it, x))
+    return b.read(got)
 
 
 @pytest.mark.parametrize("c", A.RELPOS_LONG_CASES, ids=lambda c: c["id"])
