@@ -490,7 +490,10 @@ const char* t2v_comm_window_kind(const t2v_comm* comm);
 /* In-place all-gather outside a plan, on `stream`: part q of t2v_comm_size(comm) equal parts of `bytes` bytes lives at base + q*bytes,
  * the caller's own part is in place.  The per-step exchanges around the UNet — the eps of a classifier-free-guidance pair
  * (gaussian_sampler.py:161-163 evaluates the two forwards one after the other), the uint8 frames of the decoded clip
- * (lvdm/utils/dist_utils.py:13-19) — use it, so a sharded run's data path has ONE collective stack. */
+ * (lvdm/utils/dist_utils.py:13-19) — use it, so a sharded run's data path has ONE collective stack.
+ * `base` needs no alignment: a gather the peer window carries (16-byte units) from a base off 16 bytes runs on an aligned copy owned by
+ * the communicator (two extra device copies on `stream`); use one stream per communicator for such gathers.  The collective ops of a
+ * PLAN are different: their buffers must be 16-byte aligned when a window is open (arena offsets are), else T2V_ERR_BAD_ARG. */
 int t2v_comm_all_gather(t2v_comm* comm, void* base, uint64_t bytes, void* stream);
 
 /* Drop-in entry points for the reference's call sites (thin wrappers over t2v_plan_run that

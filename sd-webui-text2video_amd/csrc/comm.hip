@@ -69,6 +69,8 @@ struct t2v_comm {
   ncclComm_t comm;
   int nranks, rank;
   PeerWindow win;
+  unsigned char* stage = nullptr;      // t2v_comm_all_gather of a base that is not 16-byte aligned goes through this (aligned) copy
+  size_t stage_bytes = 0;
 };
 
 namespace {
@@ -388,6 +390,7 @@ const char* t2v_comm_impl_window_kind(const t2v_comm* c) { return (c && c->win.l
 void t2v_comm_impl_destroy(t2v_comm* c) {
   if (!c) return;
   px_window_close(c);
+  if (c->stage) (void)hipFree(c->stage);
   const Rccl* r = rccl();
   if (r) (void)r->CommDestroy(c->comm);
   delete c;
@@ -416,8 +419,32 @@ int t2v_comm_allgather(t2v_comm* c, void* base, size_t bytes, int nparts, int pa
   return T2V_OK;
 }
 
+// Any `base` (include/t2v_hip.h): the window moves aligned 16-byte units, so a gather that the window would carry from a base off that
+// alignment runs on an aligned copy — this rank's part in, the gathered parts out, both on `s`.  Which transport carries the gather
+// still depends on `bytes` alone (the same on every rank); staging is this rank's own business, a peer never sees it.
 int t2v_comm_impl_all_gather(t2v_comm* c, void* base, size_t bytes, hipStream_t s, std::string& err) {
-  return t2v_comm_allgather(c, base, bytes, c->nranks, c->rank, s, err);
+  const PeerWindow& w = c->win;
+  const bool window = w.open && c->nranks > 1 && c->nranks <= PX_MAX_RANKS && bytes <= w.slot_bytes && (bytes & 15) == 0;
+  if (!window || ((uintptr_t)base & 15) == 0) return t2v_comm_allgather(c, base, bytes, c->nranks, c->rank, s, err);
+  const size_t total = bytes * (size_t)c->nranks;
+  if (c->stage_bytes < total) {
+    if (c->stage) { (void)hipStreamSynchronize(s); (void)hipFree(c->stage); c->stage = nullptr; c->stage_bytes = 0; }
+    void* p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess || p == nullptr) { (void)hipGetLastError(); err = "all-gather: no memory for the aligned staging copy"; return T2V_ERR_COMM; }
+    c->stage = static_cast<unsigned char*>(p);
+    c->stage_bytes = total;
+  }
+  unsigned char* b = static_cast<unsigned char*>(base);
+  const size_t mine = (size_t)c->rank * bytes;
+  if (hipMemcpyAsync(c->stage + mine, b + mine, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) { err = "all-gather: staging copy failed"; return T2V_ERR_LAUNCH; }
+  const int rc = t2v_comm_allgather(c, c->stage, bytes, c->nranks, c->rank, s, err);
+  if (rc != T2V_OK) return rc;
+  for (int q = 0; q < c->nranks; ++q)      // the caller's own part stays as it is
+    if (q != c->rank && hipMemcpyAsync(b + (size_t)q * bytes, c->stage + (size_t)q * bytes, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      err = "all-gather: staging copy failed";
+      return T2V_ERR_LAUNCH;
+    }
+  return T2V_OK;
 }
 
 // Token buffer of F+2 frames: send frame 1 to prev / frame F to next, receive into frame 0 / frame F+1.

@@ -73,7 +73,8 @@ class GroupComm:
         return self._comm
 
     def all_gather_into(self, out: torch.Tensor, mine: torch.Tensor):
-        """out = concatenation over the group's ranks of `mine` (equal sizes)."""
+        """out = concatenation over the group's ranks of `mine` (equal sizes).  `out` may be any contiguous view: t2v_comm_all_gather needs
+        no alignment of its base (a gather the peer window carries from a base off 16 bytes runs on an aligned copy inside the library)."""
         comm = self.communicator(out.device)
         if comm is None:
             return all_gather_into(out, mine, group=self.group)

@@ -11,7 +11,9 @@ tools/program_digest.py FIXED pins: T2V_DEVICE_CUS = 256.
 Out of scope (path_key returns None):
   MEMSET            hipMemsetAsync, no kernel of the project (executor.hip launch_op)
   ALLGATHER, HALO_EXCHANGE, STATS_HALO, ALLTOALL
-                    collectives: they need peers, tests/test_gpu_multiproc.py and the comm tests run them
+                    collectives: they need peers and have no record fields that choose a kernel; their code paths depend on the
+                    message size alone and have their own designed-input suite, tests/collective_inputs.py (share, trip and
+                    transport classes; test_collective_inputs_cpu.py, test_gpu_collectives_adversarial.py)
   EMBED_ROWS, RESHARD_ROWS, RESAMPLE, TO_UINT8, EMPHASIS, FINGERPRINT, LORA_MERGE
                     their tests already demand bit equality at strided and ragged shapes, or they are never part of a plan
 The plan-time feed-forward pair (executor.hip ff_pair -> t2v_launch_ff_fused) is a decision of the plan, not a field of a record: it keeps
@@ -22,8 +24,9 @@ from sd_webui_text2video_amd import _lib as L
 
 DEVICE_CUS = 256          # tools/program_digest.py FIXED["T2V_DEVICE_CUS"]
 GNC_THREADS = 512         # norm.hip:410
-OUT_OF_SCOPE = {L.OP_MEMSET: "hipMemsetAsync", L.OP_ALLGATHER: "collective", L.OP_HALO_EXCHANGE: "collective", L.OP_STATS_HALO: "collective",
-                L.OP_ALLTOALL: "collective", L.OP_EMBED_ROWS: "bit-exact tests", L.OP_RESHARD_ROWS: "bit-exact tests", L.OP_RESAMPLE: "bit-exact tests",
+_COLLECTIVE = "collective: tests/collective_inputs.py (designed sizes per message share, run by tests/test_gpu_collectives_adversarial.py)"
+OUT_OF_SCOPE = {L.OP_MEMSET: "hipMemsetAsync", L.OP_ALLGATHER: _COLLECTIVE, L.OP_HALO_EXCHANGE: _COLLECTIVE, L.OP_STATS_HALO: _COLLECTIVE,
+                L.OP_ALLTOALL: _COLLECTIVE, L.OP_EMBED_ROWS: "bit-exact tests", L.OP_RESHARD_ROWS: "bit-exact tests", L.OP_RESAMPLE: "bit-exact tests",
                 L.OP_TO_UINT8: "bit-exact tests", L.OP_EMPHASIS: "bit-exact tests", L.OP_FINGERPRINT: "never part of a plan",
                 L.OP_LORA_MERGE: "never part of a plan"}
 KIND_NAMES = {L.OP_GEMM: "GEMM", L.OP_GROUPNORM: "GROUPNORM", L.OP_LAYERNORM: "LAYERNORM", L.OP_ATTENTION: "ATTENTION", L.OP_RELPOS_ATTN: "RELPOS_ATTN",
