@@ -42,6 +42,8 @@ extern "C" {
                                changes, and a library without it refuses the record as an unknown op kind);
                                still 11: RESAMPLE i[9] = 1 / i[10] / i[11] (a float bicubic resize of planar images in one launch — the resizes around the depth
                                estimator of the VideoCrafter depth adapter; additive on fields that every earlier record leaves zero);
+                               still 11: TO_UINT8 i[15] = 1 (torch_to_np's arithmetic and per-video output blocks — the VideoCrafter driver's frames; additive on
+                               a field that every earlier record leaves zero);
                                10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
                                optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
                                9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
@@ -96,7 +98,7 @@ enum t2v_op_kind {
   T2V_OP_LINCOMB = 12,    /* out = sum_i c_i * T_i (<= 6 latent-sized tensors): UniPC / DDIM updates */
   T2V_OP_RELPOS_ATTN = 13, /* LVDM temporal attention with relative-position K / V terms (frames <= 32; <= T2V_RELPOS_MAX_FRAMES with i[17] = 3) */
   T2V_OP_EMBED_ROWS = 14,  /* token + positional embedding lookup (CLIP text towers) */
-  T2V_OP_TO_UINT8 = 15,    /* tensor2vid: float video -> uint8 frames [F,H,(i W),3], truncating (t2v_pipeline.py:447-460) */
+  T2V_OP_TO_UINT8 = 15,    /* tensor2vid: float video -> uint8 frames [F,H,(i W),3], truncating (t2v_pipeline.py:447-460); form 1: torch_to_np (sample_utils.py:98-107) */
   T2V_OP_ALLGATHER = 16,   /* in-place all-gather of equal byte parts over the plan's communicator (RCCL, launch stream) */
   T2V_OP_HALO_EXCHANGE = 17, /* +-1 frame neighbour exchange of a [F+2]-frame token buffer over the plan's communicator */
   T2V_OP_RESHARD_ROWS = 18,  /* chunked row regrouping (pack / unpack of a frame <-> pixel resharding), optional fp32 residual */
@@ -327,7 +329,11 @@ enum t2v_gather {
  * TO_UINT8: out[f, y, i*W + x, c] = trunc(clamp(v*0.5 + 0.5, 0, 1) * 255), v = in[i*si + c*sc + f*sf + y*sy + x*sx]
  *      i: 0 NI (videos side by side), 1 C, 2 F, 3 H, 4 W, 5 in dtype, 6 arithmetic (0 fp32 | 1 every intermediate rounded
  *      to fp16, the reference's half-precision VAE path), 7 channel order reversed (RGB -> BGR), 8/9 si (lo, hi), 10 sc,
- *      11/12 sf (lo, hi), 13 sy, 14 sx (element strides);  p: 0 in, 1 out uint8
+ *      11/12 sf (lo, hi), 13 sy, 14 sx (element strides), 15 form (0: the above);  p: 0 in, 1 out uint8
+ *      form i[15] = 1 (torch_to_np, videocrafter/sample_utils.py:98-107): out[i, f, y, x, c] = trunc(clamp((v + 1) * 127.5, 0, 255)) — one
+ *      [F, H, W, C] block per video instead of videos side by side.  fp32, `v + 1` and `* 127.5` each rounded by itself (no fma); +-inf -> 0 | 255,
+ *      a NaN stores 0 (torch's cast is undefined there).  i[6] = 1: the input element is rounded to fp16 FIRST and the arithmetic stays fp32
+ *      (an fp16 model's video under torch_to_np's `.float()`), not the fp16 chain of form 0.  i[7] must be 0.  Same strides, same byte extents.
  * ALLGATHER: part q of `nparts` equal parts lives at base + q*bytes; this rank's part is already in place.
  *      i: 0/1 bytes per part (lo, hi), 2 nparts, 3 this rank's part;  p: 0 base.   nparts == 1: no-op.
  * HALO_EXCHANGE: token buffer of F+2 frames (frame = `bytes`): frame 1 -> previous rank's frame F+1 slot ... i.e. this rank

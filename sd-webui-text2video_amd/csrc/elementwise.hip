@@ -889,6 +889,33 @@ __global__ __launch_bounds__(256) void to_uint8_kernel(const TIN* in, unsigned c
   }
 }
 
+// torch_to_np (videocrafter/sample_utils.py:98-107), form 1 of T2V_OP_TO_UINT8: video[i,c,f,y,x] -> uint8 out[i, f, y, x, c] (one
+// [F,H,W,C] block per video): a = x + 1, b = a * 127.5 (each rounded by itself in fp32, never an fma), clamp to [0, 255] (+-inf -> 0 | 255),
+// TRUNCATED like `.to(torch.uint8)`; a NaN stores 0.  HALF: the input element is rounded to fp16 first (the fp16 model's video), the
+// arithmetic stays fp32 — torch_to_np's `.float()` — unlike tensor2vid's fp16 chain above.  Same input addressing and pixel mapping.
+template <typename TIN, bool HALF>
+__global__ __launch_bounds__(256) void to_uint8_np_kernel(const TIN* in, unsigned char* out, int NI, int C, int F, int H, int W,
+                                                          long si, long sc, long sf, long sy, long sx) {
+  const long total = (long)NI * F * H * W;
+  for (long px = (long)blockIdx.x * 256 + threadIdx.x; px < total; px += (long)gridDim.x * 256) {
+    const int x = (int)(px % W);
+    long r = px / W;
+    const int y = (int)(r % H);
+    r /= H;
+    const int f = (int)(r % F);
+    const int i = (int)(r / F);
+    const TIN* src = in + i * si + f * sf + y * sy + x * sx;
+    unsigned char* o = out + px * C;
+    for (int c = 0; c < C; ++c) {
+      float v = (float)src[c * sc];
+      if (HALF) v = (float)(f16)v;
+      v = __fmul_rn(__fadd_rn(v, 1.f), 127.5f);
+      v = !(v > 0.f) ? 0.f : (v > 255.f ? 255.f : v);        // (a NaN fails `v > 0`)
+      o[c] = (unsigned char)(int)v;
+    }
+  }
+}
+
 // Separable table-driven resampler for uint8 [N, H, W, 3] images (T2V_OP_RESAMPLE): ONE pass of Pillow's 8-bit resize
 // (Resample.c, PRECISION_BITS = 22) — the Lanczos resize of process_modelscope.py:116-120,174-178 is a horizontal pass into a
 // uint8 intermediate followed by a vertical one.  Per output index o with table row k[0..ksize) and bounds {first, count}:
@@ -1140,6 +1167,18 @@ hipError_t t2v_launch_to_uint8(const t2v_op& op, hipStream_t s) {
   const long sy = op.i[13], sx = op.i[14];
   const int g = grid_for((long)F * H * NI * W);
   unsigned char* out = reinterpret_cast<unsigned char*>(op.p[1]);
+  if (op.i[15] == 1) {                                   // torch_to_np: a kernel of its own, form 0 launches what it always launched
+    if (op.i[5] == T2V_F32) {
+      const float* in = reinterpret_cast<const float*>(op.p[0]);
+      if (half) hipLaunchKernelGGL((to_uint8_np_kernel<float, true>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
+      else hipLaunchKernelGGL((to_uint8_np_kernel<float, false>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
+    } else {
+      const f16* in = reinterpret_cast<const f16*>(op.p[0]);
+      if (half) hipLaunchKernelGGL((to_uint8_np_kernel<f16, true>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
+      else hipLaunchKernelGGL((to_uint8_np_kernel<f16, false>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
+    }
+    return hipGetLastError();
+  }
   if (op.i[5] == T2V_F32) {
     const float* in = reinterpret_cast<const float*>(op.p[0]);
     if (half) hipLaunchKernelGGL((to_uint8_kernel<float, true>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx, bgr);

@@ -279,6 +279,8 @@ int validate_op(const t2v_op& op, int idx) {
     case T2V_OP_TO_UINT8:
       if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[1] > 4 || op.i[2] <= 0 || op.i[3] <= 0 || op.i[4] <= 0) return bad("empty uint8 conversion");
       if (op.p[0] == 0 || op.p[1] == 0) return bad("null uint8-conversion pointer");
+      if (op.i[15] != 0 && op.i[15] != 1) return bad("uint8 conversion: form i[15] must be 0 (tensor2vid) or 1 (torch_to_np)");
+      if (op.i[15] == 1 && op.i[7] != 0) return bad("uint8 conversion: the torch_to_np form has no reversed channel order (i[7] = 0)");
       return 0;
     case T2V_OP_RESAMPLE: {
       const int out = op.i[4], axis = op.i[5], form = op.i[7], ld = op.i[8];

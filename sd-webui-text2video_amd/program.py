@@ -1076,12 +1076,17 @@ class Program:
         return self._emit(op)
 
     def to_uint8(self, name: str, src: Ref, src_dtype: str, dst: Ref, *, NI: int, C: int, F: int, H: int, W: int, strides,
-                 half: bool, bgr: bool = False) -> Op:
+                 half: bool, bgr: bool = False, form: int = 0) -> Op:
         """tensor2vid on device: element (i, c, f, y, x) of the float video at i*si + c*sc + f*sf + y*sy + x*sx ->
-        uint8 out[f, y, i*W + x, c]; `half` = the reference's fp16 arithmetic (half-precision VAE)."""
+        uint8 out[f, y, i*W + x, c]; `half` = the reference's fp16 arithmetic (half-precision VAE).
+        form=1: torch_to_np (videocrafter/sample_utils.py:98-107) -> uint8 out[i, f, y, x, c], trunc(clamp((v + 1) * 127.5, 0, 255)) in
+        fp32; `half` = the input rounded to fp16 first (an fp16 model's video), the arithmetic still fp32; no `bgr`."""
         si, sc, sf, sy, sx = strides
+        if form not in (0, 1) or (form == 1 and bgr):
+            raise ValueError("to_uint8: form is 0 (tensor2vid) or 1 (torch_to_np, RGB only)")
         op = Op(L.OP_TO_UINT8, name)
         op.i[0:8] = [NI, C, F, H, W, _DT[src_dtype], int(half), int(bgr)]
+        op.i[15] = form
         op.i[8], op.i[9], op.i[10], op.i[11], op.i[12], op.i[13], op.i[14] = si & 0xFFFFFFFF, si >> 32, sc, sf & 0xFFFFFFFF, sf >> 32, sy, sx
         for v in (sc, sy, sx):
             assert 0 <= v < 2 ** 31

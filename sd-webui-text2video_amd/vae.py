@@ -19,6 +19,7 @@ from __future__ import annotations
 
 from typing import Dict
 
+import math
 import os
 
 import torch
@@ -242,15 +243,26 @@ class AutoencoderKL(nn.Module):
         """z [n, 4, h, w] (the pipeline passes x0/0.18215, t2v_pipeline.py:348) -> [n, 3, 8h, 8w]."""
         return self._decode(z, None)
 
-    def decode_to_uint8(self, z, videos: int = 1, bgr: bool = False):
+    def decode_to_uint8(self, z, videos: int = 1, bgr: bool = False, form: str = "vid", out=None):
         """decode + tensor2vid in ONE program: z [(videos f), 4, h, w] -> uint8 [f, 8h, videos * 8w, 3] (RGB, or BGR as
         postprocess_video returns them, t2v_pipeline.py:412-435).  The uint8 conversion is the decoder program's last
         op (T2V_OP_TO_UINT8 on the conv_out tokens); with fp16 weights it uses the fp16 arithmetic the reference's
-        half-precision VAE path hands tensor2vid (t2v_pipeline.py:337-351,447-460)."""
+        half-precision VAE path hands tensor2vid (t2v_pipeline.py:337-351,447-460).
+        form="np": the last op is form 1 of the same record, torch_to_np of the VideoCrafter path (sample_utils.py:98-107) ->
+        uint8 [videos, f, 8h, 8w, 3], RGB only; with fp16 weights the conv_out tokens are rounded to fp16 first, as `decode` stores
+        them, and the arithmetic is fp32.  `out`: a contiguous uint8 device tensor of that size to write instead of a new one."""
         assert z.shape[0] % videos == 0
-        return self._decode(z, (videos, bool(bgr)))
+        if form == "vid":
+            if out is not None:
+                raise ValueError('decode_to_uint8: `out` goes with form="np"')
+            return self._decode(z, (videos, bool(bgr)))
+        if form != "np":
+            raise ValueError(f'decode_to_uint8: form is "vid" (tensor2vid) or "np" (torch_to_np), got {form!r}')
+        if bgr:
+            raise ValueError('decode_to_uint8: form="np" has no BGR order')
+        return self._decode(z, (videos, False, "np"), out)
 
-    def _decode(self, z, u8):
+    def _decode(self, z, u8, out=None):
         if not z.is_cuda:
             raise L.T2VError("AutoencoderKL.decode needs device tensors on an AMD GPU (no CPU fallback)")
         n, c, h, w = z.shape
@@ -271,6 +283,14 @@ class AutoencoderKL(nn.Module):
         comp.ensure_bound(self._packed, z.device)
         if u8 is None:
             out = torch.empty((n, self.ddconfig["out_ch"], 8 * h, 8 * w), device=z.device, dtype=out_dtype)
+        elif len(u8) == 3:           # torch_to_np form: one [f, 8h, 8w, 3] block per video
+            shape = (u8[0], n // u8[0], 8 * h, 8 * w, self.ddconfig["out_ch"])
+            if out is None:
+                out = torch.empty(shape, device=z.device, dtype=torch.uint8)
+            elif out.dtype != torch.uint8 or out.device != z.device or not out.is_contiguous() or out.numel() != math.prod(shape):
+                raise ValueError(f"decode_to_uint8: `out` must be a contiguous uint8 tensor of {shape} on {z.device}")
+            else:
+                out = out.view(shape)
         else:
             out = torch.empty((n // u8[0], 8 * h, u8[0] * 8 * w, self.ddconfig["out_ch"]), device=z.device, dtype=torch.uint8)
         comp.bound.run({L.EXT_X: z.data_ptr(), L.EXT_OUT: out.data_ptr()},
@@ -495,10 +515,11 @@ class _VaeLowering(_Declarations):
         if u8 is None:
             P.cl_to_ncthw("img.from_tokens", y, Ref("ext", L.EXT_OUT), self.out_dt, B=n, C=dd["out_ch"], F=1, HW=h * w)
         else:
-            videos, bgr = u8
+            videos, bgr = u8[0], u8[1]
             Fr = n // videos                    # token row = ((video * Fr + f) * h + y) * w + x
             P.to_uint8("img.to_uint8", y.ref, y.dtype, Ref("ext", L.EXT_OUT), NI=videos, C=dd["out_ch"], F=Fr, H=h, W=w,
-                       strides=(Fr * h * w * y.ld, 1, h * w * y.ld, w * y.ld, y.ld), half=self.out_dt == "f16", bgr=bgr)
+                       strides=(Fr * h * w * y.ld, 1, h * w * y.ld, w * y.ld, y.ld), half=self.out_dt == "f16", bgr=bgr,
+                       form=int(len(u8) == 3))          # (videos, bgr, "np"): torch_to_np in place of tensor2vid
         P.free(y)
         P.finish()
         return P

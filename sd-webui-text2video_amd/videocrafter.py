@@ -17,7 +17,9 @@ the MFMA flash-attention kernel, TemporalCrossAttention with relative-position t
 from __future__ import annotations
 
 import math
+from base64 import b64encode
 from functools import partial
+from types import SimpleNamespace
 from typing import List, Optional
 
 import numpy as np
@@ -946,6 +948,24 @@ class LatentDiffusion(nn.Module):
         assert self.encoder_type == "2d" and z.dim() == 5
         return self.decode_first_stage_2DAE(z, decode_bs=decode_bs, return_cpu=return_cpu, **kwargs)
 
+    @torch.no_grad()
+    def decode_first_stage_uint8(self, z, decode_bs=16, to_host=True):
+        """z [b, 4, t, h, w] -> uint8 [b, t, H, W, 3]: the bytes of `torch_to_np(decode_first_stage(z, decode_bs, return_cpu=False))`
+        without a float video.  The frames are decoded in the chunks `decode_first_stage_2DAE` takes (None = all at once, a ragged last
+        chunk allowed); each chunk's decoder program ends in T2V_OP_TO_UINT8 form 1 in place of the NCHW store and writes its slice of
+        the one output tensor, so 3 bytes per pixel cross to the host (`to_host`) instead of 12 (fp32 weights) or 6 (fp16)."""
+        assert self.encoder_type == "2d" and z.dim() == 5
+        b, _, t, h, w = z.shape
+        zf = z.permute(0, 2, 1, 3, 4).reshape(b * t, z.shape[1], h, w)
+        zf = 1.0 / self.scale_factor * zf - self.shift_factor
+        ae = self.first_stage_model
+        out = torch.empty((b * t, 8 * h, 8 * w, ae.ddconfig["out_ch"]), device=z.device, dtype=torch.uint8)
+        step = b * t if decode_bs is None else decode_bs
+        for k in range(0, b * t, step):
+            ae.decode_to_uint8(zf[k:k + step], videos=1, form="np", out=out[k:k + step])
+        out = out.view(b, t, *out.shape[1:])
+        return out.cpu() if to_host else out
+
 
 class T2VAdapterDepth(LatentDiffusion):
     """ddpm3d.py:1436-1484 — LatentDiffusion + the depth adapter ("VideoControl").  The reference builds its parts from configs;
@@ -1029,6 +1049,10 @@ class DDIMSampler(object):
         self.schedule = schedule
         self.counter = 0
         self.noise_gen = torch.Generator(device="cpu")      # seeded by process_videocrafter.py:70
+        # one CPU generator per video of the batch (None: the single `noise_gen` above for the whole batch).  Video v's per-step noise
+        # is then torch.randn((1, *shape[1:]), generator=noise_gens[v]): the stream a batch-of-one run seeded like noise_gens[v] draws,
+        # which is what lets `process_videocrafter` make the reference's batch_count videos in one batch
+        self.noise_gens = None
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
         """ddim.py:24-53 with make_ddim_timesteps / make_ddim_sampling_parameters (util.py:36-63) on fp32 cumprods."""
@@ -1056,6 +1080,9 @@ class DDIMSampler(object):
             raise NotImplementedError("quantisation / noise dropout / score correctors are not on the hot path")
         size = (batch_size, *shape)
         assert len(size) == 5
+        gens = getattr(self, "noise_gens", None)
+        if gens is not None and len(gens) != batch_size:
+            raise ValueError(f"noise_gens holds {len(gens)} generators for a batch of {batch_size}: one per video")
         if mask is not None:
             # mask blending (ddim.py:188-195): img = q_sample(x0, step - 1) * mask + (1 - mask) * img after every step.  The mask is
             # 5-D and broadcastable to the latent, [b|1, c|1, t|1, h|1, w|1], any float values; a mask of another rank would
@@ -1111,6 +1138,9 @@ class DDIMSampler(object):
         nxt = torch.empty_like(img)
         extra = {} if features_adapter is None else {"features_adapter": features_adapter}     # the same list object every step: converted once
         nb, C = img.shape[0], img.shape[1]          # nb videos per batch (sample_text2video's batch_size)
+        gens = getattr(self, "noise_gens", None)
+        if gens is not None and len(gens) != nb:
+            raise ValueError(f"noise_gens holds {len(gens)} generators for a batch of {nb}: one per video")
         f32 = torch.float32
         if mask is not None:                        # expanded once per call: the kernel reads x0, mask and q-noise dense, like x
             known = x0.to(device=device, dtype=f32).contiguous()
@@ -1141,10 +1171,12 @@ class DDIMSampler(object):
                 sigma_t, s1m = self.ddim_sigmas[index].to(f32), self.ddim_sqrt_one_minus_alphas[index].to(f32)
                 coef = [float(s1m), float(a_t.sqrt()), float(a_prev.sqrt()), float((1.0 - a_prev - sigma_t ** 2).sqrt()),
                         float(sigma_t) * float(temperature), float(guide) if guided else 1.0]
-                if sample_noise is None:      # noise_like(..., noise_gen): CPU generator -> same stream on any device
-                    noise = torch.randn(tuple(img.shape), generator=self.noise_gen).to(device)
-                else:
+                if sample_noise is not None:
                     noise = sample_noise.to(device=device, dtype=f32).contiguous()
+                elif gens is None:            # noise_like(..., noise_gen): CPU generator -> same stream on any device
+                    noise = torch.randn(tuple(img.shape), generator=self.noise_gen).to(device)
+                else:                         # one stream per video, each drawn as a batch of one
+                    noise = torch.cat([torch.randn((1, *img.shape[1:]), generator=g) for g in gens]).to(device)
                 want_x0 = img_callback is not None or index % log_every_t == 0 or index == total_steps - 1
                 if want_x0:                   # pred_x0 = (x - sqrt(1-a_t) e) / sqrt(a_t), e = u + g (c - u)
                     px0 = torch.empty_like(img)
@@ -1318,11 +1350,42 @@ def torch_to_np(x):
     return (sample.permute(0, 2, 3, 4, 1) if sample.dim() == 5 else sample.permute(0, 2, 3, 1)).contiguous()
 
 
+def torch_to_np_device(x):
+    """`torch_to_np` of a float video that is on the device, there: [b, c, t, h, w] -> uint8 [b, t, h, w, c] (or [b, c, h, w] ->
+    [b, h, w, c]) with ONE T2V_OP_TO_UINT8 launch of form 1 — (x + 1) * 127.5 in fp32, clamped to [0, 255], truncated.  Bit-exact with
+    `torch_to_np` for the same input (a NaN aside: torch's cast of it is undefined, the kernel stores 0).  The counterpart of
+    `pipeline.tensor2vid_device`; a decoded latent never needs it: `LatentDiffusion.decode_first_stage_uint8`."""
+    import ctypes
+    if not x.is_cuda:
+        raise L.T2VError("torch_to_np_device needs a device tensor on an AMD GPU (no CPU fallback)")
+    if x.dim() not in (4, 5):
+        raise ValueError(f"expected [b, c, t, h, w] or [b, c, h, w], got {tuple(x.shape)}")
+    if x.dtype not in (torch.float16, torch.float32):
+        x = x.float()
+    v = (x if x.dim() == 5 else x.unsqueeze(2)).contiguous()
+    NI, C, Fr, H, W = v.shape
+    out = torch.empty((NI, Fr, H, W, C), dtype=torch.uint8, device=v.device)
+    op = L.T2VOp()
+    op.kind = L.OP_TO_UINT8
+    half = v.dtype == torch.float16
+    si, sc, sf, sy, sx = C * Fr * H * W, Fr * H * W, H * W, W, 1
+    if sc >= 2 ** 31 or not 1 <= C <= 4:
+        raise L.T2VError("video too large for one uint8 conversion launch (or more than 4 channels)")
+    vals = [NI, C, Fr, H, W, L.F16 if half else L.F32, 0, 0, si & 0xFFFFFFFF, si >> 32, sc, sf & 0xFFFFFFFF, sf >> 32, sy, sx, 1]
+    for k, val in enumerate(vals):
+        op.i[k] = val - (1 << 32) if val >= (1 << 31) else val       # low words as raw bits
+    op.p[0], op.p[1] = v.data_ptr(), out.data_ptr()
+    L.check(L.load().t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)))
+    return out if x.dim() == 5 else out[:, 0]
+
+
 @torch.no_grad()
 def sample_text2video(model, prompt, n_prompt, n_samples, batch_size, sample_type="ddim", sampler=None, ddim_steps=50, eta=1.0,
                       cfg_scale=7.5, decode_frame_bs=1, ddp=False, all_gather=True, batch_progress=True,
-                      show_denoising_progress=False, num_frames=None, *, mask=None, x0=None, init_video=None):
+                      show_denoising_progress=False, num_frames=None, *, mask=None, x0=None, init_video=None, device_uint8=False):
     """-> np.uint8 [n, T, H, W, 3].  `decode_frame_bs=None` decodes all frames in one VAE launch sequence.
+    device_uint8 (not in the reference's signature): the frames leave the decoder programs as uint8 (`decode_first_stage_uint8`, same
+    `decode_frame_bs` chunks) — the same array, a quarter (fp32 weights) or half (fp16) of the bytes copied to the host.
     mask / x0 (not in the reference's signature): held regions, as `DDIMSampler.sample` takes them, applied to every batch;
     init_video [b, 3, t, H, W] in [-1, 1] is encoded with `encode_first_stage_2DAE` and stands in for x0."""
     if sample_type != "ddim" or sampler is None:
@@ -1339,11 +1402,97 @@ def sample_text2video(model, prompt, n_prompt, n_samples, batch_size, sample_typ
         latent, _ = sampler.sample(S=ddim_steps, conditioning=cond, batch_size=noise_shape[0], shape=noise_shape[1:],
                                    verbose=show_denoising_progress, unconditional_guidance_scale=cfg_scale,
                                    unconditional_conditioning=uncond, eta=eta, mask=mask, x0=x0)
+        if device_uint8:
+            videos.append(model.decode_first_stage_uint8(latent, decode_bs=decode_frame_bs).numpy())
+            continue
         samples = model.decode_first_stage(latent, decode_bs=decode_frame_bs, return_cpu=False)
         videos.append(torch_to_np(samples).numpy())
     out = np.concatenate(videos, axis=0)
     assert out.shape[0] >= n_samples
     return out
+
+
+def process_videocrafter(args_dict: dict):
+    """The driver of the VideoCrafter route (process_videocrafter.py:12-98), the counterpart of `pipeline.process_modelscope`.  The
+    reference body is config / checkpoint loading and mp4 plumbing around a `batch_count` loop of single-video `sample_text2video`
+    calls (:55-98).  Here:
+      args_dict = {model (a LatentDiffusion), sampler (a DDIMSampler; one is made when absent),
+                   prompt, n_prompt, steps, frames, seed, cfg_scale, eta, batch_count, fps,
+                   stitch, one_pass (True), decode_frame_bs (1, what the reference passes)}
+    * `width` / `height` are ignored as in the reference: the model's `image_size` rules.  `sample_type` other than "ddim" is refused
+      like `sample_text2video` refuses it; masks and init videos are `sample_text2video`'s, not this seam's.
+    * loop route (`one_pass=False` or one video), the reference's loop: video b from `noise_gen.manual_seed(seed + b)` (seed -1: -1 for
+      every video, the reference's own quirk), `sample_text2video(model, prompt, n_prompt, 1, 1, ...)`, with `state.job_count` /
+      `job_no` / `job`, the `skipped` reset and the break on `interrupted`.
+    * one pass (default for batch_count > 1): the conditions once, x_T = the batch_count device draws of one video's shape that the
+      loop would make, in its order, `sampler.noise_gens[v]` seeded seed + v, ONE `sampler.sample` of batch batch_count and ONE
+      `decode_first_stage_uint8` — the loop's videos up to what a larger batch changes in the GEMM tiling.
+    * either way the frames leave the decoder programs as uint8.
+    * no `stitch`: returns the list of batch_count videos, uint8 [T, H, W, 3] RGB (fewer after an interrupt).
+      `stitch(frames, fps) -> bytes` (mp4 writing, out of scope: the reference's `npz_to_video_grid` and its soundtrack stage) given:
+      every video is handed to it and the reference's own return value comes back, `[dataurl]` of the LAST video only (:92-98)."""
+    from . import samplers as S
+    a = SimpleNamespace(**args_dict)
+    model = a.model
+    if getattr(a, "sample_type", "ddim") != "ddim":
+        raise NotImplementedError("only the DDIM path of the webui (process_videocrafter.py:57-79) is built")
+    sampler = getattr(a, "sampler", None)
+    if sampler is None:
+        sampler = DDIMSampler(model)
+    batch_count = int(getattr(a, "batch_count", 1))
+    n_prompt, eta, cfg_scale = getattr(a, "n_prompt", ""), getattr(a, "eta", 1.0), getattr(a, "cfg_scale", 7.5)
+    stitch, fps = getattr(a, "stitch", None), getattr(a, "fps", None)
+    decode_frame_bs = getattr(a, "decode_frame_bs", 1)
+    frames = getattr(a, "frames", None)
+    state = S.state
+    state.job_count = batch_count
+    videos, urls = [], []
+
+    def emit(vid):            # (the reference writes and reads back vid.mp4 inside its loop, :85-93)
+        videos.append(vid)
+        if stitch is not None:
+            urls[:] = ["data:video/mp4;base64," + b64encode(stitch(vid, fps)).decode()]
+
+    if batch_count > 1 and getattr(a, "one_pass", True):
+        state.job_no = 1
+        if state.skipped:
+            state.skipped = False
+        if not state.interrupted:
+            state.job = f"Batches 1-{batch_count} out of {batch_count}"
+            cond = get_conditions(a.prompt, model, 1)["c_crossattn"][0]
+            cond = {"c_crossattn": [cond.repeat(batch_count, *([1] * (cond.dim() - 1)))]}
+            uncond = None
+            if cfg_scale != 1.0:
+                uncond = get_conditions(n_prompt, model, 1)["c_crossattn"][0]
+                uncond = {"c_crossattn": [uncond.repeat(batch_count, *([1] * (uncond.dim() - 1)))]}
+            shape = make_model_input_shape(model, 1, T=frames)
+            x_T = torch.cat([torch.randn(tuple(shape), device=model.device) for _ in range(batch_count)])
+            gens = [torch.Generator(device="cpu") for _ in range(batch_count)]
+            for v, g in enumerate(gens):
+                g.manual_seed(a.seed + v if a.seed != -1 else -1)
+            prev, sampler.noise_gens = getattr(sampler, "noise_gens", None), gens
+            try:
+                latent, _ = sampler.sample(S=a.steps, conditioning=cond, batch_size=batch_count, shape=shape[1:], verbose=False,
+                                           unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uncond, eta=eta, x_T=x_T)
+            finally:
+                sampler.noise_gens = prev
+            u8 = model.decode_first_stage_uint8(latent, decode_bs=decode_frame_bs).numpy()
+            for v in range(batch_count):
+                emit(u8[v])
+            state.job_no = batch_count
+    else:
+        for batch in range(batch_count):
+            state.job_no = batch + 1
+            if state.skipped:
+                state.skipped = False
+            if state.interrupted:
+                break
+            state.job = f"Batch {batch + 1} out of {batch_count}"
+            sampler.noise_gen.manual_seed(a.seed + batch if a.seed != -1 else -1)
+            samples = sample_text2video(model, a.prompt, n_prompt, 1, 1, "ddim", sampler, a.steps, eta, cfg_scale, decode_frame_bs,
+                                        num_frames=frames, device_uint8=True)
+            emit(samples[0])
+    return videos if stitch is None else urls
 
 
 @torch.no_grad()
