@@ -259,6 +259,16 @@ enum t2v_gather {
  *      p[4] / p[5] + (s - alt_from) * i[21] + inner * i[10] (sequence stride i[8] as the first role); everything else as for the other
  *      samples, in the same launch (the cond | uncond pair of a guided step whose prompts have different lengths).  Not for causal
  *      launches, the p[6] scratch path or RELPOS_ATTN: refused at plan creation.
+ *      Per-sample table, optional (all zero = none; ABI 11, additive): i[22] = rows of the table (== batch_outer), i[23] = the largest
+ *      key count in it, i[24] = the K / V rows it spans (every row: first + count <= i[24]), p[7] = the table, int32 [batch_outer][2] =
+ *      {key count, first row} in device memory that nothing writes while the record runs (program data: the lowering keeps it in the
+ *      packed weight image) — outer sample s attends to table[s][0] keys at p[1] / p[2] + table[s][1] * i[8] + inner * i[10]: one key
+ *      count and one K / V location per sample, the text contexts of a batch of different prompts packed one after another without
+ *      padding.  i[1] and the outer K / V stride i[9] are not read (i[1] > 0 as always; the lowering stores i[23] there); sequence
+ *      stride, inner stride, heads and everything else as for a plain record, in the same launch; the kernel variant is chosen by i[23].
+ *      A table row outside what i[23] / i[24] allow gives that sample NaN, never a read outside the i[24] rows.  Not together with the
+ *      second role, causal launches, the p[6] scratch path or RELPOS_ATTN; a null table, i[22] != batch_outer, i[23] <= 0 or
+ *      i[24] < i[23] likewise: refused, with a message, before anything is launched.  A record without the table runs the code it ran.
  * RELPOS_ATTN: i: as ATTENTION with nk == frames of the clip (<= 32 for i[17] = 0 | 1 | 2; <= T2V_RELPOS_MAX_FRAMES for i[17] = 3),
  *      14 head_dim (multiple of 8, <= 160; 40 | 64 | 80 | 160 for i[17] = 3),
  *      15 max relative position R, 16 q_off: the nq queries are frames [q_off, q_off + nq) of the clip (nq == nk, q_off == 0

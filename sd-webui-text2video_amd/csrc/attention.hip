@@ -51,6 +51,11 @@ struct AttnParams {
   int alt_from, nk2;
   long sk2_out;
   const f16* k2; const f16* v2;
+  // per-sample table (attn_kernel<..., true> only; tab == nullptr: none): int32 [b_outer][2] = {key count, first row}; outer sample s attends
+  // to tab[s][0] keys whose K / V rows start tab[s][1] sequence rows (sk_seq) behind k / v — a batch of different prompts, packed without
+  // padding, in one launch.  nk_max / rows_all bound what the table may say: a row outside them yields no keys (NaN), never a read.
+  const int* tab;
+  int nk_max, rows_all;
 };
 
 // ---- the shared flash-attention core -----------------------------------------------------------------------------------------------
@@ -209,7 +214,7 @@ __device__ __forceinline__ void store_o_hilo(f16* orow, const f32x16 (&oacc)[NDT
 //  * attn2_kernel with the scores of tile t + 1 issued before the softmax of tile t (K tiles in a 3-deep ring): 529 / 866 TF/s against
 //    558 / 877 — the Q K^T MFMAs moved under the VALU work, but that did not hide the fp16 conversion of P, which stayed serial in
 //    front of P·V.
-template <int NW, int D, int KT = 64>
+template <int NW, int D, int KT = 64, bool TAB = false>
 __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
   constexpr int NT = NW * 64;
   constexpr int NKT = KT / 32;             // 32-key MFMA tiles per LDS tile
@@ -233,11 +238,22 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
 
   const f16* qb = p.q + bo * p.sq_out + bi * p.sq_in + head * D;
   // the sample's role (workgroup-uniform): its own key count and K / V rows; everything below works on `nk`
-  const bool alt = p.alt_from > 0 && bo >= p.alt_from;
-  const int nk = alt ? p.nk2 : p.nk;
-  const long kv_off = (alt ? (bo - p.alt_from) * p.sk2_out : bo * p.sk_out) + bi * p.sk_in + head * D;
-  const f16* kb = (alt ? p.k2 : p.k) + kv_off;
-  const f16* vb = (alt ? p.v2 : p.v) + kv_off;
+  int nk;
+  const f16 *kb, *vb;
+  if constexpr (TAB) {
+    // the sample's row of the table; the neighbours' rows lie directly before and behind its own, so every read below is bounded by `nk`
+    const int n = p.tab[2 * bo], first = p.tab[2 * bo + 1];
+    nk = (n > 0 && n <= p.nk_max && first >= 0 && first <= p.rows_all - n) ? n : 0;
+    const long kv_off = (long)first * p.sk_seq + bi * p.sk_in + head * D;
+    kb = p.k + kv_off;
+    vb = p.v + kv_off;
+  } else {
+    const bool alt = p.alt_from > 0 && bo >= p.alt_from;
+    nk = alt ? p.nk2 : p.nk;
+    const long kv_off = (alt ? (bo - p.alt_from) * p.sk2_out : bo * p.sk_out) + bi * p.sk_in + head * D;
+    kb = (alt ? p.k2 : p.k) + kv_off;
+    vb = (alt ? p.v2 : p.v) + kv_off;
+  }
   f16* ob = p.o + bo * p.so_out + bi * p.so_in + head * D;
 
   const int qrow = q0 + frow;
@@ -1223,11 +1239,17 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* in, f16*
 }
 
 // attn_kernel for head_dim D: one wave per (batch, head) for <= 32 queries (with the 32-key tile if the keys fit one), else 4 waves / 128 queries
-// (two roles: the tile of the larger key count serves both)
+// (two roles: the tile of the larger key count serves both; a per-sample table: the tile of its largest key count serves every sample)
 template <int D>
 void launch_attn(const AttnParams& p, int nbatch, hipStream_t s) {
   const bool small = p.nq <= 32;
   const dim3 g1(1, p.heads, nbatch), g4((p.nq + 127) / 128, p.heads, nbatch);
+  if (p.tab != nullptr) {
+    if (small && p.nk_max <= 32) hipLaunchKernelGGL((attn_kernel<1, D, 32, true>), g1, dim3(64), 0, s, p);
+    else if (small) hipLaunchKernelGGL((attn_kernel<1, D, 64, true>), g1, dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((attn_kernel<4, D, 64, true>), g4, dim3(256), 0, s, p);
+    return;
+  }
   if (small && (p.nk > p.nk2 ? p.nk : p.nk2) <= 32) hipLaunchKernelGGL((attn_kernel<1, D, 32>), g1, dim3(64), 0, s, p);
   else if (small) hipLaunchKernelGGL((attn_kernel<1, D, 64>), g1, dim3(64), 0, s, p);
   else hipLaunchKernelGGL((attn_kernel<4, D, 64>), g4, dim3(256), 0, s, p);
@@ -1254,6 +1276,11 @@ hipError_t t2v_launch_attention(const t2v_op& op, hipStream_t s) {
   p.k2 = reinterpret_cast<const f16*>(op.p[4]);
   p.v2 = reinterpret_cast<const f16*>(op.p[5]);
   if (p.alt_from != 0 && (p.alt_from < 0 || p.alt_from >= p.b_outer || p.nk2 <= 0 || p.sk2_out < 0 || p.k2 == nullptr || p.v2 == nullptr || p.causal || op.p[6] != 0))
+    return hipErrorInvalidValue;
+  // per-sample table (validated by the executor): i[22] = its rows (== batch_outer), i[23] = its largest key count, i[24] = K / V rows it spans
+  p.tab = op.i[22] != 0 ? reinterpret_cast<const int*>(op.p[7]) : nullptr;
+  p.nk_max = op.i[23]; p.rows_all = op.i[24];
+  if (op.i[22] != 0 && (p.tab == nullptr || op.i[22] != p.b_outer || p.nk_max <= 0 || p.rows_all < p.nk_max || p.alt_from != 0 || p.causal || op.p[6] != 0))
     return hipErrorInvalidValue;
   const int nbatch = p.b_outer * p.b_inner;
   const int hd = op.i[14] > 0 ? op.i[14] : 64;

@@ -187,6 +187,16 @@ int validate_op(const t2v_op& op, int idx) {
           return bad("attention second role: 0 < i[19] < batch_outer, i[20] keys > 0, sample stride i[21] >= 0, K / V bases p[4], p[5]");
         if (op.i[15] != 0 || op.p[6] != 0) return bad("attention second role: not for causal launches or the V^T scratch path");
       }
+      if (op.i[22] != 0 || op.i[23] != 0 || op.i[24] != 0) {       // per-sample table: every outer sample has its own key count and first K / V row
+        if (op.p[7] == 0) return bad("attention per-sample table: null table p[7]");
+        if (op.i[22] != op.i[3] || op.i[23] <= 0 || op.i[24] < op.i[23])
+          return bad("attention per-sample table: i[22] rows == batch_outer, i[23] largest key count > 0, i[24] K / V rows spanned >= i[23]");
+        if (op.i[19] != 0 || op.i[20] != 0 || op.i[21] != 0 || op.p[4] != 0 || op.p[5] != 0) return bad("attention per-sample table: not together with the second role (i[19..21], p[4], p[5])");
+        if (op.i[15] != 0) return bad("attention per-sample table: not for causal launches");
+        if (op.p[6] != 0) return bad("attention per-sample table: not for the V^T scratch path (p[6])");
+      } else if (op.p[7] != 0) {
+        return bad("attention table p[7] without its fields i[22..24]");
+      }
       return 0;
     }
     case T2V_OP_RELPOS_ATTN:
@@ -204,6 +214,7 @@ int validate_op(const t2v_op& op, int idx) {
       for (int k = 0; k < 6; ++k)
         if (op.p[k] == 0) return bad("null relative-position attention pointer");
       if (op.i[19] != 0 || op.i[20] != 0 || op.i[21] != 0) return bad("relative-position attention takes no second role (i[19..21])");
+      if (op.i[22] != 0 || op.i[23] != 0 || op.i[24] != 0) return bad("relative-position attention takes no per-sample table (i[22..24])");
       if (op.i[17] < 0 || op.i[17] > 3) return bad("relative-position attention kernel selector i[17]: 0 | 1 | 2 | 3");
       if (op.i[17] == 2 && (op.p[6] == 0 || op.p[7] == 0)) return bad("relative-position attention i[17] = 2 needs the packed fp16 tables p[6], p[7]");
       if (op.i[17] == 3 && (op.p[6] == 0 || op.p[7] == 0)) return bad("relative-position attention i[17] = 3 needs the packed fp16 tables p[6], p[7]");
@@ -647,6 +658,10 @@ bool slot_range(const t2v_op& op, int q, SlotRange* out) {
         return span((uint64_t)((outer - 1) * outer_stride + (bi - 1) * I[s0 + 2] + (n - 1) * I[s0] + heads * D) * 2);
       };
       if (q == 0) return seq(nq, 5, bo, I[6]);
+      if (!rel && I[22] != 0) {     // per-sample table: K / V are the I[24] packed rows the table spans; the table itself is I[22] pairs of int32
+        if (q == 1 || q == 2) return seq(I[24], 8, 1, 0);
+        if (q == 7) return flat((uint64_t)I[22] * 8);
+      }
       if (q == 1 || q == 2) return seq(nk, 8, bo, I[9]);
       if (q == 3) { if (!seq(nq, 11, bo, I[12])) return false; out->e += (uint64_t)(rel ? I[18] : I[16]) * 2; return true; }
       if (rel) {

@@ -45,6 +45,22 @@ class _Declarations:
         return dest
 
 
+def canonical_context_lengths(Lctx, B: int):
+    """The one form of a batch's context lengths (it is part of the program key): an int where every sample has that length, the pair
+    (Lc, Lu) where the first half of an even batch has Lc and the second half Lu, else the tuple of B lengths."""
+    if not isinstance(Lctx, (tuple, list)):
+        return int(Lctx)
+    lens = tuple(int(v) for v in Lctx)
+    if len(lens) == 2 and B != 2:
+        return lens[0] if lens[0] == lens[1] else lens
+    assert len(lens) == B, f"{len(lens)} context lengths for a batch of {B} samples"
+    if len(set(lens)) == 1:
+        return lens[0]
+    if B % 2 == 0 and len(set(lens[: B // 2])) == 1 and len(set(lens[B // 2:])) == 1:
+        return (lens[0], lens[-1])
+    return lens
+
+
 class _UNetLowering(_Declarations):
     head_per_frame = True          # statistics of the head's GroupNorm: per frame, or over all frames of a sample
 
@@ -54,20 +70,28 @@ class _UNetLowering(_Declarations):
         (SURVEY §5.7): cross-frame GroupNorm -> all-gather of statistics partials, temporal conv -> +-1 frame halo,
         temporal attention -> all-gather of K/V.  Everything else is frame-local.
         Lctx: the context length of every sample, or a pair (Lc, Lu) — the first B / 2 samples (cond) have Lc context rows each, the
-        others (uncond) Lu; the context then arrives packed, B / 2 * Lc rows followed by B / 2 * Lu rows.  Equal lengths are the int."""
+        others (uncond) Lu; the context then arrives packed, B / 2 * Lc rows followed by B / 2 * Lu rows.  Equal lengths are the int.
+        Or a tuple of B lengths, one per sample (a batch of different prompts): the context arrives packed in batch order, sum(Lctx)
+        rows, and every text cross-attention carries a per-sample table.  Lengths that the int or the pair describes ARE the int or
+        the pair (`canonical_context_lengths`): the program is then the one those forms compile to."""
         super().__init__(f"unet b{B} f{F} {H}x{W}", keep_taps)
         self.Lpair: Optional[Tuple[int, int]] = None
-        if isinstance(Lctx, (tuple, list)):
-            Lc, Lu = (int(v) for v in Lctx)
-            if Lc == Lu:
-                Lctx = Lc
-            else:
-                if shard is not None and shard.size > 1:
-                    raise L.T2VError(f"a T-sharded forward takes one context length for cond and uncond, got {Lc} and {Lu}")
-                assert B % 2 == 0, "a pair of context lengths describes a [cond | uncond] batch"
-                self.Lpair, Lctx = (Lc, Lu), max(Lc, Lu)
+        self.Lsamples: Optional[Tuple[int, ...]] = None
+        Lctx = canonical_context_lengths(Lctx, B)
+        if isinstance(Lctx, tuple) and len(Lctx) == 2:          # (two samples with their own lengths are the pair too)
+            Lc, Lu = Lctx
+            if shard is not None and shard.size > 1:
+                raise L.T2VError(f"a T-sharded forward takes one context length for cond and uncond, got {Lc} and {Lu}")
+            assert B % 2 == 0, "a pair of context lengths describes a [cond | uncond] batch"
+            self.Lpair, Lctx = (Lc, Lu), max(Lc, Lu)
+        elif isinstance(Lctx, tuple):
+            if shard is not None and shard.size > 1:
+                raise L.T2VError(f"a T-sharded forward takes one context length for every sample, got {list(Lctx)}")
+            self.Lsamples, Lctx = Lctx, max(Lctx)
         # rows of the text context (and of its K / V projections) over the whole batch
         self.ctx_rows = B * Lctx if self.Lpair is None else B // 2 * sum(self.Lpair)
+        if self.Lsamples is not None:
+            self.ctx_rows = sum(self.Lsamples)
         self.shard: Optional[TShardSpec] = shard if (shard is not None and shard.size > 1) else None
         if self.shard is not None:
             assert B == 1, "T-sharded forwards run one sample per rank (the CFG pair is split over ranks)"
@@ -138,6 +162,13 @@ class _UNetLowering(_Declarations):
             return b[pk.geglu_perm(b.shape[0] // 2, b.device)]
         return (Ref("weight", 0, self.packer.add(key + ":geglu", "f16", wfn)),
                 Ref("weight", 0, self.packer.add(key + ":geglu_b", "f32", bfn)))
+
+    def attention_table(self, lens, starts) -> Ref:
+        """The per-sample table of a text cross-attention, int32 [samples][2] = {key count, first row}: read-only program data, so it
+        lives in the packed weight image (as the tap tables of T2V_OP_RESAMPLE) and the arena holds nothing new."""
+        rows = [[int(n), int(r)] for n, r in zip(lens, starts)]
+        name = "context.table:" + ",".join(f"{n}@{r}" for n, r in rows)
+        return Ref("weight", 0, self.packer.add(name, "i32", lambda sd, rows=rows: torch.tensor(rows, dtype=torch.int32)))
 
     def ln_arg(self, key, out: Buf, eps: float = 1e-5) -> tuple:
         """`ln=` argument of Program.gemm for the LayerNorm `key` applied to a GEMM's fp32 result: fused into the epilogue of the
@@ -314,6 +345,10 @@ class _UNetLowering(_Declarations):
             q = P.alloc(Mq, inner, "f16")
             P.gemm(attn + ".to_q", nrm, self.w_linear(attn + ".to_q"), inner, inner, q)
         if q is not None:
+            if self.Lsamples is not None:
+                # every sample with its own context length, still ONE launch: sample s reads Lsamples[s] rows behind those of samples 0 .. s-1
+                starts = [sum(self.Lsamples[:b]) for b in range(self.B)]
+                attn_kw = dict(attn_kw, table=(self.attention_table(self.Lsamples, starts), self.Lsamples, starts))
             if self.Lpair is not None:
                 # cond | uncond with their own context lengths, still ONE launch: samples V .. B-1 read the rows behind the V * Lc cond rows
                 V, (Lc, Lu) = self.B // 2, self.Lpair
@@ -321,7 +356,7 @@ class _UNetLowering(_Declarations):
                 attn_kw = dict(attn_kw, alt=(V, Lu, k2.ref, v2.ref, Lu * kv.ld))
             P.attention(attn, q.ref, kbuf.ref, vbuf.ref, a.ref, out_buf=a, nq=hw, nk=Lc, heads=heads,
                         b_outer=self.Bc, b_inner=F, q_strides=(inner, q_b_stride, hw * inner),
-                        kv_strides=(kv.ld, Lc * kv.ld, 0), o_strides=(lo, F * hw * lo, hw * lo), scale=scale, **attn_kw)
+                        kv_strides=(kv.ld, 0 if self.Lsamples is not None else Lc * kv.ld, 0), o_strides=(lo, F * hw * lo, hw * lo), scale=scale, **attn_kw)
             P.free(q)
         P.free(nrm)
         return a, shared_rows

@@ -148,17 +148,28 @@ class TextToVideoSynthesis(object):
             raise RuntimeError("no text encoder attached: pass clip_encoder=... (the reference's "
                                "FrozenOpenCLIPEmbedder) or call infer_conditioned(c, uc, ...)")
         enc = self.clip_encoder
-        c = enc([prompt]) if callable(enc) else enc.encode([prompt])
-        uc = enc([n_prompt]) if callable(enc) else enc.encode([n_prompt])
-        return c, uc
+        encode = (lambda text: enc([text])) if callable(enc) else (lambda text: enc.encode([text]))
+        if isinstance(prompt, (list, tuple)) or isinstance(n_prompt, (list, tuple)):
+            # a batch of different prompts: lists of contexts, one per video.  Every prompt goes through an encoder call of ITS OWN — the
+            # reference's embedder pads all prompts of one call to the longest one's chunk count (clip_hardcode.py, chunk_count = max(...)),
+            # which would change the shorter prompts' contexts.  A text that occurs several times is encoded once.
+            prompts, n_prompts = _prompt_lists(prompt, n_prompt)
+            done = {}
+            one = lambda text: done[text] if text in done else done.setdefault(text, encode(text))
+            return [one(t) for t in prompts], [one(t) for t in n_prompts]
+        return encode(prompt), encode(n_prompt)
 
     # ---- the hot path ---------------------------------------------------------------------------
     @torch.no_grad()
     def infer_conditioned(self, c, uc, steps, frames, seed, scale, width=256, height=256, eta=0.0,
                           device=None, latents=None, strength=None, mask=None, is_vid2vid=False,
                           sampler=available_samplers[0].name, decode=True, to_host=True, _keep_sampler=False,
-                          videos: int = 1, *, clamp=None, percentile=None, unipc=None):
+                          videos: int = 1, *, clamp=None, percentile=None, unipc=None, seeds=None):
         """Stages 2-4 of `infer` for given conditioning tensors c, uc [1, 77k, 1024].
+        A batch of DIFFERENT prompts: c / uc as lists of `videos` tensors [1, 77k_v, 1024] (a single tensor beside a list = that prompt for
+        every video; lists of one entry = the tensor), contexts of any lengths — still one 2*videos forward per step, the text
+        cross-attentions with one key count per sample.  `seeds`: a list of `videos` ints, video v starts from the noise of seeds[v]
+        (default seed + v).  txt2vid and vid2vid on one device, as `videos` > 1.
         `unipc` (UniPC only; another sampler raises ValueError): a dict of the solver options of `samplers.UniPCSampler` (variant,
         skip_type, order, lower_order_final, initial_corrector, denoise_to_zero, thresholding); forwarded only when set.
         `clamp` / `percentile` (DDIM_Gaussian only; another sampler raises ValueError): the restriction of the predicted x0 of
@@ -171,12 +182,23 @@ class TextToVideoSynthesis(object):
         `tensor2vid` gives a batch, t2v_pipeline.py:447-460).  Video v starts from the noise of seed + v, i.e. the batch is
         the reference's `batch_count` loop (process_modelscope.py:152-221: one video at a time, seed + batch) in one pass."""
         dev = torch.device(device) if device is not None else self.device
+        c, uc, videos, seeds = _batch_arguments(c, uc, videos, seed, seeds)
+        several = isinstance(c, list) or isinstance(uc, list)
+        if several:
+            if mask is not None or (latents is not None and not is_vid2vid):
+                raise NotImplementedError("a batch of different prompts: text-to-video and vid2vid only — the img2vid route draws every "
+                                          "video's latents from numpy's global generator (process_modelscope.py:205), one call per video")
+            if getattr(self.sd_model, "t_shard", None) is not None:
+                raise NotImplementedError("a batch of different prompts is not supported in the T-shard multi-GPU layout (a clip whose frames "
+                                          "are split over ranks runs one video per batch)")
         self.device = dev
         self.diffusion.device = dev
         self.sd_model.to(dev)
         if not _keep_sampler:
             self.diffusion.get_sampler(sampler, return_sampler=False)
-        latents, noise, shape = self.diffusion.get_noise(1, 4, frames, height, width, seed=seed, latents=latents)
+        if several and getattr(self.diffusion.sampler, "cfg_parallel", None) is not None and self.diffusion.sampler.cfg_parallel.size == 2:
+            raise NotImplementedError("a batch of different prompts is not supported in the CFG-pair multi-GPU layout (it runs one video per pair)")
+        latents, noise, shape = self.diffusion.get_noise(1, 4, frames, height, width, seed=seeds[0], latents=latents)
         if videos > 1:
             if mask is not None or (latents is not None and not is_vid2vid):
                 raise NotImplementedError("several videos per batch: text-to-video and vid2vid only — the img2vid route draws every "
@@ -186,12 +208,12 @@ class TextToVideoSynthesis(object):
             one = (1,) + tuple(shape[1:])
             draws = []
             for v in range(videos):                      # each video from its own seed, as the batch_count loop draws them
-                self.diffusion.noise_gen.manual_seed(seed + v)
+                self.diffusion.noise_gen.manual_seed(seeds[v])
                 draws.append(torch.randn(one, generator=self.diffusion.noise_gen))
             noise = torch.cat(draws, dim=0).to(dev)
             shape = (videos,) + tuple(shape[1:])
         x0 = self.diffusion.sample_loop(
-            steps=steps, strength=strength, eta=eta, conditioning=c.to(dev), unconditional_conditioning=uc.to(dev),
+            steps=steps, strength=strength, eta=eta, conditioning=_to(c, dev), unconditional_conditioning=_to(uc, dev),
             batch_size=videos, guidance_scale=scale, latents=latents, shape=shape, noise=noise, is_vid2vid=is_vid2vid,
             sampler_name=sampler, mask=mask, **_restriction(clamp, percentile, unipc))
         self.last_tensor = x0
@@ -295,6 +317,42 @@ class TextToVideoSynthesis(object):
         return frames_bgr, self.last_tensor, create_infotext(vars_)
 
 
+def _to(c, dev):
+    return [v.to(dev) for v in c] if isinstance(c, list) else c.to(dev)
+
+
+def _prompt_lists(prompt, n_prompt):
+    """prompts / negative prompts of a batch -> two lists of one length; a single text (or a list of one) on either side is broadcast."""
+    prompts = list(prompt) if isinstance(prompt, (list, tuple)) else [prompt]
+    n_prompts = list(n_prompt) if isinstance(n_prompt, (list, tuple)) else [n_prompt]
+    n = max(len(prompts), len(n_prompts))
+    if not prompts or not n_prompts or any(len(v) not in (1, n) for v in (prompts, n_prompts)):
+        raise ValueError(f"{len(prompts)} prompts against {len(n_prompts)} negative prompts: give one negative prompt, or one per prompt")
+    return prompts * (n // len(prompts)), n_prompts * (n // len(n_prompts))
+
+
+def _batch_arguments(c, uc, videos, seed, seeds):
+    """The conditioning / videos / seeds arguments of `infer_conditioned` in one form: -> (c, uc, videos, seeds) with c / uc tensors, or lists
+    of `videos` tensors for a batch of different prompts, and seeds a list of `videos` ints."""
+    lists = [v for v in (c, uc) if isinstance(v, (list, tuple))]
+    n = max((len(v) for v in lists), default=1)
+    if any(len(v) not in (1, n) for v in lists) or not all(len(v) for v in lists):
+        raise ValueError(f"conditioning lists of {[len(v) for v in lists]} entries: give one tensor, or one per video")
+    if n > 1:
+        if videos not in (1, n):
+            raise ValueError(f"videos={videos} with conditioning lists of {n} entries")
+        videos = n
+        c, uc = (list(v) * (n // len(v)) if isinstance(v, (list, tuple)) else v for v in (c, uc))
+    else:
+        c, uc = (v[0] if isinstance(v, (list, tuple)) else v for v in (c, uc))          # lists of one entry: today's path
+    if seeds is None:
+        seeds = [seed + v for v in range(videos)]
+    seeds = [int(v) for v in seeds]
+    if len(seeds) != videos:
+        raise ValueError(f"seeds: {len(seeds)} seeds for {videos} videos")
+    return c, uc, videos, seeds
+
+
 def _restriction(clamp, percentile, unipc=None) -> dict:
     """The x0-restriction keywords and the UniPC options that are set — nothing is forwarded when none is, so a call without them is
     what it was."""
@@ -352,6 +410,11 @@ def process_modelscope(args_dict: dict, extra_args=None):
       with neither key present the call is what it was.
     * `unipc` = a dict of UniPC's solver options (variant, skip_type, order, lower_order_final, initial_corrector, denoise_to_zero,
       thresholding: `samplers.UniPCSampler`); UniPC only, and without the key the call is what it was.  webui's `shared.opts` is not read.
+    * `prompts` = [...] / `n_prompts` = [...] (or `conds` = [...] / `unconds` = [...], lists of context tensors) and optionally
+      `seeds` = [...]: a batch of DIFFERENT prompts in ONE pass, one video per entry (a single negative prompt, or `prompt` / `cond`
+      beside a list, is broadcast; every prompt is encoded by an encoder call of its own).  Video v starts from seeds[v] (default
+      seed + v).  Without `stitch` the frames come back side by side; with it they are split per video and every video is stitched:
+      one data-URL per prompt.  txt2vid and vid2vid; refused together with batch_count > 1 and on the img2vid route.
     * `stitch(frames_bgr, infotext) -> bytes` (the ffmpeg stage, out of scope — e.g. the reference's own
       `ffmpeg_stitch_video` behind a temp directory) given: returns the reference's list of data-URLs, video b from
       seed + b (seed -1 stays random), exactly the reference loop;
@@ -445,6 +508,40 @@ def process_modelscope(args_dict: dict, extra_args=None):
     else:
         latents, strength, skip_steps = None, 1, 0            # `args.strength = 1` (:145): UniPC starts at t_start = 1.0, like ns.T
 
+    if any(getattr(a, k, None) is not None for k in ("prompts", "n_prompts", "conds", "unconds", "seeds")):
+        # a batch of different prompts: ONE pass, one video per prompt
+        if batch_count > 1:
+            raise ValueError("prompts / conds lists make one pass with one video per entry: not together with batch_count > 1 "
+                             "(repeat an entry to have several videos of it)")
+        if inpainting:
+            raise NotImplementedError("a batch of different prompts: text-to-video and vid2vid only — the img2vid route draws every "
+                                      "video's latents from numpy's global generator (process_modelscope.py:205), one call per video")
+        seed = a.seed if a.seed != -1 else random.randint(0, 2 ** 32 - 1)
+        if have_cond or getattr(a, "conds", None) is not None or getattr(a, "unconds", None) is not None:
+            pick = lambda many, one: getattr(a, many) if getattr(a, many, None) is not None else getattr(a, one)
+            cs, ucs, texts = pick("conds", "cond"), pick("unconds", "uncond"), None
+        else:
+            texts = _prompt_lists(getattr(a, "prompts", None) if getattr(a, "prompts", None) is not None else a.prompt,
+                                  getattr(a, "n_prompts", None) if getattr(a, "n_prompts", None) is not None else getattr(a, "n_prompt", ""))
+            cs, ucs = pipe.preprocess(texts[0], texts[1], a.steps - skip_steps)
+        seeds = getattr(a, "seeds", None)
+        n = max([len(v) for v in (cs, ucs, seeds) if isinstance(v, (list, tuple))], default=1)
+        seeds = [int(v) for v in seeds] if seeds is not None else [seed + v for v in range(n)]
+        if "half precision" in str(cpu_vae) and getattr(pipe, "autoencoder", None) is not None:
+            pipe.autoencoder.half()
+        vid = dict(latents=latents, strength=strength, is_vid2vid=True, device=device) if do_vid2vid else {}
+        frames, _ = pipe.infer_conditioned(cs, ucs, a.steps - skip_steps, seed=seeds[0], seeds=seeds, videos=n, **vid, **common)
+        if stitch is None:
+            return frames                       # side by side, video v in columns [v * width, (v + 1) * width)
+        import base64
+        urls = []
+        for v in range(n):
+            info = "" if texts is None else create_infotext(dict(prompt=texts[0][v], n_prompt=texts[1][v], steps=a.steps, frames=a.frames,
+                                                                 seed=seeds[v], scale=a.cfg_scale, width=width, height=height,
+                                                                 eta=common["eta"], sampler=common["sampler"]))
+            own = [f[:, v * width:(v + 1) * width] for f in frames]
+            urls.append("data:video/mp4;base64," + base64.b64encode(stitch(own, info)).decode())
+        return urls
     if have_cond and stitch is None and not do_vid2vid and not inpainting:
         frames, _ = pipe.infer_conditioned(a.cond, a.uncond, steps=a.steps, seed=a.seed, videos=batch_count, **common)
         return frames

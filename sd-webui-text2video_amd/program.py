@@ -969,7 +969,8 @@ class Program:
                   rel_k: Optional[Ref] = None, rel_v: Optional[Ref] = None, max_rel: int = 0, causal: bool = False,
                   q_offset: int = 0, relpos_mfma: Optional[int] = None, lo_off: int = 0,
                   rel_k16: Optional[Ref] = None, rel_vT16: Optional[Ref] = None, rel_k_long: Optional[Ref] = None,
-                  rel_vT_long: Optional[Ref] = None, vt_scratch: Optional[Buf] = None, waves: int = 0, alt: Optional[tuple] = None) -> Op:
+                  rel_vT_long: Optional[Ref] = None, vt_scratch: Optional[Buf] = None, waves: int = 0, alt: Optional[tuple] = None,
+                  table: Optional[tuple] = None) -> Op:
         """softmax(q k^T scale) v over strided (sequence, outer, inner) batches.  With rel_k / rel_v (fp32
         [2*max_rel+1, head_dim] tables) the LVDM relative-position temporal attention op is emitted instead.
         lo_off (elements): also store the low-order fp16 image of every output value at o + lo_off (rows [hi | lo] for a K-doubled
@@ -977,7 +978,10 @@ class Program:
         rel_k_long / rel_vT_long: the same tables packed for the kernel of clips of any length (packing.relpos_table_long); required
         for clips of more than 32 frames, which only that kernel runs.
         alt = (alt_from, nk2, k2, v2, sample_stride2): a second role in the same launch — outer samples >= alt_from attend to nk2 keys at
-        k2 / v2 (outer sample s at + (s - alt_from) * sample_stride2 elements; sequence and inner strides as the first role)."""
+        k2 / v2 (outer sample s at + (s - alt_from) * sample_stride2 elements; sequence and inner strides as the first role).
+        table = (ref, lens, starts): a per-sample table in the same launch — ref names read-only int32 [b_outer][2] program data holding
+        {lens[s], starts[s]}; outer sample s attends to lens[s] keys whose rows start starts[s] sequence rows behind k / v (`nk` and the
+        outer K / V stride are then not read: pass the largest count).  `attention_table` makes the data."""
         assert head_dim in (40, 64, 80, 160) or rel_k is not None
         op = Op(L.OP_ATTENTION if rel_k is None else L.OP_RELPOS_ATTN, name)
         op.i[0:5] = [nq, nk, heads, b_outer, b_inner]
@@ -1030,6 +1034,12 @@ class Program:
             assert rel_k is None and not causal and vt_scratch is None and 0 < alt_from < b_outer and nk2 > 0 and 0 <= stride2 < 2 ** 31
             op.i[19], op.i[20], op.i[21] = alt_from, nk2, stride2
             op.p[4], op.p[5] = k2, v2
+        if table is not None:
+            tref, lens, starts = table
+            assert rel_k is None and alt is None and not causal and vt_scratch is None and len(lens) == len(starts) == b_outer
+            assert all(n > 0 and r >= 0 for n, r in zip(lens, starts)) and nk == max(lens)
+            op.i[22], op.i[23], op.i[24] = b_outer, max(lens), max(r + n for n, r in zip(lens, starts))
+            op.p[7] = tref
         op.i[5:8] = list(q_strides)
         op.i[8:11] = list(kv_strides)
         op.i[11:14] = list(o_strides)
@@ -1040,6 +1050,8 @@ class Program:
         op.flops = 4.0 * nq * nk * head_dim * heads * b_outer * b_inner
         if alt is not None:
             op.flops = 4.0 * nq * head_dim * heads * b_inner * (nk * alt[0] + alt[1] * (b_outer - alt[0]))
+        if table is not None:
+            op.flops = 4.0 * nq * head_dim * heads * b_inner * sum(table[1])
         op.out = out_buf
         return self._emit(op)
 

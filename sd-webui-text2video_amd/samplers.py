@@ -49,10 +49,63 @@ except Exception:  # pragma: no cover
 
 def reconstruct_conds(cond, uncond, step):
     """t2v_helpers/general_utils.py:27-30 — webui prompt schedules; identity for plain tensors."""
-    if _prompt_parser is not None and not torch.is_tensor(cond):
+    if _prompt_parser is not None and not torch.is_tensor(cond) and not _is_ctx_list(cond):
         return (_prompt_parser.reconstruct_cond_batch(cond, step),
                 _prompt_parser.reconstruct_cond_batch(uncond, step))
     return cond, uncond
+
+
+# ---- a batch of different prompts: conditioning as a list of one context per video ----------------------------------------------------
+def _is_ctx_list(c) -> bool:
+    return isinstance(c, (list, tuple)) and len(c) > 0 and all(torch.is_tensor(v) for v in c)
+
+
+def batch_contexts(cond, uncond, videos: int):
+    """`conditioning` / `unconditional_conditioning` given as lists of one context per video ([1, L_v, ctx] or [L_v, ctx]) -> what the
+    loops below work on.  A list of one entry is that tensor, and lists whose entries have one length per role are the tensors
+    [videos, L, ctx]: both take the paths tensors take.  Otherwise (lengths that differ between videos) -> two lists of `videos` contexts
+    [1, L_v, ctx], a single tensor on the other side repeated per video; the model evaluates them as ONE forward per step."""
+    if not (_is_ctx_list(cond) or _is_ctx_list(uncond)):
+        return cond, uncond
+
+    def entries(c):
+        if c is None:
+            return None
+        vs = [v if v.ndim == 3 else v[None] for v in c] if _is_ctx_list(c) else ([c] if c.shape[0] == 1 else list(c.split(1, dim=0)))
+        assert all(v.ndim == 3 and v.shape[0] == 1 for v in vs), "a list of contexts holds one [1, L, ctx] or [L, ctx] tensor per video"
+        if len(vs) == 1:
+            return vs * videos
+        if len(vs) != videos:
+            raise ValueError(f"{len(vs)} contexts for a batch of {videos} videos")
+        return vs
+
+    cs, us = entries(cond), entries(uncond)
+    if all(len({v.shape[1] for v in side}) == 1 for side in (cs, us) if side is not None):
+        one = lambda c, vs: c if not _is_ctx_list(c) else (vs[0] if len(c) == 1 else torch.cat(vs, dim=0))
+        return one(cond, cs), (None if us is None else one(uncond, us))
+    return cs, us
+
+
+def _eval_ragged(model, x, tt, c, uc, guided: bool, token, cfg_parallel=None):
+    """One forward of a batch whose videos have contexts of different lengths (lists from `batch_contexts`): -> eps [videos] or, guided,
+    [cond (videos) | uncond (videos)]."""
+    if cfg_parallel is not None and cfg_parallel.size == 2:
+        raise L.T2VError("a batch of different prompts is not supported in the CFG-pair multi-GPU layout: it runs one video per pair")
+    if getattr(model, "t_shard", None) is not None:
+        raise L.T2VError(f"a batch of different prompts ({[v.shape[1] for v in c]} tokens) is not supported with a clip whose frames are split "
+                         "over ranks")
+    if not hasattr(model, "forward_cfg_pair"):
+        raise L.T2VError("a batch of different prompts needs a model with forward_cfg_pair (UNetSD)")
+    if not guided:
+        model.context_token = token
+        return model(x, tt, list(c))
+    return model.forward_cfg_pair(x, tt, (list(c), list(uc)), context_token=token, single_t=True)
+
+
+def _ctx_ident(nonce, c, uc, *more):
+    """Names the content of the conditioning objects of a run (tensors or lists of tensors), for the model's context cache."""
+    flat = lambda v: () if v is None else tuple((id(e), e._version) for e in (v if isinstance(v, (list, tuple)) else (v,)))
+    return (nonce, flat(c), flat(uc)) + more
 
 
 # ---- boundary B3 (SURVEY §8b) -------------------------------------------------------------------------------------
@@ -211,6 +264,7 @@ class GaussianDiffusion(object):
         inner = Fr * Hh * Ww
         x_dt = "f16" if xt.dtype == torch.float16 else "f32"
         thresholds = None
+        conditioning, unconditional_conditioning = batch_contexts(conditioning, unconditional_conditioning, Bx)
         if restricted:
             if getattr(model, "t_shard", None) is not None or (self.shared_noise is not None and self.shared_noise.total != Fr):
                 raise L.T2VError("clamp / percentile / condition_fn with a clip whose frames are split over ranks: the restriction of x0 "
@@ -243,11 +297,17 @@ class GaussianDiffusion(object):
                 c0, uc0 = c, uc
                 t = int(all_t[step])
                 tt = tt_all[step, :Bx]
-                if Bx > 1:
+                ragged = isinstance(c, list)           # a batch of different prompts (batch_contexts): one forward of 2 * Bx samples all the same
+                if Bx > 1 and not ragged:
                     c = c.expand(Bx, *c.shape[1:]) if c.shape[0] == 1 else c
                     if uc is not None:
                         uc = uc.expand(Bx, *uc.shape[1:]) if uc.shape[0] == 1 else uc
-                if self.is_unconditional(guide):
+                if ragged:
+                    unguided = self.is_unconditional(guide)
+                    eps = _eval_ragged(model, xt, tt if unguided else tt_all[step], c, uc, not unguided,
+                                       _ctx_ident(run_nonce, c0, None if unguided else uc0, Bx), self.cfg_parallel)
+                    guided, gscale = (0, 1.0) if unguided else (C // 2 if not self.var_type.startswith("fixed") else C, float(guide))
+                elif self.is_unconditional(guide):
                     eps = model(xt, tt, c)
                     guided, gscale = 0, 1.0
                 elif self.cfg_parallel is not None and self.cfg_parallel.size == 2:
@@ -529,6 +589,10 @@ def _eval_eps_pair(model, x, t_value, c, uc, guide, cfg_parallel=None, cache: Op
     B = x.shape[0]                            # videos per batch: one timestep for all of them, eps = [cond (B), uncond (B)]
     tt = torch.full((B,), float(t_value), dtype=torch.float32, device=dev)
     c0, uc0 = c, uc
+    if isinstance(c, list):                   # a batch of different prompts (batch_contexts)
+        guided = not (guide is None or guide == 1.0 or uc is None)
+        nonce = cache.setdefault("nonce", next(_RUN_COUNTER)) if cache is not None else next(_RUN_COUNTER)
+        return _eval_ragged(model, x, tt, c, uc, guided, _ctx_ident(nonce, c, uc if guided else None), cfg_parallel).contiguous(), guided
     if B > 1:                                 # conditioning of batch 1 is expanded, conditioning of batch B is taken per video
         c = c.expand(B, *c.shape[1:]) if c.shape[0] == 1 else c
         if uc is not None:
@@ -590,6 +654,7 @@ class DDIMSampler(object):
         model, dev = self.model, img.device
         C = img.shape[1]
         _check_batch_layout(self, img.shape[0])     # several videos per batch: one 2V-row forward and one update launch per step
+        cond, uncond = batch_contexts(cond, uncond, img.shape[0])
         nxt = torch.empty_like(img)
         if hasattr(model, "verify_weights"):
             model.verify_weights(dev)           # the bytes: in-place edits (`w.data += d`) that no version counter shows — once per call
@@ -827,6 +892,7 @@ class UniPCSampler(object):
             raise L.T2VError("thresholding needs an fp32 latent x_T")
         x = x.float().contiguous()
         _check_batch_layout(self, x.shape[0])
+        conditioning, unconditional_conditioning = batch_contexts(conditioning, unconditional_conditioning, x.shape[0])
         ns = _VPSchedule(self.alphas_cumprod)
         order, steps = opt["order"], S
         assert steps >= order

@@ -31,7 +31,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import packing as pk
-from .lowering import _UNetLowering
+from .lowering import _UNetLowering, canonical_context_lengths
 from .program import COLLECTIVE_KINDS, BoundProgram, Buf, Program, Ref
 
 
@@ -232,7 +232,8 @@ class UNetSD(nn.Module):
         self.gn_producer_stats = L.knob("T2V_GN_STRIPS", "0") != "0"
         self.context_token = None     # one-shot hint consumed by the next forward (see forward_cfg_pair)
         self._pair_lens = None        # one-shot: (Lc, Lu) of a packed [cond | uncond] context (forward_cfg_pair)
-        self._pair_ctx = None         # (context token, packed context, lengths) of the last unequal pair
+        self._pair_ctx = None         # (context token, packed context, lengths) of the last unequal pair / batch of different prompts
+        self._sample_lens = None      # one-shot: the length of every sample of a packed batch of different contexts (`_context_batch`)
         # one-shot hint consumed by the next forward: every sample of the batch has the SAME timestep (forward_cfg_pair and the samplers
         # of this package set it).  Only then may the cond | uncond pair share its prefix — the shared ops use sample 0's time embedding,
         # and forward(x[1], t = [t0, t1], ctx[2]) with t0 != t1 must keep each sample's own t
@@ -484,11 +485,17 @@ class UNetSD(nn.Module):
         hint_single, self.single_timestep = bool(self.single_timestep), False
         # one-shot too (`forward_cfg_pair` with unequal lengths): y is the packed context [V * Lc + V * Lu, ctx] of a [cond | uncond] batch
         pair_lens, self._pair_lens = getattr(self, "_pair_lens", None), None
+        sample_lens, self._sample_lens = getattr(self, "_sample_lens", None), None
+        if isinstance(y, (list, tuple)):          # an unguided batch of different contexts: one [1, L_v, ctx] or [L_v, ctx] per sample
+            y, pair_lens, sample_lens = self._context_batch(list(y), self.context_token)
         if not x.is_cuda:
             raise L.T2VError("UNetSD.forward needs device tensors on an AMD GPU (no CPU fallback); "
                              "use oracle/torch_port.py for a CPU reference")
         Bx, C, F, H, W = x.shape
-        if pair_lens is None:
+        if sample_lens is not None:
+            assert y.ndim == 2 and y.shape[0] == sum(sample_lens)
+            B, Lctx = len(sample_lens), tuple(sample_lens)
+        elif pair_lens is None:
             B, Lctx = y.shape[0], y.shape[1]
         else:
             assert y.ndim == 2 and y.shape[0] % sum(pair_lens) == 0
@@ -516,6 +523,9 @@ class UNetSD(nn.Module):
             if pair_lens is not None:
                 raise L.T2VError(f"T-sharded forward: cond and uncond contexts of different lengths ({pair_lens[0]} and {pair_lens[1]} tokens) "
                                  "are not supported; run one role per rank, or pad the prompts to one length")
+            if sample_lens is not None:
+                raise L.T2VError(f"T-sharded forward: a batch of contexts of different lengths ({list(sample_lens)} tokens) is not supported; "
+                                 "run the prompts one after another, or pad them to one length")
         single = hint_single or tf.numel() == 1 or t.ndim == 0
         if not single and not tf.is_cuda:
             single = bool((tf == tf.reshape(-1)[0]).all())
@@ -571,7 +581,13 @@ class UNetSD(nn.Module):
         Unequal lengths (a prompt of several 77-token chunks against a short negative prompt): still ONE program — the two contexts
         are packed without padding (V * Lc rows, then V * Lu rows; built once per `context_token`), every text cross-attention is one
         launch whose samples take the key count and K / V rows of their role, as the reference's two forwards do."""
-        pair_lens = None
+        pair_lens = sample_lens = None
+        if isinstance(ctx_pair, (tuple, list)) and any(isinstance(v, (tuple, list)) for v in ctx_pair):
+            # a batch of different prompts: conds / unconds as lists of V contexts [1, L_v, ctx] or [L_v, ctx] (a tensor [V, L, ctx] beside
+            # a list counts as its V rows).  Lengths that one tensor or the pair describes take those paths, bit for bit.
+            c, uc = ([v for v in side] if isinstance(side, (tuple, list)) else list(side.unbind(0)) for side in ctx_pair)
+            assert len(c) == len(uc), f"{len(c)} cond contexts against {len(uc)} uncond contexts"
+            ctx_pair, pair_lens, sample_lens = self._context_batch(c + uc, context_token)
         if isinstance(ctx_pair, (tuple, list)):
             c, uc = ctx_pair
             assert c.ndim == 3 and uc.ndim == 3 and c.shape[0] == uc.shape[0] and c.shape[2] == uc.shape[2]
@@ -586,6 +602,8 @@ class UNetSD(nn.Module):
                     held = self._pair_ctx = (context_token, packed, pair_lens)
                 ctx_pair = held[1]
         B = ctx_pair.shape[0] if pair_lens is None else 2 * (ctx_pair.shape[0] // sum(pair_lens))
+        if sample_lens is not None:
+            B = len(sample_lens)
         tt = t.to(device=x.device, dtype=torch.float32).reshape(-1)
         if single_t is None:          # one t for every sample?  (a [1] tensor: yes; per-sample values: compared — the samplers say it outright)
             single_t = tt.shape[0] == 1 or bool((tt == tt[0]).all())
@@ -593,7 +611,29 @@ class UNetSD(nn.Module):
         self.context_token = context_token
         self.single_timestep = bool(single_t)
         self._pair_lens = pair_lens
+        self._sample_lens = sample_lens
         return UNetSD.forward(self, x, tt, ctx_pair)
+
+    def _context_batch(self, seqs, context_token):
+        """The contexts of a batch, one tensor [1, L, ctx] or [L, ctx] per sample -> (y, pair_lens, sample_lens) as `forward` takes them:
+        one length: y [B, L, ctx]; the lengths of a pair: the packed pair and pair_lens; else every sample's rows in batch order without
+        padding, [sum L, ctx], and sample_lens.  The packed tensor is built once per `context_token` (as the pair's)."""
+        seqs = [v.reshape(-1, v.shape[-1]) for v in seqs]
+        assert seqs and all(v.shape[1] == seqs[0].shape[1] and v.shape[0] > 0 for v in seqs)
+        lens = canonical_context_lengths([v.shape[0] for v in seqs], len(seqs))
+        key = ("batch", tuple(v.shape[0] for v in seqs))
+        held = getattr(self, "_pair_ctx", None)
+        if context_token is None or held is None or held[0] != context_token or held[2] != key:
+            dt = seqs[0].dtype
+            for v in seqs[1:]:
+                dt = torch.promote_types(dt, v.dtype)
+            held = self._pair_ctx = (context_token, torch.cat([v.to(dt) for v in seqs], dim=0), key)
+        packed = held[1]
+        if isinstance(lens, int):
+            return packed.reshape(len(seqs), lens, -1), None, None
+        if len(lens) == 2:
+            return packed, lens, None
+        return packed, None, lens
 
     max_programs = 4      # compiled geometries kept (each owns a device arena: 0.4 GiB per 24-frame sample, GiBs for long clips)
 
@@ -843,7 +883,7 @@ class _Lowering(_UNetLowering):
     def to_q_attention(self, attn, nrm: Buf, a: Buf, inner, heads, hw, scale, wrap: int) -> bool:
         """to_q + the 77-key attention as ONE launch (round 5): q never reaches HBM.  (At the parting site the projection runs
         for both samples from the one sample's rows: the A-operand row wrap.)"""
-        if self.vt_all is None or (self.F * hw) % 32 != 0 or self.Lctx > 96 or self.Lpair is not None:
+        if self.vt_all is None or (self.F * hw) % 32 != 0 or self.Lctx > 96 or self.Lpair is not None or self.Lsamples is not None:
             return False
         k0, _ = self.kv_slices[attn]
         vt = self.vt_all.row_slice(self.vt_slices[attn], self.vt_all.rows)           # this site's rows first; sample stride = all rows of a sample
@@ -944,7 +984,7 @@ class _Lowering(_UNetLowering):
     def prologue_alloc(self, sites):
         # V^T of the text context for the fused to_q + cross-attention launches: rows = the value channels of every site, keys contiguous
         # (padded to a multiple of 32, zero beyond the context length: allocated here, never freed before the end, zero from the bind)
-        if not (self.shard is None and self.Lctx <= 96 and self.Lpair is None and bool(getattr(self.net, "fused_cross_attention", True))
+        if not (self.shard is None and self.Lctx <= 96 and self.Lpair is None and self.Lsamples is None and bool(getattr(self.net, "fused_cross_attention", True))
                 and all(c % 64 == 0 for _, c in sites)):
             return []
         off = 0
