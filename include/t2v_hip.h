@@ -35,6 +35,8 @@ extern "C" {
                                classifier-guidance term of DDIM_Gaussian) — additive on fields that every earlier record leaves zero;
                                still 11: DDIM_STEP i[5] = 2 (UniPC's thresholded data prediction: a measure and an apply record) — a mode value that every earlier
                                library refuses, records with i[5] in {0, 1} are validated and run as before;
+                               still 11: DDIM_STEP i[5] = 3 (the DDIM inversion step of DDIMSampler.encode, with the optional second destination p[4]) — a mode
+                               value that every earlier library refuses, records with i[5] in {0, 1, 2} are validated and run as before;
                                still 11: T2V_OP_EMPHASIS (a new kind: no existing record changes, and a library without it refuses the record as an unknown op kind) and
                                ATTENTION i[19..21] / p[4..5] (a second role; additive on fields every earlier record leaves zero);
                                still 11: T2V_OP_FINGERPRINT (a new kind, stand-alone: 64-bit fingerprints of a table of byte ranges; no existing record changes);
@@ -331,6 +333,14 @@ enum t2v_gather {
  *          i[8] = 2  out = min(max(x0, -s), s) / s,  s = table[sample][0]   (torch.clamp with tensor bounds; NaN in s or x0 -> NaN)
  *        i[8] = 0 | 1 are refused: the plain data prediction is a LINCOMB, and the class has no clamp.  n = channels * inner <= 16 777 216.
  *        f: 0 sigma_t, 1 alpha_t, 5 guidance scale, 6 quantile (i[8] = 3);  p: 0 x, 1 eps pair, 3 out (i[8] = 2), 7 table [samples, 4]
+ *      mode 3 (DDIM inversion, one step of DDIMSampler.encode, samplers/ddim/sampler.py:242-254; fp32 x, i[7] = i[8] = i[9] = 0 or refused):
+ *          e = eu + f5 * (ec - eu)  (i[2] = channels per sample: guided; 0: e = ec, the unconditional half is not read);
+ *          out = f0 * x + f1 * e
+ *        in fp32 with every operation rounded by itself: both products, then their sum.  i[2] between 0 and the channel count is refused.
+ *        f: 0 sqrt(a_next / a), 1 sqrt(a_next) * (sqrt(1 / a_next - 1) - sqrt(1 / a - 1)), 5 guidance scale
+ *        p: 0 x fp32, 1 eps pair (fp16 or fp32), 3 out fp32, 4 (optional) a second fp32 destination that receives the same values — the
+ *           intermediate a caller keeps, at no extra launch; p[2] is not read.  Four elements per thread with 128-bit accesses when
+ *           every pointer is 16-byte aligned, one element per thread otherwise.
  * LINCOMB: i: 0 n elements, 1 n terms (<= 6), 2 out dtype, 3..8 term dtypes; f: 0..5 coefficients;
  *      p: 0..5 terms, 6 out
  * MEMSET: i: 0 bytes (lo), 1 bytes (hi); p: 0 dst

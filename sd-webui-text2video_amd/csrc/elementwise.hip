@@ -13,6 +13,7 @@
 //   x0_threshold  UniPC's thresholded data prediction (uni_pc/uni_pc.py:351-364): ddim_measure over that x0, then clamp(x0, -s, s) / s
 //                 (restrict_range_x0, gaussian_sampler.py:110-120) and / or the classifier-guidance term (get_eps, :199-211); the measure
 //                 pass is torch.quantile on fp32, exactly, by a radix select in one workgroup per video
+//   ddim_invert   the DDIM inversion step of DDIMSampler.encode (samplers/ddim/sampler.py:242-254), four elements per thread
 //   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
 //                 (process_modelscope.py:116-120, 174-178); the last pass can write the VAE encoder's tokens
 //   bicubic       torch's F.interpolate(mode="bicubic", align_corners=False) of planar float images, both axes in one launch: the resizes
@@ -298,6 +299,60 @@ __global__ __launch_bounds__(256) void x0_threshold_kernel(const DdimParams p, c
     const float x0 = x0_form<TE, 1>(p, xt, ec, eu, idx, idx - smp * per_sample < guided_n);
     const float s = table[smp * 4];
     out[idx] = nan_min(nan_max(x0, -s), s) / s;
+  }
+}
+
+// ---- mode 3: the DDIM inversion step, DDIMSampler.encode (samplers/ddim/sampler.py:242-254) ---------------------------------------------
+// A kernel of its own, like the restricted ones.  e = e_u + g (e_c - e_u) over all channels or e = e_c (the record is guided as a whole,
+// so no element needs its channel), out = f0 x + f1 e: both products first, then their sum, every operation rounded by itself.
+struct DdimInvert {
+  const float* x; const void* eps; float* out; float* keep;     // keep: optional second destination (a kept intermediate), same values
+  long total;                                                   // samples * channels * inner
+  float cx, ce, gscale;
+};
+
+__device__ __forceinline__ float ddim_invert_of(const DdimInvert& p, float x, float y, float u, bool guided) {
+#pragma clang fp contract(off)
+  float e = y;
+  if (guided) {
+    const float d = p.gscale * (y - u);
+    e = u + d;
+  }
+  const float m0 = p.cx * x, m1 = p.ce * e;
+  return m0 + m1;
+}
+
+// VEC: four elements per thread with one 128-bit access per fp32 tensor (64-bit for fp16 eps) — the launcher found every pointer
+// 16-byte aligned; the total % 4 last elements are the scalar work of workgroup 0.  !VEC: one element per thread.
+template <typename TE, bool GUIDED, bool VEC>
+__global__ __launch_bounds__(256) void ddim_invert_kernel(const DdimInvert p) {
+  const TE* ec = reinterpret_cast<const TE*>(p.eps);
+  const TE* eu = ec + p.total;                 // read only when GUIDED
+  const long stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
+  auto one = [&](long idx) {
+    const float u = GUIDED ? (float)eu[idx] : 0.f;
+    const float o = ddim_invert_of(p, p.x[idx], (float)ec[idx], u, GUIDED);
+    p.out[idx] = o;
+    if (p.keep != nullptr) p.keep[idx] = o;
+  };
+  if constexpr (VEC) {
+    using TE4 = TE __attribute__((ext_vector_type(4)));
+    const long nvec = p.total >> 2;
+    for (long v = first; v < nvec; v += stride) {
+      const f32x4 x = reinterpret_cast<const f32x4*>(p.x)[v];
+      const TE4 y = reinterpret_cast<const TE4*>(ec)[v];
+      TE4 u = y;
+      if constexpr (GUIDED) u = reinterpret_cast<const TE4*>(eu)[v];
+      f32x4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = ddim_invert_of(p, x[k], (float)y[k], (float)u[k], GUIDED);
+      reinterpret_cast<f32x4*>(p.out)[v] = o;
+      if (p.keep != nullptr) reinterpret_cast<f32x4*>(p.keep)[v] = o;
+    }
+    const long tail = (nvec << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < 4 && tail < p.total) one(tail);
+  } else {
+    for (long idx = first; idx < p.total; idx += stride) one(idx);
   }
 }
 
@@ -1381,6 +1436,32 @@ hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s) {
     else hipLaunchKernelGGL((ddim_measure_kernel<f16, FORM>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
     return hipGetLastError();
   };
+  if (p.mode == 3) {                           // DDIM inversion (DDIMSampler.encode): fp32 x, guidance over all channels or none
+    if (p.C <= 0 || p.inner <= 0 || !p.x_f32 || op.i[7] != 0 || op.i[8] != 0 || op.i[9] != 0 || (p.guided != 0 && p.guided != p.cps))
+      return hipErrorInvalidValue;
+    if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return hipErrorInvalidValue;
+    DdimInvert v;
+    v.x = reinterpret_cast<const float*>(op.p[0]); v.eps = p.eps; v.out = reinterpret_cast<float*>(op.p[3]);
+    v.keep = reinterpret_cast<float*>(op.p[4]);
+    v.total = (long)p.C * p.inner;
+    v.cx = op.f[0]; v.ce = op.f[1]; v.gscale = op.f[5];
+    const bool guided = p.guided != 0;
+    // every 16-byte access of the vector path: x, out, keep, the conditional half and — guided — the unconditional half behind it
+    const uint64_t eu = op.p[1] + (uint64_t)v.total * (p.eps_f32 ? 4 : 2);
+    const bool vec = v.total >= 4 && ((op.p[0] | op.p[1] | op.p[3] | op.p[4] | (guided ? eu : 0)) & 15) == 0;
+    const int gi = grid_for(vec ? v.total >> 2 : v.total);
+#define T2V_DDIM_INVERT(TE)                                                                                            \
+    if (guided) {                                                                                                      \
+      if (vec) hipLaunchKernelGGL((ddim_invert_kernel<TE, true, true>), dim3(gi), dim3(256), 0, s, v);                 \
+      else hipLaunchKernelGGL((ddim_invert_kernel<TE, true, false>), dim3(gi), dim3(256), 0, s, v);                    \
+    } else {                                                                                                           \
+      if (vec) hipLaunchKernelGGL((ddim_invert_kernel<TE, false, true>), dim3(gi), dim3(256), 0, s, v);                \
+      else hipLaunchKernelGGL((ddim_invert_kernel<TE, false, false>), dim3(gi), dim3(256), 0, s, v);                   \
+    }
+    if (p.eps_f32) { T2V_DDIM_INVERT(float) } else { T2V_DDIM_INVERT(f16) }
+#undef T2V_DDIM_INVERT
+    return hipGetLastError();
+  }
   if (p.mode == 2) {                           // UniPC's thresholded data prediction: measure (i[8] = 3), then apply (i[8] = 2); the executor checked
     if (!p.x_f32 || op.i[7] != 0 || op.i[9] != 0 || op.p[7] == 0 || (p.guided != 0 && p.guided != p.cps)) return hipErrorInvalidValue;
     if ((long)p.cps * p.inner > (1L << 24)) return hipErrorInvalidValue;

@@ -239,7 +239,14 @@ int validate_op(const t2v_op& op, int idx) {
     case T2V_OP_DDIM_STEP: {
       const int C = op.i[0], cps = op.i[6] > 0 ? op.i[6] : C;
       if (C <= 0 || op.i[1] <= 0 || cps <= 0 || C % cps != 0) return bad("DDIM step needs C > 0, inner > 0, C % channels-per-sample == 0");
-      if (op.i[2] < 0 || op.i[2] > cps || op.i[5] < 0 || op.i[5] > 2) return bad("DDIM step: guided channels / mode");
+      if (op.i[2] < 0 || op.i[2] > cps || op.i[5] < 0 || op.i[5] > 3) return bad("DDIM step: guided channels / mode");
+      if (op.i[5] == 3) {      // DDIM inversion (DDIMSampler.encode): out = f0 x + f1 e, nothing else
+        if (op.i[7] != 0 || op.i[8] != 0 || op.i[9] != 0) return bad("DDIM step: mode 3 (inversion) has no mask blend i[7], no x0 restriction i[8] and no classifier-guidance term i[9]");
+        if (op.i[4] != T2V_F32) return bad("DDIM step: mode 3 (inversion) needs an fp32 x");
+        if (op.i[2] != 0 && op.i[2] != cps) return bad("DDIM step: mode 3 (inversion) combines the guidance over all channels (i[2] = channels per sample) or not at all (0)");
+        if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return bad("null DDIM step pointer (mode 3 reads x p[0] and the eps pair p[1] and writes p[3])");
+        return 0;
+      }
       if (op.i[8] < 0 || op.i[8] > 3) return bad("DDIM step: x0 restriction i[8] must be 0 (none), 1 (clamp), 2 (threshold) or 3 (measure pass)");
       if (op.i[9] != 0 && op.i[9] != 1) return bad("DDIM step: classifier-guidance flag i[9] must be 0 or 1");
       if (op.p[0] == 0 || op.p[1] == 0 || (op.p[3] == 0 && op.i[8] != 3)) return bad("null DDIM step pointer");
@@ -524,6 +531,7 @@ int ff_min_m() {
 unsigned output_slots(const t2v_op& op) {
   auto bits = [](std::initializer_list<int> l) { unsigned m = 0; for (int k : l) m |= 1u << k; return m; };
   if (op.kind == T2V_OP_DDIM_STEP && op.i[8] == 3) return bits({7});      // the measure pass writes the threshold table and nothing else
+  if (op.kind == T2V_OP_DDIM_STEP && op.i[5] == 3) return bits({3, 4});   // the inversion step: p[4] is a second destination (the kept intermediate), not the blend's known x0
   switch (op.kind) {
     case T2V_OP_GEMM: return bits({5, 6, 7, 10, 11}) | (op.i[16] == T2V_EPI_GN ? bits({9}) : 0u);
     case T2V_OP_GROUPNORM: return bits({3, 4, 5, 7, 8});

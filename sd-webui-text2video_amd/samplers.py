@@ -520,6 +520,28 @@ def _ddim_update_blend(out, xt, eps_pair, noise, coef, guided: int, known, mask,
     return out
 
 
+def _ddim_invert(out, x, eps_pair, coef, guided: bool, keep=None):
+    """T2V_OP_DDIM_STEP mode 3, one step of DDIM inversion (ddim/sampler.py:242-254): out = coef[0] * x + coef[1] * e in one launch,
+    e = e_u + coef[2] * (e_c - e_u) over all channels when `guided`, else the conditional half (the other half is not read).
+    `keep`: a second fp32 tensor shaped like x that receives the same values (a kept intermediate).  x, out, keep: fp32, contiguous."""
+    for t in (x, out) + (() if keep is None else (keep,)):
+        if not (t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape and t.device == x.device):
+            raise L.T2VError("a DDIM inversion step needs fp32, contiguous x / out / keep of one shape on one device")
+    B, C = x.shape[0], x.shape[1]
+    if not eps_pair.is_contiguous() or eps_pair.numel() < (2 if guided else 1) * x.numel():
+        raise L.T2VError("a DDIM inversion step needs a contiguous eps pair [cond | uncond] (the conditional half alone when not guided)")
+    op = L.T2VOp()
+    op.kind = L.OP_DDIM_STEP
+    op.i[0], op.i[1], op.i[2] = B * C, x.numel() // (B * C), C if guided else 0
+    op.i[3], op.i[4], op.i[5], op.i[6] = _dt_tag(eps_pair), _dt_tag(x), 3, C
+    op.f[0], op.f[1], op.f[5] = float(coef[0]), float(coef[1]), float(coef[2])
+    op.p[0], op.p[1], op.p[3] = x.data_ptr(), eps_pair.data_ptr(), out.data_ptr()
+    op.p[4] = keep.data_ptr() if keep is not None else 0
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    L.check(L.load().t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(stream)))
+    return out
+
+
 _RUN_COUNTER = itertools.count(1)
 
 
@@ -650,8 +672,10 @@ class DDIMSampler(object):
         return [float(s1m), float(a_t.sqrt()), float(a_prev.sqrt()), float((1.0 - a_prev - sigma_t ** 2).sqrt()),
                 float(sigma_t), float(guide) if guide is not None else 1.0]
 
-    def _run(self, img, cond, uncond, time_range, total_steps, guide, callback):
+    def _run(self, img, cond, uncond, time_range, total_steps, guide, callback, temperature=1.0, ucg_schedule=None):
         model, dev = self.model, img.device
+        if ucg_schedule is not None:
+            assert len(ucg_schedule) == len(time_range)          # sampler.py:150-152
         C = img.shape[1]
         _check_batch_layout(self, img.shape[0])     # several videos per batch: one 2V-row forward and one update launch per step
         cond, uncond = batch_contexts(cond, uncond, img.shape[0])
@@ -669,8 +693,12 @@ class DDIMSampler(object):
             for i, step in enumerate(time_range):
                 c, uc = reconstruct_conds(cond, uncond, int(step))
                 index = total_steps - i - 1
+                if ucg_schedule is not None:
+                    guide = ucg_schedule[i]
                 eps, guided = _eval_eps_pair(model, img, int(step), c, uc, guide, self.cfg_parallel, cache=pair_cache)
                 coef = self._coef(index, guide)
+                if temperature != 1.0:                                     # sigma_t * noise * temperature (sampler.py:216); dir_xt keeps sigma_t
+                    coef[4] = float(torch.tensor(coef[4], dtype=torch.float32) * temperature)
                 noise = _step_noise(self, img, coef[4])                    # drawn every step, like noise_like(); sigma_t == 0 <=> eta == 0
                 _ddim_update(nxt, img, eps, noise, coef, C if guided else 0, mode=1)
                 img, nxt = nxt, img
@@ -684,14 +712,99 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, eta=0.0, mask=None, x0=None, x_T=None,
-               unconditional_guidance_scale=1.0, unconditional_conditioning=None, **kwargs):
-        """sampler.py:56-166."""
+               unconditional_guidance_scale=1.0, unconditional_conditioning=None, temperature=1.0, ucg_schedule=None, **kwargs):
+        """sampler.py:56-166.  `temperature` scales the step's eta noise (:216), `ucg_schedule` gives one guidance scale per step
+        (:150-152)."""
         import numpy as np
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
         img = torch.randn(tuple(shape), device=self.device) if x_T is None else x_T.clone()
         img = img.float().contiguous() if img.dtype not in (torch.float16, torch.float32) else img.contiguous()
         return self._run(img, conditioning, unconditional_conditioning, np.flip(self.ddim_timesteps),
-                         self.ddim_timesteps.shape[0], unconditional_guidance_scale, callback)
+                         self.ddim_timesteps.shape[0], unconditional_guidance_scale, callback, temperature=temperature,
+                         ucg_schedule=ucg_schedule)
+
+    def _invert_tables(self, num_steps, use_original_steps):
+        """-> (alphas_next, alphas) of `encode` in the reference's dtypes (sampler.py:230-235): the float64 schedule tables, or — original
+        steps — the fp32 `alphas_cumprod` / `alphas_cumprod_prev` buffers (sampler.py:32-33)."""
+        if not use_original_steps:
+            return self.ddim_alphas[:num_steps], self.ddim_alphas_prev[:num_steps]
+        ac = self.model.alphas_cumprod.detach().cpu()
+        prev = getattr(self.model, "alphas_cumprod_prev", None)          # register_schedule's buffer; else what it computes
+        prev = torch.cat([torch.ones(1, dtype=ac.dtype), ac[:-1]]) if prev is None else prev.detach().cpu()
+        return ac.to(torch.float32)[:num_steps], prev.to(torch.float32)[:num_steps]
+
+    @torch.no_grad()
+    def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, callback=None, *, model_timesteps="index"):
+        """sampler.py:222-267 — deterministic DDIM inversion: the latent walks UP the trajectory, one UNet evaluation (one batched
+        [cond | uncond] forward when guided) and ONE update launch (T2V_OP_DDIM_STEP mode 3) per step.
+
+        `model_timesteps="index"` is the reference statement for statement, its quirk included: the UNet is called at t = i, the loop
+        index, not at ddim_timesteps[i] (right only with use_original_steps).  "schedule" calls it at ddim_timesteps[i], the timestep
+        `decode`'s step `index = i` uses, so the two loops visit the same (timestep, level) pairs; with use_original_steps the two
+        coincide.  -> (x_next fp32, {'x_encoded', 'intermediate_steps'[, 'intermediates']})."""
+        if model_timesteps not in ("index", "schedule"):
+            raise ValueError(f"model_timesteps must be 'index' or 'schedule', not {model_timesteps!r}")
+        num_reference_steps = self.ddpm_num_timesteps if use_original_steps else self.ddim_timesteps.shape[0]
+        assert t_enc <= num_reference_steps
+        num_steps = int(t_enc)
+        if return_intermediates and return_intermediates > num_steps:
+            raise ValueError(f"return_intermediates = {return_intermediates} is larger than t_enc = {num_steps}: every "
+                             f"t_enc // return_intermediates-th step is kept")
+        if self.cfg_parallel is not None and self.cfg_parallel.size == 2:
+            raise L.T2VError("DDIM inversion (DDIMSampler.encode) is not supported in the CFG-pair multi-GPU layout: its guided step "
+                             "is one batched [cond | uncond] forward on one device")
+        if getattr(self.model, "t_shard", None) is not None:
+            raise L.T2VError("DDIM inversion (DDIMSampler.encode) is not supported with a clip whose frames are split over ranks")
+        alphas_next, alphas = self._invert_tables(num_steps, use_original_steps)
+        model = self.model
+        x = x0.to(torch.float32).contiguous()
+        dev, videos = x.device, x.shape[0]
+        guide = unconditional_guidance_scale
+        if guide != 1.0:
+            assert unconditional_conditioning is not None
+        cond, uncond = batch_contexts(c, unconditional_conditioning if guide != 1.0 else None, videos)
+        if hasattr(model, "verify_weights"):
+            model.verify_weights(dev)
+        if hasattr(model, "refresh_weights"):
+            model.refresh_weights(dev)
+        prev_auto = getattr(model, "auto_refresh", None)
+        if prev_auto is not None:
+            model.auto_refresh = False
+        prev_eps = _want_fp32_eps(model)
+        pair_cache = {}
+        intermediates, inter_steps = [], []
+        spare = None            # the buffer the next step may write: never x0 itself, never a kept intermediate
+        x_next = x
+        try:
+            for i in range(num_steps):
+                t = i if (model_timesteps == "index" or use_original_steps) else int(self.ddim_timesteps[i])
+                eps, guided = _eval_eps_pair(model, x_next, t, cond, uncond, guide, None, cache=pair_cache)
+                # 0-dim tensors of the tables' dtype; they meet the fp32 latent as fp32 scalars (sampler.py:251-253)
+                cx = (alphas_next[i] / alphas[i]).sqrt()
+                ce = alphas_next[i].sqrt() * ((1 / alphas_next[i] - 1).sqrt() - (1 / alphas[i] - 1).sqrt())
+                kept = bool(return_intermediates) and ((i % (num_steps // return_intermediates) == 0 and i < num_steps - 1)
+                                                       or i >= num_steps - 2)
+                out = spare if spare is not None else torch.empty_like(x)
+                keep = torch.empty_like(x) if kept else None
+                _ddim_invert(out, x_next, eps, (float(cx.to(torch.float32)), float(ce.to(torch.float32)), float(guide)), guided, keep=keep)
+                spare = x_next if x_next is not x else None
+                x_next = out
+                if kept:
+                    intermediates.append(keep)
+                    inter_steps.append(i)
+                if callback:
+                    callback(i)
+        finally:
+            if prev_auto is not None:
+                model.auto_refresh = prev_auto
+            _restore_eps(model, prev_eps)
+        if x_next is x and x is x0:
+            x_next = x.clone()              # t_enc = 0: the caller's tensor is not handed back
+        out = {"x_encoded": x_next, "intermediate_steps": inter_steps}
+        if return_intermediates:
+            out.update({"intermediates": intermediates})
+        return x_next, out
 
     @torch.no_grad()
     def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
@@ -997,6 +1110,10 @@ available_samplers = [
 ]
 
 
+# the options of sample_loop(..., inversion=) and what `True` means: the reference's own encode (scale 1, UNet labels t = i)
+INVERSION_DEFAULTS = {"guidance_scale": 1.0, "model_timesteps": "index"}
+
+
 class Txt2VideoSampler(object):
     """samplers_common.py:95-207.  (The reference's default sampler_name is "UniPC"; this build's
     default is the UI default "DDIM_Gaussian".)"""
@@ -1041,6 +1158,19 @@ class Txt2VideoSampler(object):
             encoded_latent = self.sampler.add_noise(latent, noise, timestep[0].cpu())
         return encoded_latent, denoise_steps
 
+    def invert_latent(self, latent, noise, strength, steps, conditioning, unconditional_conditioning, guidance_scale=1.0,
+                      model_timesteps="index"):
+        """vid2vid through DDIM inversion: `encode_latent`'s schedule and step count, the latent from `DDIMSampler.encode` instead of
+        `stochastic_encode` (`noise` only tells how many videos the batch holds), and `sample` becomes `decode` as there."""
+        if noise is not None and latent.shape[0] == 1 and noise.shape[0] > 1:
+            latent = latent.expand(noise.shape[0], *latent.shape[1:]).contiguous()
+        denoise_steps = int(strength * steps)
+        self.sampler.make_schedule(steps)
+        encoded_latent, _ = self.sampler.encode(latent, conditioning, denoise_steps, unconditional_guidance_scale=guidance_scale,
+                                                unconditional_conditioning=unconditional_conditioning, model_timesteps=model_timesteps)
+        self.sampler.sample = self.sampler.decode
+        return encoded_latent, denoise_steps
+
     def get_sampler(self, sampler_name: str, betas=None, return_sampler=True):
         betas = betas if betas is not None else self.betas
         for Sampler in available_samplers:
@@ -1056,11 +1186,16 @@ class Txt2VideoSampler(object):
 
     def sample_loop(self, steps, strength, conditioning, unconditional_conditioning, batch_size, latents=None,
                     shape=None, noise=None, is_vid2vid=False, guidance_scale=1, eta=0, mask=None,
-                    sampler_name="DDIM", *, clamp=None, percentile=None, unipc=None):
+                    sampler_name="DDIM", *, clamp=None, percentile=None, unipc=None, inversion=None):
         """samplers_common.py:165-207.  `clamp` / `percentile` (keyword, this build's addition to the signature): the x0 restriction of
         GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set, so every other call is what it was.
         `unipc` (keyword, likewise): a dict of UniPC's solver options (UNIPC_OPTIONS, see UniPCSampler) — UniPC only, forwarded only
-        when set."""
+        when set.
+        `inversion` (keyword, likewise): True (the reference's encode: scale 1, UNet labels t = i) or a dict with guidance_scale and / or
+        model_timesteps ("index" | "schedule", see DDIMSampler.encode) — sampler "DDIM" with
+        is_vid2vid only: the latents are taken up the deterministic trajectory by `DDIMSampler.encode` (under `conditioning`, each
+        video of a batch under its own prompt) instead of being noised by `stochastic_encode`; `noise` is not used; `sample` becomes
+        `decode` exactly as on the noising route."""
         restrict = {k: v for k, v in (("clamp", clamp), ("percentile", percentile)) if v is not None}
         active = next((s.name for s in available_samplers if isinstance(self.sampler, s.Sampler)), type(self.sampler).__name__)
         if restrict and not isinstance(self.sampler, GaussianDiffusion):
@@ -1072,8 +1207,23 @@ class Txt2VideoSampler(object):
             if unknown:
                 raise ValueError(f"unipc: unknown option(s) {', '.join(map(repr, unknown))}; the options are {', '.join(UNIPC_OPTIONS)}")
             restrict.update(unipc)
+        invert = None
+        if inversion is not None and inversion is not False:
+            if not isinstance(self.sampler, DDIMSampler):
+                raise ValueError(f"inversion: DDIM inversion exists for the DDIM sampler only, not for {active!r}")
+            if latents is None or not is_vid2vid:
+                raise ValueError("inversion: DDIM inversion is a vid2vid route, it needs latents and is_vid2vid=True")
+            invert = dict(INVERSION_DEFAULTS)
+            if inversion is not True:
+                unknown = [k for k in inversion if k not in INVERSION_DEFAULTS]
+                if unknown:
+                    raise ValueError(f"inversion: unknown option(s) {', '.join(map(repr, unknown))}; the options are "
+                                     f"{', '.join(INVERSION_DEFAULTS)}")
+                invert.update(inversion)
         denoise_steps = None
-        if latents is not None and is_vid2vid:
+        if invert is not None:
+            latents, denoise_steps = self.invert_latent(latents, noise, strength, steps, conditioning, unconditional_conditioning, **invert)
+        elif latents is not None and is_vid2vid:
             latents, denoise_steps = self.encode_latent(latents, noise, strength, steps)
         sampler_callback = SamplerStepCallback(sampler_name, steps, progress=self.progress)
         x0 = self.sampler.sample(
