@@ -13,9 +13,18 @@ same stream — the host only computes five fp32 scalars per step and never sync
 
 All three samplers of the reference registry are built: "DDIM_Gaussian" (UI default,
 t2v_helpers/args.py:234), "DDIM" (LDM-style, ddim/sampler.py) and "UniPC" (uni_pc/*).
+
+Every sampling loop (the three here, `DDIMSampler.encode`, and videocrafter.DDIMSampler) is built from the same three parts:
+  `_sampling_run(model, device)`  the run guard: weights verified and refreshed once, no refresh and fp32 eps inside the loop
+  `_eval_eps_pair(...)`           one step's model evaluation: plain, CFG pair, ragged prompt batch or two-GPU exchange, with the
+                                  run's context token (the VideoCrafter loop evaluates through LatentDiffusion.apply_model instead)
+  `_ddim_record` + `_run_ops`     the one builder of a T2V_OP_DDIM_STEP record and the one launch tail; `_ddim_update`,
+                                  `_ddim_update_blend`, `_ddim_restricted_*`, `_x0_threshold*`, `_ddim_invert` name its forms
+(the plain DDIM_Gaussian step alone runs a cached one-op plan through `t2v_ddim_step`).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import itertools
 import os
@@ -102,10 +111,10 @@ def _eval_ragged(model, x, tt, c, uc, guided: bool, token, cfg_parallel=None):
     return model.forward_cfg_pair(x, tt, (list(c), list(uc)), context_token=token, single_t=True)
 
 
-def _ctx_ident(nonce, c, uc, *more):
+def _ctx_ident(nonce, c, uc):
     """Names the content of the conditioning objects of a run (tensors or lists of tensors), for the model's context cache."""
     flat = lambda v: () if v is None else tuple((id(e), e._version) for e in (v if isinstance(v, (list, tuple)) else (v,)))
-    return (nonce, flat(c), flat(uc)) + more
+    return (nonce, flat(c), flat(uc))
 
 
 # ---- boundary B3 (SURVEY §8b) -------------------------------------------------------------------------------------
@@ -239,7 +248,9 @@ class GaussianDiffusion(object):
         condition_fn(xt, t) -> gradient shaped like xt: classifier guidance (get_eps, :199-211), eps -= sqrt(1 - a_t) * condition_fn(xt, t),
         x0 recomputed from that eps; called once per step with t as the long tensor [videos] the reference passes.
         Several videos per batch (this build's extension; the reference's quantile cannot run there): each video has its own s, so the
-        batch equals the single-video runs.  A clip whose frames are split over ranks is refused: the quantile spans all frames."""
+        batch equals the single-video runs.  A clip whose frames are split over ranks is refused: the quantile spans all frames.
+        The model is evaluated by `_eval_eps_pair`, as in every loop of this file: a guidance scale with
+        unconditional_conditioning=None runs unguided."""
         if model_kwargs:
             raise NotImplementedError("model_kwargs (conditioning passed as a pair, gaussian_sampler.py:156-159) is not used by the pipeline")
         if percentile is not None and not (0 < float(percentile) <= 1):
@@ -276,61 +287,18 @@ class GaussianDiffusion(object):
 
         ac = self.alphas_cumprod
         f32 = torch.float32
-        if hasattr(model, "verify_weights"):
-            model.verify_weights(dev)           # the bytes: in-place edits (`w.data += d`) that no version counter shows — once per call
-        if hasattr(model, "refresh_weights"):
-            model.refresh_weights(dev)
-        prev_auto = getattr(model, "auto_refresh", None)
-        if prev_auto is not None:
-            model.auto_refresh = False
-        prev_eps = _want_fp32_eps(model)
         stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-        pair_key = pair_ctx = pair_refs = None      # pair_refs keeps the tensors alive, so their ids stay unique
-        run_nonce = next(_RUN_COUNTER)              # a new sampling run never reuses the previous run's cached context K/V
-        try:
+        pair_cache = {}                             # of this run: a new run never reuses the previous run's cached context K/V
+        with _sampling_run(model, dev):
             all_t = self.get_time_steps(stride, 1).cpu()
             # every step's timestep row, uploaded once: [steps, 2 * Bx] fp32 (the b = 2 * Bx CFG forward reads a whole row, a
             # b = Bx forward its first half) — no per-step fill kernels inside the loop
             tt_all = all_t[:steps].to(torch.float32).view(-1, 1).repeat(1, 2 * Bx).to(dev)
             for step in range(steps):
                 c, uc = reconstruct_conds(conditioning, unconditional_conditioning, step)
-                c0, uc0 = c, uc
                 t = int(all_t[step])
-                tt = tt_all[step, :Bx]
-                ragged = isinstance(c, list)           # a batch of different prompts (batch_contexts): one forward of 2 * Bx samples all the same
-                if Bx > 1 and not ragged:
-                    c = c.expand(Bx, *c.shape[1:]) if c.shape[0] == 1 else c
-                    if uc is not None:
-                        uc = uc.expand(Bx, *uc.shape[1:]) if uc.shape[0] == 1 else uc
-                if ragged:
-                    unguided = self.is_unconditional(guide)
-                    eps = _eval_ragged(model, xt, tt if unguided else tt_all[step], c, uc, not unguided,
-                                       _ctx_ident(run_nonce, c0, None if unguided else uc0, Bx), self.cfg_parallel)
-                    guided, gscale = (0, 1.0) if unguided else (C // 2 if not self.var_type.startswith("fixed") else C, float(guide))
-                elif self.is_unconditional(guide):
-                    eps = model(xt, tt, c)
-                    guided, gscale = 0, 1.0
-                elif self.cfg_parallel is not None and self.cfg_parallel.size == 2:
-                    # CFG pair: this rank evaluates ONE of the two forwards; one eps all-gather per step
-                    assert Bx == 1, "the CFG-pair layout runs one video per pair"
-                    mine = c if self.cfg_parallel.role == 0 else uc
-                    eps = self.cfg_parallel.exchange_eps(model(xt, tt, mine))
-                    guided, gscale = C // 2 if not self.var_type.startswith("fixed") else C, float(guide)
-                else:
-                    if hasattr(model, "forward_cfg_pair"):
-                        # [cond | uncond] built once while the conditioning OBJECTS stay the same (prompt scheduling may
-                        # swap them between steps, reconstruct_cond_batch); x_t is read twice by the entry op
-                        ident = (run_nonce, id(c0), c0._version, id(uc0), uc0._version, Bx)
-                        if pair_key != ident:
-                            # (contexts of different lengths go in as the pair: one program with two key counts, forward_cfg_pair)
-                            pair_key, pair_ctx, pair_refs = ident, (c, uc) if c.shape[1] != uc.shape[1] else torch.cat([c, uc], dim=0), (c0, uc0)
-                        eps = model.forward_cfg_pair(xt, tt_all[step], pair_ctx, context_token=pair_key, single_t=True)   # (one timestep per step)
-                    elif getattr(model, "supports_cfg_batch", False) and c.shape[1] == uc.shape[1]:
-                        eps = model(torch.cat([xt, xt], dim=0), torch.cat([tt, tt]), torch.cat([c, uc], dim=0))
-                    else:
-                        eps = torch.cat([model(xt, tt, c), model(xt, tt, uc)], dim=0)
-                    guided, gscale = C // 2 if not self.var_type.startswith("fixed") else C, float(guide)
-                eps = eps.contiguous()
+                eps, is_pair = _eval_eps_pair(model, xt, tt_all[step], c, uc, guide, self.cfg_parallel, cache=pair_cache)
+                guided, gscale = (self.get_dim(xt), float(guide)) if is_pair else (0, 1.0)    # guidance over the mean's channels
                 # schedule scalars: float64 tables cast to fp32 per lookup, then fp32 arithmetic —
                 # the exact operation order of gaussian_sampler.py:269-283 / `_i` (t2v_model.py:1232)
                 a_t, a_prev = ac[t].to(f32), ac[max(t - stride, 0)].to(f32)
@@ -359,10 +327,6 @@ class GaussianDiffusion(object):
                 xt, x_next = x_next, xt
                 if callback is not None:
                     callback(step)
-        finally:
-            if prev_auto is not None:
-                model.auto_refresh = prev_auto
-            _restore_eps(model, prev_eps)
         self.last_thresholds = thresholds      # [S, videos, 4] {s, q, v_lo, v_hi} on the device (percentile runs), else None
         return xt
 
@@ -374,9 +338,62 @@ def _dt_tag(t: torch.Tensor) -> int:
     return L.F16 if t.dtype == torch.float16 else L.F32
 
 
+def _run_ops(ops, device) -> None:
+    """One record (a T2VOp) or a ctypes array of records: ONE t2v_run_ops call on `device`'s current stream."""
+    one = isinstance(ops, L.T2VOp)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    L.check(L.load().t2v_run_ops(ctypes.byref(ops) if one else ops, 1 if one else len(ops), None, 0, ctypes.c_void_p(stream)))
+
+
+def _check_operand(t, x, noun: str, what: str = "must be fp32, contiguous, on the device and shaped like x", shape=None) -> None:
+    """An operand a DDIM_STEP record reads dense: fp32, contiguous, on x's device, shaped like x (or `shape`)."""
+    if not (t is not None and t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
+            and tuple(t.shape) == tuple(x.shape if shape is None else shape)):
+        raise L.T2VError(f"{noun} {what}")
+
+
+def _ddim_record(out, xt, eps_pair, noise, coef, guided: int, mode: int, *, blend=None, restrict: int = 0, level: float = 0.0,
+                 table=None, grad=None, keep=None):
+    """-> one T2V_OP_DDIM_STEP record (include/t2v_hip.h): the header every mode shares — geometry, dtypes, f[0..5] = `coef`,
+    x / eps pair / out, and the eta noise only where coef[4] != 0 — plus what the keywords name, every other field zero:
+      blend = (known, mask, qnoise or None, qcoef)   i[7] = 1, f[6..7], p[4..6]: the known-region blend of a masked step
+      restrict, level, table                          i[8], f[6] (the clamp bound or the percentile), p[7]: the restriction of x0
+      grad = (g, sqrt(1 - a_t))                       i[9] = 1, f[7], p[8]: the classifier-guidance term
+      keep                                            p[4]: the second destination of an inversion step"""
+    op = L.T2VOp()
+    op.kind = L.OP_DDIM_STEP
+    B, C = xt.shape[0], xt.shape[1]              # B videos per batch: eps_pair = [cond (B), uncond (B)]
+    op.i[0], op.i[1], op.i[2] = B * C, xt.numel() // (B * C), guided
+    op.i[3], op.i[4], op.i[5], op.i[6] = _dt_tag(eps_pair), _dt_tag(xt), mode, C
+    for k in range(6):
+        op.f[k] = float(coef[k])
+    op.p[0], op.p[1], op.p[3] = xt.data_ptr(), eps_pair.data_ptr(), out.data_ptr()
+    op.p[2] = noise.data_ptr() if (noise is not None and float(coef[4]) != 0.0) else 0
+    if blend is not None:
+        known, mask, qnoise, qcoef = blend
+        op.i[7], op.f[6], op.f[7] = 1, float(qcoef[0]), float(qcoef[1])
+        op.p[4], op.p[5], op.p[6] = known.data_ptr(), mask.data_ptr(), qnoise.data_ptr() if qnoise is not None else 0
+    if restrict:
+        op.i[8], op.f[6] = restrict, float(level)
+    if table is not None:
+        op.p[7] = table.data_ptr()
+    if grad is not None:
+        op.i[9], op.f[7], op.p[8] = 1, float(grad[1]), grad[0].data_ptr()
+    if keep is not None:
+        op.p[4] = keep.data_ptr()
+    return op
+
+
+def _ddim_records(*records):
+    """-> the records as one ctypes array, in launch order (the passes of one step go to t2v_run_ops together)."""
+    ops = (L.T2VOp * len(records))()
+    for k, op in enumerate(records):
+        ops[k] = op
+    return ops
+
+
 def _lincomb(out: torch.Tensor, terms) -> torch.Tensor:
     """out = sum_i coef_i * tensor_i  (T2V_OP_LINCOMB; <= 6 terms, fp16/fp32 mixed, same numel)."""
-    lib = L.load()
     op = L.T2VOp()
     op.kind = L.OP_LINCOMB
     op.i[0], op.i[1], op.i[2] = out.numel(), len(terms), _dt_tag(out)
@@ -387,26 +404,13 @@ def _lincomb(out: torch.Tensor, terms) -> torch.Tensor:
         assert t.numel() == out.numel() and t.dtype in (torch.float16, torch.float32)
         op.i[3 + k], op.f[k], op.p[k] = _dt_tag(t), float(c), t.data_ptr()
     op.p[6] = out.data_ptr()
-    stream = torch.cuda.current_stream(out.device).cuda_stream
-    L.check(lib.t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(stream)))
+    _run_ops(op, out.device)
     return out
 
 
 def _ddim_update(out, xt, eps_pair, noise, coef, guided: int, mode: int):
     """T2V_OP_DDIM_STEP: CFG combine + x0 + x_{t-1} in one kernel (mode 0 DDIM_Gaussian, 1 LDM DDIM)."""
-    lib = L.load()
-    op = L.T2VOp()
-    op.kind = L.OP_DDIM_STEP
-    B, C = xt.shape[0], xt.shape[1]              # B videos per batch: eps_pair = [cond (B), uncond (B)]
-    op.i[0], op.i[1], op.i[2] = B * C, xt.numel() // (B * C), guided
-    op.i[6] = C
-    op.i[3], op.i[4], op.i[5] = _dt_tag(eps_pair), _dt_tag(xt), mode
-    for k in range(6):
-        op.f[k] = float(coef[k])
-    op.p[0], op.p[1], op.p[3] = xt.data_ptr(), eps_pair.data_ptr(), out.data_ptr()
-    op.p[2] = noise.data_ptr() if (noise is not None and float(coef[4]) != 0.0) else 0
-    stream = torch.cuda.current_stream(xt.device).cuda_stream
-    L.check(lib.t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(stream)))
+    _run_ops(_ddim_record(out, xt, eps_pair, noise, coef, guided, mode), xt.device)
     return out
 
 
@@ -415,46 +419,24 @@ def _ddim_restricted_records(out, xt, eps_pair, noise, coef, guided: int, *, per
     """-> the T2V_OP_DDIM_STEP records (mode 0) of one DDIM_Gaussian step with a restricted x0 and / or the classifier-guidance term:
     `percentile` (with `table` [videos, 4] fp32): the measure pass (i[8] = 3) and the update that reads its s (i[8] = 2); `bound`: the
     clamp (i[8] = 1); `grad`: i[9] = 1 with f[7] = sqrt(1 - a_t).  A ctypes array of one or two records."""
-    B, C = xt.shape[0], xt.shape[1]
-    if grad is not None and not (grad.dtype == torch.float32 and grad.is_contiguous() and grad.shape == xt.shape and grad.device == xt.device):
-        raise L.T2VError("the gradient of a classifier-guided DDIM step must be fp32, contiguous, on the device and shaped like x")
-    if percentile is not None and not (table is not None and table.dtype == torch.float32 and table.is_contiguous()
-                                       and tuple(table.shape) == (B, 4) and table.device == xt.device):
-        raise L.T2VError("the threshold table of a percentile DDIM step must be fp32 [videos, 4], contiguous, on the device")
-
-    def record(restrict):
-        op = L.T2VOp()
-        op.kind = L.OP_DDIM_STEP
-        op.i[0], op.i[1], op.i[2] = B * C, xt.numel() // (B * C), guided
-        op.i[6] = C
-        op.i[3], op.i[4], op.i[5] = _dt_tag(eps_pair), _dt_tag(xt), 0
-        op.i[8] = restrict
-        for k in range(6):
-            op.f[k] = float(coef[k])
-        op.p[0], op.p[1], op.p[3] = xt.data_ptr(), eps_pair.data_ptr(), out.data_ptr()
-        op.p[2] = noise.data_ptr() if (noise is not None and float(coef[4]) != 0.0) else 0
-        if restrict in (2, 3):
-            op.p[7] = table.data_ptr()
-        if restrict == 3:
-            op.f[6] = float(percentile)
-        elif restrict == 1:
-            op.f[6] = float(bound)
-        if grad is not None and restrict != 3:          # (the measure pass ranks x0 before the guidance term)
-            op.i[9], op.f[7], op.p[8] = 1, float(sqrt_1mat), grad.data_ptr()
-        return op
-
-    kinds = [3, 2] if percentile is not None else [1] if bound is not None else [0]
-    ops = (L.T2VOp * len(kinds))()
-    for k, r in enumerate(kinds):
-        ops[k] = record(r)
-    return ops
+    if grad is not None:
+        _check_operand(grad, xt, "the gradient of a classifier-guided DDIM step")
+        grad = (grad, sqrt_1mat)
+    head = (out, xt, eps_pair, noise, coef, guided, 0)
+    if percentile is not None:
+        _check_operand(table, xt, "the threshold table of a percentile DDIM step", "must be fp32 [videos, 4], contiguous, on the device",
+                       shape=(xt.shape[0], 4))
+        # (the measure pass ranks x0 before the guidance term)
+        return _ddim_records(_ddim_record(*head, restrict=3, level=percentile, table=table),
+                             _ddim_record(*head, restrict=2, table=table, grad=grad))
+    if bound is not None:
+        return _ddim_records(_ddim_record(*head, restrict=1, level=bound, grad=grad))
+    return _ddim_records(_ddim_record(*head, grad=grad))
 
 
 def _ddim_restricted_step(out, xt, eps_pair, noise, coef, guided: int, **kw):
     """One DDIM_Gaussian step with clamp / percentile / classifier guidance (`_ddim_restricted_records`): ONE t2v_run_ops call."""
-    ops = _ddim_restricted_records(out, xt, eps_pair, noise, coef, guided, **kw)
-    stream = torch.cuda.current_stream(xt.device).cuda_stream
-    L.check(L.load().t2v_run_ops(ops, len(ops), None, 0, ctypes.c_void_p(stream)))
+    _run_ops(_ddim_restricted_records(out, xt, eps_pair, noise, coef, guided, **kw), xt.device)
     return out
 
 
@@ -470,27 +452,15 @@ def _x0_threshold_records(out, x, eps_pair, sigma: float, alpha: float, guide: f
         raise L.T2VError("a thresholded data prediction needs an fp32 latent x")
     if x.numel() // B > (1 << 24):
         raise L.T2VError("a thresholded data prediction ranks at most 16 777 216 elements per video (torch.quantile's limit)")
-    if not (table is not None and table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (B, 4)
-            and table.device == x.device):
-        raise L.T2VError("the threshold table of a thresholded data prediction must be fp32 [videos, 4], contiguous, on the device")
-    ops = (L.T2VOp * 2)()
-    for k, restrict in enumerate((3, 2)):
-        op = ops[k]
-        op.kind = L.OP_DDIM_STEP
-        op.i[0], op.i[1], op.i[2] = B * C, x.numel() // (B * C), C if guided else 0
-        op.i[3], op.i[4], op.i[5], op.i[6], op.i[8] = _dt_tag(eps_pair), _dt_tag(x), 2, C, restrict
-        op.f[0], op.f[1], op.f[5] = float(sigma), float(alpha), float(guide)
-        op.p[0], op.p[1], op.p[3], op.p[7] = x.data_ptr(), eps_pair.data_ptr(), out.data_ptr(), table.data_ptr()
-        if restrict == 3:
-            op.f[6] = float(quantile)
-    return ops
+    _check_operand(table, x, "the threshold table of a thresholded data prediction", "must be fp32 [videos, 4], contiguous, on the device",
+                   shape=(B, 4))
+    head = (out, x, eps_pair, None, (sigma, alpha, 0.0, 0.0, 0.0, guide), C if guided else 0, 2)
+    return _ddim_records(_ddim_record(*head, restrict=3, level=quantile, table=table), _ddim_record(*head, restrict=2, table=table))
 
 
 def _x0_threshold(out, x, eps_pair, sigma: float, alpha: float, guide: float, guided: bool, table):
     """One thresholded data prediction (`_x0_threshold_records`): ONE t2v_run_ops call; s stays on the device."""
-    ops = _x0_threshold_records(out, x, eps_pair, sigma, alpha, guide, guided, table)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    L.check(L.load().t2v_run_ops(ops, len(ops), None, 0, ctypes.c_void_p(stream)))
+    _run_ops(_x0_threshold_records(out, x, eps_pair, sigma, alpha, guide, guided, table), x.device)
     return out
 
 
@@ -498,25 +468,9 @@ def _ddim_update_blend(out, xt, eps_pair, noise, coef, guided: int, known, mask,
     """T2V_OP_DDIM_STEP mode 1 with i[7] = 1: the LDM DDIM update of `_ddim_update` and, in the same launch, the known-region blend
     of a masked step (lvdm/samplers/ddim.py:188-195): out = (qcoef[0] * known + qcoef[1] * qnoise) * mask + (1 - mask) * x_{t-1}.
     known, mask, qnoise: fp32, contiguous, shaped like xt (qnoise may be None when qcoef[1] == 0)."""
-    lib = L.load()
-    op = L.T2VOp()
-    op.kind = L.OP_DDIM_STEP
-    B, C = xt.shape[0], xt.shape[1]
-    op.i[0], op.i[1], op.i[2] = B * C, xt.numel() // (B * C), guided
-    op.i[6] = C
-    op.i[3], op.i[4], op.i[5], op.i[7] = _dt_tag(eps_pair), _dt_tag(xt), 1, 1
-    for k in range(6):
-        op.f[k] = float(coef[k])
-    op.f[6], op.f[7] = float(qcoef[0]), float(qcoef[1])
-    for t in (known, mask, qnoise):
-        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.shape == xt.shape and t.device == xt.device):
-            raise L.T2VError("the blend operands of a masked DDIM step must be fp32, contiguous, on the device and shaped like x")
-    op.p[0], op.p[1], op.p[3] = xt.data_ptr(), eps_pair.data_ptr(), out.data_ptr()
-    op.p[2] = noise.data_ptr() if (noise is not None and float(coef[4]) != 0.0) else 0
-    op.p[4], op.p[5] = known.data_ptr(), mask.data_ptr()
-    op.p[6] = qnoise.data_ptr() if qnoise is not None else 0
-    stream = torch.cuda.current_stream(xt.device).cuda_stream
-    L.check(lib.t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(stream)))
+    for t in (known, mask) + (() if qnoise is None else (qnoise,)):
+        _check_operand(t, xt, "the blend operands of a masked DDIM step")
+    _run_ops(_ddim_record(out, xt, eps_pair, noise, coef, guided, 1, blend=(known, mask, qnoise, qcoef)), xt.device)
     return out
 
 
@@ -525,20 +479,11 @@ def _ddim_invert(out, x, eps_pair, coef, guided: bool, keep=None):
     e = e_u + coef[2] * (e_c - e_u) over all channels when `guided`, else the conditional half (the other half is not read).
     `keep`: a second fp32 tensor shaped like x that receives the same values (a kept intermediate).  x, out, keep: fp32, contiguous."""
     for t in (x, out) + (() if keep is None else (keep,)):
-        if not (t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape and t.device == x.device):
-            raise L.T2VError("a DDIM inversion step needs fp32, contiguous x / out / keep of one shape on one device")
-    B, C = x.shape[0], x.shape[1]
+        _check_operand(t, x, "a DDIM inversion step", "needs fp32, contiguous x / out / keep of one shape on one device")
     if not eps_pair.is_contiguous() or eps_pair.numel() < (2 if guided else 1) * x.numel():
         raise L.T2VError("a DDIM inversion step needs a contiguous eps pair [cond | uncond] (the conditional half alone when not guided)")
-    op = L.T2VOp()
-    op.kind = L.OP_DDIM_STEP
-    op.i[0], op.i[1], op.i[2] = B * C, x.numel() // (B * C), C if guided else 0
-    op.i[3], op.i[4], op.i[5], op.i[6] = _dt_tag(eps_pair), _dt_tag(x), 3, C
-    op.f[0], op.f[1], op.f[5] = float(coef[0]), float(coef[1]), float(coef[2])
-    op.p[0], op.p[1], op.p[3] = x.data_ptr(), eps_pair.data_ptr(), out.data_ptr()
-    op.p[4] = keep.data_ptr() if keep is not None else 0
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    L.check(L.load().t2v_run_ops(ctypes.byref(op), 1, None, 0, ctypes.c_void_p(stream)))
+    _run_ops(_ddim_record(out, x, eps_pair, None, (coef[0], coef[1], 0.0, 0.0, 0.0, coef[2]), x.shape[1] if guided else 0, 3, keep=keep),
+             x.device)
     return out
 
 
@@ -558,6 +503,28 @@ def _want_fp32_eps(model):
 def _restore_eps(model, token):
     if token != "absent":
         model.eps_out_dtype = token
+
+
+@contextlib.contextmanager
+def _sampling_run(model, device):
+    """The guard around every sampling loop.  On entry, once per run: the packed weights are verified against their bytes (in-place
+    edits, `w.data += d`, that no version counter shows) and refreshed; inside, the model neither refreshes per forward nor rounds eps
+    to fp16 (`_want_fp32_eps`).  Both settings come back on exit, also when the body raises.  A model without these attributes runs
+    as it is."""
+    if hasattr(model, "verify_weights"):
+        model.verify_weights(device)
+    if hasattr(model, "refresh_weights"):
+        model.refresh_weights(device)
+    prev_auto = getattr(model, "auto_refresh", None)
+    if prev_auto is not None:
+        model.auto_refresh = False
+    prev_eps = _want_fp32_eps(model)
+    try:
+        yield
+    finally:
+        if prev_auto is not None:
+            model.auto_refresh = prev_auto
+        _restore_eps(model, prev_eps)
 
 
 class SharedNoise:
@@ -604,22 +571,31 @@ def _check_batch_layout(sampler, videos: int) -> None:
 
 
 def _eval_eps_pair(model, x, t_value, c, uc, guide, cfg_parallel=None, cache: Optional[dict] = None):
-    """-> (eps [1 or 2, C, F, h, w] (index 0 conditional, 1 unconditional), guided: bool).  One batched
-    b=2 forward when the model supports it; t_value may be fractional (UniPC).  `cache` (one dict per sampling run): the
-    [cond | uncond] batch is built once while the conditioning objects stay the same, and the UNet reuses their K/V."""
-    dev = x.device
+    """-> (eps [1 or 2, C, F, h, w] (index 0 conditional, 1 unconditional), guided: bool) — one step's evaluation for every loop of
+    this file.  One batched b=2 forward when the model supports it.  `t_value`: a number, may be fractional (UniPC), filled into a
+    row here; or a prepared fp32 row on the device of B or 2 * B equal entries (DDIM_Gaussian uploads all its rows once): a b = B
+    forward reads the first B, `forward_cfg_pair` the whole row.  Unguided when `guide` is None or 1 or `uc` is None.
+    `cache` (one dict per sampling run): the [cond | uncond] batch is built once while the conditioning objects stay the same, and the
+    UNet reuses their K/V — the context token names the run (a fresh nonce per dict) and the caller's objects with their versions.
+    `forward_cfg_pair` needs a cache and conditioning of batch 1 or B on both sides; conditioning of any other batch never described
+    B videos and takes the forwards below it (the DDIM_Gaussian loop used to hand it to `forward_cfg_pair` as it was)."""
     B = x.shape[0]                            # videos per batch: one timestep for all of them, eps = [cond (B), uncond (B)]
-    tt = torch.full((B,), float(t_value), dtype=torch.float32, device=dev)
+    if torch.is_tensor(t_value) and t_value.ndim == 1:
+        assert t_value.shape[0] in (B, 2 * B), (tuple(t_value.shape), B)
+        tt, tt_pair = t_value[:B], t_value
+    else:
+        tt = tt_pair = torch.full((B,), float(t_value), dtype=torch.float32, device=x.device)
     c0, uc0 = c, uc
+    guided = not (guide is None or guide == 1.0 or uc is None)
+    nonce = cache.setdefault("nonce", next(_RUN_COUNTER)) if cache is not None else next(_RUN_COUNTER)
     if isinstance(c, list):                   # a batch of different prompts (batch_contexts)
-        guided = not (guide is None or guide == 1.0 or uc is None)
-        nonce = cache.setdefault("nonce", next(_RUN_COUNTER)) if cache is not None else next(_RUN_COUNTER)
-        return _eval_ragged(model, x, tt, c, uc, guided, _ctx_ident(nonce, c, uc if guided else None), cfg_parallel).contiguous(), guided
+        return _eval_ragged(model, x, tt_pair if guided else tt, c, uc, guided, _ctx_ident(nonce, c, uc if guided else None),
+                            cfg_parallel).contiguous(), guided
     if B > 1:                                 # conditioning of batch 1 is expanded, conditioning of batch B is taken per video
         c = c.expand(B, *c.shape[1:]) if c.shape[0] == 1 else c
         if uc is not None:
             uc = uc.expand(B, *uc.shape[1:]) if uc.shape[0] == 1 else uc
-    if guide is None or guide == 1.0 or uc is None:
+    if not guided:
         return model(x, tt, c).contiguous(), False
     if cfg_parallel is not None and cfg_parallel.size == 2:
         assert B == 1, "the CFG-pair layout runs one video per pair"
@@ -627,15 +603,27 @@ def _eval_eps_pair(model, x, t_value, c, uc, guide, cfg_parallel=None, cache: Op
         return cfg_parallel.exchange_eps(model(x, tt, mine)).contiguous(), True
     ragged = c.shape[1] != uc.shape[1]        # a prompt of more 77-token chunks than the negative prompt (or fewer): no padding, as the reference
     if cache is not None and hasattr(model, "forward_cfg_pair") and c.shape[0] == uc.shape[0] == B:
-        # (the conditioning OBJECTS the caller holds name the context: the expanded views of a batch are new objects every step)
-        ident = (cache.setdefault("nonce", next(_RUN_COUNTER)), id(c0), c0._version, id(uc0), uc0._version)
+        # (the conditioning OBJECTS the caller holds name the context: the expanded views of a batch are new objects every step, and
+        # prompt scheduling swaps the objects between steps, reconstruct_cond_batch)
+        ident = _ctx_ident(nonce, c0, uc0)
         if cache.get("key") != ident:
             # equal lengths: the [cond | uncond] batch; unequal: the pair itself — the model packs it once per token (forward_cfg_pair)
+            # (refs keeps the tensors alive, so their ids stay unique)
             cache.update(key=ident, ctx=(c, uc) if ragged else torch.cat([c, uc], dim=0), refs=(c0, uc0))
-        return model.forward_cfg_pair(x, tt, cache["ctx"], context_token=ident, single_t=True).contiguous(), True
+        return model.forward_cfg_pair(x, tt_pair, cache["ctx"], context_token=ident, single_t=True).contiguous(), True
     if getattr(model, "supports_cfg_batch", False) and not ragged:
         return model(torch.cat([x, x], dim=0), torch.cat([tt, tt]), torch.cat([c, uc], dim=0)).contiguous(), True
     return torch.cat([model(x, tt, c), model(x, tt, uc)], dim=0).contiguous(), True
+
+
+def _ddim_coef(alphas, alphas_prev, sigmas, sqrt_one_minus_alphas, index, guide):
+    """f[0..5] of a mode-1 DDIM_STEP record from the schedule tables of `make_schedule` (this file's or videocrafter's): every entry
+    cast to fp32 per lookup, then fp32 arithmetic (p_sample_ddim, sampler.py:197-219).  `guide` None: scale 1."""
+    f32 = torch.float32
+    a_t, a_prev = alphas[index].to(f32), alphas_prev[index].to(f32)
+    sigma_t, s1m = sigmas[index].to(f32), sqrt_one_minus_alphas[index].to(f32)
+    return [float(s1m), float(a_t.sqrt()), float(a_prev.sqrt()), float((1.0 - a_prev - sigma_t ** 2).sqrt()),
+            float(sigma_t), float(guide) if guide is not None else 1.0]
 
 
 class DDIMSampler(object):
@@ -665,13 +653,6 @@ class DDIMSampler(object):
         self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = sigmas, alphas, alphas_prev
         self.ddim_sqrt_one_minus_alphas = torch.sqrt(1.0 - alphas)
 
-    def _coef(self, index, guide):
-        f32 = torch.float32
-        a_t, a_prev = self.ddim_alphas[index].to(f32), self.ddim_alphas_prev[index].to(f32)
-        sigma_t, s1m = self.ddim_sigmas[index].to(f32), self.ddim_sqrt_one_minus_alphas[index].to(f32)
-        return [float(s1m), float(a_t.sqrt()), float(a_prev.sqrt()), float((1.0 - a_prev - sigma_t ** 2).sqrt()),
-                float(sigma_t), float(guide) if guide is not None else 1.0]
-
     def _run(self, img, cond, uncond, time_range, total_steps, guide, callback, temperature=1.0, ucg_schedule=None):
         model, dev = self.model, img.device
         if ucg_schedule is not None:
@@ -680,23 +661,15 @@ class DDIMSampler(object):
         _check_batch_layout(self, img.shape[0])     # several videos per batch: one 2V-row forward and one update launch per step
         cond, uncond = batch_contexts(cond, uncond, img.shape[0])
         nxt = torch.empty_like(img)
-        if hasattr(model, "verify_weights"):
-            model.verify_weights(dev)           # the bytes: in-place edits (`w.data += d`) that no version counter shows — once per call
-        if hasattr(model, "refresh_weights"):
-            model.refresh_weights(dev)
-        prev_auto = getattr(model, "auto_refresh", None)
-        if prev_auto is not None:
-            model.auto_refresh = False
-        prev_eps = _want_fp32_eps(model)
         pair_cache = {}
-        try:
+        with _sampling_run(model, dev):
             for i, step in enumerate(time_range):
                 c, uc = reconstruct_conds(cond, uncond, int(step))
                 index = total_steps - i - 1
                 if ucg_schedule is not None:
                     guide = ucg_schedule[i]
                 eps, guided = _eval_eps_pair(model, img, int(step), c, uc, guide, self.cfg_parallel, cache=pair_cache)
-                coef = self._coef(index, guide)
+                coef = _ddim_coef(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas, self.ddim_sqrt_one_minus_alphas, index, guide)
                 if temperature != 1.0:                                     # sigma_t * noise * temperature (sampler.py:216); dir_xt keeps sigma_t
                     coef[4] = float(torch.tensor(coef[4], dtype=torch.float32) * temperature)
                 noise = _step_noise(self, img, coef[4])                    # drawn every step, like noise_like(); sigma_t == 0 <=> eta == 0
@@ -704,10 +677,6 @@ class DDIMSampler(object):
                 img, nxt = nxt, img
                 if callback:
                     callback(i)
-        finally:
-            if prev_auto is not None:
-                model.auto_refresh = prev_auto
-            _restore_eps(model, prev_eps)
         return img
 
     @torch.no_grad()
@@ -764,19 +733,11 @@ class DDIMSampler(object):
         if guide != 1.0:
             assert unconditional_conditioning is not None
         cond, uncond = batch_contexts(c, unconditional_conditioning if guide != 1.0 else None, videos)
-        if hasattr(model, "verify_weights"):
-            model.verify_weights(dev)
-        if hasattr(model, "refresh_weights"):
-            model.refresh_weights(dev)
-        prev_auto = getattr(model, "auto_refresh", None)
-        if prev_auto is not None:
-            model.auto_refresh = False
-        prev_eps = _want_fp32_eps(model)
         pair_cache = {}
         intermediates, inter_steps = [], []
         spare = None            # the buffer the next step may write: never x0 itself, never a kept intermediate
         x_next = x
-        try:
+        with _sampling_run(model, dev):
             for i in range(num_steps):
                 t = i if (model_timesteps == "index" or use_original_steps) else int(self.ddim_timesteps[i])
                 eps, guided = _eval_eps_pair(model, x_next, t, cond, uncond, guide, None, cache=pair_cache)
@@ -795,10 +756,6 @@ class DDIMSampler(object):
                     inter_steps.append(i)
                 if callback:
                     callback(i)
-        finally:
-            if prev_auto is not None:
-                model.auto_refresh = prev_auto
-            _restore_eps(model, prev_eps)
         if x_next is x and x is x0:
             x_next = x.clone()              # t_enc = 0: the caller's tensor is not handed back
         out = {"x_encoded": x_next, "intermediate_steps": inter_steps}
@@ -1030,47 +987,37 @@ class UniPCSampler(object):
             self._thresholds = torch.zeros((steps + (1 if opt["denoise_to_zero"] else 0), x.shape[0], 4), dtype=f32, device=dev)
         guide = unconditional_guidance_scale
         self._pair_cache = {}                      # per sampling run (its nonce keeps cached context K/V from leaking across runs)
-        if hasattr(model, "verify_weights"):
-            model.verify_weights(dev)           # the bytes: in-place edits (`w.data += d`) that no version counter shows — once per call
-        if hasattr(model, "refresh_weights"):
-            model.refresh_weights(dev)
-        prev_auto = getattr(model, "auto_refresh", None)
-        if prev_auto is not None:
-            model.auto_refresh = False
-        prev_eps = _want_fp32_eps(model)
 
         def conds():
             return reconstruct_conds(conditioning, unconditional_conditioning, state.sampling_step)
 
-        try:
-            c, uc = conds()
-            m_prev, t_prev = [self._data_prediction(ns, x, ts[0], c, uc, guide)], [ts[0]]
-            for init_order in range(1, order):                       # warm-up with lower orders (+ corrector: initial_corrector)
+        with _sampling_run(model, dev):
+            try:
                 c, uc = conds()
-                x, mx = self._update(ns, x, m_prev, t_prev, ts[init_order], init_order, opt["initial_corrector"], c, uc, guide,
-                                     variant=opt["variant"])
-                if mx is None:                                       # no corrector: the model at the predicted point (uni_pc.py:705-706)
-                    mx = self._data_prediction(ns, x, ts[init_order], c, uc, guide)
-                m_prev.append(mx)
-                t_prev.append(ts[init_order])
-                if callback is not None:
-                    callback()
-            for step in range(order, steps + 1):
-                c, uc = conds()
-                step_order = min(order, steps + 1 - step) if opt["lower_order_final"] else order
-                use_corr = step != steps                             # no corrector (= no model call) at the last step
-                x, mx = self._update(ns, x, m_prev, t_prev, ts[step], step_order, use_corr, c, uc, guide, variant=opt["variant"])
-                m_prev, t_prev = m_prev[1:] + [mx], t_prev[1:] + [ts[step]]
-                if callback is not None:
-                    callback()
-            if opt["denoise_to_zero"]:                               # x0 at t_0 from the last latent (uni_pc.py:433-437, 740-741); no callback
-                c, uc = conds()
-                x = self._data_prediction(ns, x, float(torch.tensor(t_0, dtype=f32)), c, uc, guide)
-        finally:
-            if prev_auto is not None:
-                model.auto_refresh = prev_auto
-            _restore_eps(model, prev_eps)
-            self.last_thresholds, self._thresholds = self._thresholds, None      # [evaluations, videos, 4] {s, q, v_lo, v_hi} on the device, else None
+                m_prev, t_prev = [self._data_prediction(ns, x, ts[0], c, uc, guide)], [ts[0]]
+                for init_order in range(1, order):                       # warm-up with lower orders (+ corrector: initial_corrector)
+                    c, uc = conds()
+                    x, mx = self._update(ns, x, m_prev, t_prev, ts[init_order], init_order, opt["initial_corrector"], c, uc, guide,
+                                         variant=opt["variant"])
+                    if mx is None:                                       # no corrector: the model at the predicted point (uni_pc.py:705-706)
+                        mx = self._data_prediction(ns, x, ts[init_order], c, uc, guide)
+                    m_prev.append(mx)
+                    t_prev.append(ts[init_order])
+                    if callback is not None:
+                        callback()
+                for step in range(order, steps + 1):
+                    c, uc = conds()
+                    step_order = min(order, steps + 1 - step) if opt["lower_order_final"] else order
+                    use_corr = step != steps                             # no corrector (= no model call) at the last step
+                    x, mx = self._update(ns, x, m_prev, t_prev, ts[step], step_order, use_corr, c, uc, guide, variant=opt["variant"])
+                    m_prev, t_prev = m_prev[1:] + [mx], t_prev[1:] + [ts[step]]
+                    if callback is not None:
+                        callback()
+                if opt["denoise_to_zero"]:                               # x0 at t_0 from the last latent (uni_pc.py:433-437, 740-741); no callback
+                    c, uc = conds()
+                    x = self._data_prediction(ns, x, float(torch.tensor(t_0, dtype=f32)), c, uc, guide)
+            finally:
+                self.last_thresholds, self._thresholds = self._thresholds, None      # [evaluations, videos, 4] {s, q, v_lo, v_hi} on the device, else None
         return x
 
     @torch.no_grad()

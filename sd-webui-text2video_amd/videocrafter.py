@@ -1080,9 +1080,6 @@ class DDIMSampler(object):
             raise NotImplementedError("quantisation / noise dropout / score correctors are not on the hot path")
         size = (batch_size, *shape)
         assert len(size) == 5
-        gens = getattr(self, "noise_gens", None)
-        if gens is not None and len(gens) != batch_size:
-            raise ValueError(f"noise_gens holds {len(gens)} generators for a batch of {batch_size}: one per video")
         if mask is not None:
             # mask blending (ddim.py:188-195): img = q_sample(x0, step - 1) * mask + (1 - mask) * img after every step.  The mask is
             # 5-D and broadcastable to the latent, [b|1, c|1, t|1, h|1, w|1], any float values; a mask of another rank would
@@ -1130,11 +1127,6 @@ class DDIMSampler(object):
         guide = unconditional_guidance_scale
         guided = uc is not None and guide != 1.0
         unet = self.model.model.diffusion_model
-        if hasattr(unet, "verify_weights"):
-            unet.verify_weights(device)         # the bytes: a LoRA merged the reference's way (`weight.data += ...`) moves no version counter
-        unet.refresh_weights(device)
-        prev_auto, unet.auto_refresh = unet.auto_refresh, False
-        prev_eps = S._want_fp32_eps(unet)            # eps in fp32 inside the loop: the CFG combination amplifies fp16 output roundings
         nxt = torch.empty_like(img)
         extra = {} if features_adapter is None else {"features_adapter": features_adapter}     # the same list object every step: converted once
         nb, C = img.shape[0], img.shape[1]          # nb videos per batch (sample_text2video's batch_size)
@@ -1150,7 +1142,8 @@ class DDIMSampler(object):
         iterator = np.flip(timesteps)
         if verbose and S.tqdm is not None:
             iterator = S.tqdm(iterator, desc="DDIM Sampler", total=total_steps)
-        try:
+        # (a LoRA merged the reference's way, `weight.data += ...`, moves no version counter: the guard verifies the bytes)
+        with S._sampling_run(unet, device):
             for i, step in enumerate(iterator):
                 S.state.sampling_step = i
                 if S.state.interrupted:
@@ -1167,10 +1160,9 @@ class DDIMSampler(object):
                     eps = self.model.apply_model(xin, torch.cat([ts, ts]), torch.cat([c, uc]), **extra).contiguous()
                 else:
                     eps = self.model.apply_model(img, ts, c, **extra).contiguous()
-                a_t, a_prev = self.ddim_alphas[index].to(f32), self.ddim_alphas_prev[index].to(f32)
-                sigma_t, s1m = self.ddim_sigmas[index].to(f32), self.ddim_sqrt_one_minus_alphas[index].to(f32)
-                coef = [float(s1m), float(a_t.sqrt()), float(a_prev.sqrt()), float((1.0 - a_prev - sigma_t ** 2).sqrt()),
-                        float(sigma_t) * float(temperature), float(guide) if guided else 1.0]
+                coef = S._ddim_coef(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas, self.ddim_sqrt_one_minus_alphas, index,
+                                    guide if guided else None)
+                coef[4] = coef[4] * float(temperature)        # in double, rounded to fp32 when the record stores it
                 if sample_noise is not None:
                     noise = sample_noise.to(device=device, dtype=f32).contiguous()
                 elif gens is None:            # noise_like(..., noise_gen): CPU generator -> same stream on any device
@@ -1205,9 +1197,6 @@ class DDIMSampler(object):
                     intermediates["pred_x0"].append(px0)
                 if S.state.skipped:
                     break
-        finally:
-            unet.auto_refresh = prev_auto
-            S._restore_eps(unet, prev_eps)
         return img, intermediates
 
 
