@@ -330,6 +330,46 @@ for _T, _Tq, _offs, _Ds in ((5, 2, (0, 2, 3), (40,)), (8, 3, (0, 3, 5), (80,)), 
     for _D in _Ds:
         RELPOS_SHORT_CASES += [_rel(f"lowered-shard-d{_D}-T{_T}-q{_o}+{_Tq}", _D, _T, _Tq, _o, 16, False, sels=(0, 3)) for _o in _offs]
 
+# ---- the keys of the requestable lattice (tests/geometry_lattice.py; profiles/geometry_paths.txt names a witness program for each): other ----
+# ---- latents and frame counts put every head dimension on every kernel form.  The size classes are the launcher's: attention.hip:1253-1255 ----
+# ---- (launch_attn: nq <= 32 -> one wave, with the 32-key tile when the keys fit one; else 4 waves per 128 queries, 64-key tiles),      ----
+# ---- attention.hip:1293-1294 (attn2_kernel<8>: 256 queries per workgroup) and, for nk_tiles, the key-tile loop that runs once or streams ----
+ATTN_CASES += [
+    # one wave, 64 + 13 keys (text cross-attention of a latent of at most 32 positions): ragged and whole query blocks
+    _attn("lowered-cross-d80-nq16-nk77", "cross", 80, 2, 2, 2, 16, 77, 64, placement="second"),
+    _attn("lowered-cross-d64-nq32-nk77", "cross", 64, 2, 2, 2, 32, 77, 64, placement="second"),
+    _attn("lowered-cross-d80-nq32-nk77", "cross", 80, 2, 2, 2, 32, 77, 64, placement="second"),
+    _attn("lowered-cross-d160-nq32-nk77", "cross", 160, 2, 2, 2, 32, 77, 64, placement="second"),
+    # one wave, the 32-key tile, 32 queries and 32 keys: nothing ragged (a latent of 32 positions; 32 frames)
+    _attn("lowered-temporal-d64-n32", "temporal", 64, 2, 3, 2, 32, 32, 32),
+    _attn("lowered-temporal-d80-n32", "temporal", 80, 2, 3, 2, 32, 32, 32),
+    _attn("lowered-temporal-d160-n32", "temporal", 160, 2, 3, 2, 32, 32, 32),
+    # 4 waves: one key tile, ragged (48 keys) and whole (64), under a ragged query block; three whole key tiles under a ragged query block;
+    # four whole key tiles under whole query blocks; 64 + 13 keys under a whole query block
+    _attn("lowered-self-d80-hw48", "self", 80, 2, 1, 2, 48, 48, 64),
+    _attn("lowered-self-d160-hw48", "self", 160, 2, 1, 2, 48, 48, 64),
+    _attn("lowered-self-d80-hw64", "self", 80, 2, 1, 2, 64, 64, 64),
+    _attn("lowered-self-d40-hw192", "self", 40, 2, 1, 2, 192, 192, 64),
+    _attn("lowered-self-d80-hw192", "self", 80, 2, 1, 2, 192, 192, 64),
+    _attn("lowered-self-d160-hw192", "self", 160, 2, 1, 2, 192, 192, 64),
+    _attn("lowered-self-d160-hw256", "self", 160, 2, 1, 2, 256, 256, 64),
+    _attn("lowered-cross-d160-nq128-nk77", "cross", 160, 2, 1, 2, 128, 77, 64, placement="second"),
+    # attn2_kernel<8>: five whole key tiles, one whole 256-query block and a quarter of one (a 40 x 72 latent: 2880 = 11.25 blocks)
+    _attn("lowered-attn2-w8-hw320", "self", 64, 2, 1, 2, 320, 320, 64, attn2=True, waves=8, shift=3),
+]
+# the VALU kernel's TB (attention.hip:1197, 1207-1211: seqattn_kernel<TB>, TB = ceil(T / 8) up to 4) at 17 .. 24 frames (TB = 3) and 25 .. 32
+# (TB = 4), with the table index clamped (R < T - 1) and not; whole clips, then a T-sharded rank's queries at the start and inside the clip
+RELPOS_SHORT_CASES += [
+    _rel("lowered-short-d40-T17", 40, 17, 17, 0, 16, False, sels=(0, 3)),
+    _rel("lowered-short-d80-T17", 80, 17, 17, 0, 16, False, sels=(0, 3)),
+    _rel("lowered-short-d80-T18", 80, 18, 18, 0, 16, False, sels=(0, 3)),
+    _rel("lowered-short-d160-T18", 160, 18, 18, 0, 16, False, sels=(0, 3)),
+]
+RELPOS_SHORT_CASES += [_rel(f"lowered-short-d{_D}-T25", _D, 25, 25, 0, 16, False, sels=(0, 3)) for _D in (40, 80, 160)]
+RELPOS_SHORT_CASES += [_rel(f"lowered-shard-d{_D}-T24-q{_o}+3", _D, 24, 3, _o, 16, False, sels=(0, 3)) for _D in (40, 80, 160) for _o in (0, 3)]
+# relpos_long_kernel on a T-sharded rank of a clip of two key tiles (40 frames): the queries at the start and at the end of the clip
+RELPOS_LONG_CASES += [_rel(f"lowered-shard-d{_D}-T40-q{_o}+5", _D, 40, 5, _o, 16, False) for _D in (40, 80, 160) for _o in (0, 35)]
+
 
 def attn_inputs(c):
     """Item tensors of an ATTN_CASES entry: q [B heads, F nq, D] for the 'cross' layout (the F frames of a sample share its keys) and

@@ -1041,5 +1041,217 @@ _LOWERED = [
     (9, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
     (9, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
 ]
+# the keys of the requestable lattice (tests/geometry_lattice.py) that the matrix lacks: other frame counts and latents put the same
+# epilogues on other tiles and gathers and make rows and columns ragged (profiles/geometry_paths.txt names a witness program for each)
+_LOWERED += [
+    (0, 128, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 2, 0, 0, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (0, 128, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 128, 1, 2, 0, 1, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 2, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 1, 2, 0, 1, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 128, 2, 0, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 2, 0, 0, 1, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (0, 128, 2, 0, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 128, 3, 1, 0, 0, '-', 1, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (0, 64, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (0, 64, 0, 0, 0, 0, '-', 1, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 1, 1, 0, 0, '-', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (0, 64, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 2, 0, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (0, 64, 2, 0, 0, 1, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (1, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (1, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (1, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (1, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (1, 0, 1, 1, 0, 0, 'slab', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 1, 1, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 1, 1, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 2, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 2, 0, 1, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (1, 0, 1, 2, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (11, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (11, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (11, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (11, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (11, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (11, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (11, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (11, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (11, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (11, 0, 1, 1, 1, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 1, 2, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 1, 2, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 1, 2, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (11, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (11, 0, 2, 0, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (11, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (11, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (11, 0, 2, 0, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (12, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (2, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (2, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (2, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (2, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (2, 0, 1, 1, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 1, 1, 1, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (2, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (2, 0, 2, 0, 0, 1, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 2, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 2, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 0, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 0, 0, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (3, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (3, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (3, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (3, 0, 1, 1, 1, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 1, 1, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 2, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 1, 2, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 2, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 2, 0, 0, 0, '-', 0, 0, 1, 3, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 0, '-', 0, 1, 1, 3, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 0, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 1, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (3, 0, 2, 0, 0, 1, '-', 0, 1, 1, 3, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 1, 0, 1, '-', 1),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 0, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 1),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 0, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 1, 0, 1, '-', 1),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 1, 0, 0, 0, 0, '-', 0),
+    (5, 0, 0, 0, 0, 0, '-', 0, 1, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 0, 1, 3, 0, 0, 1, 1, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (5, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 1, 1, 1, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 0, '-', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 1, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 1, 2, 0, 1, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 2, 0, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (5, 0, 2, 0, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (5, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 0, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 1, '-', 0),
+    (8, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (8, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 1, 0, '-', 0),
+    (8, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (8, 0, 1, 1, 0, 0, '-', 0, 0, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 1, 0, '-', 0),
+    (8, 0, 1, 1, 0, 0, '-', 0, 1, 0, 3, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 1, 1, 1, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 1, 1, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 2, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 1, 2, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (8, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (8, 0, 2, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 2, 0, 0, 0, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (8, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (8, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 2, 0, 0, 0, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (8, 0, 2, 0, 0, 1, '-', 0, 0, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (8, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (8, 0, 2, 0, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (8, 0, 2, 0, 0, 1, '-', 0, 1, 0, 3, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 0, 1, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 1, 0, 1, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 0, 0, 0, '-', 0),
+    (9, 0, 0, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 0, 0, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 0, 1, 0, 0, 0, 1, 1, 0, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 0, 1, 3, 0, 0, 1, 1, 0, '-', 0),
+    (9, 0, 1, 1, 0, 0, '-', 0, 0, 1, 3, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 1, 1, 0, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 0, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 1, 0, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 1, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 1, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 1, 0, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 1, 1, 0, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 2, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 2, 0, 0, '-', 0, 1, 1, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 2, 0, 1, '-', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 2, 0, 1, '-', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 2, 0, 1, 'slab', 0, 0, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 1, 2, 0, 1, 'slab', 0, 1, 0, 0, 1, 0, 1, 0, 0, '-', 0),
+    (9, 0, 2, 0, 0, 0, '-', 0, 0, 1, 0, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 2, 0, 0, 0, '-', 0, 0, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 2, 0, 0, 0, '-', 0, 1, 0, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 2, 0, 0, 0, '-', 0, 1, 1, 0, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 2, 0, 0, 1, '-', 0, 0, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+    (9, 0, 2, 0, 0, 1, '-', 0, 0, 1, 3, 0, 0, 1, 0, 0, '-', 0),
+    (9, 0, 2, 0, 0, 1, '-', 0, 1, 1, 0, 1, 0, 1, 0, 1, '-', 0),
+]
 CASES += [_lowered_case(_s) for _s in _LOWERED]
 assert len({c["id"] for c in CASES}) == len(CASES)

@@ -3,6 +3,8 @@
     python tests/golden/make_golden_full.py [c1] [c2] [c3] [c4]      # default: all (~45 min on 8 cores)
     python tests/golden/make_golden_full.py w16 [c1] [c2] [c3] [c4]  # "deployed-weights" goldens  -> *_w16.npz
     python tests/golden/make_golden_full.py w16 c3x12                # 12-frame ZeroScope-XL forward -> zeroscope_xl_12f_w16.npz
+    python tests/golden/make_golden_full.py w16 zs7                  # ZeroScope's native 576x320 (latent 40x72), 7 frames: one forward
+                                                                     # -> zeroscope_40x72_7f_w16.npz
     python tests/golden/make_golden_full.py w16 c1s50                # round 4: 50-step "DDIM" / "UniPC" latents at the full size
     python tests/golden/make_golden_full.py w16 c1s c3s c2s          # round 4: OUTPUT-level goldens (sampled latents) for the other
                                                                      # two samplers at configs[1] and for configs[3] / configs[2]
@@ -53,6 +55,7 @@ XL_GRID = (slice(1, None, 4), slice(2, None, 4))            # [3, 144, 256] of t
 XL_CROP = (slice(128, 256), slice(384, 512))
 N_FRAMES_XL12 = 12
 FRAMES_XL12 = [0, 5, 11]
+N_FRAMES_ZS7 = 7
 W16 = False                 # set by "w16" on the command line
 SUFFIX = ""
 
@@ -221,6 +224,21 @@ def c3x12():
     print(f"c3x12 done forward {t_fwd:.1f}s std {eps.std():.4f}", flush=True)
 
 
+def zs7():
+    """ZeroScope's native 576 x 320 (a latent of 40 x 72) at 7 frames: ragged at every level of the UNet (20160, 5040, 1260 and 315 rows
+    per sample), a geometry outside the other goldens' tile, split-K, GroupNorm and attention classes.  All 7 frames are stored."""
+    unet, _ = _unet()
+    noise, cond, _ = _inputs(N_FRAMES_ZS7, 320, 576)
+    with torch.no_grad():
+        t0 = time.time()
+        eps = unet(noise, torch.tensor([801]), cond)
+        t_fwd = time.time() - t0
+    np.savez_compressed(os.path.join(OUT, f"zeroscope_40x72_7f{SUFFIX}.npz"), unet_eps_frames=eps.numpy(),
+                        frames=np.arange(N_FRAMES_ZS7), eps_std=np.float64(eps.std()),
+                        timing=np.array([t_fwd, torch.get_num_threads()], dtype=np.float64))
+    print(f"zs7 done forward {t_fwd:.1f}s std {eps.std():.4f}", flush=True)
+
+
 def _sample_named(ref, unet, betas, frames, steps, cond, uncond, name, h=256, w=256):
     """`name` in {"DDIM", "UniPC"}: the reference's own Txt2VideoSampler with that sampler (samplers_common.py:165-207 ->
     ddim/sampler.py:110-220 | uni_pc/uni_pc.py:683-743).  Both classes pin their buffers to torch.device("cuda")
@@ -379,6 +397,6 @@ if __name__ == "__main__":
     torch.manual_seed(0)
     if "w16" in sys.argv[1:]:
         W16, SUFFIX = True, "_w16"
-    which = [a for a in sys.argv[1:] if a in ("c1", "c2", "c3", "c4", "c3x12", "c1s", "c3s", "c2s", "c1s50", "c0", "c2s20", "c2s50", "c3s50", "c3s20")] or ["c2", "c3", "c4", "c1"]
+    which = [a for a in sys.argv[1:] if a in ("c1", "c2", "c3", "c4", "c3x12", "c1s", "c3s", "c2s", "c1s50", "c0", "c2s20", "c2s50", "c3s50", "c3s20", "zs7")] or ["c2", "c3", "c4", "c1"]
     for name in which:
         globals()[name]()

@@ -585,7 +585,12 @@ def _build_lowered_gn(c, ncu):
         rows = rows_for_kr(c["kr"], n_inst, C, ncu, COOP_KRS, True)
     elif form == "coop-fallback":
         P.target_cus, rows = 1, 485
-    P.gn_coop = form in ("cooperative", "coop-fallback")
+    elif form == "coop-fallback-one-block":
+        # more instances than compute units: no KR gives a grid of one workgroup per CU (norm.hip coop_chunking), and an instance of 4 rows is
+        # ONE statistics block of the smallest size (Program.groupnorm: 4 rows), so gn_stats_kernel finalises in place (norm.hip:893 g1) —
+        # the per-frame norms of a 250-frame clip at the coarsest level
+        n_inst, rows = ncu + 1, 4
+    P.gn_coop = form in ("cooperative", "coop-fallback", "coop-fallback-one-block")
     P.gn_fused_slice_bytes = 1 << 30 if form == "single_launch" else 0
     P.gn_fused_total_bytes = 1 << 30
     M = n_inst * rows
@@ -602,6 +607,7 @@ def _build_lowered_gn(c, ncu):
     nblk = -(-rows // op.i[11])
     kr = coop_chunking(rows, n_inst, C // 8, ncu, nblk, COOP_KRS)[0] if P.gn_coop else 0
     assert kr == (c["kr"] if form == "cooperative" else 0), (kr, rows, nblk)
+    assert form != "coop-fallback-one-block" or nblk == 1, (rows, nblk)
     if form == "cooperative":
         assert op.p[7].space == "arena" and op.i[18] > 0
         if barrier:
@@ -686,9 +692,10 @@ def _chain_gemm(b, name, kind, X, out_dt, *, seed, geo=None, stride=1, halo=Fals
 
 
 # row geometry of a fused-norm case: (frames, H, W) of one instance against the tile's rows `bm`: half a tile, a whole tile, 1.5 tiles
-# (straddle) or — M ragged — 1.25 tiles; images of 8 / 12 / 16 columns
+# (straddle) or — M ragged — 1.25 tiles (a tile and 32 rows where a quarter tile is no multiple of 32, the unit the lowering asks of an
+# instance: program.py `rows % 32`); images of 8 / 12 / 16 columns
 def _epi_rows(seam, ragged, bm):
-    return {"half": bm // 2, "whole": bm, "straddle": bm + (bm // 4 if ragged else bm // 2)}[seam]
+    return {"half": bm // 2, "whole": bm, "straddle": bm + ((bm // 4 if bm % 128 == 0 else 32) if ragged else bm // 2)}[seam]
 
 
 def _build_lowered_epi(c, ncu):
@@ -708,6 +715,8 @@ def _build_lowered_epi(c, ncu):
         n_inst = 256 * L.GEMM_TILES[tile].per_cu * bm // rows + 2
         if kind == "tconv":
             n_inst = -(-n_inst // 5) * 5
+    while (n_inst * rows % bm != 0) != bool(ragged):              # the next instance (clip) count at which M is whole tiles, or is not
+        n_inst += 5 if kind == "tconv" else 1
     M = n_inst * rows
     assert (M % bm != 0) == bool(ragged), (M, bm)
     geo = (5 if kind == "tconv" else 1, rows // 16 if rows % 16 == 0 else rows // 8, 16 if rows % 16 == 0 else 8)
@@ -899,10 +908,14 @@ _LOWERED_GN = [
     ('three_launch', 'f16', 1, 0, 0, 0, 0, 0),
     ('three_launch', 'f32', 1, 0, 0, 0, 0, 0),
 ]
-for _form, _dt, _gsilu, _lo, _cast, _kr, _bar, _cl in _LOWERED_GN:
-    CASES.append(_case("lowered_gn", f"lowered-gn-{_form}-{_dt}{'-silu' if _gsilu else ''}{'-lo' if _lo else ''}{('', '-cast', '-cast+lo')[_cast]}"
-                       f"{'-KR' + str(_kr) if _kr else ''}{'-barrier' if _bar else ''}{'-C2560' if _cl else ''}", "marked", form=_form, dt=_dt, silu=bool(_gsilu),
-                       lo=bool(_lo), cast=_cast, kr=_kr, barrier=bool(_bar), cols_loop=_cl, seed=700 + len(CASES)))
+def _lowered_gn_cases(specs):
+    for _form, _dt, _gsilu, _lo, _cast, _kr, _bar, _cl in specs:
+        CASES.append(_case("lowered_gn", f"lowered-gn-{_form}-{_dt}{'-silu' if _gsilu else ''}{'-lo' if _lo else ''}{('', '-cast', '-cast+lo')[_cast]}"
+                           f"{'-KR' + str(_kr) if _kr else ''}{'-barrier' if _bar else ''}{'-C2560' if _cl else ''}", "marked", form=_form, dt=_dt, silu=bool(_gsilu),
+                           lo=bool(_lo), cast=_cast, kr=_kr, barrier=bool(_bar), cols_loop=_cl, seed=700 + len(CASES)))
+
+
+_lowered_gn_cases(_LOWERED_GN)
 # ... sharded phases 1 / 2 and the strip-fed phase 3: halo rows on both sides (three parts), fp16 inputs, no SiLU, no low-order image, parts of
 # one statistics block (4 + 2 rows), the column loop (C = 2560), strips folded by a workgroup (C = 1280: 26 strips x 40 channels > 1024; 4160
 # rows: one row more or less in n shows only against the hi + lo figure, so those two keep the low-order image).  (`x_dead` in the
@@ -996,6 +1009,107 @@ _LOWERED_EPI = [
     (8, 'tconv', 1, 0, 0, 0, 'f16', 0, 0, 1, 0, 1, 'whole', 0),
     (8, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'straddle', 0),
 ]
+# ... of the requestable lattice (tests/geometry_lattice.py; profiles/geometry_paths.txt names a witness program for each): other frame counts
+# and latents put the same fused norms on the other tiles and make rows and columns ragged.  gn_seam is t2v_kernels.h:903-913's class (an
+# instance of half a tile, whole tiles, or a tile that straddles two instances); gn_chunked is gemm.hip:361 / gemm2.hip:519
+# t2v_launch_coresident's (more tiles than the device holds at once: the launch is cut into row chunks)
+_LOWERED_EPI += [
+    (0,'plain',1,0,0,0,'f32',0,1,0,0,0,'straddle',1), (0,'plain',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (0,'plain',1,0,0,0,'f32',0,1,1,0,0,'half',1),
+    (0,'plain',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (0,'plain',1,0,0,0,'f32',0,1,1,0,0,'straddle',1), (0,'plain',1,0,0,0,'f32',0,1,1,0,0,'whole',1),
+    (0,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',0), (0,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',1), (0,'tconv',1,0,0,0,'f16',0,0,1,0,1,'straddle',1),
+    (0,'tconv',1,0,0,0,'f16',0,0,1,0,1,'whole',1), (0,'tconv',1,0,0,0,'f32',0,1,0,0,0,'half',1), (0,'tconv',1,0,0,0,'f32',0,1,0,0,0,'straddle',0),
+    (0,'tconv',1,0,0,0,'f32',0,1,0,0,0,'straddle',1), (0,'tconv',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (0,'tconv',1,0,0,0,'f32',0,1,1,0,0,'half',1),
+    (0,'tconv',1,0,0,0,'f32',0,1,1,0,0,'straddle',1), (0,'tconv',1,0,0,0,'f32',0,1,1,0,0,'whole',1), (0,'tconv',1,0,1,0,'f32',0,1,0,0,0,'straddle',0),
+    (0,'tconv',1,0,1,0,'f32',0,1,0,0,0,'straddle',1), (0,'tconv',1,1,0,0,'f32',0,1,0,0,0,'whole',1),
+    (11,'conv',1,0,0,0,'f16',1,0,1,0,1,'half',0), (11,'conv',1,0,0,0,'f16',1,0,1,0,1,'half',1), (11,'conv',1,0,0,0,'f16',1,0,1,0,1,'straddle',0),
+    (11,'conv',1,0,0,0,'f16',1,0,1,0,1,'straddle',1), (11,'conv',1,0,0,0,'f16',1,0,1,0,1,'whole',1), (11,'conv',1,0,0,0,'f32',0,1,0,0,0,'whole',1),
+    (11,'conv',1,0,0,0,'f32',0,1,0,1,0,'straddle',0), (11,'conv',1,0,0,0,'f32',0,1,0,1,0,'straddle',1), (11,'conv',1,0,0,0,'f32',0,1,0,1,0,'whole',1),
+    (11,'conv',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (11,'conv',1,0,0,0,'f32',0,1,1,0,0,'straddle',1), (11,'conv',1,0,0,0,'f32',0,1,1,0,0,'whole',0),
+    (11,'conv',1,0,0,0,'f32',0,1,1,0,0,'whole',1), (11,'conv',1,0,1,0,'f16',1,0,1,0,1,'straddle',0), (11,'conv',1,0,1,0,'f16',1,0,1,0,1,'straddle',1),
+    (11,'conv',1,0,1,0,'f32',0,1,0,1,0,'straddle',0), (11,'conv',1,0,1,0,'f32',0,1,1,0,0,'straddle',0), (11,'conv',2,0,0,0,'f32',0,0,1,0,0,'half',0),
+    (11,'conv',2,0,0,0,'f32',0,0,1,0,0,'half',1), (11,'conv',2,0,0,0,'f32',0,0,1,0,0,'straddle',0), (11,'conv',2,0,0,0,'f32',0,0,1,0,0,'straddle',1),
+    (11,'conv',2,0,1,0,'f32',0,0,1,0,0,'straddle',0), (11,'conv',2,0,1,0,'f32',0,0,1,0,0,'straddle',1), (11,'plain',1,0,0,0,'f32',0,1,0,0,0,'straddle',0),
+    (11,'plain',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (11,'plain',1,0,0,0,'f32',0,1,0,1,0,'straddle',0), (11,'plain',1,0,0,0,'f32',0,1,0,1,0,'straddle',1),
+    (11,'plain',1,0,0,0,'f32',0,1,0,1,0,'whole',1), (11,'plain',1,0,0,0,'f32',0,1,1,0,0,'half',0), (11,'plain',1,0,0,0,'f32',0,1,1,0,0,'half',1),
+    (11,'plain',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (11,'plain',1,0,0,0,'f32',0,1,1,0,0,'straddle',1), (11,'plain',1,0,0,0,'f32',0,1,1,0,0,'whole',1),
+    (11,'plain',1,0,1,0,'f32',0,1,0,0,0,'straddle',0), (11,'plain',1,0,1,0,'f32',0,1,0,1,0,'straddle',0), (11,'plain',1,0,1,0,'f32',0,1,1,0,0,'half',0),
+    (11,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',0), (11,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',1), (11,'tconv',1,0,0,0,'f16',0,0,1,0,1,'straddle',0),
+    (11,'tconv',1,0,0,0,'f16',0,0,1,0,1,'straddle',1), (11,'tconv',1,0,0,0,'f16',0,0,1,0,1,'whole',1), (11,'tconv',1,0,0,0,'f32',0,1,0,0,0,'straddle',1),
+    (11,'tconv',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (11,'tconv',1,0,0,0,'f32',0,1,0,1,0,'half',0), (11,'tconv',1,0,0,0,'f32',0,1,0,1,0,'half',1),
+    (11,'tconv',1,0,0,0,'f32',0,1,0,1,0,'straddle',0), (11,'tconv',1,0,0,0,'f32',0,1,0,1,0,'straddle',1), (11,'tconv',1,0,0,0,'f32',0,1,0,1,0,'whole',1),
+    (11,'tconv',1,0,1,0,'f16',0,0,1,0,1,'straddle',0), (11,'tconv',1,0,1,0,'f32',0,1,0,1,0,'straddle',0), (11,'tconv',1,0,1,0,'f32',0,1,0,1,0,'straddle',1),
+    (11,'tconv',1,1,0,0,'f32',0,1,0,1,0,'straddle',0), (11,'tconv',1,1,0,0,'f32',0,1,0,1,0,'whole',1),
+    (3,'conv',1,0,0,0,'f16',1,0,1,0,1,'half',0), (3,'conv',1,0,0,0,'f16',1,0,1,0,1,'half',1), (3,'conv',1,0,0,0,'f16',1,0,1,0,1,'straddle',0),
+    (3,'conv',1,0,0,0,'f16',1,0,1,0,1,'straddle',1), (3,'conv',1,0,0,0,'f16',1,0,1,0,1,'whole',1), (3,'conv',1,0,0,0,'f32',0,1,0,0,0,'straddle',0),
+    (3,'conv',1,0,0,0,'f32',0,1,0,0,0,'whole',0), (3,'conv',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (3,'conv',1,0,0,0,'f32',0,1,1,0,0,'whole',0),
+    (3,'conv',1,0,1,0,'f16',1,0,1,0,1,'half',0), (3,'conv',1,0,1,0,'f16',1,0,1,0,1,'half',1), (3,'conv',1,0,1,0,'f16',1,0,1,0,1,'straddle',0),
+    (3,'conv',1,0,1,0,'f16',1,0,1,0,1,'straddle',1), (3,'conv',1,0,1,0,'f32',0,1,0,0,0,'straddle',0), (3,'conv',1,0,1,0,'f32',0,1,1,0,0,'straddle',0),
+    (3,'conv',2,0,0,0,'f32',0,0,1,0,0,'half',0), (3,'conv',2,0,0,0,'f32',0,0,1,0,0,'straddle',0), (3,'conv',2,0,0,0,'f32',0,0,1,0,0,'whole',0),
+    (3,'conv',2,0,1,0,'f32',0,0,1,0,0,'straddle',0), (3,'plain',1,0,0,0,'f32',0,1,0,0,0,'straddle',0), (3,'plain',1,0,0,0,'f32',0,1,0,0,0,'whole',0),
+    (3,'plain',1,0,0,0,'f32',0,1,1,0,0,'half',0), (3,'plain',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (3,'plain',1,0,0,1,'f32',0,1,0,0,0,'straddle',0),
+    (3,'plain',1,0,0,1,'f32',0,1,0,0,0,'straddle',1), (3,'plain',1,0,0,1,'f32',0,1,0,0,0,'whole',0), (3,'plain',1,0,0,1,'f32',0,1,0,0,0,'whole',1),
+    (3,'plain',1,0,0,1,'f32',0,1,1,0,0,'half',0), (3,'plain',1,0,0,1,'f32',0,1,1,0,0,'straddle',0), (3,'plain',1,0,0,1,'f32',0,1,1,0,0,'straddle',1),
+    (3,'plain',1,0,0,1,'f32',0,1,1,0,0,'whole',1), (3,'plain',1,0,1,0,'f32',0,1,0,0,0,'straddle',0), (3,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',0),
+    (3,'plain',1,0,1,1,'f32',0,1,0,0,0,'straddle',0), (3,'plain',1,0,1,1,'f32',0,1,1,0,0,'straddle',0), (3,'plain',1,0,1,1,'f32',0,1,1,0,0,'straddle',1),
+    (3,'tconv',1,0,0,0,'f16',0,0,1,0,1,'straddle',0), (3,'tconv',1,0,0,0,'f16',0,0,1,0,1,'whole',0), (3,'tconv',1,0,0,0,'f32',0,1,0,0,0,'half',0),
+    (3,'tconv',1,0,0,0,'f32',0,1,0,0,0,'straddle',0), (3,'tconv',1,0,0,0,'f32',0,1,0,0,0,'whole',0), (3,'tconv',1,0,0,0,'f32',0,1,1,0,0,'half',0),
+    (3,'tconv',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (3,'tconv',1,0,0,0,'f32',0,1,1,0,0,'whole',0), (3,'tconv',1,0,0,1,'f16',0,0,1,0,1,'straddle',0),
+    (3,'tconv',1,0,0,1,'f16',0,0,1,0,1,'straddle',1), (3,'tconv',1,0,0,1,'f16',0,0,1,0,1,'whole',0), (3,'tconv',1,0,0,1,'f16',0,0,1,0,1,'whole',1),
+    (3,'tconv',1,0,0,1,'f32',0,1,0,0,0,'half',0), (3,'tconv',1,0,0,1,'f32',0,1,0,0,0,'straddle',0), (3,'tconv',1,0,0,1,'f32',0,1,0,0,0,'straddle',1),
+    (3,'tconv',1,0,0,1,'f32',0,1,0,0,0,'whole',0), (3,'tconv',1,0,0,1,'f32',0,1,0,0,0,'whole',1), (3,'tconv',1,0,1,0,'f16',0,0,1,0,1,'straddle',0),
+    (3,'tconv',1,0,1,0,'f32',0,1,0,0,0,'straddle',0), (3,'tconv',1,0,1,0,'f32',0,1,1,0,0,'straddle',0), (3,'tconv',1,0,1,1,'f16',0,0,1,0,1,'straddle',0),
+    (3,'tconv',1,0,1,1,'f32',0,1,0,0,0,'straddle',0), (3,'tconv',1,0,1,1,'f32',0,1,0,0,0,'straddle',1), (3,'tconv',1,1,0,0,'f32',0,1,0,0,0,'half',0),
+    (3,'tconv',1,1,1,0,'f32',0,1,0,0,0,'half',0),
+    (5,'conv',1,0,0,0,'f16',1,0,1,0,1,'half',1), (5,'conv',1,0,0,0,'f16',1,0,1,0,1,'straddle',0), (5,'conv',1,0,0,0,'f16',1,0,1,0,1,'straddle',1),
+    (5,'conv',1,0,0,0,'f32',0,1,0,0,0,'straddle',0), (5,'conv',1,0,0,0,'f32',0,1,0,0,0,'straddle',1), (5,'conv',1,0,0,0,'f32',0,1,0,0,0,'whole',0),
+    (5,'conv',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (5,'conv',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (5,'conv',1,0,0,0,'f32',0,1,1,0,0,'straddle',1),
+    (5,'conv',1,0,0,0,'f32',0,1,1,0,0,'whole',1), (5,'conv',1,0,0,1,'f16',1,0,1,0,1,'half',0), (5,'conv',1,0,0,1,'f32',0,1,0,1,0,'half',0),
+    (5,'conv',1,0,0,1,'f32',0,1,1,0,0,'half',0), (5,'conv',1,0,0,1,'f32',0,1,1,0,0,'straddle',0), (5,'conv',1,0,0,1,'f32',0,1,1,0,0,'whole',0),
+    (5,'conv',1,0,1,0,'f16',1,0,1,0,1,'half',1), (5,'conv',1,0,1,0,'f16',1,0,1,0,1,'straddle',0), (5,'conv',1,0,1,0,'f16',1,0,1,0,1,'straddle',1),
+    (5,'conv',1,0,1,0,'f32',0,1,0,0,0,'straddle',0), (5,'conv',1,0,1,0,'f32',0,1,1,0,0,'straddle',0), (5,'conv',1,0,1,1,'f16',1,0,1,0,1,'half',0),
+    (5,'conv',1,0,1,1,'f32',0,1,0,1,0,'half',0), (5,'conv',1,0,1,1,'f32',0,1,1,0,0,'half',0), (5,'conv',1,0,1,1,'f32',0,1,1,0,0,'straddle',0),
+    (5,'conv',2,0,0,0,'f32',0,0,1,0,0,'half',0), (5,'conv',2,0,0,0,'f32',0,0,1,0,0,'half',1), (5,'conv',2,0,0,0,'f32',0,0,1,0,0,'straddle',0),
+    (5,'conv',2,0,0,0,'f32',0,0,1,0,0,'straddle',1), (5,'conv',2,0,0,0,'f32',0,0,1,0,0,'whole',1), (5,'conv',2,0,0,1,'f32',0,0,1,0,0,'half',0),
+    (5,'conv',2,0,0,1,'f32',0,0,1,0,0,'straddle',0), (5,'conv',2,0,1,0,'f32',0,0,1,0,0,'half',0), (5,'conv',2,0,1,0,'f32',0,0,1,0,0,'half',1),
+    (5,'conv',2,0,1,0,'f32',0,0,1,0,0,'straddle',0), (5,'conv',2,0,1,0,'f32',0,0,1,0,0,'straddle',1), (5,'conv',2,0,1,1,'f32',0,0,1,0,0,'half',0),
+    (5,'conv',2,0,1,1,'f32',0,0,1,0,0,'straddle',0), (5,'plain',1,0,0,0,'f32',0,1,0,0,0,'half',0), (5,'plain',1,0,0,0,'f32',0,1,0,0,0,'straddle',0),
+    (5,'plain',1,0,0,0,'f32',0,1,0,0,0,'straddle',1), (5,'plain',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (5,'plain',1,0,0,0,'f32',0,1,1,0,0,'half',1),
+    (5,'plain',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (5,'plain',1,0,0,0,'f32',0,1,1,0,0,'straddle',1), (5,'plain',1,0,0,0,'f32',0,1,1,0,0,'whole',1),
+    (5,'plain',1,0,0,1,'f32',0,1,0,1,0,'half',0), (5,'plain',1,0,0,1,'f32',0,1,0,1,0,'straddle',0), (5,'plain',1,0,0,1,'f32',0,1,0,1,0,'whole',0),
+    (5,'plain',1,0,0,1,'f32',0,1,1,0,0,'half',0), (5,'plain',1,0,1,0,'f32',0,1,0,0,0,'half',0), (5,'plain',1,0,1,0,'f32',0,1,0,0,0,'straddle',0),
+    (5,'plain',1,0,1,0,'f32',0,1,1,0,0,'half',0), (5,'plain',1,0,1,0,'f32',0,1,1,0,0,'half',1), (5,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',0),
+    (5,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',1), (5,'plain',1,0,1,1,'f32',0,1,0,1,0,'half',0), (5,'plain',1,0,1,1,'f32',0,1,0,1,0,'straddle',0),
+    (5,'plain',1,0,1,1,'f32',0,1,1,0,0,'half',0), (5,'tconv',1,0,0,0,'f16',0,0,1,0,1,'straddle',0), (5,'tconv',1,0,0,0,'f16',0,0,1,0,1,'straddle',1),
+    (5,'tconv',1,0,0,0,'f16',0,0,1,0,1,'whole',1), (5,'tconv',1,0,0,0,'f32',0,1,0,0,0,'half',1), (5,'tconv',1,0,0,0,'f32',0,1,0,0,0,'straddle',0),
+    (5,'tconv',1,0,0,0,'f32',0,1,0,0,0,'straddle',1), (5,'tconv',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (5,'tconv',1,0,0,0,'f32',0,1,1,0,0,'half',0),
+    (5,'tconv',1,0,0,0,'f32',0,1,1,0,0,'straddle',0), (5,'tconv',1,0,0,0,'f32',0,1,1,0,0,'whole',0), (5,'tconv',1,0,0,1,'f16',0,0,1,0,1,'half',0),
+    (5,'tconv',1,0,0,1,'f16',0,0,1,0,1,'straddle',0), (5,'tconv',1,0,0,1,'f16',0,0,1,0,1,'whole',0), (5,'tconv',1,0,0,1,'f32',0,1,0,1,0,'half',0),
+    (5,'tconv',1,0,0,1,'f32',0,1,0,1,0,'straddle',0), (5,'tconv',1,0,0,1,'f32',0,1,0,1,0,'whole',0), (5,'tconv',1,0,1,0,'f16',0,0,1,0,1,'straddle',0),
+    (5,'tconv',1,0,1,0,'f32',0,1,0,0,0,'half',0), (5,'tconv',1,0,1,0,'f32',0,1,0,0,0,'half',1), (5,'tconv',1,0,1,0,'f32',0,1,0,0,0,'straddle',0),
+    (5,'tconv',1,0,1,0,'f32',0,1,0,0,0,'straddle',1), (5,'tconv',1,0,1,0,'f32',0,1,1,0,0,'half',0), (5,'tconv',1,0,1,0,'f32',0,1,1,0,0,'straddle',0),
+    (5,'tconv',1,0,1,1,'f16',0,0,1,0,1,'half',0), (5,'tconv',1,0,1,1,'f16',0,0,1,0,1,'straddle',0), (5,'tconv',1,0,1,1,'f32',0,1,0,1,0,'half',0),
+    (5,'tconv',1,0,1,1,'f32',0,1,0,1,0,'straddle',0), (5,'tconv',1,1,0,1,'f32',0,1,0,1,0,'whole',0),
+    (8,'conv',1,0,0,0,'f16',1,0,1,0,1,'half',0), (8,'conv',1,0,0,0,'f16',1,0,1,0,1,'half',1), (8,'conv',1,0,0,0,'f16',1,0,1,0,1,'straddle',1),
+    (8,'conv',1,0,0,0,'f16',1,0,1,0,1,'whole',0), (8,'conv',1,0,0,0,'f16',1,0,1,0,1,'whole',1), (8,'conv',1,0,0,0,'f32',0,1,0,0,0,'straddle',0),
+    (8,'conv',1,0,0,0,'f32',0,1,0,0,0,'straddle',1), (8,'conv',1,0,0,0,'f32',0,1,0,0,0,'whole',0), (8,'conv',1,0,0,0,'f32',0,1,0,0,0,'whole',1),
+    (8,'conv',1,0,0,0,'f32',0,1,0,1,0,'whole',0), (8,'conv',1,0,0,0,'f32',0,1,0,1,0,'whole',1), (8,'conv',1,0,0,0,'f32',0,1,1,0,0,'straddle',0),
+    (8,'conv',1,0,0,0,'f32',0,1,1,0,0,'straddle',1), (8,'conv',1,0,0,0,'f32',0,1,1,0,0,'whole',1), (8,'conv',1,0,1,0,'f16',1,0,1,0,1,'straddle',0),
+    (8,'conv',1,0,1,0,'f16',1,0,1,0,1,'straddle',1), (8,'conv',1,0,1,0,'f32',0,1,0,0,0,'straddle',0), (8,'conv',1,0,1,0,'f32',0,1,0,0,0,'straddle',1),
+    (8,'conv',1,0,1,0,'f32',0,1,0,1,0,'straddle',0), (8,'conv',1,0,1,0,'f32',0,1,1,0,0,'straddle',0), (8,'conv',1,0,1,0,'f32',0,1,1,0,0,'straddle',1),
+    (8,'conv',2,0,0,0,'f32',0,0,1,0,0,'half',0), (8,'conv',2,0,0,0,'f32',0,0,1,0,0,'half',1), (8,'conv',2,0,0,0,'f32',0,0,1,0,0,'straddle',0),
+    (8,'conv',2,0,0,0,'f32',0,0,1,0,0,'straddle',1), (8,'conv',2,0,0,0,'f32',0,0,1,0,0,'whole',0), (8,'conv',2,0,1,0,'f32',0,0,1,0,0,'straddle',0),
+    (8,'conv',2,0,1,0,'f32',0,0,1,0,0,'straddle',1), (8,'plain',1,0,0,0,'f32',0,1,0,0,0,'straddle',1), (8,'plain',1,0,0,0,'f32',0,1,0,0,0,'whole',0),
+    (8,'plain',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (8,'plain',1,0,0,0,'f32',0,1,0,1,0,'whole',1), (8,'plain',1,0,0,0,'f32',0,1,1,0,0,'half',0),
+    (8,'plain',1,0,0,0,'f32',0,1,1,0,0,'half',1), (8,'plain',1,0,0,0,'f32',0,1,1,0,0,'straddle',1), (8,'plain',1,0,0,0,'f32',0,1,1,0,0,'whole',0),
+    (8,'plain',1,0,0,0,'f32',0,1,1,0,0,'whole',1), (8,'plain',1,0,1,0,'f32',0,1,0,0,0,'straddle',1), (8,'plain',1,0,1,0,'f32',0,1,0,1,0,'straddle',0),
+    (8,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',0), (8,'plain',1,0,1,0,'f32',0,1,1,0,0,'straddle',1), (8,'tconv',1,0,0,0,'f16',0,0,1,0,1,'straddle',1),
+    (8,'tconv',1,0,0,0,'f16',0,0,1,0,1,'whole',1), (8,'tconv',1,0,0,0,'f32',0,1,0,0,0,'half',0), (8,'tconv',1,0,0,0,'f32',0,1,0,0,0,'half',1),
+    (8,'tconv',1,0,0,0,'f32',0,1,0,0,0,'straddle',0), (8,'tconv',1,0,0,0,'f32',0,1,0,0,0,'straddle',1), (8,'tconv',1,0,0,0,'f32',0,1,0,0,0,'whole',0),
+    (8,'tconv',1,0,0,0,'f32',0,1,0,0,0,'whole',1), (8,'tconv',1,0,0,0,'f32',0,1,0,1,0,'straddle',1), (8,'tconv',1,0,0,0,'f32',0,1,0,1,0,'whole',0),
+    (8,'tconv',1,0,0,0,'f32',0,1,0,1,0,'whole',1), (8,'tconv',1,0,1,0,'f16',0,0,1,0,1,'straddle',0), (8,'tconv',1,0,1,0,'f16',0,0,1,0,1,'straddle',1),
+    (8,'tconv',1,0,1,0,'f32',0,1,0,0,0,'straddle',1), (8,'tconv',1,0,1,0,'f32',0,1,0,1,0,'straddle',0), (8,'tconv',1,0,1,0,'f32',0,1,0,1,0,'straddle',1),
+    (8,'tconv',1,1,0,0,'f32',0,1,0,1,0,'whole',0), (8,'tconv',1,1,0,0,'f32',0,1,0,1,0,'whole',1),
+]
 for _n, _e in enumerate(_LOWERED_EPI):
     CASES.append(_case("lowered_epi", "lowered-epi-t%d-%s%s%s%s%s-%s%s%s%s%s%s-%s%s" % (
         _e[0], _e[1], "-s2" if _e[2] == 2 else "", "-halo" if _e[3] else "", "-mr" if _e[4] else "", "-nr" if _e[5] else "", _e[6], "-rowbias" if _e[7] else "",
@@ -1027,6 +1141,18 @@ _LOWERED_SPLITK = [
     (8, 'f32', 0, 0, 1, 0, 0),
     (8, 'f32', 0, 1, 0, 0, 0),
     (8, 'f32', 0, 1, 1, 0, 0),
+]
+# ... of the requestable lattice (tests/geometry_lattice.py): KR is the first count of norm.hip:788 t2v_launch_splitk_reduce_gn's list
+# (1, 2, 4, 8, 12, 16, 20) whose grid is at most one workgroup per CU — other instance sizes take 16 and 20 and meet the other epilogues
+_LOWERED_SPLITK += [
+    (12, 'f32', 0, 1, 0, 0, 0),
+    (16, 'f16', 1, 0, 1, 0, 1),
+    (16, 'f32', 0, 0, 1, 0, 0),
+    (20, 'f16', 1, 0, 1, 0, 1),
+    (20, 'f32', 0, 0, 1, 0, 0),
+    (4, 'f16', 0, 0, 1, 0, 1),
+    (4, 'f32', 0, 1, 0, 1, 0),
+    (8, 'f32', 0, 1, 0, 1, 0),
 ]
 for _n, _e in enumerate(_LOWERED_SPLITK):
     CASES.append(_case("lowered_splitk", "lowered-splitk-KR%d-%s%s%s%s%s%s" % (_e[0], _e[1], "-rowbias" if _e[2] else "", "-res" if _e[3] else "",
@@ -1078,8 +1204,63 @@ _LOWERED_LN = [
     (9, 2, 1, 1, 0, 0, 1),
     (9, 2, 1, 1, 1, 0, 1),
 ]
+# ... of the requestable lattice: the same fused LayerNorms on the tiles other row counts select, ragged in M and N, and cut into row chunks
+# (lnx_chunked: more tiles than program.py's co-residency bound, per_cu x CUs or the record region)
+_LOWERED_LN += [
+    (0, 2, 0, 0, 0, 0, 1),
+    (0, 2, 0, 0, 1, 0, 1),
+    (0, 2, 1, 0, 0, 0, 1),
+    (0, 2, 1, 0, 1, 0, 1),
+    (11, 1, 1, 0, 0, 0, 0),
+    (11, 1, 1, 0, 1, 0, 0),
+    (12, 2, 1, 0, 0, 0, 1),
+    (12, 2, 1, 0, 1, 0, 1),
+    (2, 1, 1, 0, 0, 0, 0),
+    (2, 1, 1, 0, 1, 0, 0),
+    (3, 2, 0, 1, 0, 0, 1),
+    (3, 2, 0, 1, 1, 0, 1),
+    (3, 2, 1, 1, 0, 0, 0),
+    (3, 2, 1, 1, 0, 0, 1),
+    (3, 2, 1, 1, 1, 0, 0),
+    (3, 2, 1, 1, 1, 0, 1),
+    (5, 2, 0, 1, 0, 0, 0),
+    (5, 2, 1, 1, 0, 0, 0),
+    (9, 2, 0, 0, 0, 0, 0),
+    (9, 2, 0, 0, 1, 0, 0),
+    (9, 2, 0, 1, 0, 0, 1),
+    (9, 2, 0, 1, 1, 0, 1),
+]
 for _n, _e in enumerate(_LOWERED_LN):
     CASES.append(_case("lowered_ln", "lowered-ln%d-t%d%s%s%s%s%s" % (_e[1], _e[0], "-mr" if _e[2] else "", "-nr" if _e[3] else "", "-res" if _e[4] else "",
                                                                       "-wrap" if _e[5] else "", "-chunked" if _e[6] else ""),
                        ("distinct", "offset")[_n % 2 if _e[4] else 0], tile=_e[0], mode=_e[1], m_ragged=_e[2], n_ragged=_e[3], res=bool(_e[4]), wrap=_e[5], chunked=_e[6], seed=1200 + _n))
+# ... of the requestable lattice, stand-alone GroupNorm records (the fields of _LOWERED_GN; last in the list: the seeds above count the cases
+# before them).  KR: norm.hip:629 coop_chunking takes the first of (4, 8, 12, 16, 20) whose grid is at most one workgroup per CU, so every
+# latent size has its own; `cols_loop` (C = 2560: more than 256 column vectors, norm.hip:895 R = 1) meets each of them at the 8 x 8-level
+# of a large latent.  `coop-fallback-one-block`: no KR fits and an instance is one statistics block (norm.hip:893 g1)
+_lowered_gn_cases([
+    ('coop-fallback', 'f32', 1, 0, 0, 0, 0, 1),
+    ('coop-fallback-one-block', 'f16', 1, 0, 0, 0, 0, 0),
+    ('coop-fallback-one-block', 'f32', 0, 0, 0, 0, 0, 0),
+    ('coop-fallback-one-block', 'f32', 0, 1, 0, 0, 0, 0),
+    ('coop-fallback-one-block', 'f32', 1, 0, 0, 0, 0, 0),
+    ('coop-fallback-one-block', 'f32', 1, 0, 2, 0, 0, 0),
+    ('coop-fallback-one-block', 'f32', 1, 0, 2, 0, 0, 1),
+    ('cooperative', 'f16', 1, 0, 0, 20, 0, 0),
+    ('cooperative', 'f32', 0, 0, 0, 12, 0, 0),
+    ('cooperative', 'f32', 0, 0, 0, 20, 0, 0),
+    ('cooperative', 'f32', 0, 1, 0, 12, 0, 0),
+    ('cooperative', 'f32', 0, 1, 0, 20, 0, 0),
+    ('cooperative', 'f32', 1, 0, 0, 12, 0, 1),
+    ('cooperative', 'f32', 1, 0, 0, 16, 0, 1),
+    ('cooperative', 'f32', 1, 0, 2, 12, 0, 1),
+    ('cooperative', 'f32', 1, 0, 2, 16, 0, 1),
+    ('cooperative', 'f32', 1, 0, 2, 20, 0, 0),
+    ('cooperative', 'f32', 1, 0, 2, 20, 0, 1),
+    ('cooperative', 'f32', 1, 0, 2, 4, 0, 1),
+    ('cooperative', 'f32', 1, 0, 2, 8, 0, 0),
+    ('cooperative', 'f32', 1, 0, 2, 8, 0, 1),
+])
+# the strip-fed norm with the workgroup fold (norm.hip:933: more than 1024 strip sums per instance) on an fp16 stream without a low-order image
+CASES.append(_case("strips", "lowered-strips-wg-2x832x1280-f16", "marked", n_inst=2, rows=832, C=1280, wide=True, dt="f16", lo=False, seed=304))
 assert len({c["id"] for c in CASES}) == len(CASES)

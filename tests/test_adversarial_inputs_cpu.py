@@ -84,15 +84,15 @@ def test_case_lists_cover_what_they_name():
     spatial = {(c["D"], c["nq"]) for c in A.ATTN_CASES if c["id"].startswith("spatial") and c["variant"] == "late"}
     assert spatial == {(D, hw) for D in (40, 64, 80, 160) for hw in (300, 1000)}
     assert {c["nq"] for c in A.ATTN_CASES if c["causal"]} == {77, 129, 200}
-    assert {(c["nq"], c["waves"]) for c in A.ATTN_CASES if c["attn2"] and c["variant"] == "late"} == {(1024, 8), (1000, 4), (2304, 0)}
+    assert {(c["nq"], c["waves"]) for c in A.ATTN_CASES if c["attn2"] and c["variant"] == "late"} == {(1024, 8), (1000, 4), (2304, 0), (320, 8)}
     assert {(c["D"], c["T"], c["R"]) for c in A.RELPOS_LONG_CASES if c["Tq"] == c["T"] and c["variant"] == "late"} == {
         (40, 250, 16), (64, 100, 2), (80, 125, 16), (160, 48, 16), (40, 33, 2), (160, 64, 63), (40, 1024, 16), (160, 40, 16)}
     assert {(c["D"], c["T"], c["Tq"], c["off"], c["R"]) for c in A.RELPOS_LONG_CASES if c["Tq"] != c["T"]} == {
-        (64, 250, 84, 166, 2), (40, 64, 20, 0, 16), (80, 100, 34, 33, 16)}
-    assert {c["T"] for c in A.RELPOS_SHORT_CASES} == {5, 8, 16, 24, 32}
+        (64, 250, 84, 166, 2), (40, 64, 20, 0, 16), (80, 100, 34, 33, 16)} | {(D, 40, 5, off, 16) for D in (40, 80, 160) for off in (0, 35)}
+    assert {c["T"] for c in A.RELPOS_SHORT_CASES} == {5, 8, 16, 17, 18, 24, 25, 32}
     # T-sharded slices on the VALU kernel: the start, the middle and the end of clips of 5, 8 and 16 frames
     shard = {(c["T"], c["off"], c["off"] + c["Tq"] == c["T"]) for c in A.RELPOS_SHORT_CASES if c["Tq"] < c["T"] and 0 in c["sels"]}
-    assert {(T, pos) for T in (5, 8, 16) for pos in ("start", "middle", "end")} == {
+    assert {(T, pos) for T in (5, 8, 16) for pos in ("start", "middle", "end")} | {(24, "start"), (24, "middle")} == {
         (T, "start" if off == 0 else "end" if end else "middle") for T, off, end in shard}
     for c in A.RELPOS_SHORT_CASES:                        # the selectors each case names apply to it
         if 1 in c["sels"]:

@@ -159,6 +159,22 @@ def test_c3_zeroscope_xl_forward_72x128(modelscope_full_fp16):
         assert ra < GATE_FWD_W16
 
 
+def test_zeroscope_native_40x72_7_frames_forward(modelscope_full_fp16):
+    """ZeroScope's native 576 x 320 (a latent of 40 x 72) at 7 frames — ragged at every level (20160, 5040, 1260 and 315 rows per sample): the
+    most used geometry outside the matrix of tests/test_record_paths_cpu.py, whose code paths tests/test_geometry_paths_cpu.py closes case by
+    case; this is the whole forward, against the reference's classes in fp32 on the DEPLOYED weights (make_golden_full.py w16 zs7), under the
+    gate of the configs[3] forward."""
+    net, _ = modelscope_full_fp16
+    gold = np.load(os.path.join(GOLD, "zeroscope_40x72_7f_w16.npz"))
+    frames = [int(f) for f in gold["frames"]]
+    noise, cond, _ = synth.synth_inputs(7, 320, 576)
+    eps = net(noise.to(DEV), torch.tensor([801], device=DEV), cond.to(DEV).half()).float().cpu()
+    r = rel_l2(eps[:, :, frames], torch.from_numpy(gold["unet_eps_frames"]))
+    print(f"ZeroScope native geometry, 7 frames @576x320 (latent 40x72) vs the reference on the DEPLOYED weights: rel-L2 {r:.3e}")
+    assert abs(float(eps.std()) - float(gold["eps_std"])) < 2e-3 * float(gold["eps_std"])
+    assert r < GATE_FWD_W16
+
+
 @pytest.mark.skipif(os.environ.get("T2V_TEST_FULL") != "1", reason="the 4-frame forward at the same geometry runs by default; T2V_TEST_FULL=1 adds the 12-frame one")
 def test_c3_zeroscope_xl_forward_12_frames(modelscope_full_fp16):
     """VERDICT r02 missing #3: the 9216-token spatial attention at batch 12 x 5 heads (the 4-frame golden covers the geometry,

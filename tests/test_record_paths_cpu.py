@@ -28,11 +28,48 @@ from test_plan_hazards_cpu import ROOT, _fixed_environment, _lower, extra_rows
 from tools import program_digest as PD
 
 
+_ADVERSARIAL = []
+
+
+def adversarial_side():
+    """(adversarial: key -> [case id], the ids of the `lowered` cases); the caller provides the FIXED environment.  Shared with
+    tests/test_geometry_paths_cpu.py and tools/geometry_paths.py: built once per process (nobody edits the result)."""
+    if _ADVERSARIAL:
+        return _ADVERSARIAL[0]
+    adv, new = collections.OrderedDict(), set()
+
+    def add(ops, cid, is_new=False):
+        for op in ops:
+            for k in RP.path_keys(op):
+                adv.setdefault(k, []).append(cid)
+        if is_new:
+            new.add(cid)
+
+    lowered = lambda c: c.get("family") == "lowered" or str(c["id"]).startswith("lowered-")
+    for mod, tag in ((G, "gemm"), (N, "norm"), (FF, "ff"), (FA, "fused-attention")):
+        for c in mod.CASES:
+            add(mod.build(c).P.ops, f"{tag}:{c['id']}", lowered(c))
+    for c in E.CASES:
+        if not c.get("wrap"):          # (the grid-stride cases are their own size class of one kernel each and cost seconds to build)
+            b = E.build(c)
+            add(b.ops if b.ops is not None else b.P.ops, f"elementwise:{c['id']}", lowered(c))
+    for c in A.ATTN_CASES:
+        for attn2 in ((True, False) if c["attn2"] else (False,)):
+            add(AR.build_attn(c, attn2).P.ops, f"attention:{c['id']}", lowered(c))
+    for c in A.RELPOS_LONG_CASES:
+        add(AR.build_relpos(c, None).P.ops, f"relpos:{c['id']}", lowered(c))
+    for c in A.RELPOS_SHORT_CASES:
+        for sel in c["sels"]:
+            add(AR.build_relpos(c, sel).P.ops, f"relpos:{c['id']}/i[17]={sel}", lowered(c))
+    _ADVERSARIAL.append((adv, new))
+    return adv, new
+
+
 @pytest.fixture(scope="module")
 def sides():
     """(lowered: key -> [(row label, op name)], one sample record per key, adversarial: key -> [case id], the ids of the `lowered` cases)."""
     mp = pytest.MonkeyPatch()
-    low, sample, adv, new = collections.OrderedDict(), {}, collections.OrderedDict(), set()
+    low, sample = collections.OrderedDict(), {}
     try:
         _fixed_environment(mp)
         for source in (PD.rows(ROOT), extra_rows()):
@@ -41,30 +78,7 @@ def sides():
                     for k in RP.path_keys(op):
                         low.setdefault(k, []).append((r.label, op.name))
                         sample.setdefault(k, op)
-
-        def add(ops, cid, is_new=False):
-            for op in ops:
-                for k in RP.path_keys(op):
-                    adv.setdefault(k, []).append(cid)
-            if is_new:
-                new.add(cid)
-
-        lowered = lambda c: c.get("family") == "lowered" or str(c["id"]).startswith("lowered-")
-        for mod, tag in ((G, "gemm"), (N, "norm"), (FF, "ff"), (FA, "fused-attention")):
-            for c in mod.CASES:
-                add(mod.build(c).P.ops, f"{tag}:{c['id']}", lowered(c))
-        for c in E.CASES:
-            if not c.get("wrap"):          # (the grid-stride cases are their own size class of one kernel each and cost seconds to build)
-                b = E.build(c)
-                add(b.ops if b.ops is not None else b.P.ops, f"elementwise:{c['id']}", lowered(c))
-        for c in A.ATTN_CASES:
-            for attn2 in ((True, False) if c["attn2"] else (False,)):
-                add(AR.build_attn(c, attn2).P.ops, f"attention:{c['id']}", lowered(c))
-        for c in A.RELPOS_LONG_CASES:
-            add(AR.build_relpos(c, None).P.ops, f"relpos:{c['id']}", lowered(c))
-        for c in A.RELPOS_SHORT_CASES:
-            for sel in c["sels"]:
-                add(AR.build_relpos(c, sel).P.ops, f"relpos:{c['id']}/i[17]={sel}", lowered(c))
+        adv, new = adversarial_side()
     finally:
         mp.undo()
     return low, sample, adv, new

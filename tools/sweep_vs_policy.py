@@ -1,5 +1,7 @@
 """Compare tools/gemm_sweep.py output files with Program.choose_tile: for every swept shape print the policy's (tile, split), its TF/s
-and the best measured configuration; flag shapes where the best is > 7 % ahead.  Usage: python tools/sweep_vs_policy.py <sweep files...>"""
+and the best measured configuration; flag shapes where the best is > 7 % ahead.  Usage: python tools/sweep_vs_policy.py <sweep files...>
+A change of the tile policy moves the code paths of the lowered programs (tests/record_paths.py): run tools/geometry_paths.py after it, which
+lowers every requestable geometry again and rewrites profiles/geometry_paths.txt and tests/geometry_witnesses.py."""
 import os
 import re
 import sys
