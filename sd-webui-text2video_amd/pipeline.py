@@ -27,6 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import packing as pk
+from .compiled import ProgramHost, _Compiled
+from .program import Program, Ref
 from .samplers import Txt2VideoSampler, available_samplers
 from .unet import UNetSD
 from .vae import AutoencoderKL
@@ -243,29 +246,27 @@ class TextToVideoSynthesis(object):
         """uint8 RGB frames [F, H, W, 3] (numpy array or device tensor) -> device uint8 [F, height, width, 3]: the resize of
         process_modelscope.py:116-120,174-178 (`Image.resize((width, height), Image.ANTIALIAS)` = Pillow's Lanczos filter) on the
         GPU, bit-exact with Pillow (T2V_OP_RESAMPLE: a horizontal and a vertical integer pass).  Programs are cached per geometry."""
-        from . import packing as pk
-        from .program import Program, Ref
-        from .unet import _Compiled
         x = self._as_u8_frames(frames, self.device)
         n, h0, w0, _ = x.shape
         if (h0, w0) == (height, width):
             return x
-        cache = self.__dict__.setdefault("_resize_programs", {})
-        key = (n, h0, w0, height, width)
-        ent = cache.get(key)
-        if ent is None or next(iter(ent[1].values())).device != x.device:
+
+        def build():
             prog, packer = Program(f"resize n{n} {h0}x{w0} -> {height}x{width}"), pk.WeightPacker()
             prog.begin()
             prog.resample("frames.resample", Ref("ext", L.EXT_X), Ref("ext", L.EXT_OUT), packer, n=n, src_hw=(h0, w0), dst_hw=(height, width))
             prog.finish()
-            ent = (_Compiled(prog, packer), packer.materialise({}, x.device))
-            cache[key] = ent
-            while len(cache) > self.max_programs:
-                del cache[next(k for k in cache if k != key)]
-        comp, packed = ent
-        comp.ensure_bound(packed, x.device)
+            return _Compiled(prog, packer)
+
+        host = self.__dict__.get("_resize_host")          # made on first use: pipelines are also put together without __init__
+        if host is None:
+            host = self._resize_host = ProgramHost(self.max_programs)
+            self._resize_programs = host._programs          # geometry -> _Compiled (the coefficient tables are the host's pack)
+        host.max_programs = self.max_programs          # (read on every call: the bound may be changed on the pipeline at any time)
+        comp = host._program((n, h0, w0, height, width), build)
+        host._prepare(comp, x.device)
         out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=x.device)
-        comp.bound.run({L.EXT_X: x.data_ptr(), L.EXT_OUT: out.data_ptr()}, torch.cuda.current_stream(x.device).cuda_stream)
+        host._launch(comp, x.device, {L.EXT_X: x.data_ptr(), L.EXT_OUT: out.data_ptr()})
         return out
 
     @torch.no_grad()

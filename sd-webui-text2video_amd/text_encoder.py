@@ -27,15 +27,15 @@ import math
 import os
 import re
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 from torch import nn
 
 from . import _lib as L
 from . import packing as pk
+from .compiled import ProgramHost, _Compiled
 from .program import Buf, Program, Ref
-from .unet import _Compiled
 
 # open_clip model configs of the text towers the reference names (open_clip/model_configs/*.json, text_cfg)
 OPEN_CLIP_TEXT = {
@@ -204,7 +204,7 @@ class _TextLowering:
 ACT_GELU, ACT_QUICK_GELU = 2, 3
 
 
-class ClipTextTower:
+class ClipTextTower(ProgramHost):
     """tokens int [B, L] (device) (+ multipliers fp32 [B, L]) -> z fp32 [B, L, width]: the transformer part of either embedder, run from the
     parameters of `holder` (an open_clip CLIP / `OpenClipTextModel`, or a transformers `CLIPTextModel` /
     `CLIPTextTransformer`).  `skip_last` = number of trailing blocks left out (`layer_idx` of the reference: 1 for
@@ -236,13 +236,12 @@ class ClipTextTower:
             raise L.T2VError(f"unsupported CLIP activation {act!r}")
         self.heads, self.act = heads, (ACT_GELU if act == "gelu" else ACT_QUICK_GELU)
         self.eps = float(getattr(cfg, "layer_norm_eps", eps))
-        self._programs: Dict[tuple, _Compiled] = {}
-        self._packed, self._packed_sig, self._packed_device = None, None, None
-        self._fingerprint = pk.ParamFingerprint()      # byte-level values of the parameters at the last pack (verify_weights)
+        # max_programs = None: unbounded — one small program per (batch, length[, emphasis]) a session asks for
+        self._init_programs(max_programs=None, fingerprint=True)
         self.debug_taps = False
 
-    def _signature(self):
-        return tuple((id(p), p._version, p.device.type, p.dtype) for p in self.holder.parameters())
+    def _param_module(self):
+        return self.holder
 
     def _compile(self, B, Lseq, emphasis=False) -> _Compiled:
         low = _TextLowering(self.names, B=B, Lseq=Lseq, width=self.width, heads=self.heads,
@@ -250,52 +249,23 @@ class ClipTextTower:
                             keep_taps=self.debug_taps, emphasis=emphasis)
         return _Compiled(low.build(), low.packer)
 
-    def verify_weights(self, device=None) -> list:
-        """The parameters whose BYTES differ from what the packed images were made of (an edit through `.data` moves neither identity nor
-        version: packing.ParamFingerprint); any such edit drops the pack, and the encode that follows packs again.  Nothing before the first
-        pack, nothing for CPU parameters beside a GPU pack."""
-        device = torch.device(device) if device is not None else self._packed_device
-        fp = self._fingerprint
-        if self._packed is None or fp.recorded is None or device != self._packed_device:
-            return []
-        fresh = fp.compute(list(self.holder.named_parameters()), device)
-        if fresh is None:
-            return []
-        changed = [n for n, v in fresh.items() if fp.recorded.get(n) != v]
-        if changed:
-            self._packed, self._packed_sig, fp.recorded = None, None, None
-        return changed
-
-    def refresh_weights(self, comp: _Compiled, device):
-        sig = self._signature()
-        if self._packed is not None and sig == self._packed_sig and device == self._packed_device:
-            return
-        self._packed = comp.packer.materialise(self.holder.state_dict(), device)
-        self._packed_sig, self._packed_device = sig, device
-        self._fingerprint.recorded = self._fingerprint.compute(list(self.holder.named_parameters()), device)
-        for c in self._programs.values():
-            c.bound = None
-
     def __call__(self, tokens: torch.Tensor, multipliers: Optional[torch.Tensor] = None) -> torch.Tensor:
         if not tokens.is_cuda:
             raise L.T2VError("ClipTextTower needs device tensors on an AMD GPU (no CPU fallback)")
         assert tokens.ndim == 2 and tokens.shape[1] <= self.max_len
         B, Lseq = tokens.shape
         ids = tokens.to(torch.int32).contiguous()
-        key = (B, Lseq) if multipliers is None else (B, Lseq, True)
-        comp = self._programs.get(key)
-        if comp is None:
-            comp = self._programs[key] = self._compile(B, Lseq, emphasis=multipliers is not None)
-        self.verify_weights(tokens.device)
-        self.refresh_weights(comp, tokens.device)
-        comp.ensure_bound(self._packed, tokens.device)
+        comp = self._program((B, Lseq) if multipliers is None else (B, Lseq, True),
+                             lambda: self._compile(B, Lseq, emphasis=multipliers is not None))
+        self.verify_weights(tokens.device)          # an edit through `.data` drops the pack; `_prepare` packs again
+        self._prepare(comp, tokens.device)
         z = torch.empty((B, Lseq, self.width), device=tokens.device, dtype=torch.float32)
         ext = {L.EXT_X: ids.data_ptr(), L.EXT_OUT: z.data_ptr()}
         if multipliers is not None:
             assert multipliers.shape == tokens.shape and multipliers.device == tokens.device
             mult = multipliers.to(torch.float32).contiguous()
             ext[EXT_MULT] = mult.data_ptr()
-        comp.bound.run(ext, torch.cuda.current_stream(tokens.device).cuda_stream)
+        self._launch(comp, tokens.device, ext)
         return z
 
 

@@ -31,8 +31,9 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import packing as pk
+from .compiled import ProgramHost, _Compiled, _dt  # noqa: F401  (re-exported: tests and tools import them from here)
 from .lowering import _UNetLowering, canonical_context_lengths
-from .program import COLLECTIVE_KINDS, BoundProgram, Buf, Program, Ref
+from .program import BoundProgram, Buf, Ref
 
 
 # ------------------------------------------------------------------------------------------
@@ -157,7 +158,7 @@ def _conv_holder(attr, cin, cout, **kw):
     return m
 
 
-class UNetSD(nn.Module):
+class UNetSD(nn.Module, ProgramHost):
     """See module docstring.  Extra keyword (not in the reference): `init_weights=False` skips
     the (slow, 1.4 G parameter) default initialisation when a state dict is loaded right after."""
 
@@ -211,14 +212,10 @@ class UNetSD(nn.Module):
 
     def _init_runtime(self):
         """Runtime state (not part of the state dict); shared with videocrafter.UNetModel."""
-        self._programs: Dict[tuple, "_Compiled"] = {}
-        self._packed: Optional[Dict[str, torch.Tensor]] = None
-        self._packed_sig = None
-        self._packed_device = None
-        self._packed_deps = None
+        # compiled geometries kept: each owns a device arena (0.4 GiB per 24-frame sample, GiBs for long clips)
+        self._init_programs(max_programs=4, fingerprint=True)
         self._param_slots = None
         self.last_repack = None       # images rewritten by the last refresh_weights (-1 = full pack)
-        self._fingerprint = pk.ParamFingerprint()   # byte-level values of the parameters at the last pack (verify_weights)
         self.debug_taps = False
         # Storage type of tensors that are consumed ONLY by a GroupNorm (ResBlock's first conv output
         # and the three inner temporal-conv outputs): "f16" halves their HBM traffic (what the
@@ -347,48 +344,18 @@ class UNetSD(nn.Module):
         reg("posterior_mean_coef2", t32((1.0 - ac_prev) * np.sqrt(alphas) / (1.0 - ac)))
 
     # ---- weights --------------------------------------------------------------------------
-    def _param_signature(self):
-        """name -> (identity, version, device, dtype, shape) of every parameter.  Walks the cached per-module
-        `_parameters` dicts (the module tree is fixed; re-assigned or added Parameters are still seen) instead of
-        `named_parameters()`: this runs before every forward when `auto_refresh` is on."""
+    def _named_params(self):
+        """Walks the cached per-module `_parameters` dicts (the module tree is fixed; re-assigned or added Parameters are still seen)
+        instead of `named_parameters()`: the signature is taken before every forward when `auto_refresh` is on."""
         if self._param_slots is None:
             self._param_slots = [(n + "." if n else "", m._parameters) for n, m in self.named_modules() if m._parameters]
-        sig = {}
-        for prefix, pd in self._param_slots:
-            for k, p in pd.items():
-                if p is not None:
-                    sig[prefix + k] = (id(p), p._version, p.device.type, p.dtype, p.shape)
-        return sig
-
-    def invalidate(self):
-        """Drop the packed weight images (call after mutating parameters in place)."""
-        self._packed = None
-        self._packed_sig = None
-
-    def _named_params(self):
-        if self._param_slots is None:
-            self._param_signature()
         return [(prefix + k, p) for prefix, pd in self._param_slots for k, p in pd.items() if p is not None]
 
-    def verify_weights(self, device=None) -> list:
-        """Look at the BYTES of the parameters: fingerprint every tensor (one launch, packing.ParamFingerprint), compare with the values
-        recorded when the images were last packed, and re-pack the images that read a changed tensor through the partial path of
-        `refresh_weights` (same device addresses, cached text K/V dropped; `last_repack` reports it).  -> the changed names.
-        This is what sees an edit through `.data` (`w.data += d`, `w.data = saved.clone()`: the reference's VideoCrafter LoRA loaders),
-        which moves neither the parameter's identity nor its version.  The samplers call it once per sampling call; code that edits
-        weights in place between bare forwards calls it itself.  Does nothing before the first pack, and nothing for parameters that
-        live on the CPU while the pack is on a GPU (they are not fingerprinted: `invalidate()` is the call for that arrangement)."""
-        device = torch.device(device) if device is not None else self._packed_device
-        fp = getattr(self, "_fingerprint", None)
-        if fp is None or self._packed is None or device is None or device != self._packed_device or fp.recorded is None:
-            return []
-        fresh = fp.compute(self._named_params(), device)
-        if fresh is None:
-            return []
-        changed = [n for n, v in fresh.items() if fp.recorded.get(n) != v]
-        if changed:
-            self._refresh_weights(device, also_changed=changed, fingerprints=fresh)
-        return changed
+    def _bytes_changed(self, device, changed, fingerprints):
+        """`verify_weights` found edited bytes: instead of dropping the pack, re-pack the images that read a changed tensor through
+        the partial path of `refresh_weights` (same device addresses, cached text K/V dropped; `last_repack` reports it).  The samplers
+        call `verify_weights` once per sampling call; code that edits weights in place between bare forwards calls it itself."""
+        self._refresh_weights(device, also_changed=changed, fingerprints=fingerprints)
 
     def refresh_weights(self, device=None):
         self._refresh_weights(device)
@@ -439,12 +406,6 @@ class UNetSD(nn.Module):
             c.ctx_token = None
         self._record_fingerprints(device, fingerprints)
 
-    def _record_fingerprints(self, device, values=None):
-        """End of a full or partial pack: the parameters' fingerprints as of now (None when they are not fingerprinted)."""
-        fp = getattr(self, "_fingerprint", None)
-        if fp is not None:
-            fp.recorded = values if values is not None else fp.compute(self._named_params(), device)
-
     def _union_packer(self) -> pk.WeightPacker:
         if not self._programs:
             self._get_compiled_any()
@@ -453,18 +414,6 @@ class UNetSD(nn.Module):
             for name, dtype, fn in comp.packer.recipes:
                 packer.add(name, dtype, fn)
         return packer
-
-    def _pack_missing(self, comp: "_Compiled", device):
-        """Images a newly compiled program needs that no earlier program declared: packed and merged into the live
-        set (existing device tensors — and the programs bound to them — are untouched)."""
-        missing = [(n, d, f) for n, d, f in comp.packer.recipes if n not in self._packed]
-        if not missing:
-            return
-        tmp = pk.WeightPacker()
-        for n, d, f in missing:
-            tmp.add(n, d, f)
-        self._packed.update(tmp.materialise(self.state_dict(), device))
-        self._packed_deps.update(tmp.deps)
 
     def _get_compiled_any(self):
         if self._programs:
@@ -531,14 +480,14 @@ class UNetSD(nn.Module):
             single = bool((tf == tf.reshape(-1)[0]).all())
         self._share_now = bool(getattr(self, "share_cfg_prefix", False)) and single
         key = self._program_key(B, F, H, W, Lctx, x.dtype, y.dtype, out_dtype, shard, Bx) + ((("adapter", adapter[0]),) if adapter else ())
-        comp = self._programs.get(key)
-        if comp is not None and comp.prog.gn_epilogue and L.exchange_disabled():
-            comp = None        # an asynchronous fault was reported: lower again, without the norms fused into GEMM epilogues (_lib.exchange_disabled)
-        if comp is None:
-            comp = self._compile(B, F, H, W, Lctx, _dt(x.dtype), _dt(out_dtype), _dt(y.dtype), shard=shard,
-                                 x_batch=Bx if Bx != B else 0, **({"adapter": adapter[0]} if adapter else {}))
-            self._programs[key] = comp
-            self._evict_programs(keep=key)
+        build = lambda: self._compile(B, F, H, W, Lctx, _dt(x.dtype), _dt(out_dtype), _dt(y.dtype), shard=shard,
+                                      x_batch=Bx if Bx != B else 0, **({"adapter": adapter[0]} if adapter else {}))
+        held = self._programs.get(key)
+        if held is not None and held.prog.gn_epilogue and L.exchange_disabled():
+            # an asynchronous fault was reported: lower again, without the norms fused into GEMM epilogues (_lib.exchange_disabled).
+            # Assigned in place, not through `_program`: the key keeps its position in the eviction order and nothing is evicted
+            self._programs[key] = build()
+        comp = self._program(key, build)
         if self._packed is None or self._packed_device != x.device or self.auto_refresh:
             self.refresh_weights(x.device)
         self._pack_missing(comp, x.device)
@@ -635,15 +584,6 @@ class UNetSD(nn.Module):
             return packed, lens, None
         return packed, None, lens
 
-    max_programs = 4      # compiled geometries kept (each owns a device arena: 0.4 GiB per 24-frame sample, GiBs for long clips)
-
-    def _evict_programs(self, keep):
-        """Least-recently-compiled eviction: a webui session that varies frames / resolution / batch_count would otherwise
-        accumulate one arena per geometry (the reference frees its activations after every call)."""
-        while len(self._programs) > self.max_programs:
-            victim = next(k for k in self._programs if k != keep)
-            del self._programs[victim]
-
     def forward_timed(self, x, t, y):
         """Like forward, but returns (eps, per-op milliseconds) using HIP events around every op
         on the launch stream (bench.py roofline measurement)."""
@@ -663,44 +603,6 @@ class UNetSD(nn.Module):
         low = _Lowering(self, B, F, H, W, Lctx, x_dt, out_dt, ctx_dt, keep_taps=self.debug_taps, shard=shard, x_batch=x_batch)
         prog = low.build()
         return _Compiled(prog, low.packer)
-
-
-def _dt(dtype) -> str:
-    return "f16" if dtype == torch.float16 else "f32"
-
-
-class _Compiled:
-    def __init__(self, prog: Program, packer: pk.WeightPacker):
-        self.prog = prog
-        self.packer = packer
-        self.bound: Optional[BoundProgram] = None
-        self.arena: Optional[torch.Tensor] = None
-        self.ctx_token = None          # context token of the last run (step-invariant prologue reuse)
-        self.ctx_bound = None
-
-    def ensure_bound(self, packed: Dict[str, torch.Tensor], device, t_shard=None):
-        """Bind the program to a device arena and the packed weights.  A program with collective ops (T-sharded
-        forward) is bound together with the T group's communicator: its exchanges then run inside the library (RCCL on
-        the launch stream) — or, with T2V_COLLECTIVES=host / a non-GPU group, through parallel.ShardedExecutor."""
-        if self.bound is not None and self.arena is not None and self.arena.device == device:
-            return
-        # zero-filled once at bind time: padding lanes that an op reads before any op wrote them (they only ever meet
-        # zero weights) must not hold NaN bit patterns of recycled allocator blocks
-        self.arena = torch.zeros(self.prog.arena.high + 256, dtype=torch.uint8, device=device)
-        wptr = {k: v.data_ptr() for k, v in packed.items()}
-        st = torch.cuda.current_stream(device).cuda_stream       # the bind-time reset of the sync words is ordered with the first run
-        if any(op.kind in COLLECTIVE_KINDS for op in self.prog.ops):
-            if t_shard is None:
-                raise L.T2VError("a T-sharded program needs the T group (UNetSD.t_shard)")
-            comm = t_shard.communicator(device)
-            if comm is not None:
-                self.bound = BoundProgram(self.prog, self.arena.data_ptr(), wptr, comm=comm, stream=st)
-            else:
-                from .parallel import ShardedExecutor
-                self.bound = ShardedExecutor(self.prog, self.arena, t_shard,
-                                             lambda ops: BoundProgram(self.prog, self.arena.data_ptr(), wptr, ops=ops))
-        else:
-            self.bound = BoundProgram(self.prog, self.arena.data_ptr(), wptr, stream=st)
 
 
 # ------------------------------------------------------------------------------------------

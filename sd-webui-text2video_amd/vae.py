@@ -17,8 +17,6 @@ Downsample pads (0,1,0,1) and convolves with stride 2 — and returns the Diagon
 """
 from __future__ import annotations
 
-from typing import Dict
-
 import math
 import os
 
@@ -29,7 +27,7 @@ from . import _lib as L
 from . import packing as pk
 from .lowering import _Declarations
 from .program import Buf, Program, Ref
-from .unet import _Compiled, _dt
+from .compiled import ProgramHost, _Compiled, _dt
 
 
 def _resnet_params(cin, cout):
@@ -136,7 +134,7 @@ class DiagonalGaussianDistribution(object):
         return self.mean
 
 
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(nn.Module, ProgramHost):
     def __init__(self, ddconfig, embed_dim, ckpt_path=None, image_key="image", colorize_nlabels=None,
                  monitor=None, ema_decay=None, learn_logvar=False, init_weights=True):
         super().__init__()
@@ -153,10 +151,7 @@ class AutoencoderKL(nn.Module):
             self.post_quant_conv = nn.Conv2d(embed_dim, ddconfig["z_channels"], 1)
         if not init_weights:
             self.to_empty(device="cpu")
-        self._programs: Dict[tuple, _Compiled] = {}
-        self._packed = None
-        self._packed_sig = None
-        self._packed_device = None
+        self._init_programs(max_programs=4)          # each program owns a device arena
         self.debug_taps = False
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path)
@@ -177,19 +172,9 @@ class AutoencoderKL(nn.Module):
         x = x.contiguous()
         if x.dtype not in (torch.float16, torch.float32):
             x = x.float()
-        key = ("enc", n, h, w, _dt(x.dtype))
-        comp = self._programs.get(key)
-        if comp is None:
-            low = _VaeLowering(self, n, h, w, _dt(x.dtype), "f32", self.debug_taps)
-            comp = _Compiled(low.build_encoder(), low.packer)
-            self._programs[key] = comp
-        self._refresh(comp, x.device)
-        comp.ensure_bound(self._packed, x.device)
-        zc2 = 2 * self.embed_dim
-        moments = torch.empty((n, zc2, h >> nlev, w >> nlev), device=x.device, dtype=torch.float32)
-        comp.bound.run({L.EXT_X: x.data_ptr(), L.EXT_OUT: moments.data_ptr()}, torch.cuda.current_stream(x.device).cuda_stream)
-        p0 = next(self.parameters())
-        return DiagonalGaussianDistribution(moments.to(torch.float16 if p0.dtype == torch.float16 else torch.float32))
+        comp = self._program(("enc", n, h, w, _dt(x.dtype)),
+                             lambda: self._lower(n, h, w, _dt(x.dtype), "f32", lambda low: low.build_encoder()))
+        return self._posterior(comp, x, n, h >> nlev, w >> nlev)
 
     def encode_uint8(self, frames, height: int, width: int):
         """frames uint8 [n, H0, W0, 3] (RGB, any size, device tensor) -> the posterior of the frames resized to (height, width) with
@@ -203,40 +188,20 @@ class AutoencoderKL(nn.Module):
         nlev = len(self.ddconfig["ch_mult"]) - 1
         assert height % (1 << nlev) == 0 and width % (1 << nlev) == 0
         frames = frames.contiguous()
-        key = ("enc_u8", n, h0, w0, height, width)
-        comp = self._programs.get(key)
-        if comp is None:
-            low = _VaeLowering(self, n, height, width, "f16", "f32", self.debug_taps)
-            comp = _Compiled(low.build_encoder(u8_src=(h0, w0)), low.packer)
-            self._programs[key] = comp
-            while len(self._programs) > self.max_programs:          # each program owns a device arena
-                del self._programs[next(k for k in self._programs if k != key)]
-        self._refresh(comp, frames.device)
-        comp.ensure_bound(self._packed, frames.device)
-        moments = torch.empty((n, 2 * self.embed_dim, height >> nlev, width >> nlev), device=frames.device, dtype=torch.float32)
-        comp.bound.run({L.EXT_X: frames.data_ptr(), L.EXT_OUT: moments.data_ptr()}, torch.cuda.current_stream(frames.device).cuda_stream)
+        comp = self._program(("enc_u8", n, h0, w0, height, width),
+                             lambda: self._lower(n, height, width, "f16", "f32", lambda low: low.build_encoder(u8_src=(h0, w0))))
+        return self._posterior(comp, frames, n, height >> nlev, width >> nlev)
+
+    def _lower(self, n, h, w, in_dt, out_dt, build) -> _Compiled:
+        low = _VaeLowering(self, n, h, w, in_dt, out_dt, self.debug_taps)
+        return _Compiled(build(low), low.packer)
+
+    def _posterior(self, comp, x, n, h, w):
+        self._prepare(comp, x.device)
+        moments = torch.empty((n, 2 * self.embed_dim, h, w), device=x.device, dtype=torch.float32)
+        self._launch(comp, x.device, {L.EXT_X: x.data_ptr(), L.EXT_OUT: moments.data_ptr()})
         p0 = next(self.parameters())
         return DiagonalGaussianDistribution(moments.to(torch.float16 if p0.dtype == torch.float16 else torch.float32))
-
-    # ---- weights ------------------------------------------------------------------------------
-    def _param_signature(self):
-        return tuple((id(p), p._version, p.device.type, p.dtype) for p in self.parameters())
-
-    def invalidate(self):
-        self._packed, self._packed_sig = None, None
-
-    def _refresh(self, comp, device):
-        sig = self._param_signature()
-        have = self._packed is not None and all(name in self._packed for name, _, _ in comp.packer.recipes)
-        if have and sig == self._packed_sig and device == self._packed_device:
-            return
-        packed = comp.packer.materialise(self.state_dict(), device)
-        if self._packed is not None and sig == self._packed_sig and device == self._packed_device:
-            packed = {**self._packed, **packed}          # decoder and encoder programs pack disjoint weight sets
-        self._packed = packed
-        self._packed_sig, self._packed_device = sig, device
-        for c in self._programs.values():
-            c.bound = None
 
     # ---- decode -------------------------------------------------------------------------------
     def decode(self, z):
@@ -271,16 +236,9 @@ class AutoencoderKL(nn.Module):
             z = z.float()
         p0 = next(self.parameters())
         out_dtype = torch.float16 if p0.dtype == torch.float16 else torch.float32
-        key = (n, h, w, _dt(z.dtype), _dt(out_dtype), u8)
-        comp = self._programs.get(key)
-        if comp is None:
-            low = _VaeLowering(self, n, h, w, _dt(z.dtype), _dt(out_dtype), self.debug_taps)
-            comp = _Compiled(low.build(u8), low.packer)
-            self._programs[key] = comp
-            while len(self._programs) > self.max_programs:          # each program owns a device arena
-                del self._programs[next(k for k in self._programs if k != key)]
-        self._refresh(comp, z.device)
-        comp.ensure_bound(self._packed, z.device)
+        comp = self._program((n, h, w, _dt(z.dtype), _dt(out_dtype), u8),
+                             lambda: self._lower(n, h, w, _dt(z.dtype), _dt(out_dtype), lambda low: low.build(u8)))
+        self._prepare(comp, z.device)
         if u8 is None:
             out = torch.empty((n, self.ddconfig["out_ch"], 8 * h, 8 * w), device=z.device, dtype=out_dtype)
         elif len(u8) == 3:           # torch_to_np form: one [f, 8h, 8w, 3] block per video
@@ -293,11 +251,8 @@ class AutoencoderKL(nn.Module):
                 out = out.view(shape)
         else:
             out = torch.empty((n // u8[0], 8 * h, u8[0] * 8 * w, self.ddconfig["out_ch"]), device=z.device, dtype=torch.uint8)
-        comp.bound.run({L.EXT_X: z.data_ptr(), L.EXT_OUT: out.data_ptr()},
-                       torch.cuda.current_stream(z.device).cuda_stream)
+        self._launch(comp, z.device, {L.EXT_X: z.data_ptr(), L.EXT_OUT: out.data_ptr()})
         return out
-
-    max_programs = 4
 
     def forward(self, input, sample_posterior=True):
         raise NotImplementedError("only decode() is on the hot path")

@@ -30,7 +30,8 @@ from . import _lib as L
 from . import packing as pk
 from .program import Buf, Program, Ref
 from .lowering import _UNetLowering
-from .unet import UNetSD, _Compiled, _attn_params
+from .compiled import ProgramHost, _Compiled, _dt
+from .unet import UNetSD, _attn_params
 
 
 # ------------------------------------------------------------------------------------------
@@ -496,7 +497,8 @@ def _pad64(c: int) -> int:
     return (c + 63) // 64 * 64
 
 
-_BICUBIC_PROGRAMS: dict = {}          # (planes, H, W, size, dtype, device) -> (_Compiled, packed tables); at most 4 kept
+_BICUBIC = ProgramHost(max_programs=4)          # the tap tables are its pack
+_BICUBIC_PROGRAMS = _BICUBIC._programs          # (planes, H, W, size, dtype) -> _Compiled
 
 
 def _bicubic_compile(planes: int, src_hw, dst_hw, x_dt: str) -> _Compiled:
@@ -526,17 +528,10 @@ def bicubic_resize(x, size):
     if (H, W) == size:
         return x.float()
     x = x.contiguous()
-    key = (n * c, H, W, size, x.dtype, x.device)
-    ent = _BICUBIC_PROGRAMS.get(key)
-    if ent is None:
-        comp = _bicubic_compile(n * c, (H, W), size, "f16" if x.dtype == torch.float16 else "f32")
-        ent = _BICUBIC_PROGRAMS[key] = (comp, comp.packer.materialise({}, x.device))
-        while len(_BICUBIC_PROGRAMS) > 4:
-            del _BICUBIC_PROGRAMS[next(k for k in _BICUBIC_PROGRAMS if k != key)]
-    comp, packed = ent
-    comp.ensure_bound(packed, x.device)
+    comp = _BICUBIC._program((n * c, H, W, size, x.dtype), lambda: _bicubic_compile(n * c, (H, W), size, _dt(x.dtype)))
+    _BICUBIC._prepare(comp, x.device)
     out = torch.empty((n, c) + size, dtype=torch.float32, device=x.device)
-    comp.bound.run({L.EXT_X: x.data_ptr(), L.EXT_OUT: out.data_ptr()}, torch.cuda.current_stream(x.device).cuda_stream)
+    _BICUBIC._launch(comp, x.device, {L.EXT_X: x.data_ptr(), L.EXT_OUT: out.data_ptr()})
     return out
 
 
@@ -555,7 +550,7 @@ def _adapter_block_params(in_c, out_c, down, ksize, sk, use_conv):
     return m
 
 
-class Adapter(nn.Module):
+class Adapter(nn.Module, ProgramHost):
     """Drop-in for lvdm.models.modules.adapter.Adapter: same constructor, same state-dict keys (`load_state_dict(strict=True)` takes the
     reference's), `forward(x[n, 1, H, W]) -> [features [n, c_i, H / 2^(3+i), W / 2^(3+i)]]` — computed by ONE program of HIP kernels
     over all n frames (PixelUnshuffle(8) front end, convolutions as implicit GEMMs with ReLU / the skip as fused epilogues).  The
@@ -586,8 +581,7 @@ class Adapter(nn.Module):
             self.conv_in = nn.Conv2d(cin, channels[0], 3, 1, 1)
         if not init_weights:
             self.to_empty(device="cpu")
-        self._programs: dict = {}
-        self._packed, self._packed_sig, self._packed_device = None, None, None
+        self._init_programs(max_programs=4)          # each program owns a device arena
 
     def feature_shapes(self, H: int, W: int) -> List[tuple]:
         """(channels, h, w) of every feature for H x W depth frames."""
@@ -601,9 +595,6 @@ class Adapter(nn.Module):
     def _compile(self, n, H, W, x_dt="f32", normalise=False, front_only=False, src_hw=None) -> _Compiled:
         low = _AdapterLowering(self, n, H, W, x_dt, normalise, front_only, src_hw)
         return _Compiled(low.build(), low.packer)
-
-    def _signature(self):
-        return tuple((k, id(p), p._version, p.device.type, p.dtype) for k, p in self.named_parameters())
 
     def _run(self, x, normalise: bool, front_only: bool = False, size=None):
         """size (front end only): the frames arrive at another size and are first resized to `size` with the bicubic pass, in the same program."""
@@ -626,31 +617,15 @@ class Adapter(nn.Module):
         if not front_only and min(min(h, w) for _, h, w in shapes) < 1:
             raise ValueError(f"Adapter: {H} x {W} frames are too small for {len(self.channels)} levels")
         key = (n, H, W, x.dtype, bool(normalise), front_only) + ((src_hw,) if src_hw is not None else ())
-        comp = self._programs.get(key)
-        if comp is None:
-            while len(self._programs) >= 4:                    # (each program owns a device arena)
-                del self._programs[next(iter(self._programs))]
-            comp = self._programs[key] = self._compile(n, H, W, "f16" if x.dtype == torch.float16 else "f32", normalise, front_only, src_hw)
-        sig = self._signature()
-        if self._packed is None or self._packed_sig != sig or self._packed_device != x.device:
-            self._packed, self._packed_sig, self._packed_device = {}, sig, x.device
-            for c in self._programs.values():
-                c.bound = None
-        missing = pk.WeightPacker()
-        for name, dtype, fn in comp.packer.recipes:
-            if name not in self._packed:
-                missing.add(name, dtype, fn)
-        if missing.recipes:
-            self._packed.update(missing.materialise(self.state_dict(), x.device))
-            comp.bound = None
-        comp.ensure_bound(self._packed, x.device)
+        comp = self._program(key, lambda: self._compile(n, H, W, _dt(x.dtype), normalise, front_only, src_hw))
+        self._prepare(comp, x.device)
         ext = {L.EXT_X: x.data_ptr()}
         if front_only:
             outs = [torch.empty(n * (H // 8) * (W // 8), 64, device=x.device, dtype=torch.float16)]
         else:
             outs = [torch.empty(n * h * w, _pad64(c), device=x.device, dtype=torch.float32) for c, h, w in shapes]
         ext.update({L.EXT_ADAPTER + k: o.data_ptr() for k, o in enumerate(outs)})
-        comp.bound.run(ext, torch.cuda.current_stream(x.device).cuda_stream)
+        self._launch(comp, x.device, ext)
         self.last_program = comp.prog
         return outs, shapes
 
