@@ -9,11 +9,13 @@
 //   ddim_step     DDIM_Gaussian update incl. half-channel classifier-free guidance
 //                 (samplers/ddim/gaussian_sampler.py:125-136, 103-108, 199-211, 269-283); a compile-time variant adds the
 //                 known-region blend of a masked LVDM step (lvdm/samplers/ddim.py:188-195) to the same launch
-//   ddim_restrict / ddim_measure   the DDIM_Gaussian step with its x0 clamped or thresholded by a per-video quantile of |x0|
-//   x0_threshold  UniPC's thresholded data prediction (uni_pc/uni_pc.py:351-364): ddim_measure over that x0, then clamp(x0, -s, s) / s
-//                 (restrict_range_x0, gaussian_sampler.py:110-120) and / or the classifier-guidance term (get_eps, :199-211); the measure
-//                 pass is torch.quantile on fp32, exactly, by a radix select in one workgroup per video
-//   ddim_invert   the DDIM inversion step of DDIMSampler.encode (samplers/ddim/sampler.py:242-254), four elements per thread
+//   the strict forms of a DDIM_STEP record (t2v_ddim_classify names a record's form once, for validation, output slots and launch); they
+//   share one view of the record (DdimView), one guidance combine (ddim_combine) and one x0 (ddim_x0_of), every operation rounded by itself:
+//     ddim_restrict   the DDIM_Gaussian step with its x0 clamped or thresholded by a per-video quantile of |x0| (restrict_range_x0,
+//                     gaussian_sampler.py:110-120) and / or the classifier-guidance term (get_eps, :199-211); its x0 form 1 is the apply
+//                     pass of UniPC's thresholded data prediction (uni_pc/uni_pc.py:351-364), clamp(x0, -s, s) / s
+//     ddim_measure    the quantile of |x0| per video, of either x0 form: torch.quantile on fp32, exactly, by a radix select in one workgroup
+//     ddim_invert     the DDIM inversion step of DDIMSampler.encode (samplers/ddim/sampler.py:242-254), four elements per thread
 //   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
 //                 (process_modelscope.py:116-120, 174-178); the last pass can write the VAE encoder's tokens
 //   bicubic       torch's F.interpolate(mode="bicubic", align_corners=False) of planar float images, both axes in one launch: the resizes
@@ -184,61 +186,48 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const DdimParams p, cons
   }
 }
 
-// ---- mode 0 with a restriction of x0 (i[8]) and / or the classifier-guidance term (i[9]): gaussian_sampler.py:110-120, 199-211 ----------
+// ---- the strict forms of a record: restrict, threshold, measure, invert (t2v_ddim_classify) ---------------------------------------------
 // Kernels of their own, so that the plain step above stays the code it was.  Everything below rounds every operation separately
 // (no contraction), like the reference's tensor arithmetic: the x0 that the measure pass ranks IS the x0 that the apply pass thresholds.
-struct DdimRestrict {
-  const float* table;   // i[8] = 2: [samples, 4] fp32, s in column 0 (p[7])
-  const float* grad;    // i[9] = 1: condition_fn's result, fp32, dense like x (p[8])
-  float bound;          // i[8] = 1: clamp bound (f[6])
-  float sqrt_1mat;      // i[9] = 1: sqrt(1 - a_t) (f[7])
+
+// A record on the device: x_t [S,Cs,inner] fp32 with C = S*Cs rows, the eps pair [2,S,Cs,inner] (ec conditional, eu unconditional), out fp32
+template <typename TE>
+struct DdimView {
+  const float* xt; const TE* ec; const TE* eu; float* out;
+  long total, per_sample, guided_n;            // elements in all, per sample, and in a sample's first i[2] (guided) channels
+  __device__ explicit DdimView(const DdimParams& p)
+      : xt(reinterpret_cast<const float*>(p.xt)), ec(reinterpret_cast<const TE*>(p.eps)), eu(ec + (size_t)p.C * p.inner),
+        out(reinterpret_cast<float*>(p.out)), total((long)p.C * p.inner), per_sample((long)p.cps * p.inner), guided_n((long)p.guided * p.inner) {}
+  __device__ long sample(long idx) const { return idx / per_sample; }
+  __device__ bool guided(long within) const { return within < guided_n; }      // within: the element's index inside its sample
 };
 
-// x0 of a mode-0 step from x_t and the eps pair, guidance combine included (guided: element idx lies in one of the sample's first
-// i[2] channels); *ax_out = f0 * x
-template <typename TE>
-__device__ __forceinline__ float ddim_x0_of(const DdimParams& p, const float* xt, const TE* ec, const TE* eu, long idx, bool guided, float* ax_out) {
+// The guidance combine e = e_u + g (e_c - e_u) of a guided element: the difference, the product, the sum
+__device__ __forceinline__ float ddim_combine(float gscale, float e_c, float e_u) {
 #pragma clang fp contract(off)
-  const float x = xt[idx];
-  const float y = (float)ec[idx];
-  float o = y;
-  if (guided) {
-    const float u = (float)eu[idx];
-    const float d = p.gscale * (y - u);
-    o = u + d;
-  }
-  const float ax = p.a_recip * x;
-  const float bo = p.a_recipm1 * o;
-  *ax_out = ax;
-  return ax - bo;
+  const float diff = e_c - e_u;
+  const float d = gscale * diff;
+  return e_u + d;
 }
 
-// x0 of a mode-2 record, the thresholded data prediction of UniPC (uni_pc/uni_pc.py:351-364 behind model_wrapper's guidance combine,
-// :304-307): e = e_u + g (e_c - e_u) when guided, x0 = (x - f0 * e) / f1 with f0 = sigma_t, f1 = alpha_t
-template <typename TE>
-__device__ __forceinline__ float unipc_x0_of(const DdimParams& p, const float* xt, const TE* ec, const TE* eu, long idx, bool guided) {
+// FORM: which record's x0 the measure pass ranks and the apply pass thresholds.  0 the DDIM_Gaussian step (mode 0): x0 = f0 x - f1 e,
+// *ax_out = f0 x.  1 UniPC's data prediction (mode 2; uni_pc/uni_pc.py:351-364 behind model_wrapper's guidance combine, :304-307):
+// x0 = (x - f0 e) / f1 with f0 = sigma_t, f1 = alpha_t.  The unconditional eps is read only where guided.
+template <int FORM, typename TE>
+__device__ __forceinline__ float ddim_x0_of(const DdimParams& p, const DdimView<TE>& v, long idx, bool guided, float* ax_out) {
 #pragma clang fp contract(off)
-  const float x = xt[idx];
-  const float y = (float)ec[idx];
-  float e = y;
-  if (guided) {
-    const float u = (float)eu[idx];
-    const float d = p.gscale * (y - u);
-    e = u + d;
-  }
-  const float se = p.a_recip * e;
-  const float num = x - se;
-  return num / p.a_recipm1;
-}
-
-// FORM: which record's x0 the measure pass ranks and the apply pass thresholds — 0 the DDIM_Gaussian step (mode 0), 1 UniPC's data prediction (mode 2)
-template <typename TE, int FORM>
-__device__ __forceinline__ float x0_form(const DdimParams& p, const float* xt, const TE* ec, const TE* eu, long idx, bool guided) {
+  const float x = v.xt[idx];
+  float e = (float)v.ec[idx];
+  if (guided) e = ddim_combine(p.gscale, e, (float)v.eu[idx]);
   if constexpr (FORM == 0) {
-    float ax;
-    return ddim_x0_of<TE>(p, xt, ec, eu, idx, guided, &ax);
+    const float ax = p.a_recip * x;
+    const float be = p.a_recipm1 * e;
+    *ax_out = ax;
+    return ax - be;
   } else {
-    return unipc_x0_of<TE>(p, xt, ec, eu, idx, guided);
+    const float se = p.a_recip * e;
+    const float num = x - se;
+    return num / p.a_recipm1;
   }
 }
 
@@ -246,113 +235,92 @@ __device__ __forceinline__ float x0_form(const DdimParams& p, const float* xt, c
 __device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
 
-// RESTRICT: 0 none, 1 clamp to [-bound, bound], 2 dynamic threshold by table[sample][0]; COND: the classifier-guidance term
-template <typename TE, int RESTRICT, bool COND>
+// The restricted mode-0 step (FORM 0; gaussian_sampler.py:110-120, 199-211) — RESTRICT: 0 none, 1 clamp to [-bound, bound], 2 dynamic
+// threshold by table[sample][0]; COND: the classifier-guidance term — and the apply pass of mode 2 (FORM 1, RESTRICT 2): out is the
+// thresholded x0 itself, clamp(x0, -s, s) / s.  A NaN in x0 or s is the result; each form keeps torch's operand order of its clamp.
+struct DdimRestrict {
+  const float* table;   // i[8] = 2: [samples, 4] fp32, s in column 0 (p[7])
+  const float* grad;    // i[9] = 1: condition_fn's result, fp32, dense like x (p[8])
+  float bound;          // i[8] = 1: clamp bound (f[6])
+  float sqrt_1mat;      // i[9] = 1: sqrt(1 - a_t) (f[7])
+};
+
+template <typename TE, int FORM, int RESTRICT, bool COND>
 __global__ __launch_bounds__(256) void ddim_restrict_kernel(const DdimParams p, const DdimRestrict r) {
 #pragma clang fp contract(off)
-  const float* xt = reinterpret_cast<const float*>(p.xt);
-  const TE* ec = reinterpret_cast<const TE*>(p.eps);
-  const TE* eu = ec + (size_t)p.C * p.inner;
-  float* out = reinterpret_cast<float*>(p.out);
-  const long total = (long)p.C * p.inner;
-  const long per_sample = (long)p.cps * p.inner, guided_n = (long)p.guided * p.inner;
-  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-    const long smp = idx / per_sample;
-    float ax;
-    float x0 = ddim_x0_of<TE>(p, xt, ec, eu, idx, idx - smp * per_sample < guided_n, &ax);
+  const DdimView<TE> v(p);
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < v.total; idx += (long)gridDim.x * 256) {
+    const long smp = v.sample(idx);
+    float ax = 0.f;
+    float x0 = ddim_x0_of<FORM>(p, v, idx, v.guided(idx - smp * v.per_sample), &ax);
     if constexpr (RESTRICT == 1) {
       x0 = nan_min(nan_max(x0, -r.bound), r.bound);                    // torch.clamp: a NaN stays a NaN
     } else if constexpr (RESTRICT == 2) {
       const float s = r.table[smp * 4];
-      x0 = nan_min(s, nan_max(-s, x0)) / s;
+      x0 = (FORM == 0 ? nan_min(s, nan_max(-s, x0)) : nan_min(nan_max(x0, -s), s)) / s;
     }
-    float eps = (ax - x0) / p.a_recipm1;
-    if constexpr (COND) {
-      const float g = r.sqrt_1mat * r.grad[idx];
-      eps = eps - g;
-      const float be = p.a_recipm1 * eps;
-      x0 = ax - be;
+    if constexpr (FORM == 1) {
+      v.out[idx] = x0;
+    } else {
+      float eps = (ax - x0) / p.a_recipm1;
+      if constexpr (COND) {
+        const float g = r.sqrt_1mat * r.grad[idx];
+        eps = eps - g;
+        const float be = p.a_recipm1 * eps;
+        x0 = ax - be;
+      }
+      const float m0 = p.sqrt_aprev * x0, m1 = p.dir_coef * eps;
+      float xn = m0 + m1;
+      if (p.noise != nullptr && p.sigma != 0.f) {
+        const float m2 = p.sigma * p.noise[idx];
+        xn = xn + m2;
+      }
+      v.out[idx] = xn;
     }
-    const float m0 = p.sqrt_aprev * x0, m1 = p.dir_coef * eps;
-    float xn = m0 + m1;
-    if (p.noise != nullptr && p.sigma != 0.f) {
-      const float m2 = p.sigma * p.noise[idx];
-      xn = xn + m2;
-    }
-    out[idx] = xn;
-  }
-}
-
-// mode 2, i[8] = 2: out = clamp(x0, -s, s) / s with s = table[sample][0] — torch.clamp with tensor bounds, min(max(x0, -s), s); a NaN in
-// x0 or s is the result.  The x0 is unipc_x0_of's, the one the measure pass ranked.
-template <typename TE>
-__global__ __launch_bounds__(256) void x0_threshold_kernel(const DdimParams p, const float* table) {
-#pragma clang fp contract(off)
-  const float* xt = reinterpret_cast<const float*>(p.xt);
-  const TE* ec = reinterpret_cast<const TE*>(p.eps);
-  const TE* eu = ec + (size_t)p.C * p.inner;
-  float* out = reinterpret_cast<float*>(p.out);
-  const long total = (long)p.C * p.inner;
-  const long per_sample = (long)p.cps * p.inner, guided_n = (long)p.guided * p.inner;
-  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-    const long smp = idx / per_sample;
-    const float x0 = x0_form<TE, 1>(p, xt, ec, eu, idx, idx - smp * per_sample < guided_n);
-    const float s = table[smp * 4];
-    out[idx] = nan_min(nan_max(x0, -s), s) / s;
   }
 }
 
 // ---- mode 3: the DDIM inversion step, DDIMSampler.encode (samplers/ddim/sampler.py:242-254) ---------------------------------------------
-// A kernel of its own, like the restricted ones.  e = e_u + g (e_c - e_u) over all channels or e = e_c (the record is guided as a whole,
-// so no element needs its channel), out = f0 x + f1 e: both products first, then their sum, every operation rounded by itself.
-struct DdimInvert {
-  const float* x; const void* eps; float* out; float* keep;     // keep: optional second destination (a kept intermediate), same values
-  long total;                                                   // samples * channels * inner
-  float cx, ce, gscale;
-};
-
-__device__ __forceinline__ float ddim_invert_of(const DdimInvert& p, float x, float y, float u, bool guided) {
+// The record is guided as a whole (all channels or none), so no element needs its channel.  out = f0 x + f1 e: both products first,
+// then their sum, every operation rounded by itself.
+__device__ __forceinline__ float ddim_invert_of(const DdimParams& p, float x, float y, float u, bool guided) {
 #pragma clang fp contract(off)
-  float e = y;
-  if (guided) {
-    const float d = p.gscale * (y - u);
-    e = u + d;
-  }
-  const float m0 = p.cx * x, m1 = p.ce * e;
+  const float e = guided ? ddim_combine(p.gscale, y, u) : y;
+  const float m0 = p.a_recip * x, m1 = p.a_recipm1 * e;
   return m0 + m1;
 }
 
-// VEC: four elements per thread with one 128-bit access per fp32 tensor (64-bit for fp16 eps) — the launcher found every pointer
-// 16-byte aligned; the total % 4 last elements are the scalar work of workgroup 0.  !VEC: one element per thread.
+// keep: optional second destination (a kept intermediate), same values.  VEC: four elements per thread with one 128-bit access per fp32
+// tensor (64-bit for fp16 eps) — the launcher found every pointer 16-byte aligned; the total % 4 last elements are the scalar work of
+// workgroup 0.  !VEC: one element per thread.
 template <typename TE, bool GUIDED, bool VEC>
-__global__ __launch_bounds__(256) void ddim_invert_kernel(const DdimInvert p) {
-  const TE* ec = reinterpret_cast<const TE*>(p.eps);
-  const TE* eu = ec + p.total;                 // read only when GUIDED
+__global__ __launch_bounds__(256) void ddim_invert_kernel(const DdimParams p, float* keep) {
+  const DdimView<TE> v(p);                     // v.eu is read only when GUIDED
   const long stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
   auto one = [&](long idx) {
-    const float u = GUIDED ? (float)eu[idx] : 0.f;
-    const float o = ddim_invert_of(p, p.x[idx], (float)ec[idx], u, GUIDED);
-    p.out[idx] = o;
-    if (p.keep != nullptr) p.keep[idx] = o;
+    const float u = GUIDED ? (float)v.eu[idx] : 0.f;
+    const float o = ddim_invert_of(p, v.xt[idx], (float)v.ec[idx], u, GUIDED);
+    v.out[idx] = o;
+    if (keep != nullptr) keep[idx] = o;
   };
   if constexpr (VEC) {
     using TE4 = TE __attribute__((ext_vector_type(4)));
-    const long nvec = p.total >> 2;
-    for (long v = first; v < nvec; v += stride) {
-      const f32x4 x = reinterpret_cast<const f32x4*>(p.x)[v];
-      const TE4 y = reinterpret_cast<const TE4*>(ec)[v];
+    const long nvec = v.total >> 2;
+    for (long q = first; q < nvec; q += stride) {
+      const f32x4 x = reinterpret_cast<const f32x4*>(v.xt)[q];
+      const TE4 y = reinterpret_cast<const TE4*>(v.ec)[q];
       TE4 u = y;
-      if constexpr (GUIDED) u = reinterpret_cast<const TE4*>(eu)[v];
+      if constexpr (GUIDED) u = reinterpret_cast<const TE4*>(v.eu)[q];
       f32x4 o;
 #pragma unroll
       for (int k = 0; k < 4; ++k) o[k] = ddim_invert_of(p, x[k], (float)y[k], (float)u[k], GUIDED);
-      reinterpret_cast<f32x4*>(p.out)[v] = o;
-      if (p.keep != nullptr) reinterpret_cast<f32x4*>(p.keep)[v] = o;
+      reinterpret_cast<f32x4*>(v.out)[q] = o;
+      if (keep != nullptr) reinterpret_cast<f32x4*>(keep)[q] = o;
     }
     const long tail = (nvec << 2) + threadIdx.x;
-    if (blockIdx.x == 0 && threadIdx.x < 4 && tail < p.total) one(tail);
+    if (blockIdx.x == 0 && threadIdx.x < 4 && tail < v.total) one(tail);
   } else {
-    for (long idx = first; idx < p.total; idx += stride) one(idx);
+    for (long idx = first; idx < v.total; idx += stride) one(idx);
   }
 }
 
@@ -374,12 +342,11 @@ __global__ __launch_bounds__(QT_THREADS) void ddim_measure_kernel(const DdimPara
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned n = (unsigned)p.cps * (unsigned)p.inner;              // <= 2^24 (validated)
   const long base = (long)blockIdx.x * n;
-  const float* xt = reinterpret_cast<const float*>(p.xt);
-  const TE* ec = reinterpret_cast<const TE*>(p.eps);
-  const TE* eu = ec + (size_t)p.C * p.inner;
-  const unsigned guided_n = (unsigned)p.guided * (unsigned)p.inner;
+  const DdimView<TE> v(p);
+  const unsigned guided_n = (unsigned)v.guided_n;                      // (below n: the key loops compare in 32 bits)
   auto key_at = [&](unsigned i) -> unsigned {
-    return __float_as_uint(x0_form<TE, FORM>(p, xt, ec, eu, base + i, i < guided_n)) & 0x7fffffffu;     // |x0|: -0.0 is 0
+    float ax;
+    return __float_as_uint(ddim_x0_of<FORM>(p, v, base + i, i < guided_n, &ax)) & 0x7fffffffu;     // |x0|: -0.0 is 0
   };
 
   unsigned prefix = 0, k = m.lo, n_eq = 0;
@@ -1183,121 +1150,117 @@ inline int grid_for(long n) {
   return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
+// A run-time dtype tag, flag or small index as a compile-time argument of a generic lambda: f gets a value of the element type
+// (`using T = decltype(t)`), a std::bool_constant, or a std::integral_constant below N (the last one for anything at or beyond it)
+template <typename F> void by_dtype(int dtype, F&& f) { if (dtype == T2V_F32) f(float()); else f(f16()); }
+template <typename F> void by_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int N, typename F> void by_index(int i, F&& f) {
+  if constexpr (N > 1) { if (i < N - 1) return by_index<N - 1>(i, f); }
+  f(std::integral_constant<int, N - 1>{});
+}
+
 }  // namespace
 
 hipError_t t2v_launch_ncthw_to_cl(const t2v_op& op, hipStream_t s) {
   const int B = op.i[0], C = op.i[1], F = op.i[2], HW = op.i[3], ld = op.i[4];
   const long n = (long)B * F * HW;
   const int Bsrc = (op.i[6] > 0 && op.i[6] < B) ? op.i[6] : B;
-  f16* out = reinterpret_cast<f16*>(op.p[1]);
-  if (op.i[5] == T2V_F32)
-    hipLaunchKernelGGL(ncthw_to_cl_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s,
-                       reinterpret_cast<const float*>(op.p[0]), out, B, C, F, HW, ld, op.f[0], Bsrc, reinterpret_cast<f16*>(op.p[2]),
+  by_dtype(op.i[5], [&](auto t) {
+    using TIN = decltype(t);
+    hipLaunchKernelGGL(ncthw_to_cl_kernel<TIN>, dim3(grid_for(n)), dim3(256), 0, s, reinterpret_cast<const TIN*>(op.p[0]),
+                       reinterpret_cast<f16*>(op.p[1]), B, C, F, HW, ld, op.f[0], Bsrc, reinterpret_cast<f16*>(op.p[2]),
                        (op.i[7] != 0 && ld >= 2 * C) ? 1 : 0);
-  else
-    hipLaunchKernelGGL(ncthw_to_cl_kernel<f16>, dim3(grid_for(n)), dim3(256), 0, s,
-                       reinterpret_cast<const f16*>(op.p[0]), out, B, C, F, HW, ld, op.f[0], Bsrc, reinterpret_cast<f16*>(op.p[2]),
-                       (op.i[7] != 0 && ld >= 2 * C) ? 1 : 0);
+  });
   return hipGetLastError();
 }
 
 hipError_t t2v_launch_cl_to_ncthw(const t2v_op& op, hipStream_t s) {
   const int B = op.i[0], C = op.i[1], F = op.i[2], HW = op.i[3], ld = op.i[4];
   const long n = (long)B * C * F * HW;
-  const float* in = reinterpret_cast<const float*>(op.p[0]);
-  if (op.i[5] == T2V_F32)
-    hipLaunchKernelGGL(cl_to_ncthw_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s, in,
-                       reinterpret_cast<float*>(op.p[1]), B, C, F, HW, ld);
-  else
-    hipLaunchKernelGGL(cl_to_ncthw_kernel<f16>, dim3(grid_for(n)), dim3(256), 0, s, in,
-                       reinterpret_cast<f16*>(op.p[1]), B, C, F, HW, ld);
+  by_dtype(op.i[5], [&](auto t) {
+    using TOUT = decltype(t);
+    hipLaunchKernelGGL(cl_to_ncthw_kernel<TOUT>, dim3(grid_for(n)), dim3(256), 0, s, reinterpret_cast<const float*>(op.p[0]),
+                       reinterpret_cast<TOUT*>(op.p[1]), B, C, F, HW, ld);
+  });
   return hipGetLastError();
 }
 
 hipError_t t2v_launch_to_uint8(const t2v_op& op, hipStream_t s) {
   const int NI = op.i[0], C = op.i[1], F = op.i[2], H = op.i[3], W = op.i[4];
-  const bool half = op.i[6] != 0;
   const int bgr = op.i[7];
   const long si = (long)(uint32_t)op.i[8] | ((long)op.i[9] << 32), sc = op.i[10], sf = (long)(uint32_t)op.i[11] | ((long)op.i[12] << 32);
   const long sy = op.i[13], sx = op.i[14];
-  const int g = grid_for((long)F * H * NI * W);
+  const dim3 g(grid_for((long)F * H * NI * W)), b(256);
   unsigned char* out = reinterpret_cast<unsigned char*>(op.p[1]);
-  if (op.i[15] == 1) {                                   // torch_to_np: a kernel of its own, form 0 launches what it always launched
-    if (op.i[5] == T2V_F32) {
-      const float* in = reinterpret_cast<const float*>(op.p[0]);
-      if (half) hipLaunchKernelGGL((to_uint8_np_kernel<float, true>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
-      else hipLaunchKernelGGL((to_uint8_np_kernel<float, false>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
-    } else {
-      const f16* in = reinterpret_cast<const f16*>(op.p[0]);
-      if (half) hipLaunchKernelGGL((to_uint8_np_kernel<f16, true>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
-      else hipLaunchKernelGGL((to_uint8_np_kernel<f16, false>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
-    }
-    return hipGetLastError();
-  }
-  if (op.i[5] == T2V_F32) {
-    const float* in = reinterpret_cast<const float*>(op.p[0]);
-    if (half) hipLaunchKernelGGL((to_uint8_kernel<float, true>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx, bgr);
-    else hipLaunchKernelGGL((to_uint8_kernel<float, false>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx, bgr);
-  } else {
-    const f16* in = reinterpret_cast<const f16*>(op.p[0]);
-    if (half) hipLaunchKernelGGL((to_uint8_kernel<f16, true>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx, bgr);
-    else hipLaunchKernelGGL((to_uint8_kernel<f16, false>), dim3(g), dim3(256), 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx, bgr);
-  }
+  by_dtype(op.i[5], [&](auto t) {
+    by_bool(op.i[6] != 0, [&](auto half) {
+      using TIN = decltype(t);
+      constexpr bool HALF = decltype(half)::value;
+      const TIN* in = reinterpret_cast<const TIN*>(op.p[0]);
+      if (op.i[15] == 1)                                 // torch_to_np: a kernel of its own, form 0 launches what it always launched
+        hipLaunchKernelGGL((to_uint8_np_kernel<TIN, HALF>), g, b, 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx);
+      else
+        hipLaunchKernelGGL((to_uint8_kernel<TIN, HALF>), g, b, 0, s, in, out, NI, C, F, H, W, si, sc, sf, sy, sx, bgr);
+    });
+  });
   return hipGetLastError();
+}
+
+// Units of a row — bicubic: an output column; uint8 pass: a pixel (token forms), 4 pixels (horizontal, uint8) or 4 bytes (vertical,
+// uint8) — in tiles of 256, one workgroup each, over the rows (planes x output rows | images x rows of the pass)
+t2v_resample_grid t2v_resample_grid_of(const t2v_op& op) {
+  const long out = op.i[4], axis = op.i[5], form = op.i[7];
+  t2v_resample_grid g;
+  if (op.i[9] == 1) {
+    g.rows = (long)op.i[0] * out;
+    g.units = op.i[10];
+  } else {
+    const long row_px = axis == 0 ? out : op.i[2];
+    g.rows = (long)op.i[0] * (axis == 0 ? op.i[1] : out);
+    g.units = form != 0 ? row_px : (axis == 0 ? (row_px + 3) / 4 : (row_px * 3 + 3) / 4);
+  }
+  g.tiles = (g.units + 255) / 256;
+  return g;
 }
 
 hipError_t t2v_launch_resample(const t2v_op& op, hipStream_t s) {
   // (shape, pointers and the grid size were checked by the executor's validation)
+  const t2v_resample_grid grid = t2v_resample_grid_of(op);
+  const int tiles = (int)grid.tiles;
+  const dim3 g((unsigned)(grid.rows * grid.tiles)), b(256);
   if (op.i[9] == 1) {                                    // float bicubic mode: [P, H, W] -> fp32 [P, Ho, Wo], one launch
-    const int P = op.i[0], H = op.i[1], W = op.i[2], Ho = op.i[4], Wo = op.i[10];
-    const int tiles = (Wo + 255) / 256;
-    const dim3 g((unsigned)((long)P * Ho * tiles));
-    float* dst = reinterpret_cast<float*>(op.p[1]);
-    const float* wgt = reinterpret_cast<const float*>(op.p[2]);
-    const int* idx = reinterpret_cast<const int*>(op.p[3]);
-    if (op.i[11] == T2V_F32)
-      hipLaunchKernelGGL(bicubic_kernel<float>, g, dim3(256), 0, s, reinterpret_cast<const float*>(op.p[0]), dst, wgt, idx, H, W, Ho, Wo, tiles);
-    else
-      hipLaunchKernelGGL(bicubic_kernel<f16>, g, dim3(256), 0, s, reinterpret_cast<const f16*>(op.p[0]), dst, wgt, idx, H, W, Ho, Wo, tiles);
+    const int H = op.i[1], W = op.i[2], Ho = op.i[4], Wo = op.i[10];
+    by_dtype(op.i[11], [&](auto t) {
+      using TIN = decltype(t);
+      hipLaunchKernelGGL(bicubic_kernel<TIN>, g, b, 0, s, reinterpret_cast<const TIN*>(op.p[0]), reinterpret_cast<float*>(op.p[1]),
+                         reinterpret_cast<const float*>(op.p[2]), reinterpret_cast<const int*>(op.p[3]), H, W, Ho, Wo, tiles);
+    });
     return hipGetLastError();
   }
-  const int N = op.i[0], H = op.i[1], W = op.i[2], out = op.i[4], axis = op.i[5], ksize = op.i[6], form = op.i[7], ld = op.i[8];
+  const int H = op.i[1], W = op.i[2], out = op.i[4], axis = op.i[5], ksize = op.i[6], ld = op.i[8];
   const unsigned char* src = reinterpret_cast<const unsigned char*>(op.p[0]);
   void* dst = reinterpret_cast<void*>(op.p[1]);
   const int* coef = reinterpret_cast<const int*>(op.p[2]);
   const int* bounds = reinterpret_cast<const int*>(op.p[3]);
   const float* lut = reinterpret_cast<const float*>(op.p[4]);
-  const int row_px = axis == 0 ? out : W;
-  const int units = form != 0 ? row_px : (axis == 0 ? (row_px + 3) / 4 : (row_px * 3 + 3) / 4);     // (as in the executor's validation)
-  const int tiles = (units + 255) / 256;
-  const long rows = (long)N * (axis == 0 ? H : out);
-  const dim3 g((unsigned)(rows * tiles));
-  if (axis == 0) {
-    if (form == 0) hipLaunchKernelGGL(resample_h_kernel<0>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, W, out, ksize, ld, tiles);
-    else if (form == 1) hipLaunchKernelGGL(resample_h_kernel<1>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, W, out, ksize, ld, tiles);
-    else hipLaunchKernelGGL(resample_h_kernel<2>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, W, out, ksize, ld, tiles);
-  } else {
-    if (form == 0) hipLaunchKernelGGL(resample_v_kernel<0>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
-    else if (form == 1) hipLaunchKernelGGL(resample_v_kernel<1>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
-    else hipLaunchKernelGGL(resample_v_kernel<2>, g, dim3(256), 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
-  }
+  by_index<3>(op.i[7], [&](auto form) {
+    constexpr int FORM = decltype(form)::value;
+    if (axis == 0) hipLaunchKernelGGL(resample_h_kernel<FORM>, g, b, 0, s, src, dst, coef, bounds, lut, W, out, ksize, ld, tiles);
+    else hipLaunchKernelGGL(resample_v_kernel<FORM>, g, b, 0, s, src, dst, coef, bounds, lut, H, W, out, ksize, ld, tiles);
+  });
   return hipGetLastError();
 }
 
 hipError_t t2v_launch_depth_tokens(const t2v_op& op, hipStream_t s) {
   // (shape and pointers were checked by the executor's validation)
   const int n = op.i[0], H = op.i[1], W = op.i[2], ld = op.i[5];
-  const bool f32 = op.i[3] == T2V_F32, norm = op.i[4] != 0;
-  f16* out = reinterpret_cast<f16*>(op.p[1]);
-  if (f32) {
-    const float* in = reinterpret_cast<const float*>(op.p[0]);
-    if (norm) hipLaunchKernelGGL((depth_tokens_kernel<float, true>), dim3(n), dim3(256), 0, s, in, out, H, W, ld);
-    else hipLaunchKernelGGL((depth_tokens_kernel<float, false>), dim3(n), dim3(256), 0, s, in, out, H, W, ld);
-  } else {
-    const f16* in = reinterpret_cast<const f16*>(op.p[0]);
-    if (norm) hipLaunchKernelGGL((depth_tokens_kernel<f16, true>), dim3(n), dim3(256), 0, s, in, out, H, W, ld);
-    else hipLaunchKernelGGL((depth_tokens_kernel<f16, false>), dim3(n), dim3(256), 0, s, in, out, H, W, ld);
-  }
+  by_dtype(op.i[3], [&](auto t) {
+    by_bool(op.i[4] != 0, [&](auto norm) {
+      using TIN = decltype(t);
+      hipLaunchKernelGGL((depth_tokens_kernel<TIN, decltype(norm)::value>), dim3(n), dim3(256), 0, s, reinterpret_cast<const TIN*>(op.p[0]),
+                         reinterpret_cast<f16*>(op.p[1]), H, W, ld);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -1322,14 +1285,13 @@ hipError_t t2v_launch_reshard_rows(const t2v_op& op, hipStream_t s) {
   if (nparts > 1 && (op.i[10] % v != 0 || op.i[11] % v != 0 || op.i[12] % 4 != 0 || own >= nparts || (own >= 0 && op.p[3] == 0) || nparts > 64))
     return hipErrorInvalidValue;
   const int g = grid_for((long)rows * (cols / v));
-  if (f32)
-    hipLaunchKernelGGL(reshard_rows_kernel<float>, dim3(g, nparts), dim3(256), 0, s, reinterpret_cast<const float*>(op.p[0]),
-                       reinterpret_cast<float*>(op.p[1]), reinterpret_cast<const float*>(op.p[2]), rows, cols, P, s_src, s_dst,
-                       ld_src, ld_dst, ld_res, (long)op.i[10], (long)op.i[11], (long)op.i[12], own, own_is_src, reinterpret_cast<float*>(op.p[3]));
-  else
-    hipLaunchKernelGGL(reshard_rows_kernel<f16>, dim3(g, nparts), dim3(256), 0, s, reinterpret_cast<const f16*>(op.p[0]),
-                       reinterpret_cast<f16*>(op.p[1]), static_cast<const float*>(nullptr), rows, cols, P, s_src, s_dst, ld_src,
-                       ld_dst, 0, (long)op.i[10], (long)op.i[11], 0L, own, own_is_src, reinterpret_cast<f16*>(op.p[3]));
+  by_dtype(op.i[7], [&](auto t) {                        // fp16 rows carry no residual: a null pointer, zero strides
+    using T = decltype(t);
+    hipLaunchKernelGGL(reshard_rows_kernel<T>, dim3(g, nparts), dim3(256), 0, s, reinterpret_cast<const T*>(op.p[0]),
+                       reinterpret_cast<T*>(op.p[1]), f32 ? reinterpret_cast<const float*>(op.p[2]) : nullptr, rows, cols, P, s_src, s_dst,
+                       ld_src, ld_dst, f32 ? ld_res : 0, (long)op.i[10], (long)op.i[11], f32 ? (long)op.i[12] : 0L, own, own_is_src,
+                       reinterpret_cast<T*>(op.p[3]));
+  });
   return hipGetLastError();
 }
 
@@ -1342,34 +1304,30 @@ hipError_t t2v_launch_time_embed(const t2v_op& op, hipStream_t s) {
 }
 
 hipError_t t2v_launch_copy2d(const t2v_op& op, hipStream_t s) {
-  const int rows = op.i[0], cols = op.i[1], lds_ = op.i[2], ldd = op.i[3], sdt = op.i[4], ddt = op.i[5];
-  const int act = op.i[6];
+  const int rows = op.i[0], cols = op.i[1], lds_ = op.i[2], ldd = op.i[3], sdt = op.i[4], ddt = op.i[5], act = op.i[6];
   if (cols % 4 != 0) return hipErrorInvalidValue;
   const int g = grid_for((long)rows * (cols / 4));
-  if (sdt == T2V_F32 && ddt == T2V_F32)
-    hipLaunchKernelGGL((copy2d_kernel<float, float>), dim3(g), dim3(256), 0, s, reinterpret_cast<const float*>(op.p[0]),
-                       reinterpret_cast<float*>(op.p[1]), rows, cols, lds_, ldd, act, static_cast<f16*>(nullptr));
-  else if (sdt == T2V_F32 && ddt == T2V_F16)
-    hipLaunchKernelGGL((copy2d_kernel<float, f16>), dim3(g), dim3(256), 0, s, reinterpret_cast<const float*>(op.p[0]),
-                       reinterpret_cast<f16*>(op.p[1]), rows, cols, lds_, ldd, act, reinterpret_cast<f16*>(op.p[2]));
-  else if (sdt == T2V_F16 && ddt == T2V_F16)
-    hipLaunchKernelGGL((copy2d_kernel<f16, f16>), dim3(g), dim3(256), 0, s, reinterpret_cast<const f16*>(op.p[0]),
-                       reinterpret_cast<f16*>(op.p[1]), rows, cols, lds_, ldd, act, static_cast<f16*>(nullptr));
-  else
-    hipLaunchKernelGGL((copy2d_kernel<f16, float>), dim3(g), dim3(256), 0, s, reinterpret_cast<const f16*>(op.p[0]),
-                       reinterpret_cast<float*>(op.p[1]), rows, cols, lds_, ldd, act, static_cast<f16*>(nullptr));
+  const bool known = (sdt == T2V_F16 || sdt == T2V_F32) && (ddt == T2V_F16 || ddt == T2V_F32);      // (any other pair of tags: fp16 -> fp32)
+  by_dtype(known ? sdt : T2V_F16, [&](auto ts) {
+    by_dtype(known ? ddt : T2V_F32, [&](auto td) {
+      using TS = decltype(ts);
+      using TD = decltype(td);
+      constexpr bool LO = std::is_same_v<TS, float> && std::is_same_v<TD, f16>;      // the low-order image exists for fp32 -> fp16 casts only
+      hipLaunchKernelGGL((copy2d_kernel<TS, TD>), dim3(g), dim3(256), 0, s, reinterpret_cast<const TS*>(op.p[0]),
+                         reinterpret_cast<TD*>(op.p[1]), rows, cols, lds_, ldd, act, LO ? reinterpret_cast<f16*>(op.p[2]) : nullptr);
+    });
+  });
   return hipGetLastError();
 }
 
 hipError_t t2v_launch_emphasis(const t2v_op& op, hipStream_t s) {
   const int rows = op.i[0], W = op.i[1], ldz = op.i[2], ldo = op.i[3];
   if (rows <= 0 || W <= 0 || W % 4 != 0 || ldz < W || ldo < W || ldo % 4 != 0) return hipErrorInvalidValue;
-  const float* mult = reinterpret_cast<const float*>(op.p[1]);
-  float* out = reinterpret_cast<float*>(op.p[2]);
-  if (op.i[4] == T2V_F32)
-    hipLaunchKernelGGL((emphasis_kernel<float>), dim3(1), dim3(1024), 0, s, reinterpret_cast<const float*>(op.p[0]), mult, out, rows, W, ldz, ldo);
-  else
-    hipLaunchKernelGGL((emphasis_kernel<f16>), dim3(1), dim3(1024), 0, s, reinterpret_cast<const f16*>(op.p[0]), mult, out, rows, W, ldz, ldo);
+  by_dtype(op.i[4], [&](auto t) {
+    using TZ = decltype(t);
+    hipLaunchKernelGGL((emphasis_kernel<TZ>), dim3(1), dim3(1024), 0, s, reinterpret_cast<const TZ*>(op.p[0]),
+                       reinterpret_cast<const float*>(op.p[1]), reinterpret_cast<float*>(op.p[2]), rows, W, ldz, ldo);
+  });
   return hipGetLastError();
 }
 
@@ -1396,18 +1354,66 @@ hipError_t t2v_launch_lora_merge(const t2v_op& op, hipStream_t s) {
 hipError_t t2v_launch_embed_rows(const t2v_op& op, hipStream_t s) {
   const int rows = op.i[0], W = op.i[1], L = op.i[2], vocab = op.i[3];
   if (rows <= 0 || W <= 0 || L <= 0 || vocab <= 0) return hipErrorInvalidValue;
-  const int* ids = reinterpret_cast<const int*>(op.p[0]);
-  const float* pos = reinterpret_cast<const float*>(op.p[2]);
-  float* out = reinterpret_cast<float*>(op.p[3]);
-  if (op.i[4] == T2V_F32)
-    hipLaunchKernelGGL((embed_rows_kernel<float>), dim3(rows), dim3(256), 0, s, ids, reinterpret_cast<const float*>(op.p[1]), pos,
-                       out, rows, W, L, vocab);
-  else
-    hipLaunchKernelGGL((embed_rows_kernel<f16>), dim3(rows), dim3(256), 0, s, ids, reinterpret_cast<const f16*>(op.p[1]), pos,
-                       out, rows, W, L, vocab);
+  by_dtype(op.i[4], [&](auto t) {
+    using TT = decltype(t);
+    hipLaunchKernelGGL((embed_rows_kernel<TT>), dim3(rows), dim3(256), 0, s, reinterpret_cast<const int*>(op.p[0]),
+                       reinterpret_cast<const TT*>(op.p[1]), reinterpret_cast<const float*>(op.p[2]), reinterpret_cast<float*>(op.p[3]),
+                       rows, W, L, vocab);
+  });
   return hipGetLastError();
 }
 
+// What a DDIM_STEP record is, or why it is none: the one place that knows which combinations of i[5], i[7], i[8], i[9], i[4], p[3..8] and
+// f[6] are legal (include/t2v_hip.h)
+t2v_ddim_class t2v_ddim_classify(const t2v_op& op) {
+  auto is = [](t2v_ddim_form form, int x0_form = 0) { return t2v_ddim_class{form, x0_form, nullptr}; };
+  auto bad = [](const char* why) { return t2v_ddim_class{T2V_DDIM_MALFORMED, 0, why}; };
+  const int C = op.i[0], cps = op.i[6] > 0 ? op.i[6] : C;
+  if (C <= 0 || op.i[1] <= 0 || cps <= 0 || C % cps != 0) return bad("DDIM step needs C > 0, inner > 0, C % channels-per-sample == 0");
+  if (op.i[2] < 0 || op.i[2] > cps || op.i[5] < 0 || op.i[5] > 3) return bad("DDIM step: guided channels / mode");
+  if (op.i[5] == 3) {      // DDIM inversion (DDIMSampler.encode): out = f0 x + f1 e, nothing else
+    if (op.i[7] != 0 || op.i[8] != 0 || op.i[9] != 0) return bad("DDIM step: mode 3 (inversion) has no mask blend i[7], no x0 restriction i[8] and no classifier-guidance term i[9]");
+    if (op.i[4] != T2V_F32) return bad("DDIM step: mode 3 (inversion) needs an fp32 x");
+    if (op.i[2] != 0 && op.i[2] != cps) return bad("DDIM step: mode 3 (inversion) combines the guidance over all channels (i[2] = channels per sample) or not at all (0)");
+    if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return bad("null DDIM step pointer (mode 3 reads x p[0] and the eps pair p[1] and writes p[3])");
+    return is(T2V_DDIM_INVERT);
+  }
+  if (op.i[8] < 0 || op.i[8] > 3) return bad("DDIM step: x0 restriction i[8] must be 0 (none), 1 (clamp), 2 (threshold) or 3 (measure pass)");
+  if (op.i[9] != 0 && op.i[9] != 1) return bad("DDIM step: classifier-guidance flag i[9] must be 0 or 1");
+  if (op.p[0] == 0 || op.p[1] == 0 || (op.p[3] == 0 && op.i[8] != 3)) return bad("null DDIM step pointer");
+  if (op.i[7] != 0 && op.i[7] != 1) return bad("DDIM step: blend flag i[7] must be 0 or 1");
+  if (op.i[5] == 2) {      // UniPC's thresholded data prediction: a measure record and an apply record, nothing else
+    if (op.i[8] != 2 && op.i[8] != 3) return bad("DDIM step: mode 2 (thresholded data prediction) is the measure pass i[8] = 3 or the apply pass i[8] = 2; the clamp i[8] = 1 and the plain prediction (a LINCOMB) are not records of it");
+    if (op.i[7] != 0 || op.i[9] != 0) return bad("DDIM step: mode 2 has no mask blend i[7] and no classifier-guidance term i[9]");
+    if (op.i[4] != T2V_F32) return bad("DDIM step: mode 2 needs an fp32 x");
+    if (op.i[2] != 0 && op.i[2] != cps) return bad("DDIM step: mode 2 combines the guidance over all channels (i[2] = channels per sample) or not at all (0)");
+    if (op.p[7] == 0) return bad("DDIM step: mode 2 needs the threshold table p[7]");
+    if ((int64_t)cps * op.i[1] > (int64_t)16777216) return bad("DDIM step: mode 2 ranks at most 16 777 216 elements per sample (torch.quantile's limit)");
+    if (op.i[8] == 3 && !(op.f[6] > 0.f && op.f[6] <= 1.f)) return bad("DDIM step: the measure pass i[8] = 3 needs a quantile f[6] in (0, 1]");
+    return op.i[8] == 3 ? is(T2V_DDIM_MEASURE, 1) : is(T2V_DDIM_THRESHOLD);
+  }
+  if (op.i[8] != 0 || op.i[9] != 0) {
+    if (op.i[5] != 0) return bad("DDIM step: the x0 restriction i[8] and the classifier-guidance term i[9] exist for mode 0 (DDIM_Gaussian) only");
+    if (op.i[7] != 0) return bad("DDIM step: the x0 restriction i[8] / classifier-guidance term i[9] and the mask blend i[7] exclude each other");
+    if (op.i[4] != T2V_F32) return bad("DDIM step: the x0 restriction i[8] and the classifier-guidance term i[9] need an fp32 x");
+    if ((op.i[8] == 2 || op.i[8] == 3) && op.p[7] == 0) return bad("DDIM step: the x0 threshold i[8] = 2 | 3 needs the threshold table p[7]");
+    if (op.i[9] == 1 && op.p[8] == 0) return bad("DDIM step: the classifier-guidance term i[9] needs the gradient p[8]");
+    if (op.i[8] == 1 && !(op.f[6] >= 0.f)) return bad("DDIM step: the x0 clamp i[8] = 1 needs a bound f[6] >= 0");
+    if (op.i[8] != 3) return is(T2V_DDIM_RESTRICT);
+    if ((int64_t)cps * op.i[1] > (int64_t)16777216) return bad("DDIM step: the measure pass i[8] = 3 ranks at most 16 777 216 elements per sample (torch.quantile's limit)");
+    if (!(op.f[6] > 0.f && op.f[6] <= 1.f)) return bad("DDIM step: the measure pass i[8] = 3 needs a percentile f[6] in (0, 1]");
+    return is(T2V_DDIM_MEASURE, 0);
+  }
+  if (op.i[7] == 0) return is(T2V_DDIM_PLAIN);
+  if (op.i[5] != 1) return bad("DDIM step: the mask blend i[7] exists for mode 1 (LDM DDIM) only");
+  if (op.i[4] != T2V_F32) return bad("DDIM step: the mask blend i[7] needs an fp32 x");
+  if (op.p[4] == 0 || op.p[5] == 0) return bad("DDIM step: the mask blend i[7] needs the known x0 p[4] and the mask p[5]");
+  if (op.p[6] == 0 && op.f[7] != 0.f) return bad("DDIM step: the mask blend i[7] needs the q-noise p[6] unless f[7] == 0");
+  return is(T2V_DDIM_BLEND);
+}
+
+// Every caller has validated the record (t2v_run_ops and t2v_plan_create pass each record through validate_op, which asks
+// t2v_ddim_classify): the launcher asks for the form and checks nothing again.
 hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s) {
   DdimParams p;
   p.xt = reinterpret_cast<const void*>(op.p[0]);
@@ -1417,98 +1423,65 @@ hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s) {
   p.C = op.i[0]; p.inner = op.i[1]; p.guided = op.i[2]; p.eps_f32 = op.i[3] == T2V_F32; p.x_f32 = op.i[4] == T2V_F32;
   p.mode = op.i[5];
   p.cps = op.i[6] > 0 ? op.i[6] : p.C;       // channels per sample (several videos per batch: C = samples * cps)
-  if (p.C % p.cps != 0) return hipErrorInvalidValue;
   p.a_recip = op.f[0]; p.a_recipm1 = op.f[1]; p.sqrt_aprev = op.f[2]; p.dir_coef = op.f[3]; p.sigma = op.f[4];
   p.gscale = op.f[5];
-  const int g = grid_for((long)p.C * p.inner);
-  // the measure pass of a record (i[8] = 3): one workgroup per sample, writes table[sample][0..3] only
-  auto measure = [&](auto form) -> hipError_t {
-    constexpr int FORM = decltype(form)::value;
-    const long n = (long)p.cps * p.inner;
-    if (n > (1L << 24) || !(op.f[6] > 0.f && op.f[6] <= 1.f) || op.p[7] == 0) return hipErrorInvalidValue;
-    DdimMeasure m;
-    m.table = reinterpret_cast<float*>(op.p[7]);
-    volatile float rank = op.f[6] * (float)(n - 1);     // torch.quantile's fp32 rank (one rounded product)
-    const float below = floorf(rank);
-    m.lo = (unsigned)below; m.hi = (unsigned)ceilf(rank); m.w = rank - below;
-    const int samples = p.C / p.cps;
-    if (p.eps_f32) hipLaunchKernelGGL((ddim_measure_kernel<float, FORM>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
-    else hipLaunchKernelGGL((ddim_measure_kernel<f16, FORM>), dim3(samples), dim3(QT_THREADS), 0, s, p, m);
-    return hipGetLastError();
-  };
-  if (p.mode == 3) {                           // DDIM inversion (DDIMSampler.encode): fp32 x, guidance over all channels or none
-    if (p.C <= 0 || p.inner <= 0 || !p.x_f32 || op.i[7] != 0 || op.i[8] != 0 || op.i[9] != 0 || (p.guided != 0 && p.guided != p.cps))
-      return hipErrorInvalidValue;
-    if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return hipErrorInvalidValue;
-    DdimInvert v;
-    v.x = reinterpret_cast<const float*>(op.p[0]); v.eps = p.eps; v.out = reinterpret_cast<float*>(op.p[3]);
-    v.keep = reinterpret_cast<float*>(op.p[4]);
-    v.total = (long)p.C * p.inner;
-    v.cx = op.f[0]; v.ce = op.f[1]; v.gscale = op.f[5];
-    const bool guided = p.guided != 0;
-    // every 16-byte access of the vector path: x, out, keep, the conditional half and — guided — the unconditional half behind it
-    const uint64_t eu = op.p[1] + (uint64_t)v.total * (p.eps_f32 ? 4 : 2);
-    const bool vec = v.total >= 4 && ((op.p[0] | op.p[1] | op.p[3] | op.p[4] | (guided ? eu : 0)) & 15) == 0;
-    const int gi = grid_for(vec ? v.total >> 2 : v.total);
-#define T2V_DDIM_INVERT(TE)                                                                                            \
-    if (guided) {                                                                                                      \
-      if (vec) hipLaunchKernelGGL((ddim_invert_kernel<TE, true, true>), dim3(gi), dim3(256), 0, s, v);                 \
-      else hipLaunchKernelGGL((ddim_invert_kernel<TE, true, false>), dim3(gi), dim3(256), 0, s, v);                    \
-    } else {                                                                                                           \
-      if (vec) hipLaunchKernelGGL((ddim_invert_kernel<TE, false, true>), dim3(gi), dim3(256), 0, s, v);                \
-      else hipLaunchKernelGGL((ddim_invert_kernel<TE, false, false>), dim3(gi), dim3(256), 0, s, v);                   \
+  const t2v_ddim_class cls = t2v_ddim_classify(op);
+  const long total = (long)p.C * p.inner;
+  const dim3 g(grid_for(total)), b(256);
+  const DdimRestrict r = {reinterpret_cast<const float*>(op.p[7]), reinterpret_cast<const float*>(op.p[8]), op.f[6], op.f[7]};
+  by_dtype(op.i[3], [&](auto te) {
+    using TE = decltype(te);
+    switch (cls.form) {
+      case T2V_DDIM_PLAIN:
+        by_dtype(op.i[4], [&](auto tx) { hipLaunchKernelGGL((ddim_step_kernel<decltype(tx), TE>), g, b, 0, s, p); });
+        break;
+      case T2V_DDIM_BLEND: {                   // masked step: the blend is a compile-time variant (fp32 x only)
+        const DdimBlend k = {reinterpret_cast<const float*>(op.p[4]), reinterpret_cast<const float*>(op.p[5]),
+                             reinterpret_cast<const float*>(op.p[6]), op.f[6], op.f[7]};
+        hipLaunchKernelGGL((ddim_step_kernel<float, TE, DdimBlend>), g, b, 0, s, p, k);
+        break;
+      }
+      case T2V_DDIM_RESTRICT:                  // mode 0 with a restricted x0 (i[8] = 1 | 2) and / or the classifier-guidance term (i[9])
+        by_index<3>(op.i[8], [&](auto restrict_) {
+          by_bool(op.i[9] != 0, [&](auto cond) {
+            constexpr int RESTRICT = decltype(restrict_)::value;
+            constexpr bool COND = decltype(cond)::value;
+            if constexpr (RESTRICT != 0 || COND) hipLaunchKernelGGL((ddim_restrict_kernel<TE, 0, RESTRICT, COND>), g, b, 0, s, p, r);
+          });
+        });
+        break;
+      case T2V_DDIM_THRESHOLD:                 // mode 2's apply pass: the thresholded data prediction itself
+        hipLaunchKernelGGL((ddim_restrict_kernel<TE, 1, 2, false>), g, b, 0, s, p, r);
+        break;
+      case T2V_DDIM_MEASURE: {                 // one workgroup per sample, writes table[sample][0..3] only
+        const long n = (long)p.cps * p.inner;
+        DdimMeasure m;
+        m.table = reinterpret_cast<float*>(op.p[7]);
+        volatile float rank = op.f[6] * (float)(n - 1);     // torch.quantile's fp32 rank (one rounded product)
+        const float below = floorf(rank);
+        m.lo = (unsigned)below; m.hi = (unsigned)ceilf(rank); m.w = rank - below;
+        by_index<2>(cls.x0_form, [&](auto form) {
+          hipLaunchKernelGGL((ddim_measure_kernel<TE, decltype(form)::value>), dim3(p.C / p.cps), dim3(QT_THREADS), 0, s, p, m);
+        });
+        break;
+      }
+      case T2V_DDIM_INVERT: {                  // fp32 x, guidance over all channels or none; p[4]: the optional kept copy
+        const bool guided = p.guided != 0;
+        // every 16-byte access of the vector path: x, out, keep, the conditional half and — guided — the unconditional half behind it
+        const uint64_t eu = op.p[1] + (uint64_t)total * sizeof(TE);
+        const bool vec = total >= 4 && ((op.p[0] | op.p[1] | op.p[3] | op.p[4] | (guided ? eu : 0)) & 15) == 0;
+        const dim3 gi(grid_for(vec ? total >> 2 : total));
+        by_bool(guided, [&](auto gd) {
+          by_bool(vec, [&](auto vc) {
+            hipLaunchKernelGGL((ddim_invert_kernel<TE, decltype(gd)::value, decltype(vc)::value>), gi, b, 0, s, p, reinterpret_cast<float*>(op.p[4]));
+          });
+        });
+        break;
+      }
+      case T2V_DDIM_MALFORMED: break;
     }
-    if (p.eps_f32) { T2V_DDIM_INVERT(float) } else { T2V_DDIM_INVERT(f16) }
-#undef T2V_DDIM_INVERT
-    return hipGetLastError();
-  }
-  if (p.mode == 2) {                           // UniPC's thresholded data prediction: measure (i[8] = 3), then apply (i[8] = 2); the executor checked
-    if (!p.x_f32 || op.i[7] != 0 || op.i[9] != 0 || op.p[7] == 0 || (p.guided != 0 && p.guided != p.cps)) return hipErrorInvalidValue;
-    if ((long)p.cps * p.inner > (1L << 24)) return hipErrorInvalidValue;
-    if (op.i[8] == 3) return measure(std::integral_constant<int, 1>{});
-    if (op.i[8] != 2 || op.p[3] == 0) return hipErrorInvalidValue;
-    const float* table = reinterpret_cast<const float*>(op.p[7]);
-    if (p.eps_f32) hipLaunchKernelGGL((x0_threshold_kernel<float>), dim3(g), dim3(256), 0, s, p, table);
-    else hipLaunchKernelGGL((x0_threshold_kernel<f16>), dim3(g), dim3(256), 0, s, p, table);
-    return hipGetLastError();
-  }
-  if (op.i[8] != 0 || op.i[9] != 0) {          // restricted x0 / classifier guidance: mode 0, fp32 x, no blend (the executor checked)
-    if (!p.x_f32 || p.mode != 0 || op.i[7] != 0) return hipErrorInvalidValue;
-    if (op.i[8] == 3) return measure(std::integral_constant<int, 0>{});
-    DdimRestrict r;
-    r.table = reinterpret_cast<const float*>(op.p[7]);
-    r.grad = reinterpret_cast<const float*>(op.p[8]);
-    r.bound = op.f[6]; r.sqrt_1mat = op.f[7];
-    const int sel = op.i[8] * 2 + (op.i[9] != 0 ? 1 : 0);
-#define T2V_DDIM_RESTRICT(TE)                                                                                          \
-    switch (sel) {                                                                                                     \
-      case 1: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 0, true>), dim3(g), dim3(256), 0, s, p, r); break;          \
-      case 2: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 1, false>), dim3(g), dim3(256), 0, s, p, r); break;         \
-      case 3: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 1, true>), dim3(g), dim3(256), 0, s, p, r); break;          \
-      case 4: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 2, false>), dim3(g), dim3(256), 0, s, p, r); break;         \
-      case 5: hipLaunchKernelGGL((ddim_restrict_kernel<TE, 2, true>), dim3(g), dim3(256), 0, s, p, r); break;          \
-      default: return hipErrorInvalidValue;                                                                            \
-    }
-    if (p.eps_f32) { T2V_DDIM_RESTRICT(float) } else { T2V_DDIM_RESTRICT(f16) }
-#undef T2V_DDIM_RESTRICT
-    return hipGetLastError();
-  }
-  if (op.i[7] != 0) {                        // masked step: the blend is a compile-time variant (fp32 x only; the executor checked)
-    if (!p.x_f32) return hipErrorInvalidValue;
-    DdimBlend b;
-    b.x0 = reinterpret_cast<const float*>(op.p[4]);
-    b.mask = reinterpret_cast<const float*>(op.p[5]);
-    b.qnoise = reinterpret_cast<const float*>(op.p[6]);
-    b.sqrt_ac = op.f[6]; b.sqrt_1mac = op.f[7];
-    if (p.eps_f32) hipLaunchKernelGGL((ddim_step_kernel<float, float, DdimBlend>), dim3(g), dim3(256), 0, s, p, b);
-    else hipLaunchKernelGGL((ddim_step_kernel<float, f16, DdimBlend>), dim3(g), dim3(256), 0, s, p, b);
-    return hipGetLastError();
-  }
-  if (p.x_f32 && p.eps_f32) hipLaunchKernelGGL((ddim_step_kernel<float, float>), dim3(g), dim3(256), 0, s, p);
-  else if (p.x_f32) hipLaunchKernelGGL((ddim_step_kernel<float, f16>), dim3(g), dim3(256), 0, s, p);
-  else if (p.eps_f32) hipLaunchKernelGGL((ddim_step_kernel<f16, float>), dim3(g), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((ddim_step_kernel<f16, f16>), dim3(g), dim3(256), 0, s, p);
-  return hipGetLastError();
+  });
+  return cls.form == T2V_DDIM_MALFORMED ? hipErrorInvalidValue : hipGetLastError();
 }
 
 hipError_t t2v_launch_lincomb(const t2v_op& op, hipStream_t s) {

@@ -237,49 +237,8 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.p[2] != 0 && !(op.i[4] == T2V_F32 && op.i[5] == T2V_F16)) return bad("copy2d: the low-order output exists for fp32 -> fp16 casts only");
       return 0;
     case T2V_OP_DDIM_STEP: {
-      const int C = op.i[0], cps = op.i[6] > 0 ? op.i[6] : C;
-      if (C <= 0 || op.i[1] <= 0 || cps <= 0 || C % cps != 0) return bad("DDIM step needs C > 0, inner > 0, C % channels-per-sample == 0");
-      if (op.i[2] < 0 || op.i[2] > cps || op.i[5] < 0 || op.i[5] > 3) return bad("DDIM step: guided channels / mode");
-      if (op.i[5] == 3) {      // DDIM inversion (DDIMSampler.encode): out = f0 x + f1 e, nothing else
-        if (op.i[7] != 0 || op.i[8] != 0 || op.i[9] != 0) return bad("DDIM step: mode 3 (inversion) has no mask blend i[7], no x0 restriction i[8] and no classifier-guidance term i[9]");
-        if (op.i[4] != T2V_F32) return bad("DDIM step: mode 3 (inversion) needs an fp32 x");
-        if (op.i[2] != 0 && op.i[2] != cps) return bad("DDIM step: mode 3 (inversion) combines the guidance over all channels (i[2] = channels per sample) or not at all (0)");
-        if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return bad("null DDIM step pointer (mode 3 reads x p[0] and the eps pair p[1] and writes p[3])");
-        return 0;
-      }
-      if (op.i[8] < 0 || op.i[8] > 3) return bad("DDIM step: x0 restriction i[8] must be 0 (none), 1 (clamp), 2 (threshold) or 3 (measure pass)");
-      if (op.i[9] != 0 && op.i[9] != 1) return bad("DDIM step: classifier-guidance flag i[9] must be 0 or 1");
-      if (op.p[0] == 0 || op.p[1] == 0 || (op.p[3] == 0 && op.i[8] != 3)) return bad("null DDIM step pointer");
-      if (op.i[7] != 0 && op.i[7] != 1) return bad("DDIM step: blend flag i[7] must be 0 or 1");
-      if (op.i[5] == 2) {      // UniPC's thresholded data prediction: a measure record and an apply record, nothing else
-        if (op.i[8] != 2 && op.i[8] != 3) return bad("DDIM step: mode 2 (thresholded data prediction) is the measure pass i[8] = 3 or the apply pass i[8] = 2; the clamp i[8] = 1 and the plain prediction (a LINCOMB) are not records of it");
-        if (op.i[7] != 0 || op.i[9] != 0) return bad("DDIM step: mode 2 has no mask blend i[7] and no classifier-guidance term i[9]");
-        if (op.i[4] != T2V_F32) return bad("DDIM step: mode 2 needs an fp32 x");
-        if (op.i[2] != 0 && op.i[2] != cps) return bad("DDIM step: mode 2 combines the guidance over all channels (i[2] = channels per sample) or not at all (0)");
-        if (op.p[7] == 0) return bad("DDIM step: mode 2 needs the threshold table p[7]");
-        if ((int64_t)cps * op.i[1] > (int64_t)16777216) return bad("DDIM step: mode 2 ranks at most 16 777 216 elements per sample (torch.quantile's limit)");
-        if (op.i[8] == 3 && !(op.f[6] > 0.f && op.f[6] <= 1.f)) return bad("DDIM step: the measure pass i[8] = 3 needs a quantile f[6] in (0, 1]");
-        return 0;
-      }
-      if (op.i[8] != 0 || op.i[9] != 0) {
-        if (op.i[5] != 0) return bad("DDIM step: the x0 restriction i[8] and the classifier-guidance term i[9] exist for mode 0 (DDIM_Gaussian) only");
-        if (op.i[7] != 0) return bad("DDIM step: the x0 restriction i[8] / classifier-guidance term i[9] and the mask blend i[7] exclude each other");
-        if (op.i[4] != T2V_F32) return bad("DDIM step: the x0 restriction i[8] and the classifier-guidance term i[9] need an fp32 x");
-        if ((op.i[8] == 2 || op.i[8] == 3) && op.p[7] == 0) return bad("DDIM step: the x0 threshold i[8] = 2 | 3 needs the threshold table p[7]");
-        if (op.i[9] == 1 && op.p[8] == 0) return bad("DDIM step: the classifier-guidance term i[9] needs the gradient p[8]");
-        if (op.i[8] == 1 && !(op.f[6] >= 0.f)) return bad("DDIM step: the x0 clamp i[8] = 1 needs a bound f[6] >= 0");
-        if (op.i[8] == 3) {
-          if ((int64_t)cps * op.i[1] > (int64_t)16777216) return bad("DDIM step: the measure pass i[8] = 3 ranks at most 16 777 216 elements per sample (torch.quantile's limit)");
-          if (!(op.f[6] > 0.f && op.f[6] <= 1.f)) return bad("DDIM step: the measure pass i[8] = 3 needs a percentile f[6] in (0, 1]");
-        }
-      }
-      if (op.i[7] == 1) {
-        if (op.i[5] != 1) return bad("DDIM step: the mask blend i[7] exists for mode 1 (LDM DDIM) only");
-        if (op.i[4] != T2V_F32) return bad("DDIM step: the mask blend i[7] needs an fp32 x");
-        if (op.p[4] == 0 || op.p[5] == 0) return bad("DDIM step: the mask blend i[7] needs the known x0 p[4] and the mask p[5]");
-        if (op.p[6] == 0 && op.f[7] != 0.f) return bad("DDIM step: the mask blend i[7] needs the q-noise p[6] unless f[7] == 0");
-      }
-      return 0;
+      const t2v_ddim_class c = t2v_ddim_classify(op);
+      return c.form == T2V_DDIM_MALFORMED ? bad(c.why) : 0;
     }
     case T2V_OP_MEMSET:
       if (op.p[0] == 0) return bad("null memset pointer");
@@ -302,6 +261,7 @@ int validate_op(const t2v_op& op, int idx) {
       return 0;
     case T2V_OP_RESAMPLE: {
       const int out = op.i[4], axis = op.i[5], form = op.i[7], ld = op.i[8];
+      const t2v_resample_grid grid = t2v_resample_grid_of(op);
       if (op.i[9] != 0 && op.i[9] != 1) return bad("resample: mode i[9] must be 0 (uint8 pass) or 1 (float bicubic)");
       if (op.i[9] == 1) {          // float bicubic: planes [P, H, W] -> fp32 [P, Ho, Wo], one launch
         const int Wo = op.i[10];
@@ -313,7 +273,7 @@ int validate_op(const t2v_op& op, int idx) {
         if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[3] == 0) return bad("null bicubic resample pointer (source, destination, weights, indices)");
         if ((long)op.i[1] * op.i[2] > (1L << 28) || (long)out * Wo > (1L << 28)) return bad("bicubic resample: image too large");
         // one workgroup of 256 threads per (plane, output row, tile of 256 columns): HIP refuses a launch of 2^32 threads or more
-        if ((long)op.i[0] * out * ((Wo + 255) / 256) > 0xffffffL) return bad("bicubic resample: too many rows for one launch (planes x rows x tiles of 256 columns <= 2^24 - 1)");
+        if (grid.rows * grid.tiles > 0xffffffL) return bad("bicubic resample: too many rows for one launch (planes x rows x tiles of 256 columns <= 2^24 - 1)");
         return 0;
       }
       if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[2] <= 0 || out <= 0 || op.i[6] <= 0) return bad("resample: images, rows, columns, output size and table row length must be positive");
@@ -324,10 +284,8 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[3] == 0) return bad("null resample pointer (source, destination, coefficients, bounds)");
       const long row_px = axis == 0 ? out : op.i[2];
       if (row_px > (1 << 28)) return bad("resample: row too long");
-      // units of a row: a pixel (token forms), 4 pixels (horizontal, uint8) or 4 bytes (vertical, uint8) — 256 per workgroup
-      const long tiles = ((form != 0 ? row_px : (axis == 0 ? (row_px + 3) / 4 : (row_px * 3 + 3) / 4)) + 255) / 256;
       // one workgroup of 256 threads per (row, tile): HIP refuses a launch of 2^32 threads or more
-      if ((long)op.i[0] * (axis == 0 ? op.i[1] : out) * tiles > 0xffffffL) return bad("resample: too many rows for one launch (rows x tiles of 256 units <= 2^24 - 1)");
+      if (grid.rows * grid.tiles > 0xffffffL) return bad("resample: too many rows for one launch (rows x tiles of 256 units <= 2^24 - 1)");
       return 0;
     }
     case T2V_OP_DEPTH_TOKENS:
@@ -530,8 +488,9 @@ int ff_min_m() {
 // a resharding, the K / V^T operands that share numbers with the fused GroupNorm's output) is an input.
 unsigned output_slots(const t2v_op& op) {
   auto bits = [](std::initializer_list<int> l) { unsigned m = 0; for (int k : l) m |= 1u << k; return m; };
-  if (op.kind == T2V_OP_DDIM_STEP && op.i[8] == 3) return bits({7});      // the measure pass writes the threshold table and nothing else
-  if (op.kind == T2V_OP_DDIM_STEP && op.i[5] == 3) return bits({3, 4});   // the inversion step: p[4] is a second destination (the kept intermediate), not the blend's known x0
+  const t2v_ddim_form ddim = op.kind == T2V_OP_DDIM_STEP ? t2v_ddim_classify(op).form : T2V_DDIM_MALFORMED;
+  if (ddim == T2V_DDIM_MEASURE) return bits({7});      // the measure pass writes the threshold table and nothing else
+  if (ddim == T2V_DDIM_INVERT) return bits({3, 4});    // the inversion step: p[4] is a second destination (the kept intermediate), not the blend's known x0
   switch (op.kind) {
     case T2V_OP_GEMM: return bits({5, 6, 7, 10, 11}) | (op.i[16] == T2V_EPI_GN ? bits({9}) : 0u);
     case T2V_OP_GROUPNORM: return bits({3, 4, 5, 7, 8});

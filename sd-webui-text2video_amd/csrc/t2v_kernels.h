@@ -323,6 +323,15 @@ hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_lincomb(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_embed_rows(const t2v_op& op, hipStream_t s);
 
+// What a T2V_OP_DDIM_STEP record is (elementwise.hip): validation, the output slots and the launcher all ask here.  x0_form: which x0
+// the measure pass ranks (0 the DDIM_Gaussian step, 1 UniPC's data prediction); why: the reason a T2V_DDIM_MALFORMED record is refused
+enum t2v_ddim_form { T2V_DDIM_MALFORMED, T2V_DDIM_PLAIN, T2V_DDIM_BLEND, T2V_DDIM_RESTRICT, T2V_DDIM_MEASURE, T2V_DDIM_THRESHOLD, T2V_DDIM_INVERT };
+struct t2v_ddim_class { t2v_ddim_form form; int x0_form; const char* why; };
+t2v_ddim_class t2v_ddim_classify(const t2v_op& op);
+// The launch grid of a T2V_OP_RESAMPLE record (elementwise.hip), uint8 pass or bicubic: rows x tiles workgroups of 256 units
+struct t2v_resample_grid { long rows, units, tiles; };
+t2v_resample_grid t2v_resample_grid_of(const t2v_op& op);
+
 // x * sigmoid(x) as 5 VALU instructions (v_exp_f32 and v_rcp_f32 are 1-ulp; an IEEE divide would be ~12 more)
 __device__ __forceinline__ float t2v_silu(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f));

@@ -1010,7 +1010,7 @@ _LOWERED_EPI = [
     (8, 'tconv', 1, 0, 0, 0, 'f32', 0, 1, 0, 1, 0, 'straddle', 0),
 ]
 # ... of the requestable lattice (tests/geometry_lattice.py; profiles/geometry_paths.txt names a witness program for each): other frame counts
-# and latents put the same fused norms on the other tiles and make rows and columns ragged.  gn_seam is t2v_kernels.h:903-913's class (an
+# and latents put the same fused norms on the other tiles and make rows and columns ragged.  gn_seam is t2v_kernels.h:912-922's class (an
 # instance of half a tile, whole tiles, or a tile that straddles two instances); gn_chunked is gemm.hip:361 / gemm2.hip:519
 # t2v_launch_coresident's (more tiles than the device holds at once: the launch is cut into row chunks)
 _LOWERED_EPI += [

@@ -12,7 +12,7 @@ intervals (`Rect.intervals`, `overlap`); the bounding intervals are only the fas
 
 Reads a kernel performs and discards:
   * the residual prefetch of the GEMM epilogue loads rows / columns outside the matrix from the FIRST element of the residual
-    (csrc/t2v_kernels.h:409-421, "park on the first element"): inside the declared rectangle, nothing to add;
+    (csrc/t2v_kernels.h:418-430, "park on the first element"): inside the declared rectangle, nothing to add;
   * the large-tile GEMM's operand DMA parks rows past M / N and the padding taps of the convolution gathers on the library's own zero
     page (csrc/gemm2.hip:74-80), not on the arena: nothing to add;
   * T2V_EPI_XATTN reads the V^T rows up to the key count rounded up to 32 ("finite beyond i[25]", include/t2v_hip.h:136-140): declared.
@@ -243,7 +243,7 @@ def _gemm(op, b: _B):
         b.mat(0, "r", nb * (I[8] + (2 if I[23] else 0)) * I[9], I[10], lda, 2, "A clips [nb, F (+2 halo), HW, Cin]")
     b.mat(1, "r", N, K, ldw, 2, "W")
     # split-K without tickets: the GEMM launch stores fp32 slabs and a reduction launch folds them and applies the whole epilogue — bias,
-    # row bias, residual, the outputs and a fused GroupNorm belong to that second launch (csrc/t2v_kernels.h:413,445: `p.splitk == 1 &&`
+    # row bias, residual, the outputs and a fused GroupNorm belong to that second launch (csrc/t2v_kernels.h:423,455: `p.splitk == 1 &&`
     # guards the residual and bias loads of the GEMM's own epilogue; include/t2v_hip.h:199-201)
     two = split > 1 and (ln or op.p[7].space == "null")
     if two:

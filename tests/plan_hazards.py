@@ -164,9 +164,9 @@ def _copy_in_place(op, w, r):
 
 INPLACE_CLASSES = [
     ("gemm residual == out (fp32, same ld, no wrap)", _gemm_res_is_out,
-     "csrc/t2v_kernels.h:414-421 res_load and :447-451 the store: row mt + rrow + 8 i, columns n .. n + 3 of the same lane"),
+     "csrc/t2v_kernels.h:423-430 res_load and :456-460 the store: row mt + rrow + 8 i, columns n .. n + 3 of the same lane"),
     ("copy2d src == dst (same ld and dtype, no low-order image)", _copy_in_place,
-     "csrc/elementwise.hip:84-103 copy2d_kernel: a thread loads its 4 elements s[0..3] into registers, then stores d[0..3] at the same place"),
+     "csrc/elementwise.hip:93-122 copy2d_kernel: a thread loads its 4 elements s[0..3] into registers, then stores d[0..3] at the same place"),
 ]
 
 
@@ -207,7 +207,7 @@ def output_slots(op):
 
 
 def _ff_shape(ops, k, A, min_m) -> bool:
-    """The record-shape conditions of ff_pair (csrc/executor.hip:498-511), shared by both models."""
+    """The record-shape conditions of ff_pair (csrc/executor.hip:732-744), shared by both models."""
     if k + 1 >= len(ops):
         return False
     a, b = ops[k], ops[k + 1]

@@ -59,7 +59,7 @@ def _split_of(I, K):
 def gemm_keys(op):
     """The keys of a GEMM record, one per launch.  Without split-K, or with the fold in the GEMM's last-arriving workgroups (tickets), the
     record is one launch.  With a reduction launch it is two, and they share no code: the GEMM kernel stores its slab and skips every
-    epilogue (t2v_kernels.h:453 `if (p.splitk > 1)` in t2v_epilogue_rows, gemm2.hip:491 t2v_store_splitk_slab for GEGLU), and the reduction
+    epilogue (t2v_kernels.h:462 `if (p.splitk > 1)` in t2v_epilogue_rows, gemm2.hip:491 t2v_store_splitk_slab for GEGLU), and the reduction
     — splitk_reduce_kernel (gemm.hip:309) or splitk_gn_kernel (norm.hip:538) — reads slabs whatever tile and gather wrote them.  So the
     first key holds the tile, the gather and the raggedness with the epilogue fields blank, the second the epilogue fields alone."""
     I, P = op.i, op.p
@@ -67,50 +67,50 @@ def gemm_keys(op):
     plain = gather == L.GATHER_PLAIN
     tile = I[22]
     geo = L.GEMM_TILES.get(tile)
-    # executor.hip:454 launch_op: a gemm2 tile runs gemm2.hip only for K % 64 == 0 and not the C8 stem; everything else is gemm.hip's kernel
+    # executor.hip:432 launch_op: a gemm2 tile runs gemm2.hip only for K % 64 == 0 and not the C8 stem; everything else is gemm.hip's kernel
     gemm2 = geo is not None and geo.has(L.TILE_GEMM2) and (epi == L.EPI_TATTN or (gather != L.GATHER_CONV3X3_C8 and K % 64 == 0))
     kernel = tile if gemm2 else 0
     bm = L.GEMM_TILES[kernel].bm
     bn = L.GEMM_TILES[kernel].bn if gemm2 else L.tile0_bn(N)          # gemm.hip:422 t2v_launch_gemm: 128x64 when t2v_tile0_narrow(N)
-    ln = I[8] if plain and epi != L.EPI_TATTN and I[8] in (1, 2) else 0          # executor.hip:436 ln_any
+    ln = I[8] if plain and epi != L.EPI_TATTN and I[8] in (1, 2) else 0          # executor.hip:414 ln_any
     split = 1 if epi in (L.EPI_TATTN, L.EPI_XATTN, L.EPI_STATS) or ln else _split_of(I, K)
     gn = epi == L.EPI_GN
     fold = "-"
     if split > 1:
-        # executor.hip:437 p.tickets = p[7]; t2v_kernels.h:239: kept only for the plain epilogue, <= T2V_SYNC_INTS tiles, no GroupNorm behind it;
+        # executor.hip:415 p.tickets = p[7]; t2v_kernels.h:239: kept only for the plain epilogue, <= T2V_SYNC_INTS tiles, no GroupNorm behind it;
         # gemm.hip:431 / gemm2.hip:595: otherwise the reduction launch, with the GroupNorm in it when gn_out is set
         tiles = -(-M // bm) * -(-N // bn)
         fold = "tickets" if (_has(P[7]) and epi == L.EPI_NONE and tiles <= L.SYNC_INTS) else "reduce+gn" if gn else "reduce"
     slab = fold.startswith("reduce")
-    wrap = "i30" if I[30] > 0 else "i12" if (plain and epi != L.EPI_TATTN and I[12] > 0) else "-"      # executor.hip:410-411
+    wrap = "i30" if I[30] > 0 else "i12" if (plain and epi != L.EPI_TATTN and I[12] > 0) else "-"      # executor.hip:388-389
     epilogue = [
-        ("epi", epi if not gn else L.EPI_NONE),                         # executor.hip:386-398, 421, 429; gemm.hip:418, gemm2.hip:538
-        ("out", I[17]),                                                 # executor.hip:385 out_f32; gemm.hip:68, t2v_kernels.h:945, norm.hip:562
-        ("act", I[18]),                                                 # gemm.hip:51-53; t2v_kernels.h:462-463
-        ("bias", _has(P[2])),                                           # gemm.hip:38; t2v_kernels.h:446; norm.hip:548
-        ("bias_m", int(I[20] != 0) if _has(P[2]) else 0),               # t2v_kernels.h:460
-        ("rowbias", _has(P[3]) if not ln else 0),                       # gemm.hip:47; norm.hip:559; executor.hip:440 (p[3] is gamma | beta under ln_any)
-        ("res", _has(P[4])),                                            # gemm.hip:56; t2v_kernels.h:547; norm.hip:560
-        ("res_wrap", wrap if _has(P[4]) else "-"),                      # gemm.hip:57; t2v_kernels.h:420
-        ("out_lo", int(plain and I[11] == 1)),                          # executor.hip:409; gemm.hip:68
+        ("epi", epi if not gn else L.EPI_NONE),                         # executor.hip:364-376, 399, 407; gemm.hip:418, gemm2.hip:538
+        ("out", I[17]),                                                 # executor.hip:363 out_f32; gemm.hip:68, t2v_kernels.h:954, norm.hip:562
+        ("act", I[18]),                                                 # gemm.hip:51-53; t2v_kernels.h:471-472
+        ("bias", _has(P[2])),                                           # gemm.hip:38; t2v_kernels.h:455; norm.hip:548
+        ("bias_m", int(I[20] != 0) if _has(P[2]) else 0),               # t2v_kernels.h:469
+        ("rowbias", _has(P[3]) if not ln else 0),                       # gemm.hip:47; norm.hip:559; executor.hip:418 (p[3] is gamma | beta under ln_any)
+        ("res", _has(P[4])),                                            # gemm.hip:56; t2v_kernels.h:556; norm.hip:560
+        ("res_wrap", wrap if _has(P[4]) else "-"),                      # gemm.hip:57; t2v_kernels.h:429
+        ("out_lo", int(plain and I[11] == 1)),                          # executor.hip:387; gemm.hip:68
     ]
     main = [
         ("kind", "GEMM"),
-        ("tile", kernel),                                               # executor.hip:419 / 454; gemm2.hip:787 t2v_launch_gemm2 switch
+        ("tile", kernel),                                               # executor.hip:397 / 432; gemm2.hip:787 t2v_launch_gemm2 switch
         ("tile0_bn", bn if kernel == 0 else 0),                         # gemm.hip:422-428
         ("gather", gather),                                             # gemm.hip:397 launch_tile switch; gemm2.hip:549 launch_cfg switch
-        ("stride", I[11] if gather in (L.GATHER_CONV3X3, L.GATHER_CONV3X3_C8) else 0),      # executor.hip:383; gemm.hip:182 / gemm2.hip:127 tap arithmetic
+        ("stride", I[11] if gather in (L.GATHER_CONV3X3, L.GATHER_CONV3X3_C8) else 0),      # executor.hip:361; gemm.hip:182 / gemm2.hip:127 tap arithmetic
         ("up", int(I[12] != 0) if gather == L.GATHER_CONV3X3 else 0),   # gemm2.hip:582 G_CONV_UP instantiation
-        ("i23", int(I[23] != 0)),                                       # executor.hip:408 p.halo; gemm.hip:147 / 182, gemm2.hip:127 / 141
-        ("i13", int(plain and epi != L.EPI_TATTN and I[13] > 0)),       # executor.hip:410 a_wrap; gemm.hip:137, gemm2.hip:116
-        ("ln", ln),                                                     # executor.hip:438-451; gemm2.hip:564-575 XE_LN / XE_LNX
-        ("fold", "slab" if slab else fold),                             # gemm.hip:346 / gemm2.hip:525 grid.y; t2v_kernels.h:233, 453
-        ("k_tail", int(K % 64 != 0)),                                   # executor.hip:454; gemm.hip K tail of the last k-tile
-        ("m_ragged", int(M % bm != 0)),                                 # the m < p.M guards of every tail (t2v_kernels.h:452, 943)
-        ("n_ragged", int(N % bn != 0)),                                 # the n < p.N guards (t2v_kernels.h:444, 939)
+        ("i23", int(I[23] != 0)),                                       # executor.hip:386 p.halo; gemm.hip:147 / 182, gemm2.hip:127 / 141
+        ("i13", int(plain and epi != L.EPI_TATTN and I[13] > 0)),       # executor.hip:388 a_wrap; gemm.hip:137, gemm2.hip:116
+        ("ln", ln),                                                     # executor.hip:416-429; gemm2.hip:564-575 XE_LN / XE_LNX
+        ("fold", "slab" if slab else fold),                             # gemm.hip:346 / gemm2.hip:525 grid.y; t2v_kernels.h:233, 462
+        ("k_tail", int(K % 64 != 0)),                                   # executor.hip:432; gemm.hip K tail of the last k-tile
+        ("m_ragged", int(M % bm != 0)),                                 # the m < p.M guards of every tail (t2v_kernels.h:461, 952)
+        ("n_ragged", int(N % bn != 0)),                                 # the n < p.N guards (t2v_kernels.h:453, 948)
     ]
     if epi == L.EPI_XATTN:
-        # executor.hip:433: keys per sample and their padded count — t2v_epilogue_xattn walks key blocks of 32 up to xa_lcp
+        # executor.hip:411: keys per sample and their padded count — t2v_epilogue_xattn walks key blocks of 32 up to xa_lcp
         main += [("xa_ragged", int(I[25] % 32 != 0)), ("xa_blocks", min(-(-I[26] // 32), 4))]
     if ln == 2:
         cap = min(L.GEMM_TILES[kernel].per_cu * DEVICE_CUS, L.GN_PART_BYTES // (bm * 16))        # program.py:559
@@ -118,9 +118,9 @@ def gemm_keys(op):
     norm = []
     if gn:
         rows = I[24]
-        norm = [("gn_silu", int(I[26] != 0)),                          # executor.hip:394; norm.hip:794 dispatch_bool
-                ("gn_lo", int(I[27] != 0)),                            # executor.hip:394 gn_lo
-                ("i29", int(I[29] != 0))]                              # executor.hip:395 gn_store_out; t2v_kernels.h:932; norm.hip:561
+        norm = [("gn_silu", int(I[26] != 0)),                          # executor.hip:372; norm.hip:794 dispatch_bool
+                ("gn_lo", int(I[27] != 0)),                            # executor.hip:372 gn_lo
+                ("i29", int(I[29] != 0))]                              # executor.hip:373 gn_store_out; t2v_kernels.h:941; norm.hip:561
     if slab:
         second = [("kind", "GEMM.reduce+gn" if gn else "GEMM.reduce")] + epilogue + norm
         if gn:
@@ -128,7 +128,7 @@ def gemm_keys(op):
             second += [("kr", coop_chunking(I[24], M // I[24], N // 8, DEVICE_CUS, 1 << 30, (1, 2, 4, 8, 12, 16, 20))[0])]
         return [tuple(main), tuple(second)]
     if gn:
-        # t2v_kernels.h:903-913, 957: a tile meets one instance (whole), two (straddle: slot 1 is live) or — half a tile — two whole ones
+        # t2v_kernels.h:912-922, 966: a tile meets one instance (whole), two (straddle: slot 1 is live) or — half a tile — two whole ones
         norm += [("gn_seam", "half" if 2 * rows == bm else "whole" if rows % bm == 0 else "straddle")]
         # gemm.hip:361 / gemm2.hip:519 t2v_launch_coresident (t2v_kernels.h:214): more tiles than the device holds -> row chunks.  The capacity
         # is the occupancy API's on the device; the lowering's own bound (program.py:669 per_cu x CUs, the record region) stands in for it here
@@ -235,24 +235,24 @@ def relpos_key(op):
 def elementwise_key(op):
     I, P, k = op.i, op.p, op.kind
     name = ("kind", KIND_NAMES[k])
-    if k == L.OP_NCTHW_TO_CL:          # elementwise.hip:1106-1118
+    if k == L.OP_NCTHW_TO_CL:          # elementwise.hip:1164-1175
         return (name, ("in", I[5]), ("bsrc", int(0 < I[6] < I[0])), ("second", _has(P[2])), ("lo", int(I[7] != 0 and I[4] >= 2 * I[1])))
-    if k == L.OP_CL_TO_NCTHW:          # elementwise.hip:1126
+    if k == L.OP_CL_TO_NCTHW:          # elementwise.hip:1177-1186
         return (name, ("out", I[5]))
-    if k == L.OP_TIME_EMBED:           # elementwise.hip:1242: one kernel
+    if k == L.OP_TIME_EMBED:           # elementwise.hip:1298-1304: one kernel
         return (name,)
-    if k == L.OP_COPY2D:               # elementwise.hip:1255-1266
+    if k == L.OP_COPY2D:               # elementwise.hip:1306-1321
         return (name, ("src", I[4]), ("dst", I[5]), ("act", I[6]), ("second", int(_has(P[2]) and I[4] == L.F32 and I[5] == L.F16)))
     if k == L.OP_SOFTMAX:              # attention.hip:1282: one kernel; the column loop runs more than once past 256 columns
         return (name, ("cols_gt_256", int(I[1] > 256)))
-    if k == L.OP_DDIM_STEP:            # elementwise.hip:1317-1390
+    if k == L.OP_DDIM_STEP:            # elementwise.hip:1368-1485
         return (name, ("eps", I[3]), ("x", I[4]), ("mode", I[5]), ("guided", int(I[2] != 0)), ("cps", int(0 < I[6] < I[0])), ("blend", int(I[7] != 0)),
                 ("i8", I[8]), ("i9", int(I[9] != 0)))
-    if k == L.OP_LINCOMB:              # elementwise.hip:1394-1403
+    if k == L.OP_LINCOMB:              # elementwise.hip:1487-1498
         return (name, ("terms", I[1]), ("out", I[2]), ("f32_terms", tuple(int(I[3 + t] == L.F32) for t in range(I[1]))))
-    if k == L.OP_DEPTH_TOKENS:         # elementwise.hip:1196-1205
+    if k == L.OP_DEPTH_TOKENS:         # elementwise.hip:1254-1265
         return (name, ("in", I[3]), ("norm", int(I[4] != 0)))
-    assert k == L.OP_AVGPOOL2          # elementwise.hip:1210: one kernel, either output optional
+    assert k == L.OP_AVGPOOL2          # elementwise.hip:1267-1273: one kernel, either output optional
     return (name, ("f32_out", _has(P[1])), ("f16_out", _has(P[2])))
 
 
