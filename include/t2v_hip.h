@@ -37,6 +37,9 @@ extern "C" {
                                library refuses, records with i[5] in {0, 1} are validated and run as before;
                                still 11: DDIM_STEP i[5] = 3 (the DDIM inversion step of DDIMSampler.encode, with the optional second destination p[4]) — a mode
                                value that every earlier library refuses, records with i[5] in {0, 1, 2} are validated and run as before;
+                               still 11: DDIM_STEP i[5] = 4 (the DDIM_Gaussian step followed by the keyframe blend of the legacy img2vid loop, with p[4..6], f[6..7]
+                               and the threshold's bits in i[10]) — a mode value that every earlier library refuses, records with i[5] in {0, 1, 2, 3} are
+                               validated and run as before;
                                still 11: T2V_OP_EMPHASIS (a new kind: no existing record changes, and a library without it refuses the record as an unknown op kind) and
                                ATTENTION i[19..21] / p[4..5] (a second role; additive on fields every earlier record leaves zero);
                                still 11: T2V_OP_FINGERPRINT (a new kind, stand-alone: 64-bit fingerprints of a table of byte ranges; no existing record changes);
@@ -341,6 +344,18 @@ enum t2v_gather {
  *        p: 0 x fp32, 1 eps pair (fp16 or fp32), 3 out fp32, 4 (optional) a second fp32 destination that receives the same values — the
  *           intermediate a caller keeps, at no extra launch; p[2] is not read.  Four elements per thread with 128-bit accesses when
  *           every pointer is 16-byte aligned, one element per thread otherwise.
+ *      mode 4 (DDIM_Gaussian with the keyframe blend of the legacy img2vid loop, modelscope/t2v_model.py:1555-1562; fp32 x, the eps pair fp16
+ *        or fp32, i[2] as in mode 0, i[7] = i[8] = i[9] = 0 or refused): the mode-0 update x1 — bit for bit what the mode-0 record gives
+ *        on the same operands, eta noise included — and, in the same launch,
+ *          bin = mask <= v ? 0 : 1  (fp32 comparison; a NaN weight compares false: free);   known = f6 * orig + f7 * n;
+ *          out = known * (1 - bin) + x1 * bin
+ *        in fp32 with every operation rounded by itself (both products, then their sum, twice).  Arithmetic, not a select: a non-finite
+ *        value on either side reaches out, as in torch.  Weight 1 means free, weight <= v means reset to the re-noised original.
+ *        f: 0..5 as mode 0, 6 sqrt_alphas_cumprod[t'], 7 sqrt_one_minus_alphas_cumprod[t'] (t' = the next step's timestep)
+ *        i: 10 the bits of the fp32 threshold v (a word that every other DDIM_STEP record leaves zero)
+ *        p: 0 x, 1 eps pair, 2 eta noise, 3 out, 4 the original latent, 5 the mask, 6 the blend noise n (may be null only when f7 == 0;
+ *           read whenever it is given) — p[4..6] fp32, dense, shaped like x [samples, channels, inner].  Four elements per thread with
+ *           128-bit accesses when every pointer that is read is 16-byte aligned, one element per thread otherwise.
  * LINCOMB: i: 0 n elements, 1 n terms (<= 6), 2 out dtype, 3..8 term dtypes; f: 0..5 coefficients;
  *      p: 0..5 terms, 6 out
  * MEMSET: i: 0 bytes (lo), 1 bytes (hi); p: 0 dst

@@ -15,6 +15,7 @@
 //                     gaussian_sampler.py:110-120) and / or the classifier-guidance term (get_eps, :199-211); its x0 form 1 is the apply
 //                     pass of UniPC's thresholded data prediction (uni_pc/uni_pc.py:351-364), clamp(x0, -s, s) / s
 //     ddim_measure    the quantile of |x0| per video, of either x0 form: torch.quantile on fp32, exactly, by a radix select in one workgroup
+//     ddim_keyframe   the DDIM_Gaussian step and the keyframe blend of the legacy img2vid loop (modelscope/t2v_model.py:1555-1562)
 //     ddim_invert     the DDIM inversion step of DDIMSampler.encode (samplers/ddim/sampler.py:242-254), four elements per thread
 //   resample      one pass of Pillow's 8-bit Lanczos resize of the vid2vid / inpainting input, bit-exact
 //                 (process_modelscope.py:116-120, 174-178); the last pass can write the VAE encoder's tokens
@@ -316,6 +317,89 @@ __global__ __launch_bounds__(256) void ddim_invert_kernel(const DdimParams p, fl
       for (int k = 0; k < 4; ++k) o[k] = ddim_invert_of(p, x[k], (float)y[k], (float)u[k], GUIDED);
       reinterpret_cast<f32x4*>(v.out)[q] = o;
       if (keep != nullptr) reinterpret_cast<f32x4*>(keep)[q] = o;
+    }
+    const long tail = (nvec << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < 4 && tail < v.total) one(tail);
+  } else {
+    for (long idx = first; idx < v.total; idx += stride) one(idx);
+  }
+}
+
+// ---- mode 4: the DDIM_Gaussian step with the keyframe blend of the legacy img2vid loop (modelscope/t2v_model.py:1555-1562) -------------
+// After the update, elements whose mask weight is <= v are reset to the re-noised original latent: bin = mask <= v ? 0 : 1 (a NaN
+// weight compares false: free), known = f6 orig + f7 n, out = known (1 - bin) + x1 bin.
+struct DdimKeyframe {
+  const float* orig; const float* mask; const float* qnoise;     // p[4..6], fp32 and dense like x; qnoise may be null (f7 == 0)
+  float sqrt_ac, sqrt_1mac, v;                                   // f[6], f[7], the fp32 threshold (the bits of i[10])
+};
+
+// The update of the plain mode-0 step, so that a free element carries the plain record's bits.  ddim_step_kernel leaves contraction to
+// the compiler, and what the compiler fuses depends on the code around an expression (the four-element loop below fused other products
+// than the plain kernel): here the operations are pinned — the fused multiply-adds of the plain kernel's mode-0 code written as such
+// (the guidance combine, x0, the eta noise), every other operation rounded by itself.  tests/test_gpu_keyframe.py holds the two
+// kernels together, bit for bit.  u is read only where guided, n only where the step has eta noise.
+__device__ __forceinline__ float ddim_gaussian_of(const DdimParams& p, float x, float y, float u, bool guided, float n, bool noisy) {
+#pragma clang fp contract(off)
+  float o = y;
+  if (guided) o = __builtin_fmaf(p.gscale, y - u, u);
+  const float bo = p.a_recipm1 * o, ax = p.a_recip * x;
+  const float x0 = __builtin_fmaf(p.a_recip, x, -bo);
+  const float eps = (ax - x0) / p.a_recipm1;
+  const float m0 = p.sqrt_aprev * x0, m1 = p.dir_coef * eps;
+  float xn = m0 + m1;
+  if (noisy) xn = __builtin_fmaf(p.sigma, n, xn);
+  return xn;
+}
+
+// The blend: arithmetic, not a select (a non-finite value on either side propagates as in torch), every operation rounded by itself
+__device__ __forceinline__ float ddim_keyframe_of(const DdimKeyframe& k, float x1, float orig, float m, float n, bool has_q) {
+#pragma clang fp contract(off)
+  const float bin = m <= k.v ? 0.f : 1.f;
+  float known = k.sqrt_ac * orig;
+  if (has_q) {
+    const float qn = k.sqrt_1mac * n;
+    known = known + qn;
+  }
+  const float held = known * (1.f - bin), kept = x1 * bin;
+  return held + kept;
+}
+
+// VEC: four elements per thread with one 128-bit access per fp32 tensor (64-bit for fp16 eps) — the launcher found every pointer that
+// is read 16-byte aligned; the total % 4 last elements are the scalar work of workgroup 0.  !VEC: one element per thread.
+template <typename TE, bool VEC>
+__global__ __launch_bounds__(256) void ddim_keyframe_kernel(const DdimParams p, const DdimKeyframe k) {
+  const DdimView<TE> v(p);
+  const bool noisy = p.noise != nullptr && p.sigma != 0.f, has_q = k.qnoise != nullptr, any_guided = p.guided != 0;
+  const long stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
+  auto one = [&](long idx) {
+    const bool guided = v.guided(idx % v.per_sample);
+    const float y = (float)v.ec[idx];
+    const float x1 = ddim_gaussian_of(p, v.xt[idx], y, guided ? (float)v.eu[idx] : y, guided, noisy ? p.noise[idx] : 0.f, noisy);
+    v.out[idx] = ddim_keyframe_of(k, x1, k.orig[idx], k.mask[idx], has_q ? k.qnoise[idx] : 0.f, has_q);
+  };
+  if constexpr (VEC) {
+    using TE4 = TE __attribute__((ext_vector_type(4)));
+    const long nvec = v.total >> 2;
+    for (long q = first; q < nvec; q += stride) {
+      const long within = (q << 2) % v.per_sample;     // (a vector may straddle the guided channels' end or a sample's: per element below)
+      const f32x4 x = reinterpret_cast<const f32x4*>(v.xt)[q];
+      const TE4 y = reinterpret_cast<const TE4*>(v.ec)[q];
+      TE4 u = y;
+      if (any_guided) u = reinterpret_cast<const TE4*>(v.eu)[q];
+      f32x4 n = {0.f, 0.f, 0.f, 0.f}, qn = n;
+      if (noisy) n = reinterpret_cast<const f32x4*>(p.noise)[q];
+      if (has_q) qn = reinterpret_cast<const f32x4*>(k.qnoise)[q];
+      const f32x4 og = reinterpret_cast<const f32x4*>(k.orig)[q];
+      const f32x4 m = reinterpret_cast<const f32x4*>(k.mask)[q];
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        long w = within + e;
+        if (w >= v.per_sample) w -= v.per_sample;
+        const float x1 = ddim_gaussian_of(p, x[e], (float)y[e], (float)u[e], v.guided(w), n[e], noisy);
+        o[e] = ddim_keyframe_of(k, x1, og[e], m[e], qn[e], has_q);
+      }
+      reinterpret_cast<f32x4*>(v.out)[q] = o;
     }
     const long tail = (nvec << 2) + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x < 4 && tail < v.total) one(tail);
@@ -1370,13 +1454,21 @@ t2v_ddim_class t2v_ddim_classify(const t2v_op& op) {
   auto bad = [](const char* why) { return t2v_ddim_class{T2V_DDIM_MALFORMED, 0, why}; };
   const int C = op.i[0], cps = op.i[6] > 0 ? op.i[6] : C;
   if (C <= 0 || op.i[1] <= 0 || cps <= 0 || C % cps != 0) return bad("DDIM step needs C > 0, inner > 0, C % channels-per-sample == 0");
-  if (op.i[2] < 0 || op.i[2] > cps || op.i[5] < 0 || op.i[5] > 3) return bad("DDIM step: guided channels / mode");
+  if (op.i[2] < 0 || op.i[2] > cps || op.i[5] < 0 || op.i[5] > 4) return bad("DDIM step: guided channels / mode");
   if (op.i[5] == 3) {      // DDIM inversion (DDIMSampler.encode): out = f0 x + f1 e, nothing else
     if (op.i[7] != 0 || op.i[8] != 0 || op.i[9] != 0) return bad("DDIM step: mode 3 (inversion) has no mask blend i[7], no x0 restriction i[8] and no classifier-guidance term i[9]");
     if (op.i[4] != T2V_F32) return bad("DDIM step: mode 3 (inversion) needs an fp32 x");
     if (op.i[2] != 0 && op.i[2] != cps) return bad("DDIM step: mode 3 (inversion) combines the guidance over all channels (i[2] = channels per sample) or not at all (0)");
     if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return bad("null DDIM step pointer (mode 3 reads x p[0] and the eps pair p[1] and writes p[3])");
     return is(T2V_DDIM_INVERT);
+  }
+  if (op.i[5] == 4) {      // DDIM_Gaussian with the keyframe blend of the legacy img2vid loop: mode 0's update, then the blend
+    if (op.i[7] != 0 || op.i[8] != 0 || op.i[9] != 0) return bad("DDIM step: mode 4 (keyframe blend) has no mask blend flag i[7], no x0 restriction i[8] and no classifier-guidance term i[9]");
+    if (op.i[4] != T2V_F32) return bad("DDIM step: mode 4 (keyframe blend) needs an fp32 x");
+    if (op.p[0] == 0 || op.p[1] == 0 || op.p[3] == 0) return bad("null DDIM step pointer");
+    if (op.p[4] == 0 || op.p[5] == 0) return bad("DDIM step: mode 4 (keyframe blend) needs the original latent p[4] and the mask p[5]");
+    if (op.p[6] == 0 && op.f[7] != 0.f) return bad("DDIM step: mode 4 (keyframe blend) needs the blend noise p[6] unless f[7] == 0");
+    return is(T2V_DDIM_KEYFRAME);
   }
   if (op.i[8] < 0 || op.i[8] > 3) return bad("DDIM step: x0 restriction i[8] must be 0 (none), 1 (clamp), 2 (threshold) or 3 (measure pass)");
   if (op.i[9] != 0 && op.i[9] != 1) return bad("DDIM step: classifier-guidance flag i[9] must be 0 or 1");
@@ -1475,6 +1567,21 @@ hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s) {
           by_bool(vec, [&](auto vc) {
             hipLaunchKernelGGL((ddim_invert_kernel<TE, decltype(gd)::value, decltype(vc)::value>), gi, b, 0, s, p, reinterpret_cast<float*>(op.p[4]));
           });
+        });
+        break;
+      }
+      case T2V_DDIM_KEYFRAME: {                // fp32 x; p[4..6]: the original latent, the mask, the blend noise; i[10]: the threshold's bits
+        float thr;
+        __builtin_memcpy(&thr, &op.i[10], sizeof thr);
+        const DdimKeyframe k = {reinterpret_cast<const float*>(op.p[4]), reinterpret_cast<const float*>(op.p[5]),
+                                reinterpret_cast<const float*>(op.p[6]), op.f[6], op.f[7], thr};
+        // every 16-byte access of the vector path: x, out, original, mask, the conditional half, and what of the unconditional half,
+        // the eta noise and the blend noise the kernel reads
+        const uint64_t eu = p.guided != 0 ? op.p[1] + (uint64_t)total * sizeof(TE) : 0;
+        const uint64_t eta = (op.p[2] != 0 && p.sigma != 0.f) ? op.p[2] : 0;
+        const bool vec = (long)p.cps * p.inner >= 4 && ((op.p[0] | op.p[1] | op.p[3] | op.p[4] | op.p[5] | op.p[6] | eu | eta) & 15) == 0;
+        by_bool(vec, [&](auto vc) {
+          hipLaunchKernelGGL((ddim_keyframe_kernel<TE, decltype(vc)::value>), dim3(grid_for(vec ? total >> 2 : total)), b, 0, s, p, k);
         });
         break;
       }

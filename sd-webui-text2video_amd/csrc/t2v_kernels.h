@@ -325,7 +325,7 @@ hipError_t t2v_launch_embed_rows(const t2v_op& op, hipStream_t s);
 
 // What a T2V_OP_DDIM_STEP record is (elementwise.hip): validation, the output slots and the launcher all ask here.  x0_form: which x0
 // the measure pass ranks (0 the DDIM_Gaussian step, 1 UniPC's data prediction); why: the reason a T2V_DDIM_MALFORMED record is refused
-enum t2v_ddim_form { T2V_DDIM_MALFORMED, T2V_DDIM_PLAIN, T2V_DDIM_BLEND, T2V_DDIM_RESTRICT, T2V_DDIM_MEASURE, T2V_DDIM_THRESHOLD, T2V_DDIM_INVERT };
+enum t2v_ddim_form { T2V_DDIM_MALFORMED, T2V_DDIM_PLAIN, T2V_DDIM_BLEND, T2V_DDIM_RESTRICT, T2V_DDIM_MEASURE, T2V_DDIM_THRESHOLD, T2V_DDIM_INVERT, T2V_DDIM_KEYFRAME };
 struct t2v_ddim_class { t2v_ddim_form form; int x0_form; const char* why; };
 t2v_ddim_class t2v_ddim_classify(const t2v_op& op);
 // The launch grid of a T2V_OP_RESAMPLE record (elementwise.hip), uint8 pass or bicubic: rows x tiles workgroups of 256 units

@@ -167,7 +167,7 @@ class TextToVideoSynthesis(object):
     def infer_conditioned(self, c, uc, steps, frames, seed, scale, width=256, height=256, eta=0.0,
                           device=None, latents=None, strength=None, mask=None, is_vid2vid=False,
                           sampler=available_samplers[0].name, decode=True, to_host=True, _keep_sampler=False,
-                          videos: int = 1, *, clamp=None, percentile=None, unipc=None, seeds=None, inversion=None):
+                          videos: int = 1, *, clamp=None, percentile=None, unipc=None, seeds=None, inversion=None, inpaint=None):
         """Stages 2-4 of `infer` for given conditioning tensors c, uc [1, 77k, 1024].
         A batch of DIFFERENT prompts: c / uc as lists of `videos` tensors [1, 77k_v, 1024] (a single tensor beside a list = that prompt for
         every video; lists of one entry = the tensor), contexts of any lengths — still one 2*videos forward per step, the text
@@ -181,6 +181,8 @@ class TextToVideoSynthesis(object):
         `inversion` (sampler "DDIM" with is_vid2vid only; anything else raises ValueError): True (the reference's encode: scale 1, UNet labels
         t = i) or a dict with guidance_scale and / or model_timesteps ("index" | "schedule", see `DDIMSampler.encode`) — the input latents are inverted by `DDIMSampler.encode` (deterministic, structure-preserving)
         instead of noised by `stochastic_encode`; the drawn noise is not used.  Forwarded only when set (`Txt2VideoSampler.sample_loop`).
+        `inpaint` (DDIM_Gaussian only; another sampler raises ValueError): "legacy" lets `mask` hold the frames to `latents` and release them
+        along the weights — the keyframe blend of the reference's legacy loop (`GaussianDiffusion.sample`); forwarded only when set.
         Returns (frames, last_tensor): frames = list of HxWx3 uint8 BGR arrays (to_host) or a
         uint8 device tensor [F,H,W,3] RGB (to_host=False), or None when decode=False.
         `videos` > 1 (every sampler; txt2vid and vid2vid, where the ONE input clip's latents are repeated): that many independent videos of the same prompt in ONE batch — every
@@ -221,7 +223,7 @@ class TextToVideoSynthesis(object):
         x0 = self.diffusion.sample_loop(
             steps=steps, strength=strength, eta=eta, conditioning=_to(c, dev), unconditional_conditioning=_to(uc, dev),
             batch_size=videos, guidance_scale=scale, latents=latents, shape=shape, noise=noise, is_vid2vid=is_vid2vid,
-            sampler_name=sampler, mask=mask, **_restriction(clamp, percentile, unipc, inversion))
+            sampler_name=sampler, mask=mask, **_restriction(clamp, percentile, unipc, inversion, inpaint))
         self.last_tensor = x0
         if not decode:
             return None, x0
@@ -304,7 +306,8 @@ class TextToVideoSynthesis(object):
 
     def infer(self, prompt, n_prompt, steps, frames, seed, scale, width=256, height=256, eta=0.0,
               cpu_vae="GPU (half precision)", device=torch.device("cuda"), latents=None, skip_steps=0,
-              strength=0, mask=None, is_vid2vid=False, sampler=available_samplers[0].name, *, clamp=None, percentile=None, unipc=None, inversion=None):
+              strength=0, mask=None, is_vid2vid=False, sampler=available_samplers[0].name, *, clamp=None, percentile=None, unipc=None, inversion=None,
+              inpaint=None):
         vars_ = dict(prompt=prompt, n_prompt=n_prompt, steps=steps, frames=frames, seed=seed, scale=scale,
                      width=width, height=height, eta=eta, cpu_vae=cpu_vae, device=str(device),
                      skip_steps=skip_steps, strength=strength, is_vid2vid=is_vid2vid, sampler=sampler)
@@ -317,7 +320,7 @@ class TextToVideoSynthesis(object):
         c, uc = self.preprocess(prompt, n_prompt, steps)
         strength = None if (strength == 0.0 and not is_vid2vid) else strength
         frames_bgr, x0 = self.infer_conditioned(c, uc, steps, frames, seed, scale, width, height, eta, device,
-                                                latents, strength, mask, is_vid2vid, sampler, **_restriction(clamp, percentile, unipc, inversion))
+                                                latents, strength, mask, is_vid2vid, sampler, **_restriction(clamp, percentile, unipc, inversion, inpaint))
         return frames_bgr, self.last_tensor, create_infotext(vars_)
 
 
@@ -357,10 +360,11 @@ def _batch_arguments(c, uc, videos, seed, seeds):
     return c, uc, videos, seeds
 
 
-def _restriction(clamp, percentile, unipc=None, inversion=None) -> dict:
-    """The x0-restriction keywords, the UniPC options and the DDIM inversion option that are set — nothing is forwarded when none is, so a
-    call without them is what it was."""
-    return {k: v for k, v in (("clamp", clamp), ("percentile", percentile), ("unipc", unipc), ("inversion", inversion)) if v is not None}
+def _restriction(clamp, percentile, unipc=None, inversion=None, inpaint=None) -> dict:
+    """The x0-restriction keywords, the UniPC options, the DDIM inversion option and the keyframe-inpainting option that are set — nothing is
+    forwarded when none is, so a call without them is what it was."""
+    return {k: v for k, v in (("clamp", clamp), ("percentile", percentile), ("unipc", unipc), ("inversion", inversion), ("inpaint", inpaint))
+            if v is not None}
 
 
 _CPU_VAE_NOTED = False
@@ -402,6 +406,7 @@ def process_modelscope(args_dict: dict, extra_args=None):
                    clamp, percentile,                                         # x0 restriction of DDIM_Gaussian (gaussian_sampler.py:110-120), below
                    unipc,                                                     # solver options of UniPC (uni_pc/uni_pc.py:314-343), below
                    inversion,                                                 # vid2vid through DDIM inversion (ddim/sampler.py:222-267), below
+                   inpaint,                                                   # img2vid keyframe blend of the legacy loop (t2v_model.py:1555-1562), below
                    enable_emphasis, comma_padding_backtrack,                  # webui's opts of the prompt syntax (clip_hardcode.py:153,203)
                    do_vid2vid, vid2vid_frames, strength,                      # :80-147
                    inpainting_frames, inpainting_image, inpainting_weights,   # :170-217
@@ -419,6 +424,10 @@ def process_modelscope(args_dict: dict, extra_args=None):
       labels, or "schedule") (sampler "DDIM" with `do_vid2vid` only): the clip is
       taken up the deterministic trajectory by `DDIMSampler.encode` instead of being noised (`Txt2VideoSampler.sample_loop`); without
       the key the call is what it was.
+    * `inpaint` = "legacy" (sampler "DDIM_Gaussian" on the img2vid route only): the mask of the img2vid route takes effect — after every step
+      but the last, frames whose weight is <= (steps - i - 1) / steps are reset to the re-noised image latents, so weight 0 holds a frame
+      to the picture until the last blend and weight 1 leaves it free (`GaussianDiffusion.sample`); without the key the call is what
+      it was.
     * `prompts` = [...] / `n_prompts` = [...] (or `conds` = [...] / `unconds` = [...], lists of context tensors) and optionally
       `seeds` = [...]: a batch of DIFFERENT prompts in ONE pass, one video per entry (a single negative prompt, or `prompt` / `cond`
       beside a list, is broadcast; every prompt is encoded by an encoder call of its own).  Video v starts from seeds[v] (default
@@ -441,7 +450,8 @@ def process_modelscope(args_dict: dict, extra_args=None):
       is resized once like a vid2vid frame (:174-178) and encoded for every frame, `inpainting_weights` = the per-frame mask weights (a sequence of `frames` floats — the reference reads
       them from its deforum-style key string through T2VAnimKeys, host plumbing), latents = image * (1 - mask) + N(0,1) * mask
       with the noise from numpy's GLOBAL generator exactly like the reference (:205), `strength = 1`, and `mask` goes to the
-      sampler (where, for DDIM_Gaussian, the reference's hook is inert: SURVEY App. C #5)."""
+      sampler.  There the reference's hook is inert and so, by default, is this build's: the video only starts near
+      the picture.  `inpaint` = "legacy" (above) makes the mask work during sampling."""
     import math
     global pipe
     a = SimpleNamespace(**args_dict)
@@ -462,7 +472,7 @@ def process_modelscope(args_dict: dict, extra_args=None):
     common = dict(frames=a.frames, scale=a.cfg_scale, width=width, height=height, eta=getattr(a, "eta", 0.0),
                   sampler=getattr(a, "sampler", available_samplers[0].name),
                   **_restriction(getattr(a, "clamp", None), getattr(a, "percentile", None), getattr(a, "unipc", None),
-                                 getattr(a, "inversion", None)))
+                                 getattr(a, "inversion", None), getattr(a, "inpaint", None)))
     batch_count = int(getattr(a, "batch_count", 1))
     stitch = getattr(a, "stitch", None)
     cpu_vae = getattr(a, "cpu_vae", "GPU (half precision)")

@@ -28,6 +28,7 @@ import contextlib
 import ctypes
 import itertools
 import os
+import struct
 import types
 from typing import Optional
 
@@ -233,7 +234,7 @@ class GaussianDiffusion(object):
     @torch.no_grad()
     def sample(self, x_T=None, S=5, shape=None, conditioning=None, unconditional_conditioning=None,
                model_kwargs={}, clamp=None, percentile=None, condition_fn=None,
-               unconditional_guidance_scale=None, eta=0.0, callback=None, mask=None, **kwargs):
+               unconditional_guidance_scale=None, eta=0.0, callback=None, mask=None, inpaint=None, inpaint_noise=None, **kwargs):
         """gaussian_sampler.py:214-296.  Returns x_0-ish latent after S DDIM steps.
 
         Restriction of the predicted x0 (restrict_range_x0, gaussian_sampler.py:110-120, 174-178), the reference's answer to x0 blowing
@@ -250,12 +251,38 @@ class GaussianDiffusion(object):
         Several videos per batch (this build's extension; the reference's quantile cannot run there): each video has its own s, so the
         batch equals the single-video runs.  A clip whose frames are split over ranks is refused: the quantile spans all frames.
         The model is evaluated by `_eval_eps_pair`, as in every loop of this file: a guidance scale with
-        unconditional_conditioning=None runs unguided."""
+        unconditional_conditioning=None runs unguided.
+
+        Keyframe inpainting (img2vid), opt-in.  inpaint=None (the default): `mask` does nothing, as in the reference's current sampler
+        (the hook is inert, `inpaint_masking`), with the same draws.  inpaint="legacy": the reference's legacy loop
+        (GaussianDiffusion.ddim_sample_loop, modelscope/t2v_model.py:1460-1577), which needs `mask` and `x_T`:
+          original = fp32(x_T), kept for the whole run (the caller's tensor is never written);
+          xt = add_noise(original, n0, timesteps[0])                                                          (:1499-1502)
+          after every step i but the last (:1555-1562), in the same launch as the update (T2V_OP_DDIM_STEP mode 4):
+            v = (S - i - 1) / S;  bin = where(mask <= v, 0, 1);  xt = add_noise(original, n_{i+1}, timesteps[i + 1]) * (1 - bin) + xt * bin
+        Weight 1 means free; weight 0 is held until the last blend.  The mask is broadcast to the latent once and held dense in fp32:
+        the comparison is fp32(mask) <= fp32(v), what torch.where(mask.float() <= v, ...) gives; a NaN weight compares false (free).  A
+        float64 mask whose weight lies within fp32 rounding of some v_i may therefore switch one step differently from the float64
+        comparison of the reference.
+        inpaint_noise: an fp32 tensor [S, *x_T.shape], row 0 = n0, row i + 1 = the blend noise after step i, used instead of drawing.
+        Without it the draws are the legacy loop's, in its order on the global generator: n0, then per step the eta draw followed, for
+        i < S - 1, by the blend draw; the inert hook's draw does not happen in this mode.
+        The step list is this build's own (the first S entries of get_time_steps); it is the legacy loop's whenever num_timesteps % S
+        == 0, otherwise the legacy loop walks one entry more — not mirrored.
+        Refused: clamp / percentile / condition_fn beside it (ValueError); an fp16 latent, a clip whose frames are split over ranks and
+        the CFG-pair layout (T2VError)."""
         if model_kwargs:
             raise NotImplementedError("model_kwargs (conditioning passed as a pair, gaussian_sampler.py:156-159) is not used by the pipeline")
         if percentile is not None and not (0 < float(percentile) <= 1):
             raise ValueError(f"percentile must lie in (0, 1] (gaussian_sampler.py:112), got {percentile!r}")
         restricted = clamp is not None or percentile is not None or condition_fn is not None
+        if inpaint is not None:
+            if inpaint != "legacy":
+                raise ValueError(f"inpaint must be None or 'legacy' (the legacy loop's keyframe blend, t2v_model.py:1555-1562), got {inpaint!r}")
+            if mask is None or x_T is None:
+                raise ValueError("inpaint='legacy' needs the mask and the latents x_T it holds the frames to")
+            if restricted:
+                raise ValueError("inpaint together with clamp / percentile / condition_fn: the keyframe blend follows the plain DDIM_Gaussian step only")
         lib = L.load()
         model = self.model
         dev = torch.device(model.device)
@@ -284,6 +311,19 @@ class GaussianDiffusion(object):
                 raise L.T2VError("clamp / percentile / condition_fn need an fp32 latent x_T")
             if percentile is not None:
                 thresholds = torch.zeros((steps, Bx, 4), dtype=torch.float32, device=dev)    # one row per step, written by the measure pass
+        original = None
+        if inpaint is not None:
+            if getattr(model, "t_shard", None) is not None or (self.shared_noise is not None and self.shared_noise.total != Fr):
+                raise L.T2VError("inpaint with a clip whose frames are split over ranks: the keyframe blend needs the whole clip on one device")
+            if self.cfg_parallel is not None and self.cfg_parallel.size == 2:
+                raise L.T2VError("inpaint in the CFG-pair layout: the blend noise is drawn on one device")
+            if x_dt != "f32":
+                raise L.T2VError("inpaint needs an fp32 latent x_T")
+            original = xt                                # the clone made above: kept for the whole run, never written
+            mask_d = torch.as_tensor(mask).to(device=dev, dtype=torch.float32).expand(xt.shape).contiguous()
+            if inpaint_noise is not None:
+                inpaint_noise = inpaint_noise.to(dev)
+                _check_operand(inpaint_noise, xt, "inpaint_noise", "must be fp32, contiguous and shaped [S, *x_T.shape]", shape=(steps,) + tuple(xt.shape))
 
         ac = self.alphas_cumprod
         f32 = torch.float32
@@ -294,6 +334,8 @@ class GaussianDiffusion(object):
             # every step's timestep row, uploaded once: [steps, 2 * Bx] fp32 (the b = 2 * Bx CFG forward reads a whole row, a
             # b = Bx forward its first half) — no per-step fill kernels inside the loop
             tt_all = all_t[:steps].to(torch.float32).view(-1, 1).repeat(1, 2 * Bx).to(dev)
+            if original is not None:                     # the legacy loop starts from the re-noised latents (t2v_model.py:1499-1502)
+                xt = self.add_noise(original, inpaint_noise[0] if inpaint_noise is not None else torch.randn_like(original), all_t[0])
             for step in range(steps):
                 c, uc = reconstruct_conds(conditioning, unconditional_conditioning, step)
                 t = int(all_t[step])
@@ -308,8 +350,16 @@ class GaussianDiffusion(object):
                     float(torch.sqrt(a_prev)), float(torch.sqrt(1 - a_prev - sigma ** 2)),
                     float(sigma) if t != 0 else 0.0, gscale)
                 noise = _step_noise(self, xt, float(sigma) if t != 0 else 0.0)     # drawn every step, like the reference (global RNG)
-                _ = torch.randn_like(xt, dtype=f32)         # the (inert) inpaint hook's draw, gaussian_sampler.py:288
-                if restricted:
+                if original is None:
+                    _ = torch.randn_like(xt, dtype=f32)     # the (inert) inpaint hook's draw, gaussian_sampler.py:288
+                if original is not None and step < steps - 1:
+                    # the update, then frames of weight <= v are reset to the re-noised original (t2v_model.py:1555-1562): one launch
+                    qnoise = inpaint_noise[step + 1] if inpaint_noise is not None else torch.randn_like(xt, dtype=f32)
+                    t_next = int(all_t[step + 1])
+                    _ddim_update_keyframe(x_next, xt, eps, noise, coef, guided, original, mask_d, qnoise,
+                                          (float(self.sqrt_alphas_cumprod[t_next].to(f32)), float(self.sqrt_one_minus_alphas_cumprod[t_next].to(f32))),
+                                          (steps - step - 1) / steps)
+                elif restricted:
                     grad = None
                     if condition_fn is not None:
                         grad = condition_fn(xt, torch.full((Bx,), t, dtype=torch.long, device=dev))
@@ -353,13 +403,14 @@ def _check_operand(t, x, noun: str, what: str = "must be fp32, contiguous, on th
 
 
 def _ddim_record(out, xt, eps_pair, noise, coef, guided: int, mode: int, *, blend=None, restrict: int = 0, level: float = 0.0,
-                 table=None, grad=None, keep=None):
+                 table=None, grad=None, keep=None, keyframe=None):
     """-> one T2V_OP_DDIM_STEP record (include/t2v_hip.h): the header every mode shares — geometry, dtypes, f[0..5] = `coef`,
     x / eps pair / out, and the eta noise only where coef[4] != 0 — plus what the keywords name, every other field zero:
       blend = (known, mask, qnoise or None, qcoef)   i[7] = 1, f[6..7], p[4..6]: the known-region blend of a masked step
       restrict, level, table                          i[8], f[6] (the clamp bound or the percentile), p[7]: the restriction of x0
       grad = (g, sqrt(1 - a_t))                       i[9] = 1, f[7], p[8]: the classifier-guidance term
-      keep                                            p[4]: the second destination of an inversion step"""
+      keep                                            p[4]: the second destination of an inversion step
+      keyframe = (original, mask, qnoise or None, qcoef, v)   mode 4: f[6..7], p[4..6], and the fp32 threshold v as raw bits in i[10]"""
     op = L.T2VOp()
     op.kind = L.OP_DDIM_STEP
     B, C = xt.shape[0], xt.shape[1]              # B videos per batch: eps_pair = [cond (B), uncond (B)]
@@ -381,6 +432,11 @@ def _ddim_record(out, xt, eps_pair, noise, coef, guided: int, mode: int, *, blen
         op.i[9], op.f[7], op.p[8] = 1, float(grad[1]), grad[0].data_ptr()
     if keep is not None:
         op.p[4] = keep.data_ptr()
+    if keyframe is not None:
+        original, mask, qnoise, qcoef, v = keyframe
+        op.f[6], op.f[7] = float(qcoef[0]), float(qcoef[1])
+        op.i[10] = struct.unpack("<i", struct.pack("<f", float(v)))[0]
+        op.p[4], op.p[5], op.p[6] = original.data_ptr(), mask.data_ptr(), qnoise.data_ptr() if qnoise is not None else 0
     return op
 
 
@@ -471,6 +527,17 @@ def _ddim_update_blend(out, xt, eps_pair, noise, coef, guided: int, known, mask,
     for t in (known, mask) + (() if qnoise is None else (qnoise,)):
         _check_operand(t, xt, "the blend operands of a masked DDIM step")
     _run_ops(_ddim_record(out, xt, eps_pair, noise, coef, guided, 1, blend=(known, mask, qnoise, qcoef)), xt.device)
+    return out
+
+
+def _ddim_update_keyframe(out, xt, eps_pair, noise, coef, guided: int, original, mask, qnoise, qcoef, v: float):
+    """T2V_OP_DDIM_STEP mode 4: the DDIM_Gaussian update of `_ddim_update` (mode 0, bit for bit) and, in the same launch, the keyframe
+    blend of the legacy img2vid loop (modelscope/t2v_model.py:1555-1562): bin = mask <= fp32(v) ? 0 : 1,
+    out = (qcoef[0] * original + qcoef[1] * qnoise) * (1 - bin) + x_{t-1} * bin.  xt, out, original, mask, qnoise: fp32, contiguous,
+    shaped like xt (qnoise may be None when qcoef[1] == 0)."""
+    for t in (xt, out, original, mask) + (() if qnoise is None else (qnoise,)):
+        _check_operand(t, xt, "the operands of a keyframe DDIM step")
+    _run_ops(_ddim_record(out, xt, eps_pair, noise, coef, guided, 4, keyframe=(original, mask, qnoise, qcoef, v)), xt.device)
     return out
 
 
@@ -1133,7 +1200,7 @@ class Txt2VideoSampler(object):
 
     def sample_loop(self, steps, strength, conditioning, unconditional_conditioning, batch_size, latents=None,
                     shape=None, noise=None, is_vid2vid=False, guidance_scale=1, eta=0, mask=None,
-                    sampler_name="DDIM", *, clamp=None, percentile=None, unipc=None, inversion=None):
+                    sampler_name="DDIM", *, clamp=None, percentile=None, unipc=None, inversion=None, inpaint=None):
         """samplers_common.py:165-207.  `clamp` / `percentile` (keyword, this build's addition to the signature): the x0 restriction of
         GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set, so every other call is what it was.
         `unipc` (keyword, likewise): a dict of UniPC's solver options (UNIPC_OPTIONS, see UniPCSampler) — UniPC only, forwarded only
@@ -1142,9 +1209,13 @@ class Txt2VideoSampler(object):
         model_timesteps ("index" | "schedule", see DDIMSampler.encode) — sampler "DDIM" with
         is_vid2vid only: the latents are taken up the deterministic trajectory by `DDIMSampler.encode` (under `conditioning`, each
         video of a batch under its own prompt) instead of being noised by `stochastic_encode`; `noise` is not used; `sample` becomes
-        `decode` exactly as on the noising route."""
-        restrict = {k: v for k, v in (("clamp", clamp), ("percentile", percentile)) if v is not None}
+        `decode` exactly as on the noising route.
+        `inpaint` (keyword, likewise): "legacy" makes `mask` work — the keyframe blend of the reference's legacy loop, see
+        GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set."""
+        restrict = {k: v for k, v in (("clamp", clamp), ("percentile", percentile), ("inpaint", inpaint)) if v is not None}
         active = next((s.name for s in available_samplers if isinstance(self.sampler, s.Sampler)), type(self.sampler).__name__)
+        if inpaint is not None and not isinstance(self.sampler, GaussianDiffusion):
+            raise ValueError(f"inpaint: the keyframe blend exists for the DDIM_Gaussian sampler only, not for {active!r}")
         if restrict and not isinstance(self.sampler, GaussianDiffusion):
             raise ValueError(f"{' / '.join(restrict)}: the x0 restriction exists for the DDIM_Gaussian sampler only, not for {active!r}")
         if unipc is not None:
