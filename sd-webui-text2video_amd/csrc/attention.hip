@@ -1131,9 +1131,7 @@ hipError_t launch_relpos_long(const SeqAttnParams& p, const f16* ek16, const f16
 template <bool REL>
 hipError_t launch_seqattn(const t2v_op& op, hipStream_t s) {
   SeqAttnParams p;
-  p.q = reinterpret_cast<const f16*>(op.p[0]);
-  p.k = reinterpret_cast<const f16*>(op.p[1]);
-  p.v = reinterpret_cast<const f16*>(op.p[2]);
+  p.q = reinterpret_cast<const f16*>(op.p[0]); p.k = reinterpret_cast<const f16*>(op.p[1]); p.v = reinterpret_cast<const f16*>(op.p[2]);
   p.o = reinterpret_cast<f16*>(op.p[3]);
   p.ek = reinterpret_cast<const float*>(op.p[4]);
   p.ev = reinterpret_cast<const float*>(op.p[5]);
@@ -1257,11 +1255,46 @@ void launch_attn(const AttnParams& p, int nbatch, hipStream_t s) {
 
 }  // namespace
 
+// What an ATTENTION record is, or why it is none: the one place that knows which combinations of i[14..24], p[4..7] and f[0] are legal
+// (include/t2v_hip.h).  The forms exclude each other: a second role and a per-sample table are refused beside the V^T scratch and beside each other.
+t2v_attention_class t2v_attention_classify(const t2v_op& op) {
+  const int d = op.i[14] > 0 ? op.i[14] : 64;
+  auto is = [&](t2v_attention_form form) { return t2v_attention_class{form, d, op.i[18] == 4 ? 4 : 8, nullptr}; };
+  auto bad = [&](const char* why) { return t2v_attention_class{T2V_ATTN_MALFORMED, d, 0, why}; };
+  if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[2] <= 0 || op.i[3] <= 0 || op.i[4] <= 0) return bad("empty attention");
+  if (d != 40 && d != 64 && d != 80 && d != 160) return bad("attention head_dim must be 40, 64, 80 or 160");
+  for (int k = 5; k <= 13; ++k)
+    if (op.i[k] < 0) return bad("negative attention stride");
+  if (op.i[15] != 0 && op.i[0] != op.i[1]) return bad("causal attention needs nq == nk");
+  if (op.i[16] < 0) return bad("negative low-order output offset");
+  if (!(op.f[0] > 0.f)) return bad("attention scale must be > 0");
+  if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[3] == 0) return bad("null attention pointer");
+  if (op.p[6] != 0 && (d != 64 || op.i[15] != 0 || op.i[17] < op.i[1] || op.i[17] % 64 != 0 || (op.i[18] != 0 && op.i[18] != 4 && op.i[18] != 8)))
+    return bad("attention with a V^T scratch (p[6]): head_dim 64, not causal, i[17] = keys padded to a multiple of 64, i[18] = 0 | 4 | 8 waves");
+  if (op.i[19] != 0) {       // second role: outer samples >= i[19] have their own key count and K / V rows
+    if (op.i[19] < 0 || op.i[19] >= op.i[3] || op.i[20] <= 0 || op.i[21] < 0 || op.p[4] == 0 || op.p[5] == 0)
+      return bad("attention second role: 0 < i[19] < batch_outer, i[20] keys > 0, sample stride i[21] >= 0, K / V bases p[4], p[5]");
+    if (op.i[15] != 0 || op.p[6] != 0) return bad("attention second role: not for causal launches or the V^T scratch path");
+  }
+  if (op.i[22] != 0 || op.i[23] != 0 || op.i[24] != 0) {       // per-sample table: every outer sample has its own key count and first K / V row
+    if (op.p[7] == 0) return bad("attention per-sample table: null table p[7]");
+    if (op.i[22] != op.i[3] || op.i[23] <= 0 || op.i[24] < op.i[23])
+      return bad("attention per-sample table: i[22] rows == batch_outer, i[23] largest key count > 0, i[24] K / V rows spanned >= i[23]");
+    if (op.i[19] != 0 || op.i[20] != 0 || op.i[21] != 0 || op.p[4] != 0 || op.p[5] != 0) return bad("attention per-sample table: not together with the second role (i[19..21], p[4], p[5])");
+    if (op.i[15] != 0) return bad("attention per-sample table: not for causal launches");
+    if (op.p[6] != 0) return bad("attention per-sample table: not for the V^T scratch path (p[6])");
+    return is(T2V_ATTN_TABLE);
+  }
+  if (op.p[7] != 0) return bad("attention table p[7] without its fields i[22..24]");
+  return is(op.p[6] != 0 ? T2V_ATTN_VT : op.i[19] != 0 ? T2V_ATTN_SECOND_ROLE : T2V_ATTN_PLAIN);
+}
+
+// Every caller has validated the record (t2v_run_ops and t2v_plan_create pass each record through validate_op, which asks
+// t2v_attention_classify): the launcher asks for the form and checks nothing again.
 hipError_t t2v_launch_attention(const t2v_op& op, hipStream_t s) {
+  const t2v_attention_class c = t2v_attention_classify(op);
   AttnParams p;
-  p.q = reinterpret_cast<const f16*>(op.p[0]);
-  p.k = reinterpret_cast<const f16*>(op.p[1]);
-  p.v = reinterpret_cast<const f16*>(op.p[2]);
+  p.q = reinterpret_cast<const f16*>(op.p[0]); p.k = reinterpret_cast<const f16*>(op.p[1]); p.v = reinterpret_cast<const f16*>(op.p[2]);
   p.o = reinterpret_cast<f16*>(op.p[3]);
   p.nq = op.i[0]; p.nk = op.i[1]; p.heads = op.i[2]; p.b_outer = op.i[3]; p.b_inner = op.i[4];
   p.sq_seq = op.i[5]; p.sq_out = op.i[6]; p.sq_in = op.i[7];
@@ -1270,36 +1303,28 @@ hipError_t t2v_launch_attention(const t2v_op& op, hipStream_t s) {
   p.scale_log2 = op.f[0] * 1.44269504088896340736f;
   p.causal = op.i[15] != 0;
   p.lo_off = op.i[16];
-  if (p.lo_off < 0) return hipErrorInvalidValue;
-  if (p.nq <= 0 || p.nk <= 0 || !(op.f[0] > 0.f)) return hipErrorInvalidValue;
-  p.alt_from = op.i[19]; p.nk2 = p.alt_from > 0 ? op.i[20] : 0; p.sk2_out = op.i[21];
-  p.k2 = reinterpret_cast<const f16*>(op.p[4]);
-  p.v2 = reinterpret_cast<const f16*>(op.p[5]);
-  if (p.alt_from != 0 && (p.alt_from < 0 || p.alt_from >= p.b_outer || p.nk2 <= 0 || p.sk2_out < 0 || p.k2 == nullptr || p.v2 == nullptr || p.causal || op.p[6] != 0))
-    return hipErrorInvalidValue;
-  // per-sample table (validated by the executor): i[22] = its rows (== batch_outer), i[23] = its largest key count, i[24] = K / V rows it spans
-  p.tab = op.i[22] != 0 ? reinterpret_cast<const int*>(op.p[7]) : nullptr;
+  p.alt_from = op.i[19]; p.nk2 = c.form == T2V_ATTN_SECOND_ROLE ? op.i[20] : 0; p.sk2_out = op.i[21];
+  p.k2 = reinterpret_cast<const f16*>(op.p[4]); p.v2 = reinterpret_cast<const f16*>(op.p[5]);
+  // per-sample table: i[22] = its rows (== batch_outer), i[23] = its largest key count, i[24] = K / V rows it spans
+  p.tab = c.form == T2V_ATTN_TABLE ? reinterpret_cast<const int*>(op.p[7]) : nullptr;
   p.nk_max = op.i[23]; p.rows_all = op.i[24];
-  if (op.i[22] != 0 && (p.tab == nullptr || op.i[22] != p.b_outer || p.nk_max <= 0 || p.rows_all < p.nk_max || p.alt_from != 0 || p.causal || op.p[6] != 0))
-    return hipErrorInvalidValue;
   const int nbatch = p.b_outer * p.b_inner;
-  const int hd = op.i[14] > 0 ? op.i[14] : 64;
-  if (op.p[6] != 0) {
-    // round 6: V transposed once in HBM into the scratch p[6] (fp16 [batch * heads * 64, i[17]]), K / V^T tiles by LDS-DMA (attn2_kernel);
-    // validated by the executor: head_dim 64, not causal, i[17] = keys padded to a multiple of 64
-    f16* vt = reinterpret_cast<f16*>(op.p[6]);
-    const int n_pad = op.i[17];
-    hipLaunchKernelGGL(vt_transpose_kernel, dim3(n_pad / 64, p.heads, nbatch), dim3(256), 0, s, p, vt, n_pad);
-    if (op.i[18] == 4) hipLaunchKernelGGL((attn2_kernel<4>), dim3((p.nq + 127) / 128, p.heads, nbatch), dim3(256), 0, s, p, vt, n_pad);
-    else hipLaunchKernelGGL((attn2_kernel<8>), dim3((p.nq + 255) / 256, p.heads, nbatch), dim3(512), 0, s, p, vt, n_pad);
-    return hipGetLastError();
-  }
-  switch (hd) {
-    case 40: launch_attn<40>(p, nbatch, s); break;
-    case 64: launch_attn<64>(p, nbatch, s); break;
-    case 80: launch_attn<80>(p, nbatch, s); break;
-    case 160: launch_attn<160>(p, nbatch, s); break;
-    default: return hipErrorInvalidValue;
+  switch (c.form) {
+    case T2V_ATTN_MALFORMED: return hipErrorInvalidValue;
+    case T2V_ATTN_VT: {
+      // V transposed once in HBM into the scratch p[6] (fp16 [batch * heads * 64, i[17]]), K / V^T tiles by LDS-DMA (attn2_kernel): head_dim 64
+      f16* vt = reinterpret_cast<f16*>(op.p[6]);
+      const int n_pad = op.i[17];
+      hipLaunchKernelGGL(vt_transpose_kernel, dim3(n_pad / 64, p.heads, nbatch), dim3(256), 0, s, p, vt, n_pad);
+      if (c.vt_waves == 4) hipLaunchKernelGGL((attn2_kernel<4>), dim3((p.nq + 127) / 128, p.heads, nbatch), dim3(256), 0, s, p, vt, n_pad);
+      else hipLaunchKernelGGL((attn2_kernel<8>), dim3((p.nq + 255) / 256, p.heads, nbatch), dim3(512), 0, s, p, vt, n_pad);
+      break;
+    }
+    default:       // plain, second role, per-sample table: launch_attn tells them apart by p.tab / p.nk2
+      if (c.head_dim == 40) launch_attn<40>(p, nbatch, s);
+      else if (c.head_dim == 64) launch_attn<64>(p, nbatch, s);
+      else if (c.head_dim == 80) launch_attn<80>(p, nbatch, s);
+      else launch_attn<160>(p, nbatch, s);
   }
   return hipGetLastError();
 }

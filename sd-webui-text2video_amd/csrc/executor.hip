@@ -8,6 +8,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "t2v_kernels.h"
@@ -21,10 +22,6 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-struct Resolved {
-  t2v_op op;
-};
-
 inline bool resolve_ptrs(t2v_op& op, const uint64_t* ext, int n_ext) {
   for (int k = 0; k < T2V_OP_NP; ++k) {
     const uint64_t v = op.p[k];
@@ -36,6 +33,178 @@ inline bool resolve_ptrs(t2v_op& op, const uint64_t* ext, int n_ext) {
   return true;
 }
 
+// ---- the GEMM record, decoded once -------------------------------------------------------------------------------------------------------
+// What a T2V_OP_GEMM record is, or why it is none (include/t2v_hip.h): gemm_decode is the ONE function that reads the record's words and
+// pointer slots — i[8..14], i[24..28], p[3], p[7], p[8], p[9] mean different things under different gathers and epilogues.  Validation,
+// the parameter block, the slot extents, the output slots and the feed-forward recognition all ask the view and read nothing again.
+enum GemmForm {
+  GEMM_MALFORMED,
+  GEMM_PLAIN, GEMM_GEGLU,            // bias / row bias / activation / residual, hi + lo output, split-K (tickets or a reduction launch); GEGLU
+  GEMM_STATS,                        // column statistics strips beside the result (T2V_EPI_STATS)
+  GEMM_LN_ROW, GEMM_LN_CROSS,        // LayerNorm second output: the row inside one tile (plain gather, i[8] = 1); across the column tiles (i[8] = 2)
+  GEMM_GN_TILE, GEMM_GN_SPLITK,      // GroupNorm (+SiLU) of the result (T2V_EPI_GN): in the tile epilogue; in the split-K reduction launch
+  GEMM_TATTN, GEMM_XATTN,            // fused QKV projection + temporal attention; fused to_q projection + text cross-attention
+};
+inline bool gemm_writes_gn(GemmForm f) { return f == GEMM_GN_TILE || f == GEMM_GN_SPLITK; }
+struct GemmView {
+  GemmForm form;
+  const char* why;              // the refusal (GEMM_MALFORMED), else null
+  const t2v_tile* tile;
+  int M, N, K, lda, ldw, ldc, ldr, ldrb;
+  int gather, epi, act, out_dtype, out_item, split, bias_m, halo, rows_per_batch;
+  // The words i[8..14] under the gather's names.  TCONV3: F, HW (Hin = Win = 0); TATTN: F, HW, tpix (Hin = Win = Cin = 0); else Hin, Win.
+  // Under the plain gather the 3x3 names carry the record's words as they stand (the parameter block always has; no kernel reads them
+  // there) and what the words mean is named beside them: ln_mode / ld_ln, hilo, res_wrap, a_wrap.
+  int Hin, Win, Cin, stride, up, Hout, Wout, F, HW, tpix;
+  int ln_mode, ld_ln;           // plain gather, i[8] / i[9]: 1 whole-row, 2 cross-tile LayerNorm output (other values name none); its leading dimension
+  int hilo, out_lo;             // plain gather, i[11]; out_lo: the word is 1 — rows [hi | lo] of 2 N halfs
+  int res_wrap, a_wrap;         // rows after which the residual / the A operand wrap (0: none); i[30], or i[12] / i[13] of a plain gather
+  int64_t n_out;                // stored columns (GEGLU: N / 2)
+  int gn_rows, ld_gn, gn_silu, gn_lo, gn_groups, gn_skip_out;      // i[24..29] of every form but XATTN
+  int xa_ldk, xa_lc, xa_lcp, xa_k_sample, xa_vt_sample;            // i[24..28] under XATTN
+  float ln_eps, attn_scale, gn_eps;
+  bool waive_min_m;             // i[31] = 1, a word no check reads: the tests' way to the fused feed-forward pair at a few hundred rows
+  // the pointer slots by role; a role that the form does not have is 0
+  uint64_t A, W, bias, rowbias, ln_gb, res, out, ws;               // p[0..6]; p[3] is gamma | beta under the LayerNorm forms
+  uint64_t tickets, ln_out, stats;                                 // p[7]
+  uint64_t gn_gb, gn_out, xa_k, xa_vt;                             // p[8], p[9]
+  uint64_t scratch, barrier;                                       // p[10], p[11]
+};
+
+GemmView gemm_decode(const t2v_op& op) {
+  const int32_t* I = op.i;
+  const uint64_t* P = op.p;
+  GemmView v;
+  memset(&v, 0, sizeof v);
+  const int M = v.M = I[0], N = v.N = I[1], K = v.K = I[2], g = v.gather = I[7], epi = v.epi = I[16];
+  const bool plain = g == T2V_GATHER_PLAIN, conv = g == T2V_GATHER_CONV3X3 || g == T2V_GATHER_CONV3X3_C8;
+  v.lda = I[3]; v.ldw = I[4]; v.ldc = I[5]; v.ldr = I[6]; v.ldrb = I[21];
+  v.act = I[18]; v.out_dtype = I[17]; v.out_item = I[17] == T2V_F32 ? 4 : 2; v.split = I[19] > 1 ? I[19] : 1; v.bias_m = I[20]; v.halo = I[23];
+  v.rows_per_batch = I[15] > 0 ? I[15] : 1;
+  if (g == T2V_GATHER_TCONV3 || (plain && epi == T2V_EPI_TATTN)) { v.F = I[8]; v.HW = I[9]; }
+  else { v.Hin = I[8]; v.Win = I[9]; }
+  if (plain && epi == T2V_EPI_TATTN) v.tpix = I[10]; else v.Cin = I[10];
+  v.stride = I[11]; v.up = I[12]; v.Hout = I[13]; v.Wout = I[14];
+  if (plain) { v.ln_mode = I[8]; v.ld_ln = I[9]; v.hilo = I[11]; v.out_lo = I[11] == 1; }
+  if (plain && epi != T2V_EPI_TATTN) { v.res_wrap = I[12]; v.a_wrap = I[13]; }
+  if (I[30] > 0) v.res_wrap = I[30];                          // (checked below: not beside i[12])
+  v.n_out = epi == T2V_EPI_GEGLU ? N / 2 : N;
+  if (epi == T2V_EPI_XATTN) { v.xa_ldk = I[24]; v.xa_lc = I[25]; v.xa_lcp = I[26]; v.xa_k_sample = I[27]; v.xa_vt_sample = I[28]; v.xa_k = P[8]; v.xa_vt = P[9]; }
+  else { v.gn_rows = I[24]; v.ld_gn = I[25]; v.gn_silu = I[26]; v.gn_lo = I[27]; v.gn_groups = I[28]; v.gn_skip_out = I[29]; v.gn_gb = P[8]; v.gn_out = P[9]; }
+  v.ln_eps = op.f[0]; v.attn_scale = op.f[1]; v.gn_eps = op.f[2];
+  v.waive_min_m = I[31] == 1;
+  const bool ln = plain && epi != T2V_EPI_TATTN && (I[8] == 1 || I[8] == 2);
+  v.form = epi == T2V_EPI_TATTN ? GEMM_TATTN : epi == T2V_EPI_XATTN ? GEMM_XATTN : epi == T2V_EPI_GN ? (v.split > 1 ? GEMM_GN_SPLITK : GEMM_GN_TILE)
+         : epi == T2V_EPI_GEGLU ? GEMM_GEGLU : epi == T2V_EPI_STATS ? GEMM_STATS : !ln ? GEMM_PLAIN : I[8] == 1 ? GEMM_LN_ROW : GEMM_LN_CROSS;
+  v.A = P[0]; v.W = P[1]; v.bias = P[2]; v.res = P[4]; v.out = P[5]; v.ws = P[6]; v.scratch = P[10]; v.barrier = P[11];
+  (ln ? v.ln_gb : v.rowbias) = P[3];
+  (ln ? v.ln_out : v.form == GEMM_STATS ? v.stats : v.tickets) = P[7];      // tickets: T2V_SYNC_INTS zeroed ints -> the split-K fold runs in the GEMM's last-arriving workgroups; 0 -> reduction launch
+
+  // ---- the checks, in the order a caller sees their messages
+  auto bad = [&](const char* why) { v.form = GEMM_MALFORMED; v.why = why; return v; };
+  if (M <= 0 || N <= 0 || K <= 0) return bad("empty GEMM");
+  if (N % 4 != 0) return bad("N must be a multiple of 4");
+  if (K % 8 != 0 || v.lda % 8 != 0 || v.ldw % 8 != 0) return bad("K, lda, ldw must be multiples of 8");
+  if (v.ldc % 4 != 0) return bad("ldc must be a multiple of 4");
+  if (g == T2V_GATHER_CONV3X3 || g == T2V_GATHER_TCONV3) {
+    if (v.Cin % 64 != 0) return bad("conv Cin must be a multiple of 64");
+    if (K != (g == T2V_GATHER_CONV3X3 ? 9 : 3) * v.Cin) return bad("K != taps*Cin");
+  } else if (g == T2V_GATHER_CONV3X3_C8) {
+    if (v.Cin != 8 || K != 72 || v.lda != 8) return bad("C8 conv needs Cin == lda == 8, K == 72");
+  } else if (!plain) {
+    return bad("unknown gather mode");
+  }
+  if (conv) {
+    if (v.stride != 1 && v.stride != 2) return bad("stride must be 1 or 2");
+    if (v.up != 0 && v.up != 1) return bad("upsample must be 0 or 1");
+    if (v.Hout <= 0 || v.Wout <= 0 || M % (v.Hout * v.Wout) != 0) return bad("M not a multiple of Hout*Wout");
+  }
+  if (g == T2V_GATHER_TCONV3 && (v.F <= 0 || v.HW <= 0 || M % (v.F * v.HW) != 0)) return bad("M not a multiple of F*HW");
+  if (epi == T2V_EPI_GEGLU && (N % 32 != 0 || v.out_dtype != T2V_F16)) return bad("GEGLU needs N % 32 == 0, fp16 out");
+  if (epi == T2V_EPI_STATS && (P[7] == 0 || v.split > 1 || v.ln_mode == 1))
+    return bad("column statistics (T2V_EPI_STATS): strips pointer p[7], no split-K, no fused LayerNorm");
+  if (epi < 0 || epi > T2V_EPI_XATTN) return bad("unknown epilogue");
+  if (v.act < 0 || v.act > 2) return bad("unknown activation (0 none, 1 SiLU, 2 ReLU)");
+  const t2v_tile* tile = v.tile = t2v_tile_of(I[22]);          // geometry and fused epilogues of the tile: the table in t2v_kernels.h
+  if (tile == nullptr) return bad("unknown tile id");
+  if (I[30] != 0) {       // residual row wrap for every gather mode (ABI 11)
+    if (I[30] < 0 || M > 2 * I[30] || v.res == 0) return bad("residual row wrap i[30]: positive, M <= 2 * wrap, and a residual");
+    if (epi == T2V_EPI_GEGLU || epi == T2V_EPI_TATTN || epi == T2V_EPI_XATTN || (plain && (I[12] != 0 || v.ln_mode != 0)))
+      return bad("residual row wrap i[30]: plain / statistics / GroupNorm epilogues only, not beside i[12] or a fused LayerNorm");
+  }
+  if (epi == T2V_EPI_XATTN) {
+    if (!plain || N % 64 != 0 || K % 64 != 0 || v.out_dtype != T2V_F16 || v.split > 1 || v.act != 0 || v.ln_mode != 0 || v.out_lo)
+      return bad("fused cross-attention: plain gather, N = 64 * heads, K % 64 == 0, fp16 out, no split-K / activation / LayerNorm / hi + lo output");
+    if (!t2v_tile_fuses(tile, T2V_TILE_XATTN, N)) return bad("fused cross-attention: tile 8 / 11 with N == 320, or tile 0 / 5 with N % 128 == 0");
+    if (v.bias != 0 || P[3] != 0 || v.res != 0 || v.xa_k == 0 || v.xa_vt == 0 || !(v.attn_scale > 0.f)) return bad("fused cross-attention: no bias / row bias / residual; K, V^T and a positive scale are required");
+    if (v.xa_lc < 1 || v.xa_lc > 96 || v.xa_ldk < N || v.xa_ldk % 8 != 0 || v.xa_lcp < ((v.xa_lc + 31) / 32) * 32 || v.xa_lcp % 8 != 0 || I[15] <= 0 || I[15] % 32 != 0 || v.xa_k_sample < 0 || v.xa_vt_sample < 0)
+      return bad("fused cross-attention: 1 .. 96 keys, ld(K) >= N, V^T rows of >= ceil32(keys) halfs, rows per sample a multiple of 32");
+    if (v.ldc < N || v.ldc % 4 != 0) return bad("fused cross-attention: ldc");
+    if (I[12] != 0) return bad("fused cross-attention: no residual wrap");
+    return v;
+  }
+  if (epi == T2V_EPI_GN) {
+    // GroupNorm (+SiLU) of the result inside the epilogue: the tiles with an instantiation, whole 32-row strips per statistics
+    // instance, at most two instances per row tile, whole groups, every pointer of the exchange
+    const int rows = v.gn_rows, groups = v.gn_groups, bm = tile->bm, bn = tile->bn;
+    if (g == T2V_GATHER_CONV3X3_C8 || (g == T2V_GATHER_CONV3X3 && v.up != 0)) return bad("fused GroupNorm: not for the C8 stem / the upsampling gather");
+    if (v.bias_m != 0 || K % 64 != 0 || v.act != 0) return bad("fused GroupNorm: no bias along M, no activation, K % 64 == 0");
+    if (plain && (v.ln_mode != 0 || v.out_lo)) return bad("fused GroupNorm: no fused LayerNorm / hi + lo output on the same op");
+    if (groups <= 0 || N % groups != 0 || rows <= 0 || M % rows != 0) return bad("fused GroupNorm: N % groups == 0, rows per instance must divide M");
+    if (v.split > 1) {
+      // split-K: the norm runs in the reduction's launch (one thread per row x 8 channels, any tile)
+      if (groups > 32 || N % 8 != 0 || N / 8 > 512 || v.ws == 0) return bad("fused GroupNorm on a split-K GEMM: groups <= 32, N % 8 == 0, N <= 4096, a slab workspace");
+    } else {
+      if (!tile->has(T2V_TILE_GN)) return bad("fused GroupNorm: tile must be 8, 11, 3, 5 or 0");
+      if (!t2v_tile_fuses(tile, T2V_TILE_GN, N)) return bad("fused GroupNorm on the 128x128-class kernel: N % 128 == 0");
+      if (N / groups > bn || (bn + N / groups - 1) / (N / groups) + 1 > T2V_GN_PIECES) return bad("fused GroupNorm: a group no wider than the tile");
+      if (rows % 32 != 0 || !(rows >= bm || 2 * rows == bm))
+        return bad("fused GroupNorm: rows per instance must be a multiple of 32 and >= the tile's rows (or exactly half of them): at most two instances per row tile");
+    }
+    if (v.gn_gb == 0 || v.gn_out == 0 || v.scratch == 0 || v.barrier == 0) return bad("fused GroupNorm: gamma|beta, output, scratch and barrier words are required");
+    if (v.ld_gn < N * (v.gn_lo ? 2 : 1) || v.ld_gn % 4 != 0) return bad("fused GroupNorm: leading dimension of the normalised output");
+    if (v.gn_skip_out == 0 && v.out == 0) return bad("fused GroupNorm: `out` is null but i[29] asks for it");
+    if (v.ldc < N || (v.res != 0 && (v.ldr < N || v.ldr % 4 != 0))) return bad("fused GroupNorm: ldc / ldr must be >= N and multiples of 4");
+  }
+  if (v.split > 1 && v.ws == 0) return bad("split-K without workspace");
+  if (P[3] != 0 && I[15] <= 0 && !(v.ln_mode == 1 || v.ln_mode == 2)) return bad("rowbias without rows_per_batch");
+  if ((epi == T2V_EPI_TATTN) != tile->has(T2V_TILE_TATTN_ONLY)) return bad("tile 10 is the fused QKV + temporal attention tile (T2V_EPI_TATTN), and only that");
+  if (epi == T2V_EPI_TATTN) {
+    const int F = v.F, HW = v.HW, tpix = v.tpix;          // (decoded under the plain gather, which is the first thing asked)
+    if (!plain || N % 192 != 0 || K % 64 != 0 || v.out_dtype != T2V_F16 || v.split > 1 || v.act != 0)
+      return bad("fused temporal attention: plain gather, N = 192 * heads, K % 64 == 0, fp16 out, no split-K / activation");
+    if (F < 2 || F > 32 || HW < 1 || tpix < 1 || tpix > 12 || tpix * F > 192) return bad("fused temporal attention: 2 <= F <= 32, 1 <= pixels per tile <= 12, pixels * F <= 192");
+    const int tiles_ps = (HW + tpix - 1) / tpix;
+    if (M % 192 != 0 || (M / 192) % tiles_ps != 0) return bad("fused temporal attention: M must be samples * ceil(HW / pixels per tile) * 192");
+    if (v.bias != 0 || P[3] != 0 || v.res != 0 || v.A == 0 || v.W == 0 || v.out == 0 || !(v.attn_scale > 0.f))
+      return bad("fused temporal attention: no bias / row bias / residual; A, W, out and a positive scale are required");
+    if (v.ldc < (N / 192) * 64 || v.ldc % 4 != 0) return bad("fused temporal attention: ldc < heads * 64");
+    return v;
+  }
+  if (plain && (I[12] != 0 || I[13] != 0)) {       // row wrap of the residual / the A operand
+    if (I[12] < 0 || I[13] < 0 || v.split > 1 || epi == T2V_EPI_GEGLU) return bad("row wrap: non-negative, no split-K, plain epilogue");
+    if ((I[12] != 0 && (M > 2 * I[12] || v.res == 0)) || (I[13] != 0 && M > 2 * I[13])) return bad("row wrap: M <= 2 * wrap (and a residual for the residual wrap)");
+  }
+  if (v.out_lo) {       // hi + lo fp16 output
+    if (v.out_dtype != T2V_F16 || epi != T2V_EPI_NONE || v.ln_mode == 1 || v.ldc < 2 * N) return bad("hi + lo output: fp16 out, plain epilogue, no fused LayerNorm, ldc >= 2 N");
+  }
+  if (v.ln_mode == 2) {         // LayerNorm second output across the column tiles (grid barrier)
+    if (!t2v_tile_fuses(tile, T2V_TILE_LNX, N) || v.split > 1 || epi != T2V_EPI_NONE || v.out_dtype != T2V_F32 || v.act != 0 || v.bias_m != 0 || K % 64 != 0 || v.out_lo)
+      return bad("cross-tile LayerNorm output: tile 0 (N % 128 == 0), 3, 5, 9 or 12, fp32 out, plain epilogue, no split-K / activation");
+    if (v.ln_gb == 0 || v.ln_out == 0 || v.scratch == 0 || v.barrier == 0 || v.ld_ln < N || v.ld_ln % 4 != 0)
+      return bad("cross-tile LayerNorm output: gamma|beta, output, scratch, barrier words or leading dimension");
+    if (v.ldc < N || (v.res != 0 && (v.ldr < N || v.ldr % 4 != 0))) return bad("cross-tile LayerNorm output: ldc / ldr must be >= N and multiples of 4");
+  }
+  if (v.ln_mode == 1) {
+    if (!t2v_tile_fuses(tile, T2V_TILE_LN, N) || v.split > 1 || epi != T2V_EPI_NONE || v.out_dtype != T2V_F32 || v.act != 0 || v.bias_m != 0 || K % 64 != 0)
+      return bad("fused LayerNorm output needs a whole-row tile (192x320, 128x320 or 256x320), N == 320, fp32 out, no split-K / activation");
+    if (v.ln_gb == 0 || v.ln_out == 0 || v.ld_ln < N || v.ld_ln % 4 != 0) return bad("fused LayerNorm output: gamma|beta, output pointer or leading dimension");
+    // the epilogue moves whole f32x4 / f16x4 groups without tail guards
+    if (v.ldc < N || (v.res != 0 && (v.ldr < N || v.ldr % 4 != 0))) return bad("fused LayerNorm output: ldc / ldr must be >= N and multiples of 4");
+  }
+  return v;
+}
+
 int validate_op(const t2v_op& op, int idx) {
   char buf[160];
   auto bad = [&](const char* why) {
@@ -44,112 +213,8 @@ int validate_op(const t2v_op& op, int idx) {
   };
   switch (op.kind) {
     case T2V_OP_GEMM: {
-      const int M = op.i[0], N = op.i[1], K = op.i[2], g = op.i[7];
-      if (M <= 0 || N <= 0 || K <= 0) return bad("empty GEMM");
-      if (N % 4 != 0) return bad("N must be a multiple of 4");
-      if (K % 8 != 0 || op.i[3] % 8 != 0 || op.i[4] % 8 != 0) return bad("K, lda, ldw must be multiples of 8");
-      if (op.i[5] % 4 != 0) return bad("ldc must be a multiple of 4");
-      if (g == T2V_GATHER_CONV3X3 || g == T2V_GATHER_TCONV3) {
-        if (op.i[10] % 64 != 0) return bad("conv Cin must be a multiple of 64");
-        if (K != (g == T2V_GATHER_CONV3X3 ? 9 : 3) * op.i[10]) return bad("K != taps*Cin");
-      } else if (g == T2V_GATHER_CONV3X3_C8) {
-        if (op.i[10] != 8 || K != 72 || op.i[3] != 8) return bad("C8 conv needs Cin == lda == 8, K == 72");
-      } else if (g != T2V_GATHER_PLAIN) {
-        return bad("unknown gather mode");
-      }
-      if (g == T2V_GATHER_CONV3X3 || g == T2V_GATHER_CONV3X3_C8) {
-        if (op.i[11] != 1 && op.i[11] != 2) return bad("stride must be 1 or 2");
-        if (op.i[12] != 0 && op.i[12] != 1) return bad("upsample must be 0 or 1");
-        if (op.i[13] <= 0 || op.i[14] <= 0 || M % (op.i[13] * op.i[14]) != 0) return bad("M not a multiple of Hout*Wout");
-      }
-      if (g == T2V_GATHER_TCONV3 && (op.i[8] <= 0 || op.i[9] <= 0 || M % (op.i[8] * op.i[9]) != 0))
-        return bad("M not a multiple of F*HW");
-      if (op.i[16] == T2V_EPI_GEGLU && (N % 32 != 0 || op.i[17] != T2V_F16)) return bad("GEGLU needs N % 32 == 0, fp16 out");
-      if (op.i[16] == T2V_EPI_STATS && (op.p[7] == 0 || op.i[19] > 1 || (g == T2V_GATHER_PLAIN && op.i[8] == 1)))
-        return bad("column statistics (T2V_EPI_STATS): strips pointer p[7], no split-K, no fused LayerNorm");
-      if (op.i[16] < 0 || op.i[16] > T2V_EPI_XATTN) return bad("unknown epilogue");
-      if (op.i[18] < 0 || op.i[18] > 2) return bad("unknown activation (0 none, 1 SiLU, 2 ReLU)");
-      const t2v_tile* tile = t2v_tile_of(op.i[22]);          // geometry and fused epilogues of the tile: the table in t2v_kernels.h
-      if (tile == nullptr) return bad("unknown tile id");
-      if (op.i[30] != 0) {       // residual row wrap for every gather mode (ABI 11)
-        if (op.i[30] < 0 || M > 2 * op.i[30] || op.p[4] == 0) return bad("residual row wrap i[30]: positive, M <= 2 * wrap, and a residual");
-        if (op.i[16] == T2V_EPI_GEGLU || op.i[16] == T2V_EPI_TATTN || op.i[16] == T2V_EPI_XATTN || (g == T2V_GATHER_PLAIN && (op.i[12] != 0 || op.i[8] != 0)))
-          return bad("residual row wrap i[30]: plain / statistics / GroupNorm epilogues only, not beside i[12] or a fused LayerNorm");
-      }
-      if (op.i[16] == T2V_EPI_XATTN) {
-        if (g != T2V_GATHER_PLAIN || N % 64 != 0 || K % 64 != 0 || op.i[17] != T2V_F16 || op.i[19] > 1 || op.i[18] != 0 || op.i[8] != 0 || op.i[11] == 1)
-          return bad("fused cross-attention: plain gather, N = 64 * heads, K % 64 == 0, fp16 out, no split-K / activation / LayerNorm / hi + lo output");
-        if (!t2v_tile_fuses(tile, T2V_TILE_XATTN, N)) return bad("fused cross-attention: tile 8 / 11 with N == 320, or tile 0 / 5 with N % 128 == 0");
-        if (op.p[2] != 0 || op.p[3] != 0 || op.p[4] != 0 || op.p[8] == 0 || op.p[9] == 0 || !(op.f[1] > 0.f)) return bad("fused cross-attention: no bias / row bias / residual; K, V^T and a positive scale are required");
-        if (op.i[25] < 1 || op.i[25] > 96 || op.i[24] < N || op.i[24] % 8 != 0 || op.i[26] < ((op.i[25] + 31) / 32) * 32 || op.i[26] % 8 != 0 || op.i[15] <= 0 || op.i[15] % 32 != 0 || op.i[27] < 0 || op.i[28] < 0)
-          return bad("fused cross-attention: 1 .. 96 keys, ld(K) >= N, V^T rows of >= ceil32(keys) halfs, rows per sample a multiple of 32");
-        if (op.i[5] < N || op.i[5] % 4 != 0) return bad("fused cross-attention: ldc");
-        if (op.i[12] != 0) return bad("fused cross-attention: no residual wrap");
-        return 0;
-      }
-      if (op.i[16] == T2V_EPI_GN) {
-        // GroupNorm (+SiLU) of the result inside the epilogue: the tiles with an instantiation, whole 32-row strips per statistics
-        // instance, at most two instances per row tile, whole groups, every pointer of the exchange
-        const int rows = op.i[24], groups = op.i[28], bm = tile->bm, bn = tile->bn;
-        if (g == T2V_GATHER_CONV3X3_C8 || (g == T2V_GATHER_CONV3X3 && op.i[12] != 0)) return bad("fused GroupNorm: not for the C8 stem / the upsampling gather");
-        if (op.i[20] != 0 || K % 64 != 0 || op.i[18] != 0) return bad("fused GroupNorm: no bias along M, no activation, K % 64 == 0");
-        if (g == T2V_GATHER_PLAIN && (op.i[8] != 0 || op.i[11] == 1)) return bad("fused GroupNorm: no fused LayerNorm / hi + lo output on the same op");
-        if (groups <= 0 || N % groups != 0 || rows <= 0 || M % rows != 0) return bad("fused GroupNorm: N % groups == 0, rows per instance must divide M");
-        if (op.i[19] > 1) {
-          // split-K: the norm runs in the reduction's launch (one thread per row x 8 channels, any tile)
-          if (groups > 32 || N % 8 != 0 || N / 8 > 512 || op.p[6] == 0) return bad("fused GroupNorm on a split-K GEMM: groups <= 32, N % 8 == 0, N <= 4096, a slab workspace");
-        } else {
-          if (!tile->has(T2V_TILE_GN)) return bad("fused GroupNorm: tile must be 8, 11, 3, 5 or 0");
-          if (!t2v_tile_fuses(tile, T2V_TILE_GN, N)) return bad("fused GroupNorm on the 128x128-class kernel: N % 128 == 0");
-          if (N / groups > bn || (bn + N / groups - 1) / (N / groups) + 1 > T2V_GN_PIECES) return bad("fused GroupNorm: a group no wider than the tile");
-          if (rows % 32 != 0 || !(rows >= bm || 2 * rows == bm))
-            return bad("fused GroupNorm: rows per instance must be a multiple of 32 and >= the tile's rows (or exactly half of them): at most two instances per row tile");
-        }
-        if (op.p[8] == 0 || op.p[9] == 0 || op.p[10] == 0 || op.p[11] == 0) return bad("fused GroupNorm: gamma|beta, output, scratch and barrier words are required");
-        if (op.i[25] < N * (op.i[27] ? 2 : 1) || op.i[25] % 4 != 0) return bad("fused GroupNorm: leading dimension of the normalised output");
-        if (op.i[29] == 0 && op.p[5] == 0) return bad("fused GroupNorm: `out` is null but i[29] asks for it");
-        if (op.i[5] < N || (op.p[4] != 0 && (op.i[6] < N || op.i[6] % 4 != 0))) return bad("fused GroupNorm: ldc / ldr must be >= N and multiples of 4");
-      }
-      if (op.i[19] > 1 && op.p[6] == 0) return bad("split-K without workspace");
-      if (op.p[3] != 0 && op.i[15] <= 0 && !(g == T2V_GATHER_PLAIN && (op.i[8] == 1 || op.i[8] == 2))) return bad("rowbias without rows_per_batch");
-      if ((op.i[16] == T2V_EPI_TATTN) != tile->has(T2V_TILE_TATTN_ONLY)) return bad("tile 10 is the fused QKV + temporal attention tile (T2V_EPI_TATTN), and only that");
-      if (op.i[16] == T2V_EPI_TATTN) {
-        const int F = op.i[8], HW = op.i[9], tpix = op.i[10];
-        if (g != T2V_GATHER_PLAIN || N % 192 != 0 || K % 64 != 0 || op.i[17] != T2V_F16 || op.i[19] > 1 || op.i[18] != 0)
-          return bad("fused temporal attention: plain gather, N = 192 * heads, K % 64 == 0, fp16 out, no split-K / activation");
-        if (F < 2 || F > 32 || HW < 1 || tpix < 1 || tpix > 12 || tpix * F > 192) return bad("fused temporal attention: 2 <= F <= 32, 1 <= pixels per tile <= 12, pixels * F <= 192");
-        const int tiles_ps = (HW + tpix - 1) / tpix;
-        if (M % 192 != 0 || (M / 192) % tiles_ps != 0) return bad("fused temporal attention: M must be samples * ceil(HW / pixels per tile) * 192");
-        if (op.p[2] != 0 || op.p[3] != 0 || op.p[4] != 0 || op.p[0] == 0 || op.p[1] == 0 || op.p[5] == 0 || !(op.f[1] > 0.f))
-          return bad("fused temporal attention: no bias / row bias / residual; A, W, out and a positive scale are required");
-        if (op.i[5] < (N / 192) * 64 || op.i[5] % 4 != 0) return bad("fused temporal attention: ldc < heads * 64");
-        return 0;
-      }
-      if (g == T2V_GATHER_PLAIN && (op.i[12] != 0 || op.i[13] != 0)) {       // row wrap of the residual / the A operand
-        if (op.i[12] < 0 || op.i[13] < 0 || op.i[19] > 1 || op.i[16] == T2V_EPI_GEGLU) return bad("row wrap: non-negative, no split-K, plain epilogue");
-        if ((op.i[12] != 0 && (M > 2 * op.i[12] || op.p[4] == 0)) || (op.i[13] != 0 && M > 2 * op.i[13])) return bad("row wrap: M <= 2 * wrap (and a residual for the residual wrap)");
-      }
-      if (g == T2V_GATHER_PLAIN && op.i[11] == 1) {       // hi + lo fp16 output
-        if (op.i[17] != T2V_F16 || op.i[16] != T2V_EPI_NONE || op.i[8] == 1 || op.i[5] < 2 * N)
-          return bad("hi + lo output: fp16 out, plain epilogue, no fused LayerNorm, ldc >= 2 N");
-      }
-      if (g == T2V_GATHER_PLAIN && op.i[8] == 2) {         // LayerNorm second output across the column tiles (grid barrier)
-        if (!t2v_tile_fuses(tile, T2V_TILE_LNX, N) || op.i[19] > 1 || op.i[16] != T2V_EPI_NONE ||
-            op.i[17] != T2V_F32 || op.i[18] != 0 || op.i[20] != 0 || K % 64 != 0 || op.i[11] == 1)
-          return bad("cross-tile LayerNorm output: tile 0 (N % 128 == 0), 3, 5, 9 or 12, fp32 out, plain epilogue, no split-K / activation");
-        if (op.p[3] == 0 || op.p[7] == 0 || op.p[10] == 0 || op.p[11] == 0 || op.i[9] < N || op.i[9] % 4 != 0)
-          return bad("cross-tile LayerNorm output: gamma|beta, output, scratch, barrier words or leading dimension");
-        if (op.i[5] < N || (op.p[4] != 0 && (op.i[6] < N || op.i[6] % 4 != 0))) return bad("cross-tile LayerNorm output: ldc / ldr must be >= N and multiples of 4");
-      }
-      if (g == T2V_GATHER_PLAIN && op.i[8] == 1) {
-        if (!t2v_tile_fuses(tile, T2V_TILE_LN, N) || op.i[19] > 1 || op.i[16] != T2V_EPI_NONE || op.i[17] != T2V_F32 || op.i[18] != 0 || op.i[20] != 0 ||
-            K % 64 != 0)
-          return bad("fused LayerNorm output needs a whole-row tile (192x320, 128x320 or 256x320), N == 320, fp32 out, no split-K / activation");
-        if (op.p[3] == 0 || op.p[7] == 0 || op.i[9] < N || op.i[9] % 4 != 0) return bad("fused LayerNorm output: gamma|beta, output pointer or leading dimension");
-        // the epilogue moves whole f32x4 / f16x4 groups without tail guards
-        if (op.i[5] < N || (op.p[4] != 0 && (op.i[6] < N || op.i[6] % 4 != 0))) return bad("fused LayerNorm output: ldc / ldr must be >= N and multiples of 4");
-      }
-      return 0;
+      const GemmView g = gemm_decode(op);
+      return g.form == GEMM_MALFORMED ? bad(g.why) : 0;
     }
     case T2V_OP_GROUPNORM: {
       const int C = op.i[2], groups = op.i[4], phase = op.i[8], nparts = op.i[9] > 0 ? op.i[9] : 1;
@@ -171,33 +236,8 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[3] == 0) return bad("null LayerNorm pointer");
       return 0;
     case T2V_OP_ATTENTION: {
-      const int d = op.i[14] > 0 ? op.i[14] : 64;
-      if (op.i[0] <= 0 || op.i[1] <= 0 || op.i[2] <= 0 || op.i[3] <= 0 || op.i[4] <= 0) return bad("empty attention");
-      if (d != 40 && d != 64 && d != 80 && d != 160) return bad("attention head_dim must be 40, 64, 80 or 160");
-      for (int k = 5; k <= 13; ++k)
-        if (op.i[k] < 0) return bad("negative attention stride");
-      if (op.i[15] != 0 && op.i[0] != op.i[1]) return bad("causal attention needs nq == nk");
-      if (op.i[16] < 0) return bad("negative low-order output offset");
-      if (!(op.f[0] > 0.f)) return bad("attention scale must be > 0");
-      if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[3] == 0) return bad("null attention pointer");
-      if (op.p[6] != 0 && (d != 64 || op.i[15] != 0 || op.i[17] < op.i[1] || op.i[17] % 64 != 0 || (op.i[18] != 0 && op.i[18] != 4 && op.i[18] != 8)))
-        return bad("attention with a V^T scratch (p[6]): head_dim 64, not causal, i[17] = keys padded to a multiple of 64, i[18] = 0 | 4 | 8 waves");
-      if (op.i[19] != 0) {       // second role: outer samples >= i[19] have their own key count and K / V rows
-        if (op.i[19] < 0 || op.i[19] >= op.i[3] || op.i[20] <= 0 || op.i[21] < 0 || op.p[4] == 0 || op.p[5] == 0)
-          return bad("attention second role: 0 < i[19] < batch_outer, i[20] keys > 0, sample stride i[21] >= 0, K / V bases p[4], p[5]");
-        if (op.i[15] != 0 || op.p[6] != 0) return bad("attention second role: not for causal launches or the V^T scratch path");
-      }
-      if (op.i[22] != 0 || op.i[23] != 0 || op.i[24] != 0) {       // per-sample table: every outer sample has its own key count and first K / V row
-        if (op.p[7] == 0) return bad("attention per-sample table: null table p[7]");
-        if (op.i[22] != op.i[3] || op.i[23] <= 0 || op.i[24] < op.i[23])
-          return bad("attention per-sample table: i[22] rows == batch_outer, i[23] largest key count > 0, i[24] K / V rows spanned >= i[23]");
-        if (op.i[19] != 0 || op.i[20] != 0 || op.i[21] != 0 || op.p[4] != 0 || op.p[5] != 0) return bad("attention per-sample table: not together with the second role (i[19..21], p[4], p[5])");
-        if (op.i[15] != 0) return bad("attention per-sample table: not for causal launches");
-        if (op.p[6] != 0) return bad("attention per-sample table: not for the V^T scratch path (p[6])");
-      } else if (op.p[7] != 0) {
-        return bad("attention table p[7] without its fields i[22..24]");
-      }
-      return 0;
+      const t2v_attention_class c = t2v_attention_classify(op);
+      return c.form == T2V_ATTN_MALFORMED ? bad(c.why) : 0;
     }
     case T2V_OP_RELPOS_ATTN:
       if (op.i[17] == 3) {
@@ -349,88 +389,52 @@ int validate_op(const t2v_op& op, int idx) {
   }
 }
 
-// The parameter block of a GEMM record, up to what every epilogue shares (launch_op adds the fused attention / LayerNorm parts)
-GemmParams gemm_params(const t2v_op& op) {
+// The parameter block of a decoded GEMM record, complete for every form (a fused-norm form draws its launch's exchange sequence number here)
+GemmParams gemm_params(const GemmView& v) {
   GemmParams p;
   memset(&p, 0, sizeof p);
-  p.M = op.i[0]; p.N = op.i[1]; p.K = op.i[2];
-  p.lda = op.i[3]; p.ldw = op.i[4]; p.ldc = op.i[5]; p.ldr = op.i[6];
-  p.gather = op.i[7];
-  if (p.gather == T2V_GATHER_TCONV3) { p.F = op.i[8]; p.HW = op.i[9]; }
-  else { p.Hin = op.i[8]; p.Win = op.i[9]; }
-  p.Cin = op.i[10]; p.stride = op.i[11]; p.up = op.i[12]; p.Hout = op.i[13]; p.Wout = op.i[14];
-  p.rows_per_batch = op.i[15] > 0 ? op.i[15] : 1;
-  p.epi = op.i[16]; p.out_f32 = op.i[17] == T2V_F32; p.act = op.i[18];
-  if (p.epi == T2V_EPI_STATS) { p.epi = T2V_EPI_NONE; p.stats = reinterpret_cast<float*>(op.p[7]); }   // (validated: no split-K -> p[7] is not a ticket buffer)
-  if (p.epi == T2V_EPI_GN) {                                  // GroupNorm (+SiLU) of the result inside the epilogue (validated above)
-    p.epi = T2V_EPI_NONE;
-    p.gn_gb = reinterpret_cast<const float*>(op.p[8]);
-    p.gn_out = reinterpret_cast<f16*>(op.p[9]);
-    p.gn_part = reinterpret_cast<double*>(op.p[10]);
-    p.gn_bar = reinterpret_cast<unsigned*>(op.p[11]);
+  p.M = v.M; p.N = v.N; p.K = v.K;
+  p.lda = v.lda; p.ldw = v.ldw; p.ldc = v.ldc; p.ldr = v.ldr; p.ldrb = v.ldrb;
+  p.gather = v.gather;
+  p.Hin = v.Hin; p.Win = v.Win; p.Cin = v.Cin; p.stride = v.stride; p.up = v.up; p.Hout = v.Hout; p.Wout = v.Wout; p.F = v.F; p.HW = v.HW;
+  p.rows_per_batch = v.rows_per_batch;
+  p.epi = v.form == GEMM_GEGLU || v.form == GEMM_TATTN ? v.epi : T2V_EPI_NONE;      // statistics, GroupNorm, cross-attention: the plain epilogue + their pointers
+  p.out_f32 = v.out_dtype == T2V_F32; p.act = v.act; p.splitk = v.split; p.bias_m = v.bias_m; p.halo = v.halo;
+  auto ptr = [](auto& dst, uint64_t a) { dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(a); };
+  ptr(p.A, v.A); ptr(p.W, v.W); ptr(p.bias, v.bias); ptr(p.rowbias, v.rowbias); ptr(p.res, v.res); ptr(p.out, v.out); ptr(p.ws, v.ws); ptr(p.stats, v.stats);
+  if (v.split > 1) ptr(p.tickets, v.tickets);
+  p.out_lo = v.out_lo; p.res_wrap = v.res_wrap; p.a_wrap = v.a_wrap;
+  const bool gn = gemm_writes_gn(v.form), ln = v.form == GEMM_LN_ROW || v.form == GEMM_LN_CROSS;
+  if (gn) {
+    ptr(p.gn_gb, v.gn_gb); ptr(p.gn_out, v.gn_out);
+    p.gn_rows = v.gn_rows; p.ld_gn = v.ld_gn; p.gn_silu = v.gn_silu; p.gn_lo = v.gn_lo ? v.N : 0;
+    p.gn_cpg = v.N / v.gn_groups; p.gn_store_out = v.gn_skip_out ? 0 : 1; p.gn_eps = v.gn_eps;
+  }
+  if (ln) {       // a whole-row tile, N == its columns — or, GEMM_LN_CROSS, across the column tiles
+    ptr(p.ln_gb, v.ln_gb); ptr(p.ln_out, v.ln_out);
+    p.ld_ln = v.ld_ln; p.ln_eps = v.ln_eps; p.ln_x = v.form == GEMM_LN_CROSS;
+  }
+  if (gn || v.form == GEMM_LN_CROSS) {       // the exchange between the tiles of the launch
+    ptr(p.gn_part, v.scratch); ptr(p.gn_bar, v.barrier);
     p.gn_fault = t2v_coop_fault_word();
-    p.gn_rows = op.i[24]; p.ld_gn = op.i[25]; p.gn_silu = op.i[26]; p.gn_lo = op.i[27] ? op.i[1] : 0;
-    p.gn_cpg = op.i[1] / op.i[28]; p.gn_store_out = op.i[29] ? 0 : 1;
-    p.gn_eps = op.f[2];
     t2v_exchange_ids(&p.gn_seq, &p.gn_want);
   }
-  p.splitk = op.i[19] > 1 ? op.i[19] : 1;
-  p.bias_m = op.i[20]; p.ldrb = op.i[21];
-  p.A = reinterpret_cast<const f16*>(op.p[0]);
-  p.W = reinterpret_cast<const f16*>(op.p[1]);
-  p.bias = reinterpret_cast<const float*>(op.p[2]);
-  p.rowbias = reinterpret_cast<const float*>(op.p[3]);
-  p.res = reinterpret_cast<const float*>(op.p[4]);
-  p.out = reinterpret_cast<void*>(op.p[5]);
-  p.ws = reinterpret_cast<float*>(op.p[6]);
-  p.halo = op.i[23];
-  p.out_lo = (p.gather == T2V_GATHER_PLAIN && op.i[11] == 1) ? 1 : 0;
-  if (p.gather == T2V_GATHER_PLAIN && op.i[16] != T2V_EPI_TATTN) { p.res_wrap = op.i[12]; p.a_wrap = op.i[13]; }
-  if (op.i[30] > 0) p.res_wrap = op.i[30];                    // (validated: not beside i[12])
+  if (v.form == GEMM_XATTN) {
+    ptr(p.xa_k, v.xa_k); ptr(p.xa_vt, v.xa_vt);
+    p.xa_ldk = v.xa_ldk; p.xa_lc = v.xa_lc; p.xa_lcp = v.xa_lcp; p.xa_k_sample = v.xa_k_sample; p.xa_vt_sample = v.xa_vt_sample;
+  }
+  if (v.form == GEMM_TATTN) { p.tpix = v.tpix; p.tiles_ps = (v.HW + v.tpix - 1) / v.tpix; }
+  if (v.form == GEMM_TATTN || v.form == GEMM_XATTN) p.attn_scale_log2 = v.attn_scale * 1.44269504088896340736f;
   return p;
 }
-
 hipError_t launch_op(const t2v_op& op, hipStream_t s) {
   switch (op.kind) {
     case T2V_OP_GEMM: {
-      GemmParams p = gemm_params(op);
-      const int tile = op.i[22];
-      const t2v_tile* tt = t2v_tile_of(tile);
-      if (p.epi == T2V_EPI_TATTN) {                              // fused QKV projection + temporal attention (validated: its own tile)
-        p.F = op.i[8]; p.HW = op.i[9]; p.tpix = op.i[10];
-        p.tiles_ps = (p.HW + p.tpix - 1) / p.tpix;
-        p.attn_scale_log2 = op.f[1] * 1.44269504088896340736f;
-        p.Hin = p.Win = 0; p.Cin = 0;
-        return t2v_launch_gemm2(p, tile, s);
-      }
-      // split-K: p[7] = T2V_SYNC_INTS zeroed ints -> the fold runs in the GEMM's last-arriving workgroups; 0 -> reduction kernel
-      if (p.epi == T2V_EPI_XATTN) {                              // fused to_q + text cross-attention (validated above)
-        p.epi = T2V_EPI_NONE;
-        p.xa_k = reinterpret_cast<const f16*>(op.p[8]);
-        p.xa_vt = reinterpret_cast<const f16*>(op.p[9]);
-        p.xa_ldk = op.i[24]; p.xa_lc = op.i[25]; p.xa_lcp = op.i[26]; p.xa_k_sample = op.i[27]; p.xa_vt_sample = op.i[28];
-        p.attn_scale_log2 = op.f[1] * 1.44269504088896340736f;
-      }
-      const bool ln_any = p.gather == T2V_GATHER_PLAIN && (op.i[8] == 1 || op.i[8] == 2);
-      if (p.splitk > 1 && !ln_any) p.tickets = reinterpret_cast<int*>(op.p[7]);
-      if (ln_any) {       // fused LayerNorm second output (validated: a whole-row tile, N == its columns — or, i[8] == 2, across column tiles; TATTN returned above)
-        p.ln_gb = reinterpret_cast<const float*>(op.p[3]);
-        p.rowbias = nullptr;
-        p.ln_out = reinterpret_cast<f16*>(op.p[7]);
-        p.ld_ln = op.i[9];
-        p.ln_eps = op.f[0];
-        if (op.i[8] == 2) {
-          p.ln_x = 1;
-          p.ln_out = reinterpret_cast<f16*>(op.p[7]);
-          p.gn_part = reinterpret_cast<double*>(op.p[10]);
-          p.gn_bar = reinterpret_cast<unsigned*>(op.p[11]);
-          p.gn_fault = t2v_coop_fault_word();
-          t2v_exchange_ids(&p.gn_seq, &p.gn_want);
-        }
-      }
-      // the large-tile kernel advances its source pointers by whole k-tiles: needs K % BK == 0
-      if (tt != nullptr && tt->has(T2V_TILE_GEMM2) && !tt->has(T2V_TILE_TATTN_ONLY) && p.gather != T2V_GATHER_CONV3X3_C8 && p.K % 64 == 0) return t2v_launch_gemm2(p, tile, s);
-      return t2v_launch_gemm(p, s);
+      const GemmView v = gemm_decode(op);
+      if (v.form == GEMM_MALFORMED) return hipErrorInvalidValue;      // (every caller has validated the record)
+      // the large-tile kernel advances its source pointers by whole k-tiles: needs K % BK == 0; the fused temporal attention has its own tile there
+      const bool gemm2 = v.form == GEMM_TATTN || (v.tile->has(T2V_TILE_GEMM2) && v.gather != T2V_GATHER_CONV3X3_C8 && v.K % 64 == 0);
+      return gemm2 ? t2v_launch_gemm2(gemm_params(v), v.tile->id, s) : t2v_launch_gemm(gemm_params(v), s);
     }
     case T2V_OP_GROUPNORM: return t2v_launch_groupnorm(op, s);
     case T2V_OP_LAYERNORM: return t2v_launch_layernorm(op, s);
@@ -492,7 +496,7 @@ unsigned output_slots(const t2v_op& op) {
   if (ddim == T2V_DDIM_MEASURE) return bits({7});      // the measure pass writes the threshold table and nothing else
   if (ddim == T2V_DDIM_INVERT) return bits({3, 4});    // the inversion step: p[4] is a second destination (the kept intermediate), not the blend's known x0
   switch (op.kind) {
-    case T2V_OP_GEMM: return bits({5, 6, 7, 10, 11}) | (op.i[16] == T2V_EPI_GN ? bits({9}) : 0u);
+    case T2V_OP_GEMM: return bits({5, 6, 7, 10, 11}) | (gemm_writes_gn(gemm_decode(op).form) ? bits({9}) : 0u);      // p[9] is V^T, an input, under XATTN
     case T2V_OP_GROUPNORM: return bits({3, 4, 5, 7, 8});
     case T2V_OP_LAYERNORM: return bits({3});
     case T2V_OP_ATTENTION: return bits({3, 6});
@@ -548,48 +552,45 @@ bool slot_range(const t2v_op& op, int q, SlotRange* out) {
   const int f32 = T2V_F32;
   switch (op.kind) {
     case T2V_OP_GEMM: {
-      const int64_t M = I[0], N = I[1], K = I[2], lda = I[3], ldw = I[4], ldc = I[5], ldr = I[6];
-      const int g = I[7], epi = I[16], oitem = I[17] == f32 ? 4 : 2, split = I[19] > 1 ? I[19] : 1;
-      if (epi == T2V_EPI_TATTN) {
-        const int64_t tiles_ps = (I[9] + I[10] - 1) / I[10], T = M / 192 / tiles_ps * I[8] * I[9];
-        if (q == 0) return mat(T, K, lda, 2);
-        if (q == 1) return mat(N, K, ldw, 2);
-        if (q == 5) return mat(T, N / 192 * 64, ldc, 2);
-        return span(~0ull >> 2);
-      }
-      if (epi == T2V_EPI_XATTN) {
-        const int64_t samples = M / I[15], Lc = I[25];
-        if (q == 0) return mat(I[13] ? I[13] : M, K, lda, 2);
-        if (q == 1) return mat(N, K, ldw, 2);
-        if (q == 5) return mat(M, N, ldc, 2);
-        if (q == 8) return span((uint64_t)((samples - 1) * I[27] + (Lc - 1) * I[24] + N) * 2);
-        if (q == 9) return span((uint64_t)((samples - 1) * I[28] + (N - 1) * I[26] + I[26]) * 2);
-        return span(~0ull >> 2);
-      }
-      const int64_t n_out = epi == T2V_EPI_GEGLU ? N / 2 : N;
-      const bool ln = g == T2V_GATHER_PLAIN && (I[8] == 1 || I[8] == 2);
-      switch (q) {
-        case 0:
-          if (g == T2V_GATHER_PLAIN) return mat(I[13] ? I[13] : M, K, lda, 2);
-          if (g == T2V_GATHER_TCONV3) return mat(M / ((int64_t)I[8] * I[9]) * (I[8] + (I[23] ? 2 : 0)) * I[9], I[10], lda, 2);
-          return mat(M / ((int64_t)I[13] * I[14]) * I[8] * I[9], I[10], lda, 2);
-        case 1: return mat(N, K, ldw, 2);
-        case 2: return flat((uint64_t)(I[20] ? M : N) * 4);
-        case 3: return ln ? flat((uint64_t)2 * N * 4) : mat((M + (I[15] > 0 ? I[15] : 1) - 1) / (I[15] > 0 ? I[15] : 1), N, I[21], 4);
-        case 4: {
-          const int64_t rw = I[30] > 0 ? I[30] : (g == T2V_GATHER_PLAIN ? I[12] : 0);
-          return mat(rw ? rw : M, n_out, ldr, 4);
+      const GemmView g = gemm_decode(op);
+      const int64_t M = g.M, N = g.N, K = g.K;
+      if (q == 1 && g.form != GEMM_MALFORMED) return mat(N, K, g.ldw, 2);
+      switch (g.form) {
+        case GEMM_MALFORMED: return span(~0ull >> 2);
+        case GEMM_TATTN: {
+          const int64_t tiles_ps = (g.HW + g.tpix - 1) / g.tpix, T = M / 192 / tiles_ps * g.F * g.HW;
+          if (q == 0) return mat(T, K, g.lda, 2);
+          if (q == 5) return mat(T, N / 192 * 64, g.ldc, 2);
+          return span(~0ull >> 2);
         }
+        case GEMM_XATTN: {
+          const int64_t samples = M / g.rows_per_batch, Lc = g.xa_lc;
+          if (q == 0) return mat(g.a_wrap ? g.a_wrap : M, K, g.lda, 2);
+          if (q == 5) return mat(M, N, g.ldc, 2);
+          if (q == 8) return span((uint64_t)((samples - 1) * g.xa_k_sample + (Lc - 1) * g.xa_ldk + N) * 2);
+          if (q == 9) return span((uint64_t)((samples - 1) * g.xa_vt_sample + (N - 1) * g.xa_lcp + g.xa_lcp) * 2);
+          return span(~0ull >> 2);
+        }
+        default: break;
+      }
+      switch (q) {       // every other form: the slot's role is the one the view gave it
+        case 0:
+          if (g.gather == T2V_GATHER_PLAIN) return mat(g.a_wrap ? g.a_wrap : M, K, g.lda, 2);
+          if (g.gather == T2V_GATHER_TCONV3) return mat(M / ((int64_t)g.F * g.HW) * (g.F + (g.halo ? 2 : 0)) * g.HW, g.Cin, g.lda, 2);
+          return mat(M / ((int64_t)g.Hout * g.Wout) * g.Hin * g.Win, g.Cin, g.lda, 2);
+        case 2: return flat((uint64_t)(g.bias_m ? M : N) * 4);
+        case 3: return g.ln_gb != 0 ? flat((uint64_t)2 * N * 4) : mat((M + g.rows_per_batch - 1) / g.rows_per_batch, N, g.ldrb, 4);
+        case 4: return mat(g.res_wrap ? g.res_wrap : M, g.n_out, g.ldr, 4);
         case 5:
-          if (g == T2V_GATHER_PLAIN && I[11] == 1) { mat(M, 2 * N, ldc, 2); return true; }
-          return mat(M, n_out, ldc, oitem);
-        case 6: return flat((uint64_t)split * M * N * 4);
+          if (g.out_lo) { mat(M, 2 * N, g.ldc, 2); return true; }
+          return mat(M, g.n_out, g.ldc, g.out_item);
+        case 6: return flat((uint64_t)g.split * M * N * 4);
         case 7:
-          if (ln) return mat(M, N, I[9], 2);
-          if (epi == T2V_EPI_STATS) return flat((uint64_t)((M + 31) / 32) * 2 * N * 4);
+          if (g.ln_out != 0) return mat(M, N, g.ld_ln, 2);
+          if (g.stats != 0) return flat((uint64_t)((M + 31) / 32) * 2 * N * 4);
           return flat((uint64_t)T2V_SYNC_INTS * 4);
-        case 8: return flat((uint64_t)2 * N * 4);
-        case 9: return mat(M, N * (I[27] ? 2 : 1), I[25], 2);
+        case 8: return flat((uint64_t)2 * N * 4);                                  // GroupNorm gamma | beta
+        case 9: return mat(M, N * (g.gn_lo ? 2 : 1), g.ld_gn, 2);                  // GroupNorm output
         case 10: return flat(T2V_GN_PART_BYTES);
         case 11: return flat((uint64_t)T2V_SYNC_BARRIER_INTS * 4);
       }
@@ -625,7 +626,7 @@ bool slot_range(const t2v_op& op, int q, SlotRange* out) {
         return span((uint64_t)((outer - 1) * outer_stride + (bi - 1) * I[s0 + 2] + (n - 1) * I[s0] + heads * D) * 2);
       };
       if (q == 0) return seq(nq, 5, bo, I[6]);
-      if (!rel && I[22] != 0) {     // per-sample table: K / V are the I[24] packed rows the table spans; the table itself is I[22] pairs of int32
+      if (!rel && t2v_attention_classify(op).form == T2V_ATTN_TABLE) {     // K / V are the I[24] packed rows the table spans; the table itself is I[22] pairs of int32
         if (q == 1 || q == 2) return seq(I[24], 8, 1, 0);
         if (q == 7) return flat((uint64_t)I[22] * 8);
       }
@@ -730,31 +731,30 @@ bool slot_range(const t2v_op& op, int q, SlotRange* out) {
 // a few hundred rows.)
 bool ff_pair(const t2v_op* ops, int n, int k) {
   if (!ff_fuse_enabled() || k + 1 >= n) return false;
-  const t2v_op &a = ops[k], &b = ops[k + 1];
-  if (a.kind != T2V_OP_GEMM || b.kind != T2V_OP_GEMM) return false;
-  const int M = a.i[0];
-  // the GEGLU GEMM: plain gather, no split-K, N = 2560, K = 320, fp16 out, nothing but a bias beside it
-  if (a.i[16] != T2V_EPI_GEGLU || a.i[7] != T2V_GATHER_PLAIN || a.i[19] > 1 || a.i[1] != 2560 || a.i[2] != 320 || a.i[17] != T2V_F16) return false;
-  if (a.i[3] < 320 || a.i[4] < 320 || a.i[5] < 1280 || a.i[8] != 0 || a.i[11] != 0 || a.i[12] != 0 || a.i[13] != 0 || a.i[18] != 0 || a.i[20] != 0 || a.i[30] != 0) return false;
-  if (a.p[0] == 0 || a.p[1] == 0 || a.p[3] != 0 || a.p[4] != 0 || a.p[5] < T2V_EXT_SLOTS) return false;
-  // the projection: plain gather and epilogue, no split-K, N = 320, K = 1280, no fused norm, A = exactly that hidden tensor
-  if (b.i[16] != T2V_EPI_NONE || b.i[7] != T2V_GATHER_PLAIN || b.i[19] > 1 || b.i[1] != 320 || b.i[2] != 1280 || b.i[8] != 0) return false;
-  if (b.i[0] != M || b.p[0] != a.p[5] || b.i[3] != a.i[5] || b.i[4] < 1280 || b.i[13] != 0 || b.i[20] != 0 || b.p[1] == 0 || b.p[5] == 0) return false;
-  if (b.i[12] != 0 && b.i[30] != 0) return false;
-  if (M < (a.i[31] == 1 ? 1 : ff_min_m())) return false;
+  if (ops[k].kind != T2V_OP_GEMM || ops[k + 1].kind != T2V_OP_GEMM) return false;
+  const GemmView a = gemm_decode(ops[k]), b = gemm_decode(ops[k + 1]);          // (validated records: a wrap is never negative, never given twice)
+  const int M = a.M;
+  // the GEGLU GEMM: plain gather, 2560 x 320, fp16 out, no split-K, nothing beside a bias — no LayerNorm or hi + lo word, wrap, activation, row bias, residual
+  if (a.form != GEMM_GEGLU || a.gather != T2V_GATHER_PLAIN || a.split > 1 || a.N != 2560 || a.K != 320 || a.out_dtype != T2V_F16) return false;
+  if (a.lda < 320 || a.ldw < 320 || a.ldc < 1280 || a.ln_mode != 0 || a.hilo != 0 || a.res_wrap != 0 || a.a_wrap != 0 || a.act != 0 || a.bias_m != 0) return false;
+  if (a.A == 0 || a.W == 0 || a.rowbias != 0 || a.res != 0 || a.out < T2V_EXT_SLOTS) return false;
+  // the projection: plain gather and epilogue, 320 x 1280, no split-K, no fused norm, A = exactly that hidden tensor
+  if (b.form != GEMM_PLAIN || b.gather != T2V_GATHER_PLAIN || b.split > 1 || b.N != 320 || b.K != 1280 || b.ln_mode != 0) return false;
+  if (b.M != M || b.A != a.out || b.lda != a.ldc || b.ldw < 1280 || b.a_wrap != 0 || b.bias_m != 0 || b.W == 0 || b.out == 0) return false;
+  if (M < (a.waive_min_m ? 1 : ff_min_m())) return false;
   // One launch reads X, W1 and b1 until its last workgroup is done, while the first ones already store their rows of the result: the
   // result must not lie over them.  (The lowerings do hand the projection the dead X buffer as its output, with rows twice as long:
   // as two launches that is safe, as one launch a workgroup would store over rows another one has yet to read.)
   {
-    if (a.p[0] < T2V_EXT_SLOTS || a.p[1] < T2V_EXT_SLOTS || (a.p[2] != 0 && a.p[2] < T2V_EXT_SLOTS) || b.p[5] < T2V_EXT_SLOTS) return false;
-    const uint64_t o0 = b.p[5], o1 = o0 + ((uint64_t)(M - 1) * b.i[5] + 320 * (b.i[11] == 1 ? 2 : 1)) * (b.i[17] == T2V_F32 ? 4 : 2);
+    if (a.A < T2V_EXT_SLOTS || a.W < T2V_EXT_SLOTS || (a.bias != 0 && a.bias < T2V_EXT_SLOTS) || b.out < T2V_EXT_SLOTS) return false;
+    const uint64_t o0 = b.out, o1 = o0 + ((uint64_t)(M - 1) * b.ldc + 320 * (b.out_lo ? 2 : 1)) * b.out_item;
     auto apart = [&](uint64_t r0, uint64_t bytes) { return r0 == 0 || o1 <= r0 || o0 >= r0 + bytes; };
-    if (!apart(a.p[0], ((uint64_t)(M - 1) * a.i[3] + 320) * 2) || !apart(a.p[1], ((uint64_t)2559 * a.i[4] + 320) * 2) || !apart(a.p[2], 2560 * 4)) return false;
+    if (!apart(a.A, ((uint64_t)(M - 1) * a.lda + 320) * 2) || !apart(a.W, ((uint64_t)2559 * a.ldw + 320) * 2) || !apart(a.bias, 2560 * 4)) return false;
   }
   // nothing else may read the hidden tensor: scan the records behind the GEGLU GEMM, by EXTENT (slot_range), until the whole tensor has
   // been rewritten.  A record that reaches into bytes of it that no record has rewritten since — through a window that starts below it
   // as well as through a pointer inside it — reads what a fused pair never stored.  Only a dense output range proves a rewrite.
-  const uint64_t lo = a.p[5], hi = lo + ((uint64_t)(M - 1) * a.i[5] + 1280) * 2;
+  const uint64_t lo = a.out, hi = lo + ((uint64_t)(M - 1) * a.ldc + 1280) * 2;
   std::vector<std::pair<uint64_t, uint64_t>> left{{lo, hi}};          // bytes of the hidden tensor not rewritten yet
   std::vector<SlotRange> strided;                                      // strided output ranges that reached into them since
   for (int j = k + 1; j < n && !left.empty(); ++j) {
@@ -805,7 +805,7 @@ bool ff_pair(const t2v_op* ops, int n, int k) {
   return true;
 }
 
-hipError_t launch_ff_pair(const t2v_op& a, const t2v_op& b, hipStream_t s) { return t2v_launch_ff_fused(gemm_params(a), gemm_params(b), s); }
+hipError_t launch_ff_pair(const t2v_op& a, const t2v_op& b, hipStream_t s) { return t2v_launch_ff_fused(gemm_params(gemm_decode(a)), gemm_params(gemm_decode(b)), s); }
 
 // fused (plans only): fused[k] != 0 -> ops k and k + 1 run as ONE launch (ff_pair); ms[k] is that launch, ms[k + 1] exactly 0
 int run_resolved(const t2v_op* ops, int n, const uint64_t* ext, int n_ext, hipStream_t s, float* ms, t2v_comm* comm = nullptr,

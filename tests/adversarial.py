@@ -333,7 +333,7 @@ for _T, _Tq, _offs, _Ds in ((5, 2, (0, 2, 3), (40,)), (8, 3, (0, 3, 5), (80,)), 
 # ---- the keys of the requestable lattice (tests/geometry_lattice.py; profiles/geometry_paths.txt names a witness program for each): other ----
 # ---- latents and frame counts put every head dimension on every kernel form.  The size classes are the launcher's: attention.hip:1253-1255 ----
 # ---- (launch_attn: nq <= 32 -> one wave, with the 32-key tile when the keys fit one; else 4 waves per 128 queries, 64-key tiles),      ----
-# ---- attention.hip:1293-1294 (attn2_kernel<8>: 256 queries per workgroup) and, for nk_tiles, the key-tile loop that runs once or streams ----
+# ---- attention.hip t2v_launch_attention (attn2_kernel<8>: 256 queries per workgroup) and, for nk_tiles, the key-tile loop that runs once or streams ----
 ATTN_CASES += [
     # one wave, 64 + 13 keys (text cross-attention of a latent of at most 32 positions): ragged and whole query blocks
     _attn("lowered-cross-d80-nq16-nk77", "cross", 80, 2, 2, 2, 16, 77, 64, placement="second"),

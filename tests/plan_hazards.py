@@ -207,7 +207,7 @@ def output_slots(op):
 
 
 def _ff_shape(ops, k, A, min_m) -> bool:
-    """The record-shape conditions of ff_pair (csrc/executor.hip:732-744), shared by both models."""
+    """The record-shape conditions of ff_pair (csrc/executor.hip ff_pair, stated there on two decoded views), shared by both models."""
     if k + 1 >= len(ops):
         return False
     a, b = ops[k], ops[k + 1]

@@ -67,50 +67,50 @@ def gemm_keys(op):
     plain = gather == L.GATHER_PLAIN
     tile = I[22]
     geo = L.GEMM_TILES.get(tile)
-    # executor.hip:432 launch_op: a gemm2 tile runs gemm2.hip only for K % 64 == 0 and not the C8 stem; everything else is gemm.hip's kernel
+    # executor.hip launch_op: a gemm2 tile runs gemm2.hip only for K % 64 == 0 and not the C8 stem; everything else is gemm.hip's kernel
     gemm2 = geo is not None and geo.has(L.TILE_GEMM2) and (epi == L.EPI_TATTN or (gather != L.GATHER_CONV3X3_C8 and K % 64 == 0))
     kernel = tile if gemm2 else 0
     bm = L.GEMM_TILES[kernel].bm
     bn = L.GEMM_TILES[kernel].bn if gemm2 else L.tile0_bn(N)          # gemm.hip:422 t2v_launch_gemm: 128x64 when t2v_tile0_narrow(N)
-    ln = I[8] if plain and epi != L.EPI_TATTN and I[8] in (1, 2) else 0          # executor.hip:414 ln_any
+    ln = I[8] if plain and epi != L.EPI_TATTN and I[8] in (1, 2) else 0          # executor.hip gemm_decode: the LayerNorm forms
     split = 1 if epi in (L.EPI_TATTN, L.EPI_XATTN, L.EPI_STATS) or ln else _split_of(I, K)
     gn = epi == L.EPI_GN
     fold = "-"
     if split > 1:
-        # executor.hip:415 p.tickets = p[7]; t2v_kernels.h:239: kept only for the plain epilogue, <= T2V_SYNC_INTS tiles, no GroupNorm behind it;
+        # executor.hip gemm_decode / gemm_params: p[7] is the tickets of a split-K record; t2v_kernels.h:239: kept only for the plain epilogue, <= T2V_SYNC_INTS tiles, no GroupNorm behind it;
         # gemm.hip:431 / gemm2.hip:595: otherwise the reduction launch, with the GroupNorm in it when gn_out is set
         tiles = -(-M // bm) * -(-N // bn)
         fold = "tickets" if (_has(P[7]) and epi == L.EPI_NONE and tiles <= L.SYNC_INTS) else "reduce+gn" if gn else "reduce"
     slab = fold.startswith("reduce")
-    wrap = "i30" if I[30] > 0 else "i12" if (plain and epi != L.EPI_TATTN and I[12] > 0) else "-"      # executor.hip:388-389
+    wrap = "i30" if I[30] > 0 else "i12" if (plain and epi != L.EPI_TATTN and I[12] > 0) else "-"      # executor.hip gemm_decode res_wrap
     epilogue = [
-        ("epi", epi if not gn else L.EPI_NONE),                         # executor.hip:364-376, 399, 407; gemm.hip:418, gemm2.hip:538
-        ("out", I[17]),                                                 # executor.hip:363 out_f32; gemm.hip:68, t2v_kernels.h:954, norm.hip:562
+        ("epi", epi if not gn else L.EPI_NONE),                         # executor.hip gemm_params p.epi; gemm.hip:418, gemm2.hip:538
+        ("out", I[17]),                                                 # executor.hip gemm_params out_f32; gemm.hip:68, t2v_kernels.h:954, norm.hip:562
         ("act", I[18]),                                                 # gemm.hip:51-53; t2v_kernels.h:471-472
         ("bias", _has(P[2])),                                           # gemm.hip:38; t2v_kernels.h:455; norm.hip:548
         ("bias_m", int(I[20] != 0) if _has(P[2]) else 0),               # t2v_kernels.h:469
-        ("rowbias", _has(P[3]) if not ln else 0),                       # gemm.hip:47; norm.hip:559; executor.hip:418 (p[3] is gamma | beta under ln_any)
+        ("rowbias", _has(P[3]) if not ln else 0),                       # gemm.hip:47; norm.hip:559; executor.hip gemm_decode (p[3] is gamma | beta under the LayerNorm forms)
         ("res", _has(P[4])),                                            # gemm.hip:56; t2v_kernels.h:556; norm.hip:560
         ("res_wrap", wrap if _has(P[4]) else "-"),                      # gemm.hip:57; t2v_kernels.h:429
-        ("out_lo", int(plain and I[11] == 1)),                          # executor.hip:387; gemm.hip:68
+        ("out_lo", int(plain and I[11] == 1)),                          # executor.hip gemm_decode out_lo; gemm.hip:68
     ]
     main = [
         ("kind", "GEMM"),
-        ("tile", kernel),                                               # executor.hip:397 / 432; gemm2.hip:787 t2v_launch_gemm2 switch
+        ("tile", kernel),                                               # executor.hip launch_op; gemm2.hip:787 t2v_launch_gemm2 switch
         ("tile0_bn", bn if kernel == 0 else 0),                         # gemm.hip:422-428
         ("gather", gather),                                             # gemm.hip:397 launch_tile switch; gemm2.hip:549 launch_cfg switch
-        ("stride", I[11] if gather in (L.GATHER_CONV3X3, L.GATHER_CONV3X3_C8) else 0),      # executor.hip:361; gemm.hip:182 / gemm2.hip:127 tap arithmetic
+        ("stride", I[11] if gather in (L.GATHER_CONV3X3, L.GATHER_CONV3X3_C8) else 0),      # executor.hip gemm_decode stride; gemm.hip:182 / gemm2.hip:127 tap arithmetic
         ("up", int(I[12] != 0) if gather == L.GATHER_CONV3X3 else 0),   # gemm2.hip:582 G_CONV_UP instantiation
-        ("i23", int(I[23] != 0)),                                       # executor.hip:386 p.halo; gemm.hip:147 / 182, gemm2.hip:127 / 141
-        ("i13", int(plain and epi != L.EPI_TATTN and I[13] > 0)),       # executor.hip:388 a_wrap; gemm.hip:137, gemm2.hip:116
-        ("ln", ln),                                                     # executor.hip:416-429; gemm2.hip:564-575 XE_LN / XE_LNX
+        ("i23", int(I[23] != 0)),                                       # executor.hip gemm_decode halo; gemm.hip:147 / 182, gemm2.hip:127 / 141
+        ("i13", int(plain and epi != L.EPI_TATTN and I[13] > 0)),       # executor.hip gemm_decode a_wrap; gemm.hip:137, gemm2.hip:116
+        ("ln", ln),                                                     # executor.hip gemm_params (GEMM_LN_ROW / GEMM_LN_CROSS); gemm2.hip:564-575 XE_LN / XE_LNX
         ("fold", "slab" if slab else fold),                             # gemm.hip:346 / gemm2.hip:525 grid.y; t2v_kernels.h:233, 462
-        ("k_tail", int(K % 64 != 0)),                                   # executor.hip:432; gemm.hip K tail of the last k-tile
+        ("k_tail", int(K % 64 != 0)),                                   # executor.hip launch_op; gemm.hip K tail of the last k-tile
         ("m_ragged", int(M % bm != 0)),                                 # the m < p.M guards of every tail (t2v_kernels.h:461, 952)
         ("n_ragged", int(N % bn != 0)),                                 # the n < p.N guards (t2v_kernels.h:453, 948)
     ]
     if epi == L.EPI_XATTN:
-        # executor.hip:411: keys per sample and their padded count — t2v_epilogue_xattn walks key blocks of 32 up to xa_lcp
+        # executor.hip gemm_decode xa_lc / xa_lcp: keys per sample and their padded count — t2v_epilogue_xattn walks key blocks of 32 up to xa_lcp
         main += [("xa_ragged", int(I[25] % 32 != 0)), ("xa_blocks", min(-(-I[26] // 32), 4))]
     if ln == 2:
         cap = min(L.GEMM_TILES[kernel].per_cu * DEVICE_CUS, L.GN_PART_BYTES // (bm * 16))        # program.py:559
@@ -118,9 +118,9 @@ def gemm_keys(op):
     norm = []
     if gn:
         rows = I[24]
-        norm = [("gn_silu", int(I[26] != 0)),                          # executor.hip:372; norm.hip:794 dispatch_bool
-                ("gn_lo", int(I[27] != 0)),                            # executor.hip:372 gn_lo
-                ("i29", int(I[29] != 0))]                              # executor.hip:373 gn_store_out; t2v_kernels.h:941; norm.hip:561
+        norm = [("gn_silu", int(I[26] != 0)),                          # executor.hip gemm_params gn_silu; norm.hip:794 dispatch_bool
+                ("gn_lo", int(I[27] != 0)),                            # executor.hip gemm_params gn_lo
+                ("i29", int(I[29] != 0))]                              # executor.hip gemm_params gn_store_out; t2v_kernels.h:941; norm.hip:561
     if slab:
         second = [("kind", "GEMM.reduce+gn" if gn else "GEMM.reduce")] + epilogue + norm
         if gn:
@@ -185,19 +185,19 @@ def layernorm_key(op):
 def attention_key(op):
     I, P = op.i, op.p
     nq, nk = I[0], I[1]
-    alt = I[19] != 0                                                    # attention.hip:1253 second role
+    alt = I[19] != 0                                                    # attention.hip t2v_attention_classify: T2V_ATTN_SECOND_ROLE
     nkmax = max(nk, I[20]) if alt else nk
-    attn2 = _has(P[6])                                                  # attention.hip:1260
+    attn2 = _has(P[6])                                                  # attention.hip t2v_attention_classify: T2V_ATTN_VT
     if attn2:
-        kernel = "attn2<4>" if I[18] == 4 else "attn2<8>"              # attention.hip:1266-1267
+        kernel = "attn2<4>" if I[18] == 4 else "attn2<8>"              # attention.hip t2v_launch_attention (vt_waves)
     else:
-        kernel = "attn<1,32>" if nq <= 32 and nkmax <= 32 else "attn<1,64>" if nq <= 32 else "attn<4,64>"          # attention.hip:1229-1233
+        kernel = "attn<1,32>" if nq <= 32 and nkmax <= 32 else "attn<1,64>" if nq <= 32 else "attn<4,64>"          # attention.hip launch_attn
     tile = 32 if kernel == "attn<1,32>" else 64
     return (
         ("kind", "ATTENTION"),
-        ("head_dim", I[14] if I[14] > 0 else 64),                       # attention.hip:1259, 1270
-        ("causal", int(I[15] != 0)),                                    # attention.hip:1249
-        ("lo", int(I[16] != 0)),                                        # attention.hip:1250
+        ("head_dim", I[14] if I[14] > 0 else 64),                       # attention.hip t2v_attention_classify head_dim; t2v_launch_attention
+        ("causal", int(I[15] != 0)),                                    # attention.hip t2v_launch_attention p.causal
+        ("lo", int(I[16] != 0)),                                        # attention.hip t2v_launch_attention p.lo_off
         ("kernel", kernel),
         ("second_role", int(alt)),
         ("nk_tiles", min(-(-nkmax // tile), 2)),                       # one key tile, or the streaming loop
@@ -243,7 +243,7 @@ def elementwise_key(op):
         return (name,)
     if k == L.OP_COPY2D:               # elementwise.hip:1306-1321
         return (name, ("src", I[4]), ("dst", I[5]), ("act", I[6]), ("second", int(_has(P[2]) and I[4] == L.F32 and I[5] == L.F16)))
-    if k == L.OP_SOFTMAX:              # attention.hip:1282: one kernel; the column loop runs more than once past 256 columns
+    if k == L.OP_SOFTMAX:              # attention.hip t2v_launch_softmax: one kernel; the column loop runs more than once past 256 columns
         return (name, ("cols_gt_256", int(I[1] > 256)))
     if k == L.OP_DDIM_STEP:            # elementwise.hip:1368-1485
         return (name, ("eps", I[3]), ("x", I[4]), ("mode", I[5]), ("guided", int(I[2] != 0)), ("cps", int(0 < I[6] < I[0])), ("blend", int(I[7] != 0)),

@@ -220,7 +220,7 @@ def test_output_slots_mirror_the_executor():
     for kind, slots in re.findall(r"case T2V_OP_(\w+): return bits\(\{([\d, ]+)\}\)", body):
         found[getattr(FP, kind)] = tuple(int(v) for v in slots.split(","))
     assert found == H.OUTPUT_SLOTS
-    assert "op.i[16] == T2V_EPI_GN ? bits({9})" in body
+    assert "gemm_writes_gn(gemm_decode(op).form) ? bits({9})" in body          # (the two GroupNorm forms: T2V_EPI_GN with and without split-K)
 
 
 # accesses whose mode is not what output_slots says of their slot, each with its reason
