@@ -357,7 +357,22 @@ enum t2v_gather {
  *           read whenever it is given) — p[4..6] fp32, dense, shaped like x [samples, channels, inner].  Four elements per thread with
  *           128-bit accesses when every pointer that is read is 16-byte aligned, one element per thread otherwise.
  * LINCOMB: i: 0 n elements, 1 n terms (<= 6), 2 out dtype, 3..8 term dtypes; f: 0..5 coefficients;
- *      p: 0..5 terms, 6 out
+ *      p: 0..5 terms, 6 out;  i[9] = 0 (every record before the context windows leaves it zero).
+ *      The two context-window forms live here because the blend IS a linear combination, with a per-frame coefficient table instead of
+ *      f[0..5], and the gather is its transpose; the kind, its output slot p[6] and the ABI stay what they were.  Both share
+ *        i: 0 V videos, 1 C channels, 2 dtype of p[0] (fp16 | fp32), 3 F frames of the clip, 4 HW pixels per frame, 5 window length
+ *           (2 .. F), 6 nW windows per video;  p: 1 starts, int32 [nW] on the device: window w holds frames starts[w] .. starts[w] + length - 1
+ *      and batch row v * nW + w of a windowed forward is window w of video v (the window index runs fastest).  A start is clamped into
+ *      [0, F - length] where it is read; the table is validated by the host that builds it (every frame in some window).
+ *      form i[9] = 2, window gather: xw[r, c, j, :] = x[v, c, starts[w] + j, :] for the i[8] batch rows from row i[7] on, bit-exact.
+ *        i: 7 first batch row, 8 rows (i[7] + i[8] <= V * nW);  p: 0 x [V, C, F, HW], 6 xw [i[8], C, length, HW] of the same dtype.
+ *        16-byte units when HW * sizeof is a multiple of 16 and both bases are 16-byte aligned, one element per thread otherwise.
+ *      form i[9] = 1, window blend: out[role, v, c, f, :] = (sum_w wgt[f - starts[w]] * e[role, v * nW + w, c, f - starts[w], :]) / (sum_w wgt[f - starts[w]])
+ *        over the windows that hold frame f, in ascending w: acc = fma(wgt, e, acc) and wsum += wgt in fp32, then one division.  One
+ *        thread per output, no atomics: the value depends on the eps values alone.
+ *        i: 7 roles (2: [cond | uncond], 1: conditional only), 8 zero;  p: 0 e [roles, V * nW, C, length, HW] (dtype i[2]), 2 wgt fp32 [length],
+ *        6 out fp32 [roles, V, C, F, HW] — the eps pair every DDIM_STEP record reads.  Four neighbours per thread (16-byte stores) when
+ *        HW % 4 == 0 and the bases allow it, one element per thread otherwise.
  * MEMSET: i: 0 bytes (lo), 1 bytes (hi); p: 0 dst
  * EMBED_ROWS: out[r,:] = table[ids[r],:] + pos[r % L,:]   i: 0 rows, 1 width, 2 L, 3 vocab, 4 table dtype;
  *      p: 0 ids int32 [rows], 1 table [vocab,width], 2 pos fp32 [L,width], 3 out fp32 [rows,width]

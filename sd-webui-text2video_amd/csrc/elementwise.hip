@@ -553,6 +553,81 @@ __global__ __launch_bounds__(256) void lincomb_kernel(const LinParams p) {
   }
 }
 
+// ---- context windows (T2V_OP_LINCOMB forms i[9] = 2 and 1, include/t2v_hip.h) --------------------------------------------------------------
+// Batch row `row` of a windowed forward is window w = row % nW of video v = row / nW: frames starts[w] .. starts[w] + length - 1.  A start is
+// clamped into [0, F - length] where it is read, so that no table sends an access outside the clip; a table from ContextWindows.starts is
+// never changed by that.
+struct WindowGeom {
+  const int* starts;     // [nW] int32, ascending
+  int V, C, F, HW, length, nW;
+};
+
+__device__ __forceinline__ int window_start(const WindowGeom& g, int w) {
+  const int s = g.starts[w];
+  return min(max(s, 0), g.F - g.length);
+}
+
+// Gather: xw[r, c, j, :] = x[v, c, starts[w] + j, :] for the `rows` batch rows from `row0` on, a bit-exact copy.  U is the unit one thread
+// moves: uint4 (hw_units = HW * sizeof / 16) on the vector path, the element type (hw_units = HW) on the scalar path.
+template <typename U>
+__global__ __launch_bounds__(256) void window_gather_kernel(const U* __restrict__ x, U* __restrict__ xw, const WindowGeom g, int row0, int rows,
+                                                            int hw_units) {
+  const long per_frame = hw_units, per_chan = (long)g.length * per_frame, per_row = (long)g.C * per_chan;
+  const long total = (long)rows * per_row;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const long r = idx / per_row, in_row = idx - r * per_row;
+    const int c = (int)(in_row / per_chan);
+    const long in_chan = in_row - (long)c * per_chan;
+    const int j = (int)(in_chan / per_frame), u = (int)(in_chan - (long)j * per_frame);
+    const int row = row0 + (int)r, v = row / g.nW, w = row - v * g.nW;
+    const int f = window_start(g, w) + j;
+    xw[idx] = x[(((long)v * g.C + c) * g.F + f) * per_frame + u];
+  }
+}
+
+// Blend: out[role, v, c, f, :] = sum_w wgt[f - starts[w]] * e[role, v * nW + w, c, f - starts[w], :] / sum_w wgt[f - starts[w]] over the
+// windows that hold frame f, in ascending window order: acc = fma(wgt, e, acc), wsum += wgt, one division.  One thread per output element
+// (VEC = 1) or per four neighbours of a frame (VEC = 4, 16-byte stores); no thread shares an output, so nothing depends on the grid.
+template <typename TE, int VEC>
+__global__ __launch_bounds__(256) void window_blend_kernel(const TE* __restrict__ e, const float* __restrict__ wgt, float* __restrict__ out,
+                                                           const WindowGeom g, int roles) {
+  const int hw_units = g.HW / VEC;
+  const long total = (long)roles * g.V * g.C * g.F * hw_units;
+  const long rows_per_role = (long)g.V * g.nW;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const int u = (int)(idx % hw_units);
+    long rest = idx / hw_units;
+    const int f = (int)(rest % g.F); rest /= g.F;
+    const int c = (int)(rest % g.C); rest /= g.C;
+    const int v = (int)(rest % g.V);
+    const int role = (int)(rest / g.V);
+    float acc[VEC], wsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+    for (int w = 0; w < g.nW; ++w) {
+      const int j = f - window_start(g, w);
+      if (j < 0 || j >= g.length) continue;
+      const float wt = wgt[j];
+      const TE* src = e + ((((long)role * rows_per_role + (long)v * g.nW + w) * g.C + c) * g.length + j) * g.HW + (long)u * VEC;
+      if constexpr (VEC == 4) {
+        typedef TE TE4 __attribute__((ext_vector_type(4)));
+        const TE4 q = *reinterpret_cast<const TE4*>(src);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = __fmaf_rn(wt, (float)q[k], acc[k]);
+      } else {
+        acc[0] = __fmaf_rn(wt, (float)src[0], acc[0]);
+      }
+      wsum += wt;
+    }
+    float* dst = out + idx * VEC;
+    if constexpr (VEC == 4) {
+      *reinterpret_cast<float4*>(dst) = make_float4(acc[0] / wsum, acc[1] / wsum, acc[2] / wsum, acc[3] / wsum);
+    } else {
+      dst[0] = acc[0] / wsum;
+    }
+  }
+}
+
 // Row regrouping between the two layouts of a T-sharded clip (frame-sharded [frames][hw] rows <-> pixel-sharded
 // [frames][hw / R] rows): row r of the op reads source row (r / P) * S_src + r % P and writes destination row
 // (r / P) * S_dst + r % P (chunks of P rows, chunk strides in rows); optional fp32 residual, indexed like the
@@ -1591,7 +1666,71 @@ hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s) {
   return cls.form == T2V_DDIM_MALFORMED ? hipErrorInvalidValue : hipGetLastError();
 }
 
+const char* t2v_window_refusal(const t2v_op& op) {
+  const int32_t* I = op.i;
+  const bool blend = I[9] == 1;
+  const long V = I[0], C = I[1], F = I[3], HW = I[4], len = I[5], nW = I[6];
+  if (V <= 0 || C <= 0 || F <= 0 || HW <= 0 || nW <= 0)
+    return blend ? "window blend (lincomb i[9] = 1): videos, channels, frames, pixels per frame and windows per video must be positive"
+                 : "window gather (lincomb i[9] = 2): videos, channels, frames, pixels per frame and windows per video must be positive";
+  if (len < 2 || len > F)
+    return blend ? "window blend (lincomb i[9] = 1): the window length i[5] must lie in 2 .. frames"
+                 : "window gather (lincomb i[9] = 2): the window length i[5] must lie in 2 .. frames";
+  if (I[2] != T2V_F16 && I[2] != T2V_F32)
+    return blend ? "window blend (lincomb i[9] = 1): unknown eps dtype i[2] (fp16 | fp32)" : "window gather (lincomb i[9] = 2): unknown latent dtype i[2] (fp16 | fp32)";
+  const long clip = V * C * F * HW, windows = V * nW * C * len * HW;
+  if (blend) {
+    if (I[7] != 1 && I[7] != 2) return "window blend (lincomb i[9] = 1): roles i[7] must be 1 (conditional) or 2 (cond | uncond)";
+    if (I[8] != 0) return "window blend (lincomb i[9] = 1): i[8] must be 0";
+    if (op.p[0] == 0 || op.p[1] == 0 || op.p[2] == 0 || op.p[6] == 0) return "null window blend pointer (lincomb i[9] = 1: windows' eps, starts, weights, out)";
+    if (I[7] * clip > 0x7fffffffL || I[7] * windows > 0x7fffffffL) return "window blend (lincomb i[9] = 1): more than 2^31 - 1 elements";
+  } else {
+    if (I[8] <= 0 || I[7] < 0 || (long)I[7] + I[8] > V * nW) return "window gather (lincomb i[9] = 2): batch rows i[7] .. i[7] + i[8] must lie inside videos x windows";
+    if (op.p[0] == 0 || op.p[1] == 0 || op.p[6] == 0) return "null window gather pointer (lincomb i[9] = 2: latent, starts, out)";
+    if (clip > 0x7fffffffL || windows > 0x7fffffffL) return "window gather (lincomb i[9] = 2): more than 2^31 - 1 elements";
+  }
+  return nullptr;
+}
+
+static hipError_t launch_window(const t2v_op& op, hipStream_t s) {
+  if (t2v_window_refusal(op) != nullptr) return hipErrorInvalidValue;
+  const WindowGeom g = {reinterpret_cast<const int*>(op.p[1]), op.i[0], op.i[1], op.i[3], op.i[4], op.i[5], op.i[6]};
+  const int item = op.i[2] == T2V_F32 ? 4 : 2;
+  if (op.i[9] == 2) {
+    const int row0 = op.i[7], rows = op.i[8];
+    const long row_elems = (long)g.C * g.length * g.HW;
+    // every 16-byte access of the vector path: a frame is a whole number of units, and both bases sit on one
+    const bool vec = ((long)g.HW * item) % 16 == 0 && ((op.p[0] | op.p[6]) & 15) == 0;
+    if (vec) {
+      const int units = g.HW * item / 16;
+      hipLaunchKernelGGL(window_gather_kernel<uint4>, dim3(grid_for(rows * row_elems / g.HW * units)), dim3(256), 0, s,
+                         reinterpret_cast<const uint4*>(op.p[0]), reinterpret_cast<uint4*>(op.p[6]), g, row0, rows, units);
+    } else {
+      by_dtype(op.i[2], [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(window_gather_kernel<T>, dim3(grid_for(rows * row_elems)), dim3(256), 0, s, reinterpret_cast<const T*>(op.p[0]),
+                           reinterpret_cast<T*>(op.p[6]), g, row0, rows, g.HW);
+      });
+    }
+    return hipGetLastError();
+  }
+  const int roles = op.i[7];
+  const long total = (long)roles * g.V * g.C * g.F * g.HW;
+  // four neighbours of a frame per thread: 16-byte stores, 8- or 16-byte loads — HW % 4 keeps every run inside a frame and aligned
+  const bool vec = g.HW % 4 == 0 && (op.p[6] & 15) == 0 && (op.p[0] & (uint64_t)(4 * item - 1)) == 0;
+  by_dtype(op.i[2], [&](auto t) {
+    using TE = decltype(t);
+    by_bool(vec, [&](auto vc) {
+      constexpr int VEC = decltype(vc)::value ? 4 : 1;
+      hipLaunchKernelGGL((window_blend_kernel<TE, VEC>), dim3(grid_for(total / VEC)), dim3(256), 0, s, reinterpret_cast<const TE*>(op.p[0]),
+                         reinterpret_cast<const float*>(op.p[2]), reinterpret_cast<float*>(op.p[6]), g, roles);
+    });
+  });
+  return hipGetLastError();
+}
+
 hipError_t t2v_launch_lincomb(const t2v_op& op, hipStream_t s) {
+  if (op.i[9] != 0) return launch_window(op, s);      // the context-window forms; every earlier record leaves i[9] at zero
   LinParams p;
   p.n = op.i[0]; p.n_terms = op.i[1]; p.out_f32 = op.i[2] == T2V_F32;
   if (p.n_terms < 1 || p.n_terms > 6 || p.n <= 0) return hipErrorInvalidValue;

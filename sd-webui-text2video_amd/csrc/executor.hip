@@ -284,6 +284,11 @@ int validate_op(const t2v_op& op, int idx) {
       if (op.p[0] == 0) return bad("null memset pointer");
       return 0;
     case T2V_OP_LINCOMB:
+      if (op.i[9] == 1 || op.i[9] == 2) {      // the context-window forms: blend, gather
+        const char* why = t2v_window_refusal(op);
+        return why != nullptr ? bad(why) : 0;
+      }
+      if (op.i[9] != 0) return bad("lincomb: form i[9] must be 0 (linear combination), 1 (window blend) or 2 (window gather)");
       if (op.i[0] <= 0 || op.i[1] < 1 || op.i[1] > 6 || op.p[6] == 0) return bad("lincomb needs n > 0, 1..6 terms, an output");
       for (int k = 0; k < op.i[1]; ++k)
         if (op.p[k] == 0) return bad("null lincomb term");
@@ -508,7 +513,7 @@ unsigned output_slots(const t2v_op& op) {
     case T2V_OP_COPY2D: return bits({1, 2});
     case T2V_OP_DDIM_STEP: return bits({3});
     case T2V_OP_MEMSET: return bits({0});
-    case T2V_OP_LINCOMB: return bits({6});
+    case T2V_OP_LINCOMB: return bits({6});      // also the context-window forms (i[9] = 1 | 2): their tables p[1], p[2] are read
     case T2V_OP_EMBED_ROWS: return bits({3});
     case T2V_OP_TO_UINT8: return bits({1});
     case T2V_OP_RESAMPLE: return bits({1});
@@ -669,6 +674,20 @@ bool slot_range(const t2v_op& op, int q, SlotRange* out) {
       return span(~0ull >> 2);
     case T2V_OP_MEMSET: return flat(u64(0, 1));
     case T2V_OP_LINCOMB:
+      if (I[9] == 1 || I[9] == 2) {      // context windows: p0 the clip (gather) or the windows' eps (blend), p1 starts, p2 weights, p6 out
+        const uint64_t item = I[2] == f32 ? 4 : 2, roles = I[9] == 1 ? (uint64_t)I[7] : 1;
+        const uint64_t clip = (uint64_t)I[0] * I[1] * I[3] * I[4], win_row = (uint64_t)I[1] * I[5] * I[4];
+        if (q == 1) return flat((uint64_t)I[6] * 4);
+        if (I[9] == 1) {
+          if (q == 0) return flat(roles * I[0] * I[6] * win_row * item);
+          if (q == 2) return flat((uint64_t)I[5] * 4);
+          if (q == 6) return flat(roles * clip * 4);
+        } else {
+          if (q == 0) return flat(clip * item);
+          if (q == 6) return flat((uint64_t)I[8] * win_row * item);
+        }
+        return span(~0ull >> 2);
+      }
       if (q < I[1]) return flat((uint64_t)I[0] * (I[3 + q] == f32 ? 4 : 2));
       if (q == 6) return flat((uint64_t)I[0] * (I[2] == f32 ? 4 : 2));
       return span(~0ull >> 2);

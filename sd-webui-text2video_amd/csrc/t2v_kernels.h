@@ -328,6 +328,8 @@ hipError_t t2v_launch_embed_rows(const t2v_op& op, hipStream_t s);
 enum t2v_ddim_form { T2V_DDIM_MALFORMED, T2V_DDIM_PLAIN, T2V_DDIM_BLEND, T2V_DDIM_RESTRICT, T2V_DDIM_MEASURE, T2V_DDIM_THRESHOLD, T2V_DDIM_INVERT, T2V_DDIM_KEYFRAME };
 struct t2v_ddim_class { t2v_ddim_form form; int x0_form; const char* why; };
 t2v_ddim_class t2v_ddim_classify(const t2v_op& op);
+// Why a context-window form of T2V_OP_LINCOMB (i[9] = 1 blend, 2 gather; elementwise.hip) is refused, or null: validation and the launcher ask here
+const char* t2v_window_refusal(const t2v_op& op);
 // What a T2V_OP_ATTENTION record is (attention.hip): validation, the slot extents and the launcher ask here.  vt_waves: attn2_kernel's waves
 enum t2v_attention_form { T2V_ATTN_MALFORMED, T2V_ATTN_PLAIN, T2V_ATTN_SECOND_ROLE, T2V_ATTN_TABLE, T2V_ATTN_VT };
 struct t2v_attention_class { t2v_attention_form form; int head_dim, vt_waves; const char* why; };

@@ -234,7 +234,8 @@ class GaussianDiffusion(object):
     @torch.no_grad()
     def sample(self, x_T=None, S=5, shape=None, conditioning=None, unconditional_conditioning=None,
                model_kwargs={}, clamp=None, percentile=None, condition_fn=None,
-               unconditional_guidance_scale=None, eta=0.0, callback=None, mask=None, inpaint=None, inpaint_noise=None, **kwargs):
+               unconditional_guidance_scale=None, eta=0.0, callback=None, mask=None, inpaint=None, inpaint_noise=None, context_windows=None,
+               **kwargs):
         """gaussian_sampler.py:214-296.  Returns x_0-ish latent after S DDIM steps.
 
         Restriction of the predicted x0 (restrict_range_x0, gaussian_sampler.py:110-120, 174-178), the reference's answer to x0 blowing
@@ -270,7 +271,13 @@ class GaussianDiffusion(object):
         The step list is this build's own (the first S entries of get_time_steps); it is the legacy loop's whenever num_timesteps % S
         == 0, otherwise the legacy loop walks one entry more — not mirrored.
         Refused: clamp / percentile / condition_fn beside it (ValueError); an fp16 latent, a clip whose frames are split over ranks and
-        the CFG-pair layout (T2VError)."""
+        the CFG-pair layout (T2VError).
+
+        context_windows (this build's addition; `ContextWindows`, or its dict / tuple form): a clip longer than `length` frames is
+        evaluated through overlapping windows of that length at every step and the windows' eps are blended per frame
+        (`_eval_eps_windows`); the update, the restrictions, the keyframe blend and the eta noise work on the blended eps pair as on any
+        other.  A clip of at most `length` frames runs exactly as without the keyword.  Refused (T2VError): a clip whose frames are split
+        over ranks, the CFG-pair layout."""
         if model_kwargs:
             raise NotImplementedError("model_kwargs (conditioning passed as a pair, gaussian_sampler.py:156-159) is not used by the pipeline")
         if percentile is not None and not (0 < float(percentile) <= 1):
@@ -302,6 +309,7 @@ class GaussianDiffusion(object):
         inner = Fr * Hh * Ww
         x_dt = "f16" if xt.dtype == torch.float16 else "f32"
         thresholds = None
+        win = _active_windows(context_windows, Fr, model, self.cfg_parallel)
         conditioning, unconditional_conditioning = batch_contexts(conditioning, unconditional_conditioning, Bx)
         if restricted:
             if getattr(model, "t_shard", None) is not None or (self.shared_noise is not None and self.shared_noise.total != Fr):
@@ -333,13 +341,15 @@ class GaussianDiffusion(object):
             all_t = self.get_time_steps(stride, 1).cpu()
             # every step's timestep row, uploaded once: [steps, 2 * Bx] fp32 (the b = 2 * Bx CFG forward reads a whole row, a
             # b = Bx forward its first half) — no per-step fill kernels inside the loop
-            tt_all = all_t[:steps].to(torch.float32).view(-1, 1).repeat(1, 2 * Bx).to(dev)
+            # (context windows: a forward's batch is its windows, so a row holds enough entries for the largest one)
+            t_rows = Bx if win is None else max(n for _, n in win.chunks(Bx * len(win.starts(Fr))))
+            tt_all = all_t[:steps].to(torch.float32).view(-1, 1).repeat(1, 2 * t_rows).to(dev)
             if original is not None:                     # the legacy loop starts from the re-noised latents (t2v_model.py:1499-1502)
                 xt = self.add_noise(original, inpaint_noise[0] if inpaint_noise is not None else torch.randn_like(original), all_t[0])
             for step in range(steps):
                 c, uc = reconstruct_conds(conditioning, unconditional_conditioning, step)
                 t = int(all_t[step])
-                eps, is_pair = _eval_eps_pair(model, xt, tt_all[step], c, uc, guide, self.cfg_parallel, cache=pair_cache)
+                eps, is_pair = _eval_eps(model, xt, tt_all[step], c, uc, guide, win, self.cfg_parallel, cache=pair_cache)
                 guided, gscale = (self.get_dim(xt), float(guide)) if is_pair else (0, 1.0)    # guidance over the mean's channels
                 # schedule scalars: float64 tables cast to fp32 per lookup, then fp32 arithmetic —
                 # the exact operation order of gaussian_sampler.py:269-283 / `_i` (t2v_model.py:1232)
@@ -462,6 +472,259 @@ def _lincomb(out: torch.Tensor, terms) -> torch.Tensor:
     op.p[6] = out.data_ptr()
     _run_ops(op, out.device)
     return out
+
+
+# ---- context windows: a long clip sampled through overlapping windows of the trained length ---------------------------------------------
+class ContextWindows:
+    """The window schedule of `context_windows=` (AnimateDiff-style sliding context): every step denoises overlapping windows of
+    `length` frames and blends the windows' eps, per frame, into the eps pair of the whole clip.
+      starts(F)   0, stride, 2 * stride, ... while start + length < F (stride = length - overlap), then one last window flush right at
+                  F - length; every window has `length` frames, the starts ascend strictly, every frame is covered
+      weight(j)   of frame j of a window: "pyramid" min(j + 1, length - j), "flat" 1 (fp32)
+      batch       the most windows one forward evaluates; None: all videos x windows of a step in one forward.  Otherwise the batch rows
+                  (video-major, window fastest) go in ascending chunks of `batch`: at most two program shapes per run
+    A clip of F <= length frames is not windowed at all (`active`): the sampler takes the path it takes without the keyword.  The schedule
+    is the same at every step."""
+
+    def __init__(self, length, overlap, weights="pyramid", batch=None):
+        for name, v in (("length", length), ("overlap", overlap)) + ((("batch", batch),) if batch is not None else ()):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"context_windows: {name} must be an integer, got {v!r}")
+        if length < 2:
+            raise ValueError(f"context_windows: length must be at least 2, got {length}")
+        if not 1 <= overlap < length:
+            raise ValueError(f"context_windows: overlap must lie in 1 .. length - 1 = {length - 1}, got {overlap}")
+        if weights not in ("pyramid", "flat"):
+            raise ValueError(f"context_windows: weights must be 'pyramid' or 'flat', got {weights!r}")
+        if batch is not None and batch < 1:
+            raise ValueError(f"context_windows: batch must be None or at least 1, got {batch}")
+        self.length, self.overlap, self.weights, self.batch = length, overlap, weights, batch
+
+    @classmethod
+    def coerce(cls, value):
+        """None | ContextWindows | dict of the constructor's keywords | tuple of its arguments -> None | ContextWindows."""
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, dict):
+            unknown = [k for k in value if k not in ("length", "overlap", "weights", "batch")]
+            if unknown or "length" not in value or "overlap" not in value:
+                raise ValueError(f"context_windows: a dict needs length and overlap and may give weights and batch, got {sorted(value)}")
+            return cls(**value)
+        if isinstance(value, (tuple, list)) and 2 <= len(value) <= 4:
+            return cls(*value)
+        raise ValueError(f"context_windows must be a ContextWindows, a dict or a tuple (length, overlap[, weights[, batch]]), got {value!r}")
+
+    def active(self, frames: int) -> bool:
+        return frames > self.length
+
+    def starts(self, frames: int):
+        if frames <= self.length:
+            return [0]
+        stride = self.length - self.overlap
+        out = list(range(0, frames - self.length, stride))       # start + length < frames
+        if out[-1] != frames - self.length:
+            out.append(frames - self.length)
+        return out
+
+    def weight(self, j: int) -> float:
+        if not 0 <= j < self.length:
+            raise IndexError(j)
+        return float(min(j + 1, self.length - j)) if self.weights == "pyramid" else 1.0
+
+    def chunks(self, rows: int):
+        """-> [(first batch row, rows)] of the forwards of one step."""
+        b = rows if self.batch is None else min(self.batch, rows)
+        return [(r, min(b, rows - r)) for r in range(0, rows, b)]
+
+    def __repr__(self):
+        return f"ContextWindows(length={self.length}, overlap={self.overlap}, weights={self.weights!r}, batch={self.batch})"
+
+
+def _check_window_table(starts, frames: int, length: int) -> None:
+    """The blend divides by the weight sum of the windows that hold a frame: a table that leaves a frame out is refused here, on the host."""
+    ok = len(starts) > 0 and all(0 <= s <= frames - length for s in starts) and all(b > a for a, b in zip(starts, starts[1:]))
+    ok = ok and starts[0] == 0 and starts[-1] == frames - length and all(b - a <= length for a, b in zip(starts, starts[1:]))
+    if not ok:
+        raise L.T2VError(f"context windows: starts {list(starts)} of length {length} do not cover {frames} frames in ascending order")
+
+
+def _window_record(form: int, src, starts_d, out, videos: int, frames: int, length: int, hw: int):
+    """-> a T2V_OP_LINCOMB record of a context-window form (include/t2v_hip.h): i[9] = form, the geometry both forms share, p[0] src,
+    p[1] starts, p[6] out."""
+    op = L.T2VOp()
+    op.kind = L.OP_LINCOMB
+    op.i[0], op.i[1], op.i[2], op.i[3], op.i[4] = videos, src.shape[1], _dt_tag(src), frames, hw
+    op.i[5], op.i[6], op.i[9] = length, starts_d.numel(), form
+    op.p[0], op.p[1], op.p[6] = src.data_ptr(), starts_d.data_ptr(), out.data_ptr()
+    return op
+
+
+def _check_window_operands(starts_d, dense, what: str) -> None:
+    if not (starts_d.dtype == torch.int32 and starts_d.ndim == 1 and starts_d.is_contiguous()):
+        raise L.T2VError(f"{what}: the window starts must be a contiguous int32 table")
+    for t in dense:
+        if not (t.is_contiguous() and t.dtype in (torch.float16, torch.float32) and t.device == starts_d.device):
+            raise L.T2VError(f"{what}: operands must be fp16 or fp32, contiguous and on the device of the window table")
+
+
+def _window_gather(xw, x, starts_d, row0: int):
+    """T2V_OP_LINCOMB i[9] = 2: xw [rows, C, length, h, w] = the windows of batch rows row0 .. row0 + rows - 1 of the clips
+    x [V, C, F, h, w] (row v * nW + w is window w of video v), a bit-exact copy of the same dtype in one launch.
+    starts_d: int32 [nW] on the device."""
+    _check_window_operands(starts_d, (xw, x), "window gather")
+    V, C, F = x.shape[:3]
+    rows, length = xw.shape[0], xw.shape[2]
+    if xw.dtype != x.dtype or xw.shape[1] != C or tuple(xw.shape[3:]) != tuple(x.shape[3:]) or row0 < 0 or row0 + rows > V * starts_d.numel():
+        raise L.T2VError(f"window gather: windows {tuple(xw.shape)} from row {row0} do not belong to clips {tuple(x.shape)} of {starts_d.numel()} windows")
+    op = _window_record(2, x, starts_d, xw, V, F, length, x[0, 0, 0].numel())
+    op.i[7], op.i[8] = row0, rows
+    _run_ops(op, x.device)
+    return xw
+
+
+def _window_blend(out, chunks, starts_d, weights_d, roles: int, stage=None):
+    """T2V_OP_LINCOMB i[9] = 1: out [roles * V, C, F, h, w] fp32 = the per-frame weighted mean of the windows' eps — the eps pair
+    [cond (V) | uncond (V)] every step record reads.  chunks: the eps of the step's forwards in ascending batch-row order, each
+    [roles * rows_k, C, length, h, w] = [cond (rows_k) | uncond (rows_k)].  One chunk is read where it lies; several are first laid side
+    by side as [roles, V * nW, ...] (one COPY2D record each), and the blend follows in the same t2v_run_ops call — the blend always
+    reads one layout, so its result does not depend on the chunking.  weights_d: fp32 [length] on the device.  stage: a buffer of
+    the common layout that the caller keeps (allocated here otherwise; only several chunks use it)."""
+    _check_window_operands(starts_d, (out, weights_d) + tuple(chunks), "window blend")
+    nW, length = starts_d.numel(), chunks[0].shape[2]
+    V, (C, F) = out.shape[0] // roles, out.shape[1:3]
+    rows = [e.shape[0] // roles for e in chunks]
+    per_row = C * length * out[0, 0, 0].numel()
+    if (out.dtype != torch.float32 or weights_d.dtype != torch.float32 or weights_d.numel() != length or sum(rows) != V * nW
+            or any(e.dtype != chunks[0].dtype or e.shape[0] != roles * r or e[0].numel() != per_row for e, r in zip(chunks, rows))):
+        raise L.T2VError(f"window blend: eps of {[tuple(e.shape) for e in chunks]} do not make {nW} windows of an fp32 eps {tuple(out.shape)}")
+    records, e = [], chunks[0]
+    if len(chunks) > 1:
+        if per_row % 4 != 0:
+            raise L.T2VError("window blend: several forwards per step need channels x length x pixels per frame to be a multiple of 4")
+        e, row0 = stage, 0
+        if e is None:
+            e = torch.empty((roles * V * nW,) + tuple(chunks[0].shape[1:]), dtype=chunks[0].dtype, device=out.device)
+        elif not (e.is_contiguous() and e.dtype == chunks[0].dtype and e.device == out.device and e.numel() == roles * V * nW * per_row):
+            raise L.T2VError("window blend: the staging buffer must hold [roles * videos * windows, C, length, h, w] of the eps dtype")
+        for ch, r in zip(chunks, rows):            # rows [role, row0 .. row0 + r) of the common layout <- [role, 0 .. r) of the chunk
+            cp = L.T2VOp()
+            cp.kind = L.OP_COPY2D
+            cp.i[0], cp.i[1], cp.i[2], cp.i[3], cp.i[4], cp.i[5] = roles, r * per_row, r * per_row, V * nW * per_row, _dt_tag(ch), _dt_tag(e)
+            cp.p[0], cp.p[1] = ch.data_ptr(), e.data_ptr() + row0 * per_row * e.element_size()
+            records.append(cp)
+            row0 += r
+    op = _window_record(1, e, starts_d, out, V, F, length, out[0, 0, 0].numel())
+    op.i[7], op.p[2] = roles, weights_d.data_ptr()
+    _run_ops(_ddim_records(*records, op), out.device)
+    return out
+
+
+class _WindowRun:
+    """What one sampling run keeps for its windows (in the run's cache dict): the schedule of this clip, its two device tables, the
+    forwards of a step and, per forward, the conditioning of its rows — built once, so that the context K/V cache of `_eval_eps_pair`
+    (keyed by object identity) hits on every step after the first."""
+
+    def __init__(self, windows: ContextWindows, x):
+        V, F = x.shape[0], x.shape[2]
+        self.key = _WindowRun.key_of(windows, x)
+        self.starts = windows.starts(F)
+        _check_window_table(self.starts, F, windows.length)
+        self.nW = len(self.starts)
+        self.starts_d = torch.tensor(self.starts, dtype=torch.int32).to(x.device)
+        self.weights_d = torch.tensor([windows.weight(j) for j in range(windows.length)], dtype=torch.float32).to(x.device)
+        self.chunks = windows.chunks(V * self.nW)
+        self.contexts = {}        # (ids and versions of the caller's conditioning) -> per chunk (c, uc, pair cache)
+        self.shared = {}          # conditioning every row shares: one pair cache per chunk size
+
+    @staticmethod
+    def key_of(windows: ContextWindows, x):
+        return ((windows.length, windows.overlap, windows.weights, windows.batch), tuple(x.shape), x.dtype, x.device)
+
+    def videos_of(self, row0: int, rows: int):
+        return [r // self.nW for r in range(row0, row0 + rows)]
+
+    def conditioning(self, k: int, c, uc, V: int):
+        """-> (c, uc, pair cache) of chunk k: window (v, w) gets the context of video v.  A tensor of batch 1 is shared as it is."""
+        row0, rows = self.chunks[k]
+
+        def shared(t):
+            return t is None or (torch.is_tensor(t) and t.shape[0] == 1)
+        if shared(c) and shared(uc):
+            return c, uc, self.shared.setdefault(rows, {})
+        ident = _ctx_ident(0, c, uc)
+        held = self.contexts.get(ident)
+        if held is None:
+            def rows_of(t, vids):
+                if t is None or shared(t):
+                    return t
+                if isinstance(t, (list, tuple)):
+                    return [t[v] for v in vids]
+                if t.shape[0] != V:
+                    raise L.T2VError(f"context windows: conditioning of batch {t.shape[0]} for {V} videos (1 or {V} expected)")
+                return t[vids].contiguous()
+            per_chunk = []
+            for r0, n in self.chunks:
+                vids = self.videos_of(r0, n)
+                cc, uu = rows_of(c, vids), rows_of(uc, vids)
+                if isinstance(cc, list) and uu is not None and not isinstance(uu, list):      # (a list beside a shared tensor)
+                    uu = [uu] * n
+                if isinstance(uu, list) and not isinstance(cc, list):
+                    cc = [cc] * n
+                per_chunk.append((cc, uu, {}))
+            held = self.contexts[ident] = (per_chunk, (c, uc))      # (the caller's objects stay alive: their ids stay unique)
+        return held[0][k]
+
+
+def _active_windows(context_windows, frames: int, model=None, cfg_parallel=None):
+    """`context_windows=` of a sampler call -> the ContextWindows that apply to a clip of `frames` frames, or None: not given, or the
+    clip is no longer than a window (the call is then exactly the call without the keyword)."""
+    windows = ContextWindows.coerce(context_windows)
+    if windows is None or not windows.active(frames):
+        return None
+    if getattr(model, "t_shard", None) is not None:
+        raise L.T2VError("context windows are not supported with a clip whose frames are split over ranks: a window needs its frames on one device")
+    if cfg_parallel is not None and cfg_parallel.size == 2:
+        raise L.T2VError("context windows are not supported in the CFG-pair multi-GPU layout: the windows of a step are one batched "
+                         "[cond | uncond] forward on one device")
+    return windows
+
+
+def _eval_eps_windows(model, x, t_value, c, uc, guide, windows, cfg_parallel=None, cache: Optional[dict] = None):
+    """`_eval_eps_pair` of a clip longer than a window, same return contract (an fp32 eps pair over the whole clip, guided): gather the
+    windows (one launch per forward), `_eval_eps_pair` per forward with the windows as its batch, blend (one launch call per step).
+    `cache`: the run's dict; it keeps the `_WindowRun`."""
+    windows = _active_windows(windows, x.shape[2], model, cfg_parallel)
+    assert windows is not None, "a clip no longer than a window takes _eval_eps_pair"
+    cache = cache if cache is not None else {}
+    run = cache.get("windows")
+    if run is None or run.key != _WindowRun.key_of(windows, x):
+        run = cache["windows"] = _WindowRun(windows, x)
+    V, C, F = x.shape[:3]
+    x = x.contiguous()
+    parts, guided = [], None
+    for k, (row0, rows) in enumerate(run.chunks):
+        xw = torch.empty((rows, C, windows.length) + tuple(x.shape[3:]), dtype=x.dtype, device=x.device)
+        _window_gather(xw, x, run.starts_d, row0)
+        ck, uk, pair_cache = run.conditioning(k, c, uc, V)
+        tk = t_value
+        if torch.is_tensor(t_value) and t_value.ndim == 1:       # a prepared row of equal entries: 2 * rows of them
+            tk = t_value[:2 * rows] if t_value.shape[0] >= 2 * rows else t_value[:1].repeat(2 * rows)
+        eps, g = _eval_eps_pair(model, xw, tk, ck, uk, guide, None, cache=pair_cache)
+        assert guided is None or guided == g
+        guided = g
+        parts.append(eps if eps.dtype in (torch.float16, torch.float32) else eps.float())
+    roles = 2 if guided else 1
+    parts = [e[:roles * n].contiguous() for e, (_, n) in zip(parts, run.chunks)]
+    out = torch.empty((roles * V, C, F) + tuple(x.shape[3:]), dtype=torch.float32, device=x.device)
+    _window_blend(out, parts, run.starts_d, run.weights_d, roles)
+    return out, guided
+
+
+def _eval_eps(model, x, t_value, c, uc, guide, windows, cfg_parallel=None, cache: Optional[dict] = None):
+    """One step's evaluation: `_eval_eps_pair`, or `_eval_eps_windows` where the call has context windows that apply (`_active_windows`)."""
+    if windows is None:
+        return _eval_eps_pair(model, x, t_value, c, uc, guide, cfg_parallel, cache=cache)
+    return _eval_eps_windows(model, x, t_value, c, uc, guide, windows, cfg_parallel, cache)
 
 
 def _ddim_update(out, xt, eps_pair, noise, coef, guided: int, mode: int):
@@ -720,8 +983,9 @@ class DDIMSampler(object):
         self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = sigmas, alphas, alphas_prev
         self.ddim_sqrt_one_minus_alphas = torch.sqrt(1.0 - alphas)
 
-    def _run(self, img, cond, uncond, time_range, total_steps, guide, callback, temperature=1.0, ucg_schedule=None):
+    def _run(self, img, cond, uncond, time_range, total_steps, guide, callback, temperature=1.0, ucg_schedule=None, context_windows=None):
         model, dev = self.model, img.device
+        win = _active_windows(context_windows, img.shape[2], model, self.cfg_parallel)
         if ucg_schedule is not None:
             assert len(ucg_schedule) == len(time_range)          # sampler.py:150-152
         C = img.shape[1]
@@ -735,7 +999,7 @@ class DDIMSampler(object):
                 index = total_steps - i - 1
                 if ucg_schedule is not None:
                     guide = ucg_schedule[i]
-                eps, guided = _eval_eps_pair(model, img, int(step), c, uc, guide, self.cfg_parallel, cache=pair_cache)
+                eps, guided = _eval_eps(model, img, int(step), c, uc, guide, win, self.cfg_parallel, cache=pair_cache)
                 coef = _ddim_coef(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas, self.ddim_sqrt_one_minus_alphas, index, guide)
                 if temperature != 1.0:                                     # sigma_t * noise * temperature (sampler.py:216); dir_xt keeps sigma_t
                     coef[4] = float(torch.tensor(coef[4], dtype=torch.float32) * temperature)
@@ -748,16 +1012,17 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, eta=0.0, mask=None, x0=None, x_T=None,
-               unconditional_guidance_scale=1.0, unconditional_conditioning=None, temperature=1.0, ucg_schedule=None, **kwargs):
+               unconditional_guidance_scale=1.0, unconditional_conditioning=None, temperature=1.0, ucg_schedule=None, context_windows=None,
+               **kwargs):
         """sampler.py:56-166.  `temperature` scales the step's eta noise (:216), `ucg_schedule` gives one guidance scale per step
-        (:150-152)."""
+        (:150-152).  `context_windows` (also of `decode` and `encode`): see GaussianDiffusion.sample."""
         import numpy as np
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
         img = torch.randn(tuple(shape), device=self.device) if x_T is None else x_T.clone()
         img = img.float().contiguous() if img.dtype not in (torch.float16, torch.float32) else img.contiguous()
         return self._run(img, conditioning, unconditional_conditioning, np.flip(self.ddim_timesteps),
                          self.ddim_timesteps.shape[0], unconditional_guidance_scale, callback, temperature=temperature,
-                         ucg_schedule=ucg_schedule)
+                         ucg_schedule=ucg_schedule, context_windows=context_windows)
 
     def _invert_tables(self, num_steps, use_original_steps):
         """-> (alphas_next, alphas) of `encode` in the reference's dtypes (sampler.py:230-235): the float64 schedule tables, or — original
@@ -771,7 +1036,7 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
-               unconditional_conditioning=None, callback=None, *, model_timesteps="index"):
+               unconditional_conditioning=None, callback=None, *, model_timesteps="index", context_windows=None):
         """sampler.py:222-267 — deterministic DDIM inversion: the latent walks UP the trajectory, one UNet evaluation (one batched
         [cond | uncond] forward when guided) and ONE update launch (T2V_OP_DDIM_STEP mode 3) per step.
 
@@ -796,6 +1061,7 @@ class DDIMSampler(object):
         model = self.model
         x = x0.to(torch.float32).contiguous()
         dev, videos = x.device, x.shape[0]
+        win = _active_windows(context_windows, x.shape[2], model, None)
         guide = unconditional_guidance_scale
         if guide != 1.0:
             assert unconditional_conditioning is not None
@@ -807,7 +1073,7 @@ class DDIMSampler(object):
         with _sampling_run(model, dev):
             for i in range(num_steps):
                 t = i if (model_timesteps == "index" or use_original_steps) else int(self.ddim_timesteps[i])
-                eps, guided = _eval_eps_pair(model, x_next, t, cond, uncond, guide, None, cache=pair_cache)
+                eps, guided = _eval_eps(model, x_next, t, cond, uncond, guide, win, None, cache=pair_cache)
                 # 0-dim tensors of the tables' dtype; they meet the fp32 latent as fp32 scalars (sampler.py:251-253)
                 cx = (alphas_next[i] / alphas[i]).sqrt()
                 ce = alphas_next[i].sqrt() * ((1 / alphas_next[i] - 1).sqrt() - (1 / alphas[i] - 1).sqrt())
@@ -842,13 +1108,13 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False, callback=None, *args, **kwargs):
+               use_original_steps=False, callback=None, *args, context_windows=None, **kwargs):
         """sampler.py:286-306."""
         import numpy as np
         assert not use_original_steps
         timesteps = self.ddim_timesteps[:t_start]
         return self._run(x_latent.contiguous().clone(), cond, unconditional_conditioning, np.flip(timesteps),
-                         timesteps.shape[0], unconditional_guidance_scale, callback)
+                         timesteps.shape[0], unconditional_guidance_scale, callback, context_windows=context_windows)
 
 
 class _VPSchedule:
@@ -957,12 +1223,13 @@ class UniPCSampler(object):
         _unipc_options(self.options)           # a wrong value is refused where it is given
         self.last_thresholds = None            # thresholding runs: the thresholds of the last `sample` call (see the class)
         self._thresholds = None                # (the table of the run in progress, one row per evaluation)
+        self._windows = None                   # (the context windows of the run in progress, `_active_windows`)
         self._evaluation = 0
 
     # -- x0 prediction from the (guided) noise prediction: x0 = (x - sigma_t * eps_g) / alpha_t -------------
     def _data_prediction(self, ns, x, t, cond, uncond, guide):
-        eps, guided = _eval_eps_pair(self.model, x, (t - 1.0 / ns.total_N) * 1000.0, cond, uncond, guide, self.cfg_parallel,
-                                     cache=self._pair_cache)
+        eps, guided = _eval_eps(self.model, x, (t - 1.0 / ns.total_N) * 1000.0, cond, uncond, guide, self._windows, self.cfg_parallel,
+                                cache=self._pair_cache)
         a, s = ns.alpha(t), ns.std(t)
         nb = x.shape[0]
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
@@ -1017,7 +1284,8 @@ class UniPCSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, strength=None, eta=0.0, mask=None,
                x_T=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None, variant=None, skip_type=None,
                order=None, lower_order_final=None, initial_corrector=None, denoise_to_zero=None, thresholding=None,
-               predict_x0=None, method=None, max_val=None, **kwargs):
+               predict_x0=None, method=None, max_val=None, context_windows=None, **kwargs):
+        """uni_pc/sampler.py:31-90.  `context_windows`: see GaussianDiffusion.sample — every data prediction is windowed."""
         given = dict(variant=variant, skip_type=skip_type, order=order, lower_order_final=lower_order_final,
                      initial_corrector=initial_corrector, denoise_to_zero=denoise_to_zero, thresholding=thresholding,
                      predict_x0=predict_x0, method=method, max_val=max_val)
@@ -1029,6 +1297,7 @@ class UniPCSampler(object):
             raise L.T2VError("thresholding needs an fp32 latent x_T")
         x = x.float().contiguous()
         _check_batch_layout(self, x.shape[0])
+        self._windows = _active_windows(context_windows, x.shape[2], model, self.cfg_parallel)
         conditioning, unconditional_conditioning = batch_contexts(conditioning, unconditional_conditioning, x.shape[0])
         ns = _VPSchedule(self.alphas_cumprod)
         order, steps = opt["order"], S
@@ -1084,6 +1353,7 @@ class UniPCSampler(object):
                     c, uc = conds()
                     x = self._data_prediction(ns, x, float(torch.tensor(t_0, dtype=f32)), c, uc, guide)
             finally:
+                self._windows = None
                 self.last_thresholds, self._thresholds = self._thresholds, None      # [evaluations, videos, 4] {s, q, v_lo, v_hi} on the device, else None
         return x
 
@@ -1173,7 +1443,7 @@ class Txt2VideoSampler(object):
         return encoded_latent, denoise_steps
 
     def invert_latent(self, latent, noise, strength, steps, conditioning, unconditional_conditioning, guidance_scale=1.0,
-                      model_timesteps="index"):
+                      model_timesteps="index", context_windows=None):
         """vid2vid through DDIM inversion: `encode_latent`'s schedule and step count, the latent from `DDIMSampler.encode` instead of
         `stochastic_encode` (`noise` only tells how many videos the batch holds), and `sample` becomes `decode` as there."""
         if noise is not None and latent.shape[0] == 1 and noise.shape[0] > 1:
@@ -1181,7 +1451,8 @@ class Txt2VideoSampler(object):
         denoise_steps = int(strength * steps)
         self.sampler.make_schedule(steps)
         encoded_latent, _ = self.sampler.encode(latent, conditioning, denoise_steps, unconditional_guidance_scale=guidance_scale,
-                                                unconditional_conditioning=unconditional_conditioning, model_timesteps=model_timesteps)
+                                                unconditional_conditioning=unconditional_conditioning, model_timesteps=model_timesteps,
+                                                **({"context_windows": context_windows} if context_windows is not None else {}))
         self.sampler.sample = self.sampler.decode
         return encoded_latent, denoise_steps
 
@@ -1200,7 +1471,8 @@ class Txt2VideoSampler(object):
 
     def sample_loop(self, steps, strength, conditioning, unconditional_conditioning, batch_size, latents=None,
                     shape=None, noise=None, is_vid2vid=False, guidance_scale=1, eta=0, mask=None,
-                    sampler_name="DDIM", *, clamp=None, percentile=None, unipc=None, inversion=None, inpaint=None):
+                    sampler_name="DDIM", *, clamp=None, percentile=None, unipc=None, inversion=None, inpaint=None,
+                    context_windows=None):
         """samplers_common.py:165-207.  `clamp` / `percentile` (keyword, this build's addition to the signature): the x0 restriction of
         GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set, so every other call is what it was.
         `unipc` (keyword, likewise): a dict of UniPC's solver options (UNIPC_OPTIONS, see UniPCSampler) — UniPC only, forwarded only
@@ -1211,7 +1483,10 @@ class Txt2VideoSampler(object):
         video of a batch under its own prompt) instead of being noised by `stochastic_encode`; `noise` is not used; `sample` becomes
         `decode` exactly as on the noising route.
         `inpaint` (keyword, likewise): "legacy" makes `mask` work — the keyframe blend of the reference's legacy loop, see
-        GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set."""
+        GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set.
+        `context_windows` (keyword, likewise): a `ContextWindows` or its dict / tuple form, for every sampler — a clip longer than its
+        `length` is denoised through overlapping windows (GaussianDiffusion.sample); the inversion of `inversion=` is windowed too.
+        Forwarded only when set."""
         restrict = {k: v for k, v in (("clamp", clamp), ("percentile", percentile), ("inpaint", inpaint)) if v is not None}
         active = next((s.name for s in available_samplers if isinstance(self.sampler, s.Sampler)), type(self.sampler).__name__)
         if inpaint is not None and not isinstance(self.sampler, GaussianDiffusion):
@@ -1225,6 +1500,8 @@ class Txt2VideoSampler(object):
             if unknown:
                 raise ValueError(f"unipc: unknown option(s) {', '.join(map(repr, unknown))}; the options are {', '.join(UNIPC_OPTIONS)}")
             restrict.update(unipc)
+        if context_windows is not None:
+            restrict["context_windows"] = ContextWindows.coerce(context_windows)
         invert = None
         if inversion is not None and inversion is not False:
             if not isinstance(self.sampler, DDIMSampler):
@@ -1240,7 +1517,8 @@ class Txt2VideoSampler(object):
                 invert.update(inversion)
         denoise_steps = None
         if invert is not None:
-            latents, denoise_steps = self.invert_latent(latents, noise, strength, steps, conditioning, unconditional_conditioning, **invert)
+            latents, denoise_steps = self.invert_latent(latents, noise, strength, steps, conditioning, unconditional_conditioning, **invert,
+                                                        **({"context_windows": restrict["context_windows"]} if context_windows is not None else {}))
         elif latents is not None and is_vid2vid:
             latents, denoise_steps = self.encode_latent(latents, noise, strength, steps)
         sampler_callback = SamplerStepCallback(sampler_name, steps, progress=self.progress)

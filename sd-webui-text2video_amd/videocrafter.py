@@ -1053,6 +1053,9 @@ class DDIMSampler(object):
         if quantize_x0 or noise_dropout or score_corrector is not None or postprocess_fn is not None \
                 or cond_fn is not None or kwargs.get("uc_type") is not None:
             raise NotImplementedError("quantisation / noise dropout / score correctors are not on the hot path")
+        if kwargs.get("context_windows") is not None:
+            raise L.T2VError("context_windows: context windows exist for the ModelScope samplers only; the VideoCrafter loop evaluates "
+                             "through LatentDiffusion.apply_model and is out of scope")
         size = (batch_size, *shape)
         assert len(size) == 5
         if mask is not None:
