@@ -49,6 +49,8 @@ extern "C" {
                                estimator of the VideoCrafter depth adapter; additive on fields that every earlier record leaves zero);
                                still 11: TO_UINT8 i[15] = 1 (torch_to_np's arithmetic and per-video output blocks — the VideoCrafter driver's frames; additive on
                                a field that every earlier record leaves zero);
+                               still 11: T2V_OP_FREEU (a new kind: FreeU at a decoder skip concatenation, in place, one launch; no existing record changes, and
+                               a library without it refuses the record as an unknown op kind);
                                10: T2V_OP_RESAMPLE — one pass of Pillow's 8-bit Lanczos resize of uint8 frames (vid2vid / inpainting input of any size), the last pass
                                optionally writing the VAE encoder's entry tokens (additive: no existing record changes);
                                9: RELPOS_ATTN i[17] = 3 — relative-position attention for clips of up to T2V_RELPOS_MAX_FRAMES frames (tables packed
@@ -115,7 +117,8 @@ enum t2v_op_kind {
   T2V_OP_EMPHASIS = 24,      /* prompt emphasis of a batch of text-encoder chunks: per-token multipliers, then the batch mean restored (fp64 sums, one workgroup) */
   T2V_OP_FINGERPRINT = 25,   /* one 64-bit fingerprint per byte range of a device table (in-place edits of packed parameters); stand-alone, never part of a plan */
   T2V_OP_LORA_MERGE = 26,    /* W += alpha * (B A) for every weight of a device table, in place (Stable LoRA merge / un-merge); stand-alone, never part of a plan */
-  T2V_OP_KIND_MAX = 27
+  T2V_OP_KIND_MAX = 27,      /* end of the kinds 1 .. 26, the range the record-path tables classify; kinds added since follow it */
+  T2V_OP_FREEU = 27          /* FreeU (Si et al.) at one decoder skip concatenation: half of the stream's channels times b, the skip's low frequencies times s; in place */
 };
 
 /* GEMM gather modes: how row m / reduction index k of the A operand are addressed          */
@@ -474,6 +477,23 @@ enum t2v_gather {
  *      tile of every segment exactly once (a tile listed twice is merged twice), and the segments of one table must not overlap (the host's check).
  *      segment record (48 bytes): {uint64 W, uint64 A, uint64 B, int32 N, int32 J, int32 r, int32 form, int32 dtype, int32 0}
  *      i: 0 n segments, 1 n tiles (>= n);  f: 0 alpha;  p: 0 segment table, 1 tile table: n tiles x {uint32, uint32} (both 8-byte aligned)
+ * FREEU (ABI 11, additive): FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net") at ONE decoder skip concatenation — the reference's
+ *      torch.cat([x, xs.pop()], dim=1), t2v_model.py:444 — in place on the fp32 channels-last concat buffer X [rows, ld], rows = frames * h * w
+ *      (row = (frame * h + y) * w + x), whose columns [0, C_h) hold the stream and [C_h, C_total) the skip.  One launch:
+ *        X[:, 0 .. C_h/2)      *= f[0]                      one fp32 multiply per element
+ *        X[:, C_h/2 .. C_h)    untouched, as every column >= C_total (ld > C_total is fine) and every byte outside the buffer
+ *        X[:, C_h .. C_total)   = fourier_filter(., scale f[1], threshold 1) per (frame, channel) plane [h, w]:
+ *          V = fftshift(fftn(v));  V[h/2 - 1 : h/2 + 1, w/2 - 1 : w/2 + 1] *= scale  (Python slices);  out = real(ifftn(ifftshift(V)))
+ *        i.e. the frequency bins u in {-1, 0} x v in {-1, 0}, taken as DISTINCT indices modulo the axis length (an axis of length 1 has one
+ *        bin, an axis of length 2 both of its bins), are scaled — evaluated in closed form, no FFT:
+ *          out(y, x) = v(y, x) + (scale - 1) / (h w) * sum_bins ( Re c cos(theta) - Im c sin(theta) ),
+ *          theta = 2 pi (u y / h + v x / w),  c = sum_{y, x} v(y, x) e^{-i theta}
+ *        with the sums and the correction in fp64 and ONE rounding to fp32 at the store.  f[0] = f[1] = 1 leaves every finite value as it
+ *        was.  Sums are taken in a fixed order without atomics: results repeat bit for bit.  A non-finite value reaches the (frame,
+ *        channel) plane it sits in and no other.  16-byte accesses when X is 16-byte aligned, ld % 4 == 0, C_h % 8 == 0 and
+ *        (C_total - C_h) % 4 == 0; one element per lane otherwise.
+ *      i: 0 rows, 1 C_total, 2 ld (>= C_total), 3 C_h (even, 0 < C_h <= C_total), 4 frames, 5 h, 6 w (h, w <= 1024; rows == frames * h * w);
+ *      f: 0 b, 1 s (both finite);  p: 0 X fp32 (4-byte aligned).  Anything else is refused, with a message, before anything is launched.
  */
 typedef struct t2v_op {
   int32_t kind;

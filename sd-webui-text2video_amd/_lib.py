@@ -49,7 +49,8 @@ OP_FINGERPRINT = 25
 FINGERPRINT_CHUNK = 65536           # T2V_FINGERPRINT_CHUNK: bytes of one segment per workgroup (the unit of the chunk table)
 FINGERPRINT_LEN = 0x9E3779B97F4A7C15   # T2V_FINGERPRINT_LEN: multiplier of the length term
 OP_LORA_MERGE = 26
-OP_KIND_MAX = 27
+OP_KIND_MAX = 27                    # T2V_OP_KIND_MAX: end of the kinds 1 .. 26; kinds added since follow it
+OP_FREEU = 27                       # T2V_OP_FREEU
 LORA_TILE = 4096                    # T2V_LORA_TILE: elements of one weight per workgroup (the unit of the tile table)
 LORA_DIRECT, LORA_TEMPORAL = 0, 1   # T2V_LORA_DIRECT / T2V_LORA_TEMPORAL: the form of a segment
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2     # GEMM i[18]

@@ -367,6 +367,10 @@ int validate_op(const t2v_op& op, int idx) {
       for (int k = 0; k < 2; ++k)
         if (op.p[k] >= T2V_EXT_SLOTS && op.p[k] % 8 != 0) return bad("lora merge: the tables must be 8-byte aligned");
       return 0;
+    case T2V_OP_FREEU: {
+      const t2v_freeu_view v = t2v_freeu_decode(op);
+      return v.ok ? 0 : bad(v.why);
+    }
     case T2V_OP_ALLGATHER:
       if (op.i[2] < 1 || op.i[3] < 0 || op.i[3] >= op.i[2] || op.p[0] == 0) return bad("bad all-gather record");
       return 0;
@@ -461,6 +465,7 @@ hipError_t launch_op(const t2v_op& op, hipStream_t s) {
     case T2V_OP_EMPHASIS: return t2v_launch_emphasis(op, s);
     case T2V_OP_FINGERPRINT: return t2v_launch_fingerprint(op, s);
     case T2V_OP_LORA_MERGE: return t2v_launch_lora_merge(op, s);
+    case T2V_OP_FREEU: return t2v_launch_freeu(op, s);
     case T2V_OP_MEMSET: {
       const size_t bytes = (size_t)(uint32_t)op.i[0] | ((size_t)(uint32_t)op.i[1] << 32);
       return hipMemsetAsync(reinterpret_cast<void*>(op.p[0]), 0, bytes, s);
@@ -523,7 +528,7 @@ unsigned output_slots(const t2v_op& op) {
     case T2V_OP_FINGERPRINT: return bits({1});
     case T2V_OP_RESHARD_ROWS: return bits({1});
     case T2V_OP_ALLTOALL: return bits({1});
-    default: return 0u;      // ALLGATHER / HALO_EXCHANGE / STATS_HALO work in place: their slots are read
+    default: return 0u;      // ALLGATHER / HALO_EXCHANGE / STATS_HALO / FREEU work in place: their slots are read
   }
 }
 
@@ -739,6 +744,11 @@ bool slot_range(const t2v_op& op, int q, SlotRange* out) {
         if (q == 2 || q == 3) return flat((uint64_t)(I[4] + I[10]) * 4 * 4);
       }
       return span(~0ull >> 2);    // the uint8 passes: as the default below
+    case T2V_OP_FREEU: {
+      const t2v_freeu_view f = t2v_freeu_decode(op);
+      if (q == 0 && f.ok) return mat(f.rows, f.c_total, f.ld, 4);
+      return span(~0ull >> 2);
+    }
     default:
       // DDIM_STEP, TO_UINT8, RESAMPLE (uint8 passes) work on the caller's tensors in every lowering; should one name arena memory, its extent is in doubt
       return span(~0ull >> 2);

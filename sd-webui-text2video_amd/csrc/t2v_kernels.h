@@ -322,6 +322,12 @@ hipError_t t2v_launch_copy2d(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_ddim_step(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_lincomb(const t2v_op& op, hipStream_t s);
 hipError_t t2v_launch_embed_rows(const t2v_op& op, hipStream_t s);
+hipError_t t2v_launch_freeu(const t2v_op& op, hipStream_t s);               // freeu.hip
+
+// The T2V_OP_FREEU record, decoded once (freeu.hip): validation, the slot extents and the launcher all ask here.  ok = false: the record
+// is refused, `why` says why
+struct t2v_freeu_view { bool ok; const char* why; int rows, c_total, ld, c_h, frames, h, w; float b, s; uint64_t buf; };
+t2v_freeu_view t2v_freeu_decode(const t2v_op& op);
 
 // What a T2V_OP_DDIM_STEP record is (elementwise.hip): validation, the output slots and the launcher all ask here.  x0_form: which x0
 // the measure pass ranks (0 the DDIM_Gaussian step, 1 UniPC's data prediction); why: the reason a T2V_DDIM_MALFORMED record is refused

@@ -119,6 +119,8 @@ class _UNetLowering(_Declarations):
         # GroupNorm statistics from the producing GEMM's epilogue (ResBlock conv -> norm, the temporal-conv chain): opt-in (measured slower)
         self.gn_strips = bool(getattr(net, "gn_producer_stats", False))
         self.last_stats: Optional[Buf] = None
+        # FreeU at the decoder's skip concatenations (`skip_concat`): (b1, b2, s1, s2) or None.  The lowering of a network that has it sets it.
+        self.freeu: Optional[Tuple[float, float, float, float]] = None
         self.stem_dup = False
         self.P.small_rank_tiles = self.shard is not None       # (Program.choose_tile: no temporal convolution of a rank program carries a norm epilogue)
         prefixes = tuple(getattr(net, "split_weight_prefixes", ()) or ())
@@ -417,6 +419,21 @@ class _UNetLowering(_Declarations):
             return self.conv3(p, x, p, cout, h, w, cin=8, dest=dest, dup_c8=self.stem_dup, **res)
         return self.resample(p, "op" if kind == "down" else "conv", x, cout, h, w, up=kind == "up", dest=dest, **res)
 
+    def skip_concat(self, prefix: str, cat: Buf, c_h: int, h: int, w: int):
+        """The concat buffer `cat` = [stream (c_h channels) | skip] of decoder block `prefix` is complete — both halves written, the
+        copies of a shared cond | uncond prefix included — and nothing has read it yet (its readers are the block's first ResBlock:
+        the in_layers GroupNorm, the 1x1 skip_connection, any fp16 operand cast).  With FreeU on, a stream of 4 dim channels takes
+        (b1, s1) and one of 2 dim channels (b2, s2), in place, one T2V_OP_FREEU; any other width is left alone (the channel-keyed rule
+        of the FreeU authors' code).  The op is its own record between the producers and the readers, so whatever a producer recorded
+        about these columns — statistics strips, a norm in its epilogue, a low-order fp16 image — describes another buffer or is
+        never consulted here: no reader of `cat` takes anything from the op in front of it unless that op's output IS `cat`."""
+        if self.freeu is None:
+            return
+        b1, b2, s1, s2 = self.freeu
+        gains = {4 * self.net.dim: (b1, s1), 2 * self.net.dim: (b2, s2)}.get(c_h)
+        if gains is not None:
+            self.P.freeu(prefix + ".freeu", cat, c_h=c_h, frames=self.B * self.F, h=h, w=w, b=gains[0], s=gains[1])
+
     def inject_for(self, k: int, c, h, w) -> Optional[Buf]:
         """Hook: the feature added to the result (c channels at h x w) of encoder block k.  The base has none."""
         return None
@@ -532,7 +549,8 @@ class _UNetLowering(_Declarations):
                                 inject=self.inject_for(k, skip_c[k], ho, wo))
         cat = cats.pop()
         x, h, w = run_parts(middle[1], x, h, w, dest=cat.borrow_cols(0, cat.cols - skip_c[-1]))
-        for j, (_, parts) in enumerate(outputs):
+        for j, (prefix, parts) in enumerate(outputs):
+            self.skip_concat(prefix, cat, cat.cols - skip_c[n_skip - 1 - j], h, w)
             nxt = cats.pop() if cats else None
             dest = nxt.borrow_cols(0, nxt.cols - skip_c[n_skip - 2 - j]) if nxt is not None else None
             x, h, w = run_parts(parts, cat, h, w, dest=dest)

@@ -168,7 +168,7 @@ class TextToVideoSynthesis(object):
                           device=None, latents=None, strength=None, mask=None, is_vid2vid=False,
                           sampler=available_samplers[0].name, decode=True, to_host=True, _keep_sampler=False,
                           videos: int = 1, *, clamp=None, percentile=None, unipc=None, seeds=None, inversion=None, inpaint=None,
-                          context_windows=None):
+                          context_windows=None, freeu=None):
         """Stages 2-4 of `infer` for given conditioning tensors c, uc [1, 77k, 1024].
         A batch of DIFFERENT prompts: c / uc as lists of `videos` tensors [1, 77k_v, 1024] (a single tensor beside a list = that prompt for
         every video; lists of one entry = the tensor), contexts of any lengths — still one 2*videos forward per step, the text
@@ -187,6 +187,11 @@ class TextToVideoSynthesis(object):
         `context_windows` (every sampler): a `samplers.ContextWindows`, or {"length": 16, "overlap": 4[, "weights": "pyramid" | "flat",
         "batch": n]} — a clip of more than `length` frames is denoised through overlapping windows of `length` frames whose eps are blended
         per frame, so the UNet only sees clips of the length it was trained on; forwarded only when set.
+        `freeu` (every sampler): {"b1": 1.2, "b2": 1.4, "s1": 0.9, "s2": 0.2} (the FreeU authors' ModelScope values) — FreeU in the UNet for
+        this call (`UNetSD.enable_freeu`: half of the backbone channels amplified, the skips' low frequencies damped, at the decoder
+        concatenations of 4 dim and 2 dim channels); the model is restored afterwards.  The four values are part of the UNet's program
+        key (`max_programs` bounds a sweep).  A partial dict or a non-finite value raises ValueError; the T-shard and CFG-pair multi-GPU
+        layouts raise NotImplementedError.  Forwarded only when set.
         Returns (frames, last_tensor): frames = list of HxWx3 uint8 BGR arrays (to_host) or a
         uint8 device tensor [F,H,W,3] RGB (to_host=False), or None when decode=False.
         `videos` > 1 (every sampler; txt2vid and vid2vid, where the ONE input clip's latents are repeated): that many independent videos of the same prompt in ONE batch — every
@@ -227,7 +232,7 @@ class TextToVideoSynthesis(object):
         x0 = self.diffusion.sample_loop(
             steps=steps, strength=strength, eta=eta, conditioning=_to(c, dev), unconditional_conditioning=_to(uc, dev),
             batch_size=videos, guidance_scale=scale, latents=latents, shape=shape, noise=noise, is_vid2vid=is_vid2vid,
-            sampler_name=sampler, mask=mask, **_restriction(clamp, percentile, unipc, inversion, inpaint, context_windows))
+            sampler_name=sampler, mask=mask, **_restriction(clamp, percentile, unipc, inversion, inpaint, context_windows, freeu))
         self.last_tensor = x0
         if not decode:
             return None, x0
@@ -311,7 +316,7 @@ class TextToVideoSynthesis(object):
     def infer(self, prompt, n_prompt, steps, frames, seed, scale, width=256, height=256, eta=0.0,
               cpu_vae="GPU (half precision)", device=torch.device("cuda"), latents=None, skip_steps=0,
               strength=0, mask=None, is_vid2vid=False, sampler=available_samplers[0].name, *, clamp=None, percentile=None, unipc=None, inversion=None,
-              inpaint=None, context_windows=None):
+              inpaint=None, context_windows=None, freeu=None):
         vars_ = dict(prompt=prompt, n_prompt=n_prompt, steps=steps, frames=frames, seed=seed, scale=scale,
                      width=width, height=height, eta=eta, cpu_vae=cpu_vae, device=str(device),
                      skip_steps=skip_steps, strength=strength, is_vid2vid=is_vid2vid, sampler=sampler)
@@ -325,7 +330,7 @@ class TextToVideoSynthesis(object):
         strength = None if (strength == 0.0 and not is_vid2vid) else strength
         frames_bgr, x0 = self.infer_conditioned(c, uc, steps, frames, seed, scale, width, height, eta, device,
                                                 latents, strength, mask, is_vid2vid, sampler,
-                                                **_restriction(clamp, percentile, unipc, inversion, inpaint, context_windows))
+                                                **_restriction(clamp, percentile, unipc, inversion, inpaint, context_windows, freeu))
         return frames_bgr, self.last_tensor, create_infotext(vars_)
 
 
@@ -365,11 +370,11 @@ def _batch_arguments(c, uc, videos, seed, seeds):
     return c, uc, videos, seeds
 
 
-def _restriction(clamp, percentile, unipc=None, inversion=None, inpaint=None, context_windows=None) -> dict:
-    """The x0-restriction keywords, the UniPC options, the DDIM inversion option, the keyframe-inpainting option and the context windows
-    that are set — nothing is forwarded when none is, so a call without them is what it was."""
+def _restriction(clamp, percentile, unipc=None, inversion=None, inpaint=None, context_windows=None, freeu=None) -> dict:
+    """The x0-restriction keywords, the UniPC options, the DDIM inversion option, the keyframe-inpainting option, the context windows and
+    the FreeU values that are set — nothing is forwarded when none is, so a call without them is what it was."""
     return {k: v for k, v in (("clamp", clamp), ("percentile", percentile), ("unipc", unipc), ("inversion", inversion), ("inpaint", inpaint),
-                              ("context_windows", context_windows)) if v is not None}
+                              ("context_windows", context_windows), ("freeu", freeu)) if v is not None}
 
 
 _CPU_VAE_NOTED = False
@@ -413,6 +418,7 @@ def process_modelscope(args_dict: dict, extra_args=None):
                    inversion,                                                 # vid2vid through DDIM inversion (ddim/sampler.py:222-267), below
                    inpaint,                                                   # img2vid keyframe blend of the legacy loop (t2v_model.py:1555-1562), below
                    context_windows,                                           # long clips through overlapping frame windows, below
+                   freeu,                                                     # FreeU in the UNet (Si et al.), below
                    enable_emphasis, comma_padding_backtrack,                  # webui's opts of the prompt syntax (clip_hardcode.py:153,203)
                    do_vid2vid, vid2vid_frames, strength,                      # :80-147
                    inpainting_frames, inpainting_image, inpainting_weights,   # :170-217
@@ -437,6 +443,8 @@ def process_modelscope(args_dict: dict, extra_args=None):
     * `context_windows` = {"length": 16, "overlap": 4[, "weights": "pyramid" | "flat", "batch": n]} (every sampler): a clip of more than
       `length` frames is denoised through overlapping windows of `length` frames, blended per frame at every step
       (`samplers.ContextWindows`); a shorter clip, or a call without the key, is what it was.
+    * `freeu` = {"b1": 1.2, "b2": 1.4, "s1": 0.9, "s2": 0.2} (every sampler; the authors' ModelScope values): FreeU in the UNet for this
+      call (`infer_conditioned`, `UNetSD.enable_freeu`); without the key the call is what it was.
     * `prompts` = [...] / `n_prompts` = [...] (or `conds` = [...] / `unconds` = [...], lists of context tensors) and optionally
       `seeds` = [...]: a batch of DIFFERENT prompts in ONE pass, one video per entry (a single negative prompt, or `prompt` / `cond`
       beside a list, is broadcast; every prompt is encoded by an encoder call of its own).  Video v starts from seeds[v] (default
@@ -481,7 +489,8 @@ def process_modelscope(args_dict: dict, extra_args=None):
     common = dict(frames=a.frames, scale=a.cfg_scale, width=width, height=height, eta=getattr(a, "eta", 0.0),
                   sampler=getattr(a, "sampler", available_samplers[0].name),
                   **_restriction(getattr(a, "clamp", None), getattr(a, "percentile", None), getattr(a, "unipc", None),
-                                 getattr(a, "inversion", None), getattr(a, "inpaint", None), getattr(a, "context_windows", None)))
+                                 getattr(a, "inversion", None), getattr(a, "inpaint", None), getattr(a, "context_windows", None),
+                                 getattr(a, "freeu", None)))
     batch_count = int(getattr(a, "batch_count", 1))
     stitch = getattr(a, "stitch", None)
     cpu_vae = getattr(a, "cpu_vae", "GPU (half precision)")

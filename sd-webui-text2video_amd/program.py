@@ -1238,6 +1238,17 @@ class Program:
         op.out = out
         return self._emit(op)
 
+    def freeu(self, name: str, cat: Buf, *, c_h: int, frames: int, h: int, w: int, b: float, s: float) -> Op:
+        """T2V_OP_FREEU, in place on the fp32 concat buffer `cat` [frames * h * w, C_total] = [stream (c_h) | skip]: columns [0, c_h / 2)
+        times b, the skip columns through the Fourier filter of scale s, per frame and channel."""
+        assert cat.dtype == "f32" and cat.rows == frames * h * w and 0 < c_h <= cat.cols and c_h % 2 == 0
+        op = Op(L.OP_FREEU, name)
+        op.i[0:7] = [cat.rows, cat.cols, cat.ld, c_h, frames, h, w]
+        op.f[0:2] = [b, s]
+        op.p[0] = cat.ref
+        op.out = cat
+        return self._emit(op)
+
     def ddim_step(self, name: str, *, C: int, inner: int, guided: int, eps_dtype: str, x_dtype: str, mode: int = 0,
                   samples: int = 1) -> Op:
         """C channels per video, `samples` videos per batch (x [samples, C, inner], eps [2, samples, C, inner])."""

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import itertools
 import os
 import struct
@@ -36,6 +37,7 @@ import torch
 
 from . import _lib as L
 from .program import BoundProgram, Program
+from .unet import freeu_scope, freeu_values
 
 try:  # inside the webui these exist; outside we provide inert stand-ins
     from modules.shared import state  # type: ignore
@@ -110,6 +112,26 @@ def _eval_ragged(model, x, tt, c, uc, guided: bool, token, cfg_parallel=None):
         model.context_token = token
         return model(x, tt, list(c))
     return model.forward_cfg_pair(x, tt, (list(c), list(uc)), context_token=token, single_t=True)
+
+
+def _with_freeu(fn):
+    """`freeu=` of a sampler call (this build's addition): a dict {"b1", "b2", "s1", "s2"} — FreeU (`UNetSD.enable_freeu`; the authors'
+    ModelScope values: b1 1.2, b2 1.4, s1 0.9, s2 0.2) for the UNet evaluations of THIS call; the model's own state is restored
+    afterwards, also when the call raises.  Without the keyword the method is called as it was.  The values are part of the UNet's
+    program key: a sweep over values keeps at most `max_programs` programs compiled.  ValueError: a partial or unknown dict, a value
+    that is not a finite number.  NotImplementedError: a clip whose frames are split over ranks (the T-shard layout), the CFG-pair
+    multi-GPU layout, a model without FreeU (the VideoCrafter UNet)."""
+    @functools.wraps(fn)
+    def call(self, *args, freeu=None, **kwargs):
+        if freeu is None:
+            return fn(self, *args, **kwargs)
+        freeu_values(freeu)                      # (refused before the layout is looked at)
+        pair = getattr(self, "cfg_parallel", None)
+        if pair is not None and getattr(pair, "size", 1) == 2 and getattr(self.model, "t_shard", None) is None:
+            raise NotImplementedError("freeu= is not implemented for the CFG-pair multi-GPU layout (cond and uncond on two devices)")
+        with freeu_scope(self.model, freeu):
+            return fn(self, *args, **kwargs)
+    return call
 
 
 def _ctx_ident(nonce, c, uc):
@@ -231,6 +253,7 @@ class GaussianDiffusion(object):
             self._step_plans[key] = plan
         return plan
 
+    @_with_freeu
     @torch.no_grad()
     def sample(self, x_T=None, S=5, shape=None, conditioning=None, unconditional_conditioning=None,
                model_kwargs={}, clamp=None, percentile=None, condition_fn=None,
@@ -1010,6 +1033,7 @@ class DDIMSampler(object):
                     callback(i)
         return img
 
+    @_with_freeu
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, eta=0.0, mask=None, x0=None, x_T=None,
                unconditional_guidance_scale=1.0, unconditional_conditioning=None, temperature=1.0, ucg_schedule=None, context_windows=None,
@@ -1034,6 +1058,7 @@ class DDIMSampler(object):
         prev = torch.cat([torch.ones(1, dtype=ac.dtype), ac[:-1]]) if prev is None else prev.detach().cpu()
         return ac.to(torch.float32)[:num_steps], prev.to(torch.float32)[:num_steps]
 
+    @_with_freeu
     @torch.no_grad()
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
                unconditional_conditioning=None, callback=None, *, model_timesteps="index", context_windows=None):
@@ -1106,6 +1131,7 @@ class DDIMSampler(object):
         out = torch.empty_like(x0)
         return _lincomb(out, [(float(a.sqrt()), x0), (float(self.ddim_sqrt_one_minus_alphas[idx].to(torch.float32)), noise)])
 
+    @_with_freeu
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                use_original_steps=False, callback=None, *args, context_windows=None, **kwargs):
@@ -1280,6 +1306,7 @@ class UniPCSampler(object):
             x_t = x_c
         return x_t, model_t
 
+    @_with_freeu
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, strength=None, eta=0.0, mask=None,
                x_T=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None, variant=None, skip_type=None,
@@ -1443,7 +1470,7 @@ class Txt2VideoSampler(object):
         return encoded_latent, denoise_steps
 
     def invert_latent(self, latent, noise, strength, steps, conditioning, unconditional_conditioning, guidance_scale=1.0,
-                      model_timesteps="index", context_windows=None):
+                      model_timesteps="index", context_windows=None, freeu=None):
         """vid2vid through DDIM inversion: `encode_latent`'s schedule and step count, the latent from `DDIMSampler.encode` instead of
         `stochastic_encode` (`noise` only tells how many videos the batch holds), and `sample` becomes `decode` as there."""
         if noise is not None and latent.shape[0] == 1 and noise.shape[0] > 1:
@@ -1452,7 +1479,8 @@ class Txt2VideoSampler(object):
         self.sampler.make_schedule(steps)
         encoded_latent, _ = self.sampler.encode(latent, conditioning, denoise_steps, unconditional_guidance_scale=guidance_scale,
                                                 unconditional_conditioning=unconditional_conditioning, model_timesteps=model_timesteps,
-                                                **({"context_windows": context_windows} if context_windows is not None else {}))
+                                                **({"context_windows": context_windows} if context_windows is not None else {}),
+                                                **({"freeu": freeu} if freeu is not None else {}))
         self.sampler.sample = self.sampler.decode
         return encoded_latent, denoise_steps
 
@@ -1472,7 +1500,7 @@ class Txt2VideoSampler(object):
     def sample_loop(self, steps, strength, conditioning, unconditional_conditioning, batch_size, latents=None,
                     shape=None, noise=None, is_vid2vid=False, guidance_scale=1, eta=0, mask=None,
                     sampler_name="DDIM", *, clamp=None, percentile=None, unipc=None, inversion=None, inpaint=None,
-                    context_windows=None):
+                    context_windows=None, freeu=None):
         """samplers_common.py:165-207.  `clamp` / `percentile` (keyword, this build's addition to the signature): the x0 restriction of
         GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set, so every other call is what it was.
         `unipc` (keyword, likewise): a dict of UniPC's solver options (UNIPC_OPTIONS, see UniPCSampler) — UniPC only, forwarded only
@@ -1486,8 +1514,12 @@ class Txt2VideoSampler(object):
         GaussianDiffusion.sample — DDIM_Gaussian only; forwarded only when set.
         `context_windows` (keyword, likewise): a `ContextWindows` or its dict / tuple form, for every sampler — a clip longer than its
         `length` is denoised through overlapping windows (GaussianDiffusion.sample); the inversion of `inversion=` is windowed too.
-        Forwarded only when set."""
+        Forwarded only when set.
+        `freeu` (keyword, likewise): {"b1": 1.2, "b2": 1.4, "s1": 0.9, "s2": 0.2} — FreeU for the UNet evaluations of this call, every
+        sampler, the inversion of `inversion=` included (`_with_freeu`); the model is restored afterwards.  Forwarded only when set."""
         restrict = {k: v for k, v in (("clamp", clamp), ("percentile", percentile), ("inpaint", inpaint)) if v is not None}
+        if freeu is not None:
+            freeu_values(freeu)
         active = next((s.name for s in available_samplers if isinstance(self.sampler, s.Sampler)), type(self.sampler).__name__)
         if inpaint is not None and not isinstance(self.sampler, GaussianDiffusion):
             raise ValueError(f"inpaint: the keyframe blend exists for the DDIM_Gaussian sampler only, not for {active!r}")
@@ -1502,6 +1534,8 @@ class Txt2VideoSampler(object):
             restrict.update(unipc)
         if context_windows is not None:
             restrict["context_windows"] = ContextWindows.coerce(context_windows)
+        if freeu is not None:
+            restrict["freeu"] = freeu
         invert = None
         if inversion is not None and inversion is not False:
             if not isinstance(self.sampler, DDIMSampler):
@@ -1518,7 +1552,8 @@ class Txt2VideoSampler(object):
         denoise_steps = None
         if invert is not None:
             latents, denoise_steps = self.invert_latent(latents, noise, strength, steps, conditioning, unconditional_conditioning, **invert,
-                                                        **({"context_windows": restrict["context_windows"]} if context_windows is not None else {}))
+                                                        **({"context_windows": restrict["context_windows"]} if context_windows is not None else {}),
+                                                        **({"freeu": freeu} if freeu is not None else {}))
         elif latents is not None and is_vid2vid:
             latents, denoise_steps = self.encode_latent(latents, noise, strength, steps)
         sampler_callback = SamplerStepCallback(sampler_name, steps, progress=self.progress)

@@ -158,6 +158,47 @@ def _conv_holder(attr, cin, cout, **kw):
     return m
 
 
+def freeu_values(freeu) -> Tuple[float, float, float, float]:
+    """A `freeu=` argument — a dict with exactly the keys b1, b2, s1, s2, finite numbers — as the tuple (b1, b2, s1, s2); anything
+    else is a ValueError."""
+    keys = ("b1", "b2", "s1", "s2")
+    if not isinstance(freeu, dict) or set(freeu) != set(keys):
+        raise ValueError(f"freeu takes a dict with exactly the keys {list(keys)}, got {sorted(freeu) if isinstance(freeu, dict) else type(freeu).__name__}")
+    vals = []
+    for k in keys:
+        v = freeu[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"freeu['{k}'] must be a finite number, got {v!r}")
+        vals.append(float(v))
+    return tuple(vals)
+
+
+class freeu_scope:
+    """`with freeu_scope(model, freeu):` — FreeU with these values for the calls inside, the model's earlier state restored afterwards.
+    freeu = None leaves the model alone.  A model without `enable_freeu`, or one whose layout has no FreeU, refuses by raising."""
+
+    def __init__(self, model, freeu):
+        self.model, self.freeu = model, freeu
+
+    def __enter__(self):
+        if self.freeu is None:
+            return self
+        vals = freeu_values(self.freeu)
+        m = self.model
+        if not hasattr(m, "enable_freeu"):
+            raise NotImplementedError(f"freeu= needs a model with enable_freeu (UNetSD), got {type(m).__name__}")
+        if getattr(m, "t_shard", None) is not None:
+            raise NotImplementedError("freeu= is not implemented for the T-shard layout (a clip's frames split over ranks)")
+        self.held = getattr(m, "_freeu", None)
+        m.enable_freeu(s1=vals[2], s2=vals[3], b1=vals[0], b2=vals[1])
+        return self
+
+    def __exit__(self, *exc):
+        if self.freeu is not None:
+            self.model._freeu = self.held
+        return False
+
+
 class UNetSD(nn.Module, ProgramHost):
     """See module docstring.  Extra keyword (not in the reference): `init_weights=False` skips
     the (slow, 1.4 G parameter) default initialisation when a state dict is loaded right after."""
@@ -281,9 +322,30 @@ class UNetSD(nn.Module, ProgramHost):
         # is 26.09 vs 26.03 ms and 26.51 vs 26.37 ms on two boxes (the epilogue's K / V^T fragment loads from L2 are latency-bound: the fused
         # launch takes 53 us where projection + attention take 28 + 32) -> opt-in (T2V_XATTN=1)
         self.fused_cross_attention = L.knob("T2V_XATTN", "0") != "0"
+        self._freeu = None            # (b1, b2, s1, s2) while FreeU is on (`enable_freeu`); part of the program cache key
         self.auto_refresh = True      # re-check parameter versions on every forward (~1 ms); the sampler
                                       # turns this off inside its loop after one explicit refresh
         self.device = torch.device("cpu")   # SamplerBase.register_buffers_to_model overwrites it (samplers_common.py:82)
+
+    # ---- FreeU ------------------------------------------------------------------------------
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net"), diffusers' name and argument order: at every decoder skip
+        concatenation whose stream has 4 dim channels the first half of the stream is multiplied by b1 and the low frequencies of the
+        skip by s1; at 2 dim channels by b2 and s2; other widths are untouched (T2V_OP_FREEU, one in-place launch per concatenation).
+        The authors' ModelScope values: b1 1.2, b2 1.4, s1 0.9, s2 0.2.  Stays on until `disable_freeu`.
+        The four floats are part of the program key: every distinct set of values is a program of its own (with its own arena), and
+        `max_programs` bounds how many a sweep over values keeps compiled — the oldest is evicted and lowered again when it returns."""
+        if type(self) is not UNetSD:
+            raise NotImplementedError(f"FreeU is implemented for the ModelScope UNet (UNetSD) only, not for the VideoCrafter path ({type(self).__name__})")
+        self._freeu = freeu_values(dict(s1=s1, s2=s2, b1=b1, b2=b2))
+
+    def disable_freeu(self):
+        self._freeu = None
+
+    @property
+    def freeu(self) -> Optional[Dict[str, float]]:
+        """The FreeU values in force, {"b1", "b2", "s1", "s2"}, or None (read-only: `enable_freeu` / `disable_freeu`)."""
+        return dict(zip(("b1", "b2", "s1", "s2"), self._freeu)) if getattr(self, "_freeu", None) is not None else None
 
     # ---- parameter tree -------------------------------------------------------------------
     def _make(self, kind, cin, cout, dropout, decoder, stem=False):
@@ -519,7 +581,8 @@ class UNetSD(nn.Module, ProgramHost):
             ((("xattn",),) if getattr(self, "fused_cross_attention", False) else ()) + \
             ((("pattn",),) if (getattr(self, "precise_attn_out", False) and type(self) is not UNetSD) else ()) + ((("presample",),) if getattr(self, "precise_resample", False) else ()) + \
             ((("precise", str(self.precise_operands)),) if getattr(self, "precise_operands", False) else ()) + \
-            ((("tattn", str(self.fused_temporal_attention)),) if getattr(self, "fused_temporal_attention", False) else ())
+            ((("tattn", str(self.fused_temporal_attention)),) if getattr(self, "fused_temporal_attention", False) else ()) + \
+            ((("freeu",) + tuple(self._freeu),) if getattr(self, "_freeu", None) is not None else ())
 
     def forward_cfg_pair(self, x, t, ctx_pair, context_token=None, single_t=None):
         """One guided step's two evaluations (gaussian_sampler.py:161-162) as ONE forward: x [V,4,F,h,w] is read twice by
@@ -612,6 +675,9 @@ class _Lowering(_UNetLowering):
     def __init__(self, net: UNetSD, *args, **kwargs):
         super().__init__(net, *args, **kwargs)
         self.fused_tattn = bool(getattr(net, "fused_temporal_attention", False))
+        self.freeu = getattr(net, "_freeu", None)
+        if self.freeu is not None and self.shard is not None:
+            raise NotImplementedError("FreeU is not implemented for the T-shard layout (a clip's frames split over ranks)")
         # fused to_q + text cross-attention (T2V_EPI_XATTN, round 5): V^T of every site, [B][sum of inner][keys padded], step-invariant
         self.vt_all: Optional[Buf] = None
         self.vt_slices: Dict[str, int] = {}

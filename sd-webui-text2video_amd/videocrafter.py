@@ -1053,6 +1053,8 @@ class DDIMSampler(object):
         if quantize_x0 or noise_dropout or score_corrector is not None or postprocess_fn is not None \
                 or cond_fn is not None or kwargs.get("uc_type") is not None:
             raise NotImplementedError("quantisation / noise dropout / score correctors are not on the hot path")
+        if kwargs.get("freeu") is not None:
+            raise NotImplementedError("freeu: FreeU is implemented for the ModelScope UNet only, not for the VideoCrafter path (UNetModel)")
         if kwargs.get("context_windows") is not None:
             raise L.T2VError("context_windows: context windows exist for the ModelScope samplers only; the VideoCrafter loop evaluates "
                              "through LatentDiffusion.apply_model and is out of scope")
@@ -1403,6 +1405,8 @@ def process_videocrafter(args_dict: dict):
     model = a.model
     if getattr(a, "sample_type", "ddim") != "ddim":
         raise NotImplementedError("only the DDIM path of the webui (process_videocrafter.py:57-79) is built")
+    if getattr(a, "freeu", None) is not None:
+        raise NotImplementedError("freeu: FreeU is implemented for the ModelScope UNet only, not for the VideoCrafter path (process_videocrafter)")
     sampler = getattr(a, "sampler", None)
     if sampler is None:
         sampler = DDIMSampler(model)
