@@ -231,6 +231,8 @@ enum t2v_gather {
  *      any of its pointer slots, a window that starts below the tensor included — into bytes of the hidden tensor that no record has rewritten since.  THE HIDDEN BUFFER (record k's p[5]) IS NOT WRITTEN BY A FUSED PAIR.
  *      t2v_plan_run_timed reports the launch on record k and exactly 0.0f on record k + 1.  t2v_run_ops never fuses.
  *      i[31] = 1 on the GEGLU record (a word no validation reads; test hook): the M cut-off is waived.
+ *   3x3 convolutions, stride 1, width <= 32 (env T2V_CONV_HALO, read once, default on; 0 = off): the A operand is staged once per 64-channel
+ *      chunk for all nine taps instead of tap by tap; bit-identical.  i[31] = 1 on a CONV3X3 record (test hook): tap by tap for that record.
  * GROUPNORM: i: 0 n_inst, 1 rows_per_inst, 2 C, 3 ld_in, 4 groups, 5 in dtype, 6 silu,
  *      7 ld_out, 8 phase (0 whole op | 1 statistics only | 2 fold gathered parts + normalise | 3 statistics from the producing GEMM:
  *         p[6] = its T2V_EPI_STATS strips fp32 [n_inst * rows / 32][2][i[17]], rows % 32 == 0 — a fold of the strips + ONE apply pass),

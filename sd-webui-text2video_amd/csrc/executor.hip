@@ -64,6 +64,7 @@ struct GemmView {
   int xa_ldk, xa_lc, xa_lcp, xa_k_sample, xa_vt_sample;            // i[24..28] under XATTN
   float ln_eps, attn_scale, gn_eps;
   bool waive_min_m;             // i[31] = 1, a word no check reads: the tests' way to the fused feed-forward pair at a few hundred rows
+  bool conv_legacy;             // the same word on a 3x3 convolution: per-tap A staging where the halo staging would apply (gemm2.hip)
   // the pointer slots by role; a role that the form does not have is 0
   uint64_t A, W, bias, rowbias, ln_gb, res, out, ws;               // p[0..6]; p[3] is gamma | beta under the LayerNorm forms
   uint64_t tickets, ln_out, stats;                                 // p[7]
@@ -93,6 +94,7 @@ GemmView gemm_decode(const t2v_op& op) {
   else { v.gn_rows = I[24]; v.ld_gn = I[25]; v.gn_silu = I[26]; v.gn_lo = I[27]; v.gn_groups = I[28]; v.gn_skip_out = I[29]; v.gn_gb = P[8]; v.gn_out = P[9]; }
   v.ln_eps = op.f[0]; v.attn_scale = op.f[1]; v.gn_eps = op.f[2];
   v.waive_min_m = I[31] == 1;
+  v.conv_legacy = g == T2V_GATHER_CONV3X3 && I[31] == 1;
   const bool ln = plain && epi != T2V_EPI_TATTN && (I[8] == 1 || I[8] == 2);
   v.form = epi == T2V_EPI_TATTN ? GEMM_TATTN : epi == T2V_EPI_XATTN ? GEMM_XATTN : epi == T2V_EPI_GN ? (v.split > 1 ? GEMM_GN_SPLITK : GEMM_GN_TILE)
          : epi == T2V_EPI_GEGLU ? GEMM_GEGLU : epi == T2V_EPI_STATS ? GEMM_STATS : !ln ? GEMM_PLAIN : I[8] == 1 ? GEMM_LN_ROW : GEMM_LN_CROSS;
@@ -408,7 +410,7 @@ GemmParams gemm_params(const GemmView& v) {
   p.Hin = v.Hin; p.Win = v.Win; p.Cin = v.Cin; p.stride = v.stride; p.up = v.up; p.Hout = v.Hout; p.Wout = v.Wout; p.F = v.F; p.HW = v.HW;
   p.rows_per_batch = v.rows_per_batch;
   p.epi = v.form == GEMM_GEGLU || v.form == GEMM_TATTN ? v.epi : T2V_EPI_NONE;      // statistics, GroupNorm, cross-attention: the plain epilogue + their pointers
-  p.out_f32 = v.out_dtype == T2V_F32; p.act = v.act; p.splitk = v.split; p.bias_m = v.bias_m; p.halo = v.halo;
+  p.out_f32 = v.out_dtype == T2V_F32; p.act = v.act; p.splitk = v.split; p.bias_m = v.bias_m; p.halo = v.halo; p.conv_legacy = v.conv_legacy;
   auto ptr = [](auto& dst, uint64_t a) { dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(a); };
   ptr(p.A, v.A); ptr(p.W, v.W); ptr(p.bias, v.bias); ptr(p.rowbias, v.rowbias); ptr(p.res, v.res); ptr(p.out, v.out); ptr(p.ws, v.ws); ptr(p.stats, v.stats);
   if (v.split > 1) ptr(p.tickets, v.tickets);

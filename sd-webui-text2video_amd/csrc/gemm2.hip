@@ -19,6 +19,10 @@
 // LDS image: row r, 16-byte chunk c at r*64 + ((c ^ ((r>>2)&3))<<4): conflict-free for the
 // fragment reads; the XOR is applied to the per-lane DMA *source* (the destination is
 // lane-linear) and again on the read.
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
+
 #include "t2v_kernels.h"
 
 namespace {
@@ -491,11 +495,258 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_kernel(const GemmPar
   t2v_store_splitk_slab<TM, TN>(p, acc, lane, m0 + wm * TM * 32, n0 + wn * TN * 32, blockIdx.y);
 }
 
-template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int XE = T2V_XE_NONE, bool TAT = false>
+// ---- 3x3 convolution, "halo" A staging --------------------------------------------------------------------------------------------------
+// K is ordered (64-channel chunk, tap, channel): the nine k-tiles of one chunk read the SAME activation rows shifted by at most
+// +-(Win + 1) rows, and gemm2_kernel stages each of the nine with its own DMA pieces (padding taps from the zero page).  Here the
+// distinct rows of a chunk — the tile's BM rows and a fixed pad of 40 >= Win + 1 rows on either side — are staged ONCE per chunk:
+//   LDS    two halo buffers (double-buffered by chunk) of BM + 80 rows x 128 B: LDS row h = flattened token row m0 - 40 + h, channels
+//          [64 c, 64 c + 64), swizzled by h as gemm2_kernel's rows are by r; rows outside the input repeat its first / last row.  The weight
+//          ring keeps its STAGES slots of BN x 128 B.  Behind them the 1-KiB dummy piece and one 128-byte row of zeros.
+//   reads  tap (ky, kx) of tile row r reads LDS row r + 40 + (ky - 1) Win + (kx - 1).  Padding: a lane keeps the 9-bit tap mask of each
+//          32-row block it reads (the predicate of gemm2_kernel's xmask, for the fragment row) and reads the row of zeros where the bit is
+//          clear — rows of a neighbouring image (or garbage past the input) are only ever reached by masked taps.
+//   order  the k order, and so every accumulator and every epilogue, is gemm2_kernel's: the results are bit-identical.
+// Schedule: the nine taps of a chunk are unrolled; at tap T a wave issues the WPW weight pieces of k-tile t + STAGES - 1 (as gemm2_kernel)
+// and halo_geom::count(T) pieces of the NEXT chunk's halo, which are spread over the first 11 - STAGES taps: loads retire in order, so the
+// counted wait of tap 0 of chunk c + 1 (everything but the pieces of the last STAGES - 2 iterations has landed) covers the whole halo of
+// chunk c + 1, the barrier behind it covers every wave's, and the buffer is re-staged only behind the barrier of tap 0 of chunk c + 2,
+// which every wave reaches after its last read of chunk c + 1.  Every wave issues the same number of pieces at a given tap (a piece
+// that does not exist goes from the zero page to the dummy KiB), so each s_waitcnt keeps an immediate.
+template <int NW, int BM, int BN, int STAGES>
+struct halo_geom {
+  static constexpr int PAD = 40;
+  static constexpr int HROWS = BM + 2 * PAD, HSLABS = HROWS / 8, HPW = (HSLABS + NW - 1) / NW, HBYTES = HROWS * 128;
+  static constexpr int WSLABS = BN / 8, WPW = (WSLABS + NW - 1) / NW, WSLOT = BN * 128;
+  static constexpr int W_OFF = 2 * HBYTES, DUMMY_OFF = W_OFF + STAGES * WSLOT, ZERO_OFF = DUMMY_OFF + 1024, LDS = ZERO_OFF + 128;
+  static constexpr int HTAPS = 11 - STAGES;                    // taps of chunk c at which pieces of chunk c + 1's halo go out
+  static constexpr int tap_of(int i) { return (i * HTAPS) / HPW; }
+  static constexpr int count(int tap) { int n = 0; for (int i = 0; i < HPW; ++i) n += tap_of(i) == tap; return n; }
+  static constexpr int first(int tap) { int n = 0; for (int i = 0; i < HPW; ++i) n += tap_of(i) < tap; return n; }
+  // pieces a wave may have outstanding at the wait of `tap`: those of the previous STAGES - 2 iterations
+  static constexpr int wait_at(int tap) { int n = 0; for (int d = 1; d <= STAGES - 2; ++d) n += WPW + count((tap + 9 - d) % 9); return n; }
+  static_assert(STAGES >= 2 && STAGES <= 4 && HROWS % 8 == 0 && tap_of(HPW - 1) < HTAPS, "halo schedule");
+  static_assert(HPW + (STAGES - 1) * WPW + WPW + HPW < 64, "vmcnt is a 6-bit counter");
+  static_assert(LDS <= 160 * 1024, "LDS");
+};
+
+template <int WM, int WN, int TM, int TN, int STAGES, int MINW, int XE = T2V_XE_NONE>
+__global__ __launch_bounds__(WM * WN * 64, MINW) void gemm2_halo_kernel(const GemmParams p) {
+  constexpr int NW = WM * WN;
+  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  using HG = halo_geom<NW, BM, BN, STAGES>;
+  constexpr int HPW = HG::HPW, WPW = HG::WPW;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / WN, wn = wave % WN;
+
+  const int tiles_n = (p.N + BN - 1) / BN;
+  const int tiles_m = (p.M - p.m_begin + BM - 1) / BM;
+  int tile_m, tile_n;
+  t2v_tile_of_block(blockIdx.x, tiles_m, tiles_n, p.panel, tile_m, tile_n);
+  const int m0 = p.m_begin + tile_m * BM, n0 = tile_n * BN;
+
+  // (the launcher has checked: K = 9 Cin, Cin % 64 == 0, and a split starts on a chunk boundary — nkt is a multiple of 9)
+  const int KT = p.K / 64;
+  const int kt_begin = blockIdx.y * p.kt_per_split;
+  const int nkt = min(KT, kt_begin + p.kt_per_split) - kt_begin;
+  const int nch = nkt / 9;
+
+  const unsigned char* zero = g2_zero_page;
+  if (tid < 32) reinterpret_cast<int*>(smem + HG::ZERO_OFF)[tid] = 0;      // (visible behind the first barrier of the main loop)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+  // ---- per-lane DMA state
+  const int lrow = lane >> 3, pchunk = lane & 7;
+  auto swz = [](int r) { return (r >> 1) & 7; };
+  const int hw = p.Hin * p.Win;
+  const long a_rows = (long)((p.M + hw - 1) / hw) * hw;        // whole images: the rows a live tap of a row < M can reach
+  // halo pieces: a 32-bit lane offset per piece from the wave-uniform base of the chunk (the DMA address stays scalar base + lane
+  // offset).  Rows outside the input — and the rows of a piece that does not exist — read the nearest input row instead: finite or not,
+  // only masked taps ever reach them.
+  unsigned hoff[HPW];
+#pragma unroll
+  for (int i = 0; i < HPW; ++i) {
+    const int h = (wave + i * NW) * 8 + lrow;                  // piece wave + i NW = rows h .. of the halo buffer, a lane's row
+    const long g = min(max((long)m0 - HG::PAD + h, 0L), a_rows - 1);
+    hoff[i] = (unsigned)(g * p.lda * 2) + (unsigned)((pchunk ^ swz(h)) * 16);
+  }
+  // wave-uniform base of the chunk whose halo is staged next (past the split's end: the last chunk again, into a buffer nobody reads)
+  const unsigned char* hnext = reinterpret_cast<const unsigned char*>(p.A) + (long)(kt_begin / 9) * 128;
+  // weight pieces: one running pointer per piece, advanced by one k-tile (128 bytes) where its bit of wok is set (else: the zero page)
+  const unsigned char* wptr[WPW];
+  unsigned wok = 0;
+#pragma unroll
+  for (int j = 0; j < WPW; ++j) {
+    const int sl = wave + j * NW, r = sl * 8 + lrow;
+    const int n = n0 + r;
+    const bool ok = sl < HG::WSLABS && n < p.N;
+    wptr[j] = ok ? reinterpret_cast<const unsigned char*>(p.W + (size_t)n * p.ldw + kt_begin * 64 + (pchunk ^ swz(r)) * 8) : zero;
+    wok |= (ok ? 1u : 0u) << j;
+  }
+  // piece i of the next chunk's halo into the buffer at byte offset buf; piece j of a weight k-tile into ring slot fs.  `live`: the k-tile
+  // exists (past the end the pieces read the zero page: the outstanding-load count stays what the waits assume)
+  auto stage_h = [&](int buf, int i) {
+    const int sl = wave + i * NW;
+    unsigned char* dst = ((i + 1) * NW <= HG::HSLABS || sl < HG::HSLABS) ? smem + buf + sl * 1024 : smem + HG::DUMMY_OFF;
+    const unsigned char* base = hnext;
+    asm volatile("" : "+s"(base));
+    t2v_glds16(base + (size_t)hoff[i], dst);
+  };
+  auto stage_w = [&](int fs, int j, bool live) {
+    const int sl = wave + j * NW;
+    unsigned char* dst = ((j + 1) * NW <= HG::WSLABS || sl < HG::WSLABS) ? smem + HG::W_OFF + fs * HG::WSLOT + sl * 1024 : smem + HG::DUMMY_OFF;
+    const void* src = live ? wptr[j] : zero;
+    wptr[j] += ((wok >> j) & 1u) << 7;
+    t2v_glds16(src, dst);
+  };
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int a = 0; a < TM; ++a)
+#pragma unroll
+    for (int b = 0; b < TN; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+  // prologue: chunk 0's halo, then STAGES - 1 weight k-tiles (nkt >= 9: all exist) — the order the waits of the first iterations count on
+#pragma unroll
+  for (int i = 0; i < HPW; ++i) stage_h(0, i);
+  if (nch > 1) hnext += 128;
+#pragma unroll
+  for (int g = 0; g < STAGES - 1; ++g)
+#pragma unroll
+    for (int j = 0; j < WPW; ++j) stage_w(g, j, true);
+
+  // fragment addressing: lane reads tile row (block row0 + lane & 31), logical chunk kk * 2 + (lane >> 5)
+  const int frow = lane & 31, fhalf = lane >> 5;
+  int hrow[TM];                    // halo-buffer row of the centre tap
+  unsigned fmask[TM];              // bit t set <=> tap t of this row is inside its image (and the row inside M)
+#pragma unroll
+  for (int a = 0; a < TM; ++a) {
+    const int r = (wm * TM + a) * 32 + frow;
+    const int m = m0 + r;
+    hrow[a] = r + HG::PAD;
+    const int img = m / hw, rem = m - img * hw;
+    const int yo = rem / p.Win, xo = rem - yo * p.Win;
+    fmask[a] = 0;
+    for (int t = 0; t < 9; ++t) {
+      const int yv = yo + t / 3 - 1, xv = xo + t % 3 - 1;
+      if (m < p.M && yv >= 0 && yv < p.Hin && xv >= 0 && xv < p.Win) fmask[a] |= 1u << t;
+    }
+  }
+  // (every 32-row block of weight rows starts on a multiple of 32: the swizzle term depends on the lane alone)
+  const int wb0 = (wn * TN * 32 + frow) * 128, wsw = swz(frow) << 4;
+
+  int slot = 0;
+  auto tap_body = [&](auto tap_c, int c, int hcur) {
+    constexpr int tap = decltype(tap_c)::value;
+    wait_vmcnt<HG::wait_at(tap)>();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    int fs = slot + STAGES - 1;
+    if (fs >= STAGES) fs -= STAGES;
+    const bool wlive = c * 9 + tap + STAGES - 1 < nkt;
+    // (opaque to the optimiser: the nine taps' row addresses and mask bits are formed here, tap by tap — hoisted out of the chunk loop
+    //  they would be 18 registers per 32-row block, which no tile has)
+    int shift = (tap / 3 - 1) * p.Win + (tap % 3 - 1);
+    asm volatile("" : "+s"(shift));
+    int xb[TM], xs[TM];
+#pragma unroll
+    for (int a = 0; a < TM; ++a) {
+      const int h = hrow[a] + shift;
+      unsigned fm = fmask[a];
+      asm volatile("" : "+v"(fm));
+      const bool on = (fm >> tap) & 1u;
+      xb[a] = on ? hcur + h * 128 : HG::ZERO_OFF;
+      xs[a] = on ? swz(h) << 4 : 0;
+    }
+    const unsigned char* st = smem + HG::W_OFF + slot * HG::WSLOT + wb0;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int lc4 = (kk * 2 + fhalf) << 4;
+      f16x8 xf[TM], wf[TN];
+#pragma unroll
+      for (int a = 0; a < TM; ++a) xf[a] = *reinterpret_cast<const f16x8*>(smem + xb[a] + (lc4 ^ xs[a]));
+#pragma unroll
+      for (int b = 0; b < TN; ++b) wf[b] = *reinterpret_cast<const f16x8*>(st + b * 4096 + (lc4 ^ wsw));
+      // this k-step's share of the iteration's pieces (next chunk's halo first, then the weights), placed as gemm2_kernel places its own:
+      // with a 2-deep ring they must land before the next barrier and go out in the first half of the k-tile
+      constexpr int NH = HG::count(tap), H0 = HG::first(tap), NP = NH + WPW;
+      constexpr int SPREAD = STAGES == 2 ? 2 : 4;
+      if (kk < SPREAD) {
+#pragma unroll
+        for (int q = (NP * kk) / SPREAD; q < (NP * (kk + 1)) / SPREAD; ++q) {
+          if (q < NH) stage_h(HG::HBYTES - hcur, H0 + q);
+          else stage_w(fs, q - NH, wlive);
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[b], xf[a], acc[a][b], 0, 0, 0);
+    }
+    slot = slot + 1 == STAGES ? 0 : slot + 1;
+  };
+  int hcur = 0;                    // byte offset of the halo buffer the current chunk reads
+  for (int c = 0; c < nch; ++c) {
+    tap_body(std::integral_constant<int, 0>{}, c, hcur);
+    tap_body(std::integral_constant<int, 1>{}, c, hcur);
+    tap_body(std::integral_constant<int, 2>{}, c, hcur);
+    tap_body(std::integral_constant<int, 3>{}, c, hcur);
+    tap_body(std::integral_constant<int, 4>{}, c, hcur);
+    tap_body(std::integral_constant<int, 5>{}, c, hcur);
+    tap_body(std::integral_constant<int, 6>{}, c, hcur);
+    tap_body(std::integral_constant<int, 7>{}, c, hcur);
+    tap_body(std::integral_constant<int, 8>{}, c, hcur);
+    hcur = HG::HBYTES - hcur;
+    if (c + 2 < nch) hnext += 128;
+  }
+  wait_vmcnt<0>();   // drain the zero-page loads of the dead stages before the LDS goes away
+
+  // ---- epilogue: the launcher admits T2V_EPI_NONE only (gemm2_kernel's plain tail, with or without the fused GroupNorm)
+  __builtin_amdgcn_s_barrier();   // every wave is done reading the operand stages
+  if constexpr (XE == T2V_XE_GN) {
+    t2v_epilogue_rows_gn<WM, WN, TM, TN>(p, acc, smem, lane, wave, m0, n0, tile_m, tile_n, tiles_m, tiles_n);
+    return;
+  }
+  t2v_epilogue_rows<TM, TN>(p, acc, reinterpret_cast<float*>(smem) + wave * (32 * T2V_EPI_SP), lane, m0 + wm * TM * 32,
+                            n0 + wn * TN * 32, blockIdx.y, tile_m * tiles_n + tile_n);
+}
+
+// The tiles with a halo instantiation: the table entries the stride-1 ResBlock convolutions of widths <= 32 run on.
+constexpr bool conv_halo_tile(int tile) { return tile == 1 || tile == 3 || tile == 5 || tile == 8 || tile == 9 || tile == 11; }
+// T2V_CONV_HALO (read once): 0 = every 3x3 convolution of the process takes gemm2_kernel's per-tap staging.
+constexpr int CONV_HALO_DEFAULT = 1;
+bool conv_halo_enabled() {
+  static int mode = -1;
+  if (mode < 0) {
+    const char* e = getenv("T2V_CONV_HALO");
+    mode = e != nullptr ? (strcmp(e, "0") != 0 ? 1 : 0) : CONV_HALO_DEFAULT;
+  }
+  return mode == 1;
+}
+// May this launch (split-K already normalised) stage its A operand through the halo buffers?  Anything else: gemm2_kernel, unchanged.
+bool conv_halo_eligible(const GemmParams& p) {
+  return conv_halo_enabled() && !p.conv_legacy && p.gather == T2V_GATHER_CONV3X3 && p.epi == T2V_EPI_NONE && p.stride == 1 && p.up == 0 &&
+         p.halo == 0 && p.a_wrap == 0 && p.Hin == p.Hout && p.Win == p.Wout && p.Win >= 1 && p.Win <= 32 && p.Hin >= 1 && p.Cin % 64 == 0 &&
+         p.K == 9 * p.Cin && (p.splitk == 1 || p.kt_per_split % 9 == 0) &&
+         ((long)p.M + (long)p.Hin * p.Win) * p.lda * 2 < (1L << 31);      // (the halo pieces' lane offsets are 32-bit byte counts)
+}
+
+template <int WM, int WN, int TM, int TN, int BK, int STAGES, int MINW, int GATHER, int XE = T2V_XE_NONE, bool TAT = false, bool HALO = false>
 hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  static_assert(!HALO || (GATHER == T2V_GATHER_CONV3X3 && BK == 64 && !TAT), "the halo staging is a form of the 3x3 gather");
   // TAT: the attention epilogue re-uses the operand ring for q | k (BM x 272 B) and V^T (<= 12 pixels x 64 x 72 B)
-  constexpr int ring = STAGES * (BM + BN) * BK * 2 + 1024;
+  constexpr int ring = [] {
+    if constexpr (HALO) return halo_geom<WM * WN, BM, BN, STAGES>::LDS;
+    else return STAGES * (BM + BN) * BK * 2 + 1024;
+  }();
   constexpr int gn_lds = t2v_gn_epilogue_lds(WM * WN, WM * TM, BN);
   constexpr int lnx_lds = t2v_lnx_epilogue_lds(WM * WN, WN, BM);
   constexpr int xa_lds = t2v_xattn_epilogue_lds(BM, BN);
@@ -503,8 +754,11 @@ hipError_t launch_cfg_gather(const GemmParams& p, hipStream_t s) {
                           : (XE == T2V_XE_GN && gn_lds > ring ? gn_lds : (XE == T2V_XE_LNX && lnx_lds > ring ? lnx_lds : (XE == T2V_XE_XATTN && xa_lds > ring ? xa_lds : ring)));
   const int tiles_n = (p.N + BN - 1) / BN;
   const int tiles = ((p.M - p.m_begin + BM - 1) / BM) * tiles_n;
-  auto k = gemm2_kernel<WM, WN, TM, TN, BK, STAGES, MINW, GATHER, XE, TAT>;
-  static t2v_device_flags attr_set;     // once per (instantiation, device): the call costs microseconds on the host
+  void (*k)(const GemmParams) = [] {
+    if constexpr (HALO) return gemm2_halo_kernel<WM, WN, TM, TN, STAGES, MINW, XE>;
+    else return gemm2_kernel<WM, WN, TM, TN, BK, STAGES, MINW, GATHER, XE, TAT>;
+  }();
+  static t2v_device_flags attr_set;    // once per (instantiation, device): the call costs microseconds on the host
   {
     const hipError_t e = t2v_set_dynamic_lds(reinterpret_cast<const void*>(k), lds, attr_set, s);
     if (e != hipSuccess) return e;
@@ -576,6 +830,15 @@ hipError_t launch_cfg(const GemmParams& pin, hipStream_t s) {
       e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_PLAIN>(p, s);
       break;
     case T2V_GATHER_CONV3X3:
+      if constexpr (conv_halo_tile(TILE)) {
+        if (conv_halo_eligible(p)) {
+          if constexpr (T.has(T2V_TILE_GN)) {
+            if (gn_here) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, T2V_XE_GN, false, true>(p, s); break; }
+          }
+          e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, T2V_XE_NONE, false, true>(p, s);
+          break;
+        }
+      }
       if constexpr (T.has(T2V_TILE_GN)) {
         if (gn_here && !p.up) { e = launch_cfg_gather<WM, WN, TM, TN, BK, STAGES, MINW, T2V_GATHER_CONV3X3, T2V_XE_GN>(p, s); break; }
       }

@@ -37,6 +37,7 @@ struct GemmParams {
                                                // ([B][F+2][HW] rows, T-sharded forward); all 3 taps are in range.
                                                // conv3x3: 1 = asymmetric (0,1,0,1) zero padding (taps at +0..+2)
   int panel;                                   // tile columns per panel of the XCD-aware tile order (set by the launcher)
+  int conv_legacy;                             // conv3x3: 1 = per-tap A staging even where the halo staging applies (gemm2.hip; t2v_op i[31], the tests' way to both)
   // fused LayerNorm second output (192x320 tile, N == 320 == one tile row, no split-K): ln_out = LN(out row) * gamma + beta
   const float* ln_gb;                          // fp32 [2 N]: gamma | beta
   f16* ln_out;
